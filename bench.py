@@ -1,9 +1,18 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X line-feature BA + P6L RANSAC hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline alone: it sets up, runs W warm-up and K timed LM iterations, writes the
+outputs if asked to, and prints the JSON line (`value`, `ms_per_step` = milliseconds per timed LM iteration).
+`--full` adds every other row below (`phase_ms_per_call`, `roofline`, `kernels`, `widened`, `ransac`,
+`cpu_baseline` with its parity check against the oracle); the `--no-*` switches thin out a `--full` run.
+`--dump-outputs DIR` (rank 0) writes what the caller of the timed path receives after its last step, as float64:
+`poses.npy` [C,7], `points.npy` [P,3], `intrinsics.npy` [K,12] (pp_ba_get_parameters) and `summary.npy` (initial
+cost, final cost, iterations, successful steps, unsuccessful steps, termination of the last solve call).  The
+scenes are seeded, so the same arguments give the same inputs in every run.
 
 Metric (BASELINE.json): "BA iterations/sec + RANSAC hypotheses/sec, 500 cams / 200k line obs".
   * `value` / `unit` = bundle-adjustment LM iterations per second, whole job, on BASELINE configs[2]
@@ -14,18 +23,18 @@ Metric (BASELINE.json): "BA iterations/sec + RANSAC hypotheses/sec, 500 cams / 2
     trial point (K3c).  The K steps are run as K/CHUNK_ITERS solves of CHUNK_ITERS (= 10) iterations each from the same
     noise-perturbed start (every one of those iterations is a successful step, verified from the
     summary), because an LM run that is allowed to converge stops doing full iterations.
-  * `ransac` = the second half of the metric on BASELINE configs[3]: P6L (re3q3) hypotheses per second,
+  * `ransac` (--full) = the second half of the metric on BASELINE configs[3]: P6L (re3q3) hypotheses per second,
     one hypothesis = minimal solve + scoring of every returned model over all 50 000 correspondences.
   * N > 1: one process per GPU, each rank owns an independent 500-camera sub-model (N replicas of
     configs[2]; SURVEY.md §8e "independent sub-models": no data-path collective), WEAK scaling;
     value = total iterations of all ranks / max-over-ranks time.  BASELINE configs[4] taken literally
-    (N/2 sub-models over N GPUs - 4 over 8 at N = 8) is the extra row `widened.cfg5_literal`: the same
+    (N/2 sub-models over N GPUs - 4 over 8 at N = 8) is the extra row `widened.cfg5_literal` (--full): the same
     sub-models as whole-GPU replicas on half of the ranks, and point-sharded over groups of two ranks
     with the library's RCCL exchange.
-  * `roofline`: the HBM-bound Jacobian evaluation kernel K1 (north_star's ">= 60% HBM roofline on
+  * `roofline` (--full): the HBM-bound Jacobian evaluation kernel K1 (north_star's ">= 60% HBM roofline on
     Jacobian eval"), algorithmic bytes 220 B/observation, timed with HIP events on the
     library's own stream.  `kernels` adds the fp64-MFMA Cholesky and the RANSAC scoring kernel.
-  * `cpu_baseline`: the oracle (CPU restatement, "port") timed on this box's host cores on a bounded
+  * `cpu_baseline` (--full): the oracle (CPU restatement, "port") timed on the host's cores on a bounded
     sample of the same workloads.
 """
 import argparse
@@ -88,8 +97,9 @@ def dist_env():
     return rank, world, local
 
 
-def run_ba(pb, scene, steps, opts_fn):
-    """Runs exactly `steps` LM iterations (chunks of CHUNK_ITERS from the perturbed start)."""
+def run_ba(pb, scene, steps, opts_fn, summaries=None):
+    """Runs exactly `steps` LM iterations (chunks of CHUNK_ITERS from the perturbed start); the summary of every chunk is
+    appended to `summaries` if given."""
     done = 0
     succ = 0
     while done < steps:
@@ -100,6 +110,8 @@ def run_ba(pb, scene, steps, opts_fn):
             raise RuntimeError("LM chunk did %d of %d iterations (termination %d)" % (s.num_iterations, k, s.termination))
         done += k
         succ += s.num_successful_steps
+        if summaries is not None:
+            summaries.append(s)
     return succ
 
 
@@ -243,9 +255,10 @@ def opts_fn(k):
     return ba_options(max_num_iterations=k, gradient_tolerance=0.0)
 
 
-def timed_ba(be, use_dist, pb, scene, warmup, steps, active=True):
+def timed_ba(be, use_dist, pb, scene, warmup, steps, active=True, summaries=None):
     """W untimed + K timed LM iterations between barriers; returns (max-over-ranks seconds, successful steps).  Ranks with
-    active = False only take part in the barriers and the reduction (they hold no sub-model in this row)."""
+    active = False only take part in the barriers and the reduction (they hold no sub-model in this row).  The summaries of
+    the timed chunks are appended to `summaries` if given."""
     import torch.distributed as dist
 
     def barrier():
@@ -258,7 +271,7 @@ def timed_ba(be, use_dist, pb, scene, warmup, steps, active=True):
         run_ba(pb, scene, max(warmup, 1), opts_fn)
     barrier()
     t0 = time.perf_counter()
-    succ = run_ba(pb, scene, steps, opts_fn) if active else 0
+    succ = run_ba(pb, scene, steps, opts_fn, summaries) if active else 0
     be.sync()
     elapsed = time.perf_counter() - t0
     if use_dist:
@@ -266,6 +279,18 @@ def timed_ba(be, use_dist, pb, scene, warmup, steps, active=True):
         elapsed = max_over_ranks(elapsed if active else 0.0, be.device_type)
     barrier()
     return elapsed, succ
+
+
+def dump_outputs(out_dir, pb, summary):
+    """--dump-outputs: what a caller of the timed path receives after its last step - the parameters the last solve left on the
+    device and that solve's summary (its timings left out: they differ from run to run) - as float64 .npy files."""
+    os.makedirs(out_dir, exist_ok=True)
+    poses, points, intr = pb.get_parameters()
+    arrays = {"poses": poses, "points": points, "intrinsics": intr,
+              "summary": [summary.initial_cost, summary.final_cost, summary.num_iterations, summary.num_successful_steps,
+                          summary.num_unsuccessful_steps, summary.termination]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def concurrent_submodels(be, scene, steps, counts=(1, 2, 4)):
@@ -324,7 +349,13 @@ def main(argv=None, backend=None):
     ap.add_argument("--no-beyond-l3", action="store_true", help="skip the 2M-observation K1 launches (roofline.beyond_l3); use it for the rocprofv3 --stats run whose\n                    k_line_eval average profiles/ compares with roofline.ms_per_launch (the stats file averages over all launches of a kernel name)")
     ap.add_argument("--cfg5-timeout", type=float, default=240.0, help="seconds after which the widened.cfg5_literal row (the first thing that exercises the "
                     "multi-rank RCCL exchange) is abandoned and the line printed without it")
+    ap.add_argument("--full", action="store_true", help="every row beside the headline: phase breakdown, roofline and kernels, widened rows, RANSAC leg, "
+                    "CPU baseline (off: the headline LM iterations alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (rank 0: poses, points, intrinsics, "
+                    "solve summary) as float64 DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     be = backend or GpuBackend()
 
     rank, world, local = dist_env()
@@ -353,14 +384,18 @@ def main(argv=None, backend=None):
     if comm is not None:
         pb.set_communicator(comm)
     M = pb.M
-    elapsed, succ = timed_ba(be, use_dist, pb, scene, args.warmup, args.steps)
-    timings, last_summary = None, None
-    if be.has_gpu_rows:
+    summaries = []
+    elapsed, succ = timed_ba(be, use_dist, pb, scene, args.warmup, args.steps, summaries=summaries)
+    last_summary = summaries[-1]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pb, last_summary)
+    timings = None
+    if be.has_gpu_rows and args.full:
         # phase breakdown: a separate, untimed pass with the per-phase HIP events switched on (each event record costs ~5 us of
         # stream time, so the timed run above leaves them off)
         from privacy_preserving_sfm_amd.device import ba_options
         pb.set_parameters(scene["poses"], scene["points"], None)
-        last_summary = pb.solve(ba_options(max_num_iterations=CHUNK_ITERS, gradient_tolerance=0.0, phase_timings=1))
+        pb.solve(ba_options(max_num_iterations=CHUNK_ITERS, gradient_tolerance=0.0, phase_timings=1))
         timings = pb.timings()
 
     result = None
@@ -372,7 +407,7 @@ def main(argv=None, backend=None):
             workload = "configs[2]: 500 cams / 200k line obs full BA (K1+K2+K3, MFMA Schur solve) on 1xMI355X"
         elif gsize == 1:
             workload = ("%d replicas of configs[2] (500 cams / 200k line obs full BA), one independent sub-model per GPU, no data-path collective: WEAK "
-                        "scaling; configs[4] taken literally (%d sub-models over %d GPUs) is the row widened.cfg5_literal" % (world, max(world // 2, 1), world))
+                        "scaling; configs[4] taken literally (%d sub-models over %d GPUs) is the row widened.cfg5_literal of --full" % (world, max(world // 2, 1), world))
         else:
             workload = ("configs[4] shape: %d sub-models of configs[2]'s size, each point-sharded over %d ranks with the RCCL normal-equation "
                         "all-reduce inside the library" % (submodels, gsize))
@@ -387,10 +422,9 @@ def main(argv=None, backend=None):
                        "submodels": int(submodels), "ranks_per_submodel": int(gsize),
                        "exchange": "none (independent sub-models)" if gsize == 1 else "RCCL all-reduce of U/g_c, packed lower triangle of S, scalars per LM iteration"},
         }
-        if last_summary is not None:
-            result["config"]["linear_solver"] = LINSOLVE_NAMES.get(int(last_summary.linear_solver), str(int(last_summary.linear_solver)))
-            result["config"]["cholesky_fallbacks"] = int(last_summary.cholesky_fallbacks)
-    if rank == 0 and be.has_gpu_rows:
+        result["config"]["linear_solver"] = LINSOLVE_NAMES.get(int(last_summary.linear_solver), str(int(last_summary.linear_solver)))
+        result["config"]["cholesky_fallbacks"] = int(last_summary.cholesky_fallbacks)
+    if rank == 0 and be.has_gpu_rows and args.full:
         from privacy_preserving_sfm_amd.device import dense_cholesky_solve
         result["phase_ms_per_call"] = {k: (v[0] / v[1] if v[1] else 0.0) for k, v in timings.items()}
         # ---- K1 roofline: HIP events on the library's stream around 200 launches ---------------
@@ -433,7 +467,7 @@ def main(argv=None, backend=None):
         except Exception as e:
             result["roofline"]["beyond_l3"] = {"skipped": str(e)}
     # ---- rows widened after the hot path: post-BA filters on the same handle, four-view initialisation ----
-    if rank == 0 and world == 1 and be.has_gpu_rows and not args.no_widened:
+    if rank == 0 and world == 1 and be.has_gpu_rows and args.full and not args.no_widened:
         try:
             f = float(scene["intr"][0, 0])
             cam_size = np.tile(np.array([[int(4 * f), int(4 * f)]], dtype=np.int32), (scene["intr"].shape[0], 1))
@@ -674,7 +708,7 @@ def main(argv=None, backend=None):
             result["widened"] = dict(result.get("widened", {}), error=repr(e))
     # ---- RANSAC leg (every rank runs its share: hypotheses h = rank mod world) -----------------
     rs = None
-    if not args.no_ransac and be.has_gpu_rows:
+    if args.full and not args.no_ransac and be.has_gpu_rows:
         from privacy_preserving_sfm_amd.device import PoseProblem
         rsc = synthetic.make_ransac_scene(RANSAC_N, outlier_ratio=0.5, noise_px=0.5, seed=0xBADC0DE)
         pp = PoseProblem(rsc["lines"], rsc["points"], rsc["aligned"], device=local)
@@ -721,7 +755,7 @@ def main(argv=None, backend=None):
     # ---- BASELINE configs[4] taken literally: world/2 sub-models over `world` GPUs (4 over 8 at N = 8), (a) as whole-GPU replicas on the
     # first world/2 ranks, (b) point-sharded over groups of two ranks with the RCCL exchange inside the library.  Runs after the headline
     # has been measured and under a deadline: it is the first code that needs the multi-rank collectives to work.
-    if use_dist and gsize == 1 and world % 2 == 0 and not args.no_widened:
+    if use_dist and gsize == 1 and world % 2 == 0 and args.full and not args.no_widened:
         row = cfg5_literal(be, args, rank, world, full_scene)
         if rank == 0:
             result.setdefault("widened", {})["cfg5_literal"] = row
@@ -732,7 +766,7 @@ def main(argv=None, backend=None):
     if comm is not None:
         pb.set_communicator(None)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and be.has_gpu_rows:
+        if world == 1 and args.full and not args.no_cpu_baseline and be.has_gpu_rows:
             from privacy_preserving_sfm_amd.device import ba_options
             rsc = synthetic.make_ransac_scene(RANSAC_N, outlier_ratio=0.5, noise_px=0.5, seed=0xBADC0DE)
             base_scene = make_scene(0)

@@ -245,7 +245,7 @@ def _bench_worker(rank, world, port, argv, q):
         device.Communicator = FakeCommunicator
 
         class Summary:
-            pass
+            initial_cost, final_cost, num_unsuccessful_steps = 2.0, 1.0, 0
 
         class StubProblem:
             def __init__(self, scene):
@@ -257,6 +257,9 @@ def _bench_worker(rank, world, port, argv, q):
 
             def set_parameters(self, poses, points, intr):
                 pass
+
+            def get_parameters(self):
+                return self.scene["poses"], self.scene["points"], self.scene["intr"]
 
             def solve(self, o):
                 k = int(o.max_num_iterations)
@@ -326,7 +329,7 @@ def _run_bench(world, argv):
 def test_bench_main_multi_rank_control_flow_under_gloo():
     """`bench.py --gpus 4` as the driver launches it (default: 4 replicas + the widened.cfg5_literal row = 2 sub-models as replicas and
     as 2 x 2 sharded ranks) and `--submodels 2` (the headline itself sharded), executed under gloo with a stand-in problem."""
-    out = _run_bench(4, ["--gpus", "4", "--steps", "4", "--warmup", "1"])
+    out = _run_bench(4, ["--gpus", "4", "--steps", "4", "--warmup", "1", "--full"])
     line, log0 = out[0]
     assert line["n_gpus"] == 4 and line["scaling"] == "weak" and line["config"]["submodels"] == 4 and line["config"]["ranks_per_submodel"] == 1
     assert "4 replicas of configs[2]" in line["config"]["workload"] and "widened.cfg5_literal" in line["config"]["workload"]
@@ -340,8 +343,24 @@ def test_bench_main_multi_rank_control_flow_under_gloo():
     for r in range(4):
         comms = [e for e in out[r][1] if e[0] == "comm"]      # one communicator each for the sharded row, the sharded iterative row and the sharded sequence row
         assert comms == [("comm", 7 + 2 * (r // 2), 2, r % 2)] * 3 and out[r][1].count(("comm_close",)) == 3
-    out = _run_bench(4, ["--gpus", "4", "--steps", "4", "--warmup", "1", "--submodels", "2"])
+    out = _run_bench(4, ["--gpus", "4", "--steps", "4", "--warmup", "1", "--submodels", "2", "--full"])
     line = out[0][0]
     assert line["config"]["submodels"] == 2 and line["config"]["ranks_per_submodel"] == 2 and "RCCL" in line["config"]["exchange"]
     assert "cfg5_literal" not in line.get("widened", {})
     assert abs(line["value"] - 2 * 4 / (line["ms_per_step"] * 4e-3)) <= 1e-6 * line["value"]
+
+
+def test_bench_main_plain_run_times_the_steps_and_dumps_the_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps 13 --warmup 2 --dump-outputs DIR` (no --full): the line holds the headline alone, the timed region ran
+    exactly 13 LM iterations (chunks of 10 + 3), and DIR holds the last chunk's parameters and summary as float64 arrays."""
+    out = _run_bench(1, ["--gpus", "1", "--steps", "13", "--warmup", "2", "--dump-outputs", str(tmp_path / "out")])
+    line = out[0][0]
+    assert line["steps"] == 13 and line["warmup"] == 2 and line["config"]["successful_steps"] == 13
+    assert abs(line["value"] - 1e3 / line["ms_per_step"]) <= 1e-6 * line["value"]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert not {"widened", "ransac", "roofline", "kernels", "cpu_baseline", "phase_ms_per_call"} & set(line)
+    got = {f: np.load(str(tmp_path / "out" / f)) for f in sorted(os.listdir(str(tmp_path / "out")))}
+    assert sorted(got) == ["intrinsics.npy", "points.npy", "poses.npy", "summary.npy"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["poses.npy"].shape == (8, 7) and got["points.npy"].shape == (120, 3) and got["intrinsics.npy"].shape[0] == 1
+    assert got["summary.npy"].tolist() == [2.0, 1.0, 3.0, 3.0, 0.0, 1.0]      # the last chunk: 3 iterations

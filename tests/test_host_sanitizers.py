@@ -14,7 +14,7 @@ def test_host_code_is_clean_under_address_and_undefined_behaviour_sanitizers(tmp
     lib = build.build_host_sanitized()
     rt = build.sanitizer_runtime_dir()
     exe = str(tmp_path / "host_sanitizer_driver")
-    subprocess.check_call([build.hipcc(), "-x", "c++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-shared-libsan",
+    subprocess.check_call([build.hipcc(), "-x", "c++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined", "-shared-libsan",
                            os.path.join(ROOT, "tests", "host_sanitizer_driver.cpp"), "-x", "none", "-o", exe, lib,
                            "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath," + rt, "-Wl,-rpath,/opt/rocm/lib"])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1:protect_shadow_gap=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
