@@ -18,6 +18,9 @@
  *   - quaternions are (w, x, y, z) (base/image.h:219), projection matrices 3x4 ROW-major.
  *   - camera models are identified by the reference's model ids 0..10 (base/camera_models.h:189-349);
  *     every intrinsics block occupies PP_CAM_STRIDE doubles, only the first kNumParams are used.
+ *   - the optional PPSFM_* environment variables are read when a handle is created
+ *     (pp_ba_create) or a stand-alone entry point starts (pp_ba_plan_ordering, pp_dense_cholesky_solve, ...);
+ *     changing one later does not affect an existing handle.
  */
 #ifndef PPSFM_HIP_H_
 #define PPSFM_HIP_H_

@@ -498,14 +498,6 @@ using namespace ppsfm;
 
 extern "C" {
 
-static void ApplyAberthKnob() {
-  const char* e = std::getenv("PPSFM_ABERTH_SWEEPS");
-  if (!e) return;
-  int v = std::atoi(e);
-  if (v < 1) v = 1;
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(ppsfm::g_aberth_sweeps), &v, sizeof(int));
-}
-
 int pp_pose_destroy(pp_pose_handle h) try {
   if (!h) return PP_OK;
   (void)hipSetDevice(h->device);
@@ -529,7 +521,6 @@ int pp_pose_create(int32_t n, const double* lines2D, const double* points3D, con
   PP_HIP_TRY(hipGetDeviceCount(&ndev));
   PP_REQUIRE(device >= 0 && device < ndev, "pp_pose_create: device %d of %d", device, ndev);
   PP_HIP_TRY(hipSetDevice(device));
-  ApplyAberthKnob();
   pp_pose_impl* h = new pp_pose_impl();
   OnUnwind unwind{[&] { pp_pose_destroy(h); }};
   h->device = device; h->n = n;

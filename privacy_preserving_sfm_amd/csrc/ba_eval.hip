@@ -328,7 +328,8 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   // structure of the factor sparser; every per-image input / output of the C ABI (pp_ba_set/get_parameters, pp_ba_reduced_system) is
   // in the caller's order.  old_of_new empty = the caller's order.
   const auto t_create0 = std::chrono::steady_clock::now();
-  const bool create_dbg = std::getenv("PPSFM_CREATE_DEBUG") != nullptr;      // (stderr: where the host time of this create goes)
+  const ppsfm::Switches sw = ppsfm::ReadSwitches();      // (the handle's snapshot: nothing reads the environment after this)
+  const bool create_dbg = sw.create_debug;      // (stderr: where the host time of this create goes)
   auto lap = [&, last = t_create0](const char* what) mutable {
     if (!create_dbg) return;
     const auto now = std::chrono::steady_clock::now();
@@ -339,20 +340,17 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   OnUnwind unwind{[&] { pp_ba_destroy(h); }};      // (a std::bad_alloc of the host builders below must not leak the handle's device memory)
   // (a handle whose order and tile structure come from the caller's co-visibility - the union over the shards of a point-sharded group - lays out the
   // exchanged system like every other rank that was given the same matrix: it may join a group renumbered and block-sparse)
+  h->sw = sw;
   h->structure_from_covisibility = d->covisibility != nullptr;
   h->device = device; h->C = C; h->P = P; h->K = K; h->M = M;
   h->loss_type = d->loss_type; h->loss_scale = d->loss_scale;
   h->NI = NI; h->n_red = 6 * C + NI; h->intrinsics_variable = NI > 0;
   h->jcam_stride = std::max(2, (nv_widest + 1) & ~1);
-  {
-    // linear solver of the reduced camera system, chosen before the structure is built as BundleAdjuster::Solve does
-    // (bundle_adjustment.cc:273-286): ITERATIVE_SCHUR above 1000 images.  PPSFM_BA_LINEAR_SOLVER=direct|iterative overrides (tools / tests).
-    // Variable intrinsics ride along: their columns follow the pose columns in the conjugate-gradient vectors, their part of the operator is applied
-    // from the per-observation intrinsics Jacobians, their diagonal blocks (the preconditioner's) are assembled from the (k, k) pair lists alone.
-    int ls = d->linear_solver;
-    if (const char* e = std::getenv("PPSFM_BA_LINEAR_SOLVER")) ls = (e[0] == 'i' || e[0] == 'I') ? PP_LINEAR_SOLVER_ITERATIVE_SCHUR : ((e[0] == 'd' || e[0] == 'D') ? PP_LINEAR_SOLVER_DIRECT : ls);
-    h->iterative = ls == PP_LINEAR_SOLVER_ITERATIVE_SCHUR || (ls == PP_LINEAR_SOLVER_AUTO && C > PP_MAX_NUM_IMAGES_DIRECT_SOLVER);
-  }
+  // linear solver of the reduced camera system, chosen before the structure is built as BundleAdjuster::Solve does
+  // (bundle_adjustment.cc:273-286): ITERATIVE_SCHUR above 1000 images.  PPSFM_BA_LINEAR_SOLVER=direct|iterative overrides (tools / tests).
+  // Variable intrinsics ride along: their columns follow the pose columns in the conjugate-gradient vectors, their part of the operator is applied
+  // from the per-observation intrinsics Jacobians, their diagonal blocks (the preconditioner's) are assembled from the (k, k) pair lists alone.
+  h->iterative = ppsfm::WillIterate(d, sw.ba_linear_solver);
   const bool iterative = h->iterative;
   int rc = PP_OK;
 #define TRY(x) do { rc = (x); if (rc) { pp_ba_destroy(h); return rc; } } while (0)
@@ -376,7 +374,7 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   lap("CSR by point");
   // On the device when the problem is large enough to pay for the launches (pair_lists.hip): the by-point lists go up first - the co-visibility graph the
   // image order is chosen on comes from them (in the caller's numbering), then the Schur pair lists (in the order chosen).
-  bool lists_on_device = !iterative && PairListsOnDeviceEligible(C, M);
+  bool lists_on_device = !iterative && PairListsOnDeviceEligible(C, M, sw.ba_pair_lists);
   std::vector<uint64_t> graph_bits;
   double graph_ms = 0;
   if (lists_on_device) {
@@ -384,10 +382,10 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
     TRY(HandleAlloc(&h->pt_start, P + 1)); TRY(HandleAlloc(&h->pt_obs, M));
     TRY(Upload(h->obs_point, d->obs_point, M, s)); TRY(Upload(h->point_const, point_const.data(), P, s));
     TRY(Upload(h->pt_start, pt_start.data(), P + 1, s)); TRY(Upload(h->pt_obs, pt_obs.data(), M, s));
-    if (ppsfm::OrderingReadsObservations(d, NI)) {
+    if (ppsfm::OrderingReadsObservations(d, NI, sw)) {
       const auto tg = std::chrono::steady_clock::now();
       std::vector<uint8_t> fixed(C, 0);
-      if (d->pose_const && (iterative || ppsfm::PrivateIntrinsicsColumns(d) == 0)) std::memcpy(fixed.data(), d->pose_const, C);      // (as ChooseImageOrdering's fixed_image)
+      if (d->pose_const && (iterative || ppsfm::PrivateIntrinsicsColumns(d, sw.ba_intr_layout) == 0)) std::memcpy(fixed.data(), d->pose_const, C);      // (as ChooseImageOrdering's fixed_image)
       TRY(Upload(h->obs_pose, d->obs_pose, M, s)); TRY(Upload(h->pose_const, fixed.data(), C, s));
       TRY(CoVisibilityOnDevice(C, M, h->pt_start, h->pt_obs, h->obs_pose, h->obs_point, h->pose_const, h->point_const, s, &graph_bits));
       graph_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tg).count();
@@ -399,7 +397,7 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   // The images are renumbered INTERNALLY (pose index = position of its six columns in the reduced system) when that makes the tile
   // structure of the factor sparser; every per-image input / output of the C ABI (pp_ba_set/get_parameters, pp_ba_reduced_system) is
   // in the caller's order.  old_of_new empty = the caller's order.
-  ppsfm::ImageOrdering ord = ppsfm::ChooseImageOrdering(d, NI, graph_bits.empty() ? nullptr : graph_bits.data());
+  ppsfm::ImageOrdering ord = ppsfm::ChooseImageOrdering(d, NI, sw, graph_bits.empty() ? nullptr : graph_bits.data());
   const double ordering_ms = graph_ms + ord.plan_ms;
   std::vector<int32_t> old_of_new, new_of_old;
   old_of_new.swap(ord.old_of_new); new_of_old.swap(ord.new_of_old);
@@ -424,13 +422,11 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   h->nnz_tiles_natural = nnz_natural; h->nnz_tiles_ordered = nnz_ordered;
   // columns of the reduced system: the vectors' order (pose c at 6c, intrinsics block k at 6C + intr_off[k]) unless every image carries its own variable
   // intrinsics, which then sit beside its pose columns (image_ordering.hip PrivateIntrinsicsColumns; internal image order)
-  const int nv_private = iterative ? 0 : ppsfm::PrivateIntrinsicsColumns(d);
+  const int nv_private = iterative ? 0 : ppsfm::PrivateIntrinsicsColumns(d, sw.ba_intr_layout);
   const int W6 = 6 + nv_private;
   h->spos_identity = nv_private == 0;
-  {
-    const char* e = std::getenv("PPSFM_BA_INTR_WIDE");      // 0: the general block-pair lists (ba_intr.hip) also for per-image intrinsics (tests / comparisons)
-    h->intr_wide_nv = (nv_private >= 2 && nv_private <= 8 && !(e && std::atoi(e) == 0)) ? nv_private : 0;
-  }
+  // (PPSFM_BA_INTR_WIDE=0: the general block-pair lists (ba_intr.hip) also for per-image intrinsics - tests / comparisons)
+  h->intr_wide_nv = (nv_private >= 2 && nv_private <= 8 && sw.ba_intr_wide) ? nv_private : 0;
   h->spos_host.resize((size_t)h->n_red);
   for (int v = 0; v < h->n_red; ++v) h->spos_host[v] = v;
   if (nv_private)
@@ -549,8 +545,7 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
     if (NI > nv_private * C) mark(W6 * C, h->n_red - 1, 0, h->n_red - 1);      // the shared intrinsics rows couple with every image
     mark(h->n_red, h->n_red, 0, h->n_red);                        // the right-hand side's row
     const int nnz = SymbolicTileFill(Tt, nz.data());
-    const char* e = std::getenv("PPSFM_BA_SPARSE");
-    h->sparse_tiles = !iterative && !(e && std::atoi(e) == 0) && Tt >= 8 && (int64_t)nnz * 10 <= (int64_t)Tt * (Tt + 1) / 2 * 7;      // (variable intrinsics: their rows are dense, the pose part keeps its structure - an arrow)
+    h->sparse_tiles = !iterative && sw.ba_sparse && Tt >= 8 && (int64_t)nnz * 10 <= (int64_t)Tt * (Tt + 1) / 2 * 7;      // (variable intrinsics: their rows are dense, the pose part keeps its structure - an arrow)
     h->tile_nz.swap(nz);
     h->num_nz_tiles = nnz;
   }
@@ -646,15 +641,14 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   // A pair list is walked entry by entry with a dependent gather each (~0.7 us): lists of more than 64 entries are always cut into chunks of 16
   // (deterministic partial blocks + one reduction); a problem too small to fill the chip (the mapper's local bundle adjustment: 20 images /
   // 2000 observations walk 40-entry lists for 26 us with 3 % of the lanes) cuts lists of more than 12 entries into chunks of 8.
-  int32_t chunk_len = 16;      // (32 until the sequence scenes were measured: cfg-3 size, window 40 - lists of ~35 entries - Schur phase 105 us with 32, 95 with 16, 93 with 8, 98 with 4: tools/chunk_len_probe.sh)
+  int32_t chunk_len = 16;      // (32 until the sequence scenes were measured: cfg-3 size, window 40 - lists of ~35 entries - Schur phase 105 us with 32, 95 with 16, 93 with 8, 98 with 4)
   {
     int32_t longest = 0;
     int64_t total = 0;
     for (size_t i = 0; i < (size_t)h->num_pairs; ++i) { const int32_t len = pair_start[2 * i + 1] - pair_start[2 * i]; longest = std::max(longest, len); total += len; }
     const bool latency_bound = total <= 65536 && longest > 12;
-    h->pairs_chunked = !iterative && NI == 0 && (longest > 64 || latency_bound) && !(std::getenv("PPSFM_BA_CHUNKED_PAIRS") && std::atoi(std::getenv("PPSFM_BA_CHUNKED_PAIRS")) == 0);
+    h->pairs_chunked = !iterative && NI == 0 && (longest > 64 || latency_bound) && sw.ba_chunked_pairs;
     if (latency_bound) chunk_len = 8;
-    if (const char* e = std::getenv("PPSFM_BA_CHUNK_LEN")) chunk_len = std::max(1, std::atoi(e));      // (experiments: tools/nd_probe.py)
   }
   const bool want_chunks = h->pairs_chunked;
   if (want_chunks) {
@@ -681,7 +675,7 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
     // window of row images) and a record is read by at most two XCDs.  A chunk keeps its id (entry 0 of its triple): its partial block is written where
     // k_schur_chunk_reduce expects it, so the sums and their bits are unchanged.  Small problems keep the natural order (nothing to gain below a few MB).
     const size_t nch = small_chunk.size() / 3;
-    const bool xcd_order = nch >= 8 * 40 * 4 && !(std::getenv("PPSFM_BA_CHUNK_XCD") && std::atoi(std::getenv("PPSFM_BA_CHUNK_XCD")) == 0);
+    const bool xcd_order = nch >= 8 * 40 * 4 && sw.ba_chunk_xcd;
     for (size_t q = 0; q < nch; ++q) small_chunk[3 * q] = (int32_t)q;      // (entry 0: the chunk's id = where its partial block goes)
     if (xcd_order) {
       std::vector<int32_t> key_of[2] = {std::vector<int32_t>(nch), std::vector<int32_t>(nch)};      // [0] row image (minor key), [1] column image (major key) of a chunk's pair
@@ -1003,7 +997,7 @@ int pp_ba_covisibility(const pp_ba_problem_desc* d, uint8_t* out) try {
   for (int64_t o = 0; o < M; ++o) ps[d->obs_point[o] + 1]++;
   for (int p = 0; p < P; ++p) ps[p + 1] += ps[p];
   { std::vector<int32_t> f(ps.begin(), ps.end() - 1); for (int64_t o = 0; o < M; ++o) po[f[d->obs_point[o]]++] = d->obs_pose[o]; }
-  const uint8_t* fixed = (d->camera_const_mask && ppsfm::PrivateIntrinsicsColumns(d) > 0) ? nullptr : d->pose_const;      // (intrinsics of its own beside the pose: every image has columns)
+  const uint8_t* fixed = (d->camera_const_mask && ppsfm::PrivateIntrinsicsColumns(d, ppsfm::ReadSwitches().ba_intr_layout) > 0) ? nullptr : d->pose_const;      // (intrinsics of its own beside the pose: every image has columns)
   for (int p = 0; p < P; ++p) {
     if (d->point_const && d->point_const[p]) continue;
     for (int a = ps[p]; a < ps[p + 1]; ++a) {

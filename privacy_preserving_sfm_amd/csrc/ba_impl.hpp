@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "switches.hpp"
 
 namespace ppsfm {
 
@@ -34,7 +35,8 @@ __device__ __forceinline__ const double* RecX(const double* rec, size_t o) { ret
 struct ChainTask;
 // launch-structure state of the dense Cholesky (cholesky.hip)
 struct CholeskyAux {
-  int mode = -1;                    // -1: decide at the first solve (PPSFM_CHOL_MODE); 1 = task mode (one launch), 0 = one launch per block column, 2 = by size
+  Switches sw;                      // the owner's snapshot (CholeskyAuxCreate): the planner's switches, the back substitution, the small-system kernel
+  int mode = -1;                    // -1: not yet created (CholeskyAuxCreate: PPSFM_CHOL_MODE); 1 = task mode (one launch), 0 = one launch per block column, 2 = by size
   bool use_graph = true;            // capture the launch structure once, replay per solve
   hipGraphExec_t graph_exec = nullptr;
   double *g_S = nullptr, *g_Linv = nullptr, *g_x = nullptr, *g_Lfac = nullptr;
@@ -51,7 +53,6 @@ struct CholeskyAux {
   int scratch_tiles = 0;
   int critical_path = 0;                  // block-column steps on the longest dependency path of the list (T for one chain)
   double plan_ms = 0;                     // host time of the last EnsureTaskList (plan, list, replay, upload; a cache hit: the upload)
-  bool test_drop_tasks = false;     // PPSFM_CHOL_TEST_DROP_TASKS=1: launch only half of the list (exercises the timeout -> per-column fallback)
   // block-sparse factor: tile_nz = tile_T x tile_T bytes (lower triangle, closed under fill-in; owned by the caller, null = dense);
   // from it: the per-launch row / super-tile lists (host + device copies) and the byte map on the device
   const uint8_t* tile_nz = nullptr;
@@ -67,18 +68,21 @@ struct CholeskyAux {
 int SymbolicTileFill(int T, uint8_t* nz);
 // chain steps of the one-launch factorisation of a T x T tile map (closed under fill-in): the block columns on the longest dependency path when its
 // elimination tree has independent sub-trees (several chains, cholesky.hip), T otherwise; *chains (may be null): the number of chains
-int CholeskyChainSteps(int T, const uint8_t* nz, int* chains = nullptr);
+int CholeskyChainSteps(int T, const uint8_t* nz, const Switches& sw, int* chains = nullptr);
 // the same from the chain plan alone (no task list is built or replayed): what a candidate image order costs (image_ordering.hip)
-int CholeskyPlanSteps(int T, const uint8_t* nz, int* chains = nullptr);
+int CholeskyPlanSteps(int T, const uint8_t* nz, const Switches& sw, int* chains = nullptr);
 // The image order pp_ba_create gives the reduced camera system (image_ordering.hip; host only): old_of_new empty = the caller's order.
 // nnz_*: non-zero tiles of the factor in the caller's order / in the order taken (-1: not computed); dense_exit: the co-visibility turned out too dense
 // for any order to pay and was not completed; chains / chain_steps: of the order taken (0: not planned); plan_ms: host time spent.
 struct ImageOrdering { std::vector<int32_t> old_of_new, new_of_old; int nnz_natural = -1, nnz_ordered = -1, chains = 0, chain_steps = 0; bool dense_exit = false; double plan_ms = 0; };
-ImageOrdering ChooseImageOrdering(const pp_ba_problem_desc* d, int NI, const uint64_t* graph_bits = nullptr);
-bool OrderingReadsObservations(const pp_ba_problem_desc* d, int NI);      // ChooseImageOrdering would walk the observations for the co-visibility graph
+ImageOrdering ChooseImageOrdering(const pp_ba_problem_desc* d, int NI, const Switches& sw, const uint64_t* graph_bits = nullptr);
+bool OrderingReadsObservations(const pp_ba_problem_desc* d, int NI, const Switches& sw);      // ChooseImageOrdering would walk the observations for the co-visibility graph
+// the reduced camera system is solved by conjugate gradients (ba_pcg.hip): the descriptor's linear solver unless PPSFM_BA_LINEAR_SOLVER overrides it -
+// ITERATIVE_SCHUR above PP_MAX_NUM_IMAGES_DIRECT_SOLVER images for AUTO (bundle_adjustment.cc:273-286)
+bool WillIterate(const pp_ba_problem_desc* d, LinearSolverSwitch sw);
 int CountVariableIntrinsics(const pp_ba_problem_desc* d);
 // the Schur pair lists on the device (pair_lists.hip)
-bool PairListsOnDeviceEligible(int C, int64_t M);
+bool PairListsOnDeviceEligible(int C, int64_t M, PairListsSwitch sw);
 int BuildPairListsOnDevice(int C, int64_t M, const int32_t* d_pt_start, const int32_t* d_pt_obs, const int32_t* d_obs_pose, const int32_t* d_obs_point,
                            const uint8_t* d_pose_const, const uint8_t* d_point_const, hipStream_t s, int32_t** entries_out, int64_t* num_entries,
                            std::vector<int32_t>* pair_start, std::vector<int32_t>* pair_ij, bool* fallback);
@@ -88,8 +92,8 @@ void BuildPairListsOnHost(int C, int P, int64_t M, const int32_t* pt_start, cons
 // the co-visibility graph of the variable images from the same arrays (any image numbering): bits[i * ceil(C / 64) + (j >> 6)] bit (j & 63), j < i
 int CoVisibilityOnDevice(int C, int64_t M, const int32_t* d_pt_start, const int32_t* d_pt_obs, const int32_t* d_obs_pose, const int32_t* d_obs_point,
                          const uint8_t* d_pose_const, const uint8_t* d_point_const, hipStream_t s, std::vector<uint64_t>* bits);
-int PrivateIntrinsicsColumns(const pp_ba_problem_desc* d);      // n_v > 0: every image carries its own n_v variable intrinsics beside its pose columns (image_ordering.hip)
-int CholeskyAuxCreate(CholeskyAux* aux);
+int PrivateIntrinsicsColumns(const pp_ba_problem_desc* d, IntrLayout layout);      // n_v > 0: every image carries its own n_v variable intrinsics beside its pose columns (image_ordering.hip)
+int CholeskyAuxCreate(CholeskyAux* aux, const Switches& sw);
 void CholeskyAuxDestroy(CholeskyAux* aux);
 }  // namespace ppsfm
 
@@ -99,6 +103,7 @@ struct PcgState { double rho, Q0, norm_b, alpha; int32_t iter, done, status, pad
 }  // namespace ppsfm
 
 struct pp_ba_impl {
+  ppsfm::Switches sw;      // the environment switches as pp_ba_create found them (switches.hpp)
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -14,10 +14,10 @@
 //   k_pcg_images   per image (one workgroup): (S v)_c = sum_{o in c} J^_c,o^T (J^_c,o v_c - T_o a_p(o)) + d_c v_c, and v_c . (S v)_c
 // both HBM/L2-bound gathers of 144 of a record's 192 bytes per observation (algorithmic: 2 x 144 B per observation and product).
 // The vector updates, dot products (fixed order: deterministic) and the termination test of an iteration: k_pcg_wide_a / _b (many
-// workgroups, two launches), or k_pcg_vec (ONE workgroup, one launch: the first form, kept behind PPSFM_PCG_WIDE=0 for the tests).  The host enqueues a few iterations at a time and reads the
-// state back; once the loop has ended the kernels already in the stream return at their first instruction.
-// DEFAULT outside point-sharded groups: three launches per iteration (k_pcg_points_dir, k_pcg_images_dir, k_pcg_step - see below): the
-// product kernels take the decision and form the direction themselves.  PPSFM_PCG_FUSED=0 / PPSFM_PCG_WIDE=0 select the older forms.
+// workgroups, two launches).  The host enqueues a few iterations at a time and reads the state back; once the loop has ended the kernels
+// already in the stream return at their first instruction.  That four-launch form is what point-sharded groups and variable intrinsics run.
+// DEFAULT otherwise: three launches per iteration (k_pcg_points_q, k_pcg_images_q, k_pcg_step - see below): the product kernels take the
+// decision and form the direction themselves.  PPSFM_PCG_FUSED=0 selects the four-launch form (tests compare the two).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -30,21 +30,8 @@
 
 namespace ppsfm {
 
-constexpr int kVecThreads = 1024;
 constexpr int kResidualResetPeriod = 10;      // ConjugateGradientsSolver::Options::residual_reset_period
 enum { kPcgRunning = 0, kPcgConverged = 1, kPcgNoConvergence = 2, kPcgFailure = 3 };
-
-// sum over the workgroup, the same order every time: wave butterflies, then the sixteen wave totals in wave order
-__device__ __forceinline__ double BlockSum(double v, double* red) {
-  v = WaveSum(v);
-  __syncthreads();      // (red may still be read from the previous call)
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < kVecThreads / 64; ++w) s += red[w];
-  return s;
-}
 
 // inverse of the two 3x3 diagonal blocks (rotation tangent, translation) of every image's 6x6 diagonal block of S
 __global__ __launch_bounds__(256) void k_pcg_block_inverse(int C, const double* __restrict__ Sd, double* __restrict__ binv, int32_t* __restrict__ flag) {
@@ -148,88 +135,12 @@ __global__ __launch_bounds__(256) void k_pcg_images(int C, const int32_t* __rest
   }
 }
 
-// z = M^-1 r for this thread's elements i = tid, tid + 1024, ..;  returns this thread's part of r . z
-__device__ __forceinline__ double Precondition(int n, const double* __restrict__ binv, const double* __restrict__ r, double* __restrict__ z) {
-  double part = 0.0;
-  for (int i = threadIdx.x; i < n; i += kVecThreads) {
-    const int c = i / 6, j = i - 6 * c, h = j / 3, jj = j - 3 * h;
-    const double* B = binv + 18 * (size_t)c + 9 * h + 3 * jj;
-    const double* rr = r + 6 * (size_t)c + 3 * h;
-    const double zv = B[0] * rr[0] + B[1] * rr[1] + B[2] * rr[2];
-    z[i] = zv;
-    part += r[i] * zv;
-  }
-  return part;
-}
-
-// One launch per step of the loop, ONE workgroup.  mode 0: start (x = 0, r = b, first direction).  mode 1: after q = S p of iteration
-// `it`: step length, x, r (or, every 10th iteration, x only: the host then applies S to x and calls mode 2), termination test, next
-// direction.  mode 2: r = b - S x (in `q`), termination test, next direction.
-__global__ __launch_bounds__(kVecThreads) void k_pcg_vec(int mode, int it, int n, int C, const double* __restrict__ b, double* __restrict__ x, double* __restrict__ r,
-                                                         double* __restrict__ z, double* __restrict__ p, const double* __restrict__ q,
-                                                         const double* __restrict__ binv, const double* __restrict__ dotp, PcgState* __restrict__ st,
-                                                         double eta, int max_iterations, int32_t* __restrict__ flag) {
-  __shared__ double red[kVecThreads / 64];
-  __shared__ PcgState s_in;
-  const int tid = threadIdx.x;
-  if (tid == 0) s_in = *st;
-  __syncthreads();
-  // every thread works on its OWN copy of the state (all of them compute the same scalars from the same block sums, so all take the
-  // same branches); thread 0 writes the new state back at the end.  Nothing is read from the shared copy after this line: a thread
-  // that is ahead must not change what a slower wavefront is still about to read.
-  PcgState s = s_in;
-  if (mode != 0 && (s.done || s.iter != it)) return;
-  auto finish = [&](int status) {      // all threads call with the same value
-    if (tid == 0) { s.done = 1; s.status = status; *st = s; if (status == kPcgFailure) atomicOr(flag, 1); }
-  };
-  if (mode == 0) {
-    double nb = 0.0;
-    for (int i = tid; i < n; i += kVecThreads) { const double bv = b[i]; x[i] = 0.0; r[i] = bv; nb += bv * bv; }
-    nb = BlockSum(nb, red);
-    s.iter = 1; s.done = 0; s.status = kPcgRunning; s.rho = 1.0; s.Q0 = 0.0; s.norm_b = sqrt(nb); s.alpha = 0.0;
-    if (!(nb > 0.0)) { s.iter = 0; finish(nb == 0.0 ? kPcgConverged : kPcgFailure); return; }      // |b| = 0: x = 0 is the solution (NaN: failure)
-  } else if (mode == 1) {
-    double pq = 0.0;
-    if (dotp) { for (int c = tid; c < C; c += kVecThreads) pq += dotp[c]; }
-    else { for (int i = tid; i < n; i += kVecThreads) pq += p[i] * q[i]; }      // a group: q is the all-reduced product
-    pq = BlockSum(pq, red);
-    if (!(pq > 0.0) || isinf(pq)) { finish(isnan(pq) ? kPcgFailure : kPcgNoConvergence); return; }      // indefinite direction: the iterate so far is the answer
-    const double alpha = s.rho / pq;
-    if (isinf(alpha)) { finish(kPcgFailure); return; }
-    const bool reset = (it % kResidualResetPeriod) == 0;
-    for (int i = tid; i < n; i += kVecThreads) { x[i] += alpha * p[i]; if (!reset) r[i] -= alpha * q[i]; }
-    if (reset) { if (tid == 0) { s.alpha = alpha; *st = s; } return; }
-  } else {
-    for (int i = tid; i < n; i += kVecThreads) r[i] = b[i] - q[i];
-  }
-  if (mode != 0) {
-    double q1 = 0.0;
-    for (int i = tid; i < n; i += kVecThreads) q1 -= x[i] * (b[i] + r[i]);
-    q1 = BlockSum(q1, red);
-    const double zeta = it * (q1 - s.Q0) / q1;
-    if (zeta < eta) { finish(kPcgConverged); return; }
-    if (it >= max_iterations) { finish(kPcgNoConvergence); return; }
-    s.Q0 = q1; s.iter = it + 1;
-  }
-  // next direction (the block sum's barriers also order this workgroup's writes of r before the reads below)
-  const double rho = BlockSum(Precondition(n, binv, r, z), red);
-  if (rho == 0.0 || isinf(rho) || isnan(rho)) { finish(kPcgFailure); return; }
-  double beta = 0.0;
-  if (mode != 0) {
-    beta = rho / s.rho;
-    if (beta == 0.0 || isinf(beta) || isnan(beta)) { finish(kPcgFailure); return; }
-  }
-  for (int i = tid; i < n; i += kVecThreads) p[i] = (mode == 0) ? z[i] : z[i] + beta * p[i];
-  s.rho = rho;
-  if (tid == 0) *st = s;
-}
-
-// ---- the vector step over MANY workgroups (k_pcg_vec, one workgroup, is 12.5 us at 1100 images and 30 us at 4000 - the longest kernel
-// of an iteration there).  Two launches instead of one, a thread per 3 x 3 parameter block:
+// ---- the vector step over MANY workgroups (a single workgroup was 12.5 us at 1100 images and 30 us at 4000 - the longest kernel of an
+// iteration there).  Two launches, a thread per 3 x 3 parameter block:
 //   k_pcg_wide_a   alpha = rho / (p . S p) from the per-image parts (every workgroup sums them itself, in the same order: the same
 //                  bits everywhere, no exchange), x += alpha p, r -= alpha q (or the explicit residual), z = M^-1 r, and this
 //                  workgroup's parts of Q = -x . (b + r) / ... and of r . z
-//   k_pcg_wide_b   every workgroup sums the parts, takes the termination decision of k_pcg_vec (same tests, same order) and updates its
+//   k_pcg_wide_b   every workgroup sums the parts, takes the termination decision (ConjugateGradientsSolver's tests, in its order) and updates its
 //                  slice of the direction p = z + beta p
 // The state is read by every workgroup of a launch and written by workgroup 0 of k_pcg_wide_b: it ping-pongs between two copies (a
 // workgroup dispatched late must not find the NEXT iteration's state), the host tracks which one is current.
@@ -508,15 +419,15 @@ __global__ __launch_bounds__(kWideThreads) void k_pcg_wide_b(int mode, int it, i
 
 // ---- THREE launches per iteration (the default outside point-sharded groups).  k_pcg_wide_b is gone: the decision it took and the
 // direction it wrote are taken by the product kernels themselves.
-//   k_pcg_points_dir   every wavefront sums the parts of Q and r . z k_pcg_step left (the same order everywhere: the same bits, no
+//   k_pcg_points_q     every wavefront sums the parts of Q and r . z k_pcg_step left (the same order everywhere: the same bits, no
 //                      exchange), takes the termination decision and beta, and forms the direction of the images it touches on the
 //                      fly: p_c = z_c + beta p_old,c (both vectors are L2 resident: 53 KB at 1100 images)
-//   k_pcg_images_dir   the same decision, p_c once more for ITS image - stored: the direction buffer ping-pongs, like the state that workgroup 0
+//   k_pcg_images_q     the same decision, p_c once more for ITS image - stored: the direction buffer ping-pongs, like the state that workgroup 0
 //                      writes - then (S p)_c and the image's part of p . S p
 //   k_pcg_step         alpha, x, r, z = M^-1 r, parts (k_pcg_wide_a with every load issued before the first workgroup sum; at the
 //                      start of a solve it also inverts the diagonal blocks: k_pcg_block_inverse folded in)
 // and the index walks are one level shorter: (observation, image) pairs per point-list entry and (observation, point) pairs per image-list
-// entry (k_pcg_entries, built once per handle), eight lanes per point when the tracks are long enough.  The kernels of an iteration are
+// entry (k_pcg_entries, built once per handle), two, four or eight records of a point in flight by the mean track.  The kernels of an iteration are
 // bound by the LATENCY of their dependent loads (344 + 1100 + 9 workgroups at 1100 images, a few microseconds each), not by bytes.
 struct PcgDecision { PcgState s; double beta; int run; int failed; };
 
@@ -599,131 +510,9 @@ __global__ __launch_bounds__(64) void k_pcg_decide(int it, int G, const double* 
   }
 }
 
-// kDir: v = the direction z + beta p_old after the decision on iteration `it` (= the one before); otherwise v = the vector given (x of a residual-reset iteration `it`)
-template <bool kDir, int kLanes>
-__global__ __launch_bounds__(256) void k_pcg_points_dir(int P, const int32_t* __restrict__ pt_start, const int2* __restrict__ pt_entry, const double* __restrict__ rec,
-                                                        const double* __restrict__ v, const double* __restrict__ p_old, double* __restrict__ a,
-                                                        const PcgState* __restrict__ st, const double* __restrict__ part, int G, int it, double eta, int max_iterations) {
-  const int gid = blockIdx.x * 256 + threadIdx.x;
-  const int p = gid / kLanes, q = gid % kLanes;
-  int e0 = 0, e1 = 0;
-  if (p < P) { e0 = pt_start[p] + q; e1 = pt_start[p + 1]; }
-  const bool first = kDir && it == 0;
-  // The first entry of the lane and everything it points at are requested BEFORE the decision (whose loads and wavefront sums then run
-  // beside them instead of in front of them); a lane without an entry reads entry 0 and drops it.
-  double jp[12], jx[6], vc[6], po[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  auto fetch = [&](int e) {
-    const int2 en = pt_entry[e];
-    const int o = en.x, c = en.y;
-    const double2* rj = reinterpret_cast<const double2*>(RecJ(rec, (size_t)o));      // J_pose,o s_c (2 x 6) then J_pt,o (2 x 3): 144 contiguous bytes
-#pragma unroll
-    for (int j = 0; j < 6; ++j) vc[j] = v[6 * (size_t)c + j];
-    if (kDir && !first) {
-#pragma unroll
-      for (int j = 0; j < 6; ++j) po[j] = p_old[6 * (size_t)c + j];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) { const double2 t = rj[i]; jp[2 * i] = t.x; jp[2 * i + 1] = t.y; }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { const double2 t = rj[6 + i]; jx[2 * i] = t.x; jx[2 * i + 1] = t.y; }
-  };
-  fetch(e0 < e1 ? e0 : 0);
-  const PcgDecision d = kDir ? PcgDecide(it, G, part, st, eta, max_iterations) : PcgCarry(it, part, st);
-  if (!d.run) return;
-  double acc[3] = {0.0, 0.0, 0.0};
-  for (int e = e0; e < e1; e += kLanes) {
-    if (e != e0) fetch(e);
-    double m0 = 0.0, m1 = 0.0;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) { const double dv = kDir ? PcgDirection(first, d.beta, vc[j], first ? 0.0 : po[j]) : vc[j]; m0 += jp[j] * dv; m1 += jp[6 + j] * dv; }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) acc[k] += jx[k] * m0 + jx[3 + k] * m1;
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {      // the lanes of a point: fixed butterfly
-#pragma unroll
-    for (int off = 1; off < kLanes; off <<= 1) acc[k] += __shfl_xor(acc[k], off);
-  }
-  if (p < P && q == 0) { a[3 * (size_t)p] = acc[0]; a[3 * (size_t)p + 1] = acc[1]; a[3 * (size_t)p + 2] = acc[2]; }
-}
-
-template <bool kDir>
-__global__ __launch_bounds__(256) void k_pcg_images_dir(int C, const int32_t* __restrict__ pose_start, const int2* __restrict__ pose_entry, const double* __restrict__ rec,
-                                                        const double* __restrict__ v, const double* __restrict__ p_old, double* __restrict__ p_new,
-                                                        const double* __restrict__ a, const double* __restrict__ scale_c, const double* __restrict__ diag_c, double inv_radius,
-                                                        double* __restrict__ out, double* __restrict__ dotp, const PcgState* __restrict__ st, PcgState* __restrict__ st_out,
-                                                        const double* __restrict__ part, int G, int it, double eta, int max_iterations, int32_t* __restrict__ flag) {
-  __shared__ double red[4][6];
-  const int c = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  // everything that does not depend on the decision is requested first
-  const int e0 = pose_start[c] + (int)threadIdx.x, e1 = pose_start[c + 1];
-  double vc[6], po[6];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) { vc[j] = v[6 * (size_t)c + j]; po[j] = (kDir && it != 0) ? p_old[6 * (size_t)c + j] : 0.0; }
-  double sc = 1.0, dg = 0.0;
-  if (threadIdx.x < 6) { sc = scale_c[6 * (size_t)c + threadIdx.x]; dg = diag_c[6 * (size_t)c + threadIdx.x]; }
-  // the thread's first entry and what it points at: requested before the decision, whose loads and wavefront sums then run beside them
-  double t[6], jp[12], a0, a1, a2;
-  auto fetch = [&](int e) {
-    const int2 en = pose_entry[e];
-    const int o = en.x, p = en.y;
-    const double2* rt = reinterpret_cast<const double2*>(RecT(rec, (size_t)o));      // T_o (2 x 3) then J_pose,o s_c (2 x 6): 144 contiguous bytes
-    a0 = a[3 * (size_t)p]; a1 = a[3 * (size_t)p + 1]; a2 = a[3 * (size_t)p + 2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { const double2 x = rt[i]; t[2 * i] = x.x; t[2 * i + 1] = x.y; }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) { const double2 x = rt[3 + i]; jp[2 * i] = x.x; jp[2 * i + 1] = x.y; }
-  };
-  fetch(e0 < e1 ? e0 : pose_start[0]);
-  const PcgDecision d = kDir ? PcgDecide(it, G, part, st, eta, max_iterations) : PcgCarry(it, part, st);
-  if (c == 0 && threadIdx.x == 0) { *st_out = d.s; if (d.failed) atomicOr(flag, 1); }
-  if (!d.run) return;
-  const bool first = kDir && it == 0;
-  if (kDir) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) vc[j] = PcgDirection(first, d.beta, vc[j], po[j]);
-    if (threadIdx.x < 6) {
-      double mine = vc[0];
-#pragma unroll
-      for (int j = 1; j < 6; ++j) mine = ((int)threadIdx.x == j) ? vc[j] : mine;
-      p_new[6 * (size_t)c + threadIdx.x] = mine;
-    }
-  }
-  double acc[6] = {0, 0, 0, 0, 0, 0};
-  for (int e = e0; e < e1; e += 256) {
-    if (e != e0) fetch(e);
-    double m0 = -(t[0] * a0 + t[1] * a1 + t[2] * a2), m1 = -(t[3] * a0 + t[4] * a1 + t[5] * a2);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) { m0 += jp[j] * vc[j]; m1 += jp[6 + j] * vc[j]; }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) acc[j] += jp[j] * m0 + jp[6 + j] * m1;
-  }
-#pragma unroll
-  for (int j = 0; j < 6; ++j) acc[j] = WaveSum(acc[j]);
-  if (lane == 0) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) red[wv][j] = acc[j];
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {      // lanes 0..5: one component each (constant column: identity row, as the assembled system has it), then lane 0 adds v . S v in component order
-    const int j = threadIdx.x < 6 ? (int)threadIdx.x : 0;
-    double mine = vc[0];
-#pragma unroll
-    for (int k = 1; k < 6; ++k) mine = (j == k) ? vc[k] : mine;
-    const double dd = (sc == 0.0) ? 1.0 : dg * inv_radius;
-    const double qv = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j] + dd * mine;
-    if (threadIdx.x < 6) out[6 * (size_t)c + j] = qv;
-    const double term = mine * qv;
-    double dot = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) dot += __shfl(term, k);
-    if (threadIdx.x == 0) dotp[c] = dot;
-  }
-}
-
 // ---- the product kernels with COALESCED record reads.  A lane that reads its own record takes nine 16-byte pieces at a 192-byte stride: 64
-// distinct lines per wave-level load, ~15 line requests per record and product - the texture-address path is what bounds k_pcg_points_dir /
-// k_pcg_images_dir, not bytes and not latency.  Here FOUR lanes share a record: in load i lane q takes piece 4 i + q, so a quad reads 64 contiguous
+// distinct lines per wave-level load, ~15 line requests per record and product - the texture-address path bounded that first form of the
+// product kernels, not bytes and not latency.  Here FOUR lanes share a record: in load i lane q takes piece 4 i + q, so a quad reads 64 contiguous
 // bytes per load and the record in three.  What a lane holds (pieces of 2 doubles: T = pieces 0-2, J_pose row 0 = 3-5, row 1 = 6-8, J_point = 9-11):
 //   lane 0: T[0:2]   Jc0[2:4]  Jc1[4:6]          lane 2: T[4:6]    Jc1[0:2]  Jx[2:4]
 //   lane 1: T[2:4]   Jc0[4:6]  Jx[0:2]           lane 3: Jc0[0:2]  Jc1[2:4]  Jx[4:6]
@@ -744,6 +533,7 @@ __device__ __forceinline__ QuadRecord LoadQuadRecord(const double* __restrict__ 
 
 // (workgroups of 1024: at 256 threads the 2750 workgroups of 1100 images / 22 000 points took ~5 us to DISPATCH - a launch whose workgroups return at once was 6.2 us)
 constexpr int kPointsQThreads = 1024;
+// kDir: v = the direction z + beta p_old after the decision on iteration `it` (= the one before); otherwise v = the vector given (x of a residual-reset iteration `it`)
 template <bool kDir, int kQuads>      // kQuads quads (records in flight) per point: 2, 4 or 8
 __global__ __launch_bounds__(kPointsQThreads) void k_pcg_points_q(int P, const int32_t* __restrict__ pt_start, const int2* __restrict__ pt_entry, const double* __restrict__ rec,
                                                                   const double* __restrict__ v, const double* __restrict__ p_old, double* __restrict__ a,
@@ -1027,7 +817,7 @@ void PcgFreeBuffers(pp_ba_impl* h) {
 // the host's wait for k_pcg_decide: a busy spin on the ticket for as long as such a look can reasonably take (PPSFM_TICKET_SPIN_US, default 1500 us,
 // 0 = never spin), then naps; after 2 s the stream is synchronised once (a failed launch would otherwise wait forever)
 static int WaitPcgTicket(pp_ba_impl* h, int32_t ticket) {
-  static const long spin_us = []() { const char* e = std::getenv("PPSFM_TICKET_SPIN_US"); return e ? std::atol(e) : 1500L; }();
+  const long spin_us = h->sw.ticket_spin_us;
   const volatile int32_t* t = &h->pcg_state_host->pad_;
   if (spin_us == 0) { PP_HIP_TRY(hipStreamSynchronize(h->stream)); }
   const auto t0 = std::chrono::steady_clock::now();
@@ -1051,8 +841,7 @@ static int WaitPcgTicket(pp_ba_impl* h, int32_t ticket) {
 static int PcgFinishCount(pp_ba_impl* h, int* iterations) {
   const PcgState* hs = h->pcg_state_host;
   if (iterations) *iterations = hs->iter;
-  static const bool log = getenv("PPSFM_PCG_LOG") != nullptr;      // (tools: the iteration counts a look schedule has to predict)
-  if (log) fprintf(stderr, "pcg: %d iterations (previous solve %d)\n", hs->iter, h->pcg_last_iterations);
+  if (h->sw.pcg_log) fprintf(stderr, "pcg: %d iterations (previous solve %d)\n", hs->iter, h->pcg_last_iterations);
   h->pcg_last_iterations = hs->iter;
   return PP_OK;
 }
@@ -1069,9 +858,10 @@ static int PcgFusedRun(pp_ba_impl* h, double inv_radius, int max_iterations, dou
   // ---- three launches per iteration: the product kernels take the decision and form the direction themselves ----
   const int2* pt_entry = reinterpret_cast<const int2*>(h->pcg_pt_entry);
   const int2* pose_entry = reinterpret_cast<const int2*>(h->pcg_pose_entry);
-  const bool eight = h->M > (int64_t)h->P * 9 / 2;      // eight lanes per point when the mean track is longer than 4.5
-  const char* quad_env = getenv("PPSFM_PCG_QUAD");
-  const bool quad = !(quad_env && atoi(quad_env) == 0);      // four lanes per record, coalesced reads (0: a lane per record)
+  // quads per point (a record each per round): 2 up to a mean track of 2.5, 4 up to 4.5, 8 beyond (two records in flight per quad with half
+  // the quads: 11.3 us against 9.1 - the early exit waits for both)
+  const int qp = h->M > (int64_t)h->P * 9 / 2 ? 8 : (h->M > (int64_t)h->P * 5 / 2 ? 4 : 2);
+  const dim3 gq(CeilDiv(4 * qp * (int64_t)h->P, kPointsQThreads)), gi(C);
   int cur = 0, pc = 0;      // current copy of the state / of the direction
   auto step = [&](int mode, int it) {
     hipLaunchKernelGGL(k_pcg_step, dim3(G), dim3(kWideThreads), 0, s, mode, it, C, h->pcg_Sd, h->pcg_b, h->step_c, h->pcg_r, h->pcg_z, h->pcg_p + (size_t)pc * n, h->pcg_q,
@@ -1080,26 +870,12 @@ static int PcgFusedRun(pp_ba_impl* h, double inv_radius, int max_iterations, dou
   auto product = [&](bool dir, const double* v, int it) {      // dir: pcg_q = S (z + beta p) after the decision on iteration `it`; else pcg_q = S v
     const double* p_old = h->pcg_p + (size_t)pc * n;
     double* p_new = h->pcg_p + (size_t)(pc ^ 1) * n;
-    const dim3 gp(CeilDiv((eight ? 8 : 4) * (int64_t)h->P, 256)), gi(C), b(256);
-#define PP_POINTS(D, L) hipLaunchKernelGGL((k_pcg_points_dir<D, L>), gp, b, 0, s, h->P, h->pt_start, pt_entry, h->JpS, v, p_old, h->pcg_a, h->pcg_state + cur, h->pcg_part, G, \
-                                         it, eta, max_iterations)
-#define PP_IMAGES(D) hipLaunchKernelGGL((k_pcg_images_dir<D>), gi, b, 0, s, C, h->pose_start, pose_entry, h->JpS, v, p_old, p_new, h->pcg_a, h->scale_c, h->diag_c, inv_radius, \
-                                      h->pcg_q, h->pcg_dot, h->pcg_state + cur, h->pcg_state + (cur ^ 1), h->pcg_part, G, it, eta, max_iterations, h->d_flag)
 #define PP_POINTS_Q(D, L) hipLaunchKernelGGL((k_pcg_points_q<D, L>), gq, dim3(kPointsQThreads), 0, s, h->P, h->pt_start, pt_entry, h->JpS, v, p_old, h->pcg_a, h->pcg_state + cur, h->pcg_part, G, \
                                            it, eta, max_iterations)
 #define PP_IMAGES_Q(D) hipLaunchKernelGGL((k_pcg_images_q<D>), gi, dim3(kImagesQThreads), 0, s, C, h->pose_start, pose_entry, h->JpS, v, p_old, p_new, h->pcg_a, h->scale_c, h->diag_c, inv_radius, \
                                         h->pcg_q, h->pcg_dot, h->pcg_state + cur, h->pcg_state + (cur ^ 1), h->pcg_part, G, it, eta, max_iterations, h->d_flag)
-    if (quad) {
-      // quads per point (a record each per round): 2 up to a mean track of 2.5, 4 up to 4.5, 8 beyond (two records in flight per quad with half
-      // the quads: 11.3 us against 9.1 - the early exit waits for both)
-      const int qp = eight ? 8 : (h->M > (int64_t)h->P * 5 / 2 ? 4 : 2);
-      const dim3 gq(CeilDiv(4 * qp * (int64_t)h->P, kPointsQThreads));
-      if (dir) { if (qp == 8) PP_POINTS_Q(true, 8); else if (qp == 4) PP_POINTS_Q(true, 4); else PP_POINTS_Q(true, 2); PP_IMAGES_Q(true); pc ^= 1; }
-      else { if (qp == 8) PP_POINTS_Q(false, 8); else if (qp == 4) PP_POINTS_Q(false, 4); else PP_POINTS_Q(false, 2); PP_IMAGES_Q(false); }
-    } else if (dir) { if (eight) PP_POINTS(true, 8); else PP_POINTS(true, 4); PP_IMAGES(true); pc ^= 1; }
-    else { if (eight) PP_POINTS(false, 8); else PP_POINTS(false, 4); PP_IMAGES(false); }
-#undef PP_POINTS
-#undef PP_IMAGES
+    if (dir) { if (qp == 8) PP_POINTS_Q(true, 8); else if (qp == 4) PP_POINTS_Q(true, 4); else PP_POINTS_Q(true, 2); PP_IMAGES_Q(true); pc ^= 1; }
+    else { if (qp == 8) PP_POINTS_Q(false, 8); else if (qp == 4) PP_POINTS_Q(false, 4); else PP_POINTS_Q(false, 2); PP_IMAGES_Q(false); }
 #undef PP_POINTS_Q
 #undef PP_IMAGES_Q
     cur ^= 1;
@@ -1143,20 +919,13 @@ int PcgSolve(pp_ba_impl* h, double radius, int max_iterations, double eta, int* 
   int next_look = batch;
   PcgState* hs = h->pcg_state_host;
   hs->done = 0; hs->iter = 0; hs->status = kPcgRunning;
-  const char* fused_env = getenv("PPSFM_PCG_FUSED");
-  const char* wide_env0 = getenv("PPSFM_PCG_WIDE");
-  if (!group && !intr && !(fused_env && atoi(fused_env) == 0) && !(wide_env0 && atoi(wide_env0) == 0)) {
-    return PcgFusedRun(h, inv_radius, max_iterations, eta, iterations);
-  }
+  if (!group && !intr && h->sw.pcg_fused) return PcgFusedRun(h, inv_radius, max_iterations, eta, iterations);
   hipLaunchKernelGGL(k_pcg_block_inverse, dim3(CeilDiv(2 * C, 256)), dim3(256), 0, s, C, h->pcg_Sd, h->pcg_binv, h->d_flag);
   if (intr) hipLaunchKernelGGL(k_pcg_intr_inverse, dim3(CeilDiv(h->K, 64)), dim3(64), 0, s, h->K, h->intr_off, h->intr_nv, h->pcg_Scomp, h->pcg_binvI, h->d_flag);
   // the vector step: many workgroups (k_pcg_wide_a / _b, two launches) - 1100 images: 2460 -> 2860 LM it/s against the one-workgroup
   // kernel (12.5 us per step; 29.6 us at 4000 images, where it was the longest kernel of an iteration, against 6.1 + 4.4 us); 600 images
   // +6 %.  In a point-sharded group p . S p belongs to the all-reduced product: k_pcg_dot forms its per-image parts after the exchange.
-  // PPSFM_PCG_WIDE = 0 forces the one-workgroup kernel (tests compare the two).
-  const char* wide_env = getenv("PPSFM_PCG_WIDE");
-  const bool wide = intr || !(wide_env && atoi(wide_env) == 0);
-  int cur = 0;      // which copy of the state is current (wide: ping-pong; otherwise always 0)
+  int cur = 0;      // which copy of the state is current (ping-pong)
   auto wide_a = [&](int mode, int it) {
     hipLaunchKernelGGL(k_pcg_wide_a, dim3(G), dim3(kWideThreads), 0, s, mode, it, C, h->pcg_b, h->step_c, h->pcg_r, h->pcg_z, h->pcg_p, h->pcg_q, h->pcg_binv, h->pcg_dot,
                        h->pcg_state + cur, h->pcg_part, in);
@@ -1166,9 +935,7 @@ int PcgSolve(pp_ba_impl* h, double radius, int max_iterations, double eta, int* 
                        max_iterations, h->d_flag, in);
     cur ^= 1;
   };
-  if (wide) { wide_a(0, 0); wide_b(0, 0); }
-  else hipLaunchKernelGGL(k_pcg_vec, dim3(1), dim3(kVecThreads), 0, s, 0, 0, n, C, h->pcg_b, h->step_c, h->pcg_r, h->pcg_z, h->pcg_p, h->pcg_q, h->pcg_binv, h->pcg_dot,
-                          h->pcg_state, eta, max_iterations, h->d_flag);
+  wide_a(0, 0); wide_b(0, 0);
   // A point-sharded group (pp_ba_set_communicator / pp_ba_set_allreduce): every rank applies S to the same vector with ITS points'
   // observations (a point's observations all live on its owner, so the partial products simply add up), the products are summed over the
   // group - 6 C doubles per product, 24 KB at 500 images, against the 36 MB lower triangle the direct solver exchanges per LM iteration -
@@ -1192,22 +959,18 @@ int PcgSolve(pp_ba_impl* h, double radius, int max_iterations, double eta, int* 
     }
     if (group && rc_group == PP_OK) rc_group = BaGroupReduce(h, h->pcg_q, n, PP_REDUCE_SUM);
     // (the all-reduced product carries the intrinsics rows as well: n = 6 C + NI doubles; the cameras' parts of v . S v follow the images')
-    if (group && wide) hipLaunchKernelGGL(k_pcg_dot, dim3(CeilDiv(C + (intr ? h->K : 0), 256)), dim3(256), 0, s, C, v, h->pcg_q, h->pcg_dot, h->pcg_state + cur, intr ? h->K : 0,
+    if (group) hipLaunchKernelGGL(k_pcg_dot, dim3(CeilDiv(C + (intr ? h->K : 0), 256)), dim3(256), 0, s, C, v, h->pcg_q, h->pcg_dot, h->pcg_state + cur, intr ? h->K : 0,
                                           (const int32_t*)h->intr_off, (const int32_t*)h->intr_nv);
   };
   for (int it = 1; it <= cap; ++it) {
     apply(h->pcg_p);
     if (rc_group) { (void)hipStreamSynchronize(s); return rc_group; }      // (what is already enqueued reads the buffers the caller may free next)
     const bool reset = it % kResidualResetPeriod == 0;
-    if (wide) { wide_a(1, it); wide_b(reset ? 3 : 1, it); }
-    else hipLaunchKernelGGL(k_pcg_vec, dim3(1), dim3(kVecThreads), 0, s, 1, it, n, C, h->pcg_b, h->step_c, h->pcg_r, h->pcg_z, h->pcg_p, h->pcg_q, h->pcg_binv, (const double*)dotp,
-                            h->pcg_state, eta, max_iterations, h->d_flag);
+    wide_a(1, it); wide_b(reset ? 3 : 1, it);
     if (reset) {
       apply(h->step_c);
       if (rc_group) { (void)hipStreamSynchronize(s); return rc_group; }
-      if (wide) { wide_a(2, it); wide_b(1, it); }
-      else hipLaunchKernelGGL(k_pcg_vec, dim3(1), dim3(kVecThreads), 0, s, 2, it, n, C, h->pcg_b, h->step_c, h->pcg_r, h->pcg_z, h->pcg_p, h->pcg_q, h->pcg_binv, h->pcg_dot,
-                              h->pcg_state, eta, max_iterations, h->d_flag);
+      wide_a(2, it); wide_b(1, it);
     }
     if (it == next_look || it == cap) {
       PP_HIP_TRY(hipGetLastError());

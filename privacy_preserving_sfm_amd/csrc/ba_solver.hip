@@ -708,11 +708,6 @@ __global__ __launch_bounds__(256) void k_schur_self_chunks(SchurArgs a, const do
   if ((int)blockIdx.x < a.C) SchurSelfRhsBody(a, rec, blockIdx.x);
   else SchurChunksBody(rec, num_chunks, chunk, pair_entries, partials, (int64_t)blockIdx.x - a.C);
 }
-// the chunks alone (A/B: PPSFM_BA_CHUNK_SPLIT=1 launches the per-image part as k_schur_self_rhs and the chunks here, at their own register count)
-__global__ __launch_bounds__(256) void k_schur_chunks(const double* __restrict__ rec, int num_chunks, const int32_t* __restrict__ chunk,
-                                                      const int32_t* __restrict__ pair_entries, double* __restrict__ partials) {
-  SchurChunksBody(rec, num_chunks, chunk, pair_entries, partials, (int64_t)blockIdx.x);
-}
 template <bool kStore>      // kStore: the block is written, not accumulated into (pp_ba_impl::pairs_complete)
 __global__ __launch_bounds__(256) void k_schur_chunk_reduce(SchurArgs a, int64_t num_pairs, const int32_t* __restrict__ pair_ij, const int32_t* __restrict__ pair_chunk,
                                                             const double* __restrict__ partials) {
@@ -1251,7 +1246,7 @@ static int EnsureSolverBuffers(pp_ba_impl* h) {
   for (int i = 0; i < 2; ++i) if ((rc = PoolEventAcquire(&h->tev_eval[i], true))) return rc;
   if ((rc = PoolEventAcquire(&h->ev_readback, false))) return rc;
   if (h->iterative) return PcgEnsureBuffers(h);
-  if ((rc = CholeskyAuxCreate(&h->chol_aux))) return rc;
+  if ((rc = CholeskyAuxCreate(&h->chol_aux, h->sw))) return rc;
   PP_HIP_TRY(hipMemsetAsync(h->S, 0, sizeof(double) * (size_t)h->N * h->N, h->stream));
   if (h->sparse_tiles) {      // the factorisation and the assembly skip the tiles that stay zero
     const int T = h->N / 64;
@@ -1449,11 +1444,6 @@ static int AssembleReducedSystem(pp_ba_impl* h, double radius, bool refresh_diag
     return PP_OK;
   }
   if (h->pairs_chunked && h->num_pairs > 0) {      // long lists (few images, many shared points): chunks of the lists, then the blocks from their chunks
-    static const bool split = []() { const char* e = std::getenv("PPSFM_BA_CHUNK_SPLIT"); return e && std::atoi(e) != 0; }();
-    if (split) {
-      hipLaunchKernelGGL(k_schur_chunks, dim3(CeilDiv(h->small_num_chunks, 40)), dim3(256), 0, s, h->JpS, h->small_num_chunks, h->small_chunk, h->pair_entries, h->small_partials);
-      hipLaunchKernelGGL(k_schur_self_rhs, dim3(h->C), dim3(256), 0, s, a, h->JpS);
-    } else
     hipLaunchKernelGGL(k_schur_self_chunks, dim3(h->C + CeilDiv(h->small_num_chunks, 40)), dim3(256), 0, s, a, h->JpS, h->small_num_chunks, h->small_chunk, h->pair_entries,
                        h->small_partials);
     const dim3 grid(CeilDiv(36 * h->num_pairs, 256));
@@ -1514,7 +1504,7 @@ static int ReadScalars(pp_ba_impl* h) {
 // core per GPU, so after that the thread sleeps between polls (50 us naps: < 0.1 % of such an iteration).  Bounded: after ~2 s
 // without the ticket the stream is synchronised once and the ticket re-checked (a failed launch would otherwise wait forever).
 static int WaitTicket(pp_ba_impl* h, unsigned long long ticket) {
-  static const long spin_us = []() { const char* e = std::getenv("PPSFM_TICKET_SPIN_US"); return e ? std::atol(e) : 1500L; }();
+  const long spin_us = h->sw.ticket_spin_us;
   const volatile unsigned long long* t = reinterpret_cast<const volatile unsigned long long*>(h->h_scal) + kTicketSlot;
   const auto t0 = std::chrono::steady_clock::now();
   bool synced = false;
@@ -1654,7 +1644,7 @@ int pp_ba_get_structure(pp_ba_handle h, int32_t* info) try {
   // the chains of the one-launch factorisation (several: a nested-dissection order whose sub-trees are factorised side by side) and its chain steps
   info[6] = 1; info[7] = T;
   if (SparseActive(h) && T >= 4 && T <= 128 && !h->tile_nz.empty()) {
-    if (h->structure_steps < 0) h->structure_steps = CholeskyChainSteps(T, h->tile_nz.data(), &h->structure_chains);      // (planned once per handle; the plan itself is cached per tile map)
+    if (h->structure_steps < 0) h->structure_steps = CholeskyChainSteps(T, h->tile_nz.data(), h->sw, &h->structure_chains);      // (planned once per handle; the plan itself is cached per tile map)
     info[6] = h->structure_chains; info[7] = h->structure_steps;
   }
   return PP_OK;
@@ -1824,8 +1814,8 @@ int pp_ba_solve(pp_ba_handle h, const pp_ba_options* o, pp_ba_summary* sum) try 
     pending = false;
   };
   // (variable intrinsics take the fused step kernel - k_step_points<true>, the trial intrinsics applied before it - and keep the separate kernels otherwise)
-  const bool fused_step_allowed = !(getenv("PPSFM_BA_FUSED_STEP") && atoi(getenv("PPSFM_BA_FUSED_STEP")) == 0);
-  const bool fused_trial_cost = fold && (h->NI == 0 || fused_step_allowed) && !(getenv("PPSFM_BA_FUSED_TRIAL_COST") && atoi(getenv("PPSFM_BA_FUSED_TRIAL_COST")) == 0);
+  const bool fused_step_allowed = h->sw.ba_fused_step;
+  const bool fused_trial_cost = fold && (h->NI == 0 || fused_step_allowed) && h->sw.ba_fused_trial_cost;
   const bool fused_step = fused_trial_cost && fused_step_allowed;
   for (int iter = 1; sum->termination != PP_TERM_FAILURE && !user_stop; ++iter) {
     if (pending && (iter > o->max_num_iterations || radius < o->min_trust_region_radius)) {

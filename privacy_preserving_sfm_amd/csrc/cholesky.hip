@@ -1758,11 +1758,11 @@ struct ChainPlan {
   std::vector<uint8_t> map;      // empty: dense
   std::vector<int> time, rho1, chain_of;
 };
-static ChainPlan PlanChains(int T, const uint8_t* nz, int max_chains = kMaxChains) {
+static ChainPlan PlanChains(int T, const uint8_t* nz, const PlanSwitches& ps, int max_chains = kMaxChains) {
   ChainPlan p;
   std::memset(&p.cr, 0, sizeof(p.cr));
   std::vector<int> starts{0};
-  if (const char* e = getenv("PPSFM_CHOL_CHAINS")) max_chains = std::max(1, std::min(kMaxChains, atoi(e)));
+  if (ps.chains) max_chains = std::max(1, std::min(kMaxChains, *ps.chains));
   if (nz) {
     for (int k = 3; k + 4 <= T && (int)starts.size() < max_chains; ++k) {
       if (k - starts.back() < 3) continue;
@@ -1816,12 +1816,12 @@ static ChainPlan PlanChains(int T, const uint8_t* nz, int max_chains = kMaxChain
 // order in which every task only waits for earlier ones, so one pass suffices and the sorted list is a topological order by construction (for one chain
 // no key is ever raised: the list is what it was).
 struct TaskListInfo { bool fits = true; int scratch_tiles = 0; };      // fits: the scratch sequences found counters; scratch_tiles: slots of the scratch tile pool
-static std::vector<ChainTask> BuildTaskList(int T, const ChainPlan& plan, TaskListInfo* info = nullptr) {
+static std::vector<ChainTask> BuildTaskList(int T, const ChainPlan& plan, const PlanSwitches& ps, TaskListInfo* info = nullptr) {
   struct Item { double key; ChainTask t; };
   std::vector<Item> items;
   const uint8_t* nz = plan.map.empty() ? nullptr : plan.map.data();
   auto has = [&](int i, int j) { return i < T && j < T && (!nz || nz[(size_t)i * T + j] != 0); };
-  const int whole_from = getenv("PPSFM_CHOL_WHOLE_FROM") ? atoi(getenv("PPSFM_CHOL_WHOLE_FROM")) : WholeFrom(T);
+  const int whole_from = ps.whole_from ? *ps.whole_from : WholeFrom(T);
   const int nch = plan.cr.n;
   const double kNone = -1e30;
   // one SEQUENCE of updates per super-tile and accumulation target: the tiles themselves (panels of the chain that owns the super-tile's columns) or the
@@ -1850,8 +1850,8 @@ static std::vector<ChainTask> BuildTaskList(int T, const ChainPlan& plan, TaskLi
   auto sp = [&](int c, int row) -> int& { return solpost[(size_t)c * (T + 4) + row]; };
   auto rk = [&](int c, int row) -> double& { return rowkey[(size_t)c * (T + 4) + row]; };
   auto raised = [](double desired, std::initializer_list<double> deps) { double k = desired; for (double d : deps) k = std::max(k, d); return k; };
-  const bool two_panels = !nz && !(getenv("PPSFM_CHOL_TWO_PANELS") && atoi(getenv("PPSFM_CHOL_TWO_PANELS")) == 0);      // (two panels per task: dense systems)
-  const double slope = getenv("PPSFM_CHOL_SLOPE") ? atof(getenv("PPSFM_CHOL_SLOPE")) : kUpdateSlope;
+  const bool two_panels = !nz && ps.two_panels;      // (two panels per task: dense systems)
+  const double slope = ps.slope ? *ps.slope : kUpdateSlope;
   auto vp = [&](int I, int J) -> int& { return own[I * kMaxSuper + J].post; };
   auto vk = [&](int I, int J) -> double& { return own[I * kMaxSuper + J].key; };
   const std::vector<int>& time = plan.time;
@@ -2125,18 +2125,19 @@ static bool TaskListWaitsAreMet(int T, const ChainPlan& plan, const std::vector<
 }
 
 // plan + list for a tile map (null: dense); a plan of several chains whose list does not pass the replay falls back to ONE chain (the former behaviour)
-static ChainPlan PlanAndList(int T, const uint8_t* nz, std::vector<ChainTask>* list, bool* verified = nullptr, int* scratch_tiles = nullptr) {
-  ChainPlan plan = PlanChains(T, nz);
+static ChainPlan PlanAndList(int T, const uint8_t* nz, const PlanSwitches& ps, bool print, std::vector<ChainTask>* list, bool* verified = nullptr,
+                             int* scratch_tiles = nullptr) {
+  ChainPlan plan = PlanChains(T, nz, ps);
   TaskListInfo info;
-  *list = BuildTaskList(T, plan, &info);
+  *list = BuildTaskList(T, plan, ps, &info);
   bool ok = info.fits && TaskListWaitsAreMet(T, plan, *list);
   if (!ok && plan.cr.n > 1) {
     fprintf(stderr, "ppsfm: the task list of %d chains over %d block columns did not pass its replay - one chain\n", plan.cr.n, T);
-    plan = PlanChains(T, nz, 1);
-    *list = BuildTaskList(T, plan, &info);
+    plan = PlanChains(T, nz, ps, 1);
+    *list = BuildTaskList(T, plan, ps, &info);
     ok = TaskListWaitsAreMet(T, plan, *list);
   }
-  if (getenv("PPSFM_CHOL_PLAN_PRINT")) {      // (debugging aid: the chains and the closed tile map of the structure at hand)
+  if (print) {      // (debugging aid: the chains and the closed tile map of the structure at hand)
     fprintf(stderr, "ppsfm plan: T %d, %d chains:", T, plan.cr.n);
     for (int c = 0; c < plan.cr.n; ++c) fprintf(stderr, " [%d,%d)", plan.cr.begin[c], plan.cr.end[c]);
     fprintf(stderr, "\n");
@@ -2147,10 +2148,10 @@ static ChainPlan PlanAndList(int T, const uint8_t* nz, std::vector<ChainTask>* l
   return plan;
 }
 
-int CholeskyPlanSteps(int T, const uint8_t* nz, int* chains) {
+int CholeskyPlanSteps(int T, const uint8_t* nz, const Switches& sw, int* chains) {
   if (chains) *chains = 1;
   if (!nz || T < 4 || T > kMaxSteps) return T;
-  const ChainPlan plan = PlanChains(T, nz);
+  const ChainPlan plan = PlanChains(T, nz, sw.plan);
   if (chains) *chains = plan.cr.n;
   int steps = 0;
   for (int k = 0; k < T; ++k) steps = std::max(steps, plan.time[k] + 1);
@@ -2161,22 +2162,16 @@ int CholeskyPlanSteps(int T, const uint8_t* nz, int* chains) {
 static std::recursive_mutex g_setup_mutex;
 // Plans are kept process-wide, keyed on the tile map: the mapper builds a new BundleAdjuster per global bundle adjustment (src/sfm/incremental_mapper.cc:893-936)
 // and an unchanged structure (the dense list of a size; the same sequence a second time) must not pay the plan, the list and its replay again.
-struct CachedPlan { int T; std::vector<uint8_t> key; std::string knobs; ChainPlan plan; std::vector<ChainTask> list; bool verified; int scratch_tiles; };
-// the environment switches PlanChains / BuildTaskList read (tests and tools turn them): part of the key - a plan made under other switches is another plan
-// (without this the switches stopped doing anything once a matrix's plan was cached, and the tests that compare them compared a plan with itself)
-static std::string PlanKnobs() {
-  std::string k;
-  for (const char* name : {"PPSFM_CHOL_CHAINS", "PPSFM_CHOL_WHOLE_FROM", "PPSFM_CHOL_TWO_PANELS", "PPSFM_CHOL_SLOPE"}) { const char* e = getenv(name); k += e ? e : ""; k += '|'; }
-  return k;
-}
+// The planner's switches are part of the key: PlanChains / BuildTaskList read them from `ps` alone, and a plan made under other switches is another
+// plan (without this the switches stopped doing anything once a matrix's plan was cached, and the tests that compare them compared a plan with itself).
+struct CachedPlan { int T; std::vector<uint8_t> key; PlanSwitches ps; ChainPlan plan; std::vector<ChainTask> list; bool verified; int scratch_tiles; };
 static std::vector<CachedPlan> g_plan_cache;      // (guarded by g_setup_mutex, most recently used last)
 static constexpr size_t kPlanCacheEntries = 16, kPlanCacheBytes = (size_t)32 << 20;
-static const CachedPlan& PlanCached(int T, const uint8_t* nz) {
+static const CachedPlan& PlanCached(int T, const uint8_t* nz, const Switches& sw) {
   const size_t bytes = nz ? (size_t)T * T : 0;
-  const std::string knobs = PlanKnobs();
   for (size_t i = g_plan_cache.size(); i-- > 0;) {
     CachedPlan& c = g_plan_cache[i];
-    if (c.T == T && c.key.size() == bytes && c.knobs == knobs && (bytes == 0 || std::memcmp(c.key.data(), nz, bytes) == 0)) {
+    if (c.T == T && c.key.size() == bytes && c.ps == sw.plan && (bytes == 0 || std::memcmp(c.key.data(), nz, bytes) == 0)) {
       if (i + 1 != g_plan_cache.size()) std::rotate(g_plan_cache.begin() + i, g_plan_cache.begin() + i + 1, g_plan_cache.end());
       return g_plan_cache.back();
     }
@@ -2189,17 +2184,17 @@ static const CachedPlan& PlanCached(int T, const uint8_t* nz) {
   while (!g_plan_cache.empty() && (g_plan_cache.size() >= kPlanCacheEntries || held > kPlanCacheBytes)) { held -= bytes_of(g_plan_cache.front()); g_plan_cache.erase(g_plan_cache.begin()); }
   g_plan_cache.emplace_back();
   CachedPlan& c = g_plan_cache.back();
-  c.T = T; c.knobs = knobs;
+  c.T = T; c.ps = sw.plan;
   if (nz) c.key.assign(nz, nz + bytes);
-  c.plan = PlanAndList(T, nz, &c.list, &c.verified, &c.scratch_tiles);
+  c.plan = PlanAndList(T, nz, sw.plan, sw.chol_plan_print, &c.list, &c.verified, &c.scratch_tiles);
   return c;
 }
 
-int CholeskyChainSteps(int T, const uint8_t* nz, int* chains) {
+int CholeskyChainSteps(int T, const uint8_t* nz, const Switches& sw, int* chains) {
   if (chains) *chains = 1;
   if (!nz || T < 4 || T > kMaxSteps) return T;
   std::lock_guard<std::recursive_mutex> lock(g_setup_mutex);
-  const CachedPlan& cp = PlanCached(T, nz);      // (plan + list + replay, once per tile map: pp_ba_create's winner is what EnsureTaskList asks for next)
+  const CachedPlan& cp = PlanCached(T, nz, sw);      // (plan + list + replay, once per tile map: pp_ba_create's winner is what EnsureTaskList asks for next)
   if (chains) *chains = cp.plan.cr.n;
   int steps = 0;
   for (int k = 0; k < T; ++k) steps = std::max(steps, cp.plan.time[k] + 1);
@@ -2214,7 +2209,7 @@ static int EnsureTaskList(CholeskyAux* aux, int T, hipStream_t strm) {
   if (aux->tasks) { (void)hipFree(aux->tasks); aux->tasks = nullptr; }
   if (aux->tasks_nz) { (void)hipFree(aux->tasks_nz); aux->tasks_nz = nullptr; }
   std::lock_guard<std::recursive_mutex> lock(g_setup_mutex);
-  const CachedPlan& cp = PlanCached(T, src);
+  const CachedPlan& cp = PlanCached(T, src, aux->sw);
   const ChainPlan& plan = cp.plan;
   aux->tasks_T = T;
   aux->tasks_src_nz = src;
@@ -2249,7 +2244,7 @@ static int EnsureTaskList(CholeskyAux* aux, int T, hipStream_t strm) {
   std::memcpy(aux->chains, &plan.cr, sizeof(ChainRanges));
   aux->critical_path = 0;
   for (int k = 0; k < T; ++k) aux->critical_path = std::max(aux->critical_path, plan.time[k] + 1);
-  if (getenv("PPSFM_CHOL_DEBUG") && plan.cr.n > 1) {
+  if (aux->sw.chol_debug && plan.cr.n > 1) {
     fprintf(stderr, "ppsfm: %d chains over %d block columns, %d tasks, %d scratch tiles:", plan.cr.n, T, (int)cp.list.size(), cp.scratch_tiles);
     for (int c = 0; c < plan.cr.n; ++c) fprintf(stderr, " [%d,%d) t=%d..%d", plan.cr.begin[c], plan.cr.end[c], plan.time[plan.cr.begin[c]], plan.time[plan.cr.end[c] - 1]);
     fprintf(stderr, "\n");
@@ -2260,12 +2255,11 @@ static int EnsureTaskList(CholeskyAux* aux, int T, hipStream_t strm) {
 
 // the back substitution: pairs for a dense factor (k_backsub_prepare + k_backsub_pairs), block by block for a block-sparse one or a
 // small system.  Lw: where the factor's solved tiles live (S in per-column mode, the solved-tile array in task mode).
+// pairs = false (PPSFM_BACKSUB_PAIRS=0): block by block also for dense systems (what a block-sparse system always takes; tests compare the two)
 static void LaunchBacksub(const double* Lw, int N, int T, int rhs_row, double* Linv_ws, double* x_out, int32_t* d_flag, hipStream_t s, const uint8_t* nz,
-                          bool prepared = false) {
+                          bool pairs, bool prepared = false) {
   const int npairs = BacksubNumPairs(T);
-  const char* pairs_env = getenv("PPSFM_BACKSUB_PAIRS");      // 0: block by block also for dense systems (what a block-sparse system always takes; tests compare the two)
-  const bool pairs_off = pairs_env && atoi(pairs_env) == 0;
-  if (nz || npairs == 0 || pairs_off) {
+  if (nz || npairs == 0 || !pairs) {
     hipLaunchKernelGGL(k_backsub_all, dim3(T), dim3(256), 0, s, Lw, N, T, rhs_row, (const double*)Linv_ws, x_out, d_flag, nz);
     return;
   }
@@ -2289,10 +2283,7 @@ __global__ __launch_bounds__(kPanelThreads) void k_small_cholesky(const double* 
   __syncthreads();
   SmallFactorSolveTiles(tiles, inv_diag, xs, ys, flag, T, rhs_row, x_out);
 }
-static bool UseSmallCholesky(int N) {
-  static const bool enabled = []() { const char* e = getenv("PPSFM_CHOL_SMALL"); return !(e && atoi(e) == 0); }();
-  return enabled && N <= 2 * kNB;
-}
+static bool UseSmallCholesky(const CholeskyAux* aux, int N) { return (!aux || aux->sw.chol_small) && N <= 2 * kNB; }
 
 // enqueue the whole factorisation + solve on stream s
 // Linv_ws: [0, N*64) L_kk^-1 (row-major 64x64) of every diagonal block = the M_k mailboxes (solves + back substitution), then T+1
@@ -2302,7 +2293,7 @@ static bool UseSmallCholesky(int N) {
 static int EnqueueCholesky(double* S, int N, int rhs_row, double* Linv_ws, double* Lfac, double* x_out, int32_t* d_flag, hipStream_t s, CholeskyAux* aux) {
   const int T = N / kNB;
   const size_t tile = (size_t)kNB * kNB;
-  if (UseSmallCholesky(N) && x_out) {
+  if (UseSmallCholesky(aux, N) && x_out) {
     if (aux) aux->last_used = PP_LINSOLVE_CHOLESKY_COLUMNS;
     hipLaunchKernelGGL(k_small_cholesky, dim3(1), dim3(kPanelThreads), 0, s, (const double*)S, N, rhs_row, x_out, d_flag);
     PP_HIP_TRY(hipGetLastError());
@@ -2326,10 +2317,10 @@ static int EnqueueCholesky(double* S, int N, int rhs_row, double* Linv_ws, doubl
     // ONE launch: workgroup 0 = the chain, then the task list (see k_cholesky_tasks)
     // (test hook: with half of the task list missing the chain's wait for a prep task runs into its bound - the host must then repeat
     // the solve with per-column launches, tests/test_gpu_bundle_adjustment.py::test_task_mode_timeout_falls_back_to_column_launches)
-    const int grid_tasks = aux->test_drop_tasks ? aux->num_tasks / 2 : aux->num_tasks;
+    const int grid_tasks = aux->sw.chol_test_drop_tasks ? aux->num_tasks / 2 : aux->num_tasks;
     const uint8_t* nz = block_sparse ? (const uint8_t*)aux->tasks_nz : (const uint8_t*)nullptr;
     hipLaunchKernelGGL(k_cholesky_tasks, dim3(cr.n + grid_tasks), dim3(kPanelThreads), 0, s, S, Lfac, N, T, mb, d_flag, ctr, aux->tasks, nz, cr, aux->scratch);
-    LaunchBacksub(Lfac, N, T, rhs_row, Linv_ws, x_out, d_flag, s, nz, /*prepared=*/true);      // (dense: the kTaskPairPrep tasks of the launch above; block-sparse: block by block over the non-zero tiles)
+    LaunchBacksub(Lfac, N, T, rhs_row, Linv_ws, x_out, d_flag, s, nz, aux->sw.backsub_pairs, /*prepared=*/true);      // (dense: the kTaskPairPrep tasks of the launch above; block-sparse: block by block over the non-zero tiles)
     PP_HIP_TRY(hipGetLastError());
     return PP_OK;
   }
@@ -2357,7 +2348,7 @@ static int EnqueueCholesky(double* S, int N, int rhs_row, double* Linv_ws, doubl
     hipLaunchKernelGGL(k_column_step, dim3(1 + n_prep + nT + nW), dim3(kPanelThreads), 0, s, S, N, k, T, Linv_ws, xs, d_flag, skip_from, double_from,
                        (const int32_t*)nullptr, 0, 0, 0);
   }
-  LaunchBacksub(S, N, T, rhs_row, Linv_ws, x_out, d_flag, s, sparse ? (const uint8_t*)aux->sparse_nz : (const uint8_t*)nullptr);
+  LaunchBacksub(S, N, T, rhs_row, Linv_ws, x_out, d_flag, s, sparse ? (const uint8_t*)aux->sparse_nz : (const uint8_t*)nullptr, !aux || aux->sw.backsub_pairs);
   PP_HIP_TRY(hipGetLastError());
   return PP_OK;
 }
@@ -2385,7 +2376,7 @@ int CholeskySolveAugmented(double* S, int N, int rhs_row, double* Linv_ws, doubl
   // task mode is three launches: nothing to gain from a graph, and a capture is one thing less that can collide with whatever
   // other host threads do on the device meanwhile (a device-wide synchronize in another thread fails while any stream captures)
   const bool three_launches = aux && Lfac && UseTasks(aux->mode, N / kNB);
-  if (aux && aux->use_graph && !three_launches && !(UseSmallCholesky(N) && x_out)) {
+  if (aux && aux->use_graph && !three_launches && !(UseSmallCholesky(aux, N) && x_out)) {
     const bool same = aux->graph_exec && aux->g_S == S && aux->g_N == N && aux->g_rhs == rhs_row && aux->g_Linv == Linv_ws &&
                       aux->g_x == x_out && aux->g_flag == d_flag && aux->g_stream == s && aux->g_mode == aux->mode && aux->g_Lfac == Lfac &&
                       aux->g_sparse == (aux->sparse_lists != nullptr);
@@ -2418,17 +2409,14 @@ int CholeskySolveAugmented(double* S, int N, int rhs_row, double* Linv_ws, doubl
   return EnqueueCholesky(S, N, rhs_row, Linv_ws, Lfac, x_out, d_flag, s, aux);
 }
 
-int CholeskyAuxCreate(CholeskyAux* aux) {
+int CholeskyAuxCreate(CholeskyAux* aux, const Switches& sw) {
   // PPSFM_CHOL_MODE: "columns" = one launch per block column; "tasks" = the whole factorisation as one launch (k_cholesky_tasks,
   // bit-identical results); unset / "auto": tasks up to kTaskAutoMaxT block columns (0.73 against 0.84 ms at n = 3000, 0.35 against
   // 0.40 ms at n = 1500, 1.24 against 1.38 ms at n = 4030), per-column launches above (there the trailing update is the bound and
   // the per-column grid runs it in bigger, better balanced pieces)
-  if (aux->mode < 0) {
-    const char* e = getenv("PPSFM_CHOL_MODE");
-    aux->mode = !e ? 2 : ((e[0] == 't' || e[0] == '1') ? 1 : ((e[0] == 'c' || e[0] == '0') ? 0 : 2));
-  }
-  { const char* e = getenv("PPSFM_CHOL_GRAPH"); if (e && atoi(e) == 0) aux->use_graph = false; }
-  { const char* e = getenv("PPSFM_CHOL_TEST_DROP_TASKS"); aux->test_drop_tasks = e && atoi(e) != 0; }
+  aux->sw = sw;
+  if (aux->mode < 0) aux->mode = (int)sw.chol_mode;
+  if (!sw.chol_graph) aux->use_graph = false;
   return PP_OK;
 }
 void CholeskyAuxDestroy(CholeskyAux* aux) {
@@ -2451,7 +2439,8 @@ using namespace ppsfm;
 extern "C" int pp_cholesky_task_list(int32_t block_columns, int32_t* tasks, int64_t capacity, int64_t* count) try {
   PP_REQUIRE(block_columns >= 4 && block_columns <= kMaxSteps && count && (tasks || capacity == 0), "pp_cholesky_task_list: bad argument");
   std::vector<ChainTask> list;
-  (void)PlanAndList(block_columns, nullptr, &list);
+  const Switches sw = ReadSwitches();
+  (void)PlanAndList(block_columns, nullptr, sw.plan, sw.chol_plan_print, &list);
   *count = (int64_t)list.size();
   for (int64_t i = 0; i < (int64_t)list.size() && i < capacity; ++i) {
     tasks[4 * i] = list[i].type; tasks[4 * i + 1] = list[i].k; tasks[4 * i + 2] = list[i].a; tasks[4 * i + 3] = list[i].b;
@@ -2465,8 +2454,9 @@ extern "C" int pp_cholesky_task_list_sparse(int32_t block_columns, const uint8_t
   std::vector<uint8_t> closed(tile_nz, tile_nz + (size_t)T * T);
   (void)SymbolicTileFill(T, closed.data());
   std::vector<ChainTask> list;
-  const ChainPlan plan = PlanChains(T, closed.data(), 1);      // ONE chain (pp_cholesky_task_plan: as many as the structure has)
-  list = BuildTaskList(T, plan);
+  const PlanSwitches ps = ReadSwitches().plan;
+  const ChainPlan plan = PlanChains(T, closed.data(), ps, 1);      // ONE chain (pp_cholesky_task_plan: as many as the structure has)
+  list = BuildTaskList(T, plan, ps);
   if (map_out) std::memcpy(map_out, plan.map.data(), plan.map.size());
   *count = (int64_t)list.size();
   for (int64_t i = 0; i < (int64_t)list.size() && i < capacity; ++i) {
@@ -2483,9 +2473,10 @@ extern "C" int pp_cholesky_task_plan(int32_t block_columns, const uint8_t* tile_
   const int T = block_columns;
   std::vector<uint8_t> closed(tile_nz, tile_nz + (size_t)T * T);
   (void)SymbolicTileFill(T, closed.data());
-  const ChainPlan plan = PlanChains(T, closed.data(), max_chains > 0 ? max_chains : kMaxChains);
+  const PlanSwitches ps = ReadSwitches().plan;
+  const ChainPlan plan = PlanChains(T, closed.data(), ps, max_chains > 0 ? max_chains : kMaxChains);
   TaskListInfo info;
-  const std::vector<ChainTask> list = BuildTaskList(T, plan, &info);
+  const std::vector<ChainTask> list = BuildTaskList(T, plan, ps, &info);
   if (verified) *verified = (info.fits && TaskListWaitsAreMet(T, plan, list)) ? 1 : 0;
   if (map_out) std::memcpy(map_out, plan.map.data(), plan.map.size());
   if (chains_out) {
@@ -2527,14 +2518,14 @@ extern "C" int pp_dense_cholesky_solve(int32_t n, const double* A, const double*
       (rc = DeviceAlloc(&dx, (size_t)N)) || (rc = DeviceAlloc(&dflag, 4)) || (rc = DeviceAlloc(&dL, (size_t)N * N))) { cleanup(); return rc; }
   TRYH(hipEventCreate(&e0)); TRYH(hipEventCreate(&e1));
   TRYH(hipStreamCreateWithFlags(&strm, hipStreamNonBlocking));
-  if ((rc = CholeskyAuxCreate(&aux))) { cleanup(); return rc; }
+  const Switches sw = ReadSwitches();
+  if ((rc = CholeskyAuxCreate(&aux, sw))) { cleanup(); return rc; }
   // block-sparse input (PPSFM_CHOL_SPARSE=0 disables): tiles of the lower triangle that are entirely zero and stay zero in the
   // factor get no workgroup (the reference switches to SPARSE_SCHUR above 50 images, src/optim/bundle_adjustment.cc:275-286)
   std::vector<uint8_t> tile_nz;
   {
-    const char* e = getenv("PPSFM_CHOL_SPARSE");
     const int T = N / kNB;
-    if (!(e && atoi(e) == 0) && T >= 4) {
+    if (sw.chol_sparse && T >= 4) {
       tile_nz.assign((size_t)T * T, 0);
       for (int i = 0; i < N; ++i)
         for (int j = 0; j <= i; ++j)
@@ -2560,7 +2551,7 @@ extern "C" int pp_dense_cholesky_solve(int32_t n, const double* A, const double*
     TRYH(hipEventRecord(e1, strm));
     TRYH(hipEventSynchronize(e1));
     float ms = 0; TRYH(hipEventElapsedTime(&ms, e0, e1)); if (it >= 0) times.push_back(ms);
-    if (getenv("PPSFM_CHOL_DEBUG_SLOW") && ms > 5.0f) {      // (how the outliers described at `times` were caught)
+    if (sw.chol_debug_slow && ms > 5.0f) {      // (how the outliers described at `times` were caught)
       int32_t f4[4] = {0, 0, 0, 0};
       (void)hipMemcpy(f4, dflag, sizeof(f4), hipMemcpyDeviceToHost);
       fprintf(stderr, "SLOW dense solve: n=%d it=%d ms=%.3f mode=%d last_used=%d flag=%d %d %d %d\n", n, it, ms, aux.mode, aux.last_used, f4[0], f4[1], f4[2], f4[3]);

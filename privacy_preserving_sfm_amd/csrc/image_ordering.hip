@@ -411,9 +411,8 @@ struct GraphDissector {
 // 39 chain steps instead of ~25); beside their image's pose columns they belong to that image's part.  Returns n_v > 0 when EVERY image's camera is variable,
 // referenced by that image alone, with the same even number n_v of variable parameters (the pose blocks stay 16-byte aligned in the reduced system) - the
 // reduced system then has 6 + n_v columns per image and no tail -, 0 otherwise (variable intrinsics, if any, follow the pose columns).  PPSFM_BA_INTR_LAYOUT=tail: 0.
-int PrivateIntrinsicsColumns(const pp_ba_problem_desc* d) {
-  if (!d->camera_const_mask) return 0;
-  if (const char* e = std::getenv("PPSFM_BA_INTR_LAYOUT")) if (e[0] == 't' || e[0] == 'T') return 0;
+int PrivateIntrinsicsColumns(const pp_ba_problem_desc* d, IntrLayout layout) {
+  if (!d->camera_const_mask || layout == IntrLayout::Tail) return 0;
   const int C = d->num_poses, K = d->num_cameras;
   std::vector<int32_t> users(K, 0);
   for (int c = 0; c < C; ++c) users[d->pose_camera[c]]++;
@@ -487,55 +486,55 @@ static bool FillCoVisibility(const pp_ba_problem_desc* d, std::vector<uint64_t>*
   return true;
 }
 
+bool WillIterate(const pp_ba_problem_desc* d, LinearSolverSwitch sw) {
+  const int ls = sw == LinearSolverSwitch::Iterative ? PP_LINEAR_SOLVER_ITERATIVE_SCHUR : (sw == LinearSolverSwitch::Direct ? PP_LINEAR_SOLVER_DIRECT : d->linear_solver);
+  return ls == PP_LINEAR_SOLVER_ITERATIVE_SCHUR || (ls == PP_LINEAR_SOLVER_AUTO && d->num_poses > PP_MAX_NUM_IMAGES_DIRECT_SOLVER);
+}
+
 namespace {
-// what decides whether an order is looked for at all (before any graph is built)
+// what decides whether an order is looked for at all (before any graph is built).  PPSFM_BA_ORDERING: natural | rcm (forced even where it does not
+// pay: tests) | band (no dissection) | unset = by chain steps
 struct OrderingSetup {
   bool will_iterate, forced, candidate;
-  const char* eo;
   int Tt;
 };
-OrderingSetup SetupOf(const pp_ba_problem_desc* d, int NI) {
+OrderingSetup SetupOf(const pp_ba_problem_desc* d, int NI, const Switches& sw) {
   OrderingSetup u;
   const int C = d->num_poses;
-  int ls = d->linear_solver;
-  if (const char* e = std::getenv("PPSFM_BA_LINEAR_SOLVER")) ls = (e[0] == 'i' || e[0] == 'I') ? PP_LINEAR_SOLVER_ITERATIVE_SCHUR : ((e[0] == 'd' || e[0] == 'D') ? PP_LINEAR_SOLVER_DIRECT : ls);
-  u.will_iterate = ls == PP_LINEAR_SOLVER_ITERATIVE_SCHUR || (ls == PP_LINEAR_SOLVER_AUTO && C > PP_MAX_NUM_IMAGES_DIRECT_SOLVER);      // (as pp_ba_create's h->iterative)
-  const char* es = std::getenv("PPSFM_BA_SPARSE");
-  u.eo = std::getenv("PPSFM_BA_ORDERING");      // natural | rcm (forced even where it does not pay: tests) | band (no dissection) | unset = by chain steps
-  u.forced = u.eo && (u.eo[0] == 'r' || u.eo[0] == 'R');
+  u.will_iterate = WillIterate(d, sw.ba_linear_solver);
+  u.forced = sw.ba_ordering == OrderingSwitch::Rcm;
   u.Tt = ((6 * C + NI + 1 + 63) / 64);
-  u.candidate = d->ordering == PP_ORDERING_AUTO && !(u.eo && (u.eo[0] == 'n' || u.eo[0] == 'N')) && !u.will_iterate && C >= 3 &&
-                (u.forced || (!(es && std::atoi(es) == 0) && u.Tt >= 8));
+  u.candidate = d->ordering == PP_ORDERING_AUTO && sw.ba_ordering != OrderingSwitch::Natural && !u.will_iterate && C >= 3 &&
+                (u.forced || (sw.ba_sparse && u.Tt >= 8));
   return u;
 }
 }  // namespace
 
 // true when ChooseImageOrdering will build the co-visibility graph from the observations (pp_ba_create then hands it the graph's bits from the device,
 // pair_lists.hip CoVisibilityOnDevice, where the by-point lists are anyway)
-bool OrderingReadsObservations(const pp_ba_problem_desc* d, int NI) { return SetupOf(d, NI).candidate && !d->covisibility; }
+bool OrderingReadsObservations(const pp_ba_problem_desc* d, int NI, const Switches& sw) { return SetupOf(d, NI, sw).candidate && !d->covisibility; }
 
 // `graph_bits` (C x ceil(C / 64) words, bit j of row i for j < i: images i and j share a variable point, both variable) replaces the walk over the
 // observations when given.
-ImageOrdering ChooseImageOrdering(const pp_ba_problem_desc* d, int NI, const uint64_t* graph_bits) {
+ImageOrdering ChooseImageOrdering(const pp_ba_problem_desc* d, int NI, const Switches& sw, const uint64_t* graph_bits) {
   const auto t_begin = std::chrono::steady_clock::now();
   const int C = d->num_poses;
   ImageOrdering out;
-  const OrderingSetup setup = SetupOf(d, NI);
+  const OrderingSetup setup = SetupOf(d, NI, sw);
   const bool will_iterate = setup.will_iterate, forced = setup.forced, candidate = setup.candidate;
-  const char* eo = setup.eo;
   const int Tt = setup.Tt;
   // columns per image and what follows the images (the shared intrinsics blocks; none when every image carries its own)
-  const int nv_private = will_iterate ? 0 : PrivateIntrinsicsColumns(d);
+  const int nv_private = will_iterate ? 0 : PrivateIntrinsicsColumns(d, sw.ba_intr_layout);
   const int W6 = 6 + nv_private, tail0 = W6 * C, NI_tail = NI - nv_private * C;
   const Grain grain(W6);
   const int bias_images = 128 / W6;      // (two chain steps: see BestBandCut)
   auto finish = [&]() {
     out.plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    if (std::getenv("PPSFM_ORDER_DEBUG")) fprintf(stderr, "ppsfm: image ordering %.3f ms (%d images, %s)\n", out.plan_ms, C, out.dense_exit ? "co-visibility too dense: left early" : (out.old_of_new.empty() ? "caller's order" : "renumbered"));
+    if (sw.order_debug) fprintf(stderr, "ppsfm: image ordering %.3f ms (%d images, %s)\n", out.plan_ms, C, out.dense_exit ? "co-visibility too dense: left early" : (out.old_of_new.empty() ? "caller's order" : "renumbered"));
     return out;
   };
   if (!candidate) return finish();
-  const bool dbg = std::getenv("PPSFM_ORDER_DEBUG") != nullptr;
+  const bool dbg = sw.order_debug;
   auto lap = [&, last = t_begin](const char* what) mutable {
     if (!dbg) return;
     const auto now = std::chrono::steady_clock::now();
@@ -600,7 +599,7 @@ ImageOrdering ChooseImageOrdering(const pp_ba_problem_desc* d, int NI, const uin
   auto steps_of = [&](const std::vector<uint8_t>& nz, int nnz) {
     const bool sparse_path = (int64_t)nnz * 10 <= (int64_t)Tt * (Tt + 1) / 2 * 7;      // (SparseActive's threshold)
     last_chains = 1;
-    return sparse_path ? CholeskyPlanSteps(Tt, nz.data(), &last_chains) : Tt;
+    return sparse_path ? CholeskyPlanSteps(Tt, nz.data(), sw, &last_chains) : Tt;
   };
   double acc_map = 0, acc_steps = 0;
   auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -616,7 +615,7 @@ ImageOrdering ChooseImageOrdering(const pp_ba_problem_desc* d, int NI, const uin
   // solve stays bit-for-bit what it was)
   lap("cuthill-mckee + two tile maps");
   const bool take_rcm = !identity && (forced || (int64_t)out.nnz_ordered * 10 <= (int64_t)out.nnz_natural * 9);
-  const bool no_nd = eo && (eo[0] == 'r' || eo[0] == 'R' || eo[0] == 'b' || eo[0] == 'B');      // rcm (forced) / band (by tile count): the band order only
+  const bool no_nd = sw.ba_ordering == OrderingSwitch::Rcm || sw.ba_ordering == OrderingSwitch::Band;      // rcm (forced) / band (by tile count): the band order only
   struct Candidate { std::vector<int32_t> oon, noo; int steps = 0, nnz = 0, chains = 1; };
   Candidate base;      // the band (or the caller's order)
   base.nnz = take_rcm ? out.nnz_ordered : out.nnz_natural;
@@ -661,8 +660,7 @@ ImageOrdering ChooseImageOrdering(const pp_ba_problem_desc* d, int NI, const uin
     // parts re-ordered by their own Cuthill-McKee - find the same separators, and the graph's would only cost their milliseconds.  PPSFM_BA_GRAPH_ND=1 / 0: always / never)
     int best_band_steps = base.steps;
     for (const Candidate& c : ranked) best_band_steps = std::min(best_band_steps, c.steps);
-    const char* eg = std::getenv("PPSFM_BA_GRAPH_ND");
-    const bool graph_nd = eg ? std::atoi(eg) != 0 : best_band_steps * 10 > base.steps * 7;
+    const bool graph_nd = sw.ba_graph_nd >= 0 ? sw.ba_graph_nd != 0 : best_band_steps * 10 > base.steps * 7;
     for (int levels = 1; graph_nd && levels <= 4; ++levels) if (!consider(gd.Dissect(band, levels)) && levels > 1) break;
     lap("graph dissections");
     std::stable_sort(ranked.begin(), ranked.end(), [](const Candidate& a, const Candidate& b) { return a.steps != b.steps ? a.steps < b.steps : a.chains > b.chains; });
@@ -672,7 +670,7 @@ ImageOrdering ChooseImageOrdering(const pp_ba_problem_desc* d, int NI, const uin
   for (Candidate& c : ranked) {
     (void)tiles_map(&c.noo, &nzmap);
     int chains = 1;
-    const int steps = CholeskyChainSteps(Tt, nzmap.data(), &chains);
+    const int steps = CholeskyChainSteps(Tt, nzmap.data(), sw, &chains);
     if (chains == c.chains && steps == c.steps) { chosen = &c; break; }
   }
   lap("winner's list + replay");
@@ -694,10 +692,11 @@ extern "C" int pp_ba_plan_ordering(const pp_ba_problem_desc* d, int32_t* old_of_
     PP_REQUIRE(d->obs_pose[o] >= 0 && d->obs_pose[o] < C && d->obs_point[o] >= 0 && d->obs_point[o] < P, "pp_ba_plan_ordering: observation %lld indexes out of range", (long long)o);
   PP_REQUIRE(d->ordering >= PP_ORDERING_DEFAULT && d->ordering <= PP_ORDERING_AUTO, "pp_ba_plan_ordering: unknown ordering %d", d->ordering);
   const int NI = CountVariableIntrinsics(d);
-  const ImageOrdering ord = ChooseImageOrdering(d, NI);
+  const Switches sw = ReadSwitches();
+  const ImageOrdering ord = ChooseImageOrdering(d, NI, sw);
   const int Tt = (6 * C + NI + 1 + 63) / 64;
-  const bool iterate = d->linear_solver == PP_LINEAR_SOLVER_ITERATIVE_SCHUR || (d->linear_solver == PP_LINEAR_SOLVER_AUTO && C > PP_MAX_NUM_IMAGES_DIRECT_SOLVER);
-  const int nvp = iterate ? 0 : PrivateIntrinsicsColumns(d), W6 = 6 + nvp, tail0 = W6 * C, NI_tail = NI - nvp * C;
+  const bool iterate = WillIterate(d, LinearSolverSwitch::Descriptor);      // (the columns of the descriptor's solver, whatever PPSFM_BA_LINEAR_SOLVER says)
+  const int nvp = iterate ? 0 : PrivateIntrinsicsColumns(d, sw.ba_intr_layout), W6 = 6 + nvp, tail0 = W6 * C, NI_tail = NI - nvp * C;
   // the tile map of the order chosen -> chains and chain steps of its one-launch factorisation
   std::vector<uint8_t> nz((size_t)Tt * Tt, 0);
   {
@@ -720,7 +719,7 @@ extern "C" int pp_ba_plan_ordering(const pp_ba_problem_desc* d, int32_t* old_of_
   const int nnz = SymbolicTileFill(Tt, nz.data());
   const bool sparse_path = Tt >= 8 && (int64_t)nnz * 10 <= (int64_t)Tt * (Tt + 1) / 2 * 7;
   int chains = 1;
-  const int steps = sparse_path && Tt <= 128 ? CholeskyChainSteps(Tt, nz.data(), &chains) : Tt;
+  const int steps = sparse_path && Tt <= 128 ? CholeskyChainSteps(Tt, nz.data(), sw, &chains) : Tt;
   info[0] = ord.old_of_new.empty() ? 0 : 1; info[1] = ord.nnz_natural; info[2] = nnz; info[3] = chains; info[4] = steps; info[5] = Tt; info[6] = sparse_path ? 1 : 0; info[7] = NI;
   if (old_of_new) for (int c = 0; c < C; ++c) old_of_new[c] = ord.old_of_new.empty() ? c : ord.old_of_new[c];
   return PP_OK;

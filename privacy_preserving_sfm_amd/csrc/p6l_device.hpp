@@ -113,14 +113,11 @@ PP_HD double AberthRcp(double x) {
 }
 
 // All complex roots of the monic octic x^8 + a[7] x^7 + ... + a[0] by Aberth-Ehrlich.
-#if defined(__HIPCC__)
 // Sweep cap.  Measured on 16384 six-tuples (50 % outliers): with 40 sweeps every hypothesis returns the same number of models
 // as with 80 and only 3 differ by more than 1e-9 relative — the same 3 that also differ between 60 and 80 sweeps, i.e. lanes
 // that never converge (ill-conditioned octics) and whose result depends on the cap whatever it is.  A wavefront runs as long
-// as its slowest lane, so those lanes set the solver's time: 80 -> 40 sweeps halves it.  PPSFM_ABERTH_SWEEPS (read at
-// pp_pose_create) overrides the cap for experiments.
-__device__ int g_aberth_sweeps = 40;
-#endif
+// as its slowest lane, so those lanes set the solver's time: 80 -> 40 sweeps halves it.
+constexpr int kAberthSweeps = 40;
 PP_HD void AberthOctic(const double a[8], double zr[8], double zi[8]) {
   // initial circle: 0.7 * max_k |a_k|^(1/(8-k)) (half the Fujiwara bound); single precision is plenty
   float rad = 0.0f;
@@ -138,13 +135,8 @@ PP_HD void AberthOctic(const double a[8], double zr[8], double zi[8]) {
                         -0.34289780745545134, -0.9067021802217337, -0.9393727128473791, -0.4217714504102369};
 #pragma unroll
   for (int k = 0; k < 8; ++k) { zr[k] = radius * cs[k]; zi[k] = radius * sn[k]; }
-#if defined(__HIP_DEVICE_COMPILE__)
-  const int max_sweeps = g_aberth_sweeps;
-#else
-  const int max_sweeps = 40;
-#endif
 #pragma unroll 1
-  for (int it = 0; it < max_sweeps; ++it) {
+  for (int it = 0; it < kAberthSweeps; ++it) {
     double worst = 0.0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {

@@ -170,8 +170,9 @@ __global__ __launch_bounds__(256) void k_pl_bits(int C, int W, const int32_t* __
 
 }  // namespace
 
-bool PairListsOnDeviceEligible(int C, int64_t M) {
-  if (const char* e = std::getenv("PPSFM_BA_PAIR_LISTS")) { if (e[0] == 'h' || e[0] == 'H') return false; if (e[0] == 'd' || e[0] == 'D') return C <= 2048; }
+bool PairListsOnDeviceEligible(int C, int64_t M, PairListsSwitch sw) {
+  if (sw == PairListsSwitch::Host) return false;
+  if (sw == PairListsSwitch::Device) return C <= 2048;
   return M >= 50000 && C <= 2048;      // (the C x C table: 16 MB at 2048 images; below 50k observations the host builder is as fast as the launches + the read-back)
 }
 

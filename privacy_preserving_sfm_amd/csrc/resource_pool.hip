@@ -1,5 +1,6 @@
 // see resource_pool.hpp
 #include "resource_pool.hpp"
+#include "switches.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -26,12 +27,11 @@ struct Pool {
   bool poison = false;      // PPSFM_POOL_POISON=1 (debug): every block handed out - fresh or recycled - is filled with 0xFF bytes (NaN doubles, -1 ints), so a
                             // read-before-write sees garbage instead of whatever the previous handle left (recycled) or zeros (a fresh hipMalloc often is)
   Pool() {
-    const char* e = std::getenv("PPSFM_POOL_MAX_MB");
-    const long mb = e ? std::atol(e) : 1024;
+    const Switches sw = ReadSwitches();      // (once per process: the pool outlives every handle)
+    const long mb = sw.pool_max_mb;
     enabled = mb > 0;
     max_bytes = (size_t)(mb > 0 ? mb : 0) << 20;
-    const char* pz = std::getenv("PPSFM_POOL_POISON");
-    poison = pz && std::atoi(pz) != 0;
+    poison = sw.pool_poison;
   }
 };
 Pool& P() { static Pool* p = new Pool(); return *p; }      // (never destroyed: handles may outlive static destruction order)

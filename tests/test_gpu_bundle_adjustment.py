@@ -994,17 +994,15 @@ def test_forced_reordering_of_a_dense_scene_changes_nothing_visible(monkeypatch)
     assert np.array_equal(poses[5], sc["poses"][5]) and poses[9, 4] == sc["poses"][9, 4] and poses[9, 6] == sc["poses"][9, 6]
 
 
-@pytest.mark.parametrize("loss,wide,fused,track", [(0, "0", "1", 6), (2, "0", "1", 6), (0, "1", "0", 6), (2, "1", "0", 6), (0, "1", "1", 6), (2, "1", "1", 6),
-                                                   (2, "1", "1", 3), (0, "1", "1", 2)])
-def test_iterative_schur_pcg_follows_the_oracle(oracle, loss, wide, fused, track, monkeypatch):
+@pytest.mark.parametrize("loss,fused,track", [(0, "0", 6), (2, "0", 6), (0, "1", 6), (2, "1", 6), (2, "1", 3), (0, "1", 2)])
+def test_iterative_schur_pcg_follows_the_oracle(oracle, loss, fused, track, monkeypatch):
     """ITERATIVE_SCHUR + SCHUR_JACOBI (the reference's choice above 1000 images, bundle_adjustment.cc:283-286), forced on a small
     scene: the device applies the Schur complement matrix-free (ba_pcg.hip), the oracle runs the same restated Ceres CG loop on the
     explicit matrix.  Inexact steps: the LM trajectories agree iteration by iteration, and so do the conjugate-gradient counts.
-    wide: the vector step of an iteration spread over many workgroups (k_pcg_wide_a / _b, two launches and a ping-pong state: the
-    form a point-sharded group runs) or as ONE workgroup (k_pcg_vec, the first form), PPSFM_PCG_WIDE; fused (PPSFM_PCG_FUSED, the default): three
-    launches per iteration, the product kernels take the decision and form the direction themselves - four lanes per record, eight / four / two records of a point in flight (tracks of 6 / 3 / 2)."""
+    fused (PPSFM_PCG_FUSED, the default): three launches per iteration, the product kernels take the decision and form the direction themselves -
+    four lanes per record, eight / four / two records of a point in flight (tracks of 6 / 3 / 2); PPSFM_PCG_FUSED=0: the vector step of an iteration
+    spread over many workgroups (k_pcg_wide_a / _b, two launches and a ping-pong state: the form a point-sharded group runs)."""
     from privacy_preserving_sfm_amd.device import BAProblem, ba_options
-    monkeypatch.setenv("PPSFM_PCG_WIDE", wide)
     monkeypatch.setenv("PPSFM_PCG_FUSED", fused)
     sc = synthetic.make_ba_scene(60, {6: 1500, 3: 3000, 2: 6000}[track], track, seed=0xC0FFEE + 21, model=2, window=12)
     sc["loss_type"] = loss
@@ -1027,16 +1025,15 @@ def test_iterative_schur_pcg_follows_the_oracle(oracle, loss, wide, fused, track
 
 
 def test_iterative_schur_many_workgroup_vector_step_runs_the_same_loop(monkeypatch):
-    """1500 images: forced onto the one-workgroup kernel (PPSFM_PCG_WIDE=0) the loop runs the same iterations as with the default -
+    """1500 images: on the two-launch many-workgroup vector step (PPSFM_PCG_FUSED=0) the loop runs the same iterations as with the default -
     equal LM step pattern, conjugate-gradient counts within the rounding of the termination test, costs to 1e-7; the inner loops (eta = 1e-3)
     are long enough to cross the explicit-residual resets (every 10th CG iteration)."""
     from privacy_preserving_sfm_amd.device import BAProblem, ba_options
     sc = synthetic.make_ba_scene(1500, 20000, 6, seed=0xC0FFEE + 23, model=2)
     runs = []
-    # the default (three launches per iteration: the product kernels take the decision and form the direction), the two-launch
-    # many-workgroup vector step (PPSFM_PCG_FUSED=0: what a point-sharded group runs), the one-workgroup kernel
-    for wide, fused in (("1", "1"), ("1", "0"), ("0", "1")):
-        monkeypatch.setenv("PPSFM_PCG_WIDE", wide)
+    # the default (three launches per iteration: the product kernels take the decision and form the direction), then the two-launch
+    # many-workgroup vector step (PPSFM_PCG_FUSED=0: what a point-sharded group runs) - the anchor
+    for fused in ("1", "0"):
         monkeypatch.setenv("PPSFM_PCG_FUSED", fused)
         pb = BAProblem(sc)
         s = pb.solve(ba_options(max_num_iterations=5, eta=1e-3))      # (the iterations above rounding level: beyond them the inner loops count noise)
@@ -1054,13 +1051,12 @@ def test_iterative_schur_many_workgroup_vector_step_runs_the_same_loop(monkeypat
 
 
 def test_iterative_schur_iteration_cap_ends_both_vector_steps_alike(monkeypatch):
-    """max_linear_solver_iterations = 3: every inner loop ends at the cap (the iterate it has is the step, as in Ceres) - the many-workgroup
-    vector step and the one-workgroup kernel take that exit at the same iteration and give the same LM trajectory."""
+    """max_linear_solver_iterations = 3: every inner loop ends at the cap (the iterate it has is the step, as in Ceres) - the fused three-launch
+    iteration and the two-launch many-workgroup vector step take that exit at the same iteration and give the same LM trajectory."""
     from privacy_preserving_sfm_amd.device import BAProblem, ba_options
     sc = synthetic.make_ba_scene(60, 1500, 6, seed=0xC0FFEE + 24, model=2, window=12)
     runs = []
-    for wide, fused in (("1", "1"), ("1", "0"), ("0", "1")):      # three launches per iteration (default) / the two-launch vector step / one workgroup
-        monkeypatch.setenv("PPSFM_PCG_WIDE", wide)
+    for fused in ("1", "0"):      # three launches per iteration (default) / the two-launch vector step (the anchor)
         monkeypatch.setenv("PPSFM_PCG_FUSED", fused)
         pb = BAProblem(sc, linear_solver=2)
         s = pb.solve(ba_options(max_num_iterations=6, max_linear_solver_iterations=3, eta=1e-6))
