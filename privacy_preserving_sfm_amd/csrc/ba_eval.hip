@@ -264,7 +264,7 @@ int pp_ba_destroy(pp_ba_handle h) try {
                   h->small_chunk, h->small_pair_chunk, h->small_partials, h->spos, h->step_s, h->attach_slot};
   if (h->stream) (void)hipStreamSynchronize(h->stream);      // nothing of this handle is in flight when its blocks go back to the pool (resource_pool.hpp)
   for (void* b : bufs) if (b) PoolDeviceFree(b);
-  CholeskyAuxDestroy(&h->chol_aux);
+  CholeskyDestroy(h->chol);
   PcgFreeBuffers(h);
   for (int i = 0; i < 8; ++i) if (h->tev[i]) PoolEventRelease(h->tev[i], true);
   for (int i = 0; i < 2; ++i) if (h->tev_eval[i]) PoolEventRelease(h->tev_eval[i], true);
@@ -341,6 +341,7 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   // (a handle whose order and tile structure come from the caller's co-visibility - the union over the shards of a point-sharded group - lays out the
   // exchanged system like every other rank that was given the same matrix: it may join a group renumbered and block-sparse)
   h->sw = sw;
+  h->chol = CholeskyCreate(sw);
   h->structure_from_covisibility = d->covisibility != nullptr;
   h->device = device; h->C = C; h->P = P; h->K = K; h->M = M;
   h->loss_type = d->loss_type; h->loss_scale = d->loss_scale;
@@ -976,7 +977,7 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
 int pp_ba_get_create_profile(pp_ba_handle h, double* ms) try {
   PP_REQUIRE(h && ms, "pp_ba_get_create_profile: null argument");
   for (int i = 0; i < 6; ++i) ms[i] = h->create_ms[i];
-  ms[4] = h->chol_aux.plan_ms;      // (the task plan is made with the solver buffers, at the first solve or attach)
+  ms[4] = CholeskyPlanMs(h->chol);      // (the task plan is made with the solver buffers, at the first solve or attach)
   return PP_OK;
 } PP_API_CATCH("pp_ba_get_create_profile")
 

@@ -32,38 +32,6 @@ __device__ __forceinline__ const double* RecT(const double* rec, size_t o) { ret
 __device__ __forceinline__ const double* RecJ(const double* rec, size_t o) { return rec + kRecStride * o + 6; }
 __device__ __forceinline__ const double* RecX(const double* rec, size_t o) { return rec + kRecStride * o + 18; }
 #endif
-struct ChainTask;
-// launch-structure state of the dense Cholesky (cholesky.hip)
-struct CholeskyAux {
-  Switches sw;                      // the owner's snapshot (CholeskyAuxCreate): the planner's switches, the back substitution, the small-system kernel
-  int mode = -1;                    // -1: not yet created (CholeskyAuxCreate: PPSFM_CHOL_MODE); 1 = task mode (one launch), 0 = one launch per block column, 2 = by size
-  bool use_graph = true;            // capture the launch structure once, replay per solve
-  hipGraphExec_t graph_exec = nullptr;
-  double *g_S = nullptr, *g_Linv = nullptr, *g_x = nullptr, *g_Lfac = nullptr;
-  int32_t* g_flag = nullptr;
-  int g_N = 0, g_rhs = 0, g_mode = -1;
-  hipStream_t g_stream = nullptr;
-  struct ChainTask* tasks = nullptr;      // task mode: the sorted task list for tasks_T block columns (device memory)
-  int num_tasks = 0, tasks_T = 0;
-  bool tasks_rejected = false;            // the list for (tasks_T, tasks_src_nz) did not pass its host replay: per-column launches for this structure
-  const uint8_t* tasks_src_nz = nullptr;  // the tile map (tile_nz) the list was built for (null: dense)
-  uint8_t* tasks_nz = nullptr;            // device: that map + the two sub-diagonals, closed under fill-in (what the one-launch kernel and its back substitution skip by)
-  int32_t chains[1 + 3 * 16] = {1};       // the chains of the task list (ChainRanges of cholesky.hip: n, begin[16], end[16], post[16])
-  double* scratch = nullptr;              // several chains: pool of 64 x 64 tiles in which a chain accumulates for another chain's tiles
-  int scratch_tiles = 0;
-  int critical_path = 0;                  // block-column steps on the longest dependency path of the list (T for one chain)
-  double plan_ms = 0;                     // host time of the last EnsureTaskList (plan, list, replay, upload; a cache hit: the upload)
-  // block-sparse factor: tile_nz = tile_T x tile_T bytes (lower triangle, closed under fill-in; owned by the caller, null = dense);
-  // from it: the per-launch row / super-tile lists (host + device copies) and the byte map on the device
-  const uint8_t* tile_nz = nullptr;
-  int tile_T = 0, sparse_T = 0, sparse_base_rows = 0, sparse_base_sups = 0;
-  std::vector<int32_t> sparse_host;
-  int32_t* sparse_lists = nullptr;
-  uint8_t* sparse_nz = nullptr;
-  bool g_sparse = false;
-  int last_used = -1;               // launch structure of the last enqueued solve: PP_LINSOLVE_CHOLESKY_* (pp_ba_summary::linear_solver)
-  int fallbacks = 0;                // one-launch factorisations that ran into a bounded wait and were repeated per column (pp_ba_summary::cholesky_fallbacks)
-};
 // closes a T x T lower-triangular tile map under the fill-in of a Cholesky factorisation (in place); returns the number of non-zero tiles
 int SymbolicTileFill(int T, uint8_t* nz);
 // chain steps of the one-launch factorisation of a T x T tile map (closed under fill-in): the block columns on the longest dependency path when its
@@ -93,13 +61,12 @@ void BuildPairListsOnHost(int C, int P, int64_t M, const int32_t* pt_start, cons
 int CoVisibilityOnDevice(int C, int64_t M, const int32_t* d_pt_start, const int32_t* d_pt_obs, const int32_t* d_obs_pose, const int32_t* d_obs_point,
                          const uint8_t* d_pose_const, const uint8_t* d_point_const, hipStream_t s, std::vector<uint64_t>* bits);
 int PrivateIntrinsicsColumns(const pp_ba_problem_desc* d, IntrLayout layout);      // n_v > 0: every image carries its own n_v variable intrinsics beside its pose columns (image_ordering.hip)
-int CholeskyAuxCreate(CholeskyAux* aux, const Switches& sw);
-void CholeskyAuxDestroy(CholeskyAux* aux);
 }  // namespace ppsfm
 
 namespace ppsfm {
 // state of the conjugate-gradient loop of an iterative handle (ba_pcg.hip): device copy + pinned host mirror
 struct PcgState { double rho, Q0, norm_b, alpha; int32_t iter, done, status, pad_; };
+struct CholeskyState;      // the dense Cholesky's launch path and its device lists (cholesky.hip; the functions below)
 }  // namespace ppsfm
 
 struct pp_ba_impl {
@@ -230,7 +197,7 @@ struct pp_ba_impl {
   double* Spack = nullptr;                  // lower triangle + rhs row of S, packed for the group all-reduce
   hipEvent_t tev[8] = {nullptr};
   hipEvent_t tev_eval[2] = {nullptr, nullptr};   // deferred timing of the evaluation at an accepted point
-  ppsfm::CholeskyAux chol_aux;
+  ppsfm::CholeskyState* chol = nullptr;      // (pp_ba_create; bound to S and its workspaces by ApplyLinearSolverStructure)
 };
 
 namespace ppsfm {
@@ -255,11 +222,22 @@ int IntrAssemble(pp_ba_impl* h, double inv_radius, int add_diagonal);   // rows 
 // L_kk^-1 blocks (= the M_k mailboxes), three more mailbox arrays of T + 1 slots (X, D, solved X), the progress counters of task mode
 // ... and the pair inverses / pair couplings of the paired back substitution (one + four tiles per pair of block columns)
 inline size_t CholeskyWorkspaceDoubles(int N) { return (size_t)(4 * (N / 64) + 3) * 64 * 64 + 8192 + (size_t)(N / 128 + 1) * 5 * 64 * 64; }
-// Lfac: N x N array for the solved tiles of task mode (the factor ends up there); null = per-column mode only
 std::recursive_mutex& DeviceSetupMutex();      // held while a handle allocates / uploads / captures its graph: none of that may run beside another host thread's capture
-bool CholeskyWantsFactorArray(const CholeskyAux* aux, int N);      // the one-launch mode would be used for this size (it needs Lfac); block-sparse systems never do
-int CholeskyPrepare(CholeskyAux* aux, int N, bool has_factor_array, hipStream_t s);      // device lists for this size (done by the first solve otherwise)
-int CholeskySolveAugmented(double* S, int N, int rhs_row, double* Linv_ws, double* Lfac, double* x_out, int32_t* d_flag, hipStream_t s, CholeskyAux* aux);
+// The system a CholeskyState factorises: S (N x N, rhs in row rhs_row), the workspace Linv_ws, Lfac (N x N solved tiles of the one-launch path,
+// where its factor ends up; null = per-column launches only), the solution x, the failure flags, the stream
+struct CholeskySystem { double* S; int N, rhs_row; double *Linv_ws, *Lfac, *x; int32_t* flag; hipStream_t stream; };
+CholeskyState* CholeskyCreate(const Switches& sw);
+void CholeskyDestroy(CholeskyState* st);
+bool CholeskyNeedsFactorArray(const CholeskyState* st, int N);      // the one-launch path can run at this size: asked before the bind (Lfac is allocated only then)
+// decides the launch path for `sys` and the tile map (closed under fill-in, owned by the caller; null = dense), builds its device lists (a solve allocates
+// nothing) and drops any captured graph; *map_changed: the map differs from the previous bind's
+int CholeskyBind(CholeskyState* st, const CholeskySystem& sys, const uint8_t* tile_nz, bool* map_changed = nullptr);
+int CholeskySolve(CholeskyState* st);      // the bound path: its graph (captured by the first solve after a bind) or its launches
+bool CholeskyFallBackToColumns(CholeskyState* st);      // a bounded wait of the one-launch path ran out (flag bit 4): per-column launches from here on, counted; false: already so
+void CholeskyDisableGraph(CholeskyState* st);      // enqueue eagerly from now on (a host all-reduce callback)
+int CholeskyLinsolve(const CholeskyState* st);     // the bound path as PP_LINSOLVE_CHOLESKY_* (pp_ba_summary::linear_solver)
+int CholeskyFallbacks(const CholeskyState* st);    // pp_ba_summary::cholesky_fallbacks
+double CholeskyPlanMs(const CholeskyState* st);    // host time of the last task-list set-up (plan, list, replay, upload; a cache hit: the upload)
 // the group exchange of a point-sharded handle (ba_solver.hip): true inside a group; in-place reduction of `count` doubles on the handle's stream
 bool BaInGroup(const pp_ba_impl* h);
 int BaGroupReduce(pp_ba_impl* h, double* ptr, int64_t count, int op);

@@ -15,7 +15,7 @@
 //        k_schur_pairs        off-diagonal blocks by GATHER: six lanes per 6x6 block pair (i,j), ten pairs per
 //                             wavefront, each walking the precomputed list of observation pairs that share a point
 //                             (pairs ordered by list length) — deterministic, no fp64 atomics
-//   K3b  CholeskySolveAugmented   dense fp64 MFMA Cholesky of S (cholesky.hip)
+//   K3b  CholeskySolve        dense fp64 MFMA Cholesky of S (cholesky.hip)
 //   K3c  k_step_points        point steps, -(J d)^T (r + J d / 2), the trial point x (+) d (quaternion Plus) and the COST at the trial point in one
 //                             pass over the observations (four lanes per point; every observation applies the step to its own pose).
 //                             With variable intrinsics or a host-callback group: k_backsub_points, k_model_cost_apply and K1 in
@@ -1205,28 +1205,22 @@ static bool InGroup(const pp_ba_impl* h) { return h->comm != nullptr || h->allre
 // So the block-sparse path is only taken outside a group; attaching / detaching a communicator or callback switches it.
 // (inside a point-sharded group only when the tile map is the group's: built from the union co-visibility every rank was given, pp_ba_problem_desc::covisibility)
 static bool SparseActive(const pp_ba_impl* h) { return h->sparse_tiles && (!InGroup(h) || h->structure_from_covisibility); }
-// (re)binds the factorisation's launch structure to the handle's current state: the tile map (or none), the solved-tile array of the
-// one-launch mode (allocated only when that mode can run: N x N doubles, 7 GB at 5000 images), the per-size device lists
+// (re)binds the factorisation to the handle's current state: the tile map (or none) and the solved-tile array of the one-launch path
+// (allocated only when that path can run: N x N doubles, 7 GB at 5000 images)
 static int ApplyLinearSolverStructure(pp_ba_impl* h) {
   if (!h->S || h->iterative) return PP_OK;      // EnsureSolverBuffers calls this once the buffers exist; an iterative handle has no factorisation
   // the setters that end up here (pp_ba_set_communicator / pp_ba_set_allreduce) may be called, after a solve, from a host thread whose
   // current device is another one: the allocations below belong on the handle's device
   PP_HIP_TRY(hipSetDevice(h->device));
   std::lock_guard<std::recursive_mutex> setup_lock(DeviceSetupMutex());
-  ppsfm::CholeskyAux* aux = &h->chol_aux;
-  const uint8_t* want = SparseActive(h) ? h->tile_nz.data() : nullptr;
-  if (aux->tile_nz != want) {
-    PP_HIP_TRY(hipStreamSynchronize(h->stream));
-    if (aux->graph_exec) { (void)hipGraphExecDestroy(aux->graph_exec); aux->graph_exec = nullptr; }
-    if (aux->sparse_lists) { (void)hipFree(aux->sparse_lists); aux->sparse_lists = nullptr; }
-    if (aux->sparse_nz) { (void)hipFree(aux->sparse_nz); aux->sparse_nz = nullptr; }
-    aux->sparse_T = 0;
-    aux->tile_nz = want; aux->tile_T = want ? h->N / 64 : 0;
-    // whatever an earlier factorisation left outside the tiles the new structure rewrites
-    PP_HIP_TRY(hipMemsetAsync(h->S, 0, sizeof(double) * (size_t)h->N * h->N, h->stream));
-  }
-  if (!h->Lfac && CholeskyWantsFactorArray(aux, h->N)) { const int rc = HandleAlloc(&h->Lfac, (size_t)h->N * h->N); if (rc) return rc; }
-  return CholeskyPrepare(aux, h->N, h->Lfac != nullptr, h->stream);
+  if (!h->Lfac && CholeskyNeedsFactorArray(h->chol, h->N)) { const int rc = HandleAlloc(&h->Lfac, (size_t)h->N * h->N); if (rc) return rc; }
+  // (the solution comes out in the reduced system's column order: the vectors' order unless the intrinsics sit beside their images' pose columns)
+  const CholeskySystem sys{h->S, h->N, h->n_red, h->Linv, h->Lfac, h->spos_identity ? h->step_c : h->step_s, h->d_flag, h->stream};
+  bool new_map = false;
+  { const int rc = CholeskyBind(h->chol, sys, SparseActive(h) ? h->tile_nz.data() : nullptr, &new_map); if (rc) return rc; }
+  // whatever an earlier factorisation left outside the tiles the new structure rewrites
+  if (new_map) PP_HIP_TRY(hipMemsetAsync(h->S, 0, sizeof(double) * (size_t)h->N * h->N, h->stream));
+  return PP_OK;
 }
 
 static int EnsureSolverBuffers(pp_ba_impl* h) {
@@ -1246,7 +1240,6 @@ static int EnsureSolverBuffers(pp_ba_impl* h) {
   for (int i = 0; i < 2; ++i) if ((rc = PoolEventAcquire(&h->tev_eval[i], true))) return rc;
   if ((rc = PoolEventAcquire(&h->ev_readback, false))) return rc;
   if (h->iterative) return PcgEnsureBuffers(h);
-  if ((rc = CholeskyAuxCreate(&h->chol_aux, h->sw))) return rc;
   PP_HIP_TRY(hipMemsetAsync(h->S, 0, sizeof(double) * (size_t)h->N * h->N, h->stream));
   if (h->sparse_tiles) {      // the factorisation and the assembly skip the tiles that stay zero
     const int T = h->N / 64;
@@ -1608,10 +1601,7 @@ int pp_ba_set_allreduce(pp_ba_handle h, pp_allreduce_fn fn, void* ctx, int32_t g
   h->group_rank = fn ? group_rank : 0; h->group_size = fn ? group_size : 1;
   // a host callback is where other host threads do device-wide things (allocate, synchronize) while this handle would be capturing
   // its factorisation graph, and the callback's own synchronisation per LM iteration dwarfs what the graph saves: enqueue eagerly
-  if (fn) {
-    h->chol_aux.use_graph = false;
-    if (h->chol_aux.graph_exec) { (void)hipGraphExecDestroy(h->chol_aux.graph_exec); h->chol_aux.graph_exec = nullptr; }
-  }
+  if (fn) CholeskyDisableGraph(h->chol);
   return ApplyLinearSolverStructure(h);      // (a block-sparse tile map made from the shard's own observations is rank-local: not used inside a group)
 } PP_API_CATCH("pp_ba_set_allreduce")
 
@@ -1835,8 +1825,7 @@ int pp_ba_solve(pp_ba_handle h, const pp_ba_options* o, pp_ba_summary* sum) try 
       if ((rc = PcgSolve(h, radius, o->max_linear_solver_iterations, o->eta, &cg))) return rc;
       h->linear_solver_iterations += cg;
     } else {
-      // (the solution comes out in the reduced system's column order: the vectors' order unless the intrinsics sit beside their images' pose columns)
-      if ((rc = CholeskySolveAugmented(h->S, h->N, h->n_red, h->Linv, h->Lfac, h->spos_identity ? h->step_c : h->step_s, h->d_flag, s, &h->chol_aux))) return rc;
+      if ((rc = CholeskySolve(h->chol))) return rc;
       if (!h->spos_identity) hipLaunchKernelGGL(k_gather_step, dim3(CeilDiv(h->n_red, 256)), dim3(256), 0, s, h->n_red, h->spos, h->step_s, h->step_c);
     }
     t2.Mark(PP_BA_T_CHOLESKY);
@@ -1913,12 +1902,9 @@ int pp_ba_solve(pp_ba_handle h, const pp_ba_options* o, pp_ba_summary* sum) try 
     const double step_norm = std::sqrt(h->h_scal[kStepNorm2]), x_norm = std::sqrt(h->h_scal[kXNorm2]);
     bool valid = HostFlag(h) == 0 && std::isfinite(model_change) && model_change > 0.0 && std::isfinite(step_norm);
     if (HostFlag(h) != 0) PP_HIP_TRY(hipMemsetAsync(h->d_flag, 0, sizeof(int32_t), s));
-    if ((HostFlag(h) & 4) && h->chol_aux.mode != 0) {
+    if ((HostFlag(h) & 4) && CholeskyFallBackToColumns(h->chol)) {
       // a bounded wait of the one-launch factorisation (k_cholesky_tasks) ran out: nothing wrong with the system - the same step again
       // with one launch per block column, which this handle then stays with
-      h->chol_aux.mode = 0;
-      ++h->chol_aux.fallbacks;
-      if (h->chol_aux.graph_exec) { (void)hipGraphExecDestroy(h->chol_aux.graph_exec); h->chol_aux.graph_exec = nullptr; }
       PP_HIP_TRY(hipMemsetAsync(h->S, 0, sizeof(double) * (size_t)h->N * h->N, s));      // (the assembly relies on the zero padding it never rewrites; the aborted run may have touched it)
       if ((rc = undo_speculation(true))) return rc;
       --iter;
@@ -1987,8 +1973,8 @@ int pp_ba_solve(pp_ba_handle h, const pp_ba_options* o, pp_ba_summary* sum) try 
   const int neff = h->num_effective_pose_point + h->NI;     // (three synchronous read-backs of the masks per solve before: ~50 us)
   sum->num_effective_parameters = neff;
   sum->linear_solver_iterations = h->linear_solver_iterations;
-  sum->linear_solver = h->iterative ? PP_LINSOLVE_PCG : h->chol_aux.last_used < 0 ? (SparseActive(h) ? PP_LINSOLVE_CHOLESKY_SPARSE : (h->Lfac ? PP_LINSOLVE_CHOLESKY_TASKS : PP_LINSOLVE_CHOLESKY_COLUMNS)) : h->chol_aux.last_used;
-  sum->cholesky_fallbacks = h->chol_aux.fallbacks;
+  sum->linear_solver = h->iterative ? PP_LINSOLVE_PCG : CholeskyLinsolve(h->chol);
+  sum->cholesky_fallbacks = CholeskyFallbacks(h->chol);
   return sum->termination == PP_TERM_FAILURE ? PP_ERR_NUMERIC : PP_OK;
 } PP_API_CATCH("pp_ba_solve")
 

@@ -8,13 +8,18 @@
 // factor's row rhs_row is y = L^-1 b, i.e. the forward substitution is performed by the
 // factorisation itself.  Rows beyond rhs_row are identity padding.
 //
-// Two launch structures over the same work items (same arithmetic per 16x16 piece, bitwise equal results up to 48 block columns):
-//   task mode     (k_cholesky_tasks, default up to 64 block columns) the whole factorisation in ONE launch: a persistent chain
+// Four launch paths, chosen in ONE place (ChoosePath) when a system is bound (CholeskyBind) and when a bounded wait of task mode runs out
+// (CholeskyFallBackToColumns); a solve (CholeskySolve) only enqueues or replays what was chosen:
+//   small         (k_small_cholesky, 1 or 2 block columns) one launch of one workgroup, the tiles in LDS;
+//   task mode     (k_cholesky_tasks, 4 to 128 block columns, dense or block-sparse) the whole factorisation in ONE launch: a persistent chain
 //                 workgroup + one workgroup per item of a priority-sorted task list, per-tile dependency counters, mailbox
 //                 hand-offs - see "task mode" below; a block-sparse system whose elimination tree has independent sub-trees (a nested-dissection
 //                 order of the cameras, ba_eval.hip DissectBand) gets a chain workgroup per sub-tree - see "ChainRanges";
-//   column mode   (k_column_step, above 64 block columns and for a block-sparse system) one launch per block column:
-// Right-looking blocked algorithm, 64 x 64 blocks, ONE launch per block column (k_column_step, see there):
+//   column mode   (k_column_step: 3 or more than 128 block columns, PPSFM_CHOL_MODE=columns, a task list that failed its host replay, and
+//                 after a fallback) one launch per block column, over every tile or, for a block-sparse system, over its non-zero tiles only
+//                 (the per-launch lists of EnsureSparseLists); captured into a graph once per bind and replayed.
+// Task and column mode run the same work items (same arithmetic per 16x16 piece, bitwise equal results up to 48 block columns).
+// Column mode: right-looking blocked algorithm, 64 x 64 blocks, ONE launch per block column (k_column_step, see there):
 // a chain workgroup (solve of the tile X left of the next diagonal block, that block's update by X X', its
 // factorisation and the 64x64 INVERSE of the new diagonal factor) runs in the same grid as a prep workgroup (applies
 // the panel-k update to the NEXT launch's chain inputs, X into a staging tile) and the bulk work that only depends
@@ -1691,16 +1696,44 @@ int SymbolicTileFill(int T, uint8_t* nz) {
   return count;
 }
 
+enum class CholPath { Small, Tasks, Columns, SparseColumns };      // the launch path of a bound system (ChoosePath)
+
+struct CholeskyState {
+  explicit CholeskyState(const Switches& s) : sw(s), columns(s.chol_columns), use_graph(s.chol_graph) {}
+  Switches sw;                      // the owner's snapshot: the planner's switches, the back substitution, the small-system kernel
+  bool columns = false;             // per-column launches only: PPSFM_CHOL_MODE=columns, or after a fallback (CholeskyFallBackToColumns)
+  bool use_graph = true;            // capture the launch structure once per bind, replay per solve (off: PPSFM_CHOL_GRAPH=0, CholeskyDisableGraph, a failed capture)
+  CholeskySystem sys{};             // the bound system
+  const uint8_t* tile_nz = nullptr; // the bound tile map (owned by the caller, null = dense)
+  CholPath path = CholPath::Columns;
+  bool capture = false;             // the bound path is replayed from a graph
+  hipGraphExec_t graph_exec = nullptr;
+  ChainTask* tasks = nullptr;             // the one-launch path: the sorted task list for tasks_T block columns (device memory)
+  int num_tasks = 0, tasks_T = 0;
+  bool tasks_rejected = false;            // the list for (tasks_T, tasks_src_nz) did not pass its host replay: per-column launches for this structure
+  const uint8_t* tasks_src_nz = nullptr;  // the tile map the list was built for (null: dense)
+  uint8_t* tasks_nz = nullptr;            // device: that map + the two sub-diagonals, closed under fill-in (what the one-launch kernel and its back substitution skip by)
+  ChainRanges chains{};                   // the chains of the task list
+  double* scratch = nullptr;              // several chains: pool of 64 x 64 tiles in which a chain accumulates for another chain's tiles
+  int scratch_tiles = 0;
+  double plan_ms = 0;                     // host time of the last EnsureTaskList (plan, list, replay, upload; a cache hit: the upload)
+  // block-sparse per-column launches: the per-launch row / super-tile lists of tile_nz (host + device copies) and the byte map on the device
+  int sparse_T = 0, sparse_base_rows = 0, sparse_base_sups = 0;
+  std::vector<int32_t> sparse_host;
+  int32_t* sparse_lists = nullptr;
+  uint8_t* sparse_nz = nullptr;
+  int fallbacks = 0;                // one-launch factorisations that ran into a bounded wait and were repeated per column (pp_ba_summary::cholesky_fallbacks)
+};
+
 // Block-sparse structure: tile_nz (T x T, lower triangle, row-major; the caller has already closed it under the fill-in of
 // the factorisation) -> per launch k the rows of the solve workgroups and the super-tiles of the update workgroups.
-// Layout of aux->sparse_host: [T+1 offsets of the row lists | T+1 offsets of the super-tile lists | the lists]; the same
+// Layout of st->sparse_host: [T+1 offsets of the row lists | T+1 offsets of the super-tile lists | the lists]; the same
 // array on the device, plus the T x T byte map for the back substitution.
-static int EnsureSparseLists(CholeskyAux* aux, int T, hipStream_t strm) {
-  if (!aux->tile_nz || aux->tile_T != T) return PP_OK;
-  if (aux->sparse_lists && aux->sparse_T == T) return PP_OK;
-  if (aux->sparse_lists) { (void)hipFree(aux->sparse_lists); aux->sparse_lists = nullptr; }
-  if (aux->sparse_nz) { (void)hipFree(aux->sparse_nz); aux->sparse_nz = nullptr; }
-  const uint8_t* nz = aux->tile_nz;
+static int EnsureSparseLists(CholeskyState* st, int T, hipStream_t strm) {
+  if (st->sparse_lists && st->sparse_T == T) return PP_OK;
+  if (st->sparse_lists) { (void)hipFree(st->sparse_lists); st->sparse_lists = nullptr; }
+  if (st->sparse_nz) { (void)hipFree(st->sparse_nz); st->sparse_nz = nullptr; }
+  const uint8_t* nz = st->tile_nz;
   auto has = [&](int i, int j) { return i < T && j < T && nz[(size_t)i * T + j] != 0; };
   std::vector<int32_t> rows, sups, row_off(T + 1, 0), sup_off(T + 1, 0);
   for (int k = 0; k + 1 < T; ++k) {
@@ -1723,28 +1756,27 @@ static int EnsureSparseLists(CholeskyAux* aux, int T, hipStream_t strm) {
     }
   }
   for (int k = T - 1; k <= T; ++k) { row_off[k] = (int32_t)rows.size(); sup_off[k] = (int32_t)sups.size(); }
-  aux->sparse_host.clear();
-  aux->sparse_host.insert(aux->sparse_host.end(), row_off.begin(), row_off.end());
-  aux->sparse_host.insert(aux->sparse_host.end(), sup_off.begin(), sup_off.end());
-  const int base_rows = (int)aux->sparse_host.size();
-  aux->sparse_host.insert(aux->sparse_host.end(), rows.begin(), rows.end());
-  const int base_sups = (int)aux->sparse_host.size();
-  aux->sparse_host.insert(aux->sparse_host.end(), sups.begin(), sups.end());
-  aux->sparse_base_rows = base_rows; aux->sparse_base_sups = base_sups;
-  PP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&aux->sparse_lists), sizeof(int32_t) * std::max<size_t>(aux->sparse_host.size(), 1)));
-  PP_HIP_TRY(hipMemcpyAsync(aux->sparse_lists, aux->sparse_host.data(), sizeof(int32_t) * aux->sparse_host.size(), hipMemcpyHostToDevice, strm));
-  PP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&aux->sparse_nz), (size_t)T * T));
-  PP_HIP_TRY(hipMemcpyAsync(aux->sparse_nz, nz, (size_t)T * T, hipMemcpyHostToDevice, strm));
+  st->sparse_host.clear();
+  st->sparse_host.insert(st->sparse_host.end(), row_off.begin(), row_off.end());
+  st->sparse_host.insert(st->sparse_host.end(), sup_off.begin(), sup_off.end());
+  const int base_rows = (int)st->sparse_host.size();
+  st->sparse_host.insert(st->sparse_host.end(), rows.begin(), rows.end());
+  const int base_sups = (int)st->sparse_host.size();
+  st->sparse_host.insert(st->sparse_host.end(), sups.begin(), sups.end());
+  st->sparse_base_rows = base_rows; st->sparse_base_sups = base_sups;
+  PP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st->sparse_lists), sizeof(int32_t) * std::max<size_t>(st->sparse_host.size(), 1)));
+  PP_HIP_TRY(hipMemcpyAsync(st->sparse_lists, st->sparse_host.data(), sizeof(int32_t) * st->sparse_host.size(), hipMemcpyHostToDevice, strm));
+  PP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st->sparse_nz), (size_t)T * T));
+  PP_HIP_TRY(hipMemcpyAsync(st->sparse_nz, nz, (size_t)T * T, hipMemcpyHostToDevice, strm));
   PP_HIP_TRY(hipStreamSynchronize(strm));      // (the caller's stream, not the legacy one: another host thread may be capturing its own factorisation)
-  aux->sparse_T = T;
+  st->sparse_T = T;
   return PP_OK;
 }
 
-// The task list of task mode for T block columns: PrepX / PrepD / solve / update tasks sorted by priority (see above); built once
-// per matrix size, outside any stream capture.
-constexpr int kTaskAutoMaxT = kMaxSteps;      // (round 2: 88 - equal at n = 6000, slower at 8000; with the two-panel updates of round 3: n = 3000 0.68 against 0.83 ms,
-                                              // 4000 1.08 / 1.36, 6000 2.57 / 3.00, 8000 5.53 / 5.96 - tools/chol_time.py)
-static bool UseTasks(int mode, int T) { return T >= 4 && T <= kMaxSteps && (mode == 1 || (mode == 2 && T <= kTaskAutoMaxT)); }
+// The sizes of the one-launch path, dense or block-sparse: up to kMaxSteps block columns, the whole range of its counter arrays (round 2 stopped at 88 - equal
+// at n = 6000, slower at 8000; with the two-panel updates of round 3: n = 3000 0.68 against 0.83 ms, 4000 1.08 / 1.36, 6000 2.57 / 3.00, 8000 5.53 / 5.96 -
+// tools/chol_time.py)
+static bool UseTasks(int T) { return T >= 4 && T <= kMaxSteps; }
 
 // The chains of a tile map (see ChainRanges), the map the one-launch mode works with, and the ORDER in which its block columns are eliminated:
 //   map      the caller's (already closed under fill-in) plus, inside every chain, the two sub-diagonals - the tiles the chain and the prep tasks own at
@@ -2201,55 +2233,53 @@ int CholeskyChainSteps(int T, const uint8_t* nz, const Switches& sw, int* chains
   return steps;
 }
 
-static int EnsureTaskList(CholeskyAux* aux, int T, hipStream_t strm) {
-  const bool block_sparse = aux->tile_nz && aux->tile_T == T;
-  const uint8_t* src = block_sparse ? aux->tile_nz : nullptr;
-  if (aux->tasks_T == T && aux->tasks_src_nz == src && (aux->tasks || aux->tasks_rejected)) return PP_OK;
+// The task list of the one-launch path for T block columns and the bound tile map: PrepX / PrepD / solve / update tasks sorted by priority (see above);
+// built once per structure (CholeskyBind), outside any stream capture.
+static int EnsureTaskList(CholeskyState* st, int T, hipStream_t strm) {
+  const uint8_t* src = st->tile_nz;
+  if (st->tasks_T == T && st->tasks_src_nz == src && (st->tasks || st->tasks_rejected)) return PP_OK;
   const auto t0 = std::chrono::steady_clock::now();
-  if (aux->tasks) { (void)hipFree(aux->tasks); aux->tasks = nullptr; }
-  if (aux->tasks_nz) { (void)hipFree(aux->tasks_nz); aux->tasks_nz = nullptr; }
+  if (st->tasks) { (void)hipFree(st->tasks); st->tasks = nullptr; }
+  if (st->tasks_nz) { (void)hipFree(st->tasks_nz); st->tasks_nz = nullptr; }
   std::lock_guard<std::recursive_mutex> lock(g_setup_mutex);
-  const CachedPlan& cp = PlanCached(T, src, aux->sw);
+  const CachedPlan& cp = PlanCached(T, src, st->sw);
   const ChainPlan& plan = cp.plan;
-  aux->tasks_T = T;
-  aux->tasks_src_nz = src;
-  aux->tasks_rejected = !cp.verified;
+  st->tasks_T = T;
+  st->tasks_src_nz = src;
+  st->tasks_rejected = !cp.verified;
   if (!cp.verified) {
     // a list whose host replay finds a wait that no earlier task meets is not launched at all (it would run into the device's bounded waits):
     // this structure is factorised by per-column launches over its tile lists
     fprintf(stderr, "ppsfm: the one-launch task list of %d block columns (%s) did not pass its replay - per-column launches for this structure\n", T, src ? "block-sparse" : "dense");
-    aux->num_tasks = 0;
-    aux->plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->num_tasks = 0;
+    st->plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PP_OK;
   }
-  if (block_sparse) {
-    PP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&aux->tasks_nz), plan.map.size()));
-    PP_HIP_TRY(hipMemcpyAsync(aux->tasks_nz, plan.map.data(), plan.map.size(), hipMemcpyHostToDevice, strm));
+  if (src) {
+    PP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st->tasks_nz), plan.map.size()));
+    PP_HIP_TRY(hipMemcpyAsync(st->tasks_nz, plan.map.data(), plan.map.size(), hipMemcpyHostToDevice, strm));
   }
   // (measured and dropped in round 6, PPSFM_CHOL_QUIET_XCD: an empty task at every list position whose workgroup lands on the chain's XCD - a quieter L2 /
   // fabric port for the chain, a seventh less of the chip for the bulk: 705-720 -> 721-731 us per factorisation + back substitution, 809 -> 824 us per LM iteration)
   const std::vector<ChainTask>* to_upload = &cp.list;
-  PP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&aux->tasks), sizeof(ChainTask) * to_upload->size()));
+  PP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st->tasks), sizeof(ChainTask) * to_upload->size()));
   // (on the caller's stream, not the legacy one: another host thread may be capturing its own factorisation just now)
-  PP_HIP_TRY(hipMemcpyAsync(aux->tasks, to_upload->data(), sizeof(ChainTask) * to_upload->size(), hipMemcpyHostToDevice, strm));
+  PP_HIP_TRY(hipMemcpyAsync(st->tasks, to_upload->data(), sizeof(ChainTask) * to_upload->size(), hipMemcpyHostToDevice, strm));
   PP_HIP_TRY(hipStreamSynchronize(strm));
-  aux->num_tasks = (int)to_upload->size();
+  st->num_tasks = (int)to_upload->size();
   // several chains: the pool of 64 x 64 scratch tiles in which a chain accumulates for another chain's tiles
-  if (cp.scratch_tiles > aux->scratch_tiles) {
-    if (aux->scratch) { PoolDeviceFree(aux->scratch); aux->scratch = nullptr; aux->scratch_tiles = 0; }      // (recycled blocks: resource_pool.hpp)
-    { const int rc = PoolDeviceAlloc(reinterpret_cast<void**>(&aux->scratch), sizeof(double) * (size_t)cp.scratch_tiles * kNB * kNB); if (rc) return rc; }
-    aux->scratch_tiles = cp.scratch_tiles;
+  if (cp.scratch_tiles > st->scratch_tiles) {
+    if (st->scratch) { PoolDeviceFree(st->scratch); st->scratch = nullptr; st->scratch_tiles = 0; }      // (recycled blocks: resource_pool.hpp)
+    { const int rc = PoolDeviceAlloc(reinterpret_cast<void**>(&st->scratch), sizeof(double) * (size_t)cp.scratch_tiles * kNB * kNB); if (rc) return rc; }
+    st->scratch_tiles = cp.scratch_tiles;
   }
-  static_assert(sizeof(aux->chains) == sizeof(ChainRanges), "CholeskyAux::chains holds a ChainRanges");
-  std::memcpy(aux->chains, &plan.cr, sizeof(ChainRanges));
-  aux->critical_path = 0;
-  for (int k = 0; k < T; ++k) aux->critical_path = std::max(aux->critical_path, plan.time[k] + 1);
-  if (aux->sw.chol_debug && plan.cr.n > 1) {
+  st->chains = plan.cr;
+  if (st->sw.chol_debug && plan.cr.n > 1) {
     fprintf(stderr, "ppsfm: %d chains over %d block columns, %d tasks, %d scratch tiles:", plan.cr.n, T, (int)cp.list.size(), cp.scratch_tiles);
     for (int c = 0; c < plan.cr.n; ++c) fprintf(stderr, " [%d,%d) t=%d..%d", plan.cr.begin[c], plan.cr.end[c], plan.time[plan.cr.begin[c]], plan.time[plan.cr.end[c] - 1]);
     fprintf(stderr, "\n");
   }
-  aux->plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  st->plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return PP_OK;
 }
 
@@ -2283,18 +2313,19 @@ __global__ __launch_bounds__(kPanelThreads) void k_small_cholesky(const double* 
   __syncthreads();
   SmallFactorSolveTiles(tiles, inv_diag, xs, ys, flag, T, rhs_row, x_out);
 }
-static bool UseSmallCholesky(const CholeskyAux* aux, int N) { return (!aux || aux->sw.chol_small) && N <= 2 * kNB; }
 
-// enqueue the whole factorisation + solve on stream s
+// enqueue the whole factorisation + solve of the bound system, its path as CholeskyBind chose it
 // Linv_ws: [0, N*64) L_kk^-1 (row-major 64x64) of every diagonal block = the M_k mailboxes (solves + back substitution), then T+1
 // staging slots for the chain's X tile (per-column mode uses two of them in turn; task mode: one mailbox per step), then the D and
 // solved-X mailboxes of task mode (T+1 slots each), then the progress counters of task mode.
-// Lfac (may be null): the solved-tile array of task mode, N x N like S.
-static int EnqueueCholesky(double* S, int N, int rhs_row, double* Linv_ws, double* Lfac, double* x_out, int32_t* d_flag, hipStream_t s, CholeskyAux* aux) {
-  const int T = N / kNB;
+// Lfac: the solved-tile array of task mode, N x N like S.
+static int EnqueueCholesky(const CholeskyState& st) {
+  double *S = st.sys.S, *Linv_ws = st.sys.Linv_ws, *Lfac = st.sys.Lfac, *x_out = st.sys.x;
+  int32_t* d_flag = st.sys.flag;
+  const hipStream_t s = st.sys.stream;
+  const int N = st.sys.N, rhs_row = st.sys.rhs_row, T = N / kNB;
   const size_t tile = (size_t)kNB * kNB;
-  if (UseSmallCholesky(aux, N) && x_out) {
-    if (aux) aux->last_used = PP_LINSOLVE_CHOLESKY_COLUMNS;
+  if (st.path == CholPath::Small) {
     hipLaunchKernelGGL(k_small_cholesky, dim3(1), dim3(kPanelThreads), 0, s, (const double*)S, N, rhs_row, x_out, d_flag);
     PP_HIP_TRY(hipGetLastError());
     return PP_OK;
@@ -2305,22 +2336,18 @@ static int EnqueueCholesky(double* S, int N, int rhs_row, double* Linv_ws, doubl
   int32_t* ctr = reinterpret_cast<int32_t*>(mb.xsol + (size_t)(T + 1) * tile);
   mb.Pw = Linv_ws + (size_t)(4 * T + 3) * tile + 8192;      // behind the mailboxes and the counters (CholeskyWorkspaceDoubles)
   mb.Zw = mb.Pw + (size_t)BacksubNumPairs(T) * tile;
-  const bool block_sparse = aux && aux->tile_nz && aux->tile_T == T;
-  const bool tasks = aux && UseTasks(aux->mode, T) && Lfac && aux->tasks && aux->tasks_T == T && aux->tasks_src_nz == (block_sparse ? aux->tile_nz : nullptr);
-  const bool sparse = !tasks && aux && aux->sparse_lists && aux->sparse_T == T;      // (per-column launches over the non-zero tiles: above 128 block columns, or after a fallback)
-  if (aux) aux->last_used = block_sparse ? PP_LINSOLVE_CHOLESKY_SPARSE : (tasks ? PP_LINSOLVE_CHOLESKY_TASKS : PP_LINSOLVE_CHOLESKY_COLUMNS);
-  ChainRanges cr = OneChain(T);
-  if (tasks) std::memcpy(&cr, aux->chains, sizeof(cr));
+  const bool tasks = st.path == CholPath::Tasks, sparse = st.path == CholPath::SparseColumns;
+  const ChainRanges cr = tasks ? st.chains : OneChain(T);
   hipLaunchKernelGGL(k_potrf64, dim3(tasks ? 64 + cr.n : 1), dim3(kPanelThreads), 0, s, S, N, Linv_ws, xs, d_flag, x_out, tasks ? Lfac : S, ctr, (int)kNumCounters, Linv_ws,
                      (long long)((size_t)(4 * T + 3) * tile), cr);
   if (tasks) {
     // ONE launch: workgroup 0 = the chain, then the task list (see k_cholesky_tasks)
     // (test hook: with half of the task list missing the chain's wait for a prep task runs into its bound - the host must then repeat
     // the solve with per-column launches, tests/test_gpu_bundle_adjustment.py::test_task_mode_timeout_falls_back_to_column_launches)
-    const int grid_tasks = aux->sw.chol_test_drop_tasks ? aux->num_tasks / 2 : aux->num_tasks;
-    const uint8_t* nz = block_sparse ? (const uint8_t*)aux->tasks_nz : (const uint8_t*)nullptr;
-    hipLaunchKernelGGL(k_cholesky_tasks, dim3(cr.n + grid_tasks), dim3(kPanelThreads), 0, s, S, Lfac, N, T, mb, d_flag, ctr, aux->tasks, nz, cr, aux->scratch);
-    LaunchBacksub(Lfac, N, T, rhs_row, Linv_ws, x_out, d_flag, s, nz, aux->sw.backsub_pairs, /*prepared=*/true);      // (dense: the kTaskPairPrep tasks of the launch above; block-sparse: block by block over the non-zero tiles)
+    const int grid_tasks = st.sw.chol_test_drop_tasks ? st.num_tasks / 2 : st.num_tasks;
+    const uint8_t* nz = st.tile_nz ? (const uint8_t*)st.tasks_nz : (const uint8_t*)nullptr;
+    hipLaunchKernelGGL(k_cholesky_tasks, dim3(cr.n + grid_tasks), dim3(kPanelThreads), 0, s, S, Lfac, N, T, mb, d_flag, ctr, st.tasks, nz, cr, st.scratch);
+    LaunchBacksub(Lfac, N, T, rhs_row, Linv_ws, x_out, d_flag, s, nz, st.sw.backsub_pairs, /*prepared=*/true);      // (dense: the kTaskPairPrep tasks of the launch above; block-sparse: block by block over the non-zero tiles)
     PP_HIP_TRY(hipGetLastError());
     return PP_OK;
   }
@@ -2338,99 +2365,104 @@ static int EnqueueCholesky(double* S, int N, int rhs_row, double* Linv_ws, doubl
     int skip_from = kNever, double_from = pending_double;
     pending_double = kNever;
     if (sparse) {      // block-sparse: only the structurally non-zero tiles get a workgroup (no deferred pairs)
-      const int32_t* h = aux->sparse_host.data();
+      const int32_t* h = st.sparse_host.data();
       const int nTs = h[k + 1] - h[k], nWs = h[T + 1 + k + 1] - h[T + 1 + k];
       hipLaunchKernelGGL(k_column_step, dim3(1 + n_prep + nTs + nWs), dim3(kPanelThreads), 0, s, S, N, k, T, Linv_ws, xs, d_flag, kNever, kNever,
-                         (const int32_t*)aux->sparse_lists, aux->sparse_base_rows + h[k], nTs, aux->sparse_base_sups + h[T + 1 + k]);
+                         (const int32_t*)st.sparse_lists, st.sparse_base_rows + h[k], nTs, st.sparse_base_sups + h[T + 1 + k]);
       continue;
     }
     if (double_from == kNever && k >= 1 && nsup > kDeferAbove && k + 6 < T && k + 2 < T - 1) { skip_from = k + 6; pending_double = k + 6; }
     hipLaunchKernelGGL(k_column_step, dim3(1 + n_prep + nT + nW), dim3(kPanelThreads), 0, s, S, N, k, T, Linv_ws, xs, d_flag, skip_from, double_from,
                        (const int32_t*)nullptr, 0, 0, 0);
   }
-  LaunchBacksub(S, N, T, rhs_row, Linv_ws, x_out, d_flag, s, sparse ? (const uint8_t*)aux->sparse_nz : (const uint8_t*)nullptr, !aux || aux->sw.backsub_pairs);
+  LaunchBacksub(S, N, T, rhs_row, Linv_ws, x_out, d_flag, s, sparse ? (const uint8_t*)st.sparse_nz : (const uint8_t*)nullptr, st.sw.backsub_pairs);
   PP_HIP_TRY(hipGetLastError());
   return PP_OK;
 }
 
-// The launch structure is static for a given (S, N, ...): ~190 dependent launches on two streams.  It is
-// captured ONCE into a hipGraph and replayed per LM iteration (host launch cost would otherwise bound
-// the ~35 us steps of the critical path).  Falls back to eager enqueueing if capture is unavailable.
 // Allocations, uploads and the graph capture of one handle must not run beside the capture of another host thread's handle
 // (a hipMalloc from thread B invalidates thread A's capture in progress): one process-wide lock around both.
 std::recursive_mutex& DeviceSetupMutex() { return g_setup_mutex; }
 
-bool CholeskyWantsFactorArray(const CholeskyAux* aux, int N) { return aux && UseTasks(aux->mode, N / kNB); }
+CholeskyState* CholeskyCreate(const Switches& sw) { return new CholeskyState(sw); }
+static void DropGraph(CholeskyState* st) { if (st->graph_exec) (void)hipGraphExecDestroy(st->graph_exec); st->graph_exec = nullptr; }
+void CholeskyDestroy(CholeskyState* st) {
+  if (!st) return;
+  DropGraph(st);
+  if (st->tasks) (void)hipFree(st->tasks);
+  if (st->tasks_nz) (void)hipFree(st->tasks_nz);
+  if (st->scratch) PoolDeviceFree(st->scratch);
+  if (st->sparse_lists) (void)hipFree(st->sparse_lists);
+  if (st->sparse_nz) (void)hipFree(st->sparse_nz);
+  delete st;
+}
+bool CholeskyNeedsFactorArray(const CholeskyState* st, int N) { return !st->columns && UseTasks(N / kNB); }
 
-// the per-size device lists (task list, block-sparse lists): at buffer set-up, so that a solve allocates nothing
-int CholeskyPrepare(CholeskyAux* aux, int N, bool has_factor_array, hipStream_t s) {
-  if (!aux) return PP_OK;
+// The one place the launch path is chosen (a bind, a fallback; the paths: top of this file).  The per-column launches (~190 dependent ones) are
+// captured ONCE per bind into a hipGraph and replayed per LM iteration: host launch cost would otherwise bound the ~35 us steps of the critical path.
+// Not captured: the small path (one launch) and any system the one-launch path is eligible for, even when its list failed the replay (three launches:
+// nothing to gain, and a capture is one thing less that can collide with whatever other host threads do on the device meanwhile - a device-wide
+// synchronize in another thread fails while any stream captures).
+static void ChoosePath(CholeskyState* st) {
+  const bool one_launch = st->sys.Lfac && CholeskyNeedsFactorArray(st, st->sys.N);      // (the bind built the task list then; null: it failed the replay)
+  if (st->sw.chol_small && st->sys.N <= 2 * kNB) st->path = CholPath::Small;
+  else if (one_launch && st->tasks) st->path = CholPath::Tasks;
+  else st->path = st->tile_nz ? CholPath::SparseColumns : CholPath::Columns;
+  st->capture = st->use_graph && st->path != CholPath::Small && !one_launch;
+}
+
+int CholeskyBind(CholeskyState* st, const CholeskySystem& sys, const uint8_t* tile_nz, bool* map_changed) {
   std::lock_guard<std::recursive_mutex> lock(g_setup_mutex);
-  if (aux->tile_nz) { const int rc = EnsureSparseLists(aux, N / kNB, s); if (rc) return rc; }
-  if (has_factor_array && UseTasks(aux->mode, N / kNB)) { const int rc = EnsureTaskList(aux, N / kNB, s); if (rc) return rc; }      // (dense or block-sparse: one launch up to 128 block columns)
-  return PP_OK;
-}
-
-int CholeskySolveAugmented(double* S, int N, int rhs_row, double* Linv_ws, double* Lfac, double* x_out, int32_t* d_flag, hipStream_t s, CholeskyAux* aux) {
-  { const int rc = CholeskyPrepare(aux, N, Lfac != nullptr, s); if (rc) return rc; }      // (a no-op after the first call for this size)
-  // task mode is three launches: nothing to gain from a graph, and a capture is one thing less that can collide with whatever
-  // other host threads do on the device meanwhile (a device-wide synchronize in another thread fails while any stream captures)
-  const bool three_launches = aux && Lfac && UseTasks(aux->mode, N / kNB);
-  if (aux && aux->use_graph && !three_launches && !(UseSmallCholesky(aux, N) && x_out)) {
-    const bool same = aux->graph_exec && aux->g_S == S && aux->g_N == N && aux->g_rhs == rhs_row && aux->g_Linv == Linv_ws &&
-                      aux->g_x == x_out && aux->g_flag == d_flag && aux->g_stream == s && aux->g_mode == aux->mode && aux->g_Lfac == Lfac &&
-                      aux->g_sparse == (aux->sparse_lists != nullptr);
-    if (!same) {
-      std::lock_guard<std::recursive_mutex> lock(g_setup_mutex);
-      if (aux->graph_exec) { (void)hipGraphExecDestroy(aux->graph_exec); aux->graph_exec = nullptr; }
-      hipGraph_t graph = nullptr;
-      if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) {
-        const int rc = EnqueueCholesky(S, N, rhs_row, Linv_ws, Lfac, x_out, d_flag, s, aux);
-        const hipError_t e = hipStreamEndCapture(s, &graph);
-        if (rc == PP_OK && e == hipSuccess && graph && hipGraphInstantiate(&aux->graph_exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-          aux->g_S = S; aux->g_N = N; aux->g_rhs = rhs_row; aux->g_Linv = Linv_ws; aux->g_x = x_out; aux->g_flag = d_flag; aux->g_stream = s;
-          aux->g_mode = aux->mode; aux->g_Lfac = Lfac; aux->g_sparse = aux->sparse_lists != nullptr;
-        } else {
-          aux->graph_exec = nullptr;
-          aux->use_graph = false;   // do not retry
-          (void)hipGetLastError();
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-      } else {
-        aux->use_graph = false;
-        (void)hipGetLastError();
-      }
-    }
-    if (aux->graph_exec) {
-      PP_HIP_TRY(hipGraphLaunch(aux->graph_exec, s));
-      return PP_OK;
-    }
+  const int T = sys.N / kNB;
+  if (map_changed) *map_changed = st->tile_nz != tile_nz;
+  if (st->tile_nz != tile_nz) {
+    PP_HIP_TRY(hipStreamSynchronize(sys.stream));      // (the lists of the old map may still be read)
+    if (st->sparse_lists) { (void)hipFree(st->sparse_lists); st->sparse_lists = nullptr; }
+    if (st->sparse_nz) { (void)hipFree(st->sparse_nz); st->sparse_nz = nullptr; }
+    st->sparse_T = 0;
+    st->tile_nz = tile_nz;
   }
-  return EnqueueCholesky(S, N, rhs_row, Linv_ws, Lfac, x_out, d_flag, s, aux);
-}
-
-int CholeskyAuxCreate(CholeskyAux* aux, const Switches& sw) {
-  // PPSFM_CHOL_MODE: "columns" = one launch per block column; "tasks" = the whole factorisation as one launch (k_cholesky_tasks,
-  // bit-identical results); unset / "auto": tasks up to kTaskAutoMaxT block columns (0.73 against 0.84 ms at n = 3000, 0.35 against
-  // 0.40 ms at n = 1500, 1.24 against 1.38 ms at n = 4030), per-column launches above (there the trailing update is the bound and
-  // the per-column grid runs it in bigger, better balanced pieces)
-  aux->sw = sw;
-  if (aux->mode < 0) aux->mode = (int)sw.chol_mode;
-  if (!sw.chol_graph) aux->use_graph = false;
+  st->sys = sys;
+  DropGraph(st);
+  if (tile_nz) { const int rc = EnsureSparseLists(st, T, sys.stream); if (rc) return rc; }
+  if (sys.Lfac && CholeskyNeedsFactorArray(st, sys.N)) { const int rc = EnsureTaskList(st, T, sys.stream); if (rc) return rc; }
+  ChoosePath(st);
   return PP_OK;
 }
-void CholeskyAuxDestroy(CholeskyAux* aux) {
-  if (aux->graph_exec) (void)hipGraphExecDestroy(aux->graph_exec);
-  aux->graph_exec = nullptr;
-  if (aux->tasks) (void)hipFree(aux->tasks);
-  if (aux->tasks_nz) (void)hipFree(aux->tasks_nz);
-  if (aux->scratch) PoolDeviceFree(aux->scratch);
-  aux->scratch = nullptr; aux->scratch_tiles = 0;
-  aux->tasks = nullptr; aux->tasks_T = 0; aux->tasks_nz = nullptr; aux->tasks_src_nz = nullptr;
-  if (aux->sparse_lists) (void)hipFree(aux->sparse_lists);
-  if (aux->sparse_nz) (void)hipFree(aux->sparse_nz);
-  aux->sparse_lists = nullptr; aux->sparse_nz = nullptr; aux->sparse_T = 0;
+
+int CholeskySolve(CholeskyState* st) {
+  if (st->capture && !st->graph_exec) {
+    std::lock_guard<std::recursive_mutex> lock(g_setup_mutex);
+    hipGraph_t graph = nullptr;
+    bool ok = hipStreamBeginCapture(st->sys.stream, hipStreamCaptureModeRelaxed) == hipSuccess;
+    if (ok) {
+      const int rc = EnqueueCholesky(*st);
+      ok = hipStreamEndCapture(st->sys.stream, &graph) == hipSuccess && rc == PP_OK && graph &&
+           hipGraphInstantiate(&st->graph_exec, graph, nullptr, nullptr, 0) == hipSuccess;
+    }
+    if (graph) (void)hipGraphDestroy(graph);
+    if (!ok) { st->graph_exec = nullptr; st->use_graph = st->capture = false; (void)hipGetLastError(); }      // (eager from here on: no retry)
+  }
+  if (st->graph_exec) {
+    PP_HIP_TRY(hipGraphLaunch(st->graph_exec, st->sys.stream));
+    return PP_OK;
+  }
+  return EnqueueCholesky(*st);
 }
+
+bool CholeskyFallBackToColumns(CholeskyState* st) {
+  if (st->columns) return false;
+  st->columns = true; ++st->fallbacks;
+  DropGraph(st);
+  ChoosePath(st);      // (the lists of the per-column paths were built by the bind)
+  return true;
+}
+void CholeskyDisableGraph(CholeskyState* st) { st->use_graph = st->capture = false; DropGraph(st); }
+int CholeskyLinsolve(const CholeskyState* st) {      // (a block-sparse system reports SPARSE on either of its paths)
+  return st->path == CholPath::Small || st->path == CholPath::Columns ? PP_LINSOLVE_CHOLESKY_COLUMNS : st->tile_nz ? PP_LINSOLVE_CHOLESKY_SPARSE : PP_LINSOLVE_CHOLESKY_TASKS;
+}
+int CholeskyFallbacks(const CholeskyState* st) { return st->fallbacks; }
+double CholeskyPlanMs(const CholeskyState* st) { return st->plan_ms; }
 
 }  // namespace ppsfm
 
@@ -2504,10 +2536,10 @@ extern "C" int pp_dense_cholesky_solve(int32_t n, const double* A, const double*
   int32_t* dflag = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   hipStream_t strm = nullptr;
-  CholeskyAux aux;
+  CholeskyState* st = nullptr;
   int rc = PP_OK;
   auto cleanup = [&]() {
-    CholeskyAuxDestroy(&aux);
+    CholeskyDestroy(st); st = nullptr;
     if (strm) (void)hipStreamDestroy(strm);
     if (dS) (void)hipFree(dS); if (dL) (void)hipFree(dL); if (dS0) (void)hipFree(dS0); if (dLinv) (void)hipFree(dLinv); if (dx) (void)hipFree(dx); if (dflag) (void)hipFree(dflag);
     if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1);
@@ -2519,7 +2551,7 @@ extern "C" int pp_dense_cholesky_solve(int32_t n, const double* A, const double*
   TRYH(hipEventCreate(&e0)); TRYH(hipEventCreate(&e1));
   TRYH(hipStreamCreateWithFlags(&strm, hipStreamNonBlocking));
   const Switches sw = ReadSwitches();
-  if ((rc = CholeskyAuxCreate(&aux, sw))) { cleanup(); return rc; }
+  st = CholeskyCreate(sw);
   // block-sparse input (PPSFM_CHOL_SPARSE=0 disables): tiles of the lower triangle that are entirely zero and stay zero in the
   // factor get no workgroup (the reference switches to SPARSE_SCHUR above 50 images, src/optim/bundle_adjustment.cc:275-286)
   std::vector<uint8_t> tile_nz;
@@ -2530,10 +2562,10 @@ extern "C" int pp_dense_cholesky_solve(int32_t n, const double* A, const double*
       for (int i = 0; i < N; ++i)
         for (int j = 0; j <= i; ++j)
           if (h[(size_t)i * N + j] != 0.0) tile_nz[(size_t)(i / kNB) * T + j / kNB] = 1;
-      const int nnz = SymbolicTileFill(T, tile_nz.data());
-      if (nnz < T * (T + 1) / 2) { aux.tile_nz = tile_nz.data(); aux.tile_T = T; }
+      if (SymbolicTileFill(T, tile_nz.data()) == T * (T + 1) / 2) tile_nz.clear();      // (nothing to skip: dense)
     }
   }
+  if ((rc = CholeskyBind(st, CholeskySystem{dS, N, n, dLinv, dL, dx, dflag, strm}, tile_nz.empty() ? nullptr : tile_nz.data()))) { cleanup(); return rc; }
   TRYH(hipMemcpy(dS0, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
   TRYH(hipMemset(dflag, 0, sizeof(int32_t) * 4));
   // per-solve times; the MEDIAN is reported.  This entry point creates its stream (a new hardware queue), its buffers and the kernels'
@@ -2546,7 +2578,7 @@ extern "C" int pp_dense_cholesky_solve(int32_t n, const double* A, const double*
     TRYH(hipMemcpy(dS, dS0, sizeof(double) * h.size(), hipMemcpyDeviceToDevice));
     TRYH(hipDeviceSynchronize());
     TRYH(hipEventRecord(e0, strm));
-    rc = CholeskySolveAugmented(dS, N, n, dLinv, dL, dx, dflag, strm, &aux);
+    rc = CholeskySolve(st);
     if (rc) { cleanup(); return rc; }
     TRYH(hipEventRecord(e1, strm));
     TRYH(hipEventSynchronize(e1));
@@ -2554,18 +2586,14 @@ extern "C" int pp_dense_cholesky_solve(int32_t n, const double* A, const double*
     if (sw.chol_debug_slow && ms > 5.0f) {      // (how the outliers described at `times` were caught)
       int32_t f4[4] = {0, 0, 0, 0};
       (void)hipMemcpy(f4, dflag, sizeof(f4), hipMemcpyDeviceToHost);
-      fprintf(stderr, "SLOW dense solve: n=%d it=%d ms=%.3f mode=%d last_used=%d flag=%d %d %d %d\n", n, it, ms, aux.mode, aux.last_used, f4[0], f4[1], f4[2], f4[3]);
+      fprintf(stderr, "SLOW dense solve: n=%d it=%d ms=%.3f linear_solver=%d flag=%d %d %d %d\n", n, it, ms, CholeskyLinsolve(st), f4[0], f4[1], f4[2], f4[3]);
     }
-    if (aux.mode != 0) {      // a bounded wait of the one-launch factorisation ran out (bit 4): once more, with per-column launches from here on
-      int32_t f = 0;
-      TRYH(hipMemcpy(&f, dflag, sizeof(f), hipMemcpyDeviceToHost));
-      if (f & 4) {
-        aux.mode = 0;
-        if (aux.graph_exec) { (void)hipGraphExecDestroy(aux.graph_exec); aux.graph_exec = nullptr; }
-        TRYH(hipMemset(dflag, 0, sizeof(int32_t) * 4));
-        if (it >= 0) times.pop_back();
-        --it;
-      }
+    int32_t f = 0;
+    TRYH(hipMemcpy(&f, dflag, sizeof(f), hipMemcpyDeviceToHost));
+    if ((f & 4) && CholeskyFallBackToColumns(st)) {      // a bounded wait of the one-launch factorisation ran out: once more, with per-column launches from here on
+      TRYH(hipMemset(dflag, 0, sizeof(int32_t) * 4));
+      if (it >= 0) times.pop_back();
+      --it;
     }
   }
   int32_t flag = 0;

@@ -25,7 +25,7 @@ bool Starts(const char* name, char a, char b) {
 
 Switches ReadSwitches() {
   Switches s;
-  s.chol_mode = Starts("PPSFM_CHOL_MODE", 't', '1') ? CholMode::Tasks : (Starts("PPSFM_CHOL_MODE", 'c', '0') ? CholMode::Columns : CholMode::BySize);
+  s.chol_columns = Starts("PPSFM_CHOL_MODE", 'c', '0');
   s.chol_graph = Int("PPSFM_CHOL_GRAPH", 1) != 0;
   s.chol_small = Int("PPSFM_CHOL_SMALL", 1) != 0;
   s.chol_sparse = Int("PPSFM_CHOL_SPARSE", 1) != 0;

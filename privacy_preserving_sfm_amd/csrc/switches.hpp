@@ -7,9 +7,9 @@
 // (so "off" is 0); "letter": only the first character of the value counts; unset or any other value is the default.
 //
 //   name                        values                       default          read by                                      kind
-//   PPSFM_CHOL_MODE             t|1 tasks, c|0 columns       by size          CholeskyAuxCreate (task / per-column launch)  fallback
-//   PPSFM_CHOL_GRAPH            atoi, 0 = off                on               CholeskyAuxCreate (graph capture)             fallback
-//   PPSFM_CHOL_SMALL            atoi, 0 = off                on               UseSmallCholesky (one-workgroup <= 128 cols)  fallback
+//   PPSFM_CHOL_MODE             letter c|0 columns           by size          CholeskyCreate (per-column launches only)    fallback
+//   PPSFM_CHOL_GRAPH            atoi, 0 = off                on               CholeskyCreate (graph capture)               fallback
+//   PPSFM_CHOL_SMALL            atoi, 0 = off                on               ChoosePath (one-workgroup <= 128 cols)       fallback
 //   PPSFM_CHOL_SPARSE           atoi, 0 = off                on               pp_dense_cholesky_solve (skip zero tiles)     A/B
 //   PPSFM_CHOL_CHAINS           atoi, clamped to [1, 16]     by structure     PlanChains (max chains)                      A/B
 //   PPSFM_CHOL_WHOLE_FROM       atoi                         WholeFrom(T)     BuildTaskList                                A/B
@@ -45,7 +45,6 @@
 
 namespace ppsfm {
 
-enum class CholMode { Columns = 0, Tasks = 1, BySize = 2 };      // (the values of CholeskyAux::mode)
 enum class LinearSolverSwitch { Descriptor, Direct, Iterative };
 enum class OrderingSwitch { ByChainSteps, Natural, Rcm, Band };
 enum class PairListsSwitch { BySize, Host, Device };
@@ -61,7 +60,7 @@ struct PlanSwitches {
 };
 
 struct Switches {
-  CholMode chol_mode = CholMode::BySize;
+  bool chol_columns = false;      // per-column launches only (otherwise by size: the one-launch factorisation up to 128 block columns)
   bool chol_graph = true, chol_small = true, chol_sparse = true, chol_test_drop_tasks = false, backsub_pairs = true;
   PlanSwitches plan;
   bool chol_debug = false, chol_debug_slow = false, chol_plan_print = false;

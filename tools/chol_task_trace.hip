@@ -25,9 +25,11 @@ int main(int argc, char** argv) {
   hipMalloc(&S, sizeof(double) * N * N); hipMalloc(&L, sizeof(double) * N * N); hipMalloc(&ws, sizeof(double) * ppsfm::CholeskyWorkspaceDoubles(N));
   hipMalloc(&x, sizeof(double) * N); hipMalloc(&flag, 16);
   hipMemset(flag, 0, 16);
-  ppsfm::CholeskyAux aux;
-  aux.mode = 1; aux.use_graph = false;
+  ppsfm::Switches sw;
+  sw.chol_graph = false;
+  ppsfm::CholeskyState* chol = ppsfm::CholeskyCreate(sw);
   hipStream_t s; hipStreamCreate(&s);
+  ppsfm::CholeskyBind(chol, ppsfm::CholeskySystem{S, N, N - 1, ws, L, x, flag, s}, nullptr);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   static long long tr[24][128];
   if (getenv("PP_ARRIVE_STEP")) { const int st = atoi(getenv("PP_ARRIVE_STEP")); hipMemcpyToSymbol(HIP_SYMBOL(ppsfm::g_arrive_step), &st, sizeof(st)); }      // barrier arrivals of THAT step instead of the last one
@@ -37,7 +39,7 @@ int main(int argc, char** argv) {
     hipMemcpyToSymbol(HIP_SYMBOL(ppsfm::g_task_trace), tr, sizeof(tr));
     hipDeviceSynchronize();
     hipEventRecord(e0, s);
-    ppsfm::CholeskySolveAugmented(S, N, N - 1, ws, L, x, flag, s, &aux);
+    ppsfm::CholeskySolve(chol);
     hipEventRecord(e1, s); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     int32_t f[4]; hipMemcpy(f, flag, 16, hipMemcpyDeviceToHost);
