@@ -323,7 +323,13 @@ int pp_ba_set_communicator(pp_ba_handle h, pp_comm_handle comm);
  * v_mfma_f64_16x16x4_f64 + triangular solves): solves A x = b for a symmetric positive definite n x n
  * row-major A (only the lower triangle is read).  repeat > 1 re-runs the device part for timing;
  * *ms_per_solve (may be NULL) receives the HIP-event time of one factorisation + solve: the MEDIAN
- * over the `repeat` solves (an untimed one precedes them).                                        */
+ * over the `repeat` solves (an untimed one precedes them).
+ * Range: b travels through the factorisation as one more row of A whose own diagonal entry is the constant 1e100,
+ * so ||L^-1 b||_2^2 (L the Cholesky factor; for an A with a unit-size diagonal about b' A^-1 b) must stay below 1e100:
+ * beyond it that row's pivot turns non-positive and the call reports PP_ERR_NUMERIC for a positive definite A.
+ * Inside it the constant never reaches x: scaling b by 2^k, or A by 4^k, scales x exactly (no clamp, no epsilon), as
+ * long as nothing overflows or becomes subnormal.  A non-positive or non-finite pivot, or a NaN / Inf anywhere in
+ * the lower triangle or in b, is reported as PP_ERR_NUMERIC ("not positive definite"); x is then unspecified.      */
 int pp_dense_cholesky_solve(int32_t n, const double* A, const double* b, double* x, int device, int32_t repeat,
                             float* ms_per_solve);
 /* The work list of the one-launch factorisation for `block_columns` 64-wide block columns (4 .. 128), in launch order: four

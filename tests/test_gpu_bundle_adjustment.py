@@ -7,28 +7,10 @@ costs also agree closely; that is asserted with a looser bound (summation orders
 import numpy as np
 import pytest
 
+from cholesky_reference import var_cols as _var_cols
 from privacy_preserving_sfm_amd import synthetic
 
 pytestmark = pytest.mark.gpu
-
-
-def _var_cols(sc):
-    cols = []
-    for c in range(sc["poses"].shape[0]):
-        if sc["pose_const"][c]:
-            continue
-        cols += [6 * c, 6 * c + 1, 6 * c + 2]
-        cols += [6 * c + 3 + j for j in range(3) if not (sc["tvec_const_mask"][c] >> j) & 1]
-    # variable intrinsics: compact columns after the 6C pose columns, camera by camera (only cameras with observations)
-    from privacy_preserving_sfm_amd.device import camera_num_params
-    used = set(int(k) for k in np.asarray(sc["pose_camera"]))
-    ni = 0
-    for k in range(len(sc["camera_model"])):
-        if k not in used:
-            continue
-        ni += sum(1 for j in range(camera_num_params(int(sc["camera_model"][k]))) if not (int(sc["camera_const_mask"][k]) >> j) & 1)
-    cols += [6 * sc["poses"].shape[0] + i for i in range(ni)]
-    return np.array(cols)
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 200, 777])

@@ -14,13 +14,15 @@ def _rel(a, b):
     return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
-def _cost_traces_agree(dt, rt, first_tol=1e-7, later_tol=1e-4):
+def _cost_traces_agree(dt, rt, d_final, r_final, first_tol=1e-7, later_tol=1e-4):
     """cost per iteration while both loops took the same accept / reject decisions: the first trial step's cost to first_tol relative (one linear solve
-    from identical inputs), every later one to later_tol of the INITIAL cost (differences of earlier steps are carried and amplified by the problem)"""
+    from identical inputs), every later one to later_tol of the INITIAL cost (differences of earlier steps are carried and amplified by the problem).
+    From where the decisions differ the iterations are not comparable one by one, but the end still is: the first loop's final cost (d_final) must not be
+    worse than the second's (r_final) by more than later_tol of the initial cost."""
     n = min(len(dt), len(rt))
     for i in range(n):
         if dt[i, 6] != rt[i, 6]:
-            return True, i
+            return d_final <= r_final + later_tol * abs(rt[0, 0]), i
         tol = first_tol * abs(rt[i, 0]) if i <= 1 else later_tol * abs(rt[0, 0])
         if abs(dt[i, 0] - rt[i, 0]) > tol:
             return False, i
@@ -69,8 +71,8 @@ def _check_case(oracle, sc, m, what):
     assert len(cols) == ref["nc"], what
     assert _rel(S[np.ix_(cols, cols)], ref["S"]) <= 1e-8 and _rel(rhs[cols], ref["rhs"]) <= 1e-8, what      # the assembly: independent of the conditioning
     rposes, rpoints, rintr, rs, rtrace = oracle.ba_solve(sc, oracle.BAOptionsC.defaults(max_num_iterations=4))
-    ok, upto = _cost_traces_agree(dtrace, rtrace)
-    assert ok and upto >= 2, (what, upto, dtrace[:, 0], rtrace[:, 0])
+    ok, upto = _cost_traces_agree(dtrace, rtrace, s.final_cost, rs.final_cost)
+    assert ok and upto >= 2, (what, upto, dtrace[:, 0], rtrace[:, 0], s.final_cost, rs.final_cost)
     same_path = s.num_iterations == rs.num_iterations and s.num_successful_steps == rs.num_successful_steps
     drift = max(_rel(points, rpoints), _rel(poses, rposes))
     explained = None
@@ -115,8 +117,8 @@ def test_badly_determined_problems_move_parameters_not_costs(oracle, case):
     assert drift > 1e-5 and explained is not None and explained > 1e-6, (drift, explained)      # (this IS one of the flagged cases; if it stops being one, pin another)
     _, s_t, (tposes, tpoints, _), ttrace = _solve(sc, 4, {"PPSFM_BA_INTR_LAYOUT": "tail"})
     _, s_d, _, dtrace = _solve(sc, 4)
-    ok, upto = _cost_traces_agree(ttrace, dtrace)
-    assert ok and upto >= 2, (upto, ttrace[:, 0], dtrace[:, 0])
+    ok, upto = _cost_traces_agree(ttrace, dtrace, s_t.final_cost, s_d.final_cost)
+    assert ok and upto >= 2, (upto, ttrace[:, 0], dtrace[:, 0], s_t.final_cost, s_d.final_cost)
     between_layouts = max(_rel(tpoints, points), _rel(tposes, poses))
     assert between_layouts <= 20.0 * explained and max(_rel(tpoints, rpoints), _rel(tposes, rposes)) <= 20.0 * explained
 
