@@ -10,9 +10,13 @@
 //   ppsfm::EstimateAbsolutePoseFromLines  <-> src/estimators/pose.h:110-115
 //   ppsfm::BundleAdjustmentProblem         <-> the flat form of what BundleAdjuster::SetUp builds
 //        (src/optim/bundle_adjustment.cc:326-542); Solve() replaces ceres::Solve (:306)
+//   ppsfm::Normalize, AdjustGlobalBundle, IterativeGlobalRefinement over ppsfm::FlatReconstruction <-> Reconstruction::Normalize
+//        (src/base/reconstruction.cc:302-397), IncrementalMapper::AdjustGlobalBundle (src/sfm/incremental_mapper.cc:893-939) with the controller's
+//        option preset (src/controllers/incremental_mapper.cc:52-70, 221-243), IterativeGlobalRefinement (:102-124)
 //   ppsfm::init::initialize_reconstruction <-> src/init/initializer.h:103-108 (four-view initialisation: gravity
 //        alignment, FourView2dEstimator LO-MSAC, lifting, PlanarOffsetEstimator LO-MSAC; both runs on the device)
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -227,6 +231,220 @@ class BundleAdjustmentProblem {
   int C_, P_, K_;
 };
 
+
+// ---- the mapper's global refinement (controllers/incremental_mapper.cc:52-70, 102-124; sfm/incremental_mapper.cc:893-939) -----------------------------
+// A reconstruction in the flat form BundleAdjustmentProblem takes: every registered image (in registration order), every 3D point, and the
+// observations grouped per point in track order.  Deleting an observation removes its entry; a deleted point keeps its slot with point_alive = 0.
+struct FlatReconstruction {
+  std::vector<double> poses;              // C x 7 (qvec w,x,y,z; tvec)
+  std::vector<double> points;             // P x 3
+  std::vector<uint8_t> point_alive;       // P
+  std::vector<double> intr;               // K x PP_CAM_STRIDE-many doubles per camera (12)
+  std::vector<int32_t> pose_camera;       // C
+  std::vector<int32_t> camera_model;      // K
+  std::vector<int32_t> cam_size;          // K x 2 (width, height)
+  std::vector<double> lines;              // M x 3
+  std::vector<int32_t> obs_pose, obs_point;   // M
+  std::vector<uint8_t> obs_aligned;       // M
+  std::vector<int64_t> obs_id;            // M: the caller's name of the observation (kept through deletions)
+  int NumImages() const { return (int)(poses.size() / 7); }
+  int NumPoints() const { return (int)(points.size() / 3); }
+  int NumCameras() const { return (int)camera_model.size(); }
+  size_t ComputeNumObservations() const { return obs_pose.size(); }
+};
+
+// Reconstruction::Normalize (base/reconstruction.cc:302-397): translation, then scale, of every image and point.  Host, O(C log C + P).
+inline void Normalize(FlatReconstruction* rec, double extent = 10.0, double p0 = 0.1, double p1 = 0.9, bool use_images = true) {
+  if (!(extent > 0) || p0 < 0 || p0 > 1 || p1 < 0 || p1 > 1 || p0 > p1) throw Error(PP_ERR_INVALID, "Normalize: CHECK on extent / p0 / p1");
+  const int C = rec->NumImages(), P = rec->NumPoints();
+  size_t alive = 0;
+  for (int p = 0; p < P; ++p) alive += rec->point_alive[p] ? 1 : 0;
+  if ((use_images && C < 2) || (!use_images && alive < 2)) return;
+  auto rotate = [](const double* q, const double* v, double* out) {      // Eigen::Quaterniond(q) * v, q as stored
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                         2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
+    for (int i = 0; i < 3; ++i) out[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2];
+  };
+  std::vector<double> centers(3 * (size_t)C);
+  for (int c = 0; c < C; ++c) {            // ProjectionCenterFromPose (base/pose.cc:94-101): conjugate of the NORMALISED quaternion times -tvec
+    const double* q = &rec->poses[7 * c];
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double qc[4] = {q[0] / n, -q[1] / n, -q[2] / n, -q[3] / n};
+    const double mt[3] = {-q[4], -q[5], -q[6]};
+    rotate(qc, mt, &centers[3 * c]);
+  }
+  std::vector<float> coords[3];            // cast to float before the sort (:333-352)
+  if (use_images) {
+    for (int c = 0; c < C; ++c) for (int a = 0; a < 3; ++a) coords[a].push_back(static_cast<float>(centers[3 * c + a]));
+  } else {
+    for (int p = 0; p < P; ++p) if (rec->point_alive[p]) for (int a = 0; a < 3; ++a) coords[a].push_back(static_cast<float>(rec->points[3 * p + a]));
+  }
+  for (int a = 0; a < 3; ++a) std::sort(coords[a].begin(), coords[a].end());
+  const size_t n = coords[0].size();
+  const size_t P0 = static_cast<size_t>((n > 3) ? p0 * (n - 1) : 0);
+  const size_t P1 = static_cast<size_t>((n > 3) ? p1 * (n - 1) : n - 1);
+  double mean[3] = {0, 0, 0}, ext2 = 0;
+  for (int a = 0; a < 3; ++a) {
+    for (size_t i = P0; i <= P1; ++i) mean[a] += coords[a][i];
+    mean[a] /= (double)(P1 - P0 + 1);
+    const double d = (double)coords[a][P1] - (double)coords[a][P0];
+    ext2 += d * d;
+  }
+  const double old_extent = std::sqrt(ext2);
+  const double scale = old_extent < std::numeric_limits<double>::epsilon() ? 1.0 : extent / old_extent;
+  for (int c = 0; c < C; ++c) {
+    double m[3];
+    for (int a = 0; a < 3; ++a) m[a] = -((centers[3 * c + a] - mean[a]) * scale);
+    rotate(&rec->poses[7 * c], m, &rec->poses[7 * c + 4]);
+  }
+  for (int p = 0; p < P; ++p)
+    if (rec->point_alive[p]) for (int a = 0; a < 3; ++a) rec->points[3 * p + a] = (rec->points[3 * p + a] - mean[a]) * scale;
+}
+
+// controllers/incremental_mapper.cc:221-243 and, below ten registered images, :58-66
+inline pp_ba_options GlobalBundleAdjustmentOptions(size_t num_reg_images, int ba_global_max_num_iterations = 50) {
+  pp_ba_options o;
+  pp_ba_options_default(&o);
+  o.function_tolerance = 0.0; o.gradient_tolerance = 1.0; o.parameter_tolerance = 0.0;
+  o.max_num_iterations = ba_global_max_num_iterations; o.max_linear_solver_iterations = 100;
+  const size_t kMinNumRegImagesForFastBA = 10;
+  if (num_reg_images < kMinNumRegImagesForFastBA) {
+    o.function_tolerance /= 10; o.gradient_tolerance /= 10; o.parameter_tolerance /= 10;
+    o.max_num_iterations *= 2; o.max_linear_solver_iterations = 200;
+  }
+  return o;
+}
+
+namespace detail {
+// the flat problem over the live points that still have observations (a point index of the problem -> the reconstruction's)
+struct RefinementProblem {
+  std::vector<int32_t> point_of, obs_point;
+  std::vector<double> points;
+  std::vector<uint8_t> pose_const, tvec_mask, point_const;
+  std::vector<uint16_t> cam_mask;
+  pp_ba_problem_desc desc{};
+  RefinementProblem(const FlatReconstruction& r, bool gauge) {
+    const int C = r.NumImages(), P = r.NumPoints();
+    std::vector<int32_t> index(P, -1);
+    obs_point.resize(r.obs_point.size());
+    for (size_t o = 0; o < r.obs_point.size(); ++o) {
+      const int32_t p = r.obs_point[o];
+      if (index[p] < 0) { index[p] = (int32_t)point_of.size(); point_of.push_back(p); for (int a = 0; a < 3; ++a) points.push_back(r.points[3 * p + a]); }
+      obs_point[o] = index[p];
+    }
+    pose_const.assign(C, 0); tvec_mask.assign(C, 0); point_const.assign(point_of.size(), 0); cam_mask.assign(r.NumCameras(), 0xFFFF);
+    if (gauge) { pose_const[0] = 1; tvec_mask[1] = 1; }      // sfm/incremental_mapper.cc:922-926: the 7 gauge DOFs
+    desc.num_poses = C; desc.num_points = (int32_t)point_of.size(); desc.num_cameras = r.NumCameras();
+    desc.loss_type = PP_LOSS_TRIVIAL; desc.loss_scale = 1.0; desc.num_obs = (int64_t)r.obs_pose.size();
+    desc.lines = r.lines.data(); desc.obs_pose = r.obs_pose.data(); desc.obs_point = obs_point.data();
+    desc.pose_camera = r.pose_camera.data(); desc.camera_model = r.camera_model.data();
+    desc.pose_const = pose_const.data(); desc.tvec_const_mask = tvec_mask.data(); desc.point_const = point_const.data();
+    desc.camera_const_mask = cam_mask.data();
+    desc.linear_solver = C <= PP_MAX_NUM_IMAGES_DIRECT_SOLVER ? PP_LINEAR_SOLVER_DIRECT : PP_LINEAR_SOLVER_ITERATIVE_SCHUR;
+  }
+};
+inline void EraseObservations(FlatReconstruction* r, const std::vector<uint8_t>& gone) {
+  size_t w = 0;
+  for (size_t o = 0; o < gone.size(); ++o) {
+    if (gone[o]) continue;
+    for (int a = 0; a < 3; ++a) r->lines[3 * w + a] = r->lines[3 * o + a];
+    r->obs_pose[w] = r->obs_pose[o]; r->obs_point[w] = r->obs_point[o]; r->obs_aligned[w] = r->obs_aligned[o]; r->obs_id[w] = r->obs_id[o];
+    ++w;
+  }
+  r->lines.resize(3 * w); r->obs_pose.resize(w); r->obs_point.resize(w); r->obs_aligned.resize(w); r->obs_id.resize(w);
+}
+}  // namespace detail
+
+// Reconstruction::FilterObservationsWithNegativeDepth on the device; returns the number of deleted observations
+inline size_t FilterObservationsWithNegativeDepth(FlatReconstruction* rec, int device = 0) {
+  if (rec->obs_pose.empty()) return 0;
+  detail::RefinementProblem rp(*rec, false);
+  BundleAdjustmentProblem problem(rp.desc, device);
+  problem.SetParameters(rec->poses.data(), rp.points.data(), rec->intr.data());
+  std::vector<uint8_t> neg(rec->obs_pose.size());
+  int64_t n = 0;
+  Check(pp_ba_filter_negative_depth(problem.handle(), neg.data(), &n));
+  detail::EraseObservations(rec, neg);
+  return (size_t)n;
+}
+
+// Reconstruction::FilterAllPoints3D on the device; returns the reference's count.  deleted_obs_ids / deleted_points (may be null) receive what went.
+inline size_t FilterAllPoints3D(FlatReconstruction* rec, double max_reproj_error, double min_tri_angle, int device = 0,
+                                std::vector<int64_t>* deleted_obs_ids = nullptr, std::vector<int32_t>* deleted_points = nullptr) {
+  if (rec->obs_pose.empty()) return 0;
+  detail::RefinementProblem rp(*rec, false);
+  BundleAdjustmentProblem problem(rp.desc, device);
+  problem.SetParameters(rec->poses.data(), rp.points.data(), rec->intr.data());
+  const pp_filter_options fo{max_reproj_error, min_tri_angle};
+  pp_filter_report rep;
+  std::vector<uint8_t> od(rec->obs_pose.size()), pd(rp.point_of.size());
+  std::vector<double> pe(rp.point_of.size());
+  Check(pp_ba_filter_points(problem.handle(), &fo, rec->obs_aligned.data(), rec->cam_size.data(), nullptr, od.data(), pd.data(), pe.data(), &rep));
+  for (size_t k = 0; k < pd.size(); ++k)
+    if (pd[k]) { rec->point_alive[rp.point_of[k]] = 0; if (deleted_points) deleted_points->push_back(rp.point_of[k]); }
+  if (deleted_obs_ids) for (size_t o = 0; o < od.size(); ++o) if (od[o]) deleted_obs_ids->push_back(rec->obs_id[o]);
+  detail::EraseObservations(rec, od);
+  return (size_t)rep.num_filtered;
+}
+
+// IncrementalMapper::AdjustGlobalBundle (sfm/incremental_mapper.cc:893-939): negative-depth filter, every image with the first one constant and
+// tvec[0] of the second one constant, solve, Normalize.  Returns the solve's success (false: nothing to solve).  fix_existing_images is not mirrored.
+inline bool AdjustGlobalBundle(FlatReconstruction* rec, const pp_ba_options& ba_options, pp_ba_summary* summary = nullptr, int device = 0) {
+  if (rec->NumImages() < 2) throw Error(PP_ERR_INVALID, "At least two images must be registered for global bundle-adjustment");
+  FilterObservationsWithNegativeDepth(rec, device);
+  if (rec->obs_pose.empty()) return false;
+  detail::RefinementProblem rp(*rec, true);
+  BundleAdjustmentProblem problem(rp.desc, device);
+  problem.SetParameters(rec->poses.data(), rp.points.data(), rec->intr.data());
+  pp_ba_summary local;
+  pp_ba_summary* s = summary ? summary : &local;
+  const bool usable = problem.Solve(ba_options, s) && s->termination != PP_TERM_USER_FAILURE;
+  if (usable) {      // (after FAILURE Ceres restores the parameter blocks it was given: nothing is written back)
+    std::vector<double> poses(rec->poses.size()), intr(rec->intr.size());
+    problem.GetParameters(poses.data(), rp.points.data(), intr.data());
+    for (int c = 1; c < rec->NumImages(); ++c) for (int e = 0; e < 7; ++e) rec->poses[7 * c + e] = poses[7 * c + e];
+    for (size_t k = 0; k < rp.point_of.size(); ++k) for (int a = 0; a < 3; ++a) rec->points[3 * rp.point_of[k] + a] = rp.points[3 * k + a];
+  }
+  Normalize(rec);
+  return true;
+}
+
+struct GlobalRefinementOptions {      // controllers/incremental_mapper.h:102-108, sfm/incremental_mapper.h:89-92
+  int ba_global_max_num_iterations = 50;
+  int ba_global_max_refinements = 5;
+  double ba_global_max_refinement_change = 0.0005;
+  double filter_max_reproj_error = 4.0;
+  double filter_min_tri_angle = 1.5;
+};
+struct GlobalRefinementReport {
+  int num_rounds = 0;
+  std::vector<pp_ba_summary> summaries;
+  std::vector<size_t> num_filtered;
+  std::vector<double> changed;
+  std::vector<std::vector<int64_t>> obs_deleted;      // per round: obs_id of what the round's filter removed
+  std::vector<std::vector<int32_t>> point_deleted;
+};
+
+// IterativeGlobalRefinement (controllers/incremental_mapper.cc:102-124).  CompleteAndMergeTracks and FilterImages are the triangulator's and the image
+// bookkeeping's work, which this mirror does not restate: they are left out, so `changed` counts filtered observations only.
+inline GlobalRefinementReport IterativeGlobalRefinement(FlatReconstruction* rec, const GlobalRefinementOptions& options = GlobalRefinementOptions(), int device = 0) {
+  GlobalRefinementReport report;
+  for (int i = 0; i < options.ba_global_max_refinements; ++i) {
+    const size_t num_observations = rec->ComputeNumObservations();
+    pp_ba_summary summary{};
+    AdjustGlobalBundle(rec, GlobalBundleAdjustmentOptions((size_t)rec->NumImages(), options.ba_global_max_num_iterations), &summary, device);
+    std::vector<int64_t> od;
+    std::vector<int32_t> pd;
+    const size_t num_filtered = FilterAllPoints3D(rec, options.filter_max_reproj_error, options.filter_min_tri_angle, device, &od, &pd);
+    const double changed = num_observations ? static_cast<double>(num_filtered) / num_observations : 0.0;
+    ++report.num_rounds;
+    report.summaries.push_back(summary); report.num_filtered.push_back(num_filtered); report.changed.push_back(changed);
+    report.obs_deleted.push_back(od); report.point_deleted.push_back(pd);
+    if (changed < options.ba_global_max_refinement_change) break;
+  }
+  return report;
+}
 
 // ---- four-view initialisation (src/init/initializer.cc:58-216) ------------------------------------------------------
 namespace init {

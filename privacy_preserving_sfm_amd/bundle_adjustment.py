@@ -6,6 +6,10 @@ minimal data model it reads raw doubles from (`Reconstruction`, `Image`, `Camera
 base/image.h, base/camera.h, base/point3d.h, feature/types.h:98-138).  `BundleAdjuster.Solve` performs exactly
 the SetUp of bundle_adjustment.cc:326-542 (which observations exist, which blocks are constant), flattens it to
 the arrays of `pp_ba_problem_desc`, and hands the solve to the device (`pp_ba_solve`).
+
+Above it, the mapper's global refinement: `Reconstruction.Normalize` (base/reconstruction.cc:302-397), `AdjustGlobalBundle`
+(sfm/incremental_mapper.cc:893-939 with the option preset of controllers/incremental_mapper.cc:52-70, 221-243) and
+`IterativeGlobalRefinement` (controllers/incremental_mapper.cc:102-124).
 """
 import numpy as np
 
@@ -90,6 +94,32 @@ class Point3D:
         self.error = -1.0                 # Point3D::Error(), set by FilterPoints3DWithLargeReprojectionError
 
 
+def _quat_to_rot(q):
+    """[..., 4] (w,x,y,z) -> [..., 3, 3], the polynomial Eigen::Quaterniond applies to a vector (no normalisation inside)"""
+    w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                  [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                  [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+    return np.moveaxis(R, (0, 1), (-2, -1))
+
+
+def _normalize_transform(coords, extent, p0, p1):
+    """base/reconstruction.cc:324-380: (translation, scale) from N x 3 coordinates - cast to float, sorted per axis, the box between the p0 and p1
+    index (all of them up to three coordinates), the mean over that index range."""
+    c = np.sort(np.asarray(coords, dtype=np.float64).astype(np.float32), axis=0)
+    n = c.shape[0]
+    i0 = int(p0 * (n - 1)) if n > 3 else 0
+    i1 = int(p1 * (n - 1)) if n > 3 else n - 1
+    bbox_min, bbox_max = c[i0].astype(np.float64), c[i1].astype(np.float64)
+    mean = np.zeros(3)
+    for i in range(i0, i1 + 1):          # summed in double, in sorted order, as the reference does
+        mean += c[i]
+    mean /= i1 - i0 + 1
+    old_extent = float(np.linalg.norm(bbox_max - bbox_min))
+    scale = 1.0 if old_extent < np.finfo(np.float64).eps else extent / old_extent
+    return mean, scale
+
+
 class Reconstruction:
     def __init__(self):
         self.cameras, self.images, self.points3D = {}, {}, {}
@@ -155,6 +185,11 @@ class Reconstruction:
             rep, od, pd, pe = pb.filter_points(max_reproj_error, min_tri_angle, cam_size, obs_aligned=aligned, point_subset=subset)
         finally:
             pb.close()
+        self._apply_points_filter(scene, point_ids, obs_ref, od, pd, pe)
+        return int(rep.num_filtered)
+
+    def _apply_points_filter(self, scene, point_ids, obs_ref, od, pd, pe):
+        """deletes what a FilterPoints3D over `_filter_scene()` reported (masks per observation / per point, error per point)"""
         for k, pid in enumerate(point_ids):
             if pd[k]:
                 self.DeletePoint3D(pid)
@@ -164,7 +199,6 @@ class Reconstruction:
             pid = point_ids[scene["obs_point"][o]]
             if od[o] and pid in self.points3D:
                 self.DeleteObservation(iid, idx)
-        return int(rep.num_filtered)
 
     def FilterAllPoints3D(self, max_reproj_error, min_tri_angle, device=0):
         return self.FilterPoints3D(max_reproj_error, min_tri_angle, None, device=device)
@@ -185,6 +219,37 @@ class Reconstruction:
             if neg[o]:
                 self.DeleteObservation(iid, idx)
         return n
+
+    def RegImageIds(self):
+        """every image of this data model is registered; the order of registration is the order of the ids"""
+        return sorted(self.images)
+
+    def _observations(self):
+        return set((iid, idx) for iid, image in self.images.items() for idx, l in enumerate(image.lines) if l.HasPoint3D())
+
+    def ComputeNumObservations(self):
+        """base/reconstruction.cc:486-492"""
+        return len(self._observations())
+
+    def Normalize(self, extent=10.0, p0=0.1, p1=0.9, use_images=True):
+        """Reconstruction::Normalize (base/reconstruction.cc:302-397): a translation, then a scale, of every image and point, so that the robust
+        bounding box of the projection centres (or of the points) has diagonal `extent` around their robust mean.  Host, O(C log C + P)."""
+        assert extent > 0 and 0 <= p0 <= p1 <= 1
+        image_ids = self.RegImageIds()
+        if (use_images and len(image_ids) < 2) or (not use_images and len(self.points3D) < 2):
+            return
+        qvecs = np.array([self.images[i].qvec for i in image_ids]).reshape(-1, 4)
+        tvecs = np.array([self.images[i].tvec for i in image_ids]).reshape(-1, 3)
+        unit = qvecs / np.linalg.norm(qvecs, axis=1, keepdims=True)          # ProjectionCenterFromPose normalises (base/pose.cc:94-101)
+        centres = -np.einsum("cji,cj->ci", _quat_to_rot(unit), tvecs)
+        coords = centres if use_images else np.array([self.points3D[p].xyz for p in sorted(self.points3D)])
+        translation, scale = _normalize_transform(coords, extent, p0, p1)
+        centres = (centres - translation) * scale
+        new_tvecs = np.einsum("cij,cj->ci", _quat_to_rot(qvecs), -centres)    # quat * -centre with Qvec as stored (:386-389)
+        for k, iid in enumerate(image_ids):
+            self.images[iid].tvec = new_tvecs[k].copy()
+        for point in self.points3D.values():
+            point.xyz = (point.xyz - translation) * scale
 
     @staticmethod
     def from_scene(scene):
@@ -509,6 +574,13 @@ class BundleAdjuster:
         # (recollection of ceres/solver.cc, Ceres absent here: unpinned), so nothing is written back
         if self.summary_.termination in (_capi.TERM_FAILURE, _capi.TERM_USER_FAILURE):
             return True
+        self.write_back(reconstruction, flat, poses, points, intr)
+        return True
+
+    @staticmethod
+    def write_back(reconstruction, flat, poses, points, intr):
+        """the solved parameters of `flatten()`'s problem into the reconstruction: the variable blocks only"""
+        scene, pose_index, point_index, cam_index = flat
         # parameter memory is updated in place, as Ceres does through the raw pointers
         for iid, k in pose_index.items():
             if not scene["pose_const"][k]:
@@ -522,7 +594,6 @@ class BundleAdjuster:
             n = cam.NumParams()
             if (int(scene["camera_const_mask"][k]) & ((1 << n) - 1)) != (1 << n) - 1:
                 cam.params = intr[k, :n].copy()
-        return True
 
 
 def PrintSolverSummary(s):
@@ -534,3 +605,113 @@ def PrintSolverSummary(s):
             ("Final cost", "%g [px]" % np.sqrt(s.final_cost / max(s.num_residuals, 1))), ("Termination", term))
     for k, v in rows:
         print("%16s%s" % (k + " : ", v))
+
+
+class IncrementalMapperOptions:
+    """The fields of the reference's IncrementalMapperOptions (controllers/incremental_mapper.h:81-108) and IncrementalMapper::Options
+    (sfm/incremental_mapper.h:89-98) that the global refinement reads, with their defaults."""
+
+    def __init__(self):
+        self.ba_refine_focal_length = False
+        self.ba_refine_principal_point = False
+        self.ba_refine_extra_params = False
+        self.ba_min_num_residuals_for_multi_threading = 50000
+        self.ba_global_max_num_iterations = 50
+        self.ba_global_max_refinements = 5
+        self.ba_global_max_refinement_change = 0.0005
+        self.filter_max_reproj_error = 4.0
+        self.filter_min_tri_angle = 1.5
+        self.print_summary = True
+
+    def GlobalBundleAdjustment(self):
+        """controllers/incremental_mapper.cc:221-243"""
+        options = BundleAdjustmentOptions()
+        options.solver_options.function_tolerance = 0.0
+        options.solver_options.gradient_tolerance = 1.0
+        options.solver_options.parameter_tolerance = 0.0
+        options.solver_options.max_num_iterations = self.ba_global_max_num_iterations
+        options.solver_options.max_linear_solver_iterations = 100
+        options.solver_options.minimizer_progress_to_stdout = True
+        options.print_summary = self.print_summary
+        options.refine_focal_length = self.ba_refine_focal_length
+        options.refine_principal_point = self.ba_refine_principal_point
+        options.refine_extra_params = self.ba_refine_extra_params
+        options.min_num_residuals_for_multi_threading = self.ba_min_num_residuals_for_multi_threading
+        options.loss_function_type = BundleAdjustmentOptions.TRIVIAL
+        return options
+
+
+def GlobalBundleAdjustmentOptions(num_reg_images, mapper_options=None):
+    """The options the controller hands a global bundle adjustment (controllers/incremental_mapper.cc:52-70): the global preset, with
+    stricter convergence criteria while fewer than 10 images are registered."""
+    options = (mapper_options or IncrementalMapperOptions()).GlobalBundleAdjustment()
+    kMinNumRegImagesForFastBA = 10
+    if num_reg_images < kMinNumRegImagesForFastBA:
+        options.solver_options.function_tolerance /= 10
+        options.solver_options.gradient_tolerance /= 10
+        options.solver_options.parameter_tolerance /= 10
+        options.solver_options.max_num_iterations *= 2
+        options.solver_options.max_linear_solver_iterations = 200
+    return options
+
+
+def GlobalBundleAdjustmentConfig(reconstruction):
+    """sfm/incremental_mapper.cc:906-926: every registered image, the first one constant, tvec[0] of the second one constant (the 7 gauge DOFs)"""
+    reg_image_ids = reconstruction.RegImageIds()
+    assert len(reg_image_ids) >= 2, "At least two images must be registered for global bundle-adjustment"
+    config = BundleAdjustmentConfig()
+    for image_id in reg_image_ids:
+        config.AddImage(image_id)
+    config.SetConstantPose(reg_image_ids[0])
+    config.SetConstantTvec(reg_image_ids[1], [0])
+    return config
+
+
+def AdjustGlobalBundle(reconstruction, ba_options, device=0, summary_out=None):
+    """IncrementalMapper::AdjustGlobalBundle (sfm/incremental_mapper.cc:893-939): negative-depth filter, all images with the gauge fixed, solve,
+    Normalize.  Returns the solve's success; `summary_out` (a list) receives the solver summary.  `fix_existing_images` is not mirrored."""
+    reconstruction.FilterObservationsWithNegativeDepth(device=device)
+    bundle_adjuster = BundleAdjuster(ba_options, GlobalBundleAdjustmentConfig(reconstruction), device=device)
+    ok = bundle_adjuster.Solve(reconstruction)
+    if summary_out is not None:
+        summary_out.append(bundle_adjuster.Summary())
+    if not ok:
+        return False
+    reconstruction.Normalize()
+    return True
+
+
+class GlobalRefinementReport:
+    """What IterativeGlobalRefinement did: one entry per round in `summaries` (the solver summary, None where there was nothing to solve),
+    `num_filtered` (FilterAllPoints3D's count), `changed` (that count over the observations before the round), and what the round's filter
+    deleted: `obs_deleted` (sorted (image_id, line_idx) pairs, those of deleted points included) and `point_deleted` (sorted point ids)."""
+
+    def __init__(self):
+        self.num_rounds = 0
+        self.summaries, self.num_filtered, self.changed = [], [], []
+        self.obs_deleted, self.point_deleted = [], []
+
+
+def IterativeGlobalRefinement(reconstruction, mapper_options=None, device=0):
+    """IterativeGlobalRefinement (controllers/incremental_mapper.cc:102-124): up to `ba_global_max_refinements` rounds of AdjustGlobalBundle and
+    FilterAllPoints3D, until a round changes less than `ba_global_max_refinement_change` of the observations.
+    CompleteAndMergeTracks (before the loop and inside every round) and the closing FilterImages are the triangulator's and the image
+    bookkeeping's work, which this package does not mirror: they are left out, so `changed` counts filtered observations only."""
+    options = mapper_options or IncrementalMapperOptions()
+    report = GlobalRefinementReport()
+    for _ in range(options.ba_global_max_refinements):
+        num_observations = reconstruction.ComputeNumObservations()
+        summaries = []
+        AdjustGlobalBundle(reconstruction, GlobalBundleAdjustmentOptions(len(reconstruction.RegImageIds()), options), device=device, summary_out=summaries)
+        obs_before, points_before = reconstruction._observations(), set(reconstruction.points3D)
+        num_filtered = reconstruction.FilterAllPoints3D(options.filter_max_reproj_error, options.filter_min_tri_angle, device=device)
+        changed = float(num_filtered) / num_observations if num_observations else 0.0
+        report.num_rounds += 1
+        report.summaries.append(summaries[0] if summaries else None)
+        report.num_filtered.append(int(num_filtered))
+        report.changed.append(changed)
+        report.obs_deleted.append(sorted(obs_before - reconstruction._observations()))
+        report.point_deleted.append(sorted(points_before - set(reconstruction.points3D)))
+        if changed < options.ba_global_max_refinement_change:
+            break
+    return report

@@ -1911,6 +1911,12 @@ int pp_ba_solve(pp_ba_handle h, const pp_ba_options* o, pp_ba_summary* sum) try 
       continue;
     }
     if (!valid) {
+      // a factorisation that met a non-positive pivot leaves NaN where it stopped, also in the zero padding of S that the assembly never rewrites: the
+      // next, more strongly damped system would fail on what this one left behind (an iterative handle has no S: its conjugate-gradient loop raises the same bit)
+      if ((HostFlag(h) & 1) && !h->iterative && h->S) {
+        PP_HIP_TRY(hipMemsetAsync(h->S, 0, sizeof(double) * (size_t)h->N * h->N, s));
+        if (h->Lfac) PP_HIP_TRY(hipMemsetAsync(h->Lfac, 0, sizeof(double) * (size_t)h->N * h->N, s));
+      }
       ++invalid;
       if (invalid >= o->max_num_consecutive_invalid_steps) {
         if ((rc = undo_speculation(false))) return rc;

@@ -68,7 +68,7 @@ def default_intrinsics(model):
 
 def make_ba_scene(num_cams, num_points, track, seed=0xC0FFEE, model=2, num_intrinsics=1,
                   noise_point=1e-2, noise_t=1e-3, noise_q=1e-3, sort="point", window=None, loop=False, clusters=None, bridge=4,
-                  topology="star"):
+                  topology="star", line_noise_px=0.0, outlier_obs=0.0, quantise_float32=False):
     """Cameras on a circle of radius 4 looking at the origin (+ jitter), points uniform in [-1,1]^3,
     every point observed by `track` distinct cameras; start = ground truth + noise.  Gauge as the
     reference's global BA: pose[0] constant, tvec[1].x constant (sfm/incremental_mapper.cc:922-926).
@@ -81,9 +81,18 @@ def make_ba_scene(num_cams, num_points, track, seed=0xC0FFEE, model=2, num_intri
     group, and the groups are joined by a few images only: `bridge` images of a group also see points of the group it is attached to - the first group
     (`topology` "star": a hub with satellites, which no order of the images turns into a narrow band) or the previous group ("chain").
 
+    Observation model (what the mapper hands its global bundle adjustment instead of exact lines; all three off by default, and their random
+    numbers come from a second generator, so the arrays of a default scene do not depend on them):
+    `line_noise_px`: the projection a line is drawn through is moved by N(0, line_noise_px) pixels per axis (/ f of the observation's camera).
+    `outlier_obs`: this share of the observations gets a random line through a random image point instead (make_ransac_scene's recipe); never in the
+    two gauge images, and every point keeps at least two inlier observations.  `outlier_mask` [M] bytes says which.
+    `quantise_float32`: (a,b,c) rounded to float32 and re-normalised in double, as the reference's database stores and loads lines
+    (base/database.cc:55-73).
+
     Returns a dict with ground truth (`gt_*`) and perturbed start (`poses`, `points`, `intr`).
     """
     rng = np.random.default_rng(seed)
+    rng_obs = np.random.default_rng([int(seed), 0x0B5])      # the observation model's own stream
     C, P = int(num_cams), int(num_points)
     poses_gt = np.zeros((C, 7))
     Rs = np.zeros((C, 3, 3))
@@ -133,12 +142,34 @@ def make_ba_scene(num_cams, num_points, track, seed=0xC0FFEE, model=2, num_intri
     assert np.all(Xc[:, 2] > 0.5)
     xh = np.stack([Xc[:, 0] / Xc[:, 2], Xc[:, 1] / Xc[:, 2], np.ones(M)], axis=1)
     n = rng.uniform(-1, 1, (M, 3))
+    if line_noise_px > 0:
+        xh[:, :2] += rng_obs.normal(0, line_noise_px, (M, 2)) / intr[pose_camera[obs_pose], 0][:, None]
     lines = np.cross(xh, n)
     lines /= np.linalg.norm(lines[:, :2], axis=1, keepdims=True)
+    outlier_mask = np.zeros(M, dtype=np.uint8)
+    if outlier_obs > 0:
+        # in random order: an observation is taken unless it is in a gauge image or its point already lost track - 2 of its observations
+        want = int(round(outlier_obs * M))
+        perm = rng_obs.permutation(M)
+        perm = perm[obs_pose[perm] > 1]
+        by_point = perm[np.argsort(obs_point[perm], kind="stable")]
+        first = np.searchsorted(obs_point[by_point], obs_point[by_point], side="left")
+        allowed = np.zeros(M, dtype=bool)
+        allowed[by_point[np.arange(len(by_point)) - first < track - 2]] = True
+        chosen = perm[allowed[perm]][:want]
+        assert len(chosen) == want, "outlier_obs asks for more outliers than the tracks can carry"
+        outlier_mask[chosen] = 1
+        x = rng_obs.uniform(-0.5, 0.5, (want, 2))
+        th = rng_obs.uniform(0, 2 * np.pi, want)
+        a, b = np.cos(th), np.sin(th)
+        lines[chosen] = np.stack([a, b, -(a * x[:, 0] + b * x[:, 1])], axis=1)
+    if quantise_float32:
+        lines = lines.astype(np.float32).astype(np.float64)
+        lines /= np.linalg.norm(lines[:, :2], axis=1, keepdims=True)
 
     if sort == "pose":
         order = np.lexsort((obs_point, obs_pose))
-        obs_pose, obs_point, lines = obs_pose[order], obs_point[order], lines[order]
+        obs_pose, obs_point, lines, outlier_mask = obs_pose[order], obs_point[order], lines[order], outlier_mask[order]
 
     poses = poses_gt.copy()
     points = points_gt + rng.normal(0, noise_point, (P, 3))
@@ -156,7 +187,7 @@ def make_ba_scene(num_cams, num_points, track, seed=0xC0FFEE, model=2, num_intri
                 obs_point=np.ascontiguousarray(obs_point), pose_camera=pose_camera, camera_model=camera_model,
                 poses=poses, points=points, intr=intr, gt_poses=poses_gt, gt_points=points_gt,
                 pose_const=pose_const, tvec_const_mask=tvec_const_mask, point_const=point_const,
-                camera_const_mask=camera_const_mask, loss_type=0, loss_scale=1.0)
+                camera_const_mask=camera_const_mask, loss_type=0, loss_scale=1.0, outlier_mask=np.ascontiguousarray(outlier_mask))
 
 
 def shuffle_image_ids(scene, seed=0):
