@@ -34,6 +34,7 @@
 #include <thread>
 
 #include "ba_impl.hpp"
+#include "lm_policy.hpp"
 #include "resource_pool.hpp"
 #include "line_residual.hpp"
 #include "rccl_comm.hpp"
@@ -1388,6 +1389,16 @@ static int LaunchNorms(pp_ba_impl* h, bool with_step, int fold = 0, double* host
   return PP_OK;
 }
 
+// the group exchange's packed copy of S holds at least `count` doubles (grown, never shrunk; the old content is not kept)
+static int EnsureSpack(pp_ba_impl* h, int64_t count) {
+  if (h->Spack_cap >= count) return PP_OK;
+  if (h->Spack) PoolDeviceFree(h->Spack);
+  h->Spack = nullptr; h->Spack_cap = 0;
+  const int rc = HandleAlloc(&h->Spack, (size_t)count);
+  if (rc == PP_OK) h->Spack_cap = count;
+  return rc;
+}
+
 // assemble the damped reduced system for `radius` into S (lower triangle + rhs row)
 static int AssembleReducedSystem(pp_ba_impl* h, double radius, bool refresh_diagonal = false, double dmin = 0.0, double dmax = 0.0) {
   hipStream_t s = h->stream;
@@ -1403,14 +1414,9 @@ static int AssembleReducedSystem(pp_ba_impl* h, double radius, bool refresh_diag
   {      // (V + D^2 / radius)^-1, V^-1 b_p per point and the per-observation records: one launch
     const int point_blocks = CeilDiv(refresh_diagonal ? std::max(h->P, 6 * h->C) : h->P, 256);
     const dim3 grid(point_blocks + h->num_partials + zero_tiles);
-    if (refresh_diagonal)
-      hipLaunchKernelGGL(k_prepare<true>, grid, dim3(256), 0, s, point_blocks, h->P, h->V, h->gp, h->scale_p, h->diag_p, h->point_const, 1.0 / radius, h->Vinv, h->vb,
-                         h->d_flag, h->C, h->U, h->scale_c, dmin, dmax, h->diag_c, h->M, h->obs_pose, h->obs_point, h->Jpose, h->Jpoint, h->JpS, h->num_partials, h->S, h->N,
-                         (const int32_t*)h->nz_tile_list);
-    else
-      hipLaunchKernelGGL(k_prepare<false>, grid, dim3(256), 0, s, point_blocks, h->P, h->V, h->gp, h->scale_p, h->diag_p, h->point_const, 1.0 / radius, h->Vinv, h->vb,
-                         h->d_flag, h->C, h->U, h->scale_c, dmin, dmax, h->diag_c, h->M, h->obs_pose, h->obs_point, h->Jpose, h->Jpoint, h->JpS, h->num_partials, h->S, h->N,
-                         (const int32_t*)h->nz_tile_list);
+    hipLaunchKernelGGL(refresh_diagonal ? k_prepare<true> : k_prepare<false>, grid, dim3(256), 0, s, point_blocks, h->P, h->V, h->gp, h->scale_p, h->diag_p, h->point_const,
+                       1.0 / radius, h->Vinv, h->vb, h->d_flag, h->C, h->U, h->scale_c, dmin, dmax, h->diag_c, h->M, h->obs_pose, h->obs_point, h->Jpose, h->Jpoint, h->JpS,
+                       h->num_partials, h->S, h->N, (const int32_t*)h->nz_tile_list);
   }
   SchurArgs a = MakeSchurArgs(h, radius);
   if (h->iterative) { a.Sd = h->pcg_Sd; a.rhs_out = h->pcg_b; }
@@ -1466,7 +1472,7 @@ static int AssembleReducedSystem(pp_ba_impl* h, double radius, bool refresh_diag
   { const int rc = IntrAssemble(h, 1.0 / radius, a.add_diagonal); if (rc) return rc; }
   if (InGroup(h) && SparseActive(h) && h->nz_tile_list && h->num_nz_tiles > 0) {      // the non-zero tiles, packed (every rank has the group's tile map)
     const int64_t count = (int64_t)h->num_nz_tiles * 64 * 64;
-    if (h->Spack_cap < count) { if (h->Spack) PoolDeviceFree(h->Spack); h->Spack = nullptr; h->Spack_cap = 0; const int rc = HandleAlloc(&h->Spack, (size_t)count); if (rc) return rc; h->Spack_cap = count; }
+    if (const int rc = EnsureSpack(h, count)) return rc;
     hipLaunchKernelGGL(k_pack_tiles, dim3(h->num_nz_tiles), dim3(256), 0, s, h->S, h->N, (const int32_t*)h->nz_tile_list, h->Spack, 0, (double*)nullptr);
     const int rc = GroupReduce(h, h->Spack, count, PP_REDUCE_SUM);
     if (rc) return rc;
@@ -1475,7 +1481,7 @@ static int AssembleReducedSystem(pp_ba_impl* h, double radius, bool refresh_diag
   } else if (InGroup(h)) {      // lower triangle + rhs row, packed: half the bytes of the rectangle on the wire (RCCL or the host callback)
     const int rows = h->n_red + 1;
     const int64_t count = (int64_t)rows * (rows + 1) / 2;
-    if (h->Spack_cap < count) { if (h->Spack) PoolDeviceFree(h->Spack); h->Spack = nullptr; h->Spack_cap = 0; const int rc = HandleAlloc(&h->Spack, (size_t)count); if (rc) return rc; h->Spack_cap = count; }
+    if (const int rc = EnsureSpack(h, count)) return rc;
     const dim3 grid(std::max(1, std::min(64, CeilDiv(rows, 256))), rows);
     hipLaunchKernelGGL(k_pack_lower, grid, dim3(256), 0, s, h->S, h->N, rows, h->Spack, 0, (double*)nullptr);
     const int rc = GroupReduce(h, h->Spack, count, PP_REDUCE_SUM);
@@ -1536,6 +1542,204 @@ struct PhaseTimer {
     n = 0;
   }
 };
+
+
+// The start of a solve at the handle's parameters: the failure bits cleared, K1 + K2 there, and the Jacobi scale, which stays what it is here for the
+// whole solve (pp_ba_solve goes on with the gradient norm, pp_ba_reduced_system with one LM diagonal and one assembly).
+static int EvaluateAndScale(pp_ba_impl* h, const pp_ba_options* o, bool fold, PhaseTimer& timer) {
+  PP_HIP_TRY(hipMemsetAsync(h->d_flag, 0, 4 * sizeof(int32_t), h->stream));     // failure bits, the Cholesky token, the norms kernel's block counter
+  if (const int rc = EvaluateAndReduce(h, fold)) return rc;
+  timer.Mark(PP_BA_T_EVAL);
+  const int grid = CeilDiv(std::max<int64_t>(6 * (int64_t)h->C, 3 * (int64_t)h->P), 256);
+  hipLaunchKernelGGL(k_jacobi_scale, dim3(grid), dim3(256), 0, h->stream, h->C, h->P, h->U, h->V, h->pose_const, h->tvec_mask, h->point_const,
+                     o->jacobi_scaling, h->scale_c, h->scale_p);
+  return IntrScale(h, o->jacobi_scaling);
+}
+
+// How a solve enqueues its trial steps and gets their scalars: decided once, from the handle and the options, and the same for every iteration.
+struct StepPlan {
+  bool fold;                // the norms kernel sums the cost partials (a host-callback all-reduce needs the sums before it; RCCL reduces what the norms kernel folded)
+  bool speculate;           // the accept path is enqueued before the verdict is known (see Speculation); not with a host-callback all-reduce
+  bool direct;              // the norms kernel hands the scalars to the pinned host slot itself (no copy-engine hop) when nothing else touches them after it:
+                            // no group all-reduce, no intrinsics norms kernel (LaunchNorms sees to the latter)
+  bool fused_trial_cost;    // the cost at the trial point inside the step kernel (one launch less) whenever its partials are summed by the norms kernel anyway
+  bool fused_step;          // point steps, model cost change, trial point and its cost in one pass (variable intrinsics: k_step_points<true>, the trial intrinsics applied before it)
+  bool phase_timings;
+};
+static StepPlan MakeStepPlan(const pp_ba_impl* h, const pp_ba_options* o) {
+  StepPlan p;
+  p.fold = h->allreduce == nullptr;
+  p.speculate = h->allreduce == nullptr;
+  p.direct = p.speculate && !InGroup(h) && h->h_scal_dev != nullptr;
+  p.fused_trial_cost = p.fold && (h->NI == 0 || h->sw.ba_fused_step) && h->sw.ba_fused_trial_cost;
+  p.fused_step = p.fused_trial_cost && h->sw.ba_fused_step;
+  p.phase_timings = o->phase_timings != 0;
+  return p;
+}
+
+// One trial step for `radius` from the current point, straight down the stream: LM diagonal (when the point is new), reduced system, linear solve, point
+// steps + model cost change + trial point in the candidate buffers, its cost, and the norms kernel that gathers the step's scalars (and hands them to
+// the host under *ticket when plan.direct).  Waits for nothing and touches nothing of the current point.
+static int EnqueueTrialStep(pp_ba_impl* h, const pp_ba_options* o, const StepPlan& plan, double radius, bool refresh_diagonal, PhaseTimer& timer, unsigned long long* ticket) {
+  hipStream_t s = h->stream;
+  const int grid_obs = h->num_partials;
+  int rc;
+  if (refresh_diagonal && (rc = IntrDiagonal(h, o->min_lm_diagonal, o->max_lm_diagonal))) return rc;
+  if ((rc = AssembleReducedSystem(h, radius, refresh_diagonal, o->min_lm_diagonal, o->max_lm_diagonal))) return rc;
+  timer.Mark(PP_BA_T_SCHUR);
+  if (h->iterative) {
+    int cg = 0;
+    if ((rc = PcgSolve(h, radius, o->max_linear_solver_iterations, o->eta, &cg))) return rc;
+    h->linear_solver_iterations += cg;
+  } else {
+    if ((rc = CholeskySolve(h->chol))) return rc;
+    if (!h->spos_identity) hipLaunchKernelGGL(k_gather_step, dim3(CeilDiv(h->n_red, 256)), dim3(256), 0, s, h->n_red, h->spos, h->step_s, h->step_c);
+  }
+  timer.Mark(PP_BA_T_CHOLESKY);
+  StepArgs sa = MakeStepArgs(h);
+  if (plan.fused_trial_cost) {
+    sa.cand_partials = h->partials; sa.la = h->la; sa.lb = h->lb; sa.lc = h->lc; sa.poses = h->poses; sa.points = h->points; sa.intr = h->intr;
+    sa.loss_type = h->loss_type; sa.loss_scale = h->loss_scale;
+  }
+  h->trial_partials = 0;
+  if (plan.fused_step) {
+    const int point_blocks = CeilDiv(4 * (int64_t)h->P, 256);
+    h->trial_partials = point_blocks;
+    if (h->NI > 0) {
+      hipLaunchKernelGGL(k_apply_intr, dim3(CeilDiv(h->K * kCamStride, 256)), dim3(256), 0, s, h->K, h->C, h->intr_off, h->intr_col, h->intr, h->scale_c, h->step_c, h->intr_c);
+      sa.intr = h->intr_c;      // (the trial residuals are taken with the trial intrinsics)
+    }
+    hipLaunchKernelGGL(h->NI > 0 ? k_step_points<true> : k_step_points<false>, dim3(point_blocks + CeilDiv(h->C, 256)), dim3(256), 0, s, sa, point_blocks, h->poses, h->points,
+                       h->poses_c, h->points_c);
+  } else {
+    hipLaunchKernelGGL(k_backsub_points, dim3(CeilDiv(4 * (int64_t)h->P, 256)), dim3(256), 0, s, sa);
+    hipLaunchKernelGGL(k_model_cost_apply, dim3(grid_obs + CeilDiv(std::max(h->C, h->P), 256)), dim3(256), 0, s, sa, grid_obs, h->poses, h->points,
+                       h->poses_c, h->points_c);
+  }
+  if (!plan.fold) hipLaunchKernelGGL(k_sum, dim3(1), dim3(256), 0, s, sa.partials, grid_obs, h->scal + kModelChange);
+  timer.Mark(PP_BA_T_BACKSUB);
+  if (h->NI > 0 && !plan.fused_step)
+    hipLaunchKernelGGL(k_apply_intr, dim3(CeilDiv(h->K * kCamStride, 256)), dim3(256), 0, s, h->K, h->C, h->intr_off, h->intr_col, h->intr, h->scale_c,
+                       h->step_c, h->intr_c);
+  if (!plan.fused_trial_cost && (rc = LaunchCostOnly(h, h->poses_c, h->points_c, h->NI > 0 ? h->intr_c : nullptr, plan.fold ? nullptr : h->scal + kCostCand))) return rc;
+  PP_HIP_TRY(hipGetLastError());
+  if (h->allreduce) {      // (host callback: the two sums exist before the norms kernel here; with RCCL the norms call reduces what it folded)
+    if ((rc = GroupReduce(h, h->scal + kCostCand, 2, PP_REDUCE_SUM))) return rc;   // kCostCand, kModelChange are adjacent
+  }
+  *ticket = plan.direct ? ++h->ticket_seq : 0;
+  if ((rc = LaunchNorms(h, true, plan.fold ? 2 : 0, plan.direct ? h->h_scal_dev : nullptr, *ticket))) return rc;
+  timer.Mark(PP_BA_T_UPDATE_COST);
+  return PP_OK;
+}
+
+// Latency hiding around the verdict on a trial step.
+//
+// Speculative acceptance: almost every trial step is accepted, and the accept decision needs a host round trip (~30 us of idle GPU, after which the
+// host has to catch up launching ~15 kernels).  So the accept path - make the candidate the current point (a swap of buffer pointers, no copies),
+// evaluate + reduce there, norms - is enqueued BEFORE the host waits for the trial step's scalars, and the wait is on their ticket or on an event
+// recorded right after their copy, never on the stream.  Invariant: while `speculated`, h->poses / h->points hold the CANDIDATE and the Jacobians and
+// sums on the device are the candidate's; Keep or Undo ends that state, and every verdict goes through one of the two.
+//
+// Pending evaluation: the evaluation at an accepted point (cost, gradient max-norm) is only enqueued; its two scalars are first needed after the next
+// trial step's own read-back, so an accepted iteration synchronises with the host once, not twice.  Invariant: while `pending`, `pending_slot` is the
+// host slot that evaluation was enqueued into - fixed by Keep, so a later speculation, which flips `eval_slot` for ITS evaluation, cannot redirect it.
+// The sequence of accepted points, costs, radii and the termination are those of the eager loop.
+struct Speculation {
+  pp_ba_impl* const h;
+  const StepPlan plan;
+  bool speculated = false, pending = false;
+  int eval_slot = 0;                       // one of two host slots: the next evaluation is enqueued before the pending one is consumed
+  const double* pending_slot = nullptr;
+
+  void SwapPoints() {
+    std::swap(h->poses, h->poses_c); std::swap(h->points, h->points_c);
+    if (h->NI > 0) std::swap(h->intr, h->intr_c);
+  }
+  int EnqueueEvaluation() {      // at h->poses / h->points: K1 + K2, norms, scalars -> the free host slot
+    hipStream_t s = h->stream;
+    int r;
+    if (plan.phase_timings) PP_HIP_TRY(hipEventRecord(h->tev_eval[0], s));
+    if ((r = EvaluateAndReduce(h, plan.fold))) return r;
+    if (plan.phase_timings) PP_HIP_TRY(hipEventRecord(h->tev_eval[1], s));
+    eval_slot ^= 1;
+    if ((r = LaunchNorms(h, false, plan.fold ? 1 : 0, plan.direct ? h->h_scal_dev + kNumScalars * (1 + eval_slot) : nullptr))) return r;
+    if (!plan.direct) PP_HIP_TRY(hipMemcpyAsync(h->h_scal + kNumScalars * (1 + eval_slot), h->scal, sizeof(double) * kNumScalars, hipMemcpyDeviceToHost, s));
+    return PP_OK;
+  }
+  // the trial step's scalars (and a pending evaluation's, enqueued before them) are in host memory when this returns; with plan.speculate the accept
+  // path is on the stream by then, and the host has not waited on the stream
+  int AwaitTrialStep(unsigned long long ticket) {
+    if (!plan.speculate) return ReadScalars(h);
+    if (!plan.direct) {
+      PP_HIP_TRY(hipMemcpyAsync(h->h_scal, h->scal, sizeof(double) * kNumScalars, hipMemcpyDeviceToHost, h->stream));
+      PP_HIP_TRY(hipEventRecord(h->ev_readback, h->stream));
+    }
+    SwapPoints();
+    if (const int rc = EnqueueEvaluation()) return rc;
+    speculated = true;
+    if (plan.direct) return WaitTicket(h, ticket);
+    PP_HIP_TRY(hipEventSynchronize(h->ev_readback));
+    return PP_OK;
+  }
+  // the step was accepted: the candidate is the current point and its evaluation is pending
+  int Keep() {
+    if (!speculated) {
+      SwapPoints();
+      if (const int rc = EnqueueEvaluation()) return rc;
+    }
+    speculated = false;
+    pending_slot = h->h_scal + kNumScalars * (1 + eval_slot);
+    pending = true;
+    return PP_OK;
+  }
+  // the step was not accepted: the old point is current again; `reevaluate` restores its Jacobians and sums, which a solve that goes on needs (the
+  // result is what the policy already holds and is never consumed)
+  int Undo(bool reevaluate) {
+    if (!speculated) return PP_OK;
+    speculated = false;
+    SwapPoints();
+    return reevaluate ? EnqueueEvaluation() : PP_OK;
+  }
+  // requires the pending evaluation to have reached its slot (a later read-back on the same stream has arrived, or the stream was synchronised)
+  void Resolve(LmPolicy* policy) {
+    policy->Resolve(pending_slot[kCost], pending_slot[kGradMax]);
+    float ms = 0;
+    if (plan.phase_timings && hipEventElapsedTime(&ms, h->tev_eval[0], h->tev_eval[1]) == hipSuccess) { h->timings_ms[PP_BA_T_EVAL] += ms; h->timing_calls[PP_BA_T_EVAL] += 1; }
+    pending = false;
+  }
+};
+
+// After a trial step that raised failure bits: the bits are cleared and so is what the failed run left in buffers that the assembly relies on but never
+// rewrites (the zero padding of S).  Bit 4, a bounded wait of the one-launch factorisation (k_cholesky_tasks) that ran out: nothing wrong with the
+// system - *retry = the handle switched to one launch per block column (it stays with them) and the same step is to be made again.  Bit 1, a
+// non-positive pivot: the factorisation leaves NaN where it stopped, on which the next, more strongly damped system would fail too; also in the factor
+// array.  An iterative handle has no S (its conjugate-gradient loop raises the same bit).
+static int RecoverAfterFlag(pp_ba_impl* h, int32_t flag, bool* retry) {
+  *retry = false;
+  if (flag == 0) return PP_OK;
+  hipStream_t s = h->stream;
+  PP_HIP_TRY(hipMemsetAsync(h->d_flag, 0, sizeof(int32_t), s));
+  *retry = (flag & 4) && CholeskyFallBackToColumns(h->chol);
+  const bool failed_pivot = !*retry && (flag & 1) && !h->iterative && h->S;
+  if (*retry || failed_pivot) PP_HIP_TRY(hipMemsetAsync(h->S, 0, sizeof(double) * (size_t)h->N * h->N, s));
+  if (failed_pivot && h->Lfac) PP_HIP_TRY(hipMemsetAsync(h->Lfac, 0, sizeof(double) * (size_t)h->N * h->N, s));
+  return PP_OK;
+}
+
+// ceres::IterationCallback with the policy's last row; true = the callback ended the solve (termination set).  Every row is followed by exactly one
+// call, so the iteration number is the row's index.
+static bool UserStops(const pp_ba_options* o, LmPolicy* policy) {
+  if (!o->iteration_callback) return false;
+  const double* row = policy->last_row();
+  pp_ba_iteration_summary it;
+  it.iteration = policy->iteration() - 1; it.step_is_successful = row[6] != 0.0;
+  it.cost = row[0]; it.cost_change = row[1]; it.gradient_max_norm = row[2]; it.step_norm = row[3]; it.relative_decrease = row[4];
+  it.trust_region_radius = row[5];
+  const int32_t r = o->iteration_callback(o->iteration_callback_ctx, &it);
+  if (r == PP_SOLVER_ABORT) policy->termination = PP_TERM_USER_FAILURE;
+  if (r == PP_SOLVER_TERMINATE_SUCCESSFULLY) policy->termination = PP_TERM_USER_SUCCESS;
+  return r == PP_SOLVER_ABORT || r == PP_SOLVER_TERMINATE_SUCCESSFULLY;
+}
 
 }  // namespace ppsfm
 
@@ -1662,14 +1866,11 @@ int pp_ba_reduced_system(pp_ba_handle h, const pp_ba_options* o, double radius, 
   int rc;
   if ((rc = BaEnsureJacobianBuffers(h, 0, h->NI > 0 ? 1 : 0))) return rc;
   if ((rc = EnsureSolverBuffers(h))) return rc;
-  PP_HIP_TRY(hipMemsetAsync(h->d_flag, 0, sizeof(int32_t), h->stream));
-  if ((rc = EvaluateAndReduce(h))) return rc;
+  PhaseTimer untimed(h, false);
+  if ((rc = EvaluateAndScale(h, o, false, untimed))) return rc;
   const int grid = CeilDiv(std::max<int64_t>(6 * (int64_t)h->C, 3 * (int64_t)h->P), 256);
-  hipLaunchKernelGGL(k_jacobi_scale, dim3(grid), dim3(256), 0, h->stream, h->C, h->P, h->U, h->V, h->pose_const, h->tvec_mask, h->point_const,
-                     o->jacobi_scaling, h->scale_c, h->scale_p);
   hipLaunchKernelGGL(k_lm_diagonal, dim3(grid), dim3(256), 0, h->stream, h->C, h->P, h->U, h->V, h->scale_c, h->scale_p, o->min_lm_diagonal,
                      o->max_lm_diagonal, h->diag_c, h->diag_p);
-  if ((rc = IntrScale(h, o->jacobi_scaling))) return rc;
   if ((rc = IntrDiagonal(h, o->min_lm_diagonal, o->max_lm_diagonal))) return rc;
   if ((rc = AssembleReducedSystem(h, radius))) return rc;
   const int n = h->n_red;
@@ -1706,278 +1907,94 @@ int pp_ba_solve(pp_ba_handle h, const pp_ba_options* o, pp_ba_summary* sum) try 
   h->trace.clear();
   h->linear_solver_iterations = 0;
   for (int i = 0; i < PP_BA_T_COUNT; ++i) { h->timings_ms[i] = 0; h->timing_calls[i] = 0; }
-  PP_HIP_TRY(hipMemsetAsync(h->d_flag, 0, 4 * sizeof(int32_t), s));     // failure bits, the Cholesky token, the norms kernel's block counter
   PP_HIP_TRY(hipMemsetAsync(h->step_c, 0, sizeof(double) * h->N, s));
   PP_HIP_TRY(hipEventRecord(h->ev0, s));
-  const bool phase_timings = o->phase_timings != 0;
-  PhaseTimer timer(h, phase_timings);
-
-  const int grid_cp = CeilDiv(std::max<int64_t>(6 * (int64_t)h->C, 3 * (int64_t)h->P), 256);
-  const int grid_obs = h->num_partials;
+  const StepPlan plan = MakeStepPlan(h, o);
 
   // iteration 0: evaluate, Jacobi scale, gradient norm
-  const bool fold = h->allreduce == nullptr;     // (a host-callback all-reduce needs the sums before the norms kernel; RCCL reduces what the norms kernel folded)
-  if ((rc = EvaluateAndReduce(h, fold))) return rc;
-  timer.Mark(PP_BA_T_EVAL);
-  hipLaunchKernelGGL(k_jacobi_scale, dim3(grid_cp), dim3(256), 0, s, h->C, h->P, h->U, h->V, h->pose_const, h->tvec_mask, h->point_const,
-                     o->jacobi_scaling, h->scale_c, h->scale_p);
-  if ((rc = IntrScale(h, o->jacobi_scaling))) return rc;
-  // the scalars reach the host without the copy engine when nothing else touches them after the norms kernel (see below)
-  const bool direct0 = !InGroup(h) && h->h_scal_dev != nullptr;
-  if (direct0) {
-    const unsigned long long ticket0 = ++h->ticket_seq;
-    if ((rc = LaunchNorms(h, false, fold ? 1 : 0, h->h_scal_dev, ticket0))) return rc;
-    if ((rc = WaitTicket(h, ticket0))) return rc;
-  } else {
-    if ((rc = LaunchNorms(h, false, fold ? 1 : 0))) return rc;
-    if ((rc = ReadScalars(h))) return rc;
-  }
-  timer.Collect();
-  double cost = h->h_scal[kCost], gmax = h->h_scal[kGradMax];
-  sum->initial_cost = cost;
-  sum->num_residuals = (int32_t)(2 * h->M);
-  double radius = o->initial_trust_region_radius, decrease_factor = 2.0;
-  bool reuse_diagonal = false, last_successful = true;
-  int invalid = 0;
-  auto push = [&](double c, double dc, double g, double sn, double rel, double rad, int ok) {
-    const double row[7] = {c, dc, g, sn, rel, rad, (double)ok};
-    h->trace.insert(h->trace.end(), row, row + 7);
-  };
-  push(cost, 0, gmax, 0, 0, radius, 1);
-  sum->termination = PP_TERM_NO_CONVERGENCE;
-  if (!std::isfinite(cost)) { sum->termination = PP_TERM_FAILURE; SetLastError("pp_ba_solve: initial cost is not finite"); }
-  // ceres::IterationCallback: called with the last trace row; true = the callback ended the solve (termination set)
-  int cb_iteration = 0;
-  auto user_callback = [&]() -> bool {
-    if (!o->iteration_callback) return false;
-    const double* row = h->trace.data() + h->trace.size() - 7;
-    pp_ba_iteration_summary it;
-    it.iteration = cb_iteration++; it.step_is_successful = row[6] != 0.0;
-    it.cost = row[0]; it.cost_change = row[1]; it.gradient_max_norm = row[2]; it.step_norm = row[3]; it.relative_decrease = row[4];
-    it.trust_region_radius = row[5];
-    const int32_t r = o->iteration_callback(o->iteration_callback_ctx, &it);
-    if (r == PP_SOLVER_ABORT) { sum->termination = PP_TERM_USER_FAILURE; return true; }
-    if (r == PP_SOLVER_TERMINATE_SUCCESSFULLY) { sum->termination = PP_TERM_USER_SUCCESS; return true; }
-    return false;
-  };
-  bool user_stop = sum->termination != PP_TERM_FAILURE && user_callback();
-
-  // After an accepted step the evaluation at the new point (cost, gradient max-norm) is only ENQUEUED: its two scalars
-  // are first needed after the next trial step's own read-back, so a successful iteration synchronises with the
-  // host once, not twice.  The gradient-tolerance test is applied when they arrive; if it fires, the trial step that
-  // was computed speculatively is simply dropped (the trial point lives in separate buffers), so the sequence of
-  // accepted points and the termination are exactly those of the eager loop.
-  bool pending = false;
-  double* h_eval = h->h_scal + kNumScalars;     // one of two slots (the next evaluation is enqueued before this one is consumed)
-  int eval_slot = 0;
-  // Speculative acceptance.  Almost every trial step is accepted, and the accept decision needs a host round trip
-  // (~30 us of idle GPU, after which the host has to catch up launching ~15 kernels).  So the accept path — make the
-  // candidate the current point, evaluate + reduce there, norms, read-back — is enqueued BEFORE the host waits for the
-  // trial step's scalars; the wait is on an event recorded right after their copy, not on the stream.  The candidate
-  // becomes current by swapping buffer pointers (no copies).  If the step turns out rejected / invalid, the pointers are
-  // swapped back and the evaluation at the old point is enqueued again (its Jacobians were overwritten): the sequence of
-  // accepted points, costs and radii is that of the eager loop.  Not used with a group all-reduce (host callbacks).
-  const bool speculate = h->allreduce == nullptr;
-  // the norms kernel hands the scalars to the pinned host slot itself (no copy-engine hop) when nothing else touches them
-  // after it: no group all-reduce, no intrinsics norms kernel
-  const bool direct = speculate && !InGroup(h) && h->h_scal_dev != nullptr;
-  auto swap_points = [&]() {
-    std::swap(h->poses, h->poses_c); std::swap(h->points, h->points_c);
-    if (h->NI > 0) std::swap(h->intr, h->intr_c);
-  };
-  auto enqueue_evaluation = [&]() -> int {      // at h->poses / h->points: K1 + K2, norms, scalars -> the free host slot
-    int r;
-    if (phase_timings) PP_HIP_TRY(hipEventRecord(h->tev_eval[0], s));
-    if ((r = EvaluateAndReduce(h, fold))) return r;
-    if (phase_timings) PP_HIP_TRY(hipEventRecord(h->tev_eval[1], s));
-    eval_slot ^= 1;
-    if ((r = LaunchNorms(h, false, fold ? 1 : 0, direct ? h->h_scal_dev + kNumScalars * (1 + eval_slot) : nullptr))) return r;
-    if (!direct) PP_HIP_TRY(hipMemcpyAsync(h->h_scal + kNumScalars * (1 + eval_slot), h->scal, sizeof(double) * kNumScalars, hipMemcpyDeviceToHost, s));
-    return PP_OK;
-  };
-  auto resolve = [&]() {   // requires the stream to be synchronised past the enqueued evaluation
-    cost = h_eval[kCost]; gmax = h_eval[kGradMax];
-    double* row = h->trace.data() + h->trace.size() - 7;
-    row[0] = cost; row[2] = gmax;
-    float ms = 0;
-    if (phase_timings && hipEventElapsedTime(&ms, h->tev_eval[0], h->tev_eval[1]) == hipSuccess) { h->timings_ms[PP_BA_T_EVAL] += ms; h->timing_calls[PP_BA_T_EVAL] += 1; }
-    pending = false;
-  };
-  // (variable intrinsics take the fused step kernel - k_step_points<true>, the trial intrinsics applied before it - and keep the separate kernels otherwise)
-  const bool fused_step_allowed = h->sw.ba_fused_step;
-  const bool fused_trial_cost = fold && (h->NI == 0 || fused_step_allowed) && h->sw.ba_fused_trial_cost;
-  const bool fused_step = fused_trial_cost && fused_step_allowed;
-  for (int iter = 1; sum->termination != PP_TERM_FAILURE && !user_stop; ++iter) {
-    if (pending && (iter > o->max_num_iterations || radius < o->min_trust_region_radius)) {
-      PP_HIP_TRY(hipStreamSynchronize(s));
-      resolve();
-    }
-    if (!pending && last_successful && gmax <= o->gradient_tolerance) { sum->termination = PP_TERM_CONVERGENCE; break; }
-    if (iter > o->max_num_iterations) { sum->termination = PP_TERM_NO_CONVERGENCE; break; }
-    if (radius < o->min_trust_region_radius) { sum->termination = PP_TERM_CONVERGENCE; break; }
-
-    PhaseTimer t2(h, phase_timings);
-    if (!reuse_diagonal && (rc = IntrDiagonal(h, o->min_lm_diagonal, o->max_lm_diagonal))) return rc;
-    if ((rc = AssembleReducedSystem(h, radius, !reuse_diagonal, o->min_lm_diagonal, o->max_lm_diagonal))) return rc;
-    t2.Mark(PP_BA_T_SCHUR);
-    if (h->iterative) {
-      int cg = 0;
-      if ((rc = PcgSolve(h, radius, o->max_linear_solver_iterations, o->eta, &cg))) return rc;
-      h->linear_solver_iterations += cg;
+  {
+    PhaseTimer timer(h, plan.phase_timings);
+    if ((rc = EvaluateAndScale(h, o, plan.fold, timer))) return rc;
+    if (!InGroup(h) && h->h_scal_dev != nullptr) {      // the scalars reach the host without the copy engine when nothing else touches them after the norms kernel
+      const unsigned long long ticket = ++h->ticket_seq;
+      if ((rc = LaunchNorms(h, false, plan.fold ? 1 : 0, h->h_scal_dev, ticket))) return rc;
+      if ((rc = WaitTicket(h, ticket))) return rc;
     } else {
-      if ((rc = CholeskySolve(h->chol))) return rc;
-      if (!h->spos_identity) hipLaunchKernelGGL(k_gather_step, dim3(CeilDiv(h->n_red, 256)), dim3(256), 0, s, h->n_red, h->spos, h->step_s, h->step_c);
-    }
-    t2.Mark(PP_BA_T_CHOLESKY);
-    reuse_diagonal = true;
-    StepArgs sa = MakeStepArgs(h);
-    // the cost at the trial point inside k_model_cost_apply (one launch less) whenever its partials are summed by the norms kernel anyway
-    if (fused_trial_cost) {
-      sa.cand_partials = h->partials; sa.la = h->la; sa.lb = h->lb; sa.lc = h->lc; sa.poses = h->poses; sa.points = h->points; sa.intr = h->intr;
-      sa.loss_type = h->loss_type; sa.loss_scale = h->loss_scale;
-    }
-    h->trial_partials = 0;
-    if (fused_step) {      // point steps, model cost change, trial point and its cost: one pass over the observations
-      const int point_blocks = CeilDiv(4 * (int64_t)h->P, 256);
-      h->trial_partials = point_blocks;
-      if (h->NI > 0) {
-        hipLaunchKernelGGL(k_apply_intr, dim3(CeilDiv(h->K * kCamStride, 256)), dim3(256), 0, s, h->K, h->C, h->intr_off, h->intr_col, h->intr, h->scale_c, h->step_c, h->intr_c);
-        sa.intr = h->intr_c;      // (the trial residuals are taken with the trial intrinsics)
-        hipLaunchKernelGGL(k_step_points<true>, dim3(point_blocks + CeilDiv(h->C, 256)), dim3(256), 0, s, sa, point_blocks, h->poses, h->points, h->poses_c, h->points_c);
-      } else
-      hipLaunchKernelGGL(k_step_points<false>, dim3(point_blocks + CeilDiv(h->C, 256)), dim3(256), 0, s, sa, point_blocks, h->poses, h->points, h->poses_c, h->points_c);
-    } else {
-      hipLaunchKernelGGL(k_backsub_points, dim3(CeilDiv(4 * (int64_t)h->P, 256)), dim3(256), 0, s, sa);
-      hipLaunchKernelGGL(k_model_cost_apply, dim3(grid_obs + CeilDiv(std::max(h->C, h->P), 256)), dim3(256), 0, s, sa, grid_obs, h->poses, h->points,
-                         h->poses_c, h->points_c);
-    }
-    if (!fold) hipLaunchKernelGGL(k_sum, dim3(1), dim3(256), 0, s, sa.partials, grid_obs, h->scal + kModelChange);
-    t2.Mark(PP_BA_T_BACKSUB);
-    if (h->NI > 0 && !fused_step)
-      hipLaunchKernelGGL(k_apply_intr, dim3(CeilDiv(h->K * kCamStride, 256)), dim3(256), 0, s, h->K, h->C, h->intr_off, h->intr_col, h->intr, h->scale_c,
-                         h->step_c, h->intr_c);
-    if (!fused_trial_cost && (rc = LaunchCostOnly(h, h->poses_c, h->points_c, h->NI > 0 ? h->intr_c : nullptr, fold ? nullptr : h->scal + kCostCand))) return rc;
-    PP_HIP_TRY(hipGetLastError());
-    if (h->allreduce) {      // (host callback: the two sums exist before the norms kernel here; with RCCL the norms call reduces what it folded)
-      if ((rc = GroupReduce(h, h->scal + kCostCand, 2, PP_REDUCE_SUM))) return rc;   // kCostCand, kModelChange are adjacent
-    }
-    const unsigned long long ticket = direct ? ++h->ticket_seq : 0;
-    if ((rc = LaunchNorms(h, true, fold ? 2 : 0, direct ? h->h_scal_dev : nullptr, ticket))) return rc;
-    t2.Mark(PP_BA_T_UPDATE_COST);
-    bool speculated = false;
-    double* h_eval_prev = h_eval;                 // where a pending evaluation (the previous accepted step's) arrives
-    if (speculate) {
-      if (!direct) {
-        PP_HIP_TRY(hipMemcpyAsync(h->h_scal, h->scal, sizeof(double) * kNumScalars, hipMemcpyDeviceToHost, s));
-        PP_HIP_TRY(hipEventRecord(h->ev_readback, s));
-      }
-      swap_points();
-      if ((rc = enqueue_evaluation())) return rc;
-      speculated = true;
-      if (direct) { if ((rc = WaitTicket(h, ticket))) return rc; }
-      else PP_HIP_TRY(hipEventSynchronize(h->ev_readback));
-    } else {
+      if ((rc = LaunchNorms(h, false, plan.fold ? 1 : 0))) return rc;
       if ((rc = ReadScalars(h))) return rc;
     }
-    // leaves the speculated state: the old point is current again; `reevaluate` restores its Jacobians and sums
-    auto undo_speculation = [&](bool reevaluate) -> int {
-      if (!speculated) return PP_OK;
-      speculated = false;
-      swap_points();
-      if (!reevaluate) return PP_OK;
-      const int r = enqueue_evaluation();       // result identical to what `cost` / `gmax` already hold: never consumed
-      return r;
-    };
-    t2.Collect();
-    if (pending) {
-      h_eval = h_eval_prev;
-      resolve();
-      if (gmax <= o->gradient_tolerance) {   // drops the speculative trial step
-        if ((rc = undo_speculation(false))) return rc;
-        sum->termination = PP_TERM_CONVERGENCE; break;
-      }
-    }
+    timer.Collect();
+  }
+  LmPolicy policy(*o, h->trace);
+  Speculation spec{h, plan};
+  bool go_on = policy.Start(h->h_scal[kCost], h->h_scal[kGradMax]);
+  sum->initial_cost = policy.cost;
+  sum->num_residuals = (int32_t)(2 * h->M);
+  if (!go_on) SetLastError("pp_ba_solve: initial cost is not finite");
+  else go_on = !UserStops(o, &policy);
 
-    const double model_change = h->h_scal[kModelChange], ccost = h->h_scal[kCostCand];
-    const double step_norm = std::sqrt(h->h_scal[kStepNorm2]), x_norm = std::sqrt(h->h_scal[kXNorm2]);
-    bool valid = HostFlag(h) == 0 && std::isfinite(model_change) && model_change > 0.0 && std::isfinite(step_norm);
-    if (HostFlag(h) != 0) PP_HIP_TRY(hipMemsetAsync(h->d_flag, 0, sizeof(int32_t), s));
-    if ((HostFlag(h) & 4) && CholeskyFallBackToColumns(h->chol)) {
-      // a bounded wait of the one-launch factorisation (k_cholesky_tasks) ran out: nothing wrong with the system - the same step again
-      // with one launch per block column, which this handle then stays with
-      PP_HIP_TRY(hipMemsetAsync(h->S, 0, sizeof(double) * (size_t)h->N * h->N, s));      // (the assembly relies on the zero padding it never rewrites; the aborted run may have touched it)
-      if ((rc = undo_speculation(true))) return rc;
-      --iter;
-      continue;
+  while (go_on) {
+    LmNext next = policy.BeforeStep(spec.pending);
+    if (next == LmNext::kResolveFirst) {
+      PP_HIP_TRY(hipStreamSynchronize(s));
+      spec.Resolve(&policy);
+      next = policy.BeforeStep(false);
     }
-    if (!valid) {
-      // a factorisation that met a non-positive pivot leaves NaN where it stopped, also in the zero padding of S that the assembly never rewrites: the
-      // next, more strongly damped system would fail on what this one left behind (an iterative handle has no S: its conjugate-gradient loop raises the same bit)
-      if ((HostFlag(h) & 1) && !h->iterative && h->S) {
-        PP_HIP_TRY(hipMemsetAsync(h->S, 0, sizeof(double) * (size_t)h->N * h->N, s));
-        if (h->Lfac) PP_HIP_TRY(hipMemsetAsync(h->Lfac, 0, sizeof(double) * (size_t)h->N * h->N, s));
-      }
-      ++invalid;
-      if (invalid >= o->max_num_consecutive_invalid_steps) {
-        if ((rc = undo_speculation(false))) return rc;
-        sum->termination = PP_TERM_FAILURE;
-        SetLastError("pp_ba_solve: %d consecutive invalid steps (linear system not positive definite or step without model decrease)", invalid);
+    if (next == LmNext::kStop) break;
+
+    PhaseTimer timer(h, plan.phase_timings);
+    unsigned long long ticket = 0;
+    if ((rc = EnqueueTrialStep(h, o, plan, policy.radius, !policy.reuse_diagonal, timer, &ticket))) return rc;
+    if ((rc = spec.AwaitTrialStep(ticket))) return rc;
+    timer.Collect();
+    if (spec.pending) {      // the previous accepted step's evaluation came with this read-back
+      spec.Resolve(&policy);
+      if (policy.GradientToleranceReached()) {      // drops the trial step that was computed ahead of this test
+        if ((rc = spec.Undo(false))) return rc;
         break;
       }
-      if ((rc = undo_speculation(true))) return rc;
-      radius /= decrease_factor; decrease_factor *= 2.0;
-      push(cost, 0, gmax, 0, 0, radius, 0);
-      ++sum->num_unsuccessful_steps; last_successful = false;
-      user_stop = user_callback();
-      continue;
     }
-    invalid = 0;
-    if (step_norm <= o->parameter_tolerance * (x_norm + o->parameter_tolerance)) {
-      if ((rc = undo_speculation(false))) return rc;
-      sum->termination = PP_TERM_CONVERGENCE; break;
+    LmTrialStep step = {h->h_scal[kModelChange], h->h_scal[kCostCand], h->h_scal[kStepNorm2], h->h_scal[kXNorm2], HostFlag(h), false};
+    if ((rc = RecoverAfterFlag(h, step.flag, &step.retry_after_timeout))) return rc;
+    const LmVerdict verdict = policy.Judge(step);
+    // the one place that leaves the speculated state: the candidate stays the current point, or the old point is current again - evaluated again
+    // (its Jacobians and sums) exactly when the solve goes on from it
+    if ((rc = verdict == LmVerdict::kAccepted ? spec.Keep() : spec.Undo(LmStaysAtOldPoint(verdict)))) return rc;
+    switch (verdict) {
+      case LmVerdict::kInvalidFailed:
+        SetLastError("pp_ba_solve: %d consecutive invalid steps (linear system not positive definite or step without model decrease)", policy.invalid);
+        [[fallthrough]];
+      case LmVerdict::kParameterTolerance:
+      case LmVerdict::kFunctionTolerance:
+        go_on = false;
+        break;
+      case LmVerdict::kRetryAfterTimeout:      // the same step again: no iteration, no row, no callback
+        break;
+      case LmVerdict::kAccepted:
+        if (o->iteration_callback) {     // the callback sees the cost / gradient norm AT the accepted point: wait for its evaluation
+          PP_HIP_TRY(hipStreamSynchronize(s));
+          spec.Resolve(&policy);
+        }
+        [[fallthrough]];
+      case LmVerdict::kInvalid:
+      case LmVerdict::kRejected:
+        go_on = !UserStops(o, &policy);
+        break;
     }
-    const double cost_change = cost - ccost;
-    if (std::fabs(cost_change) <= o->function_tolerance * cost) {
-      if ((rc = undo_speculation(false))) return rc;
-      sum->termination = PP_TERM_CONVERGENCE; break;
-    }
-    const double rel = cost_change / model_change;
-    if (rel > o->min_relative_decrease) {
-      if (!speculated) {     // the candidate becomes the current point; its evaluation is consumed with the next read-back
-        swap_points();
-        if ((rc = enqueue_evaluation())) return rc;
-      }
-      h_eval = h->h_scal + kNumScalars * (1 + eval_slot);
-      pending = true;
-      cost = ccost;     // provisional (the candidate evaluation); replaced by the re-evaluated cost when it arrives
-      radius = radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * rel - 1.0, 3));
-      radius = std::fmin(o->max_trust_region_radius, radius);
-      decrease_factor = 2.0; reuse_diagonal = false;
-      ++sum->num_successful_steps; last_successful = true;
-      push(cost, cost_change, gmax, step_norm, rel, radius, 1);
-      if (o->iteration_callback) {     // the callback sees the cost / gradient norm AT the accepted point: wait for its evaluation
-        PP_HIP_TRY(hipStreamSynchronize(s));
-        resolve();
-      }
-    } else {
-      if ((rc = undo_speculation(true))) return rc;
-      radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true;
-      ++sum->num_unsuccessful_steps; last_successful = false;
-      push(cost, cost_change, gmax, step_norm, rel, radius, 0);
-    }
-    user_stop = user_callback();
   }
   PP_HIP_TRY(hipEventRecord(h->ev1, s));
   PP_HIP_TRY(hipEventSynchronize(h->ev1));
-  if (pending) resolve();
+  if (spec.pending) spec.Resolve(&policy);
   float ms = 0;
   PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  sum->final_cost = cost;
+  sum->termination = policy.termination;
+  sum->final_cost = policy.cost;
+  sum->num_successful_steps = policy.num_successful_steps;
+  sum->num_unsuccessful_steps = policy.num_unsuccessful_steps;
   sum->num_iterations = sum->num_successful_steps + sum->num_unsuccessful_steps;
   sum->device_time_s = ms * 1e-3;
   sum->total_time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-  const int neff = h->num_effective_pose_point + h->NI;     // (three synchronous read-backs of the masks per solve before: ~50 us)
-  sum->num_effective_parameters = neff;
+  sum->num_effective_parameters = h->num_effective_pose_point + h->NI;
   sum->linear_solver_iterations = h->linear_solver_iterations;
   sum->linear_solver = h->iterative ? PP_LINSOLVE_PCG : CholeskyLinsolve(h->chol);
   sum->cholesky_fallbacks = CholeskyFallbacks(h->chol);
