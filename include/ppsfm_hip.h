@@ -276,6 +276,33 @@ int pp_ba_get_create_profile(pp_ba_handle h, double* ms /* 6 */);
 int pp_ba_reduced_system(pp_ba_handle h, const pp_ba_options* options, double radius, int32_t* n, double* S,
                          double* rhs, int64_t capacity);
 
+/* Covariance blocks of poses and points at the handle's current parameters, from the factorised reduced camera system (the counterpart of
+ * ceres::Covariance with apply_loss_function = true; the reference has none).
+ *   H = J^T J, J the LOSS-CORRECTED Jacobian in the tangent coordinates of pp_ba_eval (jac_mode 0: 3 rotation-tangent + 3 tvec coordinates per pose, in that
+ *   order); no Levenberg-Marquardt damping enters and the solver's Jacobi scaling is undone.  No sigma^2 factor is applied: the caller scales, as with Ceres.
+ *   With the points eliminated, S = U - W V^-1 W^T:  Cov(pose i, pose j) = (S^-1)_ij,  Cov(point p) = V_p^-1 + (V_p^-1 W_p^T) S^-1 (W_p V_p^-1).
+ *   Variable intrinsics stay in S, so the pose and point blocks are the correct marginals; the intrinsics' own blocks and the pose-point cross blocks are not
+ *   returned.
+ * pose_i / pose_j (num_pose_pairs each) and point_ids (num_points) are indices in the CALLER's image and point order whatever order the handle uses inside.
+ * pose_cov: num_pose_pairs x 36, block q row-major = Cov(delta_i, delta_j) (the block of (j, i) is its transpose); point_cov: num_points x 9.
+ * Constant blocks follow Ceres' convention: a constant pose has zero rows and columns, a constant tvec component a zero row and column, a constant point a
+ * zero 3 x 3 block.
+ * The call has no side effects on the handle: parameters, Jacobi scale, the reduced system and the factor arrays of the solver are as before, and a
+ * pp_ba_solve after it is bit-identical to one without it.  It works in device buffers of its own (the inverse factor is n^2 doubles: 72 MB at 500 images),
+ * returned to the pool before it returns.  What it does overwrite is the handle's per-evaluation scratch, which every pp_ba_solve / pp_ba_eval /
+ * pp_ba_reduced_system recomputes before reading: residuals and Jacobians, the U and V blocks, the gradients and the scaled gather records.
+ * The factorisation runs on the launch path the handle has bound (per-column launches, one launch, block-sparse), except that a system of at most two
+ * block columns (n <= 128), whose one-workgroup kernel keeps the factor on chip, is factorised by per-column launches that leave it in memory.
+ * Errors: PP_ERR_INVALID for an index out of range (before any device work), for an iterative handle (no reduced system exists) and for a handle attached to
+ * a group (it holds one shard of the points); PP_ERR_NUMERIC when the undamped system is not positive definite (a free gauge, a point seen along one
+ * direction only) - the handle solves as usual afterwards.
+ * info (may be NULL): n = order of the reduced system, path = PP_LINSOLVE_* of the factorisation, device_ms = HIP-event time of the whole device path. */
+typedef struct pp_ba_covariance_info { int32_t n; int32_t path; double device_ms; double reserved[2]; } pp_ba_covariance_info;
+int pp_ba_covariance(pp_ba_handle h, const pp_ba_options* options,
+                     int32_t num_pose_pairs, const int32_t* pose_i, const int32_t* pose_j, double* pose_cov /* pairs x 36, row-major */,
+                     int32_t num_points, const int32_t* point_ids, double* point_cov /* points x 9 */,
+                     pp_ba_covariance_info* info /* may be NULL */);
+
 /* Multi-GPU hook: one BA whose POINTS (with their observations) are sharded across the
  * ranks of a group; poses/intrinsics are replicated.  Each rank creates its handle from its own shard
  * of the observations (same pose/point/camera index spaces, points it does not own simply have no

@@ -23,6 +23,7 @@
 #include <limits>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../include/ppsfm_hip.h"
@@ -223,6 +224,30 @@ class BundleAdjustmentProblem {
     if (rc == PP_ERR_NUMERIC) return false;
     Check(rc);
     return true;
+  }
+  // pp_ba_covariance at the current parameters (the counterpart of ceres::Covariance with apply_loss_function = true, no sigma^2 factor): pose_pairs = (i, j)
+  // in the descriptor's image order, pose_cov = one row-major 6 x 6 block Cov(delta_i, delta_j) per pair (tangent order: 3 rotation, 3 tvec); point_ids in the
+  // descriptor's point order, point_cov = one 3 x 3 block per point.  Either output may be null when its request is empty.  Returns false when the undamped
+  // reduced system is not positive definite (a free gauge, a point seen along one direction only); throws for an iterative or group-attached handle and
+  // for an index out of range.
+  bool Covariance(const pp_ba_options& options, const std::vector<std::pair<int32_t, int32_t>>& pose_pairs, std::vector<double>* pose_cov,
+                  const std::vector<int32_t>& point_ids, std::vector<double>* point_cov, pp_ba_covariance_info* info = nullptr) {
+    std::vector<int32_t> pi(pose_pairs.size()), pj(pose_pairs.size());
+    for (size_t q = 0; q < pose_pairs.size(); ++q) { pi[q] = pose_pairs[q].first; pj[q] = pose_pairs[q].second; }
+    if (pose_cov) pose_cov->assign(36 * pose_pairs.size(), 0.0);
+    if (point_cov) point_cov->assign(9 * point_ids.size(), 0.0);
+    const int rc = pp_ba_covariance(h_, &options, static_cast<int32_t>(pi.size()), pi.data(), pj.data(), pose_cov ? pose_cov->data() : nullptr,
+                                    static_cast<int32_t>(point_ids.size()), point_ids.data(), point_cov ? point_cov->data() : nullptr, info);
+    if (rc == PP_ERR_NUMERIC) return false;
+    Check(rc);
+    return true;
+  }
+  // every diagonal pose block (i, i), in image order
+  bool Covariance(const pp_ba_options& options, std::vector<double>* pose_cov, const std::vector<int32_t>& point_ids, std::vector<double>* point_cov,
+                  pp_ba_covariance_info* info = nullptr) {
+    std::vector<std::pair<int32_t, int32_t>> pairs;
+    for (int32_t i = 0; i < C_; ++i) pairs.emplace_back(i, i);
+    return Covariance(options, pairs, pose_cov, point_ids, point_cov, info);
   }
   pp_ba_handle handle() const { return h_; }
 

@@ -577,6 +577,28 @@ class BundleAdjuster:
         self.write_back(reconstruction, flat, poses, points, intr)
         return True
 
+    def Covariance(self, reconstruction, image_ids, point3D_ids=()):
+        """Covariance blocks at the reconstruction's current parameters (ceres::Covariance with apply_loss_function = true is the model; the reference has
+        no counterpart): ({image_id: 6 x 6}, {point3D_id: 3 x 3}) for the listed ids, and {(image_id_i, image_id_j): 6 x 6} for entries of image_ids that
+        are pairs.  Tangent order of a pose: 3 rotation, 3 tvec; no sigma^2 factor; constant blocks are zero.  Does not use up the BundleAdjuster.
+        Raises PPError (PP_ERR_NUMERIC) when the problem's gauge is free."""
+        flat = self.flatten(reconstruction)
+        if flat is None:
+            return {}, {}
+        scene, pose_index, point_index, _ = flat
+        keys = [k if isinstance(k, tuple) else (k, k) for k in image_ids]
+        pairs = [(pose_index[i], pose_index[j]) for i, j in keys]
+        pids = list(point3D_ids)
+        kMaxNumImagesDirectSparseSolver = 1000
+        if self.config_.NumImages() > kMaxNumImagesDirectSparseSolver:
+            raise ValueError("Covariance needs the direct solver's reduced camera system: at most %d images" % kMaxNumImagesDirectSparseSolver)
+        pb = BAProblem(scene, device=self.device_, linear_solver=_capi.LINEAR_SOLVER_DIRECT)
+        try:
+            pc, xc = pb.covariance(pairs if pairs else np.zeros((0, 2), dtype=np.int32), [point_index[p] for p in pids])
+        finally:
+            pb.close()
+        return ({k: pc[q] for q, k in enumerate(image_ids)}, {p: xc[q] for q, p in enumerate(pids)})
+
     @staticmethod
     def write_back(reconstruction, flat, poses, points, intr):
         """the solved parameters of `flatten()`'s problem into the reconstruction: the variable blocks only"""

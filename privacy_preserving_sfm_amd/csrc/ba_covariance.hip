@@ -1,0 +1,373 @@
+// pp_ba_covariance: covariance blocks of poses and points from the factorised reduced camera system (ceres::Covariance with
+// apply_loss_function = true is the model; the reference has no counterpart).
+//
+// At the handle's parameters H = J^T J, J the loss-corrected Jacobian in the tangent coordinates of pp_ba_eval, no LM damping.  With the points eliminated,
+// S = U - W V^-1 W^T = L L^T and Z = L^-1:
+//   Cov(pose i, pose j)  = (S^-1)_ij = sum_k Z[k, cols_i]^T Z[k, cols_j]
+//   Cov(point p)         = V_p^-1 + Y^T Y,   Y = Z (W_p V_p^-1)        (W_p V_p^-1 is non-zero only in the columns of p's observing images)
+// The solver works in Jacobi-scaled coordinates (S_s = D S D): Z is the inverse factor of S_s, the pose blocks are scaled back by s_i s_j, and the scaled
+// records (J_pose s)^T J_pt V_p^-1 of the solver's own gather (ba_impl.hpp, kRecStride) make Y^T Y come out unscaled.  Columns of constant blocks carry
+// scale 0: their rows and columns of the result are exactly zero.
+//
+// Device path: the solver's own evaluate / reduce / prepare / Schur kernels with a zero LM diagonal (BaAssembleUndamped) and its own factorisation
+// (a CholeskyState of this call, the launch path the handle's has), all on buffers of this call - the handle's S, factor arrays, Jacobi scale and LM
+// diagonal are not touched; then
+//   k_tri_inverse        Z = L^-1 on 64 x 64 tiles (v_mfma_f64_16x16x4_f64), stored TRANSPOSED (row c of Zt = column c of Z: the gathers below read along k)
+//   k_cov_pose_blocks    one workgroup per requested pair
+//   k_cov_points         one workgroup per requested point
+// No kernel here waits for another workgroup.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "ba_impl.hpp"
+#include "resource_pool.hpp"
+
+namespace ppsfm {
+
+typedef double cov_v4 __attribute__((ext_vector_type(4)));
+constexpr int kTile = 64;
+
+// acc + A B over an inner dimension of 64: lane (lr = l & 15, g = l >> 4) holds A[lr][16 g + kk] and B[16 g + kk][lr], kk = 0 .. 15 - the inner index of
+// slice kk is 16 g + kk for both operands (any pairing of the inner index is a valid product; this one makes every lane's 16 values contiguous in memory).
+// Four independent accumulators (a dependent v_mfma_f64_16x16x4 waits for its predecessor), summed in a fixed order.
+__device__ __forceinline__ cov_v4 CovMfma64(const double (&a)[16], const double (&b)[16], cov_v4 acc) {
+  cov_v4 p1 = (cov_v4){0.0, 0.0, 0.0, 0.0}, p2 = p1, p3 = p1;
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b[kk], acc, 0, 0, 0);
+    p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[4 + kk], b[4 + kk], p1, 0, 0, 0);
+    p2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[8 + kk], b[8 + kk], p2, 0, 0, 0);
+    p3 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[12 + kk], b[12 + kk], p3, 0, 0, 0);
+  }
+  return (acc + p1) + (p2 + p3);
+}
+__device__ __forceinline__ void CovLoad16(const double* __restrict__ p, double (&v)[16]) {      // 16 contiguous doubles, 16-byte aligned
+  const double2* q = reinterpret_cast<const double2*>(p);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { const double2 t = q[i]; v[2 * i] = t.x; v[2 * i + 1] = t.y; }
+}
+
+// Z = L^-1 by block columns: Z_jj = M_j (= L_jj^-1, left in memory by the factorisation), Z_kj = -M_k sum_{j <= m < k} L_km Z_mj.  A column of Z depends on L
+// and on itself only: workgroup (j, strip) computes the 16 columns `strip` of block column j top down and never looks at another workgroup's part.  Wavefront
+// w owns rows 16 w .. 16 w + 15 of every 64 x 16 piece; the piece goes through LDS between the two products, and what the workgroup wrote to Zt is read back
+// by the same workgroup after a barrier.  nz (may be null): the tile map of a block-sparse factor - only its non-zero tiles L_km are read; Z is dense.
+// L: tile (k, m) at L[(64 k + r) ld + 64 m + c]; Minv: T row-major 64 x 64 tiles; Zt[c ld + k] = Z[k][c] (zero above the diagonal: the diagonal tiles
+// are masked here, the tiles above them are never written and were cleared by the caller).
+__global__ __launch_bounds__(256) void k_tri_inverse(const double* __restrict__ L, int ld, int T, const double* __restrict__ Minv, const uint8_t* __restrict__ nz, double* Zt) {
+  __shared__ double P[kTile * 17];
+  const int j = (int)blockIdx.x >> 2, strip = (int)blockIdx.x & 3;
+  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, lr = l & 15, g = l >> 4;
+  double* zcol = Zt + ((size_t)j * kTile + 16 * strip) * ld;
+  for (int idx = tid; idx < kTile * 16; idx += 256) {
+    const int cc = idx >> 6, rr = idx & 63, gcol = 16 * strip + cc;
+    zcol[(size_t)cc * ld + (size_t)j * kTile + rr] = rr >= gcol ? Minv[(size_t)j * kTile * kTile + rr * kTile + gcol] : 0.0;
+  }
+  __syncthreads();
+  for (int k = j + 1; k < T; ++k) {
+    cov_v4 acc = (cov_v4){0.0, 0.0, 0.0, 0.0};
+    for (int m = j; m < k; ++m) {
+      if (nz && !nz[(size_t)k * T + m]) continue;
+      double av[16], bv[16];
+      CovLoad16(L + ((size_t)k * kTile + 16 * w + lr) * ld + (size_t)m * kTile + 16 * g, av);
+      CovLoad16(zcol + (size_t)lr * ld + (size_t)m * kTile + 16 * g, bv);
+      acc = CovMfma64(av, bv, acc);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) P[(16 * w + g + 4 * i) * 17 + lr] = acc[i];      // D layout: register i <-> row g + 4 i, column lr
+    __syncthreads();
+    double av[16], bv[16];
+    CovLoad16(Minv + (size_t)k * kTile * kTile + (size_t)(16 * w + lr) * kTile + 16 * g, av);
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+      if (16 * g + kk > 16 * w + lr) av[kk] = 0.0;      // (the strictly upper part of an inverse tile is not relied on)
+      bv[kk] = P[(16 * g + kk) * 17 + lr];
+    }
+    const cov_v4 d = CovMfma64(av, bv, (cov_v4){0.0, 0.0, 0.0, 0.0});
+#pragma unroll
+    for (int i = 0; i < 4; ++i) zcol[(size_t)lr * ld + (size_t)k * kTile + 16 * w + g + 4 * i] = -d[i];
+    __syncthreads();
+  }
+}
+
+// Cov(pose i, pose j) = s_i s_j sum_{k >= max(col_i, col_j)} Z[k, col_i + a] Z[k, col_j + b]: one workgroup per pair, thread t the rows k0 + t, k0 + t + 256, ..
+// in order, then the wavefront butterfly and the four wavefronts in order - the same bits on every call.  pairs: the handle's image numbering.
+__global__ __launch_bounds__(256) void k_cov_pose_blocks(const int32_t* __restrict__ pairs, const int32_t* __restrict__ spos, const double* __restrict__ scale_c,
+                                                         const double* __restrict__ Zt, int N, int n, double* __restrict__ out) {
+  __shared__ double red[4][36];
+  const int pr = blockIdx.x, tid = threadIdx.x;
+  const int pi = pairs[2 * pr], pj = pairs[2 * pr + 1];
+  const int ci = spos[6 * pi], cj = spos[6 * pj];
+  const double* zi = Zt + (size_t)ci * N;
+  const double* zj = Zt + (size_t)cj * N;
+  double acc[36];
+#pragma unroll
+  for (int i = 0; i < 36; ++i) acc[i] = 0.0;
+  for (int k = max(ci, cj) + tid; k < n; k += 256) {
+    double a[6], b[6];
+#pragma unroll
+    for (int x = 0; x < 6; ++x) { a[x] = zi[(size_t)x * N + k]; b[x] = zj[(size_t)x * N + k]; }
+#pragma unroll
+    for (int x = 0; x < 6; ++x)
+#pragma unroll
+      for (int y = 0; y < 6; ++y) acc[6 * x + y] += a[x] * b[y];
+  }
+#pragma unroll
+  for (int i = 0; i < 36; ++i) acc[i] = WaveSum(acc[i]);
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < 36; ++i) red[tid >> 6][i] = acc[i];
+  }
+  __syncthreads();
+  if (tid < 36) {
+    const double v = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    out[36 * (size_t)pr + tid] = scale_c[6 * pi + tid / 6] * scale_c[6 * pj + tid % 6] * v;
+  }
+}
+
+struct CovPointArgs {
+  int C, n, N;
+  const int32_t *pt_start, *pt_obs, *obs_pose, *obs_cam, *spos, *intr_off, *intr_nv;
+  const uint8_t* point_const;
+  const double *rec, *JkS /* null: no variable intrinsics */, *Vinv, *scale_p, *Zt;
+};
+constexpr int kCovChunk = 64;      // observations of a point staged at a time
+
+// Cov(point p) = V_p^-1 + Y^T Y, Y = Z B, B = the point's 6 x 3 records (J_pose s)^T J_pt V_p^-1 in the columns of its observing images (and, with variable
+// intrinsics, (J_intr s)^T J_pt V_p^-1 in theirs): one workgroup per requested point, thread t row k of Y (rows in blocks of 256 from the first column the
+// point touches), the observations in list order; y y^T is summed per thread in row order, then as in k_cov_pose_blocks.  The records are those the
+// prepare kernel left at zero damping; V_p^-1 = s (s V s)^-1 s from the point role's inverse.
+__global__ __launch_bounds__(256) void k_cov_points(CovPointArgs a, const int32_t* __restrict__ ids, double* __restrict__ out) {
+  __shared__ int s_kmin, s_col[kCovChunk], s_nv[kCovChunk], s_colI[kCovChunk][kCamStride];      // 31 KB of LDS in all
+  __shared__ double s_B[kCovChunk][18], s_BI[kCovChunk][3 * kCamStride], red[4][6];
+  const int tid = threadIdx.x;
+  const int p = ids[blockIdx.x];
+  if (a.point_const[p]) {      // (workgroup-uniform) Ceres' convention: a constant block has a zero covariance
+    if (tid < 9) out[9 * (size_t)blockIdx.x + tid] = 0.0;
+    return;
+  }
+  const int begin = a.pt_start[p], end = a.pt_start[p + 1];
+  if (tid == 0) s_kmin = a.n;
+  __syncthreads();
+  for (int e = begin + tid; e < end; e += 256) {
+    const int o = a.pt_obs[e];
+    int kmin = a.spos[6 * a.obs_pose[o]];
+    if (a.JkS) {
+      const int cam = a.obs_cam[o] >> 4, off = a.intr_off[cam];
+      if (off >= 0) for (int c = 0; c < a.intr_nv[cam]; ++c) kmin = min(kmin, a.spos[6 * a.C + off + c]);
+    }
+    atomicMin(&s_kmin, kmin);
+  }
+  __syncthreads();
+  const int kmin = s_kmin;
+  const int nchunks = (end - begin + kCovChunk - 1) / kCovChunk;
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int k0 = kmin; k0 < a.n; k0 += 256) {
+    const int k = k0 + tid;
+    const bool live = k < a.n;
+    double y0 = 0.0, y1 = 0.0, y2 = 0.0;
+    for (int ch = 0; ch < nchunks; ++ch) {
+      const int cnt = min(kCovChunk, end - begin - kCovChunk * ch);
+      if (nchunks > 1 || k0 == kmin) {      // (workgroup-uniform) one chunk: staged once
+        __syncthreads();
+        if (tid < cnt) {
+          const int o = a.pt_obs[begin + kCovChunk * ch + tid];
+          const double* t = RecT(a.rec, (size_t)o);
+          const double* jp = RecJ(a.rec, (size_t)o);
+          s_col[tid] = a.spos[6 * a.obs_pose[o]];
+#pragma unroll
+          for (int x = 0; x < 6; ++x)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) s_B[tid][3 * x + c] = jp[x] * t[c] + jp[6 + x] * t[3 + c];
+          int nv = 0;
+          if (a.JkS) {
+            const int cam = a.obs_cam[o] >> 4, off = a.intr_off[cam];
+            if (off >= 0) {
+              nv = a.intr_nv[cam];      // (at most kCamStride: every variable parameter of the model)
+              const double* jk = a.JkS + (size_t)2 * kCamStride * o;
+              for (int x = 0; x < nv; ++x) {
+                s_colI[tid][x] = a.spos[6 * a.C + off + x];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) s_BI[tid][3 * x + c] = jk[x] * t[c] + jk[kCamStride + x] * t[3 + c];
+              }
+            }
+          }
+          s_nv[tid] = nv;
+        }
+        __syncthreads();
+      }
+      if (live) {
+        for (int q = 0; q < cnt; ++q) {
+          const double* z = a.Zt + (size_t)s_col[q] * a.N + k;
+#pragma unroll
+          for (int x = 0; x < 6; ++x) {
+            const double zz = z[(size_t)x * a.N];
+            y0 += zz * s_B[q][3 * x]; y1 += zz * s_B[q][3 * x + 1]; y2 += zz * s_B[q][3 * x + 2];
+          }
+          const int nv = s_nv[q];
+          for (int x = 0; x < nv; ++x) {
+            const double zz = a.Zt[(size_t)s_colI[q][x] * a.N + k];
+            y0 += zz * s_BI[q][3 * x]; y1 += zz * s_BI[q][3 * x + 1]; y2 += zz * s_BI[q][3 * x + 2];
+          }
+        }
+      }
+    }
+    acc[0] += y0 * y0; acc[1] += y0 * y1; acc[2] += y0 * y2; acc[3] += y1 * y1; acc[4] += y1 * y2; acc[5] += y2 * y2;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) acc[i] = WaveSum(acc[i]);
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) red[tid >> 6][i] = acc[i];
+  }
+  __syncthreads();
+  if (tid < 9) {
+    const int r = tid / 3, c = tid % 3;
+    const int lo = min(r, c), hi = max(r, c);
+    const int sym = lo == 0 ? hi : (lo == 1 ? 2 + hi : 5);      // (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
+    const double yy = ((red[0][sym] + red[1][sym]) + red[2][sym]) + red[3][sym];
+    out[9 * (size_t)blockIdx.x + tid] = a.scale_p[3 * p + r] * a.scale_p[3 * p + c] * a.Vinv[6 * (size_t)p + sym] + yy;
+  }
+}
+
+namespace {
+// the buffers of one pp_ba_covariance call: pool blocks, returned on every way out (after the stream has drained)
+struct CovBuffers {
+  hipStream_t stream = nullptr;
+  std::vector<void*> blocks;
+  CholeskyState* chol = nullptr;
+  template <typename T> int Alloc(T** p, size_t count) { const int rc = HandleAlloc(p, count); if (rc == PP_OK && *p) blocks.push_back(*p); return rc; }
+  ~CovBuffers() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (chol) CholeskyDestroy(chol);
+    for (void* b : blocks) PoolDeviceFree(b);
+  }
+};
+// the handle's solver buffers while the assembly kernels run on this call's: put back on every way out.  This relies on every evaluate / assembly launch
+// taking its pointers from the handle when it is enqueued (MakeStepArgs and its like; nothing of the assembly is cached or captured in a graph - only the
+// factorisation is, and that runs on a CholeskyState of this call); tests/test_gpu_covariance.py pins it on fresh and on used handles.
+struct BufferSwap {
+  pp_ba_impl* h;
+  double *S, *scale_c, *scale_p, *diag_c, *diag_p, *Vinv, *vb;
+  int32_t* d_flag;
+  explicit BufferSwap(pp_ba_impl* hh) : h(hh), S(hh->S), scale_c(hh->scale_c), scale_p(hh->scale_p), diag_c(hh->diag_c), diag_p(hh->diag_p), Vinv(hh->Vinv), vb(hh->vb), d_flag(hh->d_flag) {}
+  ~BufferSwap() { h->S = S; h->scale_c = scale_c; h->scale_p = scale_p; h->diag_c = diag_c; h->diag_p = diag_p; h->Vinv = Vinv; h->vb = vb; h->d_flag = d_flag; }
+};
+}  // namespace
+
+}  // namespace ppsfm
+
+using namespace ppsfm;
+
+extern "C" int pp_ba_covariance(pp_ba_handle h, const pp_ba_options* o, int32_t num_pose_pairs, const int32_t* pose_i, const int32_t* pose_j, double* pose_cov,
+                                int32_t num_points, const int32_t* point_ids, double* point_cov, pp_ba_covariance_info* info) try {
+  PP_REQUIRE(h && o, "pp_ba_covariance: null handle or options");
+  PP_REQUIRE(num_pose_pairs >= 0 && num_points >= 0, "pp_ba_covariance: negative count");
+  PP_REQUIRE(num_pose_pairs == 0 || (pose_i && pose_j && pose_cov), "pp_ba_covariance: %d pose pairs without their arrays", (int)num_pose_pairs);
+  PP_REQUIRE(num_points == 0 || (point_ids && point_cov), "pp_ba_covariance: %d points without their arrays", (int)num_points);
+  for (int32_t q = 0; q < num_pose_pairs; ++q)
+    PP_REQUIRE(pose_i[q] >= 0 && pose_i[q] < h->C && pose_j[q] >= 0 && pose_j[q] < h->C, "pp_ba_covariance: pose pair %d = (%d, %d) is out of range (%d images)", (int)q,
+               (int)pose_i[q], (int)pose_j[q], (int)h->C);
+  for (int32_t q = 0; q < num_points; ++q)
+    PP_REQUIRE(point_ids[q] >= 0 && point_ids[q] < h->P, "pp_ba_covariance: point %d = %d is out of range (%d points)", (int)q, (int)point_ids[q], (int)h->P);
+  PP_REQUIRE(!h->iterative, "pp_ba_covariance: an iterative (ITERATIVE_SCHUR) handle never forms the reduced camera system the covariance is taken from - create "
+             "the handle with pp_ba_problem_desc::linear_solver = PP_LINEAR_SOLVER_DIRECT (or PPSFM_BA_LINEAR_SOLVER=direct)");
+  PP_REQUIRE(!BaInGroup(h), "pp_ba_covariance: the handle is attached to a group (pp_ba_set_allreduce / pp_ba_set_communicator) and holds one shard of the points - "
+             "detach it, or take the covariance from a handle that holds the whole problem");
+  if (info) std::memset(info, 0, sizeof(*info));
+  PP_HIP_TRY(hipSetDevice(h->device));
+  int rc;
+  if ((rc = BaEnsureJacobianBuffers(h, 0, h->NI > 0 ? 1 : 0))) return rc;
+  if ((rc = BaEnsureSolverBuffers(h))) return rc;
+  hipStream_t s = h->stream;
+  const int N = h->N, n = h->n_red, T = N / kTile;
+  const size_t NN = (size_t)N * N;
+
+  CovBuffers buf;
+  buf.stream = s;
+  double *S2 = nullptr, *Linv2 = nullptr, *Lfac2 = nullptr, *x2 = nullptr, *scale_c2 = nullptr, *scale_p2 = nullptr, *diag_c2 = nullptr, *diag_p2 = nullptr, *Vinv2 = nullptr,
+         *vb2 = nullptr, *Zt = nullptr, *d_pose = nullptr, *d_point = nullptr;
+  int32_t *flag2 = nullptr, *d_pairs = nullptr, *d_ids = nullptr;
+  Switches sw = h->sw;
+  sw.chol_small = false;      // (the one-workgroup kernel of one or two block columns keeps its factor in LDS: per-column launches leave it in memory, the same arithmetic)
+  {
+    std::lock_guard<std::recursive_mutex> setup_lock(DeviceSetupMutex());      // (allocations: not beside another host thread's graph capture)
+    if ((rc = buf.Alloc(&S2, NN)) || (rc = buf.Alloc(&Linv2, CholeskyWorkspaceDoubles(N))) || (rc = buf.Alloc(&x2, (size_t)N)) || (rc = buf.Alloc(&flag2, 4)) ||
+        (rc = buf.Alloc(&scale_c2, (size_t)n)) || (rc = buf.Alloc(&scale_p2, 3 * (size_t)h->P)) || (rc = buf.Alloc(&diag_c2, (size_t)n)) ||
+        (rc = buf.Alloc(&diag_p2, 3 * (size_t)h->P)) || (rc = buf.Alloc(&Vinv2, 6 * (size_t)h->P)) || (rc = buf.Alloc(&vb2, 3 * (size_t)h->P)) || (rc = buf.Alloc(&Zt, NN)) ||
+        (rc = buf.Alloc(&d_pose, 36 * (size_t)num_pose_pairs)) || (rc = buf.Alloc(&d_point, 9 * (size_t)num_points)) || (rc = buf.Alloc(&d_pairs, 2 * (size_t)num_pose_pairs)) ||
+        (rc = buf.Alloc(&d_ids, (size_t)num_points)))
+      return rc;
+    buf.chol = CholeskyCreate(sw);
+    CholeskyDisableGraph(buf.chol);      // one factorisation: nothing to replay
+    if (CholeskyNeedsFactorArray(buf.chol, N) && !CholeskyColumnsOnly(h->chol) && (rc = buf.Alloc(&Lfac2, NN))) return rc;
+    PP_HIP_TRY(hipMemsetAsync(S2, 0, sizeof(double) * NN, s));
+    if (Lfac2) PP_HIP_TRY(hipMemsetAsync(Lfac2, 0, sizeof(double) * NN, s));
+    PP_HIP_TRY(hipMemsetAsync(Zt, 0, sizeof(double) * NN, s));
+    PP_HIP_TRY(hipMemsetAsync(flag2, 0, 4 * sizeof(int32_t), s));
+    const CholeskySystem sys{S2, N, n, Linv2, Lfac2, x2, flag2, s};
+    const bool sparse = h->sparse_tiles && !h->tile_nz.empty();
+    if ((rc = CholeskyBind(buf.chol, sys, sparse ? h->tile_nz.data() : nullptr))) return rc;
+    if (CholeskyColumnsOnly(h->chol)) (void)CholeskyFallBackToColumns(buf.chol);      // the launch path the handle's own factorisation has
+  }
+  // the requests in the handle's image numbering (pp_ba_create may have renumbered the images; the points keep their order)
+  if (num_pose_pairs > 0) {
+    std::vector<int32_t> pairs(2 * (size_t)num_pose_pairs);
+    const bool perm = !h->pose_new_of_old.empty();
+    for (int32_t q = 0; q < num_pose_pairs; ++q) {
+      pairs[2 * (size_t)q] = perm ? h->pose_new_of_old[pose_i[q]] : pose_i[q];
+      pairs[2 * (size_t)q + 1] = perm ? h->pose_new_of_old[pose_j[q]] : pose_j[q];
+    }
+    PP_HIP_TRY(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(int32_t) * pairs.size(), hipMemcpyHostToDevice, s));
+    PP_HIP_TRY(hipStreamSynchronize(s));
+  }
+  if (num_points > 0) PP_HIP_TRY(hipMemcpyAsync(d_ids, point_ids, sizeof(int32_t) * (size_t)num_points, hipMemcpyHostToDevice, s));
+  PP_HIP_TRY(hipEventRecord(h->ev0, s));
+
+  int32_t flag = 0;
+  {
+    BufferSwap swap(h);
+    h->S = S2; h->scale_c = scale_c2; h->scale_p = scale_p2; h->diag_c = diag_c2; h->diag_p = diag_p2; h->Vinv = Vinv2; h->vb = vb2; h->d_flag = flag2;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      if ((rc = BaAssembleUndamped(h, o, attempt == 0))) return rc;
+      if ((rc = CholeskySolve(buf.chol))) return rc;
+      PP_HIP_TRY(hipMemcpyAsync(&flag, flag2, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      PP_HIP_TRY(hipStreamSynchronize(s));
+      // a bounded wait of the one-launch factorisation ran out: nothing wrong with the system - once more with per-column launches (what RecoverAfterFlag does)
+      if (!(flag & 4) || (flag & 3) || attempt == 1 || !CholeskyFallBackToColumns(buf.chol)) break;
+      PP_HIP_TRY(hipMemsetAsync(flag2, 0, sizeof(int32_t), s));
+      PP_HIP_TRY(hipMemsetAsync(S2, 0, sizeof(double) * NN, s));
+    }
+  }
+  if (flag & 7) {      // (this call's buffers carry whatever the failed factorisation left: they are returned, the handle's own were never written)
+    SetLastError("pp_ba_covariance: the undamped reduced camera system is not positive definite (%s) - a free gauge, or a point seen along one direction only, has no covariance",
+                 (flag & 2) ? "a point block is singular" : (flag & 1) ? "non-positive pivot" : "the factorisation did not finish");
+    return PP_ERR_NUMERIC;
+  }
+  const double* Minv = nullptr;
+  const uint8_t* nz = nullptr;
+  const double* L = CholeskyFactor(buf.chol, &Minv, &nz);
+  if (!L) { SetLastError("pp_ba_covariance: the factorisation left no factor in memory"); return PP_ERR_INTERNAL; }
+  hipLaunchKernelGGL(k_tri_inverse, dim3(4 * T), dim3(256), 0, s, L, N, T, Minv, nz, Zt);
+  if (num_pose_pairs > 0)
+    hipLaunchKernelGGL(k_cov_pose_blocks, dim3(num_pose_pairs), dim3(256), 0, s, (const int32_t*)d_pairs, (const int32_t*)h->spos, (const double*)scale_c2, (const double*)Zt, N, n, d_pose);
+  if (num_points > 0) {
+    CovPointArgs a;
+    a.C = h->C; a.n = n; a.N = N;
+    a.pt_start = h->pt_start; a.pt_obs = h->pt_obs; a.obs_pose = h->obs_pose; a.obs_cam = h->obs_cam; a.spos = h->spos; a.intr_off = h->intr_off; a.intr_nv = h->intr_nv;
+    a.point_const = h->point_const; a.rec = h->JpS; a.JkS = h->NI > 0 ? h->JkS_intr : nullptr; a.Vinv = Vinv2; a.scale_p = scale_p2; a.Zt = Zt;
+    hipLaunchKernelGGL(k_cov_points, dim3(num_points), dim3(256), 0, s, a, (const int32_t*)d_ids, d_point);
+  }
+  PP_HIP_TRY(hipGetLastError());
+  PP_HIP_TRY(hipEventRecord(h->ev1, s));
+  if (num_pose_pairs > 0) PP_HIP_TRY(hipMemcpyAsync(pose_cov, d_pose, sizeof(double) * 36 * (size_t)num_pose_pairs, hipMemcpyDeviceToHost, s));
+  if (num_points > 0) PP_HIP_TRY(hipMemcpyAsync(point_cov, d_point, sizeof(double) * 9 * (size_t)num_points, hipMemcpyDeviceToHost, s));
+  PP_HIP_TRY(hipStreamSynchronize(s));
+  if (info) {
+    float ms = 0;
+    PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    info->n = n; info->path = CholeskyLinsolve(buf.chol); info->device_ms = ms;
+  }
+  return PP_OK;
+} PP_API_CATCH("pp_ba_covariance")

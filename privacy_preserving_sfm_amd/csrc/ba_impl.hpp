@@ -238,6 +238,17 @@ void CholeskyDisableGraph(CholeskyState* st);      // enqueue eagerly from now o
 int CholeskyLinsolve(const CholeskyState* st);     // the bound path as PP_LINSOLVE_CHOLESKY_* (pp_ba_summary::linear_solver)
 int CholeskyFallbacks(const CholeskyState* st);    // pp_ba_summary::cholesky_fallbacks
 double CholeskyPlanMs(const CholeskyState* st);    // host time of the last task-list set-up (plan, list, replay, upload; a cache hit: the upload)
+bool CholeskyColumnsOnly(const CholeskyState* st);  // per-column launches only (PPSFM_CHOL_MODE=columns, or after a fallback)
+// After a CholeskySolve on any path but the small one (null): where the factor's 64x64 tiles live (N x N row-major, tile (k, j), k > j, holds L_kj; the diagonal
+// tiles are not to be read), *diag_inverses: the T row-major 64x64 inverses L_kk^-1, *tile_map: T x T bytes on the device, non-zero where tile (k, j) of the
+// factor is (null: every tile)
+const double* CholeskyFactor(const CholeskyState* st, const double** diag_inverses, const uint8_t** tile_map);
+// pp_ba_covariance (ba_covariance.hip) runs the solver's own assembly on buffers of its own: the solver buffers of the handle exist afterwards
+int BaEnsureSolverBuffers(pp_ba_impl* h);
+// K1 + K2 and the Jacobi scale at the handle's parameters (evaluate), then the UNDAMPED reduced system into h->S: the LM diagonal h->diag_c / h->diag_p is
+// zeroed and 1 / radius is exactly 0, so neither the diagonal nor its clamp (min_lm_diagonal / radius) enters any sum.  The records h->JpS and the point
+// inverses h->Vinv are then those of zero damping.
+int BaAssembleUndamped(pp_ba_impl* h, const pp_ba_options* o, bool evaluate);
 // the group exchange of a point-sharded handle (ba_solver.hip): true inside a group; in-place reduction of `count` doubles on the handle's stream
 bool BaInGroup(const pp_ba_impl* h);
 int BaGroupReduce(pp_ba_impl* h, double* ptr, int64_t count, int op);

@@ -1741,6 +1741,17 @@ static bool UserStops(const pp_ba_options* o, LmPolicy* policy) {
   return r == PP_SOLVER_ABORT || r == PP_SOLVER_TERMINATE_SUCCESSFULLY;
 }
 
+int BaEnsureSolverBuffers(pp_ba_impl* h) { return EnsureSolverBuffers(h); }
+int BaAssembleUndamped(pp_ba_impl* h, const pp_ba_options* o, bool evaluate) {
+  if (evaluate) {
+    PhaseTimer untimed(h, false);
+    if (const int rc = EvaluateAndScale(h, o, /*fold=*/true, untimed)) return rc;      // (no cost sum: nothing of the solver's scalars is touched)
+  }
+  PP_HIP_TRY(hipMemsetAsync(h->diag_c, 0, sizeof(double) * (size_t)h->n_red, h->stream));
+  PP_HIP_TRY(hipMemsetAsync(h->diag_p, 0, sizeof(double) * 3 * (size_t)h->P, h->stream));
+  return AssembleReducedSystem(h, HUGE_VAL);      // 1 / radius == 0.0
+}
+
 }  // namespace ppsfm
 
 using namespace ppsfm;

@@ -2463,6 +2463,13 @@ int CholeskyLinsolve(const CholeskyState* st) {      // (a block-sparse system r
 }
 int CholeskyFallbacks(const CholeskyState* st) { return st->fallbacks; }
 double CholeskyPlanMs(const CholeskyState* st) { return st->plan_ms; }
+bool CholeskyColumnsOnly(const CholeskyState* st) { return st->columns; }
+const double* CholeskyFactor(const CholeskyState* st, const double** diag_inverses, const uint8_t** tile_map) {
+  if (st->path == CholPath::Small) return nullptr;      // (neither the factor nor the block inverses leave the CU)
+  *diag_inverses = st->sys.Linv_ws;
+  *tile_map = st->path == CholPath::Tasks ? (st->tile_nz ? st->tasks_nz : nullptr) : st->path == CholPath::SparseColumns ? st->sparse_nz : nullptr;
+  return st->path == CholPath::Tasks ? st->sys.Lfac : st->sys.S;
+}
 
 }  // namespace ppsfm
 

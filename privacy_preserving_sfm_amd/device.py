@@ -198,6 +198,23 @@ class BAProblem:
         n = n.value
         return S[: n * n].reshape(n, n).copy(), rhs[:n].copy()
 
+    def covariance(self, pose_pairs=None, points=None, options=None, return_info=False):
+        """pp_ba_covariance at the current parameters: (pose_cov [pairs, 6, 6], point_cov [points, 3, 3]).
+        pose_pairs: sequence of (i, j) in the scene's image order, block = Cov(delta_i, delta_j) in the tangent order of `evaluate` (3 rotation, 3 tvec);
+        None = every diagonal block (i, i).  points: point indices; None = no points.  No sigma^2 factor is applied.  return_info: also the
+        BACovarianceInfo (n, path, device_ms)."""
+        o = options or ba_options()
+        if pose_pairs is None:
+            pose_pairs = np.stack([np.arange(self.C), np.arange(self.C)], axis=1)
+        pp = np.asarray(pose_pairs, dtype=np.int64).reshape(-1, 2)
+        pi = np.ascontiguousarray(pp[:, 0], dtype=np.int32); pj = np.ascontiguousarray(pp[:, 1], dtype=np.int32)
+        ids = np.ascontiguousarray(np.asarray([] if points is None else points, dtype=np.int64).reshape(-1), dtype=np.int32)
+        pc = np.zeros((len(pi), 6, 6)); xc = np.zeros((len(ids), 3, 3))
+        info = _capi.BACovarianceInfo()
+        check(_capi.lib().pp_ba_covariance(self._h, C.byref(o), len(pi), ptr(pi, _capi.c_ip), ptr(pj, _capi.c_ip), dp(pc), len(ids), ptr(ids, _capi.c_ip), dp(xc),
+                                           C.byref(info)))
+        return (pc, xc, info) if return_info else (pc, xc)
+
     def timings(self):
         ms = np.zeros(len(_capi.BA_T_NAMES)); calls = np.zeros(len(_capi.BA_T_NAMES), dtype=np.int32)
         check(_capi.lib().pp_ba_get_timings(self._h, dp(ms), ptr(calls, _capi.c_ip)))
