@@ -513,6 +513,93 @@ int pp_triangulate_tracks(int device, int32_t num_tracks, const int32_t* track_s
                           int32_t* num_trials, float* device_ms /* may be NULL */);
 
 /* ======================================================================================== *
+ *  Track completion and merging                                                              *
+ *  replaces: IncrementalTriangulator::CompleteTracks / CompleteAllTracks / MergeTracks /     *
+ *  MergeAllTracks (sfm/incremental_triangulator.cc:237-293) with Complete (:697-765) and      *
+ *  Merge (:606-695), on CalculateSquaredLineReprojectionError (base/projection.cc:162-203).   *
+ *  The device speculates (kernels K10a k_complete_tracks, K10b k_merge_candidates: one          *
+ *  wavefront per point, on the state at the start of the call), the host replays the          *
+ *  sequential decisions, as pp_pose_ransac does for RANSAC.                                   *
+ *  POINT ORDER: the reference iterates an unordered_set, so its order is unspecified, and     *
+ *  unlike the bundle adjustment the result depends on it.  Here it is ASCENDING POINT INDEX,  *
+ *  for the whole-model form (point_subset NULL) and the subset form alike.                    *
+ *  EXACTNESS: the result of a call equals the strictly sequential loop in that order - the    *
+ *  same pairs in the same order, the same merges, new indices and counts - whatever the       *
+ *  schedule of the device work.                                                               *
+ * ======================================================================================== */
+
+/* The state the triangulator reads, flattened.  Lines are numbered 0..L-1 over all images; a point's track lists line numbers. */
+typedef struct pp_tracks_desc {
+  int32_t num_images;    /* C */
+  int32_t num_cameras;   /* K */
+  int32_t num_points;    /* P */
+  int32_t reserved_;
+  int64_t num_lines;     /* L */
+  int64_t num_corrs;     /* E = corr_start[L] */
+  const double* poses;            /* C x 7 (qw,qx,qy,qz,tx,ty,tz); normalised inside, as Image::ProjectionMatrix does */
+  const int32_t* pose_camera;     /* C */
+  const int32_t* camera_model;    /* K, as pp_triangulate_tracks */
+  const double* intr;             /* K x PP_CAM_STRIDE */
+  const int32_t* cam_size;        /* K x 2 (width, height) */
+  const uint8_t* camera_skip;     /* K  1: HasCameraBogusParams, decided once per camera on the host (:767-779); NULL = none */
+  const uint8_t* image_registered;/* C  Image::IsRegistered; NULL = all */
+  const double* lines;            /* L x 3 FeatureLine::Line(), a^2 + b^2 = 1 (projection.cc:166) */
+  const int32_t* line_image;      /* L */
+  const int32_t* line_point;      /* L  point of the line, -1 = free */
+  const int32_t* corr_start;      /* L + 1: CSR of the correspondence graph over lines */
+  const int32_t* corr_line;       /* E: the neighbours of each line in the order FindCorrespondences returns them */
+  const double* points;           /* P x 3 */
+  const int32_t* track_start;     /* P + 1: tracks as CSR, in track order; an empty track = the point does not exist */
+  const int32_t* track_line;      /* track_start[P] */
+} pp_tracks_desc;
+
+/* IncrementalTriangulator::Options, the fields Complete and Merge read (incremental_triangulator.h:57-64) */
+typedef struct pp_tracks_options {
+  double merge_max_reproj_error;       /* 4.0 */
+  double complete_max_reproj_error;    /* 4.0 */
+  int32_t complete_max_transitivity;   /* 5 */
+  int32_t reserved_;
+} pp_tracks_options;
+void pp_tracks_options_default(pp_tracks_options* o);
+
+typedef struct pp_tracks_report {
+  int64_t num_changed;           /* the reference's return value: completed observations / merged observations (rule of :684-689) */
+  int64_t num_entries;           /* pairs (complete) / merges (merge) of this call; those beyond `capacity` are not written */
+  int64_t candidates_evaluated;  /* line errors the device computed, speculation included; a point of `overflow_points` is walked twice (its
+                                    aborted first pass and the second launch), and both walks are counted */
+  int32_t conflict_replays;      /* complete: points whose walk the host redid because an earlier point took one of their lines */
+  int32_t overflow_points;       /* complete: points whose closure outgrew the on-chip list and were finished by the second launch;
+                                    merge: points whose candidate list did (their pairs are evaluated one by one) */
+  int32_t fresh_pair_launches;   /* merge: pairs evaluated by a launch of their own (a merged point, a candidate changed since the speculation) */
+  int32_t second_launches;       /* complete: launches of the global-memory list kernel */
+  double device_ms;              /* HIP-event time of the speculative launches */
+  double replay_ms;              /* host replay, fresh-pair launches included */
+  double total_ms;
+} pp_tracks_report;
+
+typedef struct pp_tracks_impl* pp_tracks_handle;
+/* Validates the descriptor (every index in range, tracks and line_point consistent: PP_ERR_INVALID before any device work), then uploads it.
+ * The handle keeps the evolving state (line_point, points, tracks) on the host and re-uploads it at the start of each call. */
+int pp_tracks_create(const pp_tracks_desc* desc, int device, pp_tracks_handle* out);
+int pp_tracks_destroy(pp_tracks_handle h);
+/* CompleteTracks (point_subset: P bytes over the CURRENT points, new ones included) / CompleteAllTracks (NULL).  added_point / added_line: the
+ * (point, line) pairs in the order the reference appends them to the tracks. */
+int pp_tracks_complete(pp_tracks_handle h, const pp_tracks_options* options, const uint8_t* point_subset, pp_tracks_report* report,
+                       int32_t* added_point, int32_t* added_line, int64_t capacity);
+/* MergeTracks / MergeAllTracks.  Merge q: points merged_a[q] (the one being visited) and merged_b[q] are deleted, merged_new[q] is created with the
+ * next unused index (P, P + 1, ...: ++num_added_points3D_), the length-weighted mean position and track a followed by track b; the merged point is
+ * visited at once (the recursion of :684).  A point's merge_trials_ live for one call. */
+int pp_tracks_merge(pp_tracks_handle h, const pp_tracks_options* options, const uint8_t* point_subset, pp_tracks_report* report,
+                    int32_t* merged_a, int32_t* merged_b, int32_t* merged_new, int64_t capacity);
+/* The current state.  *num_points / *num_track_elements are always written; an array that is not NULL is filled: line_point L, points P' x 3,
+ * deleted P' (1: merged away or never existed), track_start P' + 1, track_line; PP_ERR_INVALID when a capacity is too small for it. */
+/* ERRORS of pp_tracks_complete / pp_tracks_merge: PP_ERR_INVALID (bad argument or options) leaves the handle as it was.  Any other error (PP_ERR_HIP from a
+ * launch or a copy, PP_ERR_NOMEM, ...) can arrive in the middle of the host replay, when some pairs or merges have been applied to the handle's state and
+ * others have not; `report` and the output arrays are then unspecified.  The handle is no longer the state the caller knows: destroy it and create a new one. */
+int pp_tracks_get_state(pp_tracks_handle h, int32_t* num_points, int64_t* num_track_elements, int32_t* line_point, double* points,
+                        uint8_t* deleted, int32_t* track_start, int32_t* track_line, int32_t point_capacity, int64_t element_capacity);
+
+/* ======================================================================================== *
  *  Four-view line initialisation (LO-MSAC)                                                   *
  *  replaces, for the out-of-plane-translation stage: ransac_lib::LocallyOptimizedMSAC<        *
  *  PlanarOffsetEstimator::Reconstruction, ..., PlanarOffsetEstimator>::EstimateModel            *

@@ -101,6 +101,25 @@ class FilterReport(C.Structure):
     _fields_ = [("num_filtered", C.c_int64), ("num_points_deleted", C.c_int64), ("num_observations_deleted", C.c_int64)]
 
 
+class TracksDesc(C.Structure):
+    _fields_ = [("num_images", C.c_int32), ("num_cameras", C.c_int32), ("num_points", C.c_int32), ("reserved_", C.c_int32),
+                ("num_lines", C.c_int64), ("num_corrs", C.c_int64),
+                ("poses", c_dp), ("pose_camera", c_ip), ("camera_model", c_ip), ("intr", c_dp), ("cam_size", c_ip),
+                ("camera_skip", c_u8p), ("image_registered", c_u8p), ("lines", c_dp), ("line_image", c_ip), ("line_point", c_ip),
+                ("corr_start", c_ip), ("corr_line", c_ip), ("points", c_dp), ("track_start", c_ip), ("track_line", c_ip)]
+
+
+class TracksOptions(C.Structure):
+    _fields_ = [("merge_max_reproj_error", C.c_double), ("complete_max_reproj_error", C.c_double),
+                ("complete_max_transitivity", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class TracksReport(C.Structure):
+    _fields_ = [("num_changed", C.c_int64), ("num_entries", C.c_int64), ("candidates_evaluated", C.c_int64),
+                ("conflict_replays", C.c_int32), ("overflow_points", C.c_int32), ("fresh_pair_launches", C.c_int32),
+                ("second_launches", C.c_int32), ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -129,6 +148,7 @@ _EXPORTS = [
     "pp_lomsac_options_default", "pp_planar_create", "pp_planar_destroy", "pp_planar_solve_batch", "pp_planar_score",
     "pp_planar_evaluate", "pp_planar_lomsac", "pp_fourview2d_create", "pp_fourview2d_destroy", "pp_fourview2d_score",
     "pp_triangulate_tracks", "pp_ba_filter_points", "pp_ba_filter_negative_depth", "pp_pose2d_create", "pp_pose2d_destroy", "pp_pose2d_solve_batch", "pp_pose2d_score", "pp_pose2d_evaluate", "pp_pose2d_lomsac",
+    "pp_tracks_options_default", "pp_tracks_create", "pp_tracks_destroy", "pp_tracks_complete", "pp_tracks_merge", "pp_tracks_get_state",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -219,6 +239,12 @@ def lib():
     L.pp_fourview2d_nonminimal_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int32, c_ip, c_dp, C.c_double, c_dp, c_dp, c_ip]
     L.pp_fourview2d_least_squares.argtypes = [C.c_void_p, C.c_int32, c_ip, c_dp, c_dp]
     L.pp_fourview2d_lomsac.argtypes = [C.c_void_p, C.POINTER(LoMsacOptions), c_dp, C.POINTER(LoMsacReport), c_dp, c_dp, c_ip]
+    L.pp_tracks_options_default.argtypes = [C.POINTER(TracksOptions)]
+    L.pp_tracks_create.argtypes = [C.POINTER(TracksDesc), C.c_int, C.POINTER(C.c_void_p)]
+    L.pp_tracks_destroy.argtypes = [C.c_void_p]
+    L.pp_tracks_complete.argtypes = [C.c_void_p, C.POINTER(TracksOptions), c_u8p, C.POINTER(TracksReport), c_ip, c_ip, C.c_int64]
+    L.pp_tracks_merge.argtypes = [C.c_void_p, C.POINTER(TracksOptions), c_u8p, C.POINTER(TracksReport), c_ip, c_ip, c_ip, C.c_int64]
+    L.pp_tracks_get_state.argtypes = [C.c_void_p, c_ip, C.POINTER(C.c_int64), c_ip, c_dp, c_u8p, c_ip, c_ip, C.c_int32, C.c_int64]
     L.pp_camera_image_to_world_threshold.argtypes = [C.c_int, c_dp, C.c_double, c_dp]
     _lib = L
     return L

@@ -41,8 +41,10 @@ class FeatureLine:
 
 
 class Camera:
-    def __init__(self, camera_id, model_id, params):
+    def __init__(self, camera_id, model_id, params, width=None, height=None):
         self.camera_id, self.model_id = camera_id, int(model_id)
+        if width is not None:          # (a camera without a size keeps the filters' "no image bounds" default)
+            self.width, self.height = int(width), int(height)
         n = _capi.lib().pp_camera_num_params(self.model_id)
         if n < 0:
             raise ValueError("camera model %d does not exist" % model_id)   # CAMERA_MODEL_DOES_NOT_EXIST_EXCEPTION
@@ -64,6 +66,22 @@ class Camera:
     def ExtraParamsIdxs(self):
         first = 3 if self.model_id in (0, 2, 3, 8, 9) else 4
         return list(range(first, len(self.params)))
+
+
+    def HasBogusParams(self, min_focal_length_ratio, max_focal_length_ratio, max_extra_param):
+        """Camera::HasBogusParams (base/camera.cc:186-192, base/camera_models.h:473-531): principal point outside the image, a focal length
+        outside [min, max] x max(width, height), or an extra parameter beyond max_extra_param in magnitude"""
+        if not hasattr(self, "width"):
+            raise ValueError("Camera.HasBogusParams needs the camera's width and height")
+        cx, cy = (self.params[i] for i in self.PrincipalPointIdxs())
+        if cx < 0 or cx > self.width or cy < 0 or cy > self.height:
+            return True
+        max_size = max(self.width, self.height)
+        for i in self.FocalLengthIdxs():
+            ratio = self.params[i] / max_size
+            if ratio < min_focal_length_ratio or ratio > max_focal_length_ratio:
+                return True
+        return any(abs(self.params[i]) > max_extra_param for i in self.ExtraParamsIdxs())
 
 
 class Image:
@@ -169,6 +187,31 @@ class Reconstruction:
         for (iid, idx) in self.points3D[pid].track:
             self.images[iid].lines[idx].point3D_id = kInvalidPoint3DId
         del self.points3D[pid]
+
+    def AddObservation(self, point3D_id, track_el):
+        """Reconstruction::AddObservation (base/reconstruction.cc:190-204): the line gets the point, the track its element at the end"""
+        image_id, line_idx = track_el
+        fl = self.images[image_id].lines[line_idx]
+        assert not fl.HasPoint3D()
+        fl.point3D_id = point3D_id
+        self.points3D[point3D_id].track.append((image_id, line_idx))
+
+    def MergePoints3D(self, point3D_id1, point3D_id2):
+        """Reconstruction::MergePoints3D (base/reconstruction.cc:206-232): the length-weighted mean position, track 1 followed by track 2, both points
+        deleted, the merged one added under the next unused id (++num_added_points3D_; here one past the largest id ever seen)."""
+        p1, p2 = self.points3D[point3D_id1], self.points3D[point3D_id2]
+        l1, l2 = float(len(p1.track)), float(len(p2.track))
+        merged_xyz = (l1 * p1.xyz + l2 * p2.xyz) / (l1 + l2)
+        merged_track = list(p1.track) + list(p2.track)
+        self._num_added_points3D = max(getattr(self, "_num_added_points3D", 0), max(self.points3D) + 1)
+        self.DeletePoint3D(point3D_id1)
+        self.DeletePoint3D(point3D_id2)
+        new_id = self._num_added_points3D
+        self._num_added_points3D += 1
+        self.points3D[new_id] = Point3D(merged_xyz, merged_track)
+        for (iid, idx) in merged_track:
+            self.images[iid].lines[idx].point3D_id = new_id
+        return new_id
 
     def FilterPoints3D(self, max_reproj_error, min_tri_angle, point3D_ids=None, device=0):
         """Reconstruction::FilterPoints3D / FilterAllPoints3D (point3D_ids = None): returns the number of filtered
@@ -705,29 +748,45 @@ def AdjustGlobalBundle(reconstruction, ba_options, device=0, summary_out=None):
 
 class GlobalRefinementReport:
     """What IterativeGlobalRefinement did: one entry per round in `summaries` (the solver summary, None where there was nothing to solve),
-    `num_filtered` (FilterAllPoints3D's count), `changed` (that count over the observations before the round), and what the round's filter
-    deleted: `obs_deleted` (sorted (image_id, line_idx) pairs, those of deleted points included) and `point_deleted` (sorted point ids)."""
+    `num_filtered` (FilterAllPoints3D's count), `changed` (the changed observations over the observations before the round), and what the round's filter
+    deleted: `obs_deleted` (sorted (image_id, line_idx) pairs, those of deleted points included) and `point_deleted` (sorted point ids).
+    With a triangulator also, per round, `num_completed` / `num_merged` (CompleteAllTracks' / MergeAllTracks' counts, part of `changed`),
+    `completed` [(point id, (image_id, line_idx))] and `merged` [(id a, id b, new id)] in the order they happened, and `initial` = the same four for the
+    CompleteAndMergeTracks before the first round."""
 
     def __init__(self):
         self.num_rounds = 0
         self.summaries, self.num_filtered, self.changed = [], [], []
         self.obs_deleted, self.point_deleted = [], []
+        self.num_completed, self.num_merged, self.completed, self.merged = [], [], [], []
+        self.initial = None
 
 
-def IterativeGlobalRefinement(reconstruction, mapper_options=None, device=0):
-    """IterativeGlobalRefinement (controllers/incremental_mapper.cc:102-124): up to `ba_global_max_refinements` rounds of AdjustGlobalBundle and
-    FilterAllPoints3D, until a round changes less than `ba_global_max_refinement_change` of the observations.
-    CompleteAndMergeTracks (before the loop and inside every round) and the closing FilterImages are the triangulator's and the image
-    bookkeeping's work, which this package does not mirror: they are left out, so `changed` counts filtered observations only."""
+def IterativeGlobalRefinement(reconstruction, mapper_options=None, device=0, triangulator=None):
+    """IterativeGlobalRefinement (controllers/incremental_mapper.cc:102-124): up to `ba_global_max_refinements` rounds of AdjustGlobalBundle,
+    CompleteAndMergeTracks and FilterAllPoints3D, until a round changes less than `ba_global_max_refinement_change` of the observations.
+    `triangulator` (an incremental_triangulator.IncrementalTriangulator over this reconstruction; its options are `mapper_options.triangulation`
+    when that exists, the reference's defaults otherwise) does CompleteAndMergeTracks before the loop and in every round between the bundle adjustment and
+    the filter.  Without one that step is left out and `changed` counts filtered observations only, as before.  The closing FilterImages is the image
+    bookkeeping's work, which this package does not mirror."""
     options = mapper_options or IncrementalMapperOptions()
     report = GlobalRefinementReport()
+    tri_options = None
+    if triangulator is not None:
+        tri_options = getattr(options, "triangulation", None) or triangulator.Options()
+        report.initial = triangulator.CompleteAndMergeAllTracks(tri_options)
     for _ in range(options.ba_global_max_refinements):
         num_observations = reconstruction.ComputeNumObservations()
         summaries = []
         AdjustGlobalBundle(reconstruction, GlobalBundleAdjustmentOptions(len(reconstruction.RegImageIds()), options), device=device, summary_out=summaries)
+        num_changed = 0
+        if triangulator is not None:
+            nc, nm, completed, merged = triangulator.CompleteAndMergeAllTracks(tri_options)
+            report.num_completed.append(nc); report.num_merged.append(nm); report.completed.append(completed); report.merged.append(merged)
+            num_changed = nc + nm
         obs_before, points_before = reconstruction._observations(), set(reconstruction.points3D)
         num_filtered = reconstruction.FilterAllPoints3D(options.filter_max_reproj_error, options.filter_min_tri_angle, device=device)
-        changed = float(num_filtered) / num_observations if num_observations else 0.0
+        changed = float(num_changed + num_filtered) / num_observations if num_observations else 0.0
         report.num_rounds += 1
         report.summaries.append(summaries[0] if summaries else None)
         report.num_filtered.append(int(num_filtered))

@@ -12,16 +12,9 @@
 
 #include "ba_impl.hpp"
 #include "camera_models.hpp"
+#include "line_error.hpp"
 
 namespace ppsfm {
-
-__device__ __forceinline__ void QuatToRotNormalized(const double* q_in, double R[9]) {   // QuaternionToRotationMatrix(NormalizeQuaternion(q))
-  const double n = sqrt(q_in[0] * q_in[0] + q_in[1] * q_in[1] + q_in[2] * q_in[2] + q_in[3] * q_in[3]);
-  const double w = q_in[0] / n, x = q_in[1] / n, y = q_in[2] / n, z = q_in[3] / n;
-  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
-  R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
-  R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
-}
 
 __global__ __launch_bounds__(256) void k_filter_obs(int64_t M, const double* __restrict__ la, const double* __restrict__ lb, const double* __restrict__ lc,
                                                     const int32_t* __restrict__ obs_pose, const int32_t* __restrict__ obs_point, const int32_t* __restrict__ obs_cam,
@@ -38,23 +31,8 @@ __global__ __launch_bounds__(256) void k_filter_obs(int64_t M, const double* __r
   const double pz = R[6] * X0 + R[7] * X1 + R[8] * X2 + pose[6];
   if (negative) negative[o] = !(pz >= DBL_EPSILON);       // HasPointPositiveDepth
   if (!err2) return;
-  double e = DBL_MAX;
-  if (!(pz < DBL_EPSILON)) {
-    const double px = R[0] * X0 + R[1] * X1 + R[2] * X2 + pose[4], py = R[3] * X0 + R[4] * X1 + R[5] * X2 + pose[5];
-    const double inv = 1.0 / pz;
-    const double u = inv * px, v = inv * py;
-    const double a = la[o], b = lb[o];
-    const double alpha = a * u + b * v + lc[o];
-    const double lu = u - a * alpha, lv = v - b * alpha;
-    const double* cam = intr + (size_t)kCamStride * k;
-    double ix, iy;
-    WorldToImage<double, double>(model, cam, u, v, &ix, &iy);
-    if (ix >= 0 && ix < (double)cam_size[2 * k] && iy >= 0 && iy < (double)cam_size[2 * k + 1]) {
-      double jx, jy;
-      WorldToImage<double, double>(model, cam, lu, lv, &jx, &jy);
-      e = (ix - jx) * (ix - jx) + (iy - jy) * (iy - jy);
-    }
-  }
+  const double px = R[0] * X0 + R[1] * X1 + R[2] * X2 + pose[4], py = R[3] * X0 + R[4] * X1 + R[5] * X2 + pose[5];
+  const double e = SquaredPixelLineError(px, py, pz, la[o], lb[o], lc[o], model, intr + (size_t)kCamStride * k, cam_size + 2 * k);
   err2[o] = e;
 }
 

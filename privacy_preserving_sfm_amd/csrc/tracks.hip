@@ -1,0 +1,660 @@
+// K10 - track completion and merging: IncrementalTriangulator::CompleteTracks / MergeTracks and their All forms
+//   Complete   reference src/sfm/incremental_triangulator.cc:697-765      Merge   :606-695      drivers :237-293
+//   CalculateSquaredLineReprojectionError   src/base/projection.cc:162-203 (line_error.hpp, shared with K7a)
+//   Reconstruction::AddObservation / MergePoints3D   src/base/reconstruction.cc:190-232
+// The arithmetic is data-parallel (one line error per candidate), the control flow sequential (a line one point claims is gone for the
+// next, a merge creates a point and recurses).  As pp_pose_ransac: the device SPECULATES on the state at the start of the call, the host
+// replays the sequential decisions in ascending point order (tracks_replay.hpp).
+// K10a k_complete_tracks   one wavefront per point: its whole transitive closure over the free lines that pass, breadth first; the lanes run
+//                         over the correspondences of the current frontier line; the accepted lines live in LDS (kLdsList entries), appended
+//                         by ballot + lane prefix in (frontier, correspondence) order.  A closure that outgrows the list flags its point,
+//                         which the <true> instantiation finishes with a list in global memory sized by the host.
+// K10b k_merge_candidates  one wavefront per point: the de-duplicated partner points in (track element, correspondence) order, then per
+//                         candidate the merged position and both tracks against it, the lanes over the track elements, 64 at a time, stopping
+//                         at the first chunk with a failure.
+// K10c k_merge_pair        one wavefront: the same test for ONE pair whose tracks the host hands over (a merged point, a changed candidate).
+// No kernel here waits for another workgroup; the only atomics reserve a point's output segment (one per point) and sum the counters.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <type_traits>
+
+#include "line_error.hpp"
+#include "resource_pool.hpp"
+#include "tracks_replay.hpp"
+
+namespace ppsfm {
+
+constexpr int kLdsList = 512;       // accepted lines of a point kept on chip (4 KiB of LDS per wavefront with their levels)
+constexpr int kCandList = 256;      // candidate partner points of a point kept on chip
+
+struct TrackDev {
+  // static (uploaded at create)
+  const double *proj, *intr, *lines;
+  const int32_t *pose_camera, *camera_model, *cam_size, *line_image, *corr_start, *corr_line;
+  const uint8_t *camera_skip, *image_registered;
+  // state at the start of the call
+  int P;
+  const int32_t *line_point, *track_start, *track_line;
+  const double* points;
+  const uint8_t* subset;
+};
+
+__global__ __launch_bounds__(256) void k_tracks_proj(int C, const double* __restrict__ poses, double* __restrict__ proj) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  double R[9];
+  QuatToRotNormalized(poses + 7 * (size_t)c, R);      // ComposeProjectionMatrix(qvec, tvec)
+  double* o = proj + 12 * (size_t)c;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) { o[4 * r] = R[3 * r]; o[4 * r + 1] = R[3 * r + 1]; o[4 * r + 2] = R[3 * r + 2]; o[4 * r + 3] = poses[7 * (size_t)c + 4 + r]; }
+}
+
+__device__ __forceinline__ double TrackLineError(const TrackDev& d, double X0, double X1, double X2, int l) {
+  const int c = d.line_image[l], k = d.pose_camera[c];
+  const double* Pm = d.proj + 12 * (size_t)c;
+  const double* ln = d.lines + 3 * (size_t)l;
+  const double px = Pm[0] * X0 + Pm[1] * X1 + Pm[2] * X2 + Pm[3], py = Pm[4] * X0 + Pm[5] * X1 + Pm[6] * X2 + Pm[7];
+  const double pz = Pm[8] * X0 + Pm[9] * X1 + Pm[10] * X2 + Pm[11];
+  return SquaredPixelLineError(px, py, pz, ln[0], ln[1], ln[2], d.camera_model[k], d.intr + (size_t)kCamStride * k, d.cam_size + 2 * k);
+}
+
+__device__ __forceinline__ int WaveSumInt(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// lanes whose key an earlier lane of `mask` also holds leave the mask: the first holder in lane order stays
+__device__ __forceinline__ unsigned long long DropLaterDuplicates(unsigned long long mask, int key, int lane) {
+  if (__popcll(mask) < 2) return mask;
+  bool dup = false;
+  for (unsigned long long m = mask; m; m &= m - 1) {
+    const int k = __ffsll((long long)m) - 1;
+    const int other = __shfl(key, k, 64);
+    dup = dup || (k < lane && other == key);
+  }
+  return mask & ~__ballot(dup);
+}
+
+struct CompleteArgs {
+  int num_work;                  // wavefronts: points (first launch) or entries of `work` (second launch)
+  const int32_t* work;           // second launch: the flagged points
+  int max_transitivity;
+  double max2;
+  int32_t *glist_line, *glist_level;      // second launch: num_work x gcap
+  int64_t gcap;
+  int32_t *pool_line, *pool_level;        // first launch: the points' segments
+  unsigned long long pool_cap;
+  unsigned long long* counters;           // [0] pool cursor, [1] line errors computed
+  int64_t* out_start;                     // P: segment of the point (first launch) / unused
+  int32_t* out_count;                     // P (first launch) or num_work (second launch)
+  uint8_t* overflow;                      // P: 1 = finish this point in the second launch
+};
+
+template <bool kGlobal>
+__global__ __launch_bounds__(64) void k_complete_tracks(TrackDev d, CompleteArgs a) {
+  __shared__ int32_t s_line[kGlobal ? 1 : kLdsList], s_level[kGlobal ? 1 : kLdsList];
+  const int w = blockIdx.x, lane = threadIdx.x;
+  if (w >= a.num_work) return;
+  const int p = kGlobal ? a.work[w] : w;
+  int32_t* list_line = kGlobal ? a.glist_line + (size_t)w * a.gcap : s_line;
+  int32_t* list_level = kGlobal ? a.glist_level + (size_t)w * a.gcap : s_level;
+  const int64_t cap = kGlobal ? a.gcap : kLdsList;
+  const int e0 = d.track_start[p], e1 = d.track_start[p + 1];
+  if (!kGlobal) {
+    if (lane == 0) { a.out_count[p] = 0; a.out_start[p] = 0; a.overflow[p] = 0; }
+    if (e1 == e0 || (d.subset && !d.subset[p])) return;
+  }
+  const double X0 = d.points[3 * (size_t)p], X1 = d.points[3 * (size_t)p + 1], X2 = d.points[3 * (size_t)p + 2];
+  int n = 0, evals = 0;
+  int lvl_begin = 0, lvl_end = 0;
+  bool overflow = false;
+  for (int t = 0; t < a.max_transitivity && !overflow; ++t) {
+    const int nf = t == 0 ? e1 - e0 : lvl_end - lvl_begin;
+    if (nf == 0) break;
+    const int n_before = n;
+    for (int f = 0; f < nf && !overflow; ++f) {
+      const int fl = t == 0 ? d.track_line[e0 + f] : list_line[lvl_begin + f];
+      const int c0 = d.corr_start[fl], c1 = d.corr_start[fl + 1];
+      for (int base = c0; base < c1; base += 64) {
+        const int i = base + lane;
+        bool pass = false;
+        int l = -1;
+        if (i < c1) {
+          l = d.corr_line[i];
+          const int img = d.line_image[l];
+          if (d.image_registered[img] && d.line_point[l] < 0 && !d.camera_skip[d.pose_camera[img]]) {
+            bool seen = false;
+            for (int j = 0; j < n; ++j) seen = seen || list_line[j] == l;      // (every lane reads the same entry: a broadcast)
+            if (!seen) { ++evals; pass = !(TrackLineError(d, X0, X1, X2, l) > a.max2); }
+          }
+        }
+        const unsigned long long m = DropLaterDuplicates(__ballot(pass), l, lane);
+        const int cnt = __popcll(m);
+        if (cnt == 0) continue;
+        if ((int64_t)n + cnt > cap) { overflow = true; break; }
+        if ((m >> lane) & 1) {
+          const int pos = n + __popcll(m & ((1ull << lane) - 1));
+          list_line[pos] = l; list_level[pos] = t;
+        }
+        n += cnt;
+        __syncthreads();      // (one wavefront per workgroup, wave-uniform control flow: the appended entries become visible to every lane)
+      }
+    }
+    lvl_begin = n_before; lvl_end = n;
+    if (t >= a.max_transitivity - 1) break;      // what the last level adds is not queued again (:755)
+  }
+  evals = WaveSumInt(evals);
+  if (kGlobal) {
+    if (lane == 0) { a.out_count[w] = overflow ? -1 : n; atomicAdd(&a.counters[1], (unsigned long long)evals); }
+    return;
+  }
+  unsigned long long off = 0;
+  if (lane == 0) {
+    atomicAdd(&a.counters[1], (unsigned long long)evals);
+    if (!overflow && n > 0) {
+      off = atomicAdd(&a.counters[0], (unsigned long long)n);      // the point's segment: one reservation per point, none per entry
+      if (off + (unsigned long long)n > a.pool_cap) overflow = true;
+    }
+    a.overflow[p] = overflow ? 1 : 0;
+    a.out_count[p] = overflow ? 0 : n;
+    a.out_start[p] = (int64_t)off;
+  }
+  overflow = __shfl((int)overflow, 0, 64) != 0;
+  off = ((unsigned long long)(unsigned)__shfl((int)(off >> 32), 0, 64) << 32) | (unsigned)__shfl((int)(off & 0xFFFFFFFFull), 0, 64);
+  if (overflow) return;
+  for (int j = lane; j < n; j += 64) { a.pool_line[off + j] = list_line[j]; a.pool_level[off + j] = list_level[j]; }
+}
+
+struct MergeArgs {
+  double max2;
+  int32_t* pool_cand;
+  uint8_t* pool_ok;
+  unsigned long long pool_cap;
+  unsigned long long* counters;      // [0] pool cursor, [1] line errors computed
+  int64_t* out_start;
+  int32_t* out_count;
+  uint8_t* overflow;
+};
+
+// every element of track a, then of track b, against the merged position: false at the first chunk of 64 with a failure
+template <typename LineAt>
+__device__ __forceinline__ bool MergedTracksPass(const TrackDev& d, const double* Xa, const double* Xb, int la, int lb, double max2, int lane, int* evals, LineAt&& line_at) {
+  const double wa = (double)la, wb = (double)lb;
+  const double M0 = (wa * Xa[0] + wb * Xb[0]) / (wa + wb), M1 = (wa * Xa[1] + wb * Xb[1]) / (wa + wb), M2 = (wa * Xa[2] + wb * Xb[2]) / (wa + wb);
+  const int total = la + lb;
+  for (int base = 0; base < total; base += 64) {
+    const int i = base + lane;
+    bool fail = false;
+    if (i < total) { ++*evals; fail = TrackLineError(d, M0, M1, M2, line_at(i)) > max2; }
+    if (__ballot(fail)) return false;
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(64) void k_merge_candidates(TrackDev d, MergeArgs a) {
+  __shared__ int32_t s_cand[kCandList];
+  const int p = blockIdx.x, lane = threadIdx.x;
+  if (p >= d.P) return;
+  if (lane == 0) { a.out_count[p] = 0; a.out_start[p] = 0; a.overflow[p] = 0; }
+  const int e0 = d.track_start[p], e1 = d.track_start[p + 1];
+  if (e1 == e0 || (d.subset && !d.subset[p])) return;
+  int n = 0;
+  bool overflow = false;
+  for (int f = e0; f < e1 && !overflow; ++f) {
+    const int fl = d.track_line[f];
+    const int c0 = d.corr_start[fl], c1 = d.corr_start[fl + 1];
+    for (int base = c0; base < c1; base += 64) {
+      const int i = base + lane;
+      bool cand = false;
+      int q = -1;
+      if (i < c1) {
+        const int l = d.corr_line[i];
+        if (d.image_registered[d.line_image[l]]) {
+          q = d.line_point[l];
+          if (q >= 0 && q != p) {
+            bool seen = false;
+            for (int j = 0; j < n; ++j) seen = seen || s_cand[j] == q;
+            cand = !seen;
+          }
+        }
+      }
+      const unsigned long long m = DropLaterDuplicates(__ballot(cand), q, lane);
+      const int cnt = __popcll(m);
+      if (cnt == 0) continue;
+      if (n + cnt > kCandList) { overflow = true; break; }
+      if ((m >> lane) & 1) s_cand[n + __popcll(m & ((1ull << lane) - 1))] = q;
+      n += cnt;
+      __syncthreads();
+    }
+  }
+  unsigned long long off = 0;
+  if (lane == 0) {
+    if (!overflow && n > 0) {
+      off = atomicAdd(&a.counters[0], (unsigned long long)n);
+      if (off + (unsigned long long)n > a.pool_cap) overflow = true;
+    }
+    a.overflow[p] = overflow ? 1 : 0;
+    a.out_count[p] = overflow ? 0 : n;
+    a.out_start[p] = (int64_t)off;
+  }
+  overflow = __shfl((int)overflow, 0, 64) != 0;
+  off = ((unsigned long long)(unsigned)__shfl((int)(off >> 32), 0, 64) << 32) | (unsigned)__shfl((int)(off & 0xFFFFFFFFull), 0, 64);
+  if (overflow) return;
+  int evals = 0;
+  const double* Xa = d.points + 3 * (size_t)p;
+  for (int ci = 0; ci < n; ++ci) {
+    const int q = s_cand[ci];
+    const int b0 = d.track_start[q], lb = d.track_start[q + 1] - b0, la = e1 - e0;
+    const bool ok = MergedTracksPass(d, Xa, d.points + 3 * (size_t)q, la, lb, a.max2, lane, &evals,
+                                     [&](int i) { return i < la ? d.track_line[e0 + i] : d.track_line[b0 + i - la]; });
+    if (lane == 0) { a.pool_cand[off + ci] = q; a.pool_ok[off + ci] = ok ? 1 : 0; }
+  }
+  evals = WaveSumInt(evals);
+  if (lane == 0) atomicAdd(&a.counters[1], (unsigned long long)evals);
+}
+
+// one pair: slot[0] <- 1 / 0, slot[1] <- line errors computed; slot + 2 = the la + lb lines of the two tracks (pinned host memory)
+__global__ __launch_bounds__(64) void k_merge_pair(TrackDev d, int32_t* slot, int la, int lb, double xa0, double xa1, double xa2, double xb0, double xb1, double xb2, double max2) {
+  const int lane = threadIdx.x;
+  const double Xa[3] = {xa0, xa1, xa2}, Xb[3] = {xb0, xb1, xb2};
+  const int32_t* lines = slot + 2;
+  int evals = 0;
+  const bool ok = MergedTracksPass(d, Xa, Xb, la, lb, max2, lane, &evals, [&](int i) { return lines[i]; });
+  evals = WaveSumInt(evals);
+  if (lane == 0) { slot[1] = evals; slot[0] = ok ? 1 : 0; }
+}
+
+}  // namespace ppsfm
+
+using namespace ppsfm;
+
+struct pp_tracks_impl {
+  int device = 0, C = 0, K = 0;
+  int64_t L = 0, E = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  TrackState st;
+  std::vector<void*> blocks;      // the static device arrays (pool blocks)
+  TrackDev dev{};
+  int32_t* d_line_point = nullptr;
+  int32_t* pin = nullptr;         // pinned slots of the fresh-pair launches
+  size_t pin_ints = 0;
+};
+
+namespace {
+
+using Clock = std::chrono::steady_clock;
+double MsSince(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+
+// pool blocks of one call, returned after the stream has drained on every way out
+struct CallBlocks {
+  hipStream_t s;
+  std::vector<void*> b;
+  explicit CallBlocks(hipStream_t stream) : s(stream) {}
+  ~CallBlocks() { (void)hipStreamSynchronize(s); for (void* p : b) PoolDeviceFree(p); }
+  template <typename T>
+  int Alloc(T** p, size_t count) {
+    void* q = nullptr;
+    const int rc = PoolDeviceAlloc(&q, std::max<size_t>(count, 1) * sizeof(T));
+    if (!rc) { b.push_back(q); *p = (T*)q; }
+    return rc;
+  }
+  template <typename T>
+  int Put(T** p, const T* src, size_t count) {
+    int rc = Alloc(p, count);
+    if (!rc) rc = Upload(*p, src, count, s);
+    return rc;
+  }
+};
+
+#define TR(x) do { const int _rc = (x); if (_rc) return _rc; } while (0)
+
+// uploads the state at the start of a call; flat track CSR in start / elems (kept alive by the caller until the stream drains)
+int UploadState(pp_tracks_impl* h, CallBlocks& cb, const uint8_t* subset, std::vector<int32_t>& start, std::vector<int32_t>& elems, TrackDev* d) {
+  const TrackState& st = h->st;
+  const int P = st.NumPoints();
+  start.assign((size_t)P + 1, 0);
+  size_t T = 0;
+  for (int p = 0; p < P; ++p) { T += st.tracks[(size_t)p].size(); PP_REQUIRE(T < 0x7FFFFFFFull, "pp_tracks: too many track elements"); start[(size_t)p + 1] = (int32_t)T; }
+  elems.resize(T);
+  for (int p = 0; p < P; ++p) std::copy(st.tracks[(size_t)p].begin(), st.tracks[(size_t)p].end(), elems.begin() + start[(size_t)p]);
+  *d = h->dev;
+  d->P = P;
+  TR(Upload(h->d_line_point, st.line_point.data(), (size_t)h->L, h->stream));
+  d->line_point = h->d_line_point;
+  int32_t *d_start = nullptr, *d_elems = nullptr;
+  double* d_points = nullptr;
+  uint8_t* d_subset = nullptr;
+  TR(cb.Put(&d_start, start.data(), start.size()));
+  TR(cb.Put(&d_elems, elems.data(), elems.size()));
+  TR(cb.Put(&d_points, st.points.data(), st.points.size()));
+  if (subset) TR(cb.Put(&d_subset, subset, (size_t)P));
+  d->track_start = d_start; d->track_line = d_elems; d->points = d_points; d->subset = d_subset;
+  return PP_OK;
+}
+
+int CheckOptions(const pp_tracks_options* o, const char* where) {
+  PP_REQUIRE(o && o->merge_max_reproj_error >= 0 && o->complete_max_reproj_error >= 0 && o->complete_max_transitivity >= 0, "%s: bad options", where);
+  return PP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void pp_tracks_options_default(pp_tracks_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->merge_max_reproj_error = 4.0; o->complete_max_reproj_error = 4.0; o->complete_max_transitivity = 5;
+}
+
+int pp_tracks_destroy(pp_tracks_handle h) try {
+  if (!h) return PP_OK;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (void* p : h->blocks) PoolDeviceFree(p);
+  PoolPinnedFree(h->pin);
+  PoolEventRelease(h->ev0, true); PoolEventRelease(h->ev1, true);
+  PoolStreamRelease(h->stream);
+  delete h;
+  return PP_OK;
+} PP_API_CATCH("pp_tracks_destroy")
+
+int pp_tracks_create(const pp_tracks_desc* d, int device, pp_tracks_handle* out) try {
+  PP_REQUIRE(d && out, "pp_tracks_create: null argument");
+  *out = nullptr;
+  const int C = d->num_images, K = d->num_cameras, P = d->num_points;
+  const int64_t L = d->num_lines, E = d->num_corrs;
+  PP_REQUIRE(C > 0 && K > 0 && P >= 0 && L >= 0 && E >= 0 && L < 0x7FFFFFFF && E < 0x7FFFFFFF, "pp_tracks_create: bad sizes");
+  PP_REQUIRE(d->poses && d->pose_camera && d->camera_model && d->intr && d->cam_size && d->corr_start && d->track_start && (P == 0 || d->points) &&
+                 (L == 0 || (d->lines && d->line_image && d->line_point)) && (E == 0 || d->corr_line),
+             "pp_tracks_create: null array");
+  for (int k = 0; k < K; ++k) PP_REQUIRE(pp_camera_num_params(d->camera_model[k]) > 0, "pp_tracks_create: unknown camera model");
+  for (int c = 0; c < C; ++c) PP_REQUIRE(d->pose_camera[c] >= 0 && d->pose_camera[c] < K, "pp_tracks_create: camera index out of range");
+  PP_REQUIRE(d->corr_start[0] == 0 && d->corr_start[L] == E, "pp_tracks_create: corr_start does not span num_corrs");
+  for (int64_t l = 0; l < L; ++l) {
+    PP_REQUIRE(d->line_image[l] >= 0 && d->line_image[l] < C, "pp_tracks_create: image index out of range");
+    PP_REQUIRE(d->line_point[l] >= -1 && d->line_point[l] < P, "pp_tracks_create: point index out of range");
+    PP_REQUIRE(d->corr_start[l] <= d->corr_start[l + 1], "pp_tracks_create: corr_start decreases");
+    const double a = d->lines[3 * l], b = d->lines[3 * l + 1];
+    PP_REQUIRE(std::fabs(std::sqrt(a * a + b * b) - 1.0) <= 1e-6, "pp_tracks_create: line %lld is not normalised (a^2 + b^2 = 1)", (long long)l);
+  }
+  for (int64_t e = 0; e < E; ++e) PP_REQUIRE(d->corr_line[e] >= 0 && d->corr_line[e] < L, "pp_tracks_create: correspondence out of range");
+  PP_REQUIRE(d->track_start[0] == 0, "pp_tracks_create: track_start[0] != 0");
+  for (int p = 0; p < P; ++p) PP_REQUIRE(d->track_start[p] <= d->track_start[p + 1], "pp_tracks_create: track_start decreases");
+  const int64_t T = d->track_start[P];
+  PP_REQUIRE(T == 0 || d->track_line, "pp_tracks_create: null array");
+  {
+    std::vector<uint8_t> seen((size_t)L, 0);
+    for (int p = 0; p < P; ++p)
+      for (int64_t e = d->track_start[p]; e < d->track_start[p + 1]; ++e) {
+        const int32_t l = d->track_line[e];
+        PP_REQUIRE(l >= 0 && l < L && d->line_point[l] == p && !seen[(size_t)l], "pp_tracks_create: track of point %d and line_point disagree", p);
+        seen[(size_t)l] = 1;
+      }
+    for (int64_t l = 0; l < L; ++l) PP_REQUIRE((d->line_point[l] >= 0) == (seen[(size_t)l] != 0), "pp_tracks_create: line %lld has a point but is in no track", (long long)l);
+  }
+  int ndev = 0;
+  PP_HIP_TRY(hipGetDeviceCount(&ndev));
+  PP_REQUIRE(device >= 0 && device < ndev, "pp_tracks_create: device %d of %d", device, ndev);
+  PP_HIP_TRY(hipSetDevice(device));
+  pp_tracks_impl* h = new pp_tracks_impl();
+  OnUnwind unwind{[&] { (void)pp_tracks_destroy(h); }};
+  int rc = PP_OK;
+#define TRYC(x) do { rc = (x); if (rc) { (void)pp_tracks_destroy(h); return rc; } } while (0)
+  h->device = device; h->C = C; h->K = K; h->L = L; h->E = E;
+  TrackState& st = h->st;
+  st.L = L;
+  st.line_image.assign(d->line_image, d->line_image + L);
+  st.corr_start.assign(d->corr_start, d->corr_start + L + 1);
+  st.corr_line.assign(d->corr_line, d->corr_line + E);
+  st.image_registered.assign((size_t)C, 1);
+  if (d->image_registered) st.image_registered.assign(d->image_registered, d->image_registered + C);
+  st.line_point.assign(d->line_point, d->line_point + L);
+  st.points.assign(d->points, d->points + 3 * (size_t)P);
+  st.tracks.resize((size_t)P);
+  st.deleted.assign((size_t)P, 0);
+  for (int p = 0; p < P; ++p) { st.tracks[(size_t)p].assign(d->track_line + d->track_start[p], d->track_line + d->track_start[p + 1]); st.deleted[(size_t)p] = st.tracks[(size_t)p].empty(); }
+  std::vector<uint8_t> skip((size_t)K, 0);
+  if (d->camera_skip) skip.assign(d->camera_skip, d->camera_skip + K);
+  TRYC(PoolStreamAcquire(&h->stream));
+  TRYC(PoolEventAcquire(&h->ev0, true)); TRYC(PoolEventAcquire(&h->ev1, true));
+  hipStream_t s = h->stream;
+  auto put = [&](auto** p, const auto* src, size_t count) {
+    void* q = nullptr;
+    int r = PoolDeviceAlloc(&q, std::max<size_t>(count, 1) * sizeof(**p));
+    if (r) return r;
+    h->blocks.push_back(q);
+    *p = (std::remove_reference_t<decltype(*p)>)q;
+    return src ? Upload(*p, src, count, s) : PP_OK;
+  };
+  double *d_poses = nullptr, *d_proj = nullptr, *d_intr = nullptr, *d_lines = nullptr;
+  int32_t *d_pc = nullptr, *d_cm = nullptr, *d_cs = nullptr, *d_li = nullptr, *d_c0 = nullptr, *d_cl = nullptr;
+  uint8_t *d_skip = nullptr, *d_reg = nullptr;
+  TRYC(put(&d_poses, d->poses, (size_t)7 * C)); TRYC(put(&d_proj, (const double*)nullptr, (size_t)12 * C)); TRYC(put(&d_intr, d->intr, (size_t)kCamStride * K));
+  TRYC(put(&d_lines, d->lines, (size_t)3 * L)); TRYC(put(&d_pc, d->pose_camera, (size_t)C)); TRYC(put(&d_cm, d->camera_model, (size_t)K));
+  TRYC(put(&d_cs, d->cam_size, (size_t)2 * K)); TRYC(put(&d_li, d->line_image, (size_t)L)); TRYC(put(&d_c0, d->corr_start, (size_t)L + 1));
+  TRYC(put(&d_cl, d->corr_line, (size_t)E)); TRYC(put(&d_skip, skip.data(), (size_t)K)); TRYC(put(&d_reg, st.image_registered.data(), (size_t)C));
+  TRYC(put(&h->d_line_point, (const int32_t*)nullptr, (size_t)L));
+  hipLaunchKernelGGL(k_tracks_proj, dim3(CeilDiv(C, 256)), dim3(256), 0, s, C, d_poses, d_proj);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { SetLastError("pp_tracks_create: upload failed"); (void)pp_tracks_destroy(h); return PP_ERR_HIP; }
+#undef TRYC
+  h->dev.proj = d_proj; h->dev.intr = d_intr; h->dev.lines = d_lines; h->dev.pose_camera = d_pc; h->dev.camera_model = d_cm; h->dev.cam_size = d_cs;
+  h->dev.line_image = d_li; h->dev.corr_start = d_c0; h->dev.corr_line = d_cl; h->dev.camera_skip = d_skip; h->dev.image_registered = d_reg;
+  *out = h;
+  return PP_OK;
+} PP_API_CATCH("pp_tracks_create")
+
+int pp_tracks_complete(pp_tracks_handle h, const pp_tracks_options* o, const uint8_t* point_subset, pp_tracks_report* report, int32_t* added_point,
+                       int32_t* added_line, int64_t capacity) try {
+  PP_REQUIRE(h && report && capacity >= 0 && (capacity == 0 || (added_point && added_line)), "pp_tracks_complete: bad argument");
+  TR(CheckOptions(o, "pp_tracks_complete"));
+  const auto t_begin = Clock::now();
+  std::memset(report, 0, sizeof(*report));
+  PP_HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  TrackState& st = h->st;
+  const int P = st.NumPoints();
+  if (P == 0) return PP_OK;
+  std::vector<int32_t> start, elems;
+  std::vector<int32_t> pool_line, count((size_t)P);
+  std::vector<int64_t> seg((size_t)P);
+  std::vector<uint8_t> over((size_t)P);
+  std::vector<std::vector<int32_t>> second;      // lists of the points the second launch finished
+  std::vector<int32_t> second_of((size_t)P, -1);
+  unsigned long long counters[2] = {0, 0};
+  float ms_total = 0.f;
+  {
+    CallBlocks cb(s);
+    TrackDev d;
+    TR(UploadState(h, cb, point_subset, start, elems, &d));
+    CompleteArgs a{};
+    a.num_work = P; a.max_transitivity = o->complete_max_transitivity; a.max2 = o->complete_max_reproj_error * o->complete_max_reproj_error;
+    a.pool_cap = (unsigned long long)(2 * h->E + 1024);
+    TR(cb.Alloc(&a.pool_line, (size_t)a.pool_cap)); TR(cb.Alloc(&a.pool_level, (size_t)a.pool_cap)); TR(cb.Alloc(&a.counters, 2));
+    TR(cb.Alloc(&a.out_start, (size_t)P)); TR(cb.Alloc(&a.out_count, (size_t)P)); TR(cb.Alloc(&a.overflow, (size_t)P));
+    PP_HIP_TRY(hipMemsetAsync(a.counters, 0, 2 * sizeof(unsigned long long), s));
+    PP_HIP_TRY(hipEventRecord(h->ev0, s));
+    hipLaunchKernelGGL(k_complete_tracks<false>, dim3(P), dim3(64), 0, s, d, a);
+    PP_HIP_TRY(hipGetLastError());
+    PP_HIP_TRY(hipEventRecord(h->ev1, s));
+    TR(Download(count.data(), a.out_count, (size_t)P, s)); TR(Download(seg.data(), a.out_start, (size_t)P, s)); TR(Download(over.data(), a.overflow, (size_t)P, s));
+    TR(Download(counters, a.counters, 2, s));
+    PP_HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0.f;
+    PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    ms_total += ms;
+    const size_t used = (size_t)std::min<unsigned long long>(counters[0], a.pool_cap);
+    pool_line.resize(used);
+    TR(Download(pool_line.data(), a.pool_line, used, s));
+    PP_HIP_TRY(hipStreamSynchronize(s));
+    // the flagged points: a list in global memory that cannot overflow (a closure holds free lines only, each once)
+    std::vector<int32_t> work;
+    for (int p = 0; p < P; ++p) if (over[(size_t)p]) work.push_back(p);
+    if (!work.empty()) {
+      int64_t gcap = 0;
+      for (int64_t l = 0; l < h->L; ++l) gcap += st.line_point[(size_t)l] < 0;
+      gcap = std::max<int64_t>(gcap, 1);
+      const size_t batch = (size_t)std::max<int64_t>(1, std::min<int64_t>((int64_t)work.size(), (int64_t)(32 << 20) / gcap));
+      int32_t *d_work = nullptr, *d_cnt = nullptr;
+      TR(cb.Alloc(&a.glist_line, batch * (size_t)gcap)); TR(cb.Alloc(&a.glist_level, batch * (size_t)gcap));
+      TR(cb.Alloc(&d_work, batch)); TR(cb.Alloc(&d_cnt, batch));
+      a.gcap = gcap;
+      std::vector<int32_t> cnt2(batch), rows;
+      for (size_t b0 = 0; b0 < work.size(); b0 += batch) {
+        const size_t nb = std::min(batch, work.size() - b0);
+        TR(Upload(d_work, work.data() + b0, nb, s));
+        a.num_work = (int)nb; a.work = d_work; a.out_count = d_cnt;
+        PP_HIP_TRY(hipEventRecord(h->ev0, s));
+        hipLaunchKernelGGL(k_complete_tracks<true>, dim3((unsigned)nb), dim3(64), 0, s, d, a);
+        PP_HIP_TRY(hipGetLastError());
+        PP_HIP_TRY(hipEventRecord(h->ev1, s));
+        TR(Download(cnt2.data(), d_cnt, nb, s));
+        PP_HIP_TRY(hipStreamSynchronize(s));
+        PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        ms_total += ms;
+        ++report->second_launches;
+        for (size_t i = 0; i < nb; ++i) {
+          if (cnt2[i] < 0 || cnt2[i] > gcap) { SetLastError("pp_tracks_complete: the closure of point %d outgrew every free line", work[b0 + i]); return PP_ERR_INTERNAL; }
+          rows.resize((size_t)cnt2[i]);
+          TR(Download(rows.data(), a.glist_line + i * (size_t)gcap, (size_t)cnt2[i], s));
+          PP_HIP_TRY(hipStreamSynchronize(s));
+          second_of[(size_t)work[b0 + i]] = (int32_t)second.size();
+          second.push_back(rows);
+        }
+      }
+      TR(Download(counters, a.counters, 2, s));
+      PP_HIP_TRY(hipStreamSynchronize(s));
+      report->overflow_points = (int32_t)work.size();
+    }
+  }
+  report->device_ms = ms_total;
+  report->candidates_evaluated = (int64_t)counters[1];
+  const auto t_replay = Clock::now();
+  int64_t written = 0;
+  const CompleteCounters cnt = ReplayComplete(
+      st, point_subset, o->complete_max_transitivity,
+      [&](int p) {
+        const int32_t k = second_of[(size_t)p];
+        if (k >= 0) return SpecList{second[(size_t)k].data(), (int64_t)second[(size_t)k].size()};
+        return SpecList{pool_line.data() + seg[(size_t)p], (int64_t)count[(size_t)p]};
+      },
+      [&](int p, int32_t l) { if (written < capacity) { added_point[written] = p; added_line[written] = l; } ++written; });
+  report->num_changed = cnt.num_completed;
+  report->num_entries = written;
+  report->conflict_replays = cnt.conflict_replays;
+  report->replay_ms = MsSince(t_replay);
+  report->total_ms = MsSince(t_begin);
+  return PP_OK;
+} PP_API_CATCH("pp_tracks_complete")
+
+int pp_tracks_merge(pp_tracks_handle h, const pp_tracks_options* o, const uint8_t* point_subset, pp_tracks_report* report, int32_t* merged_a,
+                    int32_t* merged_b, int32_t* merged_new, int64_t capacity) try {
+  PP_REQUIRE(h && report && capacity >= 0 && (capacity == 0 || (merged_a && merged_b && merged_new)), "pp_tracks_merge: bad argument");
+  TR(CheckOptions(o, "pp_tracks_merge"));
+  const auto t_begin = Clock::now();
+  std::memset(report, 0, sizeof(*report));
+  PP_HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  TrackState& st = h->st;
+  const int P0 = st.NumPoints();
+  if (P0 == 0) return PP_OK;
+  const double max2 = o->merge_max_reproj_error * o->merge_max_reproj_error;
+  std::vector<int32_t> start, elems, count((size_t)P0), pool_cand;
+  std::vector<int64_t> seg((size_t)P0);
+  std::vector<uint8_t> over((size_t)P0), pool_ok;
+  unsigned long long counters[2] = {0, 0};
+  TrackDev d;
+  CallBlocks cb(s);      // (the state arrays stay up for the fresh-pair launches)
+  TR(UploadState(h, cb, point_subset, start, elems, &d));
+  {
+    MergeArgs a{};
+    a.max2 = max2;
+    a.pool_cap = (unsigned long long)(h->E + 1);      // a line has one point: the candidate lists together hold at most one entry per correspondence
+    TR(cb.Alloc(&a.pool_cand, (size_t)a.pool_cap)); TR(cb.Alloc(&a.pool_ok, (size_t)a.pool_cap)); TR(cb.Alloc(&a.counters, 2));
+    TR(cb.Alloc(&a.out_start, (size_t)P0)); TR(cb.Alloc(&a.out_count, (size_t)P0)); TR(cb.Alloc(&a.overflow, (size_t)P0));
+    PP_HIP_TRY(hipMemsetAsync(a.counters, 0, 2 * sizeof(unsigned long long), s));
+    PP_HIP_TRY(hipEventRecord(h->ev0, s));
+    hipLaunchKernelGGL(k_merge_candidates, dim3(P0), dim3(64), 0, s, d, a);
+    PP_HIP_TRY(hipGetLastError());
+    PP_HIP_TRY(hipEventRecord(h->ev1, s));
+    TR(Download(count.data(), a.out_count, (size_t)P0, s)); TR(Download(seg.data(), a.out_start, (size_t)P0, s)); TR(Download(over.data(), a.overflow, (size_t)P0, s));
+    TR(Download(counters, a.counters, 2, s));
+    PP_HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0.f;
+    PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    report->device_ms = ms;
+    const size_t used = (size_t)std::min<unsigned long long>(counters[0], a.pool_cap);
+    pool_cand.resize(used); pool_ok.resize(used);
+    TR(Download(pool_cand.data(), a.pool_cand, used, s)); TR(Download(pool_ok.data(), a.pool_ok, used, s));
+    PP_HIP_TRY(hipStreamSynchronize(s));
+  }
+  for (int p = 0; p < P0; ++p) report->overflow_points += over[(size_t)p];
+  int64_t evaluated = (int64_t)counters[1];
+  const auto t_replay = Clock::now();
+  auto fresh = [&](int a, int q) -> int {      // one small synchronous launch; the result comes back through the pinned slot
+    const std::vector<int32_t>&ta = st.tracks[(size_t)a], &tb = st.tracks[(size_t)q];
+    const size_t need = 2 + ta.size() + tb.size();
+    if (need > h->pin_ints) {
+      PoolPinnedFree(h->pin); h->pin = nullptr; h->pin_ints = 0;
+      void* q2 = nullptr;
+      if (PoolPinnedAlloc(&q2, std::max<size_t>(need * 2, 1024) * sizeof(int32_t))) return PP_ERR_HIP;
+      h->pin = (int32_t*)q2; h->pin_ints = std::max<size_t>(need * 2, 1024);
+    }
+    h->pin[0] = -1; h->pin[1] = 0;
+    std::copy(ta.begin(), ta.end(), h->pin + 2);
+    std::copy(tb.begin(), tb.end(), h->pin + 2 + ta.size());
+    const double *xa = &st.points[3 * (size_t)a], *xb = &st.points[3 * (size_t)q];
+    hipLaunchKernelGGL(k_merge_pair, dim3(1), dim3(64), 0, s, d, h->pin, (int)ta.size(), (int)tb.size(), xa[0], xa[1], xa[2], xb[0], xb[1], xb[2], max2);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess || h->pin[0] < 0) { SetLastError("pp_tracks_merge: the launch for pair (%d, %d) failed", a, q); return PP_ERR_HIP; }
+    ++report->fresh_pair_launches;
+    evaluated += h->pin[1];
+    return h->pin[0];
+  };
+  auto eval = [&](int a, int q) -> int {
+    if (a < P0 && q < P0 && !over[(size_t)a]) {      // both as the speculation saw them (a merge only deletes points and creates new ones)
+      const int32_t* c = pool_cand.data() + seg[(size_t)a];
+      for (int32_t i = 0; i < count[(size_t)a]; ++i) if (c[i] == q) return pool_ok[(size_t)seg[(size_t)a] + i];
+    }
+    return fresh(a, q);
+  };
+  int64_t written = 0;
+  auto emit = [&](int a, int q, int m) { if (written < capacity) { merged_a[written] = a; merged_b[written] = q; merged_new[written] = m; } ++written; };
+  MergeReplay<decltype(eval), decltype(emit)> replay{st, eval, emit, {}, {}, 0};
+  replay.Run(point_subset);
+  if (replay.error) return replay.error;      // (the merges made so far stay applied: the header tells the caller to destroy the handle)
+  report->num_changed = replay.cnt.num_merged;
+  report->num_entries = written;
+  report->candidates_evaluated = evaluated;
+  report->replay_ms = MsSince(t_replay);
+  report->total_ms = MsSince(t_begin);
+  return PP_OK;
+} PP_API_CATCH("pp_tracks_merge")
+
+int pp_tracks_get_state(pp_tracks_handle h, int32_t* num_points, int64_t* num_track_elements, int32_t* line_point, double* points, uint8_t* deleted,
+                        int32_t* track_start, int32_t* track_line, int32_t point_capacity, int64_t element_capacity) try {
+  PP_REQUIRE(h && num_points && num_track_elements, "pp_tracks_get_state: null argument");
+  const TrackState& st = h->st;
+  const int P = st.NumPoints();
+  int64_t T = 0;
+  for (int p = 0; p < P; ++p) T += (int64_t)st.tracks[(size_t)p].size();
+  *num_points = P; *num_track_elements = T;
+  PP_REQUIRE(!(points || deleted || track_start) || point_capacity >= P, "pp_tracks_get_state: point_capacity %d < %d points", point_capacity, P);
+  PP_REQUIRE(!track_line || element_capacity >= T, "pp_tracks_get_state: element_capacity too small");
+  if (line_point) std::copy(st.line_point.begin(), st.line_point.end(), line_point);
+  if (points) std::copy(st.points.begin(), st.points.end(), points);
+  if (deleted) for (int p = 0; p < P; ++p) deleted[p] = st.tracks[(size_t)p].empty() ? 1 : 0;
+  int64_t e = 0;
+  for (int p = 0; p < P; ++p) {
+    if (track_start) track_start[p] = (int32_t)e;
+    if (track_line) std::copy(st.tracks[(size_t)p].begin(), st.tracks[(size_t)p].end(), track_line + e);
+    e += (int64_t)st.tracks[(size_t)p].size();
+  }
+  if (track_start) track_start[P] = (int32_t)e;
+  return PP_OK;
+} PP_API_CATCH("pp_tracks_get_state")
+
+}  // extern "C"

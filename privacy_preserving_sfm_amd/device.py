@@ -580,3 +580,99 @@ def triangulate_tracks(track_start, lines, obs_view, proj_matrices, proj_centers
                                             ptr(cm, _capi.c_ip), dp(it), ptr(cs, _capi.c_ip), C.byref(options), ptr(ok, _capi.c_u8p), dp(xyz), ptr(mask, _capi.c_u8p),
                                             ptr(nt, _capi.c_ip), C.byref(ms)))
     return ok.astype(bool), xyz, mask[: len(ov)].astype(bool), nt, float(ms.value)
+
+
+def tracks_options(**kw):
+    o = _capi.TracksOptions()
+    _capi.lib().pp_tracks_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+_TRACKS_FIELDS = (("poses", np.float64, dp), ("pose_camera", np.int32, None), ("camera_model", np.int32, None), ("intr", np.float64, dp),
+                  ("cam_size", np.int32, None), ("camera_skip", np.uint8, None), ("image_registered", np.uint8, None), ("lines", np.float64, dp),
+                  ("line_image", np.int32, None), ("line_point", np.int32, None), ("corr_start", np.int32, None), ("corr_line", np.int32, None),
+                  ("points", np.float64, dp), ("track_start", np.int32, None), ("track_line", np.int32, None))
+
+
+def tracks_desc(flat, keep):
+    """pp_tracks_desc of a flat dict (IncrementalTriangulator.flatten's first result; camera_skip / image_registered may be missing or None)"""
+    d = _capi.TracksDesc()
+    d.num_images, d.num_cameras, d.num_points = int(np.shape(flat["poses"])[0]), int(np.shape(flat["intr"])[0]), int(np.shape(flat["points"])[0])
+    d.num_lines, d.num_corrs = int(len(flat["line_image"])), int(len(flat["corr_line"]))
+    types = {np.int32: _capi.c_ip, np.uint8: _capi.c_u8p}
+    for name, dt, _ in _TRACKS_FIELDS:
+        a = flat.get(name)
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        setattr(d, name, dp(a) if dt is np.float64 else ptr(a, types[dt]))
+    return d
+
+
+class TracksProblem:
+    """pp_tracks_handle: the flattened state of the triangulator on the device; complete() / merge() advance it, state() reads it."""
+
+    def __init__(self, flat, device=0):
+        self._keep = []
+        self._h = C.c_void_p()
+        self.num_lines = int(len(flat["line_image"]))
+        d = tracks_desc(flat, self._keep)
+        check(_capi.lib().pp_tracks_create(C.byref(d), int(device), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            _capi.lib().pp_tracks_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def num_points(self):
+        n, t = C.c_int32(), C.c_int64()
+        check(_capi.lib().pp_tracks_get_state(self._h, C.byref(n), C.byref(t), None, None, None, None, None, 0, 0))
+        return n.value, t.value
+
+    def _subset(self, point_subset):
+        return None if point_subset is None else np.ascontiguousarray(point_subset, dtype=np.uint8)
+
+    def complete(self, options=None, point_subset=None):
+        """-> (report, pairs [n, 2] (point, line) in the order the reference appends them)"""
+        o = options or tracks_options()
+        sub = self._subset(point_subset)
+        assert sub is None or len(sub) == self.num_points()[0]
+        cap = self.num_lines
+        ap, al = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+        rep = _capi.TracksReport()
+        check(_capi.lib().pp_tracks_complete(self._h, C.byref(o), ptr(sub, _capi.c_u8p), C.byref(rep), ptr(ap, _capi.c_ip), ptr(al, _capi.c_ip), cap))
+        n = int(rep.num_entries)
+        return rep, np.stack([ap[:n], al[:n]], axis=1)
+
+    def merge(self, options=None, point_subset=None):
+        """-> (report, merges [n, 3] (a, b, new index) in order)"""
+        o = options or tracks_options()
+        sub = self._subset(point_subset)
+        cap = self.num_points()[0]
+        assert sub is None or len(sub) == cap
+        a, b, m = (np.zeros(cap, dtype=np.int32) for _ in range(3))
+        rep = _capi.TracksReport()
+        check(_capi.lib().pp_tracks_merge(self._h, C.byref(o), ptr(sub, _capi.c_u8p), C.byref(rep), ptr(a, _capi.c_ip), ptr(b, _capi.c_ip), ptr(m, _capi.c_ip), cap))
+        n = int(rep.num_entries)
+        return rep, np.stack([a[:n], b[:n], m[:n]], axis=1)
+
+    def state(self):
+        """-> dict(line_point [L], points [P', 3], deleted [P'], track_start [P' + 1], track_line)"""
+        P, T = self.num_points()
+        lp, pts, dele = np.zeros(self.num_lines, dtype=np.int32), np.zeros((P, 3)), np.zeros(P, dtype=np.uint8)
+        ts, tl = np.zeros(P + 1, dtype=np.int32), np.zeros(T, dtype=np.int32)
+        n, t = C.c_int32(), C.c_int64()
+        check(_capi.lib().pp_tracks_get_state(self._h, C.byref(n), C.byref(t), ptr(lp, _capi.c_ip), dp(pts), ptr(dele, _capi.c_u8p), ptr(ts, _capi.c_ip),
+                                              ptr(tl, _capi.c_ip), P, T))
+        return dict(line_point=lp, points=pts, deleted=dele, track_start=ts, track_line=tl)

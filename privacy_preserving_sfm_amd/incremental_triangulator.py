@@ -1,0 +1,190 @@
+"""Host mirror of the reference's track completion and merging (sfm/incremental_triangulator.{h,cc}: `CompleteTracks`, `CompleteAllTracks`,
+`MergeTracks`, `MergeAllTracks`, `GetModifiedPoints3D`, `ClearModifiedPoints3D`) and of the `CorrespondenceGraph` query they read
+(base/correspondence_graph.h `FindCorrespondences`), on top of pp_tracks_* (include/ppsfm_hip.h).
+
+Each call flattens the reconstruction (`flatten`), hands it to the device and applies what comes back through `Reconstruction.AddObservation` /
+`Reconstruction.MergePoints3D`.  The reference visits the points in the order of an unordered_set; here the order is ASCENDING POINT ID.
+`TriangulateImage`, `CompleteImage` and `Retriangulate` (commented out in the reference) are not mirrored."""
+import numpy as np
+
+from . import _capi
+from .bundle_adjustment import Camera, FeatureLine, Image, Point3D, Reconstruction
+from .device import TracksProblem, tracks_options
+
+
+class CorrespondenceGraph:
+    """The part of base/correspondence_graph.h the triangulator reads: per (image, line) the corresponding (image, line) pairs, in a fixed order."""
+
+    def __init__(self):
+        self._corrs = {}
+
+    def AddCorrespondence(self, image_id1, line_idx1, image_id2, line_idx2):
+        self._corrs.setdefault((image_id1, line_idx1), []).append((image_id2, line_idx2))
+
+    def FindCorrespondences(self, image_id, line_idx):
+        return self._corrs.get((image_id, line_idx), [])
+
+
+class IncrementalTriangulator:
+    class Options:
+        """incremental_triangulator.h:37-90, the reference's defaults"""
+
+        def __init__(self):
+            self.max_transitivity = 1
+            self.create_max_angle_error = 2.0
+            self.continue_max_angle_error = 2.0
+            self.merge_max_reproj_error = 4.0
+            self.complete_max_reproj_error = 4.0
+            self.complete_max_transitivity = 5
+            self.re_max_angle_error = 5.0
+            self.re_min_ratio = 0.2
+            self.re_max_trials = 1
+            self.min_angle = 1.5
+            self.ignore_two_view_tracks = True
+            self.min_focal_length_ratio = 0.1
+            self.max_focal_length_ratio = 10.0
+            self.max_extra_param = 1.0
+
+        def Check(self):
+            return (self.merge_max_reproj_error >= 0 and self.complete_max_reproj_error >= 0 and self.complete_max_transitivity >= 0 and
+                    self.min_focal_length_ratio > 0 and self.max_focal_length_ratio > 0 and self.max_extra_param >= 0)
+
+    def __init__(self, correspondence_graph, reconstruction, device=0):
+        self.correspondence_graph_, self.reconstruction_, self.device_ = correspondence_graph, reconstruction, device
+        self.modified_point3D_ids_ = set()
+        self.last_reports = []      # the pp_tracks_report of every device call of the last driver call
+
+    def GetModifiedPoints3D(self):
+        rec = self.reconstruction_
+        return set(p for p in self.modified_point3D_ids_ if p in rec.points3D)      # "assume that all other points were deleted"
+
+    def ClearModifiedPoints3D(self):
+        self.modified_point3D_ids_.clear()
+
+    def flatten(self, options=None):
+        """-> (flat dict for device.TracksProblem, point_ids [P], line_ref [L] = (image_id, line_idx)).  Host only.  Lines are numbered image by
+        image in id order; camera_skip is HasCameraBogusParams per camera (decided once per camera, :767-779)."""
+        options = options or self.Options()
+        rec, graph = self.reconstruction_, self.correspondence_graph_
+        image_ids, point_ids, cam_ids = sorted(rec.images), sorted(rec.points3D), sorted(rec.cameras)
+        unsized = [c for c in cam_ids if not hasattr(rec.cameras[c], "width")]
+        if unsized:      # the line error's in-image gate and HasBogusParams both read the image size (Camera(..., width=, height=))
+            raise ValueError("IncrementalTriangulator needs the width and height of every camera; missing for camera ids %s" % unsized)
+        cam_index = {c: k for k, c in enumerate(cam_ids)}
+        point_index = {p: k for k, p in enumerate(point_ids)}
+        offset, line_ref = {}, []
+        for iid in image_ids:
+            offset[iid] = len(line_ref)
+            line_ref.extend((iid, idx) for idx in range(len(rec.images[iid].lines)))
+        L = len(line_ref)
+        lines, line_image, line_point = np.zeros((L, 3)), np.zeros(L, dtype=np.int32), np.full(L, -1, dtype=np.int32)
+        corr_start, corr_line = np.zeros(L + 1, dtype=np.int32), []
+        for c, iid in enumerate(image_ids):
+            for idx, fl in enumerate(rec.images[iid].lines):
+                l = offset[iid] + idx
+                lines[l], line_image[l] = fl.Line(), c
+                if fl.HasPoint3D():
+                    line_point[l] = point_index[fl.Point3DId()]
+                corr_line.extend(offset[i2] + x2 for (i2, x2) in graph.FindCorrespondences(iid, idx) if i2 in offset)
+                corr_start[l + 1] = len(corr_line)
+        track_start, track_line = np.zeros(len(point_ids) + 1, dtype=np.int32), []
+        for k, pid in enumerate(point_ids):
+            track_line.extend(offset[iid] + idx for (iid, idx) in rec.points3D[pid].track)
+            track_start[k + 1] = len(track_line)
+        intr = np.zeros((len(cam_ids), _capi.CAM_STRIDE))
+        for cid, k in cam_index.items():
+            intr[k, : rec.cameras[cid].NumParams()] = rec.cameras[cid].params
+        flat = dict(poses=np.array([np.concatenate([rec.images[i].qvec, rec.images[i].tvec]) for i in image_ids]).reshape(-1, 7),
+                    pose_camera=np.array([cam_index[rec.images[i].camera_id] for i in image_ids], dtype=np.int32),
+                    camera_model=np.array([rec.cameras[c].model_id for c in cam_ids], dtype=np.int32), intr=intr,
+                    cam_size=np.array([[rec.cameras[c].width, rec.cameras[c].height] for c in cam_ids], dtype=np.int32).reshape(-1, 2),
+                    camera_skip=np.array([rec.cameras[c].HasBogusParams(options.min_focal_length_ratio, options.max_focal_length_ratio, options.max_extra_param)
+                                          for c in cam_ids], dtype=np.uint8),
+                    image_registered=np.array([getattr(rec.images[i], "registered", True) for i in image_ids], dtype=np.uint8),
+                    lines=lines, line_image=line_image, line_point=line_point, corr_start=corr_start, corr_line=np.array(corr_line, dtype=np.int32),
+                    points=np.array([rec.points3D[p].xyz for p in point_ids]).reshape(-1, 3), track_start=track_start,
+                    track_line=np.array(track_line, dtype=np.int32))
+        return flat, point_ids, line_ref
+
+    @staticmethod
+    def device_options(options):
+        return tracks_options(merge_max_reproj_error=options.merge_max_reproj_error, complete_max_reproj_error=options.complete_max_reproj_error,
+                              complete_max_transitivity=options.complete_max_transitivity)
+
+    def _run(self, options, point3D_ids, complete, merge):
+        assert options.Check()
+        rec = self.reconstruction_
+        self.last_reports = []
+        if not rec.points3D:
+            return 0, 0, [], []
+        flat, point_ids, line_ref = self.flatten(options)
+        wanted = None if point3D_ids is None else set(point3D_ids)
+        subset = None if wanted is None else np.array([p in wanted for p in point_ids], dtype=np.uint8)
+        o = self.device_options(options)
+        ids = list(point_ids)      # device index -> point id, new points appended as the merges are applied
+        completed, merged, num_completed, num_merged = [], [], 0, 0
+        pb = TracksProblem(flat, device=self.device_)
+        try:
+            if complete:
+                rep, pairs = pb.complete(o, subset)
+                self.last_reports.append(rep)
+                num_completed = int(rep.num_changed)
+                for p, l in pairs:
+                    rec.AddObservation(ids[p], line_ref[l])
+                    self.modified_point3D_ids_.add(ids[p])
+                    completed.append((ids[p], line_ref[l]))
+            if merge:
+                rep, merges = pb.merge(o, subset)
+                self.last_reports.append(rep)
+                num_merged = int(rep.num_changed)
+                for a, b, m in merges:
+                    new_id = rec.MergePoints3D(ids[a], ids[b])
+                    assert m == len(ids)
+                    self.modified_point3D_ids_.discard(ids[a]); self.modified_point3D_ids_.discard(ids[b])
+                    self.modified_point3D_ids_.add(new_id)
+                    merged.append((ids[a], ids[b], new_id))
+                    ids.append(new_id)
+        finally:
+            pb.close()
+        return num_completed, num_merged, completed, merged
+
+    def CompleteTracks(self, options, point3D_ids):
+        return self._run(options, point3D_ids, True, False)[0]
+
+    def CompleteAllTracks(self, options):
+        return self._run(options, None, True, False)[0]
+
+    def MergeTracks(self, options, point3D_ids):
+        return self._run(options, point3D_ids, False, True)[1]
+
+    def MergeAllTracks(self, options):
+        return self._run(options, None, False, True)[1]
+
+    def CompleteAndMergeAllTracks(self, options):
+        """CompleteAllTracks then MergeAllTracks (controllers/incremental_mapper.cc:160-172) on ONE device handle:
+        -> (num_completed, num_merged, [(point id, (image_id, line_idx))], [(id a, id b, new id)])"""
+        return self._run(options, None, True, True)
+
+
+def reconstruction_from_completion_scene(scene):
+    """(Reconstruction, CorrespondenceGraph) of synthetic.make_completion_scene: image ids 0..C-1, point ids 0..P'-1, the cameras sized by `cam_size`"""
+    rec, graph = Reconstruction(), CorrespondenceGraph()
+    for k in range(scene["intr"].shape[0]):
+        m = int(scene["camera_model"][k])
+        rec.cameras[k] = Camera(k, m, scene["intr"][k, : _capi.lib().pp_camera_num_params(m)], width=int(scene["cam_size"][k, 0]), height=int(scene["cam_size"][k, 1]))
+    for c in range(scene["poses"].shape[0]):
+        rec.images[c] = Image(c, int(scene["pose_camera"][c]), scene["poses"][c, :4], scene["poses"][c, 4:])
+    for p in range(scene["points"].shape[0]):
+        rec.points3D[p] = Point3D(scene["points"][p])
+    ref = []
+    for l in range(len(scene["line_image"])):
+        c, p = int(scene["line_image"][l]), int(scene["line_point"][l])
+        rec.images[c].lines.append(FeatureLine(scene["line_xyz"][l], False, p))
+        ref.append((c, len(rec.images[c].lines) - 1))
+        if p >= 0:
+            rec.points3D[p].track.append(ref[-1])
+    cs, cl = scene["corr_start"], scene["corr_line"]
+    for l in range(len(ref)):
+        for e in range(cs[l], cs[l + 1]):
+            graph.AddCorrespondence(ref[l][0], ref[l][1], ref[cl[e]][0], ref[cl[e]][1])
+    return rec, graph

@@ -370,3 +370,79 @@ def make_track_scene(num_views, num_tracks, seed=0, min_len=3, max_len=12, noise
     return dict(track_start=np.array(track_start, dtype=np.int32), lines=np.array(lines), obs_view=np.array(obs_view, dtype=np.int32), P=P, centers=centers,
                 view_camera=np.zeros(num_views, dtype=np.int32), camera_model=np.array([model], dtype=np.int32), intr=intr,
                 cam_size=np.array([[1280, 960]], dtype=np.int32), points=pts, is_outlier=np.array(is_out))
+
+
+def make_completion_scene(num_cams, num_points, track, seed=0, withheld=0.25, split=0.15, edge_density=0.15, false_edges=0.05,
+                          width=1280, height=960, **ba_kw):
+    """A reconstruction with planted work for track completion and merging (reference sfm/incremental_triangulator.cc:606-765), on top of
+    make_ba_scene(num_cams, num_points, track, seed, **ba_kw) and a random stream of its own (make_ba_scene's arrays are untouched).
+
+    Every observation of the base scene is one line of its image (several lines per image).  Planted:
+    `withheld`: this share of each true point's observations has no 3D point (free lines) - every Point3D keeps at least 4 observations;
+    `split`: this share of the true points is two Point3Ds with disjoint tracks (the second one's position carries its own noise);
+    the correspondence graph holds, per true point, a random path through ALL its lines (withheld ones included) plus each further pair
+    with probability `edge_density` - no clique, so a withheld line may hang on withheld lines only (transitivity 2 and above) - and
+    `false_edges` (a share of the line count) edges between lines of different true points.  All edges are symmetric.
+
+    Returns the base scene's dict plus: `line_xyz` [L, 3] lines grouped by image (idx within the image = position in the group), `line_image`,
+    `line_point` (-1 free), `line_true_point`, `corr_start` / `corr_line` (CSR over lines), `points` [P', 3] (P' = P + split points),
+    `cam_size`, and the planted truth: `withheld_lines`, `split_pairs` [(first, second)], `false_edge_list`."""
+    base = make_ba_scene(num_cams, num_points, track, seed=seed, **ba_kw)
+    rng = np.random.default_rng([int(seed), 0xC0DE])
+    C, P, M = int(num_cams), int(num_points), int(num_points) * int(track)
+    order = np.argsort(base["obs_pose"], kind="stable")              # lines grouped by image
+    line_of_obs = np.empty(M, dtype=np.int64); line_of_obs[order] = np.arange(M)
+    line_image = base["obs_pose"][order].astype(np.int32)
+    line_true = base["obs_point"][order].astype(np.int32)
+    line_point = line_true.copy()
+    points = [base["points"][p] for p in range(P)]
+    noise = float(ba_kw.get("noise_point", 1e-2))
+    obs_of_point = [np.flatnonzero(base["obs_point"] == p) for p in range(P)] if P * M < 5e7 else None
+    if obs_of_point is None:
+        by_point = np.argsort(base["obs_point"], kind="stable")
+        obs_of_point = np.split(by_point, np.cumsum(np.bincount(base["obs_point"], minlength=P))[:-1])
+    split_pairs, withheld_lines, edges = [], [], set()
+    is_split = rng.uniform(size=P) < split
+    for p in range(P):
+        lines_p = line_of_obs[obs_of_point[p]]
+        perm = rng.permutation(len(lines_p))
+        groups = [lines_p]
+        if is_split[p] and len(lines_p) >= 8:
+            half = len(lines_p) // 2
+            groups = [lines_p[perm[:half]], lines_p[perm[half:]]]
+            q = len(points)
+            points.append(base["gt_points"][p] + rng.normal(0, noise, 3))
+            line_point[groups[1]] = q
+            split_pairs.append((p, q))
+        for g in groups:
+            nfree = min(int(round(withheld * len(g))), max(len(g) - 4, 0))
+            free = rng.choice(g, size=nfree, replace=False) if nfree else []
+            for l in free:
+                line_point[l] = -1
+                withheld_lines.append(int(l))
+        path = lines_p[rng.permutation(len(lines_p))]
+        for a, b in zip(path[:-1], path[1:]):
+            edges.add((int(min(a, b)), int(max(a, b))))
+        for i in range(len(lines_p)):
+            for j in range(i + 1, len(lines_p)):
+                if rng.uniform() < edge_density:
+                    edges.add((int(min(lines_p[i], lines_p[j])), int(max(lines_p[i], lines_p[j]))))
+    false_list = []
+    for _ in range(int(round(false_edges * M))):
+        a, b = (int(v) for v in rng.integers(0, M, 2))
+        if line_true[a] != line_true[b] and (min(a, b), max(a, b)) not in edges:
+            edges.add((min(a, b), max(a, b)))
+            false_list.append((min(a, b), max(a, b)))
+    nbr = [[] for _ in range(M)]
+    for a, b in sorted(edges):
+        nbr[a].append(b); nbr[b].append(a)
+    for l in range(M):                                      # the order FindCorrespondences returns: a fixed shuffle per line
+        nbr[l] = [nbr[l][i] for i in rng.permutation(len(nbr[l]))]
+    corr_start = np.zeros(M + 1, dtype=np.int32)
+    corr_start[1:] = np.cumsum([len(v) for v in nbr])
+    corr_line = np.array([b for v in nbr for b in v], dtype=np.int32)
+    out = dict(base)
+    out.update(line_xyz=np.ascontiguousarray(base["lines"][order]), line_image=line_image, line_point=line_point.astype(np.int32), line_true_point=line_true,
+               corr_start=corr_start, corr_line=corr_line, points=np.array(points), cam_size=np.tile(np.array([[width, height]], dtype=np.int32), (base["intr"].shape[0], 1)),
+               withheld_lines=sorted(withheld_lines), split_pairs=split_pairs, false_edge_list=false_list)
+    return out
