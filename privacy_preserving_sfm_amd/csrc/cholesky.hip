@@ -19,6 +19,9 @@
 //                 after a fallback) one launch per block column, over every tile or, for a block-sparse system, over its non-zero tiles only
 //                 (the per-launch lists of EnsureSparseLists); captured into a graph once per bind and replayed.
 // Task and column mode run the same work items (same arithmetic per 16x16 piece, bitwise equal results up to 48 block columns).
+// This file is the device code and its launch driver (CholeskyState, ChoosePath, CholeskyBind, CholeskySolve, the plan cache, the uploads).  The
+// PLANNER of task mode - the chains of a tile map, the task list, its host replay, the lists of the block-sparse per-column launches, and the
+// vocabulary the kernels share with it (ChainRanges, the counter layout, ChainTask) - is host-only and lives in chol_plan.hpp.
 // Column mode: right-looking blocked algorithm, 64 x 64 blocks, ONE launch per block column (k_column_step, see there):
 // a chain workgroup (solve of the tile X left of the next diagonal block, that block's update by X X', its
 // factorisation and the 64x64 INVERSE of the new diagonal factor) runs in the same grid as a prep workgroup (applies
@@ -50,19 +53,10 @@
 
 #include "ba_impl.hpp"
 #include "chol_block.hpp"
+#include "chol_plan.hpp"
 #include "resource_pool.hpp"
 
 namespace ppsfm {
-
-// SEVERAL CHAINS (a block-sparse system whose elimination tree has independent sub-trees - a nested-dissection order of the cameras: the leaves are
-// factorised side by side, the separators last).  A chain is a run of consecutive block columns [begin, end) whose tiles (k+1,k) / (k+2,k) exist; it
-// STARTS at a block column whose rows k, k+1, k+2 have nothing left of column k (no panel ever touches the three tiles of its first step: k_potrf64
-// factorises every chain's first diagonal block) and a chain that is followed by another one STOPS after the step that produces M_(end-1): its last
-// block column is solved by solve tasks alone (rows >= end + 3: the separators), and `post` is what it stores into sol[end - 1] when the solved tile
-// (end-1,end-2) is in L.  Workgroup c of k_cholesky_tasks runs chain c; the task list follows.
-constexpr int kMaxChains = 16;
-struct ChainRanges { int32_t n; int32_t begin[kMaxChains]; int32_t end[kMaxChains]; int32_t post[kMaxChains]; };
-inline ChainRanges OneChain(int T) { ChainRanges cr; std::memset(&cr, 0, sizeof(cr)); cr.n = 1; cr.end[0] = T; return cr; }
 
 // the FIRST diagonal block of every chain (workgroup c: block column cr.begin[c]; one chain: block column 0): factor in place, emit its inverse
 // (row-major 64x64) to that block column's slot of Minv, copy the tile below it to its X slot
@@ -116,14 +110,6 @@ __global__ __launch_bounds__(kPanelThreads) void k_potrf64(double* __restrict__ 
       *reinterpret_cast<double2*>(xs + (size_t)kb * kNB * kNB + r * kNB + 2 * c2) = *reinterpret_cast<const double2*>(S + diag + (size_t)(kNB + r) * ld + 2 * c2);
     }
   }
-}
-
-// lower-triangular tile index t -> (row, col), row >= col
-__device__ __forceinline__ void TriIndex(int t, int* row, int* col) {
-  int r = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-  while ((r + 1) * (r + 2) / 2 <= t) ++r;
-  while (r * (r + 1) / 2 > t) --r;
-  *row = r; *col = t - r * (r + 1) / 2;
 }
 
 // Trailing update by block column kp of the region below / right of block (kp+2, kp+2):  C -= A_i A_j^T, in 128x128
@@ -441,8 +427,6 @@ __global__ __launch_bounds__(kPanelThreads) void k_column_step(double* __restric
   PP_CHOL_LAUNCH(2, k);
 }
 
-__host__ __device__ inline int BacksubNumPairs(int T) { return T >= 7 ? (T - 3) / 2 : 0; }      // blocks 0 .. 2 npairs - 1 in pairs, the 3 or 4 above singly
-
 // C (16 x 16 piece (ti, tj), D layout) = A B over K = 64, A and B 64 x 64 tiles in LDS (row stride kLS), four partial accumulators
 __device__ __forceinline__ v4f64 TileProduct64(const double* A, const double* B, int ti, int tj, int lr, int g) {
   double av[16], bv[16];
@@ -548,50 +532,7 @@ __global__ __launch_bounds__(kPanelThreads) void k_backsub_prepare(const double*
 //   * data written exactly ONCE per launch and only read after a counter says so can not be stale in any L2 and is read with
 //     plain, L2-cached loads: the solved tiles live in their own array L (the factor ends up there; the back substitution reads
 //     it from there), and so does M_k for the solve tasks.
-constexpr int kMaxSteps = 128;       // block columns the counter arrays hold (N <= 8192)
-constexpr int kMaxSuper = kMaxSteps / 2 + 1;
-constexpr int kScratchCounters = 2048;      // counters of the per-chain accumulation sequences (several chains, see ChainRanges), handed out by the host
-enum { cSol0 = 8, cVer0 = cSol0 + kMaxChains * kMaxSteps, cSub0 = cVer0 + kMaxSuper * kMaxSuper, cScratch0 = cSub0 + kMaxSuper * kMaxSuper,
-       kNumCounters = cScratch0 + kScratchCounters };      // sol: one set of row counters per chain (cSol0 + chain x kMaxSteps + row)
-static_assert(kNumCounters * sizeof(int32_t) <= 8192 * sizeof(double), "counters exceed their part of the workspace (CholeskyWorkspaceDoubles)");
-enum { kTaskPrepX = 1, kTaskPrepD = 2, kTaskSolve = 3, kTaskUpdate = 4, kTaskPairPrep = 5, kTaskMerge = 6 };      // pair prep: a = pair, b = part (paired back substitution)
-// solve: a = block row; update: a = I, b = J | part << 8 | parts << 12 | target << 16: a PART of super-tile (I,J) - parts = 2: block row
-// 2I + part (both block columns); parts = 4: the one 64x64 tile (2I + part / 2, 2J + part % 2).  The part that brings the
-// super-tile's sub-counter to `target` (the parts listed for it so far) moves its ver counter.
-// w0, w1: the values the task's ver counters must have reached (the panels an EXISTING earlier task applies; in a dense system k - 1).  In a
-// block-sparse system a panel only touches the super-tiles whose tiles it couples, so "every panel below k" becomes "the last panel below k that has
-// an update task for this super-tile" - which only the host, who lists the tasks, knows.
-// w2: the value the row counter sol[] of the row the task SOLVES a tile of must have reached - the row's previous structurally non-zero column, solved:
-// the solves of a row stay in column order (a counter value then says "every non-zero column below it is solved"), whichever columns exist.
-// Values a task STORES into a counter come from the host as well (they were k / k + 1 while the block columns were eliminated in index order):
-//   PrepX / PrepD  a = the value "column k-1 of a row is solved" (0 for the first step of a chain), b = "column k is solved"
-//   solve          w1 = "column k is solved" (stored into sol[i])
-//   update         w1 = the value the super-tile's ver counter takes once every part of this panel is applied, w2 = "column k-1 is solved"
-// flags: bit 0 = k is the FIRST block column of a chain (nothing pending from a column k-1; M_k is k_potrf64's); bits 4..7 = the chain whose row counters the
-// task waits for / moves (the chain of block column k; of column k-1 for an update)
-// update / merge tasks: cidx / sidx = the ver / sub counter of the sequence the task belongs to (absolute index), zsel = -1: the tiles of S themselves, >= 0:
-// the chain whose scratch tiles the task accumulates into (update) or adds to S (merge: cidx = the super-tile's own ver counter, sidx = the scratch sequence's, w2 = the
-// value that one must have reached), mask = bits 0..3: tiles of the super-tile nothing has been accumulated into yet (update: taken as zero instead of read;
-// merge: the tiles to add)
-// slot[q]: where tile q (2 x row + column) of the super-tile lives in the scratch pool (64 x 64 doubles per slot, row stride 64) when zsel >= 0
-struct ChainTask { int32_t type, k, a, b, w0, w1, w2, flags, cidx, sidx, zsel, mask, slot[4]; };
-constexpr int kPartsTwoPanels = 8;      // `parts` of an update task that applies panels k-1 and k to its whole super-tile (far from the front)
 constexpr int kSpinBound = 1 << 21;
-// Super-tile columns this far right of the front are updated whole, nearer ones in two halves.  Halves keep the per-super-tile
-// sequence of updates shorter than a step of the chain (they cannot fall behind), whole super-tiles move the least operand bytes
-// per flop: the smaller the matrix, the more the chain bounds the time and the further out halves pay.  Measured optimum
-// (tools/chol_time.py with PPSFM_CHOL_WHOLE_FROM), round 2, priority slope 0.5: 12 at 47 block columns (0.73 against 0.77 ms with 6), 9 at 63,
-// 6 at 79, 3 at 94.  Round 3 (tools/sched_sweep.sh, the knobs swept on one box): what the chain still waited for in steps 8-18 of a
-// 47-column factorisation (~45 us in all) was the BULK - every CU busy with updates, the front updates of the step dispatched late - and
-// not the position of PrepX / PrepD in the list (moving them one or two steps ahead changed nothing); and the bulk of the early steps is
-// bound by its TRAFFIC (~800 tiles per step x ~100 KB per tile and panel = 6 TB/s).  So: (a) a flatter priority (far updates deferred
-// by 0.3 instead of 0.5 steps per super-column: less of the far work piles up behind the front later on; steeper ones are much worse -
-// 0.75: 804 us, 1.0: 887 us at 47 columns) with whole super-tiles five columns nearer: 743 -> 728 us (factorisation + back
-// substitution in the tool); (b) far super-tiles take TWO panels per task (UpdateSuperTile<true>: C read and written once per two
-// steps, the second panel's operands in flight under the first panel's products), and with that "far" starts three super-columns from
-// the front: 47 columns 728 -> 706 us, 63: 1262 -> 1120, 79: 2135 -> 1765 (whole_from 2), 16 - 32 columns unchanged.
-constexpr double kUpdateSlope = 0.3;
-static int WholeFrom(int T) { return T >= 56 ? 2 : 3; }
 constexpr unsigned long long kPoison = 0xFFFFFFFFFFFFFFFFull;
 
 // mailboxes of one factorisation: 64x64 row-major slots (stride 64), one per step
@@ -1260,8 +1201,8 @@ __global__ __launch_bounds__(kPanelThreads) void k_cholesky_tasks(double* S, dou
 #endif
   const ChainTask t = tasks[b - cr.n];
   const int k = t.k;
-  const bool first = (t.flags & 1) != 0;
-  const int solbase = cSol0 + ((t.flags >> 4) & 15) * kMaxSteps;
+  const bool first = TaskFirstOfChain(t.flags);
+  const int solbase = cSol0 + TaskChain(t.flags) * kMaxSteps;
   double* B0 = smem; double* B1 = smem + kNB * kLS; double* B2 = smem + 2 * kNB * kLS; double* B3 = smem + 3 * kNB * kLS;
   auto tile_nz = [&](int r, int c) { return !nz || nz[(size_t)r * T + c] != 0; };
   if (t.type == kTaskPrepX || t.type == kTaskPrepD) {
@@ -1300,7 +1241,7 @@ __global__ __launch_bounds__(kPanelThreads) void k_cholesky_tasks(double* S, dou
   }
   if (t.type == kTaskMerge) {
     // what another chain has accumulated for super-tile (I,J) in its scratch array is added to the tiles themselves: one step of the super-tile's own sequence
-    const int I = t.a, J = t.b & 255;
+    const int I = t.a, J = t.b & 255;      // (TaskSuperColumn, spelled out: through the accessor the four tile offsets below come out with other shifts)
     WaitList wl;
     wl.p0 = ctr + t.cidx; wl.n0 = t.w0;
     wl.p1 = ctr + t.sidx; wl.n1 = t.w2;
@@ -1323,7 +1264,7 @@ __global__ __launch_bounds__(kPanelThreads) void k_cholesky_tasks(double* S, dou
   }
   {
     // super-tile (I,J) by panel k-1: column k-1 of its block rows solved, the panels <= k-2 applied to it
-    const int I = t.a, J = t.b & 255, part = (t.b >> 8) & 15, parts = (t.b >> 12) & 15, target = t.b >> 16;
+    const int I = t.a, J = TaskSuperColumn(t.b), part = TaskPart(t.b), parts = TaskParts(t.b), target = TaskTarget(t.b);
     const bool two = parts == kPartsTwoPanels;      // the whole super-tile by panels k-1 AND k: column k solved as well, ver moves by two
     WaitList wl;
     wl.p0 = ctr + t.cidx; wl.n0 = t.w0;
@@ -1681,20 +1622,8 @@ __global__ __launch_bounds__(kPairThreads) void k_backsub_pairs(const double* __
 // (Four consecutive blocks per workgroup - 12 hand-offs between workgroups instead of 47, the hops inside a group through LDS - was
 // measured at 98 us against 62 us: the x_k of the group above arrive as a burst, and the 4 x 4 tiles they multiply (512 KB) have no
 // place on the CU to wait in, so their loads queue up behind each other on the critical path; see DESIGN.md.)
-// Symbolic Cholesky on the tile graph: eliminating block column k couples every pair of rows that have a non-zero tile in it.
-int SymbolicTileFill(int T, uint8_t* nz) {
-  for (int i = 0; i < T; ++i) nz[(size_t)i * T + i] = 1;
-  std::vector<int> rows;
-  for (int k = 0; k < T; ++k) {
-    rows.clear();
-    for (int i = k + 1; i < T; ++i) if (nz[(size_t)i * T + k]) rows.push_back(i);
-    for (size_t a = 0; a < rows.size(); ++a)
-      for (size_t b = 0; b <= a; ++b) nz[(size_t)rows[a] * T + rows[b]] = 1;
-  }
-  int count = 0;
-  for (int i = 0; i < T; ++i) for (int j = 0; j <= i; ++j) count += nz[(size_t)i * T + j] ? 1 : 0;
-  return count;
-}
+// (the planner's CloseTileMap under the name the other translation units call it by: ba_impl.hpp)
+int SymbolicTileFill(int T, uint8_t* nz) { return CloseTileMap(T, nz); }
 
 enum class CholPath { Small, Tasks, Columns, SparseColumns };      // the launch path of a bound system (ChoosePath)
 
@@ -1725,45 +1654,16 @@ struct CholeskyState {
   int fallbacks = 0;                // one-launch factorisations that ran into a bounded wait and were repeated per column (pp_ba_summary::cholesky_fallbacks)
 };
 
-// Block-sparse structure: tile_nz (T x T, lower triangle, row-major; the caller has already closed it under the fill-in of
-// the factorisation) -> per launch k the rows of the solve workgroups and the super-tiles of the update workgroups.
-// Layout of st->sparse_host: [T+1 offsets of the row lists | T+1 offsets of the super-tile lists | the lists]; the same
+// Block-sparse structure: the per-launch lists of the bound tile map (BuildSparseColumnLists, chol_plan.hpp) in st->sparse_host; the same
 // array on the device, plus the T x T byte map for the back substitution.
 static int EnsureSparseLists(CholeskyState* st, int T, hipStream_t strm) {
   if (st->sparse_lists && st->sparse_T == T) return PP_OK;
   if (st->sparse_lists) { (void)hipFree(st->sparse_lists); st->sparse_lists = nullptr; }
   if (st->sparse_nz) { (void)hipFree(st->sparse_nz); st->sparse_nz = nullptr; }
   const uint8_t* nz = st->tile_nz;
-  auto has = [&](int i, int j) { return i < T && j < T && nz[(size_t)i * T + j] != 0; };
-  std::vector<int32_t> rows, sups, row_off(T + 1, 0), sup_off(T + 1, 0);
-  for (int k = 0; k + 1 < T; ++k) {
-    row_off[k] = (int32_t)rows.size(); sup_off[k] = (int32_t)sups.size();
-    for (int i = k + 3; i < T; ++i) if (has(i, k)) rows.push_back(i);
-    if (k >= 1) {
-      const int kp = k - 1, k1 = kp + 2, nb = T - k1, ns = (nb + 1) / 2, nsup = ns * (ns + 1) / 2 - 1;
-      for (int u = 0; u < nsup; ++u) {
-        int I = (int)((std::sqrt(8.0 * (u + 1) + 1.0) - 1.0) * 0.5);      // TriIndex(u + 1)
-        while ((I + 1) * (I + 2) / 2 <= u + 1) ++I;
-        while (I * (I + 1) / 2 > u + 1) --I;
-        const int J = u + 1 - I * (I + 1) / 2;
-        bool any = false;
-        for (int q = 0; q < 4; ++q) {
-          const int bi = k1 + 2 * I + (q >> 1), bj = k1 + 2 * J + (q & 1);
-          any = any || (bi < T && bj < T && bi >= bj && has(bi, kp) && has(bj, kp));
-        }
-        if (any) sups.push_back(u);
-      }
-    }
-  }
-  for (int k = T - 1; k <= T; ++k) { row_off[k] = (int32_t)rows.size(); sup_off[k] = (int32_t)sups.size(); }
-  st->sparse_host.clear();
-  st->sparse_host.insert(st->sparse_host.end(), row_off.begin(), row_off.end());
-  st->sparse_host.insert(st->sparse_host.end(), sup_off.begin(), sup_off.end());
-  const int base_rows = (int)st->sparse_host.size();
-  st->sparse_host.insert(st->sparse_host.end(), rows.begin(), rows.end());
-  const int base_sups = (int)st->sparse_host.size();
-  st->sparse_host.insert(st->sparse_host.end(), sups.begin(), sups.end());
-  st->sparse_base_rows = base_rows; st->sparse_base_sups = base_sups;
+  SparseColumnLists lists = BuildSparseColumnLists(T, nz);
+  st->sparse_host.swap(lists.lists);
+  st->sparse_base_rows = lists.base_rows; st->sparse_base_sups = lists.base_sups;
   PP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st->sparse_lists), sizeof(int32_t) * std::max<size_t>(st->sparse_host.size(), 1)));
   PP_HIP_TRY(hipMemcpyAsync(st->sparse_lists, st->sparse_host.data(), sizeof(int32_t) * st->sparse_host.size(), hipMemcpyHostToDevice, strm));
   PP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st->sparse_nz), (size_t)T * T));
@@ -1778,418 +1678,13 @@ static int EnsureSparseLists(CholeskyState* st, int T, hipStream_t strm) {
 // tools/chol_time.py)
 static bool UseTasks(int T) { return T >= 4 && T <= kMaxSteps; }
 
-// The chains of a tile map (see ChainRanges), the map the one-launch mode works with, and the ORDER in which its block columns are eliminated:
-//   map      the caller's (already closed under fill-in) plus, inside every chain, the two sub-diagonals - the tiles the chain and the prep tasks own at
-//            every step whether anything couples them or not - closed under fill-in again (a no-op for a band of at least two tiles)
-//   time[k]  length of the longest dependency path below block column k (k for one chain): columns of different chains with the same time are
-//            eliminated side by side
-//   rho1[k]  1 + the rank of k in the order (time, k): the value that says "column k is done" in a counter.  Every counter is moved by tasks that wait
-//            for each other in this order, so "counter >= rho1[k]" means k's contribution and every earlier one are in (k + 1 for one chain).
-struct ChainPlan {
-  ChainRanges cr;
-  std::vector<uint8_t> map;      // empty: dense
-  std::vector<int> time, rho1, chain_of;
-};
-static ChainPlan PlanChains(int T, const uint8_t* nz, const PlanSwitches& ps, int max_chains = kMaxChains) {
-  ChainPlan p;
-  std::memset(&p.cr, 0, sizeof(p.cr));
-  std::vector<int> starts{0};
-  if (ps.chains) max_chains = std::max(1, std::min(kMaxChains, *ps.chains));
-  if (nz) {
-    for (int k = 3; k + 4 <= T && (int)starts.size() < max_chains; ++k) {
-      if (k - starts.back() < 3) continue;
-      bool empty = true;
-      for (int r = k; r <= k + 2 && empty; ++r)
-        for (int c = 0; c < k && empty; ++c) empty = nz[(size_t)r * T + c] == 0;
-      if (empty) starts.push_back(k);
-    }
-  }
-  p.cr.n = (int)starts.size();
-  p.chain_of.assign(T, 0);
-  for (int c = 0; c < p.cr.n; ++c) {
-    p.cr.begin[c] = starts[c]; p.cr.end[c] = c + 1 < p.cr.n ? starts[c + 1] : T;
-    for (int k = p.cr.begin[c]; k < p.cr.end[c]; ++k) p.chain_of[k] = c;
-  }
-  if (nz) {
-    p.map.assign(nz, nz + (size_t)T * T);
-    for (int c = 0; c < p.cr.n; ++c)
-      for (int k = p.cr.begin[c]; k < p.cr.end[c]; ++k)
-        for (int i = k; i < p.cr.end[c] && i <= k + 2; ++i) p.map[(size_t)i * T + k] = 1;
-    (void)SymbolicTileFill(T, p.map.data());
-  }
-  p.time.assign(T, 0);
-  for (int k = 0; k < T; ++k) {
-    // (the panels of ANOTHER chain reach the tiles of this column's tasks - rows k .. k+2: PrepX / PrepD(k) finish tiles of row k+2 - when that chain is
-    // through: its merge tasks are listed a step behind the solves of its last block column, and they must be listed before this column's tasks)
-    int t = 0;
-    const int ck = p.chain_of[k];
-    for (int j = 0; j < k; ++j) {
-      if (!nz) { t = std::max(t, p.time[j] + 1); continue; }
-      if (p.chain_of[j] == ck) { if (p.map[(size_t)k * T + j]) t = std::max(t, p.time[j] + 1); continue; }
-      for (int r = k; r <= k + 2 && r < p.cr.end[ck]; ++r) if (p.map[(size_t)r * T + j]) t = std::max(t, p.time[p.cr.end[p.chain_of[j]] - 1] + 2);
-    }
-    p.time[k] = t;
-  }
-  std::vector<int> order(T);
-  for (int k = 0; k < T; ++k) order[k] = k;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return p.time[a] < p.time[b]; });
-  p.rho1.assign(T, 0);
-  for (int r = 0; r < T; ++r) p.rho1[order[r]] = r + 1;
-  for (int c = 0; c < p.cr.n; ++c) p.cr.post[c] = p.cr.end[c] < T ? p.rho1[p.cr.end[c] - 2] : 0;
-  return p;
-}
-
-// The task list of a plan.  A solve task exists per non-zero tile below the two sub-diagonals, an update task per super-tile and panel that couples one of
-// its tiles; the values that depend on which tasks exist and on the elimination order (ChainTask::w0, w1, w2, a, b) are computed here.  The block columns
-// are visited in the plan's order; the update tasks of panel k-1 are listed with block column k ("step k"), those of a stopping chain's last panel
-// (end-1) in a pseudo step of their own (k = end) behind it.
-// Priorities: a task's key is the one of the single-chain list with the step's TIME in place of its index - and never below the key of anything the task
-// waits for (the task that stored the counter value it waits for, the prep tasks of the chain step whose mailbox it reads): tasks are generated in an
-// order in which every task only waits for earlier ones, so one pass suffices and the sorted list is a topological order by construction (for one chain
-// no key is ever raised: the list is what it was).
-struct TaskListInfo { bool fits = true; int scratch_tiles = 0; };      // fits: the scratch sequences found counters; scratch_tiles: slots of the scratch tile pool
-static std::vector<ChainTask> BuildTaskList(int T, const ChainPlan& plan, const PlanSwitches& ps, TaskListInfo* info = nullptr) {
-  struct Item { double key; ChainTask t; };
-  std::vector<Item> items;
-  const uint8_t* nz = plan.map.empty() ? nullptr : plan.map.data();
-  auto has = [&](int i, int j) { return i < T && j < T && (!nz || nz[(size_t)i * T + j] != 0); };
-  const int whole_from = ps.whole_from ? *ps.whole_from : WholeFrom(T);
-  const int nch = plan.cr.n;
-  const double kNone = -1e30;
-  // one SEQUENCE of updates per super-tile and accumulation target: the tiles themselves (panels of the chain that owns the super-tile's columns) or the
-  // scratch array of another chain c (its panels; added to the tiles by one merge task when chain c is through).  Per sequence: ver / sub counter,
-  // parts listed, the value of ver once the tasks listed so far are done, the key of the last task, the tiles touched so far (scratch: what is not zero yet)
-  struct Seq { int cidx = 0, sidx = 0, listed = 0, post = 0, touched = 0; double key = -1e30; int slot[4] = {-1, -1, -1, -1}; };      // slot: the scratch tiles of a scratch sequence's four tiles
-  std::vector<Seq> own(kMaxSuper * kMaxSuper);
-  for (int I = 0; I < kMaxSuper; ++I) for (int J = 0; J < kMaxSuper; ++J) { own[I * kMaxSuper + J].cidx = cVer0 + I * kMaxSuper + J; own[I * kMaxSuper + J].sidx = cSub0 + I * kMaxSuper + J; }
-  std::vector<std::vector<std::pair<int, Seq>>> scratch(nch);      // per chain: (I * kMaxSuper + J, sequence)
-  int scratch_used = 0, slots_used = 0;
-  bool ok = true;
-  auto owner = [&](int J) { return plan.chain_of[std::min(2 * J, T - 1)]; };      // (a super-tile column that straddles two chains: its second block column starts a chain and never takes a panel)
-  auto seq_of = [&](int c, int I, int J) -> Seq& {
-    if (c == owner(J)) return own[I * kMaxSuper + J];
-    for (auto& e : scratch[c]) if (e.first == I * kMaxSuper + J) return e.second;
-    Seq q;
-    if (scratch_used + 2 > kScratchCounters) ok = false; else { q.cidx = cScratch0 + scratch_used; q.sidx = cScratch0 + scratch_used + 1; scratch_used += 2; }
-    scratch[c].push_back({I * kMaxSuper + J, q});
-    return scratch[c].back().second;
-  };
-  std::vector<int> solpost((size_t)nch * (T + 4), 0);              // per chain: value of the row's sol counter once the solves listed so far are done
-  std::vector<double> rowkey((size_t)nch * (T + 4), kNone);        // key of the last task that moves it
-  std::vector<double> tilekey((size_t)(T + 4) * (T + 4), kNone);  // key of the task that solves tile (row, column)
-  std::vector<double> stepkey(T + 4, kNone);                      // key of the last prep task chain step s takes its inputs from (a chain's first step: none)
-  auto tk_ = [&](int r, int c) -> double& { return tilekey[(size_t)r * (T + 4) + c]; };
-  auto sp = [&](int c, int row) -> int& { return solpost[(size_t)c * (T + 4) + row]; };
-  auto rk = [&](int c, int row) -> double& { return rowkey[(size_t)c * (T + 4) + row]; };
-  auto raised = [](double desired, std::initializer_list<double> deps) { double k = desired; for (double d : deps) k = std::max(k, d); return k; };
-  const bool two_panels = !nz && ps.two_panels;      // (two panels per task: dense systems)
-  const double slope = ps.slope ? *ps.slope : kUpdateSlope;
-  auto vp = [&](int I, int J) -> int& { return own[I * kMaxSuper + J].post; };
-  auto vk = [&](int I, int J) -> double& { return own[I * kMaxSuper + J].key; };
-  const std::vector<int>& time = plan.time;
-  const std::vector<int>& rho1 = plan.rho1;
-  auto own3 = [](int k, int r, int c) { return (r == k + 1 && c == k + 1) || (r == k + 2 && (c == k + 1 || c == k + 2)); };
-  // the update tasks of panel k - 1 at (pseudo) step k, which happens at time ts
-  auto list_updates = [&](int k, int ts, bool pseudo) {
-    const int pc = plan.chain_of[k - 1], fl = pc << 4;
-    for (int J = (k + 1) / 2; 2 * J < T; ++J)
-      for (int I = J; 2 * I < T; ++I) {
-        int tiles = 0;      // the tiles of the region below / right of (k+1,k+1) that are not one of the chain's / prep's three and that panel k-1 couples (the device's `valid`)
-        for (int q = 0; q < 4; ++q) {
-          const int bi = 2 * I + (q >> 1), bj = 2 * J + (q & 1);
-          if (bi < T && bj < T && bi >= bj && bj >= k + 1 && !own3(k, bi, bj) && has(bi, k - 1) && has(bj, k - 1)) tiles |= 1 << q;
-        }
-        if (!tiles) continue;
-        Seq& sq = seq_of(pc, I, J);
-        const bool into_scratch = pc != owner(J);
-        const int zsel = into_scratch ? pc : -1;
-        // what the task waits for: the sequence's previous update, column k-1 of the block rows it reads
-        double dep = sq.key;
-        for (int row : {2 * I, 2 * I + 1, 2 * J, 2 * J + 1})
-          if (row < T && row >= k + 1 && has(row, k - 1)) dep = std::max(dep, tk_(row, k - 1));
-        // the time at which the super-tile's columns become the front, in steps from now (2J - (k+1) for one chain)
-        const int tJ = std::min(time[2 * J], 2 * J + 1 < T ? time[2 * J + 1] : time[2 * J]);
-        const int Jt = std::max(tJ / 2, (ts + 1) / 2);
-        // in parts (UpdateTilesTask): four single tiles for the super-tiles PrepX(k+1) / PrepD(k+1) wait for, two block rows otherwise
-        const bool front = !pseudo && I == (k + 3) / 2 && (J == I - 1 || J == I);
-        const bool far = Jt - (ts + 1) / 2 >= whole_from;
-        // far at the next step too: steps k (odd) and k + 1 in one task, listed where step k + 1's update would be
-        const bool far_next = two_panels && k + 2 < T && J - (k + 2) / 2 >= whole_from;
-        if (far && (k & 1) == 0 && two_panels) continue;      // (the odd step before it took this one along: far at k => far at k - 1)
-        if (far && far_next && (k & 1) == 1) {
-          sq.listed += 1;
-          for (int row : {2 * I, 2 * I + 1, 2 * J, 2 * J + 1}) if (row < T && row >= k + 1) dep = std::max(dep, tk_(row, k));      // (column k as well)
-          const double key = raised((k + 1) + slope * (J - 0.5 * (k + 2)), {dep});
-          items.push_back({key, {kTaskUpdate, k, I, J | (kPartsTwoPanels << 12) | (sq.listed << 16), sq.post, k + 1, k, 0, sq.cidx, sq.sidx, -1, 0, {0, 0, 0, 0}}});
-          sq.post = k + 1; sq.key = key;
-          continue;
-        }      // (whole: the least operand traffic per flop; a far super-tile has steps of slack.  A lower
-               // threshold for the first steps, where the bulk is the bound: +-1 %, not kept)
-        const int parts = front ? 4 : (far ? 1 : 2);      // (four tiles also for the next ring of super-tiles, other slopes of the priority: measured, no gain)
-        sq.listed += parts;
-        const double dist = std::max(0.5 * tJ - 0.5 * (ts + 1), -0.5);
-        const double key = raised(front ? ts - 0.2 : ts + slope * dist, {dep});
-        const int post = std::max(rho1[k - 1], sq.post + 1);      // (k for one chain; several sequences and merges move a separator's counters)
-        const int fresh = into_scratch ? (tiles & ~sq.touched) : 0;
-        if (into_scratch) for (int q = 0; q < 4; ++q) if (((fresh >> q) & 1) && sq.slot[q] < 0) sq.slot[q] = slots_used++;
-        for (int q = 0; q < parts; ++q)
-          items.push_back({key, {kTaskUpdate, k, I, J | (q << 8) | (parts << 12) | (sq.listed << 16), sq.post, post, rho1[k - 1], fl, sq.cidx, sq.sidx, zsel, fresh,
-                                 {sq.slot[0], sq.slot[1], sq.slot[2], sq.slot[3]}}});
-        sq.post = post; sq.key = key; sq.touched |= tiles;
-      }
-  };
-  // chain c is through (its last panel's updates are listed): what it accumulated for other chains' super-tiles joins their own sequences
-  auto list_merges = [&](int c, int ts) {
-    for (auto& e : scratch[c]) {
-      const int I = e.first / kMaxSuper, J = e.first % kMaxSuper;
-      Seq& z = e.second;
-      Seq& o = own[e.first];
-      const double key = raised(ts + 0.05, {z.key, o.key});
-      const int post = o.post + 1;
-      items.push_back({key, {kTaskMerge, plan.cr.end[c], I, J, o.post, post, z.post, 0, o.cidx, z.cidx, c, z.touched, {z.slot[0], z.slot[1], z.slot[2], z.slot[3]}}});
-      o.post = post; o.key = key;
-    }
-  };
-  struct Event { int t, kind, k; };
-  std::vector<Event> events;
-  for (int k = 0; k + 1 < T; ++k) events.push_back({time[k], 0, k});
-  for (int c = 0; c + 1 < nch; ++c) events.push_back({time[plan.cr.end[c] - 1] + 1, 1, plan.cr.end[c]});
-  std::stable_sort(events.begin(), events.end(), [](const Event& a, const Event& b) { return a.t != b.t ? a.t < b.t : (a.kind != b.kind ? a.kind < b.kind : a.k < b.k); });
-  for (const Event& ev : events) {
-    const int k = ev.k;
-    if (ev.kind == 1) { list_updates(k, ev.t, true); list_merges(plan.chain_of[k - 1], ev.t); continue; }
-    const int c = plan.chain_of[k], e = plan.cr.end[c];
-    const bool first = k == plan.cr.begin[c];
-    const int fl = (first ? 1 : 0) | (c << 4), tk = time[k];
-    const int prev_done = first ? 0 : rho1[k - 1];
-    const double step_prev = first ? kNone : stepkey[k - 1];      // M_k and the solved tile (k,k-1): chain step k-1
-    if (k + 2 < e) {
-      // (their ver waits only exist behind a chain's first step: PrepTask's `prev`)
-      const int I2 = (k + 2) >> 1;
-      const int wx0 = !first ? vp(I2, k >> 1) : 0, wx1 = !first ? vp(I2, (k + 1) >> 1) : 0, wd1 = !first ? vp(I2, (k + 2) >> 1) : 0;
-      const double far_key = !first && has(k + 2, k - 1) ? tk_(k + 2, k - 1) : kNone;
-      const double kx = first ? tk - 0.4 : raised(tk - 0.4, {vk(I2, k >> 1), vk(I2, (k + 1) >> 1), rk(c, k + 2), rk(c, k + 1), step_prev, stepkey[k]});
-      const double kd = first ? tk - 0.4 : raised(tk - 0.4, {vk(I2, k >> 1), vk(I2, (k + 2) >> 1), far_key, step_prev});
-      // PrepX: a = what sol[k+1] must have reached (column k-1 solved - by PrepX(k-1)), w2 = the same for sol[k+2];  PrepD: a = "column k-1 of row k+2 is solved"
-      items.push_back({kx, {kTaskPrepX, k, first ? 0 : sp(c, k + 1), rho1[k], wx0, wx1, sp(c, k + 2), fl, 0, 0, -1, 0, {0, 0, 0, 0}}});
-      items.push_back({kd, {kTaskPrepD, k, prev_done, rho1[k], wx0, wd1, 0, fl, 0, 0, -1, 0, {0, 0, 0, 0}}});
-      tk_(k + 2, k) = kx; tk_(k + 1, k) = kx; rk(c, k + 2) = kx; rk(c, k + 1) = kx;
-      stepkey[k + 1] = std::max(std::max(kx, kd), stepkey[k]);
-      sp(c, k + 2) = rho1[k]; sp(c, k + 1) = rho1[k];
-    } else if (k + 1 < e) {      // the last step of a chain that stops: the chain itself stores the tile and moves the counter
-      tk_(k + 1, k) = stepkey[k]; rk(c, k + 1) = std::max(rk(c, k + 1), stepkey[k]);
-      sp(c, k + 1) = rho1[k];
-    }
-    for (int i = k + 3; i < T; ++i)
-      if (has(i, k)) {
-        const double key = raised(tk - 0.3, {vk(i >> 1, k >> 1), rk(c, i), step_prev});
-        items.push_back({key, {kTaskSolve, k, i, 0, vp(i >> 1, k >> 1), rho1[k], sp(c, i), fl, 0, 0, -1, 0, {0, 0, 0, 0}}});
-        sp(c, i) = rho1[k]; tk_(i, k) = key; rk(c, i) = key;
-      }
-    if (!first) list_updates(k, tk, false);
-  }
-  // the pair inverses / couplings of the paired back substitution (dense systems): off every critical path, behind the tasks of step 2g + 2
-  if (!nz)
-    for (int gp = 0; gp < BacksubNumPairs(T); ++gp)
-      for (int part = 0; part < (gp + 1 < BacksubNumPairs(T) ? 3 : 1); ++part) items.push_back({2 * gp + 2.2, {kTaskPairPrep, 2 * gp + 2, gp, part, 0, 0, 0, 0, 0, 0, -1, 0, {0, 0, 0, 0}}});
-  std::stable_sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return a.key < b.key; });
-  std::vector<ChainTask> list(items.size());
-  for (size_t i = 0; i < items.size(); ++i) list[i] = items[i].t;
-  if (info) { info->fits = ok; info->scratch_tiles = slots_used; }
-  return list;
-}
-
-// Replay of a list on the host (what tests/test_cholesky_task_order.py does for a set of shapes, here for the structure at hand):
-//   * every counter value a task waits for has been stored by a task EARLIER in the list (or by a chain whose inputs were), and every counter only
-//     grows - what makes the one launch free of deadlocks however few workgroups are resident;
-//   * every tile has received exactly the panels that couple it when a task consumes it, every operand is solved, every non-zero tile gets solved.
-static bool TaskListWaitsAreMet(int T, const ChainPlan& plan, const std::vector<ChainTask>& list) {
-  const uint8_t* nz = plan.map.empty() ? nullptr : plan.map.data();
-  auto has = [&](int i, int j) { return i < T && j < T && (!nz || nz[(size_t)i * T + j] != 0); };
-  const int nch = plan.cr.n;
-  std::vector<int> ctr(kNumCounters, 0);      // the device's counters
-  auto ver = [&](int I, int J) -> int& { return ctr[cVer0 + I * kMaxSuper + J]; };
-  auto sol = [&](int c, int row) -> int& { return ctr[cSol0 + c * kMaxSteps + row]; };
-  std::vector<char> px(T + 2, 0), pd(T + 2, 0), solved((size_t)T * T, 0);
-  struct Bits { uint64_t w[2] = {0, 0}; bool operator==(const Bits& o) const { return w[0] == o.w[0] && w[1] == o.w[1]; } bool none() const { return !w[0] && !w[1]; } };
-  std::vector<Bits> applied((size_t)T * T);
-  std::vector<std::vector<Bits>> zapplied(nch, std::vector<Bits>((size_t)T * T));      // per chain: what sits in its scratch tiles
-  std::vector<std::vector<int>> zslot(nch, std::vector<int>((size_t)T * T, -1));        // ... and where: a slot of the pool per (chain, tile), nobody else's
-  std::vector<char> slot_taken;
-  auto bit = [](Bits* b, int p) { b->w[p >> 6] |= 1ull << (p & 63); };
-  auto coupling = [&](int r, int c, int below) {      // the panels p < below that couple tile (r,c)
-    Bits b;
-    for (int p = 0; p < below && p < c; ++p) if (has(r, p) && has(c, p)) bit(&b, p);
-    return b;
-  };
-  auto own = [](int k, int r, int c) { return (r == k + 1 && c == k + 1) || (r == k + 2 && (c == k + 1 || c == k + 2)); };
-  // chain step s (the solve of tile (s+1,s), M_(s+1)) can run: its inputs come from k_potrf64 (a chain's first step) or from PrepX / PrepD(s-1), and step s-1 ran
-  auto can_run = [&](int s) {
-    const int c = plan.chain_of[s], b = plan.cr.begin[c];
-    if (s + 1 >= plan.cr.end[c]) return false;
-    for (int q = b + 1; q <= s; ++q) if (!px[q - 1] || !pd[q - 1]) return false;
-    return true;
-  };
-  auto chain_stores = [&](int row, int col) {      // tile (row,col) is the last solved tile of a chain that stops, and that step can run
-    const int c = plan.chain_of[col];
-    return plan.cr.end[c] < T && row == plan.cr.end[c] - 1 && col == row - 1 && can_run(col);
-  };
-  for (const ChainTask& t : list) {
-    const int k = t.k;
-    const bool first = (t.flags & 1) != 0;
-    const int fc = (t.flags >> 4) & 15;
-    if (t.type == kTaskPrepX || t.type == kTaskPrepD) {
-      const bool X = t.type == kTaskPrepX;
-      const int oc = X ? k + 1 : k + 2;
-      if (fc != plan.chain_of[k] || k + 2 >= plan.cr.end[fc] || first != (k == plan.cr.begin[fc])) return false;
-      if (!first) {
-        if (ver((k + 2) >> 1, k >> 1) < t.w0) return false;
-        if (ver((k + 2) >> 1, oc >> 1) < t.w1) return false;
-        const bool far = has(k + 2, k - 1);
-        if (sol(fc, k + 2) < (X ? t.w2 : (far ? t.a : 0))) return false;
-        if (X && sol(fc, k + 1) < t.a) return false;
-        if (!can_run(k - 1)) return false;      // M_k, the solved tile (k,k-1)
-        if (far && !solved[(size_t)(k + 2) * T + k - 1]) return false;
-        if (X && !solved[(size_t)(k + 1) * T + k - 1]) return false;
-      }
-      // the update tasks have applied every panel below k-1 (k-1 and k the task applies itself; a chain's first step: there are none at all)
-      if (!(applied[(size_t)(k + 2) * T + k] == coupling(k + 2, k, first ? k : k - 1))) return false;
-      if (!(applied[(size_t)(k + 2) * T + oc] == coupling(k + 2, oc, first ? k : k - 1))) return false;
-      if (X) {
-        if (!can_run(k)) return false;          // the solved tile (k+1,k)
-        if (sol(fc, k + 2) >= t.b || sol(fc, k + 1) >= t.b) return false;
-        sol(fc, k + 2) = t.b; sol(fc, k + 1) = t.b;
-        solved[(size_t)(k + 2) * T + k] = 1; solved[(size_t)(k + 1) * T + k] = 1;
-        px[k] = 1;
-      } else pd[k] = 1;
-    } else if (t.type == kTaskSolve) {
-      const int i = t.a;
-      if (fc != plan.chain_of[k] || i < k + 3 || i >= T || !has(i, k) || first != (k == plan.cr.begin[fc])) return false;
-      if (sol(fc, i) < t.w2 || ver(i >> 1, k >> 1) < t.w0) return false;
-      if (!first && (!can_run(k - 1) || (has(i, k - 1) && !solved[(size_t)i * T + k - 1]))) return false;
-      if (!(applied[(size_t)i * T + k] == coupling(i, k, first ? k : k - 1))) return false;
-      if (sol(fc, i) >= t.w1) return false;
-      sol(fc, i) = t.w1;
-      solved[(size_t)i * T + k] = 1;
-    } else if (t.type == kTaskMerge) {
-      const int I = t.a, J = t.b & 255, c = t.zsel;
-      if (c < 0 || c >= nch || t.cidx != cVer0 + I * kMaxSuper + J) return false;
-      if (ctr[t.cidx] < t.w0 || ctr[t.sidx] < t.w2) return false;
-      for (int q = 0; q < 4; ++q) {
-        const int r = 2 * I + (q >> 1), cc = 2 * J + (q & 1);
-        if (r >= T || cc >= T) { if ((t.mask >> q) & 1) return false; continue; }
-        Bits& z = zapplied[c][(size_t)r * T + cc];
-        if (((t.mask >> q) & 1) != (z.none() ? 0 : 1)) return false;
-        if (!z.none() && t.slot[q] != zslot[c][(size_t)r * T + cc]) return false;      // ... from the scratch tile they were accumulated in
-        Bits& a = applied[(size_t)r * T + cc];
-        if ((a.w[0] & z.w[0]) || (a.w[1] & z.w[1])) return false;
-        a.w[0] |= z.w[0]; a.w[1] |= z.w[1];
-        z = Bits();
-      }
-      if (ctr[t.cidx] >= t.w1) return false;
-      ctr[t.cidx] = t.w1;
-    } else if (t.type == kTaskUpdate) {
-      const int I = t.a, J = t.b & 255, part = (t.b >> 8) & 15, parts = (t.b >> 12) & 15, target = t.b >> 16;
-      const bool two = parts == kPartsTwoPanels;
-      if (fc != plan.chain_of[k - 1] || t.zsel >= nch || (t.zsel >= 0 && t.zsel != fc)) return false;
-      if (t.zsel < 0 && (t.cidx != cVer0 + I * kMaxSuper + J || t.sidx != cSub0 + I * kMaxSuper + J)) return false;
-      if (ctr[t.cidx] < t.w0) return false;
-      auto row_ok = [&](int row, bool distinct) {
-        if (!(distinct && row < T && row >= k + 1 && has(row, k - 1))) return true;
-        int have = sol(fc, row);
-        if (chain_stores(row, k - 1)) have = std::max(have, plan.cr.post[fc]);
-        return have >= (two ? t.w2 + 1 : t.w2);
-      };
-      const int bi = 2 * I + (parts == 2 ? part : part >> 1), bj0 = 2 * J + (parts == 2 ? 0 : part & 1), nb = parts == 2 ? 2 : 1;
-      bool ok;
-      if (parts == 1 || two) ok = row_ok(2 * I, true) && row_ok(2 * I + 1, true) && row_ok(2 * J, J != I) && row_ok(2 * J + 1, J != I);
-      else ok = row_ok(bi, true) && row_ok(bj0, bj0 != bi) && row_ok(bj0 + 1, nb == 2 && bj0 + 1 != bi);
-      if (!ok) return false;
-      // the tiles it updates (the device's `valid`), panel k-1 (and k: two)
-      for (int q = 0; q < 4; ++q) {
-        const int r = 2 * I + (q >> 1), c = 2 * J + (q & 1);
-        const bool mine = (parts == 1 || two) || (parts == 2 ? (q >> 1) == part : q == part);
-        for (int kk = k; kk <= (two ? k + 1 : k); ++kk) {
-          const bool valid = r < T && c < T && r >= c && c >= kk + 1 && !own(kk, r, c) && has(r, kk - 1) && has(c, kk - 1);
-          if (!mine || !valid) continue;
-          for (int row : {r, c}) if (!solved[(size_t)row * T + kk - 1] && !chain_stores(row, kk - 1) && !(two && kk == k + 1)) return false;
-          // a panel goes to the tile itself exactly when its chain owns the tile's block column
-          if ((t.zsel < 0) != (plan.chain_of[kk - 1] == plan.chain_of[c])) return false;
-          Bits& a = t.zsel < 0 ? applied[(size_t)r * T + c] : zapplied[t.zsel][(size_t)r * T + c];
-          if (t.zsel >= 0 && (((t.mask >> q) & 1) != (a.none() ? 1 : 0))) return false;      // taken as zero exactly when nothing has been accumulated yet
-          if (t.zsel >= 0) {
-            int& zs = zslot[t.zsel][(size_t)r * T + c];
-            if (t.slot[q] < 0) return false;
-            if (zs < 0) {
-              if ((int)slot_taken.size() <= t.slot[q]) slot_taken.resize(t.slot[q] + 1, 0);
-              if (slot_taken[t.slot[q]]) return false;
-              slot_taken[t.slot[q]] = 1; zs = t.slot[q];
-            } else if (zs != t.slot[q]) return false;
-          }
-          if (a.w[(kk - 1) >> 6] >> ((kk - 1) & 63) & 1) return false;
-          bit(&a, kk - 1);
-        }
-      }
-      if (++ctr[t.sidx] == target) {
-        if (ctr[t.cidx] >= t.w1) return false;
-        ctr[t.cidx] = t.w1;
-      }
-    }
-  }
-  // every non-zero tile below the diagonal is solved, every tile got the panels that couple it (those its own tasks apply aside), nothing is left in a scratch array
-  for (int c = 0; c + 1 < T; ++c)
-    for (int r = c + 1; r < T; ++r) {
-      if (!has(r, c)) continue;
-      const int e = plan.cr.end[plan.chain_of[c]];
-      if (r == c + 1 && r < e) { if (!solved[(size_t)r * T + c] && !(c + 2 >= e && can_run(c))) return false; }
-      else if (!solved[(size_t)r * T + c]) return false;
-    }
-  for (int c = 1; c < T; ++c)
-    for (int r = c; r < T; ++r) {
-      for (int ch = 0; ch < nch; ++ch) if (!zapplied[ch][(size_t)r * T + c].none()) return false;
-      if (!has(r, c)) continue;
-      Bits want = coupling(r, c, c);
-      auto clear = [&](int p) { if (p >= 0) want.w[p >> 6] &= ~(1ull << (p & 63)); };
-      clear(c - 1); if (r <= c + 1) clear(c - 2); if (r == c) clear(c - 3);
-      if (!(applied[(size_t)r * T + c] == want)) return false;
-    }
-  return true;
-}
-
-// plan + list for a tile map (null: dense); a plan of several chains whose list does not pass the replay falls back to ONE chain (the former behaviour)
-static ChainPlan PlanAndList(int T, const uint8_t* nz, const PlanSwitches& ps, bool print, std::vector<ChainTask>* list, bool* verified = nullptr,
-                             int* scratch_tiles = nullptr) {
-  ChainPlan plan = PlanChains(T, nz, ps);
-  TaskListInfo info;
-  *list = BuildTaskList(T, plan, ps, &info);
-  bool ok = info.fits && TaskListWaitsAreMet(T, plan, *list);
-  if (!ok && plan.cr.n > 1) {
-    fprintf(stderr, "ppsfm: the task list of %d chains over %d block columns did not pass its replay - one chain\n", plan.cr.n, T);
-    plan = PlanChains(T, nz, ps, 1);
-    *list = BuildTaskList(T, plan, ps, &info);
-    ok = TaskListWaitsAreMet(T, plan, *list);
-  }
-  if (print) {      // (debugging aid: the chains and the closed tile map of the structure at hand)
-    fprintf(stderr, "ppsfm plan: T %d, %d chains:", T, plan.cr.n);
-    for (int c = 0; c < plan.cr.n; ++c) fprintf(stderr, " [%d,%d)", plan.cr.begin[c], plan.cr.end[c]);
-    fprintf(stderr, "\n");
-    for (int r = 0; r < T && !plan.map.empty(); ++r) { for (int c = 0; c <= r; ++c) fputc(plan.map[(size_t)r * T + c] ? '#' : '.', stderr); fputc('\n', stderr); }
-  }
-  if (verified) *verified = ok;
-  if (scratch_tiles) *scratch_tiles = info.scratch_tiles;
-  return plan;
-}
-
 int CholeskyPlanSteps(int T, const uint8_t* nz, const Switches& sw, int* chains) {
   if (chains) *chains = 1;
-  if (!nz || T < 4 || T > kMaxSteps) return T;
+  if (!nz || !UseTasks(T)) return T;
   const ChainPlan plan = PlanChains(T, nz, sw.plan);
   if (chains) *chains = plan.cr.n;
-  int steps = 0;
-  for (int k = 0; k < T; ++k) steps = std::max(steps, plan.time[k] + 1);
-  return steps;
+  return plan.Steps();
 }
-
 
 static std::recursive_mutex g_setup_mutex;
 // Plans are kept process-wide, keyed on the tile map: the mapper builds a new BundleAdjuster per global bundle adjustment (src/sfm/incremental_mapper.cc:893-936)
@@ -2224,13 +1719,11 @@ static const CachedPlan& PlanCached(int T, const uint8_t* nz, const Switches& sw
 
 int CholeskyChainSteps(int T, const uint8_t* nz, const Switches& sw, int* chains) {
   if (chains) *chains = 1;
-  if (!nz || T < 4 || T > kMaxSteps) return T;
+  if (!nz || !UseTasks(T)) return T;
   std::lock_guard<std::recursive_mutex> lock(g_setup_mutex);
   const CachedPlan& cp = PlanCached(T, nz, sw);      // (plan + list + replay, once per tile map: pp_ba_create's winner is what EnsureTaskList asks for next)
   if (chains) *chains = cp.plan.cr.n;
-  int steps = 0;
-  for (int k = 0; k < T; ++k) steps = std::max(steps, cp.plan.time[k] + 1);
-  return steps;
+  return cp.plan.Steps();
 }
 
 // The task list of the one-launch path for T block columns and the bound tile map: PrepX / PrepD / solve / update tasks sorted by priority (see above);
@@ -2475,48 +1968,21 @@ const double* CholeskyFactor(const CholeskyState* st, const double** diag_invers
 
 using namespace ppsfm;
 
-extern "C" int pp_cholesky_task_list(int32_t block_columns, int32_t* tasks, int64_t capacity, int64_t* count) try {
-  PP_REQUIRE(block_columns >= 4 && block_columns <= kMaxSteps && count && (tasks || capacity == 0), "pp_cholesky_task_list: bad argument");
-  std::vector<ChainTask> list;
+// The three probes of the planner (tests, tools): the task list of a tile map (null: dense, through PlanAndList as a solve builds it; else closed under
+// fill-in first) of at most max_chains chains, the first `words` words of every task; the plan and the replay's verdict where asked for.
+static void ProbeTaskList(int T, const uint8_t* tile_nz, int max_chains, int words, uint8_t* map_out, int32_t* tasks, int64_t capacity, int64_t* count,
+                          int32_t* chains_out = nullptr, int32_t* time_out = nullptr, int32_t* rho1_out = nullptr, int32_t* verified = nullptr) {
   const Switches sw = ReadSwitches();
-  (void)PlanAndList(block_columns, nullptr, sw.plan, sw.chol_plan_print, &list);
-  *count = (int64_t)list.size();
-  for (int64_t i = 0; i < (int64_t)list.size() && i < capacity; ++i) {
-    tasks[4 * i] = list[i].type; tasks[4 * i + 1] = list[i].k; tasks[4 * i + 2] = list[i].a; tasks[4 * i + 3] = list[i].b;
-  }
-  return PP_OK;
-} PP_API_CATCH("pp_cholesky_task_list")
-
-extern "C" int pp_cholesky_task_list_sparse(int32_t block_columns, const uint8_t* tile_nz, uint8_t* map_out, int32_t* tasks, int64_t capacity, int64_t* count) try {
-  PP_REQUIRE(block_columns >= 4 && block_columns <= kMaxSteps && count && tile_nz && (tasks || capacity == 0), "pp_cholesky_task_list_sparse: bad argument");
-  const int T = block_columns;
-  std::vector<uint8_t> closed(tile_nz, tile_nz + (size_t)T * T);
-  (void)SymbolicTileFill(T, closed.data());
   std::vector<ChainTask> list;
-  const PlanSwitches ps = ReadSwitches().plan;
-  const ChainPlan plan = PlanChains(T, closed.data(), ps, 1);      // ONE chain (pp_cholesky_task_plan: as many as the structure has)
-  list = BuildTaskList(T, plan, ps);
-  if (map_out) std::memcpy(map_out, plan.map.data(), plan.map.size());
-  *count = (int64_t)list.size();
-  for (int64_t i = 0; i < (int64_t)list.size() && i < capacity; ++i) {
-    const ChainTask& t = list[i];
-    const int32_t row[7] = {t.type, t.k, t.a, t.b, t.w0, t.w1, t.w2};
-    std::memcpy(tasks + 7 * i, row, sizeof(row));
-  }
-  return PP_OK;
-} PP_API_CATCH("pp_cholesky_task_list_sparse")
-
-extern "C" int pp_cholesky_task_plan(int32_t block_columns, const uint8_t* tile_nz, int32_t max_chains, uint8_t* map_out, int32_t* tasks, int64_t capacity,
-                                     int64_t* count, int32_t* chains_out, int32_t* time_out, int32_t* rho1_out, int32_t* verified) try {
-  PP_REQUIRE(block_columns >= 4 && block_columns <= kMaxSteps && count && tile_nz && (tasks || capacity == 0), "pp_cholesky_task_plan: bad argument");
-  const int T = block_columns;
-  std::vector<uint8_t> closed(tile_nz, tile_nz + (size_t)T * T);
-  (void)SymbolicTileFill(T, closed.data());
-  const PlanSwitches ps = ReadSwitches().plan;
-  const ChainPlan plan = PlanChains(T, closed.data(), ps, max_chains > 0 ? max_chains : kMaxChains);
-  TaskListInfo info;
-  const std::vector<ChainTask> list = BuildTaskList(T, plan, ps, &info);
-  if (verified) *verified = (info.fits && TaskListWaitsAreMet(T, plan, list)) ? 1 : 0;
+  ChainPlan plan;
+  if (tile_nz) {
+    std::vector<uint8_t> closed(tile_nz, tile_nz + (size_t)T * T);
+    (void)CloseTileMap(T, closed.data());
+    plan = PlanChains(T, closed.data(), sw.plan, max_chains);
+    TaskListInfo info;
+    list = BuildTaskList(T, plan, sw.plan, &info);
+    if (verified) *verified = (info.fits && TaskListWaitsAreMet(T, plan, list)) ? 1 : 0;
+  } else plan = PlanAndList(T, nullptr, sw.plan, sw.chol_plan_print, &list);
   if (map_out) std::memcpy(map_out, plan.map.data(), plan.map.size());
   if (chains_out) {
     chains_out[0] = plan.cr.n;
@@ -2524,7 +1990,25 @@ extern "C" int pp_cholesky_task_plan(int32_t block_columns, const uint8_t* tile_
   }
   for (int k = 0; k < T; ++k) { if (time_out) time_out[k] = plan.time[k]; if (rho1_out) rho1_out[k] = plan.rho1[k]; }
   *count = (int64_t)list.size();
-  for (int64_t i = 0; i < (int64_t)list.size() && i < capacity; ++i) std::memcpy(tasks + 16 * i, &list[i], 16 * sizeof(int32_t));
+  for (int64_t i = 0; i < (int64_t)list.size() && i < capacity; ++i) std::memcpy(tasks + words * i, &list[i], words * sizeof(int32_t));      // (type, k, a, b, w0, w1, w2, ...: ChainTask's order)
+}
+
+extern "C" int pp_cholesky_task_list(int32_t block_columns, int32_t* tasks, int64_t capacity, int64_t* count) try {
+  PP_REQUIRE(block_columns >= 4 && block_columns <= kMaxSteps && count && (tasks || capacity == 0), "pp_cholesky_task_list: bad argument");
+  ProbeTaskList(block_columns, nullptr, kMaxChains, 4, nullptr, tasks, capacity, count);
+  return PP_OK;
+} PP_API_CATCH("pp_cholesky_task_list")
+
+extern "C" int pp_cholesky_task_list_sparse(int32_t block_columns, const uint8_t* tile_nz, uint8_t* map_out, int32_t* tasks, int64_t capacity, int64_t* count) try {
+  PP_REQUIRE(block_columns >= 4 && block_columns <= kMaxSteps && count && tile_nz && (tasks || capacity == 0), "pp_cholesky_task_list_sparse: bad argument");
+  ProbeTaskList(block_columns, tile_nz, 1, 7, map_out, tasks, capacity, count);      // ONE chain (pp_cholesky_task_plan: as many as the structure has)
+  return PP_OK;
+} PP_API_CATCH("pp_cholesky_task_list_sparse")
+
+extern "C" int pp_cholesky_task_plan(int32_t block_columns, const uint8_t* tile_nz, int32_t max_chains, uint8_t* map_out, int32_t* tasks, int64_t capacity,
+                                     int64_t* count, int32_t* chains_out, int32_t* time_out, int32_t* rho1_out, int32_t* verified) try {
+  PP_REQUIRE(block_columns >= 4 && block_columns <= kMaxSteps && count && tile_nz && (tasks || capacity == 0), "pp_cholesky_task_plan: bad argument");
+  ProbeTaskList(block_columns, tile_nz, max_chains > 0 ? max_chains : kMaxChains, 16, map_out, tasks, capacity, count, chains_out, time_out, rho1_out, verified);
   return PP_OK;
 } PP_API_CATCH("pp_cholesky_task_plan")
 

@@ -11,15 +11,15 @@
 //   PPSFM_CHOL_GRAPH            atoi, 0 = off                on               CholeskyCreate (graph capture)               fallback
 //   PPSFM_CHOL_SMALL            atoi, 0 = off                on               ChoosePath (one-workgroup <= 128 cols)       fallback
 //   PPSFM_CHOL_SPARSE           atoi, 0 = off                on               pp_dense_cholesky_solve (skip zero tiles)     A/B
-//   PPSFM_CHOL_CHAINS           atoi, clamped to [1, 16]     by structure     PlanChains (max chains)                      A/B
-//   PPSFM_CHOL_WHOLE_FROM       atoi                         WholeFrom(T)     BuildTaskList                                A/B
-//   PPSFM_CHOL_TWO_PANELS       atoi, 0 = off                on               BuildTaskList (two panels per dense task)    A/B
-//   PPSFM_CHOL_SLOPE            atof                         kUpdateSlope     BuildTaskList (deferral of far updates)      A/B
+//   PPSFM_CHOL_CHAINS           atoi, clamped to [1, 16]     by structure     PlanChains (chol_plan.hpp: max chains)       A/B
+//   PPSFM_CHOL_WHOLE_FROM       atoi                         WholeFrom(T)     TaskListBuilder (chol_plan.hpp)              A/B
+//   PPSFM_CHOL_TWO_PANELS       atoi, 0 = off                on               TaskListBuilder (two panels per dense task)  A/B
+//   PPSFM_CHOL_SLOPE            atof                         kUpdateSlope     TaskListBuilder (deferral of far updates)    A/B
 //   PPSFM_CHOL_TEST_DROP_TASKS  atoi, non-0 = on             off              EnqueueCholesky (half the list: a timeout)    A/B
 //   PPSFM_BACKSUB_PAIRS         atoi, 0 = off                on               LaunchBacksub (paired dense back subst.)     A/B
 //   PPSFM_CHOL_DEBUG            set = on                     off              EnsureTaskList (the chains of a list)         debug
 //   PPSFM_CHOL_DEBUG_SLOW       set = on                     off              pp_dense_cholesky_solve (solves > 5 ms)       debug
-//   PPSFM_CHOL_PLAN_PRINT       set = on                     off              PlanAndList (chains, closed tile map)         debug
+//   PPSFM_CHOL_PLAN_PRINT       set = on                     off              PrintPlan (chains, closed tile map)           debug
 //   PPSFM_BA_LINEAR_SOLVER      letter i|I iterative,        descriptor's     WillIterate (pp_ba_create, SetupOf)           A/B
 //                               d|D direct
 //   PPSFM_BA_SPARSE             atoi, 0 = off                on               pp_ba_create, SetupOf (block-sparse system)   A/B

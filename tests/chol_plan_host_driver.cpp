@@ -1,0 +1,74 @@
+// Host driver of csrc/chol_plan.hpp (tests/test_chol_plan_host.py): the Cholesky task planner without a device and without the library.
+// g++ -std=c++17 -Wall -Wextra -fsanitize=address,undefined compiles it; it includes the planner header and nothing else of the project.
+// stdin: one structure per line, "<name> <T> <max_chains> dense" (no tile map: the list a dense solve builds) or "<name> <T> <max_chains> <T*T x 0|1>"
+// (a lower-triangular tile map, row-major; max_chains 0: as many as the structure has) - what pp_cholesky_task_list / pp_cholesky_task_plan take.
+// stdout: the counter layout once, then per structure the chains, time, rho1, the closed map, the replay's verdict, the 16 words of every task and
+// the per-column lists of the block-sparse per-column launches.
+#include <cstdio>
+#include <iostream>
+#include <sstream>
+#include <string>
+
+#include "../privacy_preserving_sfm_amd/csrc/chol_plan.hpp"
+
+using namespace ppsfm;
+
+template <typename V>
+static void PrintInts(const char* what, const V& v) {
+  std::printf("%s", what);
+  for (auto x : v) std::printf(" %d", (int)x);
+  std::printf("\n");
+}
+
+int main() {
+  static_assert(sizeof(ChainTask) == 16 * sizeof(int32_t), "a task is 16 words");
+  std::printf("layout cSol0 %d cVer0 %d cSub0 %d cScratch0 %d kMaxSteps %d kMaxSuper %d kMaxChains %d kScratchCounters %d kPartsTwoPanels %d\n", (int)cSol0, (int)cVer0,
+              (int)cSub0, (int)cScratch0, kMaxSteps, kMaxSuper, kMaxChains, kScratchCounters, kPartsTwoPanels);
+  // the packed fields: what the pack functions put in, the accessors give back
+  const ChainTask packed{kTaskUpdate, 0, 0, PackUpdate(64, 3, kPartsTwoPanels, 1234), 0, 0, 0, PackFlags(true, 15), 0, 0, 0, 0, {0, 0, 0, 0}};
+  std::printf("packed %d %d %d %d %d %d b %d flags %d\n", TaskSuperColumn(packed.b), TaskPart(packed.b), TaskParts(packed.b), TaskTarget(packed.b), TaskFirstOfChain(packed.flags) ? 1 : 0, TaskChain(packed.flags),
+              (int)packed.b, (int)packed.flags);
+  const PlanSwitches ps;
+  std::string line;
+  while (std::getline(std::cin, line)) {
+    std::istringstream in(line);
+    std::string name, bits;
+    int T = 0, max_chains = 0;
+    if (!(in >> name >> T >> max_chains >> bits)) continue;
+    if (T < 4 || T > kMaxSteps || (bits != "dense" && bits.size() != (size_t)T * T)) { std::fprintf(stderr, "bad structure %s\n", name.c_str()); return 2; }
+    std::vector<ChainTask> list;
+    ChainPlan plan;
+    bool verified = false;
+    std::vector<uint8_t> closed;
+    if (bits == "dense") {
+      plan = PlanAndList(T, nullptr, ps, false, &list, &verified);
+    } else {
+      closed.resize(bits.size());
+      for (size_t i = 0; i < bits.size(); ++i) closed[i] = bits[i] == '1';
+      (void)CloseTileMap(T, closed.data());
+      plan = PlanChains(T, closed.data(), ps, max_chains > 0 ? max_chains : kMaxChains);
+      TaskListInfo info;
+      list = BuildTaskList(T, plan, ps, &info);
+      verified = info.fits && TaskListWaitsAreMet(T, plan, list);
+    }
+    std::printf("struct %s %d\n", name.c_str(), T);
+    std::printf("chains %d", plan.cr.n);
+    for (int c = 0; c < plan.cr.n; ++c) std::printf(" %d %d %d", plan.cr.begin[c], plan.cr.end[c], plan.cr.post[c]);
+    std::printf("\nsteps %d\n", plan.Steps());
+    PrintInts("time", plan.time);
+    PrintInts("rho1", plan.rho1);
+    std::printf("map ");
+    for (uint8_t m : plan.map) std::putchar(m ? '1' : '0');
+    std::printf("%s\nverified %d\ntasks %zu\n", plan.map.empty() ? "dense" : "", verified ? 1 : 0, list.size());
+    for (const ChainTask& t : list)
+      std::printf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d\n", t.type, t.k, t.a, t.b, t.w0, t.w1, t.w2, t.flags, t.cidx, t.sidx, t.zsel, t.mask, t.slot[0], t.slot[1],
+                  t.slot[2], t.slot[3]);
+    if (!closed.empty()) {      // (the map a bind hands the per-column launches: the caller's, closed under fill-in)
+      const SparseColumnLists sl = BuildSparseColumnLists(T, closed.data());
+      std::printf("sparse %d %d", sl.base_rows, sl.base_sups);
+      PrintInts("", sl.lists);
+    }
+    std::printf("end\n");
+  }
+  return 0;
+}

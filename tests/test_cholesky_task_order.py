@@ -1,4 +1,4 @@
-"""The task list of the one-launch Cholesky factorisation (csrc/cholesky.hip: k_cholesky_tasks) must be a topological order of
+"""The task list of the one-launch Cholesky factorisation (csrc/cholesky.hip: k_cholesky_tasks; built by csrc/chol_plan.hpp) must be a topological order of
 its own dependency graph: a workgroup may only wait for the chain workgroup (resident from the first cycle) and for tasks
 dispatched BEFORE it - workgroups are dispatched in list order, so then the lowest unfinished task always has its inputs
 complete and the grid cannot deadlock however few workgroups fit the chip.  This replays the list on the host (no GPU) with the
@@ -22,6 +22,10 @@ def _task_list(T):
     buf = np.zeros(4 * n.value, dtype=np.int32)
     assert L.pp_cholesky_task_list(T, buf.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n)) == 0
     return buf.reshape(-1, 4)
+
+
+def _unpack_update(b):      # ChainTask::b of an update / merge task = J | part << 8 | parts << 12 | target << 16 (csrc/chol_plan.hpp) -> (J, part, parts, target)
+    return b & 255, (b >> 8) & 15, (b >> 12) & 15, b >> 16
 
 
 def _own(k, r, c):      # the three tiles the chain / the prep tasks of step k update themselves
@@ -83,7 +87,7 @@ def test_task_list_is_a_topological_order_and_complete(T):
                 need_sol(lo + 2, lo + 2, what); need_sol(lo + 3, lo + 2, what)      # tiles (lo+2, {lo, hi}), (lo+3, {lo, hi})
         else:
             assert typ == UPDATE and k >= 1
-            I, J, part, parts, target = a, b & 255, (b >> 8) & 15, (b >> 12) & 15, b >> 16
+            I, (J, part, parts, target) = a, _unpack_update(b)
             need_ver(I, J, k - 1, what)
             npan = parts - 6 if parts > 6 else 1   # np > 1: the whole super-tile by the panels k-1 .. k+np-2 (far from the front)
             assert npan in (1, 2, 3, 4)
@@ -215,7 +219,7 @@ def test_sparse_task_list_waits_only_for_earlier_tasks_and_covers_the_structure(
             solved.add((i, k))
         else:
             assert typ == UPDATE and k >= 1
-            I, J, part, parts, target = a, b & 255, (b >> 8) & 15, (b >> 12) & 15, b >> 16
+            I, (J, part, parts, target) = a, _unpack_update(b)
             assert parts in (1, 2, 4), what + ": block-sparse lists hold single-panel updates"
             assert ver.get((I, J), 0) >= w0, what
             if parts == 1:
@@ -298,7 +302,7 @@ def _two_level(T, leaf, w, sep1, top):      # [leaf leaf sep1] [leaf leaf sep1] 
 
 
 MERGE = 6
-C_SOL0, MAX_STEPS, MAX_SUPER = 8, 128, 65
+C_SOL0, MAX_STEPS, MAX_SUPER = 8, 128, 65      # the counter layout of csrc/chol_plan.hpp, spelled out (test_chol_plan_host.py holds the header to it)
 C_VER0 = C_SOL0 + 16 * MAX_STEPS
 C_SUB0 = C_VER0 + MAX_SUPER * MAX_SUPER
 
@@ -340,8 +344,7 @@ def _replay_plan(T, tasks, has, ranges, time, rho1):
     for typ, k, a, b, w0, w1, w2, flags, cidx, sidx, zsel, mask, s0, s1, s2, s3 in tasks:
         slots = (s0, s1, s2, s3)
         what = "task (type %d, k %d, a %d, b 0x%x)" % (typ, k, a, b)
-        first = bool(flags & 1)
-        fc = (flags >> 4) & 15
+        first, fc = bool(flags & 1), (flags >> 4) & 15      # flags = first | chain << 4
         if typ in (PREP_X, PREP_D):
             assert fc == chain_of[k] and first == (k == begin(k)) and k + 2 < end(k), what
             X = typ == PREP_X
@@ -383,7 +386,7 @@ def _replay_plan(T, tasks, has, ranges, time, rho1):
             post(C_SOL0 + fc * MAX_STEPS + i, w1, what)
             solved.add((i, k))
         elif typ == MERGE:
-            I, J, c = a, b & 255, zsel
+            I, J, c = a, _unpack_update(b)[0], zsel
             assert 0 <= c < len(ranges) and cidx == C_VER0 + I * MAX_SUPER + J, what
             assert ctr.get(cidx, 0) >= w0 and ctr.get(sidx, 0) >= w2, what
             for q in range(4):
@@ -396,7 +399,7 @@ def _replay_plan(T, tasks, has, ranges, time, rho1):
             post(cidx, w1, what)
         else:
             assert typ == UPDATE and k >= 1
-            I, J, part, parts, target = a, b & 255, (b >> 8) & 15, (b >> 12) & 15, b >> 16
+            I, (J, part, parts, target) = a, _unpack_update(b)
             assert parts in (1, 2, 4), what + ": block-sparse lists hold single-panel updates"
             assert fc == chain_of[k - 1] and zsel in (-1, fc) and w2 == rho1[k - 1], what
             if zsel < 0:
