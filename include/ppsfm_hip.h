@@ -247,6 +247,11 @@ int pp_ba_get_trace(pp_ba_handle h, double* trace, int32_t capacity_rows, int32_
  * internal order is a nested dissection whose independent parts are factorised side by side), info[7] = block-column steps on its longest
  * dependency path (info[0]'s block-column count for one chain). */
 int pp_ba_get_structure(pp_ba_handle h, int32_t* info /* 8 */);
+/* Where the handle put the variable intrinsics: info[0] = their columns in the reduced system over all referenced cameras, info[1] = n_v > 0 when every
+ * image owns a camera with the same even number n_v of variable parameters and those columns sit beside its pose columns (6 + n_v columns per image, no
+ * tail), 0 when they follow the 6 C pose columns, info[2] = n_v when such an image's 6 + n_v columns are assembled as one block by the pose gather with
+ * wider rows (n_v = 2, 4, 6, 8), 0 when the general block pairs assemble them, info[3] = row width of the compact camera Jacobians (the widest camera). */
+int pp_ba_get_intrinsics_layout(pp_ba_handle h, int32_t* info /* 4 */);
 /* The image order pp_ba_create would give this problem's reduced camera system, computed on the host alone (no device is touched: what the ordering tests
  * run without a GPU).  Only the structure fields of the descriptor are read (counts, obs_pose, obs_point, pose_camera, camera_model, the const masks,
  * linear_solver, ordering).  old_of_new (num_poses ints, may be NULL): the caller's index of the image at every internal position.  info[0] = 1 if the

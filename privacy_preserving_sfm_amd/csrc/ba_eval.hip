@@ -426,6 +426,7 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   const int nv_private = iterative ? 0 : ppsfm::PrivateIntrinsicsColumns(d, sw.ba_intr_layout);
   const int W6 = 6 + nv_private;
   h->spos_identity = nv_private == 0;
+  h->intr_private_nv = nv_private;
   // (PPSFM_BA_INTR_WIDE=0: the general block-pair lists (ba_intr.hip) also for per-image intrinsics - tests / comparisons)
   h->intr_wide_nv = (nv_private >= 2 && nv_private <= 8 && sw.ba_intr_wide) ? nv_private : 0;
   h->spos_host.resize((size_t)h->n_red);

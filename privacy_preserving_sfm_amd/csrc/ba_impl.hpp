@@ -110,6 +110,7 @@ struct pp_ba_impl {
   int jcam_stride = 2;              // row width of the compact camera Jacobians (the widest camera's variable parameters, even)
   bool jcam_compact = false;        // layout the last evaluation with camera Jacobians left in Jcam (EvalArgs::cam_col)
   int intr_wide_nv = 0;             // > 0: every image carries n_v variable intrinsics beside its pose columns and its (6 + n_v)-wide blocks come from the pose gather with wider rows (k_schur_wide_*)
+  int intr_private_nv = 0;          // n_v of PrivateIntrinsicsColumns: the variable intrinsics every image carries beside its pose columns (0: they follow the pose columns); pp_ba_get_intrinsics_layout
   double* step_s = nullptr;
   double* attach_slot = nullptr;    // four doubles of the collective attach check (pp_ba_set_allreduce / pp_ba_set_communicator)
   bool structure_from_covisibility = false;      // order and tile map come from pp_ba_problem_desc::covisibility (a group's union): the same on every rank that was given it

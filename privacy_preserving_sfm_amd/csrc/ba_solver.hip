@@ -1855,6 +1855,12 @@ int pp_ba_get_structure(pp_ba_handle h, int32_t* info) try {
   return PP_OK;
 } PP_API_CATCH("pp_ba_get_structure")
 
+int pp_ba_get_intrinsics_layout(pp_ba_handle h, int32_t* info) try {
+  PP_REQUIRE(h && info, "pp_ba_get_intrinsics_layout: null argument");
+  info[0] = h->NI; info[1] = h->intr_private_nv; info[2] = h->intr_wide_nv; info[3] = h->jcam_stride;
+  return PP_OK;
+} PP_API_CATCH("pp_ba_get_intrinsics_layout")
+
 int pp_ba_get_trace(pp_ba_handle h, double* trace, int32_t capacity_rows, int32_t* num_rows) try {
   PP_REQUIRE(h && num_rows, "pp_ba_get_trace: null argument");
   const int rows = (int)(h->trace.size() / 7);

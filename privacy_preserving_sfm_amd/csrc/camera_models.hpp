@@ -8,8 +8,11 @@
 //                         point Jacobians cost two width-2 duals instead of the reference's
 //                         width-(10+N) Ceres jets
 //   T = Dual<2+N>         additionally d/d(intrinsics), only when intrinsics are refined
-// The model id is wave-uniform in practice (observations are grouped by image), so the switch
-// does not diverge.
+// The model id is per observation (its image's camera).  It is uniform over a wavefront - and the
+// switch does not diverge - only where the observations are sorted by image and the cameras of a
+// wavefront's images share a model; in point order, or with cameras of several models, the lanes of
+// a wavefront take different arms with different Dual widths one after the other: slower, and still
+// correct (every lane reads its own model id, intrinsics row and Jacobian columns).
 #pragma once
 #include <hip/hip_runtime.h>
 

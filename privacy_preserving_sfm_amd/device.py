@@ -104,11 +104,16 @@ class BAProblem:
             self.set_parameters(scene["poses"], scene["points"], scene["intr"])
 
     def structure(self):
-        """pp_ba_get_structure: dict(tiles, nnz_natural, nnz_used, reordered, block_sparse, iterative, chains, chain_steps) of the reduced camera system"""
+        """pp_ba_get_structure: dict(tiles, nnz_natural, nnz_used, reordered, block_sparse, iterative, chains, chain_steps) of the reduced camera system, and
+        pp_ba_get_intrinsics_layout: intrinsics_columns, private_intrinsics (n_v beside every image's pose columns, 0: behind all pose columns),
+        wide_intrinsics (n_v of the wide-row assembly, 0: the general block pairs), jcam_stride"""
         info = np.zeros(8, dtype=np.int32)
         check(_capi.lib().pp_ba_get_structure(self._h, ptr(info, _capi.c_ip)))
+        lay = np.zeros(4, dtype=np.int32)
+        check(_capi.lib().pp_ba_get_intrinsics_layout(self._h, ptr(lay, _capi.c_ip)))
         return dict(tiles=int(info[0]), nnz_natural=int(info[1]), nnz_used=int(info[2]), reordered=bool(info[3]), block_sparse=bool(info[4]),
-                    iterative=bool(info[5]), chains=int(info[6]), chain_steps=int(info[7]))
+                    iterative=bool(info[5]), chains=int(info[6]), chain_steps=int(info[7]), intrinsics_columns=int(lay[0]), private_intrinsics=int(lay[1]),
+                    wide_intrinsics=int(lay[2]), jcam_stride=int(lay[3]))
 
     def create_profile(self):
         """pp_ba_get_create_profile: host ms of the pp_ba_create behind this handle - dict(ordering, pair_lists, structure, upload, task_plan, total)"""

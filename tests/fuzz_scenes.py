@@ -5,9 +5,12 @@ import numpy as np
 from privacy_preserving_sfm_amd import synthetic
 
 
-def reduced_system_case(seed, case, camera_num_params):
+def reduced_system_case(seed, case, camera_num_params, mixed=False):
     """small scenes: 8-70 images, tracks 3-6, dense / window / loop / clusters, shuffled ids, constant poses / points / tvec components, three camera
-    models, fixed / shared / per-image intrinsics with a random constant mask, three losses, a random trust-region radius -> (scene, meta) or (None, why)"""
+    models, fixed / shared / per-image intrinsics with a random constant mask, three losses, a random trust-region radius -> (scene, meta) or (None, why).
+    mixed=True: the same scene with its cameras re-labelled to models drawn per camera from all 11 (tests/mixed_models.py) and, unless the layout is "fixed",
+    a random constant mask per camera (meta["masks"]; never everything constant on every camera) - drawn from a generator of their own, so case (s, k)
+    without `mixed` is what it always was."""
     rng = np.random.default_rng([int(seed), int(case)])
     C = int(rng.integers(8, 70)); track = int(rng.integers(3, 7)); P = int(rng.integers(8, 40)) * C // 2
     model = int(rng.choice([1, 2, 4])); layout = str(rng.choice(["fixed", "shared", "per_image"]))
@@ -35,6 +38,17 @@ def reduced_system_case(seed, case, camera_num_params):
     tm = np.ascontiguousarray(sc["tvec_const_mask"]).copy(); tm[rng.random(len(tm)) < 0.05] = int(rng.integers(1, 8)); sc["tvec_const_mask"] = tm
     sc["loss_type"] = int(rng.choice([0, 1, 2])); sc["loss_scale"] = 0.05
     radius = float(10.0 ** rng.uniform(0, 4))
+    if mixed:
+        import mixed_models
+        rng_m = np.random.default_rng([int(seed), int(case), 0x4D58])
+        sc = mixed_models.mix_camera_models(sc, [int(v) for v in rng_m.integers(0, 11, nintr)])
+        masks = np.full(nintr, 0xFFFF, dtype=np.uint16)
+        if layout != "fixed":
+            while True:
+                masks = np.array([(0xFFFF << camera_num_params(int(mk))) & 0xFFFF | int(rng_m.integers(0, 1 << camera_num_params(int(mk)))) for mk in sc["camera_model"]], dtype=np.uint16)
+                if (masks != 0xFFFF).any(): break
+        sc["camera_const_mask"] = masks
+        return sc, dict(C=C, shape=shape, shuffled=shuffled, model=[int(v) for v in sc["camera_model"]], layout=layout, nintr=nintr, masks=[int(v) for v in masks], radius=radius)
     return sc, dict(C=C, shape=shape, shuffled=shuffled, model=model, layout=layout, nintr=nintr, npar=npar, mask=mask, radius=radius)
 
 
@@ -50,13 +64,17 @@ def oracle_columns(sc, meta, n_device):
     ni = n_device - 6 * C
     icols, at = [], 6 * C
     if meta["layout"] != "fixed":
-        nv = sum(1 for j in range(meta["npar"]) if not (meta["mask"] >> j) & 1)
+        if "masks" in meta:      # (a mixed case: a width per camera)
+            from privacy_preserving_sfm_amd import synthetic as _syn
+            nvs = [sum(1 for j in range(_syn.NUM_PARAMS[m]) if not (c >> j) & 1) for m, c in zip(meta["model"], meta["masks"])]
+        else:
+            nvs = [sum(1 for j in range(meta["npar"]) if not (meta["mask"] >> j) & 1)] * meta["nintr"]
         seen = np.zeros(meta["nintr"], dtype=bool); seen[np.asarray(sc["pose_camera"])[np.asarray(sc["obs_pose"])]] = True
         used = set(int(x) for x in sc["pose_camera"])
         for k in range(meta["nintr"]):
             if k in used:
-                if seen[k]: icols += list(range(at, at + nv))
-                at += nv
+                if seen[k]: icols += list(range(at, at + nvs[k]))
+                at += nvs[k]
         assert at == 6 * C + ni, (at, ni)
     return np.array(cols + icols)
 
