@@ -604,6 +604,53 @@ int pp_tracks_merge(pp_tracks_handle h, const pp_tracks_options* options, const 
 int pp_tracks_get_state(pp_tracks_handle h, int32_t* num_points, int64_t* num_track_elements, int32_t* line_point, double* points,
                         uint8_t* deleted, int32_t* track_start, int32_t* track_line, int32_t point_capacity, int64_t element_capacity);
 
+/* ---- TriangulateImage / CompleteImage on a pp_tracks_handle (kernels K11a k_image_find, K11b k_image_triangulate) --------------------------------
+ * replaces IncrementalTriangulator::TriangulateImage (sfm/incremental_triangulator.cc:63-121: Find :426-466, Continue :563-604, Create :468-561) and
+ * CompleteImage (:123-235), the two places where the reference creates 3D points, with FindTransitiveCorrespondences / IsTwoViewObservation
+ * (base/correspondence_graph.cc:166-224, 252-263) and CalculateNormalizedLineAngularError (base/projection.cc:241-260).
+ * The device speculates over ALL lines of the image on the state at the start of the call (one wavefront per line for the closure, the Continue
+ * candidate and the create set; one lane per create set for the LORANSAC of pp_triangulate_tracks with Create's recursion in place); the host
+ * visits the lines in ascending line index and applies the answers.  An answer holds only while no line it read (the line itself and its closure)
+ * has changed line_point since the snapshot; otherwise the line is evaluated again on the current state by launches of its own.
+ * EXACTNESS: the result of a call equals the strictly sequential loop, whatever the schedule of the device work.
+ * EVENTS: the (point, line) pairs in the order the reference's Reconstruction receives them - one per AddObservation (a continue, a completion),
+ * and for an AddPoint3D the elements of the new track in track order.  New points take the next unused indices P, P + 1, ... as pp_tracks_merge's
+ * do; their positions are read with pp_tracks_get_state.  Events beyond `capacity` are not written (num_entries counts them all).
+ * An unregistered image, or one whose camera is flagged in camera_skip, returns 0 changes.
+ * CompleteImage keeps ONE options object over its loop (:142, :205-209): a set of more than 15 observations runs with the min_num_trials the last
+ * shorter set left behind.  That is kept; a line whose speculation assumed another value is evaluated again.
+ * ERRORS: as pp_tracks_complete / pp_tracks_merge (PP_ERR_INVALID leaves the handle as it was).                                              */
+typedef struct pp_tracks_image_options {   /* IncrementalTriangulator::Options, incremental_triangulator.h:47-87 */
+  double create_max_angle_error;     /* 2.0 degrees */
+  double continue_max_angle_error;   /* 2.0 degrees */
+  double complete_max_reproj_error;  /* 4.0 px */
+  double min_angle;                  /* 1.5 degrees */
+  int32_t max_transitivity;          /* 1 */
+  int32_t complete_max_transitivity; /* 5 */
+  int32_t ignore_two_view_tracks;    /* 1 */
+  int32_t reserved_;
+} pp_tracks_image_options;
+void pp_tracks_image_options_default(pp_tracks_image_options* o);
+
+typedef struct pp_tracks_image_report {
+  int64_t num_changed;       /* the reference's return value (num_tris) */
+  int64_t num_entries;       /* events of this call; those beyond `capacity` are not written */
+  int64_t ransac_trials;     /* trials of the RANSACs whose result was applied, summed */
+  int32_t points_created;
+  int32_t lines_continued;   /* TriangulateImage: lines that joined an existing point (Continue) */
+  int32_t lines_redone;      /* lines whose speculation did not hold and which were evaluated again on the current state */
+  int32_t fresh_launches;    /* kernel launches spent on them */
+  double device_ms;          /* HIP-event time of the speculative launches */
+  double replay_ms;          /* host replay, fresh launches included */
+  double total_ms;
+} pp_tracks_image_report;
+
+/* line_aligned: L bytes, FeatureLine::IsAligned per line (Create makes no point from aligned lines alone, :511-514); NULL = none aligned */
+int pp_tracks_triangulate_image(pp_tracks_handle h, const pp_tracks_image_options* options, int32_t image, const uint8_t* line_aligned,
+                                pp_tracks_image_report* report, int32_t* event_point, int32_t* event_line, int64_t capacity);
+int pp_tracks_complete_image(pp_tracks_handle h, const pp_tracks_image_options* options, int32_t image, pp_tracks_image_report* report,
+                             int32_t* event_point, int32_t* event_line, int64_t capacity);
+
 /* ======================================================================================== *
  *  Four-view line initialisation (LO-MSAC)                                                   *
  *  replaces, for the out-of-plane-translation stage: ransac_lib::LocallyOptimizedMSAC<        *

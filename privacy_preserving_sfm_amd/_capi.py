@@ -120,6 +120,18 @@ class TracksReport(C.Structure):
                 ("second_launches", C.c_int32), ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class TracksImageOptions(C.Structure):
+    _fields_ = [("create_max_angle_error", C.c_double), ("continue_max_angle_error", C.c_double), ("complete_max_reproj_error", C.c_double),
+                ("min_angle", C.c_double), ("max_transitivity", C.c_int32), ("complete_max_transitivity", C.c_int32),
+                ("ignore_two_view_tracks", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class TracksImageReport(C.Structure):
+    _fields_ = [("num_changed", C.c_int64), ("num_entries", C.c_int64), ("ransac_trials", C.c_int64), ("points_created", C.c_int32),
+                ("lines_continued", C.c_int32), ("lines_redone", C.c_int32), ("fresh_launches", C.c_int32),
+                ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -149,6 +161,7 @@ _EXPORTS = [
     "pp_planar_evaluate", "pp_planar_lomsac", "pp_fourview2d_create", "pp_fourview2d_destroy", "pp_fourview2d_score",
     "pp_triangulate_tracks", "pp_ba_filter_points", "pp_ba_filter_negative_depth", "pp_pose2d_create", "pp_pose2d_destroy", "pp_pose2d_solve_batch", "pp_pose2d_score", "pp_pose2d_evaluate", "pp_pose2d_lomsac",
     "pp_tracks_options_default", "pp_tracks_create", "pp_tracks_destroy", "pp_tracks_complete", "pp_tracks_merge", "pp_tracks_get_state",
+    "pp_tracks_image_options_default", "pp_tracks_triangulate_image", "pp_tracks_complete_image",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -246,6 +259,9 @@ def lib():
     L.pp_tracks_complete.argtypes = [C.c_void_p, C.POINTER(TracksOptions), c_u8p, C.POINTER(TracksReport), c_ip, c_ip, C.c_int64]
     L.pp_tracks_merge.argtypes = [C.c_void_p, C.POINTER(TracksOptions), c_u8p, C.POINTER(TracksReport), c_ip, c_ip, c_ip, C.c_int64]
     L.pp_tracks_get_state.argtypes = [C.c_void_p, c_ip, C.POINTER(C.c_int64), c_ip, c_dp, c_u8p, c_ip, c_ip, C.c_int32, C.c_int64]
+    L.pp_tracks_image_options_default.argtypes = [C.POINTER(TracksImageOptions)]
+    L.pp_tracks_triangulate_image.argtypes = [C.c_void_p, C.POINTER(TracksImageOptions), C.c_int32, c_u8p, C.POINTER(TracksImageReport), c_ip, c_ip, C.c_int64]
+    L.pp_tracks_complete_image.argtypes = [C.c_void_p, C.POINTER(TracksImageOptions), C.c_int32, C.POINTER(TracksImageReport), c_ip, c_ip, C.c_int64]
     L.pp_camera_image_to_world_threshold.argtypes = [C.c_int, c_dp, C.c_double, c_dp]
     _lib = L
     return L

@@ -196,6 +196,18 @@ class Reconstruction:
         fl.point3D_id = point3D_id
         self.points3D[point3D_id].track.append((image_id, line_idx))
 
+    def AddPoint3D(self, xyz, track):
+        """Reconstruction::AddPoint3D (base/reconstruction.cc:167-188): a new point under the next unused id (++num_added_points3D_; here one past the
+        largest id ever seen), every element of its track gets the point.  -> the id"""
+        self._num_added_points3D = max(getattr(self, "_num_added_points3D", 0), max(self.points3D, default=-1) + 1)
+        new_id = self._num_added_points3D
+        self._num_added_points3D += 1
+        self.points3D[new_id] = Point3D(xyz, track)
+        for (iid, idx) in self.points3D[new_id].track:
+            assert not self.images[iid].lines[idx].HasPoint3D()
+            self.images[iid].lines[idx].point3D_id = new_id
+        return new_id
+
     def MergePoints3D(self, point3D_id1, point3D_id2):
         """Reconstruction::MergePoints3D (base/reconstruction.cc:206-232): the length-weighted mean position, track 1 followed by track 2, both points
         deleted, the merged one added under the next unused id (++num_added_points3D_; here one past the largest id ever seen)."""

@@ -27,13 +27,39 @@ struct SpecList { const int32_t* line; int64_t count; };
 
 struct CompleteCounters { int64_t num_completed = 0; int32_t conflict_replays = 0; };
 
+// Complete for ONE existing point p whose track is as the speculation saw it: `s` = the device's list of p; claim(p, line) per observation added.
+// -> true if the host had to redo the walk.
+template <typename ClaimFn>
+inline bool ReplayCompletePoint(TrackState& st, int p, const SpecList s, int max_transitivity, ClaimFn&& claim) {
+  bool conflict = false;
+  for (int64_t i = 0; i < s.count && !conflict; ++i) conflict = st.line_point[(size_t)s.line[i]] != -1;
+  if (!conflict) {      // nothing this point can reach was taken: its list is what the sequential loop appends
+    for (int64_t i = 0; i < s.count; ++i) claim(p, s.line[i]);
+    return false;
+  }
+  // an earlier point took one of its lines: redo the breadth-first walk with "free now and in the device's pass set" as the test
+  // (the pass / fail of a (position, line) pair does not depend on the state, and what a point reaches only shrinks with fewer free lines)
+  std::unordered_set<int32_t> pass(s.line, s.line + s.count);
+  std::vector<int32_t> queue = st.tracks[(size_t)p], prev;
+  for (int t = 0; t < max_transitivity && !queue.empty(); ++t) {
+    prev.swap(queue);
+    queue.clear();
+    for (const int32_t fl : prev)
+      for (int32_t e = st.corr_start[(size_t)fl]; e < st.corr_start[(size_t)fl + 1]; ++e) {
+        const int32_t l = st.corr_line[(size_t)e];
+        if (st.line_point[(size_t)l] != -1 || !pass.count(l)) continue;
+        claim(p, l);
+        if (t < max_transitivity - 1) queue.push_back(l);
+      }
+  }
+  return true;
+}
+
 // Complete for the points of `subset` (nullptr = all) in ascending order.  spec(p) = the device's list of p; emit(p, line) per observation added.
 template <typename SpecFn, typename EmitFn>
 inline CompleteCounters ReplayComplete(TrackState& st, const uint8_t* subset, int max_transitivity, SpecFn&& spec, EmitFn&& emit) {
   CompleteCounters cnt;
   const int P = st.NumPoints();
-  std::unordered_set<int32_t> pass;
-  std::vector<int32_t> queue, prev;
   auto claim = [&](int p, int32_t l) {
     st.line_point[(size_t)l] = p;
     st.tracks[(size_t)p].push_back(l);
@@ -42,30 +68,7 @@ inline CompleteCounters ReplayComplete(TrackState& st, const uint8_t* subset, in
   };
   for (int p = 0; p < P; ++p) {
     if ((subset && !subset[p]) || !st.Exists(p)) continue;
-    const SpecList s = spec(p);
-    bool conflict = false;
-    for (int64_t i = 0; i < s.count && !conflict; ++i) conflict = st.line_point[(size_t)s.line[i]] != -1;
-    if (!conflict) {      // nothing this point can reach was taken: its list is what the sequential loop appends
-      for (int64_t i = 0; i < s.count; ++i) claim(p, s.line[i]);
-      continue;
-    }
-    // an earlier point took one of its lines: redo the breadth-first walk with "free now and in the device's pass set" as the test
-    // (the pass / fail of a (position, line) pair does not depend on the state, and what a point reaches only shrinks with fewer free lines)
-    ++cnt.conflict_replays;
-    pass.clear();
-    pass.insert(s.line, s.line + s.count);
-    queue = st.tracks[(size_t)p];
-    for (int t = 0; t < max_transitivity && !queue.empty(); ++t) {
-      prev.swap(queue);
-      queue.clear();
-      for (const int32_t fl : prev)
-        for (int32_t e = st.corr_start[(size_t)fl]; e < st.corr_start[(size_t)fl + 1]; ++e) {
-          const int32_t l = st.corr_line[(size_t)e];
-          if (st.line_point[(size_t)l] != -1 || !pass.count(l)) continue;
-          claim(p, l);
-          if (t < max_transitivity - 1) queue.push_back(l);
-        }
-    }
+    if (ReplayCompletePoint(st, p, spec(p), max_transitivity, claim)) ++cnt.conflict_replays;
   }
   return cnt;
 }

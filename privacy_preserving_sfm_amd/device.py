@@ -597,6 +597,16 @@ def tracks_options(**kw):
     return o
 
 
+def tracks_image_options(**kw):
+    o = _capi.TracksImageOptions()
+    _capi.lib().pp_tracks_image_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
 _TRACKS_FIELDS = (("poses", np.float64, dp), ("pose_camera", np.int32, None), ("camera_model", np.int32, None), ("intr", np.float64, dp),
                   ("cam_size", np.int32, None), ("camera_skip", np.uint8, None), ("image_registered", np.uint8, None), ("lines", np.float64, dp),
                   ("line_image", np.int32, None), ("line_point", np.int32, None), ("corr_start", np.int32, None), ("corr_line", np.int32, None),
@@ -671,6 +681,26 @@ class TracksProblem:
         check(_capi.lib().pp_tracks_merge(self._h, C.byref(o), ptr(sub, _capi.c_u8p), C.byref(rep), ptr(a, _capi.c_ip), ptr(b, _capi.c_ip), ptr(m, _capi.c_ip), cap))
         n = int(rep.num_entries)
         return rep, np.stack([a[:n], b[:n], m[:n]], axis=1)
+
+    def _image_call(self, fn, options, image, *extra):
+        o = options or tracks_image_options()
+        cap = 2 * self.num_lines      # every event gives a free line its point, and a line gets one once: L would do
+        ep, el = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+        rep = _capi.TracksImageReport()
+        check(fn(self._h, C.byref(o), int(image), *extra, C.byref(rep), ptr(ep, _capi.c_ip), ptr(el, _capi.c_ip), cap))
+        n = int(rep.num_entries)
+        return rep, np.stack([ep[:n], el[:n]], axis=1)
+
+    def triangulate_image(self, image, options=None, line_aligned=None):
+        """TriangulateImage for image index `image` -> (report, events [n, 2] (point, line) in the order the reference's Reconstruction receives them;
+        new points take the next unused indices, their positions are in state()["points"]).  line_aligned: [L] flags or None."""
+        al = None if line_aligned is None else np.ascontiguousarray(line_aligned, dtype=np.uint8)
+        assert al is None or len(al) == self.num_lines
+        return self._image_call(_capi.lib().pp_tracks_triangulate_image, options, image, ptr(al, _capi.c_u8p))
+
+    def complete_image(self, image, options=None):
+        """CompleteImage for image index `image` -> (report, events) as triangulate_image"""
+        return self._image_call(_capi.lib().pp_tracks_complete_image, options, image)
 
     def state(self):
         """-> dict(line_point [L], points [P', 3], deleted [P'], track_start [P' + 1], track_line)"""

@@ -4,12 +4,13 @@
 
 Each call flattens the reconstruction (`flatten`), hands it to the device and applies what comes back through `Reconstruction.AddObservation` /
 `Reconstruction.MergePoints3D`.  The reference visits the points in the order of an unordered_set; here the order is ASCENDING POINT ID.
-`TriangulateImage`, `CompleteImage` and `Retriangulate` (commented out in the reference) are not mirrored."""
+`TriangulateImage` and `CompleteImage` (the two places where the reference creates points) visit the lines of the image in ascending index, as the
+reference does.  `Retriangulate` (commented out in the reference) is not mirrored."""
 import numpy as np
 
 from . import _capi
 from .bundle_adjustment import Camera, FeatureLine, Image, Point3D, Reconstruction
-from .device import TracksProblem, tracks_options
+from .device import TracksProblem, tracks_image_options, tracks_options
 
 
 class CorrespondenceGraph:
@@ -23,6 +24,33 @@ class CorrespondenceGraph:
 
     def FindCorrespondences(self, image_id, line_idx):
         return self._corrs.get((image_id, line_idx), [])
+
+    def FindTransitiveCorrespondences(self, image_id, line_idx, transitivity):
+        """base/correspondence_graph.cc:166-224: the direct list for transitivity 1; otherwise level by level, a line collected on first sight, and at
+        the end the query (the first element) is overwritten by the LAST element - so the order is not plain breadth-first order"""
+        if transitivity == 1:
+            return list(self.FindCorrespondences(image_id, line_idx))
+        if not self.FindCorrespondences(image_id, line_idx):
+            return []
+        found, seen = [(image_id, line_idx)], {(image_id, line_idx)}
+        begin, end = 0, 1
+        for _ in range(transitivity):
+            for ref in found[begin:end]:
+                for corr in self.FindCorrespondences(*ref):
+                    if corr not in seen:
+                        seen.add(corr)
+                        found.append(corr)
+            begin, end = end, len(found)
+            if begin == end:
+                break
+        found[0] = found[-1]
+        found.pop()
+        return found
+
+    def IsTwoViewObservation(self, image_id, line_idx):
+        """base/correspondence_graph.cc:252-263"""
+        corrs = self.FindCorrespondences(image_id, line_idx)
+        return len(corrs) == 1 and len(self.FindCorrespondences(*corrs[0])) == 1
 
 
 class IncrementalTriangulator:
@@ -62,7 +90,8 @@ class IncrementalTriangulator:
         self.modified_point3D_ids_.clear()
 
     def flatten(self, options=None):
-        """-> (flat dict for device.TracksProblem, point_ids [P], line_ref [L] = (image_id, line_idx)).  Host only.  Lines are numbered image by
+        """-> (flat dict for device.TracksProblem, point_ids [P], line_ref [L] = (image_id, line_idx)).  flat["line_aligned"] [L] holds
+        FeatureLine.IsAligned (pp_tracks_triangulate_image's argument; not part of pp_tracks_desc).  Host only.  Lines are numbered image by
         image in id order; camera_skip is HasCameraBogusParams per camera (decided once per camera, :767-779)."""
         options = options or self.Options()
         rec, graph = self.reconstruction_, self.correspondence_graph_
@@ -78,11 +107,12 @@ class IncrementalTriangulator:
             line_ref.extend((iid, idx) for idx in range(len(rec.images[iid].lines)))
         L = len(line_ref)
         lines, line_image, line_point = np.zeros((L, 3)), np.zeros(L, dtype=np.int32), np.full(L, -1, dtype=np.int32)
+        line_aligned = np.zeros(L, dtype=np.uint8)
         corr_start, corr_line = np.zeros(L + 1, dtype=np.int32), []
         for c, iid in enumerate(image_ids):
             for idx, fl in enumerate(rec.images[iid].lines):
                 l = offset[iid] + idx
-                lines[l], line_image[l] = fl.Line(), c
+                lines[l], line_image[l], line_aligned[l] = fl.Line(), c, fl.IsAligned()
                 if fl.HasPoint3D():
                     line_point[l] = point_index[fl.Point3DId()]
                 corr_line.extend(offset[i2] + x2 for (i2, x2) in graph.FindCorrespondences(iid, idx) if i2 in offset)
@@ -103,7 +133,7 @@ class IncrementalTriangulator:
                     image_registered=np.array([getattr(rec.images[i], "registered", True) for i in image_ids], dtype=np.uint8),
                     lines=lines, line_image=line_image, line_point=line_point, corr_start=corr_start, corr_line=np.array(corr_line, dtype=np.int32),
                     points=np.array([rec.points3D[p].xyz for p in point_ids]).reshape(-1, 3), track_start=track_start,
-                    track_line=np.array(track_line, dtype=np.int32))
+                    track_line=np.array(track_line, dtype=np.int32), line_aligned=line_aligned)
         return flat, point_ids, line_ref
 
     @staticmethod
@@ -147,6 +177,54 @@ class IncrementalTriangulator:
         finally:
             pb.close()
         return num_completed, num_merged, completed, merged
+
+    @staticmethod
+    def device_image_options(options):
+        return tracks_image_options(create_max_angle_error=options.create_max_angle_error, continue_max_angle_error=options.continue_max_angle_error,
+                                    complete_max_reproj_error=options.complete_max_reproj_error, min_angle=options.min_angle,
+                                    max_transitivity=options.max_transitivity, complete_max_transitivity=options.complete_max_transitivity,
+                                    ignore_two_view_tracks=int(bool(options.ignore_two_view_tracks)))
+
+    def _run_image(self, options, image_id, complete):
+        assert options.Check()
+        rec = self.reconstruction_
+        self.last_reports = []
+        flat, point_ids, line_ref = self.flatten(options)
+        image = sorted(rec.images).index(image_id)
+        ids = list(point_ids)      # device index -> point id, new points appended as the events name them
+        pb = TracksProblem(flat, device=self.device_)
+        try:
+            o = self.device_image_options(options)
+            rep, events = pb.complete_image(image, o) if complete else pb.triangulate_image(image, o, flat["line_aligned"])
+            points = pb.state()["points"] if rep.points_created else None
+        finally:
+            pb.close()
+        self.last_reports.append(rep)
+        k = 0
+        while k < len(events):
+            p, l = int(events[k][0]), int(events[k][1])
+            if p < len(ids):
+                rec.AddObservation(ids[p], line_ref[l])
+                self.modified_point3D_ids_.add(ids[p])
+                k += 1
+                continue
+            assert p == len(ids)      # AddPoint3D: the whole track of the new point follows in track order
+            k1 = k
+            while k1 < len(events) and int(events[k1][0]) == p:
+                k1 += 1
+            new_id = rec.AddPoint3D(points[p], [line_ref[int(e[1])] for e in events[k:k1]])
+            ids.append(new_id)
+            self.modified_point3D_ids_.add(new_id)
+            k = k1
+        return int(rep.num_changed)
+
+    def TriangulateImage(self, options, image_id):
+        """sfm/incremental_triangulator.cc:63-121 (Find, Continue, Create) -> num_tris"""
+        return self._run_image(options, image_id, False)
+
+    def CompleteImage(self, options, image_id):
+        """sfm/incremental_triangulator.cc:123-235 -> num_tris"""
+        return self._run_image(options, image_id, True)
 
     def CompleteTracks(self, options, point3D_ids):
         return self._run(options, point3D_ids, True, False)[0]
