@@ -196,6 +196,9 @@ int pp_ba_destroy(pp_ba_handle h);
  * device blocks, pinned blocks, stream and events of a destroyed handle are kept (by size class, at most PPSFM_POOL_MAX_MB = 1024 MB of device memory
  * per process; 0 disables) and handed to the next one.  pp_pool_trim frees everything that is cached. */
 int pp_pool_trim(void);
+/* What the pool holds for this process: device blocks and pinned blocks handed out and not yet returned, device bytes cached for reuse (all devices).
+ * Null outputs are skipped.  The pool tracks nothing when it is disabled: with PPSFM_POOL_MAX_MB=0 all three are zero. */
+int pp_pool_stats(int64_t* live_device_blocks, int64_t* live_pinned_blocks, int64_t* cached_device_bytes);
 
 /* parameter blocks: poses C x 7 (qw,qx,qy,qz,tx,ty,tz), points P x 3, intrinsics K x PP_CAM_STRIDE.
  * PRECONDITION: unit quaternions.  BundleAdjuster::AddImageToProblem normalises every image of the configuration before it hands the block to Ceres

@@ -23,12 +23,14 @@
 
 #include "common.hpp"
 #include "p6l_device.hpp"
+#include "resource_pool.hpp"
 #include "ransac_host.hpp"
 
 struct pp_pose_impl {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  ppsfm::DeviceBlocks blocks{false};      // every device and pinned block below (plain hipMalloc / hipHostMalloc)
   int32_t n = 0;
   double *l0 = nullptr, *l1 = nullptr, *l2 = nullptr, *x0 = nullptr, *x1 = nullptr, *x2 = nullptr;
   uint8_t* aligned = nullptr;
@@ -445,33 +447,27 @@ static void LaunchScoreFlat(pp_pose_impl* h, int64_t max_models, double max_resi
 static int EnsureCapacity(pp_pose_impl* h, int64_t hyp) {
   h->last_hyp = 0;      // every user of the work buffers passes here first: the scores of an earlier pp_pose_hypotheses are gone
   if (hyp <= h->cap_hyp) return PP_OK;
-  void* old[] = {h->samples, h->models, h->num_models, h->inliers, h->sums, h->flat};
-  for (void* p : old) if (p) (void)hipFree(p);
-  h->samples = nullptr; h->models = nullptr; h->num_models = nullptr; h->inliers = nullptr; h->sums = nullptr; h->flat = nullptr;
+  DeviceBlocks& B = h->blocks;
+  B.Free(&h->samples); B.Free(&h->models); B.Free(&h->num_models); B.Free(&h->inliers); B.Free(&h->sums); B.Free(&h->flat);
   h->cap_hyp = 0; h->last_hyp = 0;
-  int rc;
-  if ((rc = DeviceAlloc(&h->samples, (size_t)hyp * 6))) return rc;
-  if ((rc = DeviceAlloc(&h->models, (size_t)hyp * 96))) return rc;
-  if ((rc = DeviceAlloc(&h->num_models, (size_t)hyp))) return rc;
-  if ((rc = DeviceAlloc(&h->inliers, (size_t)hyp * 8))) return rc;
-  if ((rc = DeviceAlloc(&h->sums, (size_t)hyp * 8))) return rc;
-  if ((rc = DeviceAlloc(&h->flat, (size_t)hyp * 8))) return rc;
-  if (!h->flat_total && (rc = DeviceAlloc(&h->flat_total, 4))) return rc;
-  if (!h->flat_blocks && (rc = DeviceAlloc(&h->flat_blocks, 1024))) return rc;
+  PP_TRY(B.Alloc(&h->samples, (size_t)hyp * 6)); PP_TRY(B.Alloc(&h->models, (size_t)hyp * 96)); PP_TRY(B.Alloc(&h->num_models, (size_t)hyp));
+  PP_TRY(B.Alloc(&h->inliers, (size_t)hyp * 8)); PP_TRY(B.Alloc(&h->sums, (size_t)hyp * 8)); PP_TRY(B.Alloc(&h->flat, (size_t)hyp * 8));
+  if (!h->flat_total) PP_TRY(B.Alloc(&h->flat_total, 4));
+  if (!h->flat_blocks) PP_TRY(B.Alloc(&h->flat_blocks, 1024));
   h->cap_hyp = hyp;
   return PP_OK;
 }
 
 static int EnsurePinned(pp_pose_impl* h, int64_t hyp) {
   if (hyp <= h->cap_pin) return PP_OK;
-  void* old[] = {h->pin_samples, h->pin_inl, h->pin_nm, h->pin_sm, h->pin_mdl};
-  for (void* p : old) if (p) (void)hipHostFree(p);
-  h->pin_samples = nullptr; h->pin_inl = nullptr; h->pin_nm = nullptr; h->pin_sm = nullptr; h->pin_mdl = nullptr; h->cap_pin = 0;
-  PP_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_samples), sizeof(uint32_t) * 6 * (size_t)hyp));
-  PP_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_inl), sizeof(uint32_t) * 8 * (size_t)hyp));
-  PP_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_nm), sizeof(int32_t) * (size_t)hyp));
-  PP_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_sm), sizeof(double) * 8 * (size_t)hyp));
-  PP_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_mdl), sizeof(double) * 96 * (size_t)hyp));
+  DeviceBlocks& B = h->blocks;
+  B.Free(&h->pin_samples); B.Free(&h->pin_inl); B.Free(&h->pin_nm); B.Free(&h->pin_sm); B.Free(&h->pin_mdl);
+  h->cap_pin = 0;
+  PP_TRY(B.AllocPinned(reinterpret_cast<void**>(&h->pin_samples), sizeof(uint32_t) * 6 * (size_t)hyp));
+  PP_TRY(B.AllocPinned(reinterpret_cast<void**>(&h->pin_inl), sizeof(uint32_t) * 8 * (size_t)hyp));
+  PP_TRY(B.AllocPinned(reinterpret_cast<void**>(&h->pin_nm), sizeof(int32_t) * (size_t)hyp));
+  PP_TRY(B.AllocPinned(reinterpret_cast<void**>(&h->pin_sm), sizeof(double) * 8 * (size_t)hyp));
+  PP_TRY(B.AllocPinned(reinterpret_cast<void**>(&h->pin_mdl), sizeof(double) * 96 * (size_t)hyp));
   h->cap_pin = hyp;
   return PP_OK;
 }
@@ -501,10 +497,7 @@ extern "C" {
 int pp_pose_destroy(pp_pose_handle h) try {
   if (!h) return PP_OK;
   (void)hipSetDevice(h->device);
-  void* bufs[] = {h->l0, h->l1, h->l2, h->x0, h->x1, h->x2, h->aligned, h->samples, h->models, h->num_models, h->inliers,
-                  h->sums, h->residuals, h->best_key, h->flat, h->flat_total, h->flat_blocks};
-  for (void* b : bufs) if (b) (void)hipFree(b);
-  { void* pins[] = {h->pin_samples, h->pin_inl, h->pin_nm, h->pin_sm, h->pin_mdl}; for (void* b : pins) if (b) (void)hipHostFree(b); }
+  h->blocks.Release();      // (plain device memory: freeing it waits for the device)
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -521,28 +514,20 @@ int pp_pose_create(int32_t n, const double* lines2D, const double* points3D, con
   PP_HIP_TRY(hipGetDeviceCount(&ndev));
   PP_REQUIRE(device >= 0 && device < ndev, "pp_pose_create: device %d of %d", device, ndev);
   PP_HIP_TRY(hipSetDevice(device));
-  pp_pose_impl* h = new pp_pose_impl();
-  OnUnwind unwind{[&] { pp_pose_destroy(h); }};
-  h->device = device; h->n = n;
-  int rc = PP_OK;
-#define TRY(x) do { rc = (x); if (rc) { pp_pose_destroy(h); return rc; } } while (0)
-#define TRYH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { SetLastError("%s: %s", #x, hipGetErrorString(e_)); pp_pose_destroy(h); return PP_ERR_HIP; } } while (0)
-  TRYH(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  TRYH(hipEventCreate(&h->ev0)); TRYH(hipEventCreate(&h->ev1));
   const size_t nn = std::max(n, 1);
-  std::vector<double> soa(6 * nn, 0.0);
+  std::vector<double> soa(6 * nn, 0.0);      // (before the handle: on an error return the handle's release - of plain device memory, which waits for the device - comes first)
   for (int i = 0; i < n; ++i)
     for (int c = 0; c < 3; ++c) { soa[c * nn + i] = lines2D[3 * i + c]; soa[(3 + c) * nn + i] = points3D[3 * i + c]; }
-  TRY(DeviceAlloc(&h->l0, nn)); TRY(DeviceAlloc(&h->l1, nn)); TRY(DeviceAlloc(&h->l2, nn));
-  TRY(DeviceAlloc(&h->x0, nn)); TRY(DeviceAlloc(&h->x1, nn)); TRY(DeviceAlloc(&h->x2, nn));
-  double* dst[6] = {h->l0, h->l1, h->l2, h->x0, h->x1, h->x2};
-  for (int c = 0; c < 6; ++c) TRY(Upload(dst[c], soa.data() + c * nn, nn, h->stream));
-  if (aligned && n > 0) { TRY(DeviceAlloc(&h->aligned, nn)); TRY(Upload(h->aligned, aligned, (size_t)n, h->stream)); }
-  TRY(DeviceAlloc(&h->best_key, 3 * 1024));
-  TRYH(hipStreamSynchronize(h->stream));
-#undef TRY
-#undef TRYH
-  *out = h;
+  UnderConstruction<pp_pose_impl, pp_pose_destroy> h{new pp_pose_impl()};
+  h->device = device; h->n = n;
+  PP_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  PP_HIP_TRY(hipEventCreate(&h->ev0)); PP_HIP_TRY(hipEventCreate(&h->ev1));
+  double** dst[6] = {&h->l0, &h->l1, &h->l2, &h->x0, &h->x1, &h->x2};
+  for (int c = 0; c < 6; ++c) PP_TRY(h->blocks.Put(dst[c], soa.data() + c * nn, nn, h->stream));
+  if (aligned && n > 0) PP_TRY(h->blocks.Put(&h->aligned, aligned, (size_t)n, h->stream, nn));
+  PP_TRY(h->blocks.Alloc(&h->best_key, 3 * 1024));
+  PP_HIP_TRY(hipStreamSynchronize(h->stream));
+  *out = h.release();
   return PP_OK;
 } PP_API_CATCH("pp_pose_create")
 
@@ -552,9 +537,9 @@ int pp_pose_residuals(pp_pose_handle h, int32_t num_models, const double* models
   PP_HIP_TRY(hipSetDevice(h->device));
   const int64_t need = (int64_t)num_models * h->n;
   if (need > h->cap_res) {
-    if (h->residuals) (void)hipFree(h->residuals);
-    h->residuals = nullptr; h->cap_res = 0;
-    int rc = DeviceAlloc(&h->residuals, (size_t)need); if (rc) return rc;
+    h->blocks.Free(&h->residuals);
+    h->cap_res = 0;
+    PP_TRY(h->blocks.Alloc(&h->residuals, (size_t)need));
     h->cap_res = need;
   }
   int rc = EnsureCapacity(h, CeilDiv(num_models, 8) + 1); if (rc) return rc;
@@ -616,11 +601,8 @@ int pp_re3q3_batch(int64_t num, const double* coeffs, double* solutions, int32_t
   if (num == 0) return PP_OK;
   PP_HIP_TRY(hipSetDevice(device));
   double *dc = nullptr, *ds = nullptr; int32_t* dn = nullptr;
-  int rc;
-  if ((rc = DeviceAlloc(&dc, (size_t)num * 30)) || (rc = DeviceAlloc(&ds, (size_t)num * 24)) || (rc = DeviceAlloc(&dn, (size_t)num))) {
-    if (dc) (void)hipFree(dc); if (ds) (void)hipFree(ds); if (dn) (void)hipFree(dn);
-    return rc;
-  }
+  DeviceBlocks scratch(false);      // (the copies below are synchronous)
+  PP_TRY(scratch.Alloc(&dc, (size_t)num * 30)); PP_TRY(scratch.Alloc(&ds, (size_t)num * 24)); PP_TRY(scratch.Alloc(&dn, (size_t)num));
   hipError_t e = hipMemcpy(dc, coeffs, sizeof(double) * 30 * num, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_re3q3, dim3(CeilDiv(num, 64)), dim3(64), 0, 0, num, dc, ds, dn);
@@ -628,7 +610,6 @@ int pp_re3q3_batch(int64_t num, const double* coeffs, double* solutions, int32_t
   }
   if (e == hipSuccess) e = hipMemcpy(solutions, ds, sizeof(double) * 24 * num, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(num_solutions, dn, sizeof(int32_t) * num, hipMemcpyDeviceToHost);
-  (void)hipFree(dc); (void)hipFree(ds); (void)hipFree(dn);
   if (e != hipSuccess) { SetLastError("pp_re3q3_batch: %s", hipGetErrorString(e)); return PP_ERR_HIP; }
   return PP_OK;
 } PP_API_CATCH("pp_re3q3_batch")

@@ -232,16 +232,14 @@ __global__ __launch_bounds__(256) void k_cov_points(CovPointArgs a, const int32_
 }
 
 namespace {
-// the buffers of one pp_ba_covariance call: pool blocks, returned on every way out (after the stream has drained)
+// the buffers of one pp_ba_covariance call: pool blocks, returned on every way out - after the stream has drained (`blocks` is destroyed after the body)
 struct CovBuffers {
   hipStream_t stream = nullptr;
-  std::vector<void*> blocks;
   CholeskyState* chol = nullptr;
-  template <typename T> int Alloc(T** p, size_t count) { const int rc = HandleAlloc(p, count); if (rc == PP_OK && *p) blocks.push_back(*p); return rc; }
+  DeviceBlocks blocks;
   ~CovBuffers() {
     if (stream) (void)hipStreamSynchronize(stream);
     if (chol) CholeskyDestroy(chol);
-    for (void* b : blocks) PoolDeviceFree(b);
   }
 };
 // the handle's solver buffers while the assembly kernels run on this call's: put back on every way out.  This relies on every evaluate / assembly launch
@@ -277,9 +275,8 @@ extern "C" int pp_ba_covariance(pp_ba_handle h, const pp_ba_options* o, int32_t 
              "detach it, or take the covariance from a handle that holds the whole problem");
   if (info) std::memset(info, 0, sizeof(*info));
   PP_HIP_TRY(hipSetDevice(h->device));
-  int rc;
-  if ((rc = BaEnsureJacobianBuffers(h, 0, h->NI > 0 ? 1 : 0))) return rc;
-  if ((rc = BaEnsureSolverBuffers(h))) return rc;
+  PP_TRY(BaEnsureJacobianBuffers(h, 0, h->NI > 0 ? 1 : 0));
+  PP_TRY(BaEnsureSolverBuffers(h));
   hipStream_t s = h->stream;
   const int N = h->N, n = h->n_red, T = N / kTile;
   const size_t NN = (size_t)N * N;
@@ -293,22 +290,22 @@ extern "C" int pp_ba_covariance(pp_ba_handle h, const pp_ba_options* o, int32_t 
   sw.chol_small = false;      // (the one-workgroup kernel of one or two block columns keeps its factor in LDS: per-column launches leave it in memory, the same arithmetic)
   {
     std::lock_guard<std::recursive_mutex> setup_lock(DeviceSetupMutex());      // (allocations: not beside another host thread's graph capture)
-    if ((rc = buf.Alloc(&S2, NN)) || (rc = buf.Alloc(&Linv2, CholeskyWorkspaceDoubles(N))) || (rc = buf.Alloc(&x2, (size_t)N)) || (rc = buf.Alloc(&flag2, 4)) ||
-        (rc = buf.Alloc(&scale_c2, (size_t)n)) || (rc = buf.Alloc(&scale_p2, 3 * (size_t)h->P)) || (rc = buf.Alloc(&diag_c2, (size_t)n)) ||
-        (rc = buf.Alloc(&diag_p2, 3 * (size_t)h->P)) || (rc = buf.Alloc(&Vinv2, 6 * (size_t)h->P)) || (rc = buf.Alloc(&vb2, 3 * (size_t)h->P)) || (rc = buf.Alloc(&Zt, NN)) ||
-        (rc = buf.Alloc(&d_pose, 36 * (size_t)num_pose_pairs)) || (rc = buf.Alloc(&d_point, 9 * (size_t)num_points)) || (rc = buf.Alloc(&d_pairs, 2 * (size_t)num_pose_pairs)) ||
-        (rc = buf.Alloc(&d_ids, (size_t)num_points)))
-      return rc;
+    DeviceBlocks& B = buf.blocks;
+    PP_TRY(B.Alloc(&S2, NN)); PP_TRY(B.Alloc(&Linv2, CholeskyWorkspaceDoubles(N))); PP_TRY(B.Alloc(&x2, (size_t)N)); PP_TRY(B.Alloc(&flag2, 4));
+    PP_TRY(B.Alloc(&scale_c2, (size_t)n)); PP_TRY(B.Alloc(&scale_p2, 3 * (size_t)h->P)); PP_TRY(B.Alloc(&diag_c2, (size_t)n)); PP_TRY(B.Alloc(&diag_p2, 3 * (size_t)h->P));
+    PP_TRY(B.Alloc(&Vinv2, 6 * (size_t)h->P)); PP_TRY(B.Alloc(&vb2, 3 * (size_t)h->P)); PP_TRY(B.Alloc(&Zt, NN));
+    PP_TRY(B.Alloc(&d_pose, 36 * (size_t)num_pose_pairs)); PP_TRY(B.Alloc(&d_point, 9 * (size_t)num_points)); PP_TRY(B.Alloc(&d_pairs, 2 * (size_t)num_pose_pairs));
+    PP_TRY(B.Alloc(&d_ids, (size_t)num_points));
     buf.chol = CholeskyCreate(sw);
     CholeskyDisableGraph(buf.chol);      // one factorisation: nothing to replay
-    if (CholeskyNeedsFactorArray(buf.chol, N) && !CholeskyColumnsOnly(h->chol) && (rc = buf.Alloc(&Lfac2, NN))) return rc;
+    if (CholeskyNeedsFactorArray(buf.chol, N) && !CholeskyColumnsOnly(h->chol)) PP_TRY(B.Alloc(&Lfac2, NN));
     PP_HIP_TRY(hipMemsetAsync(S2, 0, sizeof(double) * NN, s));
     if (Lfac2) PP_HIP_TRY(hipMemsetAsync(Lfac2, 0, sizeof(double) * NN, s));
     PP_HIP_TRY(hipMemsetAsync(Zt, 0, sizeof(double) * NN, s));
     PP_HIP_TRY(hipMemsetAsync(flag2, 0, 4 * sizeof(int32_t), s));
     const CholeskySystem sys{S2, N, n, Linv2, Lfac2, x2, flag2, s};
     const bool sparse = h->sparse_tiles && !h->tile_nz.empty();
-    if ((rc = CholeskyBind(buf.chol, sys, sparse ? h->tile_nz.data() : nullptr))) return rc;
+    PP_TRY(CholeskyBind(buf.chol, sys, sparse ? h->tile_nz.data() : nullptr));
     if (CholeskyColumnsOnly(h->chol)) (void)CholeskyFallBackToColumns(buf.chol);      // the launch path the handle's own factorisation has
   }
   // the requests in the handle's image numbering (pp_ba_create may have renumbered the images; the points keep their order)
@@ -330,8 +327,8 @@ extern "C" int pp_ba_covariance(pp_ba_handle h, const pp_ba_options* o, int32_t 
     BufferSwap swap(h);
     h->S = S2; h->scale_c = scale_c2; h->scale_p = scale_p2; h->diag_c = diag_c2; h->diag_p = diag_p2; h->Vinv = Vinv2; h->vb = vb2; h->d_flag = flag2;
     for (int attempt = 0; attempt < 2; ++attempt) {
-      if ((rc = BaAssembleUndamped(h, o, attempt == 0))) return rc;
-      if ((rc = CholeskySolve(buf.chol))) return rc;
+      PP_TRY(BaAssembleUndamped(h, o, attempt == 0));
+      PP_TRY(CholeskySolve(buf.chol));
       PP_HIP_TRY(hipMemcpyAsync(&flag, flag2, sizeof(int32_t), hipMemcpyDeviceToHost, s));
       PP_HIP_TRY(hipStreamSynchronize(s));
       // a bounded wait of the one-launch factorisation ran out: nothing wrong with the system - once more with per-column launches (what RecoverAfterFlag does)

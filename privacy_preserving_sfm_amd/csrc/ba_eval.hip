@@ -191,16 +191,11 @@ static EvalArgs MakeArgs(pp_ba_impl* h, const double* poses, const double* point
 int BaEnsureJacobianBuffers(pp_ba_impl* h, int jac_mode, int want_cam) {
   const int width = jac_mode == 1 ? 14 : 12;
   if (!h->Jpose || h->jpose_width < width) {
-    if (h->Jpose) PoolDeviceFree(h->Jpose);
-    h->Jpose = nullptr;
-    int rc = HandleAlloc(&h->Jpose, (size_t)h->M * width);
-    if (rc) return rc;
+    h->blocks.Free(&h->Jpose);
+    PP_TRY(h->blocks.Alloc(&h->Jpose, (size_t)h->M * width));
     h->jpose_width = width;
   }
-  if (want_cam && !h->Jcam) {
-    int rc = HandleAlloc(&h->Jcam, (size_t)h->M * 2 * kCamStride);
-    if (rc) return rc;
-  }
+  if (want_cam && !h->Jcam) PP_TRY(h->blocks.Alloc(&h->Jcam, (size_t)h->M * 2 * kCamStride));
   return PP_OK;
 }
 
@@ -254,22 +249,12 @@ extern "C" {
 int pp_ba_destroy(pp_ba_handle h) try {
   if (!h) return PP_OK;
   (void)hipSetDevice(h->device);
-  void* bufs[] = {h->la, h->lb, h->lc, h->obs_cam, h->obs_pose, h->obs_point, h->pose_camera, h->camera_model, h->pose_const,
-                  h->tvec_mask, h->point_const, h->pt_start, h->pt_obs, h->pose_start, h->pose_obs, h->pair_start,
-                  h->pair_ij, h->pair_entries, h->poses, h->points, h->intr, h->poses_c, h->points_c, h->r, h->Jpose,
-                  h->Jpoint, h->Jcam, h->partials, h->U, h->gc, h->V, h->gp, h->Vinv, h->vb, h->scale_c, h->scale_p,
-                  h->diag_c, h->diag_p, h->S, h->Linv, h->Lfac, h->step_c, h->step_p, h->scal, h->JpS, h->Q, h->norm_part,
-                  h->intr_c, h->cam_np, h->intr_off, h->intr_nv, h->intr_col, h->cam_start, h->cam_obs, h->gen_pair, h->gen_pair_chunk, h->gen_chunk,
-                  h->gen_multi, h->gen_grp_start, h->gen_grp_obs, h->gen_L, h->kk_entries, h->kk_pair, h->kk_pair_chunk, h->kk_chunk, h->kk_multi, h->kk_partial, h->gen_entries, h->isum_chunk, h->isum_cam_chunk, h->gen_partial, h->isum_partial, h->cnI, h->JkS_intr, h->Spack, h->nz_tile_list,
-                  h->small_chunk, h->small_pair_chunk, h->small_partials, h->spos, h->step_s, h->attach_slot};
   if (h->stream) (void)hipStreamSynchronize(h->stream);      // nothing of this handle is in flight when its blocks go back to the pool (resource_pool.hpp)
-  for (void* b : bufs) if (b) PoolDeviceFree(b);
   CholeskyDestroy(h->chol);
-  PcgFreeBuffers(h);
+  h->blocks.Release();
+  h->mirrors.Release();
   for (int i = 0; i < 8; ++i) if (h->tev[i]) PoolEventRelease(h->tev[i], true);
   for (int i = 0; i < 2; ++i) if (h->tev_eval[i]) PoolEventRelease(h->tev_eval[i], true);
-  if (h->h_scal) PoolPinnedFree(h->h_scal);
-  { void* pins[] = {h->pin_r, h->pin_jpose, h->pin_jpoint, h->pin_jcam}; for (void* b : pins) if (b) (void)hipHostFree(b); }
   if (h->ev_readback) PoolEventRelease(h->ev_readback, false);
   if (h->ev0) PoolEventRelease(h->ev0, true);
   if (h->ev1) PoolEventRelease(h->ev1, true);
@@ -336,8 +321,8 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
     fprintf(stderr, "ppsfm: create %-34s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - last).count());
     last = now;
   };
-  pp_ba_impl* h = new pp_ba_impl();
-  OnUnwind unwind{[&] { pp_ba_destroy(h); }};      // (a std::bad_alloc of the host builders below must not leak the handle's device memory)
+  UnderConstruction<pp_ba_impl, pp_ba_destroy> guard{new pp_ba_impl()};      // (an error return or a std::bad_alloc of the host builders below: the handle's device memory goes back)
+  pp_ba_impl* const h = guard.h;
   // (a handle whose order and tile structure come from the caller's co-visibility - the union over the shards of a point-sharded group - lays out the
   // exchanged system like every other rank that was given the same matrix: it may join a group renumbered and block-sparse)
   h->sw = sw;
@@ -353,13 +338,11 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   // from the per-observation intrinsics Jacobians, their diagonal blocks (the preconditioner's) are assembled from the (k, k) pair lists alone.
   h->iterative = ppsfm::WillIterate(d, sw.ba_linear_solver);
   const bool iterative = h->iterative;
-  int rc = PP_OK;
-#define TRY(x) do { rc = (x); if (rc) { pp_ba_destroy(h); return rc; } } while (0)
-#define TRYH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { SetLastError("%s: %s", #x, hipGetErrorString(e_)); pp_ba_destroy(h); return PP_ERR_HIP; } } while (0)
-  TRY(PoolStreamAcquire(&h->stream));
-  TRY(PoolEventAcquire(&h->ev0, true));
-  TRY(PoolEventAcquire(&h->ev1, true));
+  PP_TRY(PoolStreamAcquire(&h->stream));
+  PP_TRY(PoolEventAcquire(&h->ev0, true));
+  PP_TRY(PoolEventAcquire(&h->ev1, true));
   hipStream_t s = h->stream;
+  DeviceBlocks& B = h->blocks;
   lap("handle, stream, events");
 
   // ---- the by-point lists (no image order in them) ---------------------------------------------------------------------------------------------------
@@ -379,16 +362,14 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   std::vector<uint64_t> graph_bits;
   double graph_ms = 0;
   if (lists_on_device) {
-    TRY(HandleAlloc(&h->obs_pose, M)); TRY(HandleAlloc(&h->obs_point, M)); TRY(HandleAlloc(&h->pose_const, C)); TRY(HandleAlloc(&h->point_const, P));
-    TRY(HandleAlloc(&h->pt_start, P + 1)); TRY(HandleAlloc(&h->pt_obs, M));
-    TRY(Upload(h->obs_point, d->obs_point, M, s)); TRY(Upload(h->point_const, point_const.data(), P, s));
-    TRY(Upload(h->pt_start, pt_start.data(), P + 1, s)); TRY(Upload(h->pt_obs, pt_obs.data(), M, s));
+    PP_TRY(B.Alloc(&h->obs_pose, M)); PP_TRY(B.Put(&h->obs_point, d->obs_point, M, s)); PP_TRY(B.Alloc(&h->pose_const, C)); PP_TRY(B.Put(&h->point_const, point_const.data(), P, s));
+    PP_TRY(B.Put(&h->pt_start, pt_start.data(), P + 1, s)); PP_TRY(B.Put(&h->pt_obs, pt_obs.data(), M, s));
     if (ppsfm::OrderingReadsObservations(d, NI, sw)) {
       const auto tg = std::chrono::steady_clock::now();
       std::vector<uint8_t> fixed(C, 0);
       if (d->pose_const && (iterative || ppsfm::PrivateIntrinsicsColumns(d, sw.ba_intr_layout) == 0)) std::memcpy(fixed.data(), d->pose_const, C);      // (as ChooseImageOrdering's fixed_image)
-      TRY(Upload(h->obs_pose, d->obs_pose, M, s)); TRY(Upload(h->pose_const, fixed.data(), C, s));
-      TRY(CoVisibilityOnDevice(C, M, h->pt_start, h->pt_obs, h->obs_pose, h->obs_point, h->pose_const, h->point_const, s, &graph_bits));
+      PP_TRY(Upload(h->obs_pose, d->obs_pose, M, s)); PP_TRY(Upload(h->pose_const, fixed.data(), C, s));
+      PP_TRY(CoVisibilityOnDevice(C, M, h->pt_start, h->pt_obs, h->obs_pose, h->obs_point, h->pose_const, h->point_const, s, &graph_bits));
       graph_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tg).count();
       lap("co-visibility graph (device)");
     }
@@ -478,21 +459,18 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
     }
     if (bound >= ((int64_t)1 << 31) - 1) {
       SetLastError("pp_ba_create: %lld Schur pair entries (sum over points of track^2 / 2) exceed the 32-bit pair lists", (long long)bound);
-      pp_ba_destroy(h);
       return PP_ERR_INVALID;
     }
   }
   // The pair lists on the device (the by-point lists are there): the lists' 3 ints per list come back, the entries never leave the device.  A structure with a list too long for the device's per-list sort takes the host builder below.
-  int32_t* dev_entries = nullptr;
   const bool arrays_on_device = lists_on_device;      // (the by-point lists, obs_pose / obs_point and the constant flags are on the device already - also when the host builder takes over below)
   if (lists_on_device) {
-    TRY(Upload(h->obs_pose, in_obs_pose, M, s)); TRY(Upload(h->pose_const, list_const.data(), C, s));      // (the order chosen)
+    PP_TRY(Upload(h->obs_pose, in_obs_pose, M, s)); PP_TRY(Upload(h->pose_const, list_const.data(), C, s));      // (the order chosen)
     bool fallback = false;
-    rc = BuildPairListsOnDevice(C, M, h->pt_start, h->pt_obs, h->obs_pose, h->obs_point, h->pose_const, h->point_const, s, &dev_entries, &total_entries, &pair_start, &pair_ij, &fallback);
-    if (rc && !fallback) { pp_ba_destroy(h); return rc; }
-    if (fallback) { lists_on_device = false; rc = PP_OK; total_entries = 0; pair_start.clear(); pair_ij.clear(); }
-    else h->pair_entries = dev_entries;
-    if (nv_private > 0) TRY(Upload(h->pose_const, pose_const.data(), C, s));      // (the handle's array says which POSES are constant)
+    const int rc = BuildPairListsOnDevice(C, M, h->pt_start, h->pt_obs, h->obs_pose, h->obs_point, h->pose_const, h->point_const, s, &B, &h->pair_entries, &total_entries, &pair_start, &pair_ij, &fallback);
+    if (rc && !fallback) return rc;
+    if (fallback) { lists_on_device = false; total_entries = 0; pair_start.clear(); pair_ij.clear(); }
+    if (nv_private > 0) PP_TRY(Upload(h->pose_const, pose_const.data(), C, s));      // (the handle's array says which POSES are constant)
   }
   if (!iterative && !lists_on_device) {      // (an iterative handle applies S from the records: no pair lists)
     // (pair_lists.hip BuildPairListsOnHost: buckets per row image + a counting sort per row, on a few host threads)
@@ -529,7 +507,6 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
         if (oi != oj && !d->covisibility[(size_t)oi * C + oj] && !d->covisibility[(size_t)oj * C + oi]) {
           SetLastError("pp_ba_create: images %d and %d share a point of this shard but pp_ba_problem_desc::covisibility has no entry for them - the matrix must be "
                        "the union over the group's shards (pp_ba_covisibility of every rank, element-wise MAX)", oi, oj);
-          pp_ba_destroy(h);
           return PP_ERR_INVALID;
         }
       }
@@ -881,89 +858,68 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   lap("chunks, intrinsics lists");
   const auto t_create3 = std::chrono::steady_clock::now();
   // ---- device allocation + upload --------------------------------------------------------------
-  TRY(HandleAlloc(&h->la, M)); TRY(HandleAlloc(&h->lb, M)); TRY(HandleAlloc(&h->lc, M));
-  if (!arrays_on_device) { TRY(HandleAlloc(&h->obs_pose, M)); TRY(HandleAlloc(&h->obs_point, M)); }
-  TRY(HandleAlloc(&h->obs_cam, M));
-  TRY(HandleAlloc(&h->pose_camera, C)); TRY(HandleAlloc(&h->camera_model, K));
-  if (!arrays_on_device) { TRY(HandleAlloc(&h->pose_const, C)); TRY(HandleAlloc(&h->point_const, P)); TRY(HandleAlloc(&h->pt_start, P + 1)); TRY(HandleAlloc(&h->pt_obs, M)); }
-  TRY(HandleAlloc(&h->tvec_mask, C));
-  TRY(HandleAlloc(&h->pose_start, C + 1)); TRY(HandleAlloc(&h->pose_obs, M));
-  TRY(HandleAlloc(&h->pair_start, pair_start.size())); TRY(HandleAlloc(&h->pair_ij, std::max<size_t>(pair_ij.size(), 2)));
-  if (!h->pair_entries) TRY(HandleAlloc(&h->pair_entries, std::max<size_t>(pair_entries.size(), 2)));      // (built on the device: already there)
-  TRY(HandleAlloc(&h->poses, (size_t)7 * C)); TRY(HandleAlloc(&h->points, (size_t)3 * P)); TRY(HandleAlloc(&h->intr, (size_t)kCamStride * K));
-  TRY(HandleAlloc(&h->poses_c, (size_t)7 * C)); TRY(HandleAlloc(&h->points_c, (size_t)3 * P)); TRY(HandleAlloc(&h->intr_c, (size_t)kCamStride * K));
-  TRY(HandleAlloc(&h->cam_np, K));
-  TRY(HandleAlloc(&h->intr_off, K)); TRY(HandleAlloc(&h->intr_nv, K)); TRY(HandleAlloc(&h->intr_col, (size_t)K * kCamStride));
+  PP_TRY(B.Put(&h->la, la.data(), M, s)); PP_TRY(B.Put(&h->lb, lb.data(), M, s)); PP_TRY(B.Put(&h->lc, lc.data(), M, s));
+  if (!arrays_on_device) { PP_TRY(B.Put(&h->obs_pose, in_obs_pose, M, s)); PP_TRY(B.Put(&h->obs_point, d->obs_point, M, s)); }
+  PP_TRY(B.Put(&h->obs_cam, obs_cam.data(), M, s));
+  PP_TRY(B.Put(&h->pose_camera, in_pose_camera, C, s)); PP_TRY(B.Put(&h->camera_model, d->camera_model, K, s));
+  if (!arrays_on_device) {
+    PP_TRY(B.Put(&h->pose_const, pose_const.data(), C, s)); PP_TRY(B.Put(&h->point_const, point_const.data(), P, s));
+    PP_TRY(B.Put(&h->pt_start, pt_start.data(), P + 1, s)); PP_TRY(B.Put(&h->pt_obs, pt_obs.data(), M, s));
+  }
+  PP_TRY(B.Put(&h->tvec_mask, tvec_mask.data(), C, s));
+  PP_TRY(B.Put(&h->pose_start, pose_start.data(), C + 1, s)); PP_TRY(B.Put(&h->pose_obs, pose_obs.data(), M, s));
+  PP_TRY(B.Put(&h->pair_start, pair_start.data(), pair_start.size(), s)); PP_TRY(B.Put(&h->pair_ij, pair_ij.data(), pair_ij.size(), s, 2));
+  if (!h->pair_entries) PP_TRY(B.Put(&h->pair_entries, pair_entries.data(), pair_entries.size(), s, 2));      // (built on the device: already there, and the handle's)
+  PP_TRY(B.Alloc(&h->poses, (size_t)7 * C)); PP_TRY(B.Alloc(&h->points, (size_t)3 * P)); PP_TRY(B.Alloc(&h->intr, (size_t)kCamStride * K));
+  PP_TRY(B.Alloc(&h->poses_c, (size_t)7 * C)); PP_TRY(B.Alloc(&h->points_c, (size_t)3 * P)); PP_TRY(B.Alloc(&h->intr_c, (size_t)kCamStride * K));
+  {
+    std::vector<int32_t> np(K);
+    for (int k = 0; k < K; ++k) np[k] = CameraNumParams(d->camera_model[k]);
+    PP_TRY(B.Put(&h->cam_np, np.data(), K, s)); PP_HIP_TRY(hipStreamSynchronize(s));
+  }
+  PP_TRY(B.Put(&h->intr_off, intr_off.data(), K, s)); PP_TRY(B.Put(&h->intr_nv, intr_nv.data(), K, s)); PP_TRY(B.Put(&h->intr_col, intr_col.data(), intr_col.size(), s));
   if (NI > 0) {
-    TRY(HandleAlloc(&h->cam_start, K + 1)); TRY(HandleAlloc(&h->cam_obs, M));
-    TRY(HandleAlloc(&h->gen_pair, std::max<size_t>(gen_pair.size(), 4))); TRY(HandleAlloc(&h->gen_pair_chunk, gen_pair_chunk.size()));
-    TRY(HandleAlloc(&h->gen_chunk, gen_chunk.size())); TRY(HandleAlloc(&h->gen_entries, std::max<size_t>(gen_entries.size(), 2)));
-    TRY(HandleAlloc(&h->gen_multi, std::max<size_t>(gen_multi.size(), 1)));
+    PP_TRY(B.Put(&h->cam_start, cam_start.data(), K + 1, s)); PP_TRY(B.Put(&h->cam_obs, cam_obs.data(), M, s));
+    PP_TRY(B.Put(&h->gen_pair, gen_pair.data(), gen_pair.size(), s, 4)); PP_TRY(B.Put(&h->gen_pair_chunk, gen_pair_chunk.data(), gen_pair_chunk.size(), s));
+    PP_TRY(B.Put(&h->gen_chunk, gen_chunk.data(), gen_chunk.size(), s)); PP_TRY(B.Put(&h->gen_entries, gen_entries.data(), gen_entries.size(), s, 2));
+    PP_TRY(B.Put(&h->gen_multi, gen_multi.data(), gen_multi.size(), s, 1));
     if (!iterative) {
       h->kk_num_groups = kk.num_groups; h->kk_num_pairs = (int64_t)(kk.pair.size() / 4); h->kk_num_chunks = (int64_t)(kk.chunk.size() / 3); h->kk_num_multi = (int64_t)kk.multi.size();
-      TRY(HandleAlloc(&h->kk_entries, std::max<size_t>(kk.entries.size(), 1))); TRY(HandleAlloc(&h->kk_pair, std::max<size_t>(kk.pair.size(), 1)));
-      TRY(HandleAlloc(&h->kk_pair_chunk, std::max<size_t>(kk.pair_chunk.size(), 1))); TRY(HandleAlloc(&h->kk_chunk, std::max<size_t>(kk.chunk.size(), 1)));
-      TRY(HandleAlloc(&h->kk_multi, std::max<size_t>(kk.multi.size(), 1))); TRY(HandleAlloc(&h->kk_partial, 144 * std::max<size_t>((size_t)h->kk_num_chunks, 1)));
-      TRY(Upload(h->kk_entries, kk.entries.data(), kk.entries.size(), s)); TRY(Upload(h->kk_pair, kk.pair.data(), kk.pair.size(), s));
-      TRY(Upload(h->kk_pair_chunk, kk.pair_chunk.data(), kk.pair_chunk.size(), s)); TRY(Upload(h->kk_chunk, kk.chunk.data(), kk.chunk.size(), s));
-      TRY(Upload(h->kk_multi, kk.multi.data(), kk.multi.size(), s));
-      TRY(HandleAlloc(&h->gen_grp_start, std::max<size_t>(gen_grp_start.size(), 1))); TRY(HandleAlloc(&h->gen_grp_obs, std::max<size_t>(gen_grp_obs.size(), 1)));
-      TRY(HandleAlloc(&h->gen_L, 36 * std::max<size_t>((size_t)h->gen_num_groups, 1)));
+      PP_TRY(B.Put(&h->kk_entries, kk.entries.data(), kk.entries.size(), s, 1)); PP_TRY(B.Put(&h->kk_pair, kk.pair.data(), kk.pair.size(), s, 1));
+      PP_TRY(B.Put(&h->kk_pair_chunk, kk.pair_chunk.data(), kk.pair_chunk.size(), s, 1)); PP_TRY(B.Put(&h->kk_chunk, kk.chunk.data(), kk.chunk.size(), s, 1));
+      PP_TRY(B.Put(&h->kk_multi, kk.multi.data(), kk.multi.size(), s, 1)); PP_TRY(B.Alloc(&h->kk_partial, 144 * std::max<size_t>((size_t)h->kk_num_chunks, 1)));
+      PP_TRY(B.Put(&h->gen_grp_start, gen_grp_start.data(), gen_grp_start.size(), s, 1)); PP_TRY(B.Put(&h->gen_grp_obs, gen_grp_obs.data(), gen_grp_obs.size(), s, 1));
+      PP_TRY(B.Alloc(&h->gen_L, 36 * std::max<size_t>((size_t)h->gen_num_groups, 1)));
     }
-    TRY(HandleAlloc(&h->isum_chunk, isum_chunk.size())); TRY(HandleAlloc(&h->isum_cam_chunk, isum_cam_chunk.size()));
-    TRY(HandleAlloc(&h->gen_partial, (size_t)std::max<int64_t>(h->gen_num_chunks, 1) * 144)); TRY(HandleAlloc(&h->isum_partial, (size_t)std::max<int64_t>(h->isum_num_chunks, 1) * 24));
-    TRY(HandleAlloc(&h->cnI, (size_t)NI)); TRY(HandleAlloc(&h->JkS_intr, (size_t)M * 2 * kCamStride));
-    TRYH(hipMemsetAsync(h->JkS_intr, 0, sizeof(double) * (size_t)M * 2 * kCamStride, s));      // (k_intr_prepare only ever writes a camera's variable columns)
+    PP_TRY(B.Put(&h->isum_chunk, isum_chunk.data(), isum_chunk.size(), s)); PP_TRY(B.Put(&h->isum_cam_chunk, isum_cam_chunk.data(), isum_cam_chunk.size(), s));
+    PP_TRY(B.Alloc(&h->gen_partial, (size_t)std::max<int64_t>(h->gen_num_chunks, 1) * 144)); PP_TRY(B.Alloc(&h->isum_partial, (size_t)std::max<int64_t>(h->isum_num_chunks, 1) * 24));
+    PP_TRY(B.Alloc(&h->cnI, (size_t)NI)); PP_TRY(B.Alloc(&h->JkS_intr, (size_t)M * 2 * kCamStride));
+    PP_HIP_TRY(hipMemsetAsync(h->JkS_intr, 0, sizeof(double) * (size_t)M * 2 * kCamStride, s));      // (k_intr_prepare only ever writes a camera's variable columns)
   }
-  TRY(HandleAlloc(&h->r, (size_t)2 * M)); TRY(HandleAlloc(&h->Jpoint, (size_t)6 * M));
+  PP_TRY(B.Alloc(&h->r, (size_t)2 * M)); PP_TRY(B.Alloc(&h->Jpoint, (size_t)6 * M));
   h->num_partials = CeilDiv(M, 256);
   h->partials_stride = std::max(std::max(h->num_partials, 4096), CeilDiv(4 * (int64_t)P, 256));      // (k_step_points: one partial per 64 points)
-  TRY(HandleAlloc(&h->partials, 2 * (size_t)h->partials_stride));     // K1's cost partials, then the model-cost partials
+  PP_TRY(B.Alloc(&h->partials, 2 * (size_t)h->partials_stride));     // K1's cost partials, then the model-cost partials
   // the int32 flag words live in the last scalar slot (+ one more double), so ONE copy of kNumScalars doubles reads back the
   // scalars and the failure flag
-  TRY(HandleAlloc(&h->scal, kNumScalars + 1));
+  PP_TRY(B.Alloc(&h->scal, kNumScalars + 1));
   h->d_flag = reinterpret_cast<int32_t*>(h->scal + kNumScalars - 1);
-  TRY(PoolPinnedAlloc(reinterpret_cast<void**>(&h->h_scal), sizeof(double) * 3 * kNumScalars));   // read-back + two evaluation slots
+  PP_TRY(B.AllocPinned(reinterpret_cast<void**>(&h->h_scal), sizeof(double) * 3 * kNumScalars));   // read-back + two evaluation slots
   std::memset(h->h_scal, 0, sizeof(double) * 3 * kNumScalars);     // the ticket slot starts at 0 = "no ticket"
   if (hipHostGetDevicePointer(reinterpret_cast<void**>(&h->h_scal_dev), h->h_scal, 0) != hipSuccess) { h->h_scal_dev = nullptr; (void)hipGetLastError(); }
-  TRYH(hipMemsetAsync(h->scal, 0, sizeof(double) * (kNumScalars + 1), s));
-
-  TRY(Upload(h->la, la.data(), M, s)); TRY(Upload(h->lb, lb.data(), M, s)); TRY(Upload(h->lc, lc.data(), M, s));
-  if (!arrays_on_device) { TRY(Upload(h->obs_pose, in_obs_pose, M, s)); TRY(Upload(h->obs_point, d->obs_point, M, s)); }
-  TRY(Upload(h->obs_cam, obs_cam.data(), M, s));
-  TRY(Upload(h->pose_camera, in_pose_camera, C, s)); TRY(Upload(h->camera_model, d->camera_model, K, s));
-  if (!arrays_on_device) { TRY(Upload(h->pose_const, pose_const.data(), C, s)); TRY(Upload(h->point_const, point_const.data(), P, s)); }
-  TRY(Upload(h->tvec_mask, tvec_mask.data(), C, s));
+  PP_HIP_TRY(hipMemsetAsync(h->scal, 0, sizeof(double) * (kNumScalars + 1), s));
   {  // effective parameters (tangent dimensions of the variable blocks): fixed with the masks, reported by every solve
     int neff = 0;
     for (int c = 0; c < C; ++c) if (!pose_const[c]) neff += 6 - __builtin_popcount(tvec_mask[c] & 7);
     for (int p = 0; p < P; ++p) if (!point_const[p]) neff += 3;
     h->num_effective_pose_point = neff;
   }
-  if (!arrays_on_device) { TRY(Upload(h->pt_start, pt_start.data(), P + 1, s)); TRY(Upload(h->pt_obs, pt_obs.data(), M, s)); }
-  TRY(Upload(h->pose_start, pose_start.data(), C + 1, s)); TRY(Upload(h->pose_obs, pose_obs.data(), M, s));
-  TRY(Upload(h->pair_start, pair_start.data(), pair_start.size(), s));
-  TRY(Upload(h->pair_ij, pair_ij.data(), pair_ij.size(), s));
-  if (!lists_on_device) TRY(Upload(h->pair_entries, pair_entries.data(), pair_entries.size(), s));
-  { std::vector<int32_t> np(K); for (int k = 0; k < K; ++k) np[k] = CameraNumParams(d->camera_model[k]); TRY(Upload(h->cam_np, np.data(), K, s)); TRYH(hipStreamSynchronize(s)); }
-  TRY(HandleAlloc(&h->spos, std::max<size_t>(h->spos_host.size(), 1))); TRY(Upload(h->spos, h->spos_host.data(), h->spos_host.size(), s));
-  TRY(Upload(h->intr_off, intr_off.data(), K, s)); TRY(Upload(h->intr_nv, intr_nv.data(), K, s)); TRY(Upload(h->intr_col, intr_col.data(), intr_col.size(), s));
-  if (NI > 0) {
-    TRY(Upload(h->cam_start, cam_start.data(), K + 1, s)); TRY(Upload(h->cam_obs, cam_obs.data(), M, s));
-    TRY(Upload(h->gen_pair, gen_pair.data(), gen_pair.size(), s)); TRY(Upload(h->gen_pair_chunk, gen_pair_chunk.data(), gen_pair_chunk.size(), s));
-    TRY(Upload(h->gen_chunk, gen_chunk.data(), gen_chunk.size(), s)); TRY(Upload(h->gen_entries, gen_entries.data(), gen_entries.size(), s));
-    TRY(Upload(h->gen_multi, gen_multi.data(), gen_multi.size(), s));
-    if (!iterative) { TRY(Upload(h->gen_grp_start, gen_grp_start.data(), gen_grp_start.size(), s)); TRY(Upload(h->gen_grp_obs, gen_grp_obs.data(), gen_grp_obs.size(), s)); }
-    TRY(Upload(h->isum_chunk, isum_chunk.data(), isum_chunk.size(), s)); TRY(Upload(h->isum_cam_chunk, isum_cam_chunk.data(), isum_cam_chunk.size(), s));
-  }
+  PP_TRY(B.Put(&h->spos, h->spos_host.data(), h->spos_host.size(), s, 1));
   if (want_chunks) {
-    TRY(HandleAlloc(&h->small_chunk, std::max<size_t>(small_chunk.size(), 3))); TRY(HandleAlloc(&h->small_pair_chunk, small_pair_chunk.size()));
-    TRY(HandleAlloc(&h->small_partials, 36 * std::max<size_t>((size_t)h->small_num_chunks, 1)));
-    TRY(Upload(h->small_chunk, small_chunk.data(), small_chunk.size(), s)); TRY(Upload(h->small_pair_chunk, small_pair_chunk.data(), small_pair_chunk.size(), s));
+    PP_TRY(B.Put(&h->small_chunk, small_chunk.data(), small_chunk.size(), s, 3)); PP_TRY(B.Put(&h->small_pair_chunk, small_pair_chunk.data(), small_pair_chunk.size(), s));
+    PP_TRY(B.Alloc(&h->small_partials, 36 * std::max<size_t>((size_t)h->small_num_chunks, 1)));
   }
-  TRYH(hipStreamSynchronize(s));  // host staging vectors die at scope exit
-#undef TRY
-#undef TRYH
+  PP_HIP_TRY(hipStreamSynchronize(s));  // host staging vectors die at scope exit
   {
     const auto t_create4 = std::chrono::steady_clock::now();
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -971,7 +927,7 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
     h->create_ms[0] = ordering_ms; h->create_ms[1] = ms(t_create0, t_create2) - ordering_ms; h->create_ms[2] = ms(t_create2, t_create3);
     h->create_ms[3] = ms(t_create3, t_create4); h->create_ms[4] = 0; h->create_ms[5] = ms(t_create0, t_create4);
   }
-  *out = h;
+  *out = guard.release();
   return PP_OK;
 } PP_API_CATCH("pp_ba_create")
 
@@ -1085,12 +1041,13 @@ int pp_ba_eval_host_view(pp_ba_handle h, int jac_mode, int want_cam, int want_ja
   int rc = BaEnsureJacobianBuffers(h, jac_mode, cam);
   if (rc) return rc;
   const size_t M = (size_t)h->M;
-  if (!h->pin_r) PP_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_r), sizeof(double) * 2 * M));
+  auto pin = [&](double** p, size_t doubles) { return *p ? PP_OK : h->mirrors.AllocPinned(reinterpret_cast<void**>(p), sizeof(double) * doubles); };
+  PP_TRY(pin(&h->pin_r, 2 * M));
   if (want_jacobians) {
-    if (h->pin_jpose && h->pin_width < width) { (void)hipHostFree(h->pin_jpose); h->pin_jpose = nullptr; }
-    if (!h->pin_jpose) { PP_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_jpose), sizeof(double) * width * M)); h->pin_width = width; }
-    if (!h->pin_jpoint) PP_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_jpoint), sizeof(double) * 6 * M));
-    if (cam && !h->pin_jcam) PP_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_jcam), sizeof(double) * 2 * kCamStride * M));
+    if (h->pin_jpose && h->pin_width < width) h->mirrors.Free(&h->pin_jpose);
+    if (!h->pin_jpose) { PP_TRY(pin(&h->pin_jpose, width * M)); h->pin_width = width; }
+    PP_TRY(pin(&h->pin_jpoint, 6 * M));
+    if (cam) PP_TRY(pin(&h->pin_jcam, 2 * kCamStride * M));
   }
   // a cost-only evaluation (Ceres asks for residuals without Jacobians at every trial point) runs K1's cost-only variant and
   // moves 16 B per observation instead of 220 B+

@@ -118,32 +118,24 @@ int pp_ba_filter_points(pp_ba_handle h, const pp_filter_options* o, const uint8_
   uint8_t *d_al = nullptr, *d_sub = nullptr, *d_od = nullptr, *d_pd = nullptr;
   int32_t* d_cs = nullptr;
   unsigned long long* d_cnt = nullptr;
-  int rc = PP_OK;
-  auto cleanup = [&]() { void* b[] = {err2, centers, perr, d_al, d_sub, d_od, d_pd, d_cs, d_cnt}; for (void* p : b) if (p) (void)hipFree(p); };
-  OnUnwind unwind{[&] { cleanup(); }};
-#define TRY(x) do { rc = (x); if (rc) { cleanup(); return rc; } } while (0)
-#define TRYH(x) do { if ((x) != hipSuccess) { SetLastError("pp_ba_filter_points: %s failed", #x); cleanup(); return PP_ERR_HIP; } } while (0)
-  TRY(DeviceAlloc(&err2, (size_t)M)); TRY(DeviceAlloc(&centers, (size_t)3 * C)); TRY(DeviceAlloc(&perr, (size_t)P));
-  TRY(DeviceAlloc(&d_al, (size_t)M)); TRY(DeviceAlloc(&d_od, (size_t)M)); TRY(DeviceAlloc(&d_pd, (size_t)P)); TRY(DeviceAlloc(&d_cs, (size_t)2 * K));
-  TRY(DeviceAlloc(&d_cnt, 2));
-  std::vector<uint8_t> al(M, 0);
+  std::vector<uint8_t> al(M, 0);      // (declared before the blocks: on an error return their release - of plain device memory, which waits for the device - comes before the staging vector goes)
   if (obs_aligned) al.assign(obs_aligned, obs_aligned + M);
-  TRY(Upload(d_al, al.data(), (size_t)M, s)); TRY(Upload(d_cs, cam_size, (size_t)2 * K, s));
-  if (point_subset) { TRY(DeviceAlloc(&d_sub, (size_t)P)); TRY(Upload(d_sub, point_subset, (size_t)P, s)); }
-  TRYH(hipMemsetAsync(d_od, 0, (size_t)M, s)); TRYH(hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), s));
+  DeviceBlocks scratch(false);
+  PP_TRY(scratch.Alloc(&err2, (size_t)M)); PP_TRY(scratch.Alloc(&centers, (size_t)3 * C)); PP_TRY(scratch.Alloc(&perr, (size_t)P));
+  PP_TRY(scratch.Put(&d_al, al.data(), (size_t)M, s)); PP_TRY(scratch.Alloc(&d_od, (size_t)M)); PP_TRY(scratch.Alloc(&d_pd, (size_t)P)); PP_TRY(scratch.Put(&d_cs, cam_size, (size_t)2 * K, s));
+  PP_TRY(scratch.Alloc(&d_cnt, 2));
+  if (point_subset) PP_TRY(scratch.Put(&d_sub, point_subset, (size_t)P, s));
+  PP_HIP_TRY(hipMemsetAsync(d_od, 0, (size_t)M, s)); PP_HIP_TRY(hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), s));
   hipLaunchKernelGGL(k_filter_obs, dim3(CeilDiv(M, 256)), dim3(256), 0, s, M, h->la, h->lb, h->lc, h->obs_pose, h->obs_point, h->obs_cam, h->poses, h->points, h->intr, d_cs,
                      err2, (uint8_t*)nullptr);
   hipLaunchKernelGGL(k_proj_centers, dim3(CeilDiv(C, 256)), dim3(256), 0, s, C, h->poses, centers);
   hipLaunchKernelGGL(k_filter_points, dim3(CeilDiv(P, 256)), dim3(256), 0, s, P, h->pt_start, h->pt_obs, h->obs_pose, d_al, err2, centers, h->points, d_sub,
                      o->max_reproj_error * o->max_reproj_error, o->min_tri_angle_deg * 3.14159265358979323846 / 180.0, d_od, d_pd, perr, d_cnt);
-  TRYH(hipGetLastError());
+  PP_HIP_TRY(hipGetLastError());
   unsigned long long cnt[2] = {0, 0};
-  TRY(Download(obs_deleted, d_od, (size_t)M, s)); TRY(Download(point_deleted, d_pd, (size_t)P, s)); TRY(Download(point_error, perr, (size_t)P, s));
-  TRY(Download(cnt, d_cnt, 2, s));
-  TRYH(hipStreamSynchronize(s));
-#undef TRY
-#undef TRYH
-  cleanup();
+  PP_TRY(Download(obs_deleted, d_od, (size_t)M, s)); PP_TRY(Download(point_deleted, d_pd, (size_t)P, s)); PP_TRY(Download(point_error, perr, (size_t)P, s));
+  PP_TRY(Download(cnt, d_cnt, 2, s));
+  PP_HIP_TRY(hipStreamSynchronize(s));
   rep->num_filtered = (int64_t)cnt[0];
   rep->num_points_deleted = (int64_t)cnt[1];
   rep->num_observations_deleted = 0;
@@ -155,14 +147,13 @@ int pp_ba_filter_negative_depth(pp_ba_handle h, uint8_t* obs_negative, int64_t* 
   PP_REQUIRE(h && obs_negative && num_filtered, "pp_ba_filter_negative_depth: null argument");
   PP_HIP_TRY(hipSetDevice(h->device));
   uint8_t* d = nullptr;
-  int rc = DeviceAlloc(&d, (size_t)h->M); if (rc) return rc;
+  DeviceBlocks scratch(false);
+  PP_TRY(scratch.Alloc(&d, (size_t)h->M));
   hipLaunchKernelGGL(k_filter_obs, dim3(CeilDiv(h->M, 256)), dim3(256), 0, h->stream, h->M, h->la, h->lb, h->lc, h->obs_pose, h->obs_point, h->obs_cam, h->poses, h->points,
                      h->intr, (const int32_t*)nullptr, (double*)nullptr, d);
-  if (hipGetLastError() != hipSuccess) { (void)hipFree(d); SetLastError("pp_ba_filter_negative_depth: launch failed"); return PP_ERR_HIP; }
-  rc = Download(obs_negative, d, (size_t)h->M, h->stream);
-  if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = PP_ERR_HIP;
-  (void)hipFree(d);
-  if (rc) return rc;
+  if (hipGetLastError() != hipSuccess) { SetLastError("pp_ba_filter_negative_depth: launch failed"); return PP_ERR_HIP; }
+  PP_TRY(Download(obs_negative, d, (size_t)h->M, h->stream));
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return PP_ERR_HIP;
   *num_filtered = 0;
   for (int64_t i = 0; i < h->M; ++i) *num_filtered += obs_negative[i];
   return PP_OK;

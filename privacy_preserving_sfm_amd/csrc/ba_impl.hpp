@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "resource_pool.hpp"
 #include "switches.hpp"
 
 namespace ppsfm {
@@ -52,8 +53,8 @@ int CountVariableIntrinsics(const pp_ba_problem_desc* d);
 // the Schur pair lists on the device (pair_lists.hip)
 bool PairListsOnDeviceEligible(int C, int64_t M, PairListsSwitch sw);
 int BuildPairListsOnDevice(int C, int64_t M, const int32_t* d_pt_start, const int32_t* d_pt_obs, const int32_t* d_obs_pose, const int32_t* d_obs_point,
-                           const uint8_t* d_pose_const, const uint8_t* d_point_const, hipStream_t s, int32_t** entries_out, int64_t* num_entries,
-                           std::vector<int32_t>* pair_start, std::vector<int32_t>* pair_ij, bool* fallback);
+                           const uint8_t* d_pose_const, const uint8_t* d_point_const, hipStream_t s, DeviceBlocks* owner, int32_t** entries_out,
+                           int64_t* num_entries, std::vector<int32_t>* pair_start, std::vector<int32_t>* pair_ij, bool* fallback);
 void BuildPairListsOnHost(int C, int P, int64_t M, const int32_t* pt_start, const int32_t* pt_obs, const int32_t* obs_pose, const uint8_t* list_const,
                           const uint8_t* point_const, int threads, const std::function<void(const char*)>& lap, int64_t* total_entries,
                           std::vector<int32_t>* pair_start, std::vector<int32_t>* pair_ij, std::vector<int32_t>* pair_entries);
@@ -74,6 +75,9 @@ struct pp_ba_impl {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // every device block and pooled pinned block behind the pointers below (pp_ba_destroy releases them; resource_pool.hpp), and the plain pinned mirrors
+  // of pp_ba_eval_host_view
+  ppsfm::DeviceBlocks blocks, mirrors{false};
 
   int32_t C = 0, P = 0, K = 0;
   int64_t M = 0;
@@ -255,7 +259,6 @@ bool BaInGroup(const pp_ba_impl* h);
 int BaGroupReduce(pp_ba_impl* h, double* ptr, int64_t count, int op);
 // matrix-free PCG on the implicit Schur complement (ba_pcg.hip)
 int PcgEnsureBuffers(pp_ba_impl* h);
-void PcgFreeBuffers(pp_ba_impl* h);
 int PcgSolve(pp_ba_impl* h, double radius, int max_iterations, double eta, int* iterations);
 // rho(s) and rho'(s) of the loss functions the reference uses (TrivialLoss, SoftLOneLoss, CauchyLoss; ceres/loss_function.cc as configured
 // in src/optim/bundle_adjustment.cc:260-271)

@@ -782,34 +782,23 @@ __global__ __launch_bounds__(kWideThreads) void k_pcg_step(int mode, int it, int
 int PcgEnsureBuffers(pp_ba_impl* h) {
   if (h->pcg_state) return PP_OK;
   const size_t n = (size_t)h->n_red;      // 6 C pose columns, then the NI variable intrinsics
-  int rc;
-#define A(ptr, cnt) if ((rc = HandleAlloc(&h->ptr, (size_t)(cnt)))) return rc
-  A(pcg_Sd, 36 * (size_t)h->C); A(pcg_binv, 18 * (size_t)h->C); A(pcg_b, n); A(pcg_r, n); A(pcg_z, n); A(pcg_p, 2 * n); A(pcg_q, n);      // (pcg_p: two copies, the fused direction update ping-pongs)
-  A(pcg_a, 3 * (size_t)h->P); A(pcg_dot, (size_t)h->C + (h->NI > 0 ? h->K : 0));
-  A(pcg_part, 4 * (size_t)(CeilDiv(2 * (int64_t)h->C, kWideThreads) + (h->NI > 0 ? CeilDiv(h->K, kWideThreads) : 0)));
-  if (h->NI > 0) { A(pcg_tk, 2 * (size_t)h->M); A(pcg_w, 2 * (size_t)h->M); A(pcg_Scomp, 12 * (size_t)h->NI); A(pcg_binvI, 12 * (size_t)h->NI); }
-  { const int rcp = PoolDeviceAlloc(reinterpret_cast<void**>(&h->pcg_state), 2 * sizeof(PcgState)); if (rcp) return rcp; }      // (two copies: the many-workgroup vector step ping-pongs)
-#undef A
-  { const int rcp = PoolPinnedAlloc(reinterpret_cast<void**>(&h->pcg_state_host), sizeof(PcgState)); if (rcp) return rcp; }
+  DeviceBlocks& B = h->blocks;
+  PP_TRY(B.Alloc(&h->pcg_Sd, 36 * (size_t)h->C)); PP_TRY(B.Alloc(&h->pcg_binv, 18 * (size_t)h->C)); PP_TRY(B.Alloc(&h->pcg_b, n)); PP_TRY(B.Alloc(&h->pcg_r, n)); PP_TRY(B.Alloc(&h->pcg_z, n));
+  PP_TRY(B.Alloc(&h->pcg_p, 2 * n)); PP_TRY(B.Alloc(&h->pcg_q, n));      // (pcg_p: two copies, the fused direction update ping-pongs)
+  PP_TRY(B.Alloc(&h->pcg_a, 3 * (size_t)h->P)); PP_TRY(B.Alloc(&h->pcg_dot, (size_t)h->C + (h->NI > 0 ? h->K : 0)));
+  PP_TRY(B.Alloc(&h->pcg_part, 4 * (size_t)(CeilDiv(2 * (int64_t)h->C, kWideThreads) + (h->NI > 0 ? CeilDiv(h->K, kWideThreads) : 0))));
+  if (h->NI > 0) { PP_TRY(B.Alloc(&h->pcg_tk, 2 * (size_t)h->M)); PP_TRY(B.Alloc(&h->pcg_w, 2 * (size_t)h->M)); PP_TRY(B.Alloc(&h->pcg_Scomp, 12 * (size_t)h->NI)); PP_TRY(B.Alloc(&h->pcg_binvI, 12 * (size_t)h->NI)); }
+  PP_TRY(B.Alloc(&h->pcg_state, 2));      // (two copies: the many-workgroup vector step ping-pongs)
+  PP_TRY(B.AllocPinned(reinterpret_cast<void**>(&h->pcg_state_host), sizeof(PcgState)));
   // the list entries with what they point at beside them (one dependent load less per product kernel)
-  { int rcp = PoolDeviceAlloc(reinterpret_cast<void**>(&h->pcg_pt_entry), std::max<size_t>(1, (size_t)h->M) * sizeof(int2)); if (rcp) return rcp;
-    rcp = PoolDeviceAlloc(reinterpret_cast<void**>(&h->pcg_pose_entry), std::max<size_t>(1, (size_t)h->M) * sizeof(int2)); if (rcp) return rcp; }
+  PP_TRY(B.Alloc(reinterpret_cast<int2**>(&h->pcg_pt_entry), std::max<size_t>(1, (size_t)h->M)));
+  PP_TRY(B.Alloc(reinterpret_cast<int2**>(&h->pcg_pose_entry), std::max<size_t>(1, (size_t)h->M)));
   if (h->M > 0) {
     hipLaunchKernelGGL(k_pcg_entries, dim3(CeilDiv(h->M, (int64_t)256)), dim3(256), 0, h->stream, h->M, h->pt_obs, h->obs_pose, h->pose_obs, h->obs_point,
                        reinterpret_cast<int2*>(h->pcg_pt_entry), reinterpret_cast<int2*>(h->pcg_pose_entry));
     PP_HIP_TRY(hipGetLastError());
   }
   return PP_OK;
-}
-
-void PcgFreeBuffers(pp_ba_impl* h) {
-  double** bufs[] = {&h->pcg_Sd, &h->pcg_binv, &h->pcg_b, &h->pcg_r, &h->pcg_z, &h->pcg_p, &h->pcg_q, &h->pcg_a, &h->pcg_dot, &h->pcg_part, &h->pcg_tk, &h->pcg_w, &h->pcg_Scomp, &h->pcg_binvI};
-  for (double** b : bufs) { if (*b) PoolDeviceFree(*b); *b = nullptr; }
-  if (h->pcg_state) PoolDeviceFree(h->pcg_state);
-  if (h->pcg_state_host) PoolPinnedFree(h->pcg_state_host);
-  if (h->pcg_pt_entry) PoolDeviceFree(h->pcg_pt_entry);
-  if (h->pcg_pose_entry) PoolDeviceFree(h->pcg_pose_entry);
-  h->pcg_state = nullptr; h->pcg_state_host = nullptr; h->pcg_pt_entry = nullptr; h->pcg_pose_entry = nullptr;
 }
 
 // S x = b for the system k_schur_self_rhs (compact) + k_prepare have set up for `radius`; x -> h->step_c (scaled space).

@@ -1214,7 +1214,7 @@ static int ApplyLinearSolverStructure(pp_ba_impl* h) {
   // current device is another one: the allocations below belong on the handle's device
   PP_HIP_TRY(hipSetDevice(h->device));
   std::lock_guard<std::recursive_mutex> setup_lock(DeviceSetupMutex());
-  if (!h->Lfac && CholeskyNeedsFactorArray(h->chol, h->N)) { const int rc = HandleAlloc(&h->Lfac, (size_t)h->N * h->N); if (rc) return rc; }
+  if (!h->Lfac && CholeskyNeedsFactorArray(h->chol, h->N)) PP_TRY(h->blocks.Alloc(&h->Lfac, (size_t)h->N * h->N));
   // (the solution comes out in the reduced system's column order: the vectors' order unless the intrinsics sit beside their images' pose columns)
   const CholeskySystem sys{h->S, h->N, h->n_red, h->Linv, h->Lfac, h->spos_identity ? h->step_c : h->step_s, h->d_flag, h->stream};
   bool new_map = false;
@@ -1229,25 +1229,24 @@ static int EnsureSolverBuffers(pp_ba_impl* h) {
   std::lock_guard<std::recursive_mutex> setup_lock(DeviceSetupMutex());      // (allocations: not beside another host thread's graph capture)
   const int C = h->C, P = h->P;
   h->N = ((h->n_red + 1 + 63) / 64) * 64;
-  int rc;
-#define A(ptr, n) if ((rc = HandleAlloc(&h->ptr, (size_t)(n)))) return rc
-  A(U, 36 * (size_t)C); A(gc, (size_t)h->n_red); A(V, 6 * (size_t)P); A(gp, 3 * (size_t)P); A(Vinv, 6 * (size_t)P); A(vb, 3 * (size_t)P);
-  A(scale_c, (size_t)h->n_red); A(scale_p, 3 * (size_t)P); A(diag_c, (size_t)h->n_red); A(diag_p, 3 * (size_t)P);
-  if (!h->iterative) { A(S, (size_t)h->N * h->N); A(Linv, CholeskyWorkspaceDoubles(h->N)); }
-  A(JpS, kRecStride * (size_t)h->M); A(norm_part, 3 * 256); A(step_c, (size_t)h->N); A(step_p, 3 * (size_t)P);
-  if (!h->spos_identity) { A(step_s, (size_t)h->N); }
-#undef A
-  for (int i = 0; i < 8; ++i) if ((rc = PoolEventAcquire(&h->tev[i], true))) return rc;
-  for (int i = 0; i < 2; ++i) if ((rc = PoolEventAcquire(&h->tev_eval[i], true))) return rc;
-  if ((rc = PoolEventAcquire(&h->ev_readback, false))) return rc;
+  DeviceBlocks& B = h->blocks;
+  const size_t n = (size_t)h->n_red, N = (size_t)h->N;
+  PP_TRY(B.Alloc(&h->U, 36 * (size_t)C)); PP_TRY(B.Alloc(&h->gc, n)); PP_TRY(B.Alloc(&h->V, 6 * (size_t)P)); PP_TRY(B.Alloc(&h->gp, 3 * (size_t)P));
+  PP_TRY(B.Alloc(&h->Vinv, 6 * (size_t)P)); PP_TRY(B.Alloc(&h->vb, 3 * (size_t)P));
+  PP_TRY(B.Alloc(&h->scale_c, n)); PP_TRY(B.Alloc(&h->scale_p, 3 * (size_t)P)); PP_TRY(B.Alloc(&h->diag_c, n)); PP_TRY(B.Alloc(&h->diag_p, 3 * (size_t)P));
+  if (!h->iterative) { PP_TRY(B.Alloc(&h->S, N * N)); PP_TRY(B.Alloc(&h->Linv, CholeskyWorkspaceDoubles(h->N))); }
+  PP_TRY(B.Alloc(&h->JpS, kRecStride * (size_t)h->M)); PP_TRY(B.Alloc(&h->norm_part, 3 * 256)); PP_TRY(B.Alloc(&h->step_c, N)); PP_TRY(B.Alloc(&h->step_p, 3 * (size_t)P));
+  if (!h->spos_identity) PP_TRY(B.Alloc(&h->step_s, N));
+  for (int i = 0; i < 8; ++i) PP_TRY(PoolEventAcquire(&h->tev[i], true));
+  for (int i = 0; i < 2; ++i) PP_TRY(PoolEventAcquire(&h->tev_eval[i], true));
+  PP_TRY(PoolEventAcquire(&h->ev_readback, false));
   if (h->iterative) return PcgEnsureBuffers(h);
   PP_HIP_TRY(hipMemsetAsync(h->S, 0, sizeof(double) * (size_t)h->N * h->N, h->stream));
   if (h->sparse_tiles) {      // the factorisation and the assembly skip the tiles that stay zero
     const int T = h->N / 64;
     std::vector<int32_t> list;
     for (int i = 0; i < T; ++i) for (int j = 0; j <= i; ++j) if (h->tile_nz[(size_t)i * T + j]) { list.push_back(i); list.push_back(j); }
-    if ((rc = HandleAlloc(&h->nz_tile_list, list.size()))) return rc;
-    PP_HIP_TRY(hipMemcpyAsync(h->nz_tile_list, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, h->stream));
+    PP_TRY(B.Put(&h->nz_tile_list, list.data(), list.size(), h->stream));
     PP_HIP_TRY(hipStreamSynchronize(h->stream));
   }
   return ApplyLinearSolverStructure(h);
@@ -1392,11 +1391,11 @@ static int LaunchNorms(pp_ba_impl* h, bool with_step, int fold = 0, double* host
 // the group exchange's packed copy of S holds at least `count` doubles (grown, never shrunk; the old content is not kept)
 static int EnsureSpack(pp_ba_impl* h, int64_t count) {
   if (h->Spack_cap >= count) return PP_OK;
-  if (h->Spack) PoolDeviceFree(h->Spack);
-  h->Spack = nullptr; h->Spack_cap = 0;
-  const int rc = HandleAlloc(&h->Spack, (size_t)count);
-  if (rc == PP_OK) h->Spack_cap = count;
-  return rc;
+  h->blocks.Free(&h->Spack);
+  h->Spack_cap = 0;
+  PP_TRY(h->blocks.Alloc(&h->Spack, (size_t)count));
+  h->Spack_cap = count;
+  return PP_OK;
 }
 
 // assemble the damped reduced system for `radius` into S (lower triangle + rhs row)
@@ -1781,7 +1780,7 @@ static int GroupAgreeOnRefusal(pp_ba_impl* h, int* bad, int* mismatch, pp_allred
   PP_HIP_TRY(hipSetDevice(h->device));
   const double hash = GroupStructureHash(h);
   double v[3] = {*bad ? 1.0 : 0.0, hash, -hash};
-  if (!h->attach_slot) { const int rc = HandleAlloc(&h->attach_slot, 4); if (rc) return rc; }      // (a slot of its own: nothing of a solve lives here)
+  if (!h->attach_slot) PP_TRY(h->blocks.Alloc(&h->attach_slot, 4));      // (a slot of its own: nothing of a solve lives here)
   double* slot = h->attach_slot;
   PP_HIP_TRY(hipMemcpyAsync(slot, v, sizeof(v), hipMemcpyHostToDevice, h->stream));
   PP_HIP_TRY(hipStreamSynchronize(h->stream));

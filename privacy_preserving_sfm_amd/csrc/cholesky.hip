@@ -2025,24 +2025,21 @@ extern "C" int pp_dense_cholesky_solve(int32_t n, const double* A, const double*
   for (int i = n + 1; i < N; ++i) h[(size_t)i * N + i] = 1.0;
   double *dS = nullptr, *dS0 = nullptr, *dLinv = nullptr, *dx = nullptr, *dL = nullptr;
   int32_t* dflag = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipStream_t strm = nullptr;
-  CholeskyState* st = nullptr;
-  int rc = PP_OK;
-  auto cleanup = [&]() {
-    CholeskyDestroy(st); st = nullptr;
-    if (strm) (void)hipStreamDestroy(strm);
-    if (dS) (void)hipFree(dS); if (dL) (void)hipFree(dL); if (dS0) (void)hipFree(dS0); if (dLinv) (void)hipFree(dLinv); if (dx) (void)hipFree(dx); if (dflag) (void)hipFree(dflag);
-    if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1);
-  };
-  OnUnwind unwind{[&] { cleanup(); }};
-#define TRYH(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { SetLastError("%s: %s", #expr, hipGetErrorString(e_)); cleanup(); return PP_ERR_HIP; } } while (0)
-  if ((rc = DeviceAlloc(&dS, (size_t)N * N)) || (rc = DeviceAlloc(&dS0, (size_t)N * N)) || (rc = DeviceAlloc(&dLinv, CholeskyWorkspaceDoubles(N))) ||
-      (rc = DeviceAlloc(&dx, (size_t)N)) || (rc = DeviceAlloc(&dflag, 4)) || (rc = DeviceAlloc(&dL, (size_t)N * N))) { cleanup(); return rc; }
-  TRYH(hipEventCreate(&e0)); TRYH(hipEventCreate(&e1));
-  TRYH(hipStreamCreateWithFlags(&strm, hipStreamNonBlocking));
+  DeviceBlocks scratch(false);      // (released last: after the factorisation's state and the stream it ran on)
+  struct Session {
+    CholeskyState* st = nullptr;
+    hipStream_t strm = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Session() { CholeskyDestroy(st); if (strm) (void)hipStreamDestroy(strm); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+  } ses;
+  PP_TRY(scratch.Alloc(&dS, (size_t)N * N)); PP_TRY(scratch.Alloc(&dS0, (size_t)N * N)); PP_TRY(scratch.Alloc(&dLinv, CholeskyWorkspaceDoubles(N)));
+  PP_TRY(scratch.Alloc(&dx, (size_t)N)); PP_TRY(scratch.Alloc(&dflag, 4)); PP_TRY(scratch.Alloc(&dL, (size_t)N * N));
+  PP_HIP_TRY(hipEventCreate(&ses.e0)); PP_HIP_TRY(hipEventCreate(&ses.e1));
+  PP_HIP_TRY(hipStreamCreateWithFlags(&ses.strm, hipStreamNonBlocking));
+  const hipEvent_t e0 = ses.e0, e1 = ses.e1;
+  const hipStream_t strm = ses.strm;
   const Switches sw = ReadSwitches();
-  st = CholeskyCreate(sw);
+  CholeskyState* const st = ses.st = CholeskyCreate(sw);
   // block-sparse input (PPSFM_CHOL_SPARSE=0 disables): tiles of the lower triangle that are entirely zero and stay zero in the
   // factor get no workgroup (the reference switches to SPARSE_SCHUR above 50 images, src/optim/bundle_adjustment.cc:275-286)
   std::vector<uint8_t> tile_nz;
@@ -2056,9 +2053,9 @@ extern "C" int pp_dense_cholesky_solve(int32_t n, const double* A, const double*
       if (SymbolicTileFill(T, tile_nz.data()) == T * (T + 1) / 2) tile_nz.clear();      // (nothing to skip: dense)
     }
   }
-  if ((rc = CholeskyBind(st, CholeskySystem{dS, N, n, dLinv, dL, dx, dflag, strm}, tile_nz.empty() ? nullptr : tile_nz.data()))) { cleanup(); return rc; }
-  TRYH(hipMemcpy(dS0, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
-  TRYH(hipMemset(dflag, 0, sizeof(int32_t) * 4));
+  PP_TRY(CholeskyBind(st, CholeskySystem{dS, N, n, dLinv, dL, dx, dflag, strm}, tile_nz.empty() ? nullptr : tile_nz.data()));
+  PP_HIP_TRY(hipMemcpy(dS0, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
+  PP_HIP_TRY(hipMemset(dflag, 0, sizeof(int32_t) * 4));
   // per-solve times; the MEDIAN is reported.  This entry point creates its stream (a new hardware queue), its buffers and the kernels'
   // scratch per call, and the first dispatches on a fresh queue now and then take tens of milliseconds (observed: the untimed warm-up at
   // 70 ms instead of ~2, flag clear, three times a timed solve at 62-69 ms in ~60 calls of five to ten solves; never in 4000 LM
@@ -2066,32 +2063,29 @@ extern "C" int pp_dense_cholesky_solve(int32_t n, const double* A, const double*
   std::vector<float> times;
   for (int it = -1; it < repeat; ++it) {   // it = -1: untimed warm-up (graph capture + instantiate)
     if (it == -1 && repeat == 1) continue;
-    TRYH(hipMemcpy(dS, dS0, sizeof(double) * h.size(), hipMemcpyDeviceToDevice));
-    TRYH(hipDeviceSynchronize());
-    TRYH(hipEventRecord(e0, strm));
-    rc = CholeskySolve(st);
-    if (rc) { cleanup(); return rc; }
-    TRYH(hipEventRecord(e1, strm));
-    TRYH(hipEventSynchronize(e1));
-    float ms = 0; TRYH(hipEventElapsedTime(&ms, e0, e1)); if (it >= 0) times.push_back(ms);
+    PP_HIP_TRY(hipMemcpy(dS, dS0, sizeof(double) * h.size(), hipMemcpyDeviceToDevice));
+    PP_HIP_TRY(hipDeviceSynchronize());
+    PP_HIP_TRY(hipEventRecord(e0, strm));
+    PP_TRY(CholeskySolve(st));
+    PP_HIP_TRY(hipEventRecord(e1, strm));
+    PP_HIP_TRY(hipEventSynchronize(e1));
+    float ms = 0; PP_HIP_TRY(hipEventElapsedTime(&ms, e0, e1)); if (it >= 0) times.push_back(ms);
     if (sw.chol_debug_slow && ms > 5.0f) {      // (how the outliers described at `times` were caught)
       int32_t f4[4] = {0, 0, 0, 0};
       (void)hipMemcpy(f4, dflag, sizeof(f4), hipMemcpyDeviceToHost);
       fprintf(stderr, "SLOW dense solve: n=%d it=%d ms=%.3f linear_solver=%d flag=%d %d %d %d\n", n, it, ms, CholeskyLinsolve(st), f4[0], f4[1], f4[2], f4[3]);
     }
     int32_t f = 0;
-    TRYH(hipMemcpy(&f, dflag, sizeof(f), hipMemcpyDeviceToHost));
+    PP_HIP_TRY(hipMemcpy(&f, dflag, sizeof(f), hipMemcpyDeviceToHost));
     if ((f & 4) && CholeskyFallBackToColumns(st)) {      // a bounded wait of the one-launch factorisation ran out: once more, with per-column launches from here on
-      TRYH(hipMemset(dflag, 0, sizeof(int32_t) * 4));
+      PP_HIP_TRY(hipMemset(dflag, 0, sizeof(int32_t) * 4));
       if (it >= 0) times.pop_back();
       --it;
     }
   }
   int32_t flag = 0;
-  TRYH(hipMemcpy(&flag, dflag, sizeof(flag), hipMemcpyDeviceToHost));
-  TRYH(hipMemcpy(x, dx, sizeof(double) * n, hipMemcpyDeviceToHost));
-#undef TRYH
-  cleanup();
+  PP_HIP_TRY(hipMemcpy(&flag, dflag, sizeof(flag), hipMemcpyDeviceToHost));
+  PP_HIP_TRY(hipMemcpy(x, dx, sizeof(double) * n, hipMemcpyDeviceToHost));
   if (ms_per_solve) {
     std::sort(times.begin(), times.end());
     const size_t m = times.size();

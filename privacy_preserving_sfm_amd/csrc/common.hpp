@@ -38,6 +38,9 @@ const char* LastError();
     }                                   \
   } while (0)
 
+// the one spelling of "return on a non-zero code"
+#define PP_TRY(x) do { if (int rc_ = (x)) return rc_; } while (0)
+
 // "never abort/throw across the boundary" (include/ppsfm_hip.h; the reference itself aborts through CHECK,
 // src/optim/bundle_adjustment.cc:261-262): every extern "C" entry point that can allocate is a function-try-block
 //     int pp_xxx(args) try { ... } PP_API_CATCH("pp_xxx")
@@ -45,15 +48,14 @@ const char* LastError();
 int ApiExceptionToCode(const char* where);      // called inside a catch (...) block: rethrows, classifies, sets pp_last_error(); never throws
 #define PP_API_CATCH(where) catch (...) { return ::ppsfm::ApiExceptionToCode(where); }
 
-// fn() when the scope is left by an EXCEPTION (a handle under construction, the scratch buffers of an entry point): the error
-// returns of the TRY macros clean up themselves, a throw from a std::vector in between would otherwise leak device memory.
-template <typename F>
-struct OnUnwind {
-  F fn;
-  int n = std::uncaught_exceptions();
-  ~OnUnwind() { if (std::uncaught_exceptions() > n) fn(); }
+// A handle under construction: destroyed on every way out of its create function - an error return or a throw - unless released to the caller.
+template <class H, int (*Destroy)(H*)>
+struct UnderConstruction {
+  H* h;
+  ~UnderConstruction() { if (h) (void)Destroy(h); }
+  H* operator->() const { return h; }
+  H* release() { H* out = h; h = nullptr; return out; }
 };
-template <typename F> OnUnwind(F) -> OnUnwind<F>;
 
 // body(t) for t = 0 .. nthreads - 1 on that many host threads (t = 0 on the caller's).  An exception inside a worker would end the
 // process (std::terminate); here every worker hands its exception to the caller, all threads are joined whatever happens - also
@@ -76,13 +78,6 @@ inline void ParallelFor(int nthreads, Body&& body) {
 constexpr int kWave = 64;          // gfx950 wavefront
 constexpr int kCamStride = 12;     // doubles per intrinsics block (max kNumParams of the 11 models)
 
-template <typename T>
-inline int DeviceAlloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) return PP_OK;
-  PP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
-  return PP_OK;
-}
 template <typename T>
 inline int Upload(T* dst, const T* src, size_t count, hipStream_t s) {
   if (count == 0) return PP_OK;

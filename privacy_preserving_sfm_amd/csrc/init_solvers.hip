@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "resource_pool.hpp"
 #include "p6l_device.hpp"   // Solve3, Det3x3
 #include "init_lsq.hpp"
 #include "small_eigen.hpp"
@@ -52,6 +53,7 @@ struct PlanarView {   // per-view constants
 }  // namespace ppsfm
 
 struct pp_planar_impl {
+  ppsfm::DeviceBlocks blocks{false};      // every device / pinned block of the handle (plain hipMalloc / hipHostMalloc)
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -69,6 +71,7 @@ struct pp_planar_impl {
 };
 
 struct pp_fourview2d_impl {
+  ppsfm::DeviceBlocks blocks{false};      // every device / pinned block of the handle (plain hipMalloc / hipHostMalloc)
   int device = 0;
   hipStream_t stream = nullptr;
   int32_t n = 0;
@@ -103,6 +106,7 @@ struct pp_fourview2d_impl {
 };
 
 struct pp_pose2d_impl {
+  ppsfm::DeviceBlocks blocks{false};      // every device / pinned block of the handle (plain hipMalloc / hipHostMalloc)
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -643,14 +647,10 @@ static double TreeMsacScore(const double* err, int n, double thr) {
 
 static int PlanarEnsure(pp_planar_impl* h, int64_t cap) {
   if (cap <= h->cap) return PP_OK;
-  void* old[] = {h->samples, h->offsets, h->scores, h->inl};
-  for (void* p : old) if (p) (void)hipFree(p);
-  h->samples = nullptr; h->offsets = nullptr; h->scores = nullptr; h->inl = nullptr; h->cap = 0;
-  int rc;
-  if ((rc = DeviceAlloc(&h->samples, (size_t)cap * 32))) return rc;
-  if ((rc = DeviceAlloc(&h->offsets, (size_t)cap * 3))) return rc;
-  if ((rc = DeviceAlloc(&h->scores, (size_t)cap))) return rc;
-  if ((rc = DeviceAlloc(&h->inl, (size_t)cap))) return rc;
+  DeviceBlocks& B = h->blocks;
+  B.Free(&h->samples); B.Free(&h->offsets); B.Free(&h->scores); B.Free(&h->inl);
+  h->cap = 0;
+  PP_TRY(B.Alloc(&h->samples, (size_t)cap * 32)); PP_TRY(B.Alloc(&h->offsets, (size_t)cap * 3)); PP_TRY(B.Alloc(&h->scores, (size_t)cap)); PP_TRY(B.Alloc(&h->inl, (size_t)cap));
   h->cap = cap;
   return PP_OK;
 }
@@ -912,15 +912,12 @@ static int LoMsacRun(const pp_lomsac_options* o, Backend& be, pp_lomsac_report* 
 
 static int Pose2dEnsure(pp_pose2d_impl* h, int64_t cap, int32_t m) {
   if (cap <= h->cap && m <= h->cap_m) return PP_OK;
-  void* old[] = {h->samples, h->poses, h->scores, h->inl};
-  for (void* p : old) if (p) (void)hipFree(p);
-  h->samples = nullptr; h->poses = nullptr; h->scores = nullptr; h->inl = nullptr;
+  DeviceBlocks& B = h->blocks;
+  B.Free(&h->samples); B.Free(&h->poses); B.Free(&h->scores); B.Free(&h->inl);
   const int64_t c = std::max(cap, h->cap);
   const int32_t mm = std::max(m, h->cap_m);
   h->cap = 0; h->cap_m = 0;
-  int rc;
-  if ((rc = DeviceAlloc(&h->samples, (size_t)c * mm)) || (rc = DeviceAlloc(&h->poses, (size_t)c * 6)) || (rc = DeviceAlloc(&h->scores, (size_t)c)) ||
-      (rc = DeviceAlloc(&h->inl, (size_t)c))) return rc;
+  PP_TRY(B.Alloc(&h->samples, (size_t)c * mm)); PP_TRY(B.Alloc(&h->poses, (size_t)c * 6)); PP_TRY(B.Alloc(&h->scores, (size_t)c)); PP_TRY(B.Alloc(&h->inl, (size_t)c));
   h->cap = c; h->cap_m = mm;
   return PP_OK;
 }
@@ -993,16 +990,14 @@ struct Pose2dBackend {
 // pool (-1: the points are the three-view triangulation of its cameras, what MinimalSolver produces).
 static int FourViewEnsureHyp(pp_fourview2d_impl* h, int64_t num, int32_t m) {
   if (num <= h->hyp_cap && m <= h->hyp_m) return PP_OK;
-  void* old[] = {h->samples, h->counts, h->best_index, h->models, h->mscores, h->best_cams, h->best_score, h->minl};
-  for (void* p : old) if (p) (void)hipFree(p);
-  h->samples = h->counts = h->best_index = h->minl = nullptr; h->models = h->mscores = h->best_cams = h->best_score = nullptr;
+  DeviceBlocks& B = h->blocks;
+  B.Free(&h->samples); B.Free(&h->counts); B.Free(&h->best_index); B.Free(&h->models); B.Free(&h->mscores); B.Free(&h->best_cams); B.Free(&h->best_score); B.Free(&h->minl);
   h->hyp_cap = 0; h->hyp_m = 0;
   const int64_t cap = std::max<int64_t>(num, h->hyp_cap);
   const int32_t mm = std::max(m, h->hyp_m);
-  int rc;
-  if ((rc = DeviceAlloc(&h->samples, (size_t)cap * mm)) || (rc = DeviceAlloc(&h->counts, (size_t)cap)) || (rc = DeviceAlloc(&h->best_index, (size_t)cap)) ||
-      (rc = DeviceAlloc(&h->models, (size_t)cap * 16 * 24)) || (rc = DeviceAlloc(&h->mscores, (size_t)cap * 16)) || (rc = DeviceAlloc(&h->minl, (size_t)cap * 16)) ||
-      (rc = DeviceAlloc(&h->best_cams, (size_t)cap * 24)) || (rc = DeviceAlloc(&h->best_score, (size_t)cap))) return rc;
+  PP_TRY(B.Alloc(&h->samples, (size_t)cap * mm)); PP_TRY(B.Alloc(&h->counts, (size_t)cap)); PP_TRY(B.Alloc(&h->best_index, (size_t)cap));
+  PP_TRY(B.Alloc(&h->models, (size_t)cap * 16 * 24)); PP_TRY(B.Alloc(&h->mscores, (size_t)cap * 16)); PP_TRY(B.Alloc(&h->minl, (size_t)cap * 16));
+  PP_TRY(B.Alloc(&h->best_cams, (size_t)cap * 24)); PP_TRY(B.Alloc(&h->best_score, (size_t)cap));
   h->hyp_cap = cap; h->hyp_m = mm;
   return PP_OK;
 }
@@ -1030,20 +1025,18 @@ static int FourViewPoolEnsure(pp_fourview2d_impl* h, int slots) {
   if (slots > h->pool_cap) {
     const int cap = std::max(256, std::max(slots, 2 * h->pool_cap));
     double *cams = nullptr, *scores = nullptr;
-    int rc;
-    if ((rc = DeviceAlloc(&cams, (size_t)cap * 24)) || (rc = DeviceAlloc(&scores, (size_t)cap))) { if (cams) (void)hipFree(cams); return rc; }
+    PP_TRY(h->blocks.Alloc(&cams, (size_t)cap * 24)); PP_TRY(h->blocks.Alloc(&scores, (size_t)cap));      // (the handle's from here on, whatever happens below)
     if (h->pool_used > 0) {
       PP_HIP_TRY(hipMemcpyAsync(cams, h->pool_cams, sizeof(double) * 24 * h->pool_used, hipMemcpyDeviceToDevice, h->stream));
       PP_HIP_TRY(hipMemcpyAsync(scores, h->pool_scores, sizeof(double) * h->pool_used, hipMemcpyDeviceToDevice, h->stream));
       PP_HIP_TRY(hipStreamSynchronize(h->stream));
     }
-    if (h->pool_cams) (void)hipFree(h->pool_cams);
-    if (h->pool_scores) (void)hipFree(h->pool_scores);
+    h->blocks.Free(&h->pool_cams); h->blocks.Free(&h->pool_scores);
     h->pool_cams = cams; h->pool_scores = scores; h->pool_cap = cap;
   }
   while ((int)h->pool_X.size() * kPoolChunk < slots) {
     double* chunk = nullptr;
-    const int rc = DeviceAlloc(&chunk, (size_t)kPoolChunk * 2 * h->n); if (rc) return rc;
+    PP_TRY(h->blocks.Alloc(&chunk, (size_t)kPoolChunk * 2 * h->n));
     h->pool_X.push_back(chunk);
   }
   if ((int)h->slot_refined.size() < slots) { h->slot_refined.resize(slots, 0); h->slot_has_X.resize(slots, 0); h->slot_scored.resize(slots, 0); }
@@ -1067,13 +1060,13 @@ struct FourView2dBackend {
   double* SlotX(int s) const { return h->pool_X[s / kPoolChunk] + (size_t)(s % kPoolChunk) * 2 * h->n; }
   int EnsureLsq() {
     if (h->lsq_scale) return PP_OK;
-    int r;
-    if ((r = DeviceAlloc(&h->lsq_scale, (size_t)6 * h->n))   // scale (2n) + observation ratios (4n): k_fv2d_points, the many-points fallback
-         || (r = DeviceAlloc(&h->lsq_Xc, (size_t)2 * h->n)) || (r = DeviceAlloc(&h->xch, kPointsSlotDoubles))   // the point kernels' exchange slots
-         || (r = DeviceAlloc(&h->d_iterations, 4))) return r;
+    DeviceBlocks& B = h->blocks;
+    PP_TRY(B.Alloc(&h->lsq_scale, (size_t)6 * h->n));   // scale (2n) + observation ratios (4n): k_fv2d_points, the many-points fallback
+    PP_TRY(B.Alloc(&h->lsq_Xc, (size_t)2 * h->n)); PP_TRY(B.Alloc(&h->xch, kPointsSlotDoubles));   // the point kernels' exchange slots
+    PP_TRY(B.Alloc(&h->d_iterations, 4));
     h->sample_cap = std::max<int64_t>(1024, h->n);
-    if ((r = DeviceAlloc(&h->d_sample, (size_t)kSampleRing * h->sample_cap))) return r;
-    if (hipHostMalloc(&h->pinned, sizeof(int32_t) * kSampleRing * h->sample_cap + sizeof(double) * ((size_t)h->n + 32 + 2), hipHostMallocDefault) != hipSuccess) { h->pinned = nullptr; return PP_ERR_HIP; }
+    PP_TRY(B.Alloc(&h->d_sample, (size_t)kSampleRing * h->sample_cap));
+    PP_TRY(B.AllocPinned(&h->pinned, sizeof(int32_t) * kSampleRing * h->sample_cap + sizeof(double) * ((size_t)h->n + 32 + 2)));
     if (hipHostGetDevicePointer(&h->pinned_dev, h->pinned, 0) != hipSuccess) { h->pinned_dev = nullptr; (void)hipGetLastError(); }
     *PinnedTicket() = 0;
     return FourViewPoolEnsure(h, 64);
@@ -1311,8 +1304,7 @@ void pp_lomsac_options_default(pp_lomsac_options* o) {
 int pp_planar_destroy(pp_planar_handle h) try {
   if (!h) return PP_OK;
   (void)hipSetDevice(h->device);
-  void* bufs[] = {h->rec, h->lines, h->samples, h->offsets, h->scores, h->err, h->X, h->inl, h->d_poses, h->d_Rg};
-  for (void* b : bufs) if (b) (void)hipFree(b);
+  h->blocks.Release();      // (plain device memory: freeing it waits for the device)
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1327,8 +1319,8 @@ int pp_planar_create(int32_t n, const double* poses, const double* lines, const 
   PP_HIP_TRY(hipGetDeviceCount(&ndev));
   PP_REQUIRE(device >= 0 && device < ndev, "pp_planar_create: device %d of %d", device, ndev);
   PP_HIP_TRY(hipSetDevice(device));
-  pp_planar_impl* h = new pp_planar_impl();
-  OnUnwind unwind{[&] { pp_planar_destroy(h); }};
+  std::vector<double> rec((size_t)n * kRec);      // (before the handle: on an error return the handle's release - of plain device memory, which waits for the device - comes first)
+  UnderConstruction<pp_planar_impl, pp_planar_destroy> h{new pp_planar_impl()};
   h->device = device; h->n = n;
   std::memcpy(h->poses, poses, sizeof(h->poses));
   std::memcpy(h->Rg, Rg, sizeof(h->Rg));
@@ -1345,7 +1337,6 @@ int pp_planar_create(int32_t n, const double* poses, const double* lines, const 
     h->view.c1[j] = (j > 0) ? G[3 + 2] : 0.0;    // d t_j(2) / d ty_j = Rg_j[1][2]
   }
   // per-track records
-  std::vector<double> rec((size_t)n * kRec);
   for (int i = 0; i < n; ++i) {
     double* r = &rec[(size_t)i * kRec];
     double A[12];
@@ -1370,19 +1361,13 @@ int pp_planar_create(int32_t n, const double* poses, const double* lines, const 
     inv[6] = inv[2]; inv[7] = inv[5]; inv[8] = (AtA[0] * AtA[4] - AtA[1] * AtA[3]) / det;
     for (int c = 0; c < 3; ++c) for (int j = 0; j < 4; ++j) r[4 * c + j] = inv[3 * c] * A[3 * j] + inv[3 * c + 1] * A[3 * j + 1] + inv[3 * c + 2] * A[3 * j + 2];
   }
-  int rc = PP_OK;
-#define TRY(x) do { rc = (x); if (rc) { pp_planar_destroy(h); return rc; } } while (0)
-#define TRYH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { SetLastError("%s: %s", #x, hipGetErrorString(e_)); pp_planar_destroy(h); return PP_ERR_HIP; } } while (0)
-  TRYH(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  TRYH(hipEventCreate(&h->ev0)); TRYH(hipEventCreate(&h->ev1));
-  TRY(DeviceAlloc(&h->rec, rec.size())); TRY(DeviceAlloc(&h->lines, (size_t)12 * n)); TRY(DeviceAlloc(&h->err, (size_t)n)); TRY(DeviceAlloc(&h->X, (size_t)3 * n));
-  TRY(DeviceAlloc(&h->d_poses, 48)); TRY(DeviceAlloc(&h->d_Rg, 36));
-  TRY(Upload(h->rec, rec.data(), rec.size(), h->stream)); TRY(Upload(h->lines, lines, (size_t)12 * n, h->stream));
-  TRY(Upload(h->d_poses, poses, 48, h->stream)); TRY(Upload(h->d_Rg, Rg, 36, h->stream));
-  TRYH(hipStreamSynchronize(h->stream));
-#undef TRY
-#undef TRYH
-  *out = h;
+  PP_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  PP_HIP_TRY(hipEventCreate(&h->ev0)); PP_HIP_TRY(hipEventCreate(&h->ev1));
+  DeviceBlocks& B = h->blocks;
+  PP_TRY(B.Put(&h->rec, rec.data(), rec.size(), h->stream)); PP_TRY(B.Put(&h->lines, lines, (size_t)12 * n, h->stream)); PP_TRY(B.Alloc(&h->err, (size_t)n)); PP_TRY(B.Alloc(&h->X, (size_t)3 * n));
+  PP_TRY(B.Put(&h->d_poses, poses, 48, h->stream)); PP_TRY(B.Put(&h->d_Rg, Rg, 36, h->stream));
+  PP_HIP_TRY(hipStreamSynchronize(h->stream));
+  *out = h.release();
   return PP_OK;
 } PP_API_CATCH("pp_planar_create")
 
@@ -1445,8 +1430,7 @@ int pp_planar_lomsac(pp_planar_handle h, const pp_lomsac_options* o, pp_lomsac_r
 int pp_pose2d_destroy(pp_pose2d_handle h) try {
   if (!h) return PP_OK;
   (void)hipSetDevice(h->device);
-  void* bufs[] = {h->x, h->X, h->samples, h->poses, h->scores, h->err, h->inl};
-  for (void* b : bufs) if (b) (void)hipFree(b);
+  h->blocks.Release();      // (plain device memory: freeing it waits for the device)
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1461,19 +1445,15 @@ int pp_pose2d_create(int32_t n, const double* x, const double* X, int device, pp
   PP_HIP_TRY(hipGetDeviceCount(&ndev));
   PP_REQUIRE(device >= 0 && device < ndev, "pp_pose2d_create: device %d of %d", device, ndev);
   PP_HIP_TRY(hipSetDevice(device));
-  pp_pose2d_impl* h = new pp_pose2d_impl();
-  OnUnwind unwind{[&] { pp_pose2d_destroy(h); }};
+  std::vector<double> xn(x, x + (size_t)2 * n);      // (before the handle: on an error return the handle's release - of plain device memory, which waits for the device - comes first)
+  UnderConstruction<pp_pose2d_impl, pp_pose2d_destroy> h{new pp_pose2d_impl()};
   h->device = device; h->n = n;
-  std::vector<double> xn(x, x + (size_t)2 * n);
   for (int i = 0; i < n; ++i) { const double nr = std::sqrt(xn[2 * i] * xn[2 * i] + xn[2 * i + 1] * xn[2 * i + 1]); xn[2 * i] /= nr; xn[2 * i + 1] /= nr; }   // sfm2d.h:104-109
-  int rc = PP_OK;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
-    SetLastError("pp_pose2d_create: stream/event creation failed"); pp_pose2d_destroy(h); return PP_ERR_HIP;
-  }
-  if ((rc = DeviceAlloc(&h->x, xn.size())) || (rc = DeviceAlloc(&h->X, (size_t)2 * n)) || (rc = DeviceAlloc(&h->err, (size_t)n)) ||
-      (rc = Upload(h->x, xn.data(), xn.size(), h->stream)) || (rc = Upload(h->X, X, (size_t)2 * n, h->stream))) { pp_pose2d_destroy(h); return rc; }
-  if (hipStreamSynchronize(h->stream) != hipSuccess) { pp_pose2d_destroy(h); return PP_ERR_HIP; }
-  *out = h;
+  PP_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  PP_HIP_TRY(hipEventCreate(&h->ev0)); PP_HIP_TRY(hipEventCreate(&h->ev1));
+  PP_TRY(h->blocks.Put(&h->x, xn.data(), xn.size(), h->stream)); PP_TRY(h->blocks.Put(&h->X, X, (size_t)2 * n, h->stream)); PP_TRY(h->blocks.Alloc(&h->err, (size_t)n));
+  PP_HIP_TRY(hipStreamSynchronize(h->stream));
+  *out = h.release();
   return PP_OK;
 } PP_API_CATCH("pp_pose2d_create")
 
@@ -1509,7 +1489,7 @@ int pp_pose2d_evaluate(pp_pose2d_handle h, const double* pose, double* errors) t
   PP_REQUIRE(h && pose && errors, "pp_pose2d_evaluate: bad argument");
   PP_HIP_TRY(hipSetDevice(h->device));
   int rc = Pose2dEnsure(h, 1, 3); if (rc) return rc;
-  if (!h->err && (rc = DeviceAlloc(&h->err, (size_t)h->n))) return rc;
+  if (!h->err) PP_TRY(h->blocks.Alloc(&h->err, (size_t)h->n));
   rc = Upload(h->poses, pose, 6, h->stream); if (rc) return rc;
   hipLaunchKernelGGL(k_pose2d_evaluate, dim3(CeilDiv(h->n, 256)), dim3(256), 0, h->stream, h->n, h->x, h->X, h->poses, h->err);
   PP_HIP_TRY(hipGetLastError());
@@ -1535,11 +1515,7 @@ int pp_pose2d_lomsac(pp_pose2d_handle h, const pp_lomsac_options* o, pp_lomsac_r
 int pp_fourview2d_destroy(pp_fourview2d_handle h) try {
   if (!h) return PP_OK;
   (void)hipSetDevice(h->device);
-  void* bufs[] = {h->x, h->cams, h->scores, h->err, h->X, h->inl, h->samples, h->counts, h->best_index, h->models, h->mscores, h->best_cams, h->best_score, h->minl,
-                  h->lsq_scale, h->lsq_Xc, h->xch, h->d_sample, h->d_iterations, h->pool_cams, h->pool_scores};
-  for (void* b : bufs) if (b) (void)hipFree(b);
-  for (double* p : h->pool_X) if (p) (void)hipFree(p);
-  if (h->pinned) (void)hipHostFree(h->pinned);
+  h->blocks.Release();      // (plain device memory: freeing it waits for the device)
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1554,20 +1530,15 @@ int pp_fourview2d_create(int32_t n, const double* x, int device, pp_fourview2d_h
   PP_HIP_TRY(hipGetDeviceCount(&ndev));
   PP_REQUIRE(device >= 0 && device < ndev, "pp_fourview2d_create: device %d of %d", device, ndev);
   PP_HIP_TRY(hipSetDevice(device));
-  pp_fourview2d_impl* h = new pp_fourview2d_impl();
-  OnUnwind unwind{[&] { pp_fourview2d_destroy(h); }};
+  std::vector<double> xn(x, x + (size_t)8 * n);      // (before the handle: on an error return the handle's release - of plain device memory, which waits for the device - comes first)
+  UnderConstruction<pp_fourview2d_impl, pp_fourview2d_destroy> h{new pp_fourview2d_impl()};
   h->device = device; h->n = n;
-  std::vector<double> xn(x, x + (size_t)8 * n);
   for (size_t i = 0; i < (size_t)4 * n; ++i) { const double nr = std::sqrt(xn[2 * i] * xn[2 * i] + xn[2 * i + 1] * xn[2 * i + 1]); xn[2 * i] /= nr; xn[2 * i + 1] /= nr; }   // sfm2d.h:62-67
-  int rc = PP_OK;
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev1);
-  if (e != hipSuccess) { SetLastError("hipStreamCreate: %s", hipGetErrorString(e)); pp_fourview2d_destroy(h); return PP_ERR_HIP; }
-  if ((rc = DeviceAlloc(&h->x, xn.size())) || (rc = DeviceAlloc(&h->err, (size_t)n)) || (rc = DeviceAlloc(&h->X, (size_t)2 * n)) ||
-      (rc = Upload(h->x, xn.data(), xn.size(), h->stream))) { pp_fourview2d_destroy(h); return rc; }
-  if (hipStreamSynchronize(h->stream) != hipSuccess) { pp_fourview2d_destroy(h); return PP_ERR_HIP; }
-  *out = h;
+  PP_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  PP_HIP_TRY(hipEventCreate(&h->ev0)); PP_HIP_TRY(hipEventCreate(&h->ev1));
+  PP_TRY(h->blocks.Put(&h->x, xn.data(), xn.size(), h->stream)); PP_TRY(h->blocks.Alloc(&h->err, (size_t)n)); PP_TRY(h->blocks.Alloc(&h->X, (size_t)2 * n));
+  PP_HIP_TRY(hipStreamSynchronize(h->stream));
+  *out = h.release();
   return PP_OK;
 } PP_API_CATCH("pp_fourview2d_create")
 
@@ -1576,11 +1547,10 @@ int pp_fourview2d_score(pp_fourview2d_handle h, int32_t num, const double* cams,
   if (num == 0) return PP_OK;
   PP_HIP_TRY(hipSetDevice(h->device));
   if (num > h->cap) {
-    void* old[] = {h->cams, h->scores, h->inl};
-    for (void* p : old) if (p) (void)hipFree(p);
-    h->cams = nullptr; h->scores = nullptr; h->inl = nullptr; h->cap = 0;
-    int rc;
-    if ((rc = DeviceAlloc(&h->cams, (size_t)num * 24)) || (rc = DeviceAlloc(&h->scores, (size_t)num)) || (rc = DeviceAlloc(&h->inl, (size_t)num))) return rc;
+    DeviceBlocks& B = h->blocks;
+    B.Free(&h->cams); B.Free(&h->scores); B.Free(&h->inl);
+    h->cap = 0;
+    PP_TRY(B.Alloc(&h->cams, (size_t)num * 24)); PP_TRY(B.Alloc(&h->scores, (size_t)num)); PP_TRY(B.Alloc(&h->inl, (size_t)num));
     h->cap = num;
   }
   int rc = Upload(h->cams, cams, (size_t)num * 24, h->stream); if (rc) return rc;
@@ -1596,8 +1566,7 @@ int pp_fourview2d_evaluate(pp_fourview2d_handle h, const double* cams, double* e
   PP_REQUIRE(h && cams && errors, "pp_fourview2d_evaluate: bad argument");
   PP_HIP_TRY(hipSetDevice(h->device));
   if (h->cap < 1) {
-    int rc;
-    if ((rc = DeviceAlloc(&h->cams, 24)) || (rc = DeviceAlloc(&h->scores, 1)) || (rc = DeviceAlloc(&h->inl, 1))) return rc;
+    PP_TRY(h->blocks.Alloc(&h->cams, 24)); PP_TRY(h->blocks.Alloc(&h->scores, 1)); PP_TRY(h->blocks.Alloc(&h->inl, 1));
     h->cap = 1;
   }
   int rc = Upload(h->cams, cams, 24, h->stream); if (rc) return rc;
@@ -1614,8 +1583,7 @@ int pp_fourview2d_evaluate_points(pp_fourview2d_handle h, const double* cams, co
   PP_REQUIRE(h && cams && X && errors, "pp_fourview2d_evaluate_points: bad argument");
   PP_HIP_TRY(hipSetDevice(h->device));
   if (h->cap < 1) {
-    int rc;
-    if ((rc = DeviceAlloc(&h->cams, 24)) || (rc = DeviceAlloc(&h->scores, 1)) || (rc = DeviceAlloc(&h->inl, 1))) return rc;
+    PP_TRY(h->blocks.Alloc(&h->cams, 24)); PP_TRY(h->blocks.Alloc(&h->scores, 1)); PP_TRY(h->blocks.Alloc(&h->inl, 1));
     h->cap = 1;
   }
   int rc = Upload(h->cams, cams, 24, h->stream); if (rc) return rc;

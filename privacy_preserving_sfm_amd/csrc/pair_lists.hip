@@ -180,46 +180,40 @@ int CoVisibilityOnDevice(int C, int64_t M, const int32_t* d_pt_start, const int3
                          const uint8_t* d_pose_const, const uint8_t* d_point_const, hipStream_t s, std::vector<uint64_t>* bits) {
   const int64_t K = (int64_t)C * C;
   const int W = (C + 63) / 64;
-  void *q_pose = nullptr, *q_count = nullptr, *q_bits = nullptr;
-  int rc;
-  if ((rc = PoolDeviceAlloc(&q_pose, sizeof(int32_t) * (size_t)M)) || (rc = PoolDeviceAlloc(&q_count, sizeof(int32_t) * (size_t)K)) ||
-      (rc = PoolDeviceAlloc(&q_bits, sizeof(uint64_t) * (size_t)C * W))) { PoolDeviceFree(q_pose); PoolDeviceFree(q_count); PoolDeviceFree(q_bits); return rc; }
-  int32_t* pt_pose = (int32_t*)q_pose; int32_t* count = (int32_t*)q_count;
+  DeviceBlocks scratch;      // (every way out below has waited for the stream or failed on it)
+  int32_t *pt_pose = nullptr, *count = nullptr;
+  unsigned long long* q_bits = nullptr;
+  PP_TRY(scratch.Alloc(&pt_pose, (size_t)M)); PP_TRY(scratch.Alloc(&count, (size_t)K)); PP_TRY(scratch.Alloc(&q_bits, (size_t)C * W));
   bits->resize((size_t)C * W);
   const dim3 gm((unsigned)((M + 255) / 256));
   hipError_t e = hipMemsetAsync(count, 0, sizeof(int32_t) * K, s);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_pl_images, gm, dim3(256), 0, s, M, d_pt_obs, d_obs_pose, d_obs_point, d_pose_const, d_point_const, pt_pose);
     hipLaunchKernelGGL(k_pl_walk<false>, gm, dim3(256), 0, s, M, C, d_pt_start, d_pt_obs, d_obs_point, (const int32_t*)pt_pose, count, (const int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
-    hipLaunchKernelGGL(k_pl_bits, dim3((unsigned)(((int64_t)C * W + 3) / 4)), dim3(256), 0, s, C, W, (const int32_t*)count, (unsigned long long*)q_bits);
+    hipLaunchKernelGGL(k_pl_bits, dim3((unsigned)(((int64_t)C * W + 3) / 4)), dim3(256), 0, s, C, W, (const int32_t*)count, q_bits);
     e = hipMemcpyAsync(bits->data(), q_bits, sizeof(uint64_t) * (size_t)C * W, hipMemcpyDeviceToHost, s);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e == hipSuccess) e = hipGetLastError();
-  PoolDeviceFree(q_pose); PoolDeviceFree(q_count); PoolDeviceFree(q_bits);
   if (e != hipSuccess) { SetLastError("co-visibility on the device: %s", hipGetErrorString(e)); return PP_ERR_HIP; }
   return PP_OK;
 }
 
-// d_* : the problem's device arrays (internal image order).  On success: *entries_out (pool block: 2 x *num_entries ints, or null when there is none),
+// d_* : the problem's device arrays (internal image order).  On success: *entries_out (a block of `owner`: 2 x *num_entries ints, or null when there is none),
 // pair_start (lists + 1) / pair_ij (2 x lists) on the host.  PP_ERR_INVALID with *fallback = true: a list longer than kMaxSortedList - the caller takes the host builder.
 int BuildPairListsOnDevice(int C, int64_t M, const int32_t* d_pt_start, const int32_t* d_pt_obs, const int32_t* d_obs_pose, const int32_t* d_obs_point,
-                           const uint8_t* d_pose_const, const uint8_t* d_point_const, hipStream_t s, int32_t** entries_out, int64_t* num_entries,
-                           std::vector<int32_t>* pair_start, std::vector<int32_t>* pair_ij, bool* fallback) {
+                           const uint8_t* d_pose_const, const uint8_t* d_point_const, hipStream_t s, DeviceBlocks* owner, int32_t** entries_out,
+                           int64_t* num_entries, std::vector<int32_t>* pair_start, std::vector<int32_t>* pair_ij, bool* fallback) {
   *entries_out = nullptr; *num_entries = 0; *fallback = false;
   const int64_t K = (int64_t)C * C;
-  void* blocks[12] = {nullptr};
-  int nb = 0;
-  auto alloc = [&](size_t ints, int32_t** p) { void* q = nullptr; const int rc = PoolDeviceAlloc(&q, ints * sizeof(int32_t)); if (!rc) { blocks[nb++] = q; *p = (int32_t*)q; } return rc; };
-  auto release = [&]() { for (int i = 0; i < nb; ++i) PoolDeviceFree(blocks[i]); nb = 0; };
+  DeviceBlocks scratch;      // the call's own blocks; the sorted lists are `owner`'s from the moment they exist
   int32_t *pt_pose, *count, *fill, *start, *flag, *small;
-  int rc;
-  if ((rc = alloc((size_t)M, &pt_pose)) || (rc = alloc((size_t)K, &count)) || (rc = alloc((size_t)K, &fill)) || (rc = alloc((size_t)K + 1, &start)) || (rc = alloc((size_t)K, &flag)) ||
-      (rc = alloc(kScanThreads + 8, &small))) { release(); return rc; }
+  PP_TRY(scratch.Alloc(&pt_pose, (size_t)M)); PP_TRY(scratch.Alloc(&count, (size_t)K)); PP_TRY(scratch.Alloc(&fill, (size_t)K)); PP_TRY(scratch.Alloc(&start, (size_t)K + 1));
+  PP_TRY(scratch.Alloc(&flag, (size_t)K)); PP_TRY(scratch.Alloc(&small, kScanThreads + 8));
   ScanScratch sc{small, small + kScanThreads};
   int32_t* d_max = small + kScanThreads + 1;
   int32_t* d_lists = small + kScanThreads + 2;
-  auto fail = [&](hipError_t e) { release(); SetLastError("pair lists on the device: %s", hipGetErrorString(e)); return PP_ERR_HIP; };
+  auto fail = [&](hipError_t e) { SetLastError("pair lists on the device: %s", hipGetErrorString(e)); return PP_ERR_HIP; };
   hipError_t e;
   if ((e = hipMemsetAsync(count, 0, sizeof(int32_t) * K, s)) != hipSuccess) return fail(e);
   if ((e = hipMemsetAsync(fill, 0, sizeof(int32_t) * K, s)) != hipSuccess) return fail(e);
@@ -234,13 +228,13 @@ int BuildPairListsOnDevice(int C, int64_t M, const int32_t* d_pt_start, const in
   if ((e = hipMemcpyAsync(&host2[1], d_max, sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e);
   const int64_t E = host2[0];
-  if (host2[1] > kMaxSortedList) { release(); *fallback = true; return PP_ERR_INVALID; }
+  if (host2[1] > kMaxSortedList) { *fallback = true; return PP_ERR_INVALID; }
   pair_start->assign(1, 0); pair_ij->clear();
-  if (E == 0) { release(); return PP_OK; }
-  int32_t* entries = nullptr;      // the sorted lists (the caller's); the lists in arrival order and the list of every entry: scratch
+  if (E == 0) return PP_OK;
+  int32_t* entries = nullptr;      // the sorted lists (the owner's); the lists in arrival order and the list of every entry: scratch
   int32_t *arrival = nullptr, *entry_key = nullptr;
-  { void* q = nullptr; if ((rc = PoolDeviceAlloc(&q, sizeof(int32_t) * 2 * (size_t)E))) { release(); return rc; } entries = (int32_t*)q; }
-  if ((rc = alloc(2 * (size_t)E, &arrival)) || (rc = alloc((size_t)E, &entry_key))) { PoolDeviceFree(entries); release(); return rc; }
+  PP_TRY(owner->Alloc(&entries, 2 * (size_t)E));
+  PP_TRY(scratch.Alloc(&arrival, 2 * (size_t)E)); PP_TRY(scratch.Alloc(&entry_key, (size_t)E));
   hipLaunchKernelGGL(k_pl_walk<true>, gm, dim3(256), 0, s, M, C, d_pt_start, d_pt_obs, d_obs_point, (const int32_t*)pt_pose, fill, (const int32_t*)start, arrival, entry_key);
   hipLaunchKernelGGL(k_pl_rank, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, E, (const int32_t*)entry_key, (const int32_t*)count, (const int32_t*)start,
                      (const long long*)arrival, (long long*)entries);
@@ -249,17 +243,16 @@ int BuildPairListsOnDevice(int C, int64_t M, const int32_t* d_pt_start, const in
   ScanScratch sc2{small, d_lists};
   ExclusiveScan(flag, fill, K, sc2, s);
   int32_t lists = 0;
-  if ((e = hipMemcpyAsync(&lists, d_lists, sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) { PoolDeviceFree(entries); return fail(e); }
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) { PoolDeviceFree(entries); return fail(e); }
+  if ((e = hipMemcpyAsync(&lists, d_lists, sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e);
   int32_t *d_pstart = nullptr, *d_pij = nullptr;
-  if ((rc = alloc((size_t)lists + 1, &d_pstart)) || (rc = alloc(2 * (size_t)lists + 2, &d_pij))) { PoolDeviceFree(entries); release(); return rc; }
+  PP_TRY(scratch.Alloc(&d_pstart, (size_t)lists + 1)); PP_TRY(scratch.Alloc(&d_pij, 2 * (size_t)lists + 2));
   hipLaunchKernelGGL(k_pl_heads, gk, dim3(256), 0, s, K, C, (const int32_t*)flag, (const int32_t*)fill, (const int32_t*)start, d_pstart, d_pij);
   pair_start->resize((size_t)lists + 1); pair_ij->resize(2 * (size_t)lists);
   if ((e = hipMemcpyAsync(pair_start->data(), d_pstart, sizeof(int32_t) * lists, hipMemcpyDeviceToHost, s)) != hipSuccess ||
       (e = hipMemcpyAsync(pair_ij->data(), d_pij, sizeof(int32_t) * 2 * lists, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-      (e = hipStreamSynchronize(s)) != hipSuccess || (e = hipGetLastError()) != hipSuccess) { PoolDeviceFree(entries); return fail(e); }
+      (e = hipStreamSynchronize(s)) != hipSuccess || (e = hipGetLastError()) != hipSuccess) return fail(e);
   (*pair_start)[(size_t)lists] = (int32_t)E;
-  release();
   *entries_out = entries; *num_entries = E;
   return PP_OK;
 }

@@ -2,6 +2,7 @@
 #include "resource_pool.hpp"
 #include "switches.hpp"
 
+#include <cassert>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -195,6 +196,43 @@ void PoolTrim() {
   for (void* p : pinned) (void)hipHostFree(p);
 }
 
+int DeviceBlocks::AllocBytes(void** p, size_t bytes, bool pinned) {
+  *p = nullptr;
+  if (bytes == 0) return PP_OK;
+  if (blocks_.empty()) blocks_.reserve(128);      // (a bundle-adjustment handle holds about a hundred)
+  if (pooled_) PP_TRY(pinned ? PoolPinnedAlloc(p, bytes) : PoolDeviceAlloc(p, bytes));
+  else if (pinned) PP_HIP_TRY(hipHostMalloc(p, bytes));
+  else PP_HIP_TRY(hipMalloc(p, bytes));
+  blocks_.push_back(Block{*p, pinned});
+  return PP_OK;
+}
+
+void DeviceBlocks::FreeBlock(void* p) {
+  if (!p) return;
+  size_t i = 0;
+  while (i < blocks_.size() && blocks_[i].p != p) ++i;
+#if defined(__SANITIZE_ADDRESS__) || __has_feature(address_sanitizer)
+  assert(i < blocks_.size() && "DeviceBlocks::Free: not a block of this owner");
+#endif
+  if (i == blocks_.size()) return;
+  const bool pinned = blocks_[i].pinned;
+  blocks_.erase(blocks_.begin() + (std::ptrdiff_t)i);
+  if (pinned) PoolPinnedFree(p); else PoolDeviceFree(p);      // (a pointer the pool does not know: hipHostFree / hipFree)
+}
+
+void DeviceBlocks::Release() {
+  for (const Block& b : blocks_) { if (b.pinned) PoolPinnedFree(b.p); else PoolDeviceFree(b.p); }
+  blocks_.clear();
+}
+
 }  // namespace ppsfm
 
+extern "C" int pp_pool_stats(int64_t* live_device_blocks, int64_t* live_pinned_blocks, int64_t* cached_device_bytes) try {
+  ppsfm::Pool& pool = ppsfm::P();
+  std::lock_guard<std::mutex> lock(pool.mu);
+  if (live_device_blocks) *live_device_blocks = (int64_t)pool.live.size();
+  if (live_pinned_blocks) *live_pinned_blocks = (int64_t)pool.live_pinned.size();
+  if (cached_device_bytes) { size_t sum = 0; for (const auto& kv : pool.cached_bytes) sum += kv.second; *cached_device_bytes = (int64_t)sum; }
+  return PP_OK;
+} PP_API_CATCH("pp_pool_stats")
 extern "C" int pp_pool_trim(void) try { ppsfm::PoolTrim(); return PP_OK; } PP_API_CATCH("pp_pool_trim")

@@ -21,11 +21,34 @@ int PoolEventAcquire(hipEvent_t* e, bool timing);
 void PoolEventRelease(hipEvent_t e, bool timing);
 void PoolTrim();                                  // frees everything cached (tests; pp_pool_trim)
 
-template <typename T>
-inline int HandleAlloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) return PP_OK;
-  return PoolDeviceAlloc(reinterpret_cast<void**>(p), count * sizeof(T));
-}
+// The device and pinned blocks of one owner - a handle, or one call's scratch: what Alloc / Put / AllocPinned hand out is recorded and goes back in
+// Release() (the destructor), so "allocated" means "owned" and no destroy function lists buffers.  pooled = false: plain hipMalloc / hipHostMalloc
+// (memory the pool never sees; freeing it waits for the device).  The owner NEVER synchronises: the rule above holds - whoever owns it drains its stream
+// before it lets the owner release anything.
+class DeviceBlocks {
+ public:
+  explicit DeviceBlocks(bool pooled = true) : pooled_(pooled) {}
+  DeviceBlocks(const DeviceBlocks&) = delete;
+  DeviceBlocks& operator=(const DeviceBlocks&) = delete;
+  ~DeviceBlocks() { Release(); }
+  // count == 0: *p = nullptr, PP_OK, nothing recorded; nothing is recorded on failure either
+  template <class T> int Alloc(T** p, size_t count) { return AllocBytes(reinterpret_cast<void**>(p), count * sizeof(T), false); }
+  // max(count, min_count) elements, the first `count` of them uploaded from src (when not null) on `s`
+  template <class T> int Put(T** p, const T* src, size_t count, hipStream_t s, size_t min_count = 0) {
+    PP_TRY(Alloc(p, count > min_count ? count : min_count));
+    return src ? Upload(*p, src, count, s) : PP_OK;
+  }
+  int AllocPinned(void** p, size_t bytes) { return AllocBytes(p, bytes, true); }
+  // one block back early (a buffer that is regrown); *p = nullptr.  A pointer this owner does not hold is a programming error.
+  template <class T> void Free(T** p) { FreeBlock(*p); *p = nullptr; }
+  void Release();      // everything, in allocation order
+
+ private:
+  int AllocBytes(void** p, size_t bytes, bool pinned);
+  void FreeBlock(void* p);
+  struct Block { void* p; bool pinned; };
+  std::vector<Block> blocks_;
+  bool pooled_;
+};
 
 }  // namespace ppsfm

@@ -153,8 +153,7 @@ int pp_tracks_destroy(pp_tracks_handle h) try {
   if (!h) return PP_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : h->blocks) PoolDeviceFree(p);
-  PoolPinnedFree(h->pin);
+  h->blocks.Release();
   PoolEventRelease(h->ev0, true); PoolEventRelease(h->ev1, true);
   PoolStreamRelease(h->stream);
   delete h;
@@ -199,10 +198,7 @@ int pp_tracks_create(const pp_tracks_desc* d, int device, pp_tracks_handle* out)
   PP_HIP_TRY(hipGetDeviceCount(&ndev));
   PP_REQUIRE(device >= 0 && device < ndev, "pp_tracks_create: device %d of %d", device, ndev);
   PP_HIP_TRY(hipSetDevice(device));
-  pp_tracks_impl* h = new pp_tracks_impl();
-  OnUnwind unwind{[&] { (void)pp_tracks_destroy(h); }};
-  int rc = PP_OK;
-#define TRYC(x) do { rc = (x); if (rc) { (void)pp_tracks_destroy(h); return rc; } } while (0)
+  UnderConstruction<pp_tracks_impl, pp_tracks_destroy> h{new pp_tracks_impl()};
   h->device = device; h->C = C; h->K = K; h->L = L; h->E = E;
   TrackState& st = h->st;
   st.L = L;
@@ -220,38 +216,30 @@ int pp_tracks_create(const pp_tracks_desc* d, int device, pp_tracks_handle* out)
   if (d->camera_skip) skip.assign(d->camera_skip, d->camera_skip + K);
   h->image_skip.resize((size_t)C);
   for (int c = 0; c < C; ++c) h->image_skip[(size_t)c] = skip[(size_t)d->pose_camera[c]];
-  TRYC(PoolStreamAcquire(&h->stream));
-  TRYC(PoolEventAcquire(&h->ev0, true)); TRYC(PoolEventAcquire(&h->ev1, true));
+  PP_TRY(PoolStreamAcquire(&h->stream));
+  PP_TRY(PoolEventAcquire(&h->ev0, true)); PP_TRY(PoolEventAcquire(&h->ev1, true));
   hipStream_t s = h->stream;
-  auto put = [&](auto** p, const auto* src, size_t count) {
-    void* q = nullptr;
-    int r = PoolDeviceAlloc(&q, std::max<size_t>(count, 1) * sizeof(**p));
-    if (r) return r;
-    h->blocks.push_back(q);
-    *p = (std::remove_reference_t<decltype(*p)>)q;
-    return src ? Upload(*p, src, count, s) : PP_OK;
-  };
+  auto put = [&](auto** p, const auto* src, size_t count) { return h->blocks.Put(p, src, count, s, 1); };
   double *d_poses = nullptr, *d_proj = nullptr, *d_intr = nullptr, *d_lines = nullptr;
   int32_t *d_pc = nullptr, *d_cm = nullptr, *d_cs = nullptr, *d_li = nullptr, *d_c0 = nullptr, *d_cl = nullptr;
   uint8_t *d_skip = nullptr, *d_reg = nullptr;
-  TRYC(put(&d_poses, d->poses, (size_t)7 * C)); TRYC(put(&d_proj, (const double*)nullptr, (size_t)12 * C)); TRYC(put(&d_intr, d->intr, (size_t)kCamStride * K));
-  TRYC(put(&d_lines, d->lines, (size_t)3 * L)); TRYC(put(&d_pc, d->pose_camera, (size_t)C)); TRYC(put(&d_cm, d->camera_model, (size_t)K));
-  TRYC(put(&d_cs, d->cam_size, (size_t)2 * K)); TRYC(put(&d_li, d->line_image, (size_t)L)); TRYC(put(&d_c0, d->corr_start, (size_t)L + 1));
-  TRYC(put(&d_cl, d->corr_line, (size_t)E)); TRYC(put(&d_skip, skip.data(), (size_t)K)); TRYC(put(&d_reg, st.image_registered.data(), (size_t)C));
-  TRYC(put(&h->d_line_point, (const int32_t*)nullptr, (size_t)L));
+  PP_TRY(put(&d_poses, d->poses, (size_t)7 * C)); PP_TRY(put(&d_proj, (const double*)nullptr, (size_t)12 * C)); PP_TRY(put(&d_intr, d->intr, (size_t)kCamStride * K));
+  PP_TRY(put(&d_lines, d->lines, (size_t)3 * L)); PP_TRY(put(&d_pc, d->pose_camera, (size_t)C)); PP_TRY(put(&d_cm, d->camera_model, (size_t)K));
+  PP_TRY(put(&d_cs, d->cam_size, (size_t)2 * K)); PP_TRY(put(&d_li, d->line_image, (size_t)L)); PP_TRY(put(&d_c0, d->corr_start, (size_t)L + 1));
+  PP_TRY(put(&d_cl, d->corr_line, (size_t)E)); PP_TRY(put(&d_skip, skip.data(), (size_t)K)); PP_TRY(put(&d_reg, st.image_registered.data(), (size_t)C));
+  PP_TRY(put(&h->d_line_point, (const int32_t*)nullptr, (size_t)L));
   hipLaunchKernelGGL(k_tracks_proj, dim3(CeilDiv(C, 256)), dim3(256), 0, s, C, d_poses, d_proj);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { SetLastError("pp_tracks_create: upload failed"); (void)pp_tracks_destroy(h); return PP_ERR_HIP; }
-#undef TRYC
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { SetLastError("pp_tracks_create: upload failed"); return PP_ERR_HIP; }
   h->dev.proj = d_proj; h->dev.intr = d_intr; h->dev.lines = d_lines; h->dev.pose_camera = d_pc; h->dev.camera_model = d_cm; h->dev.cam_size = d_cs;
   h->dev.line_image = d_li; h->dev.corr_start = d_c0; h->dev.corr_line = d_cl; h->dev.camera_skip = d_skip; h->dev.image_registered = d_reg;
-  *out = h;
+  *out = h.release();
   return PP_OK;
 } PP_API_CATCH("pp_tracks_create")
 
 int pp_tracks_complete(pp_tracks_handle h, const pp_tracks_options* o, const uint8_t* point_subset, pp_tracks_report* report, int32_t* added_point,
                        int32_t* added_line, int64_t capacity) try {
   PP_REQUIRE(h && report && capacity >= 0 && (capacity == 0 || (added_point && added_line)), "pp_tracks_complete: bad argument");
-  TR(CheckOptions(o, "pp_tracks_complete"));
+  PP_TRY(CheckOptions(o, "pp_tracks_complete"));
   const auto t_begin = Clock::now();
   std::memset(report, 0, sizeof(*report));
   PP_HIP_TRY(hipSetDevice(h->device));
@@ -259,7 +247,7 @@ int pp_tracks_complete(pp_tracks_handle h, const pp_tracks_options* o, const uin
   const int P = st.NumPoints();
   if (P == 0) return PP_OK;
   CompleteSpec spec;
-  TR(SpeculateComplete(h, point_subset, o->complete_max_transitivity, o->complete_max_reproj_error * o->complete_max_reproj_error, "pp_tracks_complete", &spec));
+  PP_TRY(SpeculateComplete(h, point_subset, o->complete_max_transitivity, o->complete_max_reproj_error * o->complete_max_reproj_error, "pp_tracks_complete", &spec));
   report->overflow_points = spec.overflow_points; report->second_launches = spec.second_launches;
   report->device_ms = spec.device_ms;
   report->candidates_evaluated = (int64_t)spec.counters[1];
@@ -279,7 +267,7 @@ int pp_tracks_complete(pp_tracks_handle h, const pp_tracks_options* o, const uin
 int pp_tracks_merge(pp_tracks_handle h, const pp_tracks_options* o, const uint8_t* point_subset, pp_tracks_report* report, int32_t* merged_a,
                     int32_t* merged_b, int32_t* merged_new, int64_t capacity) try {
   PP_REQUIRE(h && report && capacity >= 0 && (capacity == 0 || (merged_a && merged_b && merged_new)), "pp_tracks_merge: bad argument");
-  TR(CheckOptions(o, "pp_tracks_merge"));
+  PP_TRY(CheckOptions(o, "pp_tracks_merge"));
   const auto t_begin = Clock::now();
   std::memset(report, 0, sizeof(*report));
   PP_HIP_TRY(hipSetDevice(h->device));
@@ -294,27 +282,27 @@ int pp_tracks_merge(pp_tracks_handle h, const pp_tracks_options* o, const uint8_
   unsigned long long counters[2] = {0, 0};
   TrackDev d;
   CallBlocks cb(s);      // (the state arrays stay up for the fresh-pair launches)
-  TR(UploadState(h, cb, point_subset, start, elems, &d));
+  PP_TRY(UploadState(h, cb, point_subset, start, elems, &d));
   {
     MergeArgs a{};
     a.max2 = max2;
     a.pool_cap = (unsigned long long)(h->E + 1);      // a line has one point: the candidate lists together hold at most one entry per correspondence
-    TR(cb.Alloc(&a.pool_cand, (size_t)a.pool_cap)); TR(cb.Alloc(&a.pool_ok, (size_t)a.pool_cap)); TR(cb.Alloc(&a.counters, 2));
-    TR(cb.Alloc(&a.out_start, (size_t)P0)); TR(cb.Alloc(&a.out_count, (size_t)P0)); TR(cb.Alloc(&a.overflow, (size_t)P0));
+    PP_TRY(cb.Alloc(&a.pool_cand, (size_t)a.pool_cap)); PP_TRY(cb.Alloc(&a.pool_ok, (size_t)a.pool_cap)); PP_TRY(cb.Alloc(&a.counters, 2));
+    PP_TRY(cb.Alloc(&a.out_start, (size_t)P0)); PP_TRY(cb.Alloc(&a.out_count, (size_t)P0)); PP_TRY(cb.Alloc(&a.overflow, (size_t)P0));
     PP_HIP_TRY(hipMemsetAsync(a.counters, 0, 2 * sizeof(unsigned long long), s));
     PP_HIP_TRY(hipEventRecord(h->ev0, s));
     hipLaunchKernelGGL(k_merge_candidates, dim3(P0), dim3(64), 0, s, d, a);
     PP_HIP_TRY(hipGetLastError());
     PP_HIP_TRY(hipEventRecord(h->ev1, s));
-    TR(Download(count.data(), a.out_count, (size_t)P0, s)); TR(Download(seg.data(), a.out_start, (size_t)P0, s)); TR(Download(over.data(), a.overflow, (size_t)P0, s));
-    TR(Download(counters, a.counters, 2, s));
+    PP_TRY(Download(count.data(), a.out_count, (size_t)P0, s)); PP_TRY(Download(seg.data(), a.out_start, (size_t)P0, s)); PP_TRY(Download(over.data(), a.overflow, (size_t)P0, s));
+    PP_TRY(Download(counters, a.counters, 2, s));
     PP_HIP_TRY(hipStreamSynchronize(s));
     float ms = 0.f;
     PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     report->device_ms = ms;
     const size_t used = (size_t)std::min<unsigned long long>(counters[0], a.pool_cap);
     pool_cand.resize(used); pool_ok.resize(used);
-    TR(Download(pool_cand.data(), a.pool_cand, used, s)); TR(Download(pool_ok.data(), a.pool_ok, used, s));
+    PP_TRY(Download(pool_cand.data(), a.pool_cand, used, s)); PP_TRY(Download(pool_ok.data(), a.pool_ok, used, s));
     PP_HIP_TRY(hipStreamSynchronize(s));
   }
   for (int p = 0; p < P0; ++p) report->overflow_points += over[(size_t)p];
@@ -324,10 +312,9 @@ int pp_tracks_merge(pp_tracks_handle h, const pp_tracks_options* o, const uint8_
     const std::vector<int32_t>&ta = st.tracks[(size_t)a], &tb = st.tracks[(size_t)q];
     const size_t need = 2 + ta.size() + tb.size();
     if (need > h->pin_ints) {
-      PoolPinnedFree(h->pin); h->pin = nullptr; h->pin_ints = 0;
-      void* q2 = nullptr;
-      if (PoolPinnedAlloc(&q2, std::max<size_t>(need * 2, 1024) * sizeof(int32_t))) return PP_ERR_HIP;
-      h->pin = (int32_t*)q2; h->pin_ints = std::max<size_t>(need * 2, 1024);
+      h->blocks.Free(&h->pin); h->pin_ints = 0;
+      if (h->blocks.AllocPinned(reinterpret_cast<void**>(&h->pin), std::max<size_t>(need * 2, 1024) * sizeof(int32_t))) return PP_ERR_HIP;
+      h->pin_ints = std::max<size_t>(need * 2, 1024);
     }
     h->pin[0] = -1; h->pin[1] = 0;
     std::copy(ta.begin(), ta.end(), h->pin + 2);

@@ -155,7 +155,7 @@ struct pp_tracks_impl {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   ppsfm::TrackState st;
   std::vector<uint8_t> image_skip;      // per image: its camera is flagged in camera_skip
-  std::vector<void*> blocks;      // the static device arrays (pool blocks)
+  ppsfm::DeviceBlocks blocks;     // the static device arrays and the pinned slots (pool blocks)
   ppsfm::TrackDev dev{};
   int32_t* d_line_point = nullptr;
   double* d_centers = nullptr;    // C x 3 projection centres (K11b's triangulation-angle test)
@@ -168,28 +168,15 @@ namespace ppsfm {
 using Clock = std::chrono::steady_clock;
 inline double MsSince(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
-// pool blocks of one call, returned after the stream has drained on every way out
+// pool blocks of one call (at least one element each), returned after the stream has drained on every way out (`b` is destroyed after the body)
 struct CallBlocks {
   hipStream_t s;
-  std::vector<void*> b;
+  DeviceBlocks b;
   explicit CallBlocks(hipStream_t stream) : s(stream) {}
-  ~CallBlocks() { (void)hipStreamSynchronize(s); for (void* p : b) PoolDeviceFree(p); }
-  template <typename T>
-  int Alloc(T** p, size_t count) {
-    void* q = nullptr;
-    const int rc = PoolDeviceAlloc(&q, std::max<size_t>(count, 1) * sizeof(T));
-    if (!rc) { b.push_back(q); *p = (T*)q; }
-    return rc;
-  }
-  template <typename T>
-  int Put(T** p, const T* src, size_t count) {
-    int rc = Alloc(p, count);
-    if (!rc) rc = Upload(*p, src, count, s);
-    return rc;
-  }
+  ~CallBlocks() { (void)hipStreamSynchronize(s); }
+  template <typename T> int Alloc(T** p, size_t count) { return b.Alloc(p, std::max<size_t>(count, 1)); }
+  template <typename T> int Put(T** p, const T* src, size_t count) { return b.Put(p, src, count, s, 1); }
 };
-
-#define TR(x) do { const int _rc = (x); if (_rc) return _rc; } while (0)
 
 // uploads the state at the start of a call; flat track CSR in start / elems (kept alive by the caller until the stream drains)
 inline int UploadState(pp_tracks_impl* h, CallBlocks& cb, const uint8_t* subset, std::vector<int32_t>& start, std::vector<int32_t>& elems, TrackDev* d) {
@@ -202,15 +189,15 @@ inline int UploadState(pp_tracks_impl* h, CallBlocks& cb, const uint8_t* subset,
   for (int p = 0; p < P; ++p) std::copy(st.tracks[(size_t)p].begin(), st.tracks[(size_t)p].end(), elems.begin() + start[(size_t)p]);
   *d = h->dev;
   d->P = P;
-  TR(Upload(h->d_line_point, st.line_point.data(), (size_t)h->L, h->stream));
+  PP_TRY(Upload(h->d_line_point, st.line_point.data(), (size_t)h->L, h->stream));
   d->line_point = h->d_line_point;
   int32_t *d_start = nullptr, *d_elems = nullptr;
   double* d_points = nullptr;
   uint8_t* d_subset = nullptr;
-  TR(cb.Put(&d_start, start.data(), start.size()));
-  TR(cb.Put(&d_elems, elems.data(), elems.size()));
-  TR(cb.Put(&d_points, st.points.data(), st.points.size()));
-  if (subset) TR(cb.Put(&d_subset, subset, (size_t)P));
+  PP_TRY(cb.Put(&d_start, start.data(), start.size()));
+  PP_TRY(cb.Put(&d_elems, elems.data(), elems.size()));
+  PP_TRY(cb.Put(&d_points, st.points.data(), st.points.size()));
+  if (subset) PP_TRY(cb.Put(&d_subset, subset, (size_t)P));
   d->track_start = d_start; d->track_line = d_elems; d->points = d_points; d->subset = d_subset;
   return PP_OK;
 }
@@ -245,26 +232,26 @@ inline int SpeculateComplete(pp_tracks_impl* h, const uint8_t* point_subset, int
   {
     CallBlocks cb(s);
     TrackDev d;
-    TR(UploadState(h, cb, point_subset, start, elems, &d));
+    PP_TRY(UploadState(h, cb, point_subset, start, elems, &d));
     CompleteArgs a{};
     a.num_work = P; a.max_transitivity = max_transitivity; a.max2 = max2;
     a.pool_cap = (unsigned long long)(2 * h->E + 1024);
-    TR(cb.Alloc(&a.pool_line, (size_t)a.pool_cap)); TR(cb.Alloc(&a.pool_level, (size_t)a.pool_cap)); TR(cb.Alloc(&a.counters, 2));
-    TR(cb.Alloc(&a.out_start, (size_t)P)); TR(cb.Alloc(&a.out_count, (size_t)P)); TR(cb.Alloc(&a.overflow, (size_t)P));
+    PP_TRY(cb.Alloc(&a.pool_line, (size_t)a.pool_cap)); PP_TRY(cb.Alloc(&a.pool_level, (size_t)a.pool_cap)); PP_TRY(cb.Alloc(&a.counters, 2));
+    PP_TRY(cb.Alloc(&a.out_start, (size_t)P)); PP_TRY(cb.Alloc(&a.out_count, (size_t)P)); PP_TRY(cb.Alloc(&a.overflow, (size_t)P));
     PP_HIP_TRY(hipMemsetAsync(a.counters, 0, 2 * sizeof(unsigned long long), s));
     PP_HIP_TRY(hipEventRecord(h->ev0, s));
     hipLaunchKernelGGL(k_complete_tracks<false>, dim3(P), dim3(64), 0, s, d, a);
     PP_HIP_TRY(hipGetLastError());
     PP_HIP_TRY(hipEventRecord(h->ev1, s));
-    TR(Download(count.data(), a.out_count, (size_t)P, s)); TR(Download(seg.data(), a.out_start, (size_t)P, s)); TR(Download(over.data(), a.overflow, (size_t)P, s));
-    TR(Download(counters, a.counters, 2, s));
+    PP_TRY(Download(count.data(), a.out_count, (size_t)P, s)); PP_TRY(Download(seg.data(), a.out_start, (size_t)P, s)); PP_TRY(Download(over.data(), a.overflow, (size_t)P, s));
+    PP_TRY(Download(counters, a.counters, 2, s));
     PP_HIP_TRY(hipStreamSynchronize(s));
     float ms = 0.f;
     PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     ms_total += ms;
     const size_t used = (size_t)std::min<unsigned long long>(counters[0], a.pool_cap);
     pool_line.resize(used);
-    TR(Download(pool_line.data(), a.pool_line, used, s));
+    PP_TRY(Download(pool_line.data(), a.pool_line, used, s));
     PP_HIP_TRY(hipStreamSynchronize(s));
     // the flagged points: a list in global memory that cannot overflow (a closure holds free lines only, each once)
     std::vector<int32_t> work;
@@ -275,19 +262,19 @@ inline int SpeculateComplete(pp_tracks_impl* h, const uint8_t* point_subset, int
       gcap = std::max<int64_t>(gcap, 1);
       const size_t batch = (size_t)std::max<int64_t>(1, std::min<int64_t>((int64_t)work.size(), (int64_t)(32 << 20) / gcap));
       int32_t *d_work = nullptr, *d_cnt = nullptr;
-      TR(cb.Alloc(&a.glist_line, batch * (size_t)gcap)); TR(cb.Alloc(&a.glist_level, batch * (size_t)gcap));
-      TR(cb.Alloc(&d_work, batch)); TR(cb.Alloc(&d_cnt, batch));
+      PP_TRY(cb.Alloc(&a.glist_line, batch * (size_t)gcap)); PP_TRY(cb.Alloc(&a.glist_level, batch * (size_t)gcap));
+      PP_TRY(cb.Alloc(&d_work, batch)); PP_TRY(cb.Alloc(&d_cnt, batch));
       a.gcap = gcap;
       std::vector<int32_t> cnt2(batch), rows;
       for (size_t b0 = 0; b0 < work.size(); b0 += batch) {
         const size_t nb = std::min(batch, work.size() - b0);
-        TR(Upload(d_work, work.data() + b0, nb, s));
+        PP_TRY(Upload(d_work, work.data() + b0, nb, s));
         a.num_work = (int)nb; a.work = d_work; a.out_count = d_cnt;
         PP_HIP_TRY(hipEventRecord(h->ev0, s));
         hipLaunchKernelGGL(k_complete_tracks<true>, dim3((unsigned)nb), dim3(64), 0, s, d, a);
         PP_HIP_TRY(hipGetLastError());
         PP_HIP_TRY(hipEventRecord(h->ev1, s));
-        TR(Download(cnt2.data(), d_cnt, nb, s));
+        PP_TRY(Download(cnt2.data(), d_cnt, nb, s));
         PP_HIP_TRY(hipStreamSynchronize(s));
         PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
         ms_total += ms;
@@ -295,13 +282,13 @@ inline int SpeculateComplete(pp_tracks_impl* h, const uint8_t* point_subset, int
         for (size_t i = 0; i < nb; ++i) {
           if (cnt2[i] < 0 || cnt2[i] > gcap) { SetLastError("%s: the closure of point %d outgrew every free line", where, work[b0 + i]); return PP_ERR_INTERNAL; }
           rows.resize((size_t)cnt2[i]);
-          TR(Download(rows.data(), a.glist_line + i * (size_t)gcap, (size_t)cnt2[i], s));
+          PP_TRY(Download(rows.data(), a.glist_line + i * (size_t)gcap, (size_t)cnt2[i], s));
           PP_HIP_TRY(hipStreamSynchronize(s));
           second_of[(size_t)work[b0 + i]] = (int32_t)second.size();
           second.push_back(rows);
         }
       }
-      TR(Download(counters, a.counters, 2, s));
+      PP_TRY(Download(counters, a.counters, 2, s));
       PP_HIP_TRY(hipStreamSynchronize(s));
       out->overflow_points = (int32_t)work.size();
     }

@@ -279,16 +279,13 @@ struct ImageCall {
   int Begin() {
     const TrackState& st = h->st;
     if (!h->d_centers) {
-      void* q = nullptr;
-      TR(PoolDeviceAlloc(&q, std::max<size_t>((size_t)3 * h->C, 1) * sizeof(double)));
-      h->blocks.push_back(q);
-      hipLaunchKernelGGL(k_image_centers, dim3(CeilDiv(h->C, 256)), dim3(256), 0, s, h->C, h->dev.proj, (double*)q);
+      PP_TRY(h->blocks.Alloc(&h->d_centers, std::max<size_t>((size_t)3 * h->C, 1)));
+      hipLaunchKernelGGL(k_image_centers, dim3(CeilDiv(h->C, 256)), dim3(256), 0, s, h->C, h->dev.proj, h->d_centers);
       PP_HIP_TRY(hipGetLastError());
-      h->d_centers = (double*)q;
     }
     points_cap = (size_t)st.NumPoints() + (size_t)h->L / 3 + 1;      // every new point takes at least three free lines
-    TR(cb.Alloc(&d_points, 3 * points_cap));
-    if (aligned) TR(cb.Put(&d_aligned, aligned, (size_t)h->L));
+    PP_TRY(cb.Alloc(&d_points, 3 * points_cap));
+    if (aligned) PP_TRY(cb.Put(&d_aligned, aligned, (size_t)h->L));
     d = h->dev;
     d.P = st.NumPoints();
     d.line_point = h->d_line_point;
@@ -300,8 +297,8 @@ struct ImageCall {
     const TrackState& st = h->st;
     const size_t P = (size_t)st.NumPoints();
     PP_REQUIRE(P <= points_cap, "pp_tracks: more new points than free lines allow");
-    TR(Upload(h->d_line_point, st.line_point.data(), (size_t)h->L, s));
-    if (P > points_up) TR(Upload(d_points + 3 * points_up, st.points.data() + 3 * points_up, 3 * (P - points_up), s));
+    PP_TRY(Upload(h->d_line_point, st.line_point.data(), (size_t)h->L, s));
+    if (P > points_up) PP_TRY(Upload(d_points + 3 * points_up, st.points.data() + 3 * points_up, 3 * (P - points_up), s));
     points_up = P;
     d.P = (int)P;
     return PP_OK;
@@ -327,11 +324,11 @@ struct ImageCall {
     a.num_work = (int)W; a.transitivity = transitivity; a.continue_max = kDegToRad * o->continue_max_angle_error;
     a.pool_cap = (unsigned long long)(transitivity == 1 ? direct : direct + 2 * h->E + 1024);      // exact for the direct lists; a closure that finds the pool full goes to the second launch
     int32_t* d_work = nullptr;
-    TR(lb.Put(&d_work, work.data(), W));
+    PP_TRY(lb.Put(&d_work, work.data(), W));
     a.work_line = d_work;
-    TR(lb.Alloc(&a.pool_list, (size_t)a.pool_cap)); TR(lb.Alloc(&a.pool_set, (size_t)a.pool_cap)); TR(lb.Alloc(&a.cursor, 1));
-    TR(lb.Alloc(&a.out_start, W)); TR(lb.Alloc(&a.out_count, W)); TR(lb.Alloc(&a.out_set_count, W)); TR(lb.Alloc(&a.out_num_tri, W));
-    TR(lb.Alloc(&a.out_cont_point, W)); TR(lb.Alloc(&a.overflow, W));
+    PP_TRY(lb.Alloc(&a.pool_list, (size_t)a.pool_cap)); PP_TRY(lb.Alloc(&a.pool_set, (size_t)a.pool_cap)); PP_TRY(lb.Alloc(&a.cursor, 1));
+    PP_TRY(lb.Alloc(&a.out_start, W)); PP_TRY(lb.Alloc(&a.out_count, W)); PP_TRY(lb.Alloc(&a.out_set_count, W)); PP_TRY(lb.Alloc(&a.out_num_tri, W));
+    PP_TRY(lb.Alloc(&a.out_cont_point, W)); PP_TRY(lb.Alloc(&a.overflow, W));
     PP_HIP_TRY(hipMemsetAsync(a.cursor, 0, sizeof(unsigned long long), s));
     PP_HIP_TRY(hipEventRecord(h->ev0, s));
     hipLaunchKernelGGL(k_image_find<false>, dim3((unsigned)W), dim3(64), 0, s, d, a);
@@ -343,17 +340,17 @@ struct ImageCall {
     std::vector<uint8_t> over(W);
     unsigned long long cursor = 0;
     auto fetch = [&](size_t nw) {
-      TR(Download(seg.data(), a.out_start, nw, s)); TR(Download(count.data(), a.out_count, nw, s)); TR(Download(set_count.data(), a.out_set_count, nw, s));
-      TR(Download(num_tri.data(), a.out_num_tri, nw, s)); TR(Download(cont.data(), a.out_cont_point, nw, s)); TR(Download(over.data(), a.overflow, nw, s));
+      PP_TRY(Download(seg.data(), a.out_start, nw, s)); PP_TRY(Download(count.data(), a.out_count, nw, s)); PP_TRY(Download(set_count.data(), a.out_set_count, nw, s));
+      PP_TRY(Download(num_tri.data(), a.out_num_tri, nw, s)); PP_TRY(Download(cont.data(), a.out_cont_point, nw, s)); PP_TRY(Download(over.data(), a.overflow, nw, s));
       return PP_OK;
     };
-    TR(fetch(W));
-    TR(Download(&cursor, a.cursor, 1, s));
+    PP_TRY(fetch(W));
+    PP_TRY(Download(&cursor, a.cursor, 1, s));
     PP_HIP_TRY(hipStreamSynchronize(s));
-    TR(Timed(ms_acc));
+    PP_TRY(Timed(ms_acc));
     const size_t used = (size_t)std::min<unsigned long long>(cursor, a.pool_cap);
     pool_list.resize(used); pool_set.resize(used);
-    TR(Download(pool_list.data(), a.pool_list, used, s)); TR(Download(pool_set.data(), a.pool_set, used, s));
+    PP_TRY(Download(pool_list.data(), a.pool_list, used, s)); PP_TRY(Download(pool_set.data(), a.pool_set, used, s));
     PP_HIP_TRY(hipStreamSynchronize(s));
     std::vector<int32_t> again;
     for (size_t w = 0; w < W; ++w) {
@@ -368,29 +365,29 @@ struct ImageCall {
     // the flagged lines: lists in global memory that cannot overflow (a closure holds every line at most once, a direct list is as long as its row)
     const int64_t gcap = std::max<int64_t>(h->L, maxc) + 1;
     const size_t batch = (size_t)std::max<int64_t>(1, std::min<int64_t>((int64_t)again.size(), (int64_t)(32 << 20) / gcap));
-    TR(lb.Alloc(&a.glist, batch * (size_t)gcap)); TR(lb.Alloc(&a.gset, batch * (size_t)gcap));
+    PP_TRY(lb.Alloc(&a.glist, batch * (size_t)gcap)); PP_TRY(lb.Alloc(&a.gset, batch * (size_t)gcap));
     int32_t* d_work2 = nullptr;
-    TR(lb.Alloc(&d_work2, batch));
+    PP_TRY(lb.Alloc(&d_work2, batch));
     a.gcap = gcap; a.work_line = d_work2;
     std::vector<int32_t> lines2(batch);
     for (size_t b0 = 0; b0 < again.size(); b0 += batch) {
       const size_t nb = std::min(batch, again.size() - b0);
       for (size_t i = 0; i < nb; ++i) lines2[i] = work[(size_t)again[b0 + i]];
-      TR(Upload(d_work2, lines2.data(), nb, s));
+      PP_TRY(Upload(d_work2, lines2.data(), nb, s));
       a.num_work = (int)nb;
       PP_HIP_TRY(hipEventRecord(h->ev0, s));
       hipLaunchKernelGGL(k_image_find<true>, dim3((unsigned)nb), dim3(64), 0, s, d, a);
       PP_HIP_TRY(hipGetLastError());
       PP_HIP_TRY(hipEventRecord(h->ev1, s));
       ++launches;
-      TR(fetch(nb));
+      PP_TRY(fetch(nb));
       PP_HIP_TRY(hipStreamSynchronize(s));
-      TR(Timed(ms_acc));
+      PP_TRY(Timed(ms_acc));
       for (size_t i = 0; i < nb; ++i) {
         PP_REQUIRE_INTERNAL(count[i] >= 0 && count[i] < gcap && set_count[i] <= count[i] + 1, "pp_tracks: the closure of a line outgrew every line");
         ImageLineResult& r = out[(size_t)again[b0 + i]];
         r.list.resize((size_t)count[i]); r.set.resize((size_t)set_count[i]);
-        TR(Download(r.list.data(), a.glist + i * (size_t)gcap, r.list.size(), s)); TR(Download(r.set.data(), a.gset + i * (size_t)gcap, r.set.size(), s));
+        PP_TRY(Download(r.list.data(), a.glist + i * (size_t)gcap, r.list.size(), s)); PP_TRY(Download(r.set.data(), a.gset + i * (size_t)gcap, r.set.size(), s));
         PP_HIP_TRY(hipStreamSynchronize(s));
         r.num_triangulated = num_tri[i]; r.continue_point = cont[i];
       }
@@ -416,9 +413,9 @@ struct ImageCall {
     a.S = (int)S; a.aligned = d_aligned; a.recurse = create ? 1 : 0;
     int32_t* d_start = nullptr;
     unsigned long long* d_mt = nullptr;
-    TR(lb.Put(&d_start, start.data(), S + 1)); TR(lb.Put(&a.work_line, flat.data(), N)); TR(lb.Put(&d_mt, mt.data(), S));
+    PP_TRY(lb.Put(&d_start, start.data(), S + 1)); PP_TRY(lb.Put(&a.work_line, flat.data(), N)); PP_TRY(lb.Put(&d_mt, mt.data(), S));
     a.set_start = d_start; a.min_trials = d_mt;
-    TR(lb.Alloc(&a.work_pos, N)); TR(lb.Alloc(&a.flags, N)); TR(lb.Alloc(&a.round_of, N)); TR(lb.Alloc(&a.xyz, 3 * N)); TR(lb.Alloc(&a.num_rounds, S)); TR(lb.Alloc(&a.trials, S));
+    PP_TRY(lb.Alloc(&a.work_pos, N)); PP_TRY(lb.Alloc(&a.flags, N)); PP_TRY(lb.Alloc(&a.round_of, N)); PP_TRY(lb.Alloc(&a.xyz, 3 * N)); PP_TRY(lb.Alloc(&a.num_rounds, S)); PP_TRY(lb.Alloc(&a.trials, S));
     a.m.view_camera = d.pose_camera; a.m.camera_model = d.camera_model; a.m.cam_size = d.cam_size; a.m.P = d.proj; a.m.centers = h->d_centers; a.m.intr = d.intr;
     a.m.min_tri_angle = kDegToRad * o->min_angle;
     const double max_error = create ? kDegToRad * o->create_max_angle_error : o->complete_max_reproj_error;
@@ -434,10 +431,10 @@ struct ImageCall {
     std::vector<int32_t> round_of(N), rounds(S);
     std::vector<double> xyz(3 * N);
     std::vector<unsigned long long> trials(S);
-    TR(Download(round_of.data(), a.round_of, N, s)); TR(Download(xyz.data(), a.xyz, 3 * N, s)); TR(Download(rounds.data(), a.num_rounds, S, s));
-    TR(Download(trials.data(), a.trials, S, s));
+    PP_TRY(Download(round_of.data(), a.round_of, N, s)); PP_TRY(Download(xyz.data(), a.xyz, 3 * N, s)); PP_TRY(Download(rounds.data(), a.num_rounds, S, s));
+    PP_TRY(Download(trials.data(), a.trials, S, s));
     PP_HIP_TRY(hipStreamSynchronize(s));
-    TR(Timed(ms_acc));
+    PP_TRY(Timed(ms_acc));
     for (size_t i = 0; i < S; ++i) {
       ImageLineResult& r = *items[i];
       const size_t e0 = (size_t)start[i], n = r.set.size();
@@ -485,7 +482,7 @@ void pp_tracks_image_options_default(pp_tracks_image_options* o) {
 int pp_tracks_triangulate_image(pp_tracks_handle h, const pp_tracks_image_options* o, int32_t image, const uint8_t* line_aligned, pp_tracks_image_report* report,
                                 int32_t* event_point, int32_t* event_line, int64_t capacity) try {
   const char* where = "pp_tracks_triangulate_image";
-  TR(CheckImageCall(h, o, image, report, event_point, event_line, capacity, where));
+  PP_TRY(CheckImageCall(h, o, image, report, event_point, event_line, capacity, where));
   const auto t_begin = Clock::now();
   std::memset(report, 0, sizeof(*report));
   TrackState& st = h->st;
@@ -494,7 +491,7 @@ int pp_tracks_triangulate_image(pp_tracks_handle h, const pp_tracks_image_option
   if (lines.empty()) return PP_OK;
   PP_HIP_TRY(hipSetDevice(h->device));
   ImageCall call(h, o, line_aligned, true);
-  TR(call.Begin());
+  PP_TRY(call.Begin());
   std::vector<ImageLineResult> res;
   auto triangulate = [&](std::vector<ImageLineResult>& rs, float* ms) {
     std::vector<ImageLineResult*> items;
@@ -504,8 +501,8 @@ int pp_tracks_triangulate_image(pp_tracks_handle h, const pp_tracks_image_option
     }
     return call.Triangulate(items, ms);
   };
-  TR(call.Find(lines, o->max_transitivity, res, &call.device_ms));
-  TR(triangulate(res, &call.device_ms));
+  PP_TRY(call.Find(lines, o->max_transitivity, res, &call.device_ms));
+  PP_TRY(triangulate(res, &call.device_ms));
   report->device_ms = call.device_ms;
   const int32_t spec_launches = call.launches;
   const auto t_replay = Clock::now();
@@ -518,7 +515,7 @@ int pp_tracks_triangulate_image(pp_tracks_handle h, const pp_tracks_image_option
         return &one[0];
       },
       [&](int p, int32_t l) { if (written < capacity) { event_point[written] = p; event_line[written] = l; } ++written; });
-  TR(ReplayError(cnt.error, where));
+  PP_TRY(ReplayError(cnt.error, where));
   report->num_changed = cnt.num_tris; report->num_entries = written; report->ransac_trials = cnt.trials;
   report->points_created = cnt.points_created; report->lines_continued = cnt.lines_continued; report->lines_redone = cnt.lines_redone;
   report->fresh_launches = call.launches - spec_launches;
@@ -530,7 +527,7 @@ int pp_tracks_triangulate_image(pp_tracks_handle h, const pp_tracks_image_option
 int pp_tracks_complete_image(pp_tracks_handle h, const pp_tracks_image_options* o, int32_t image, pp_tracks_image_report* report, int32_t* event_point,
                              int32_t* event_line, int64_t capacity) try {
   const char* where = "pp_tracks_complete_image";
-  TR(CheckImageCall(h, o, image, report, event_point, event_line, capacity, where));
+  PP_TRY(CheckImageCall(h, o, image, report, event_point, event_line, capacity, where));
   const auto t_begin = Clock::now();
   std::memset(report, 0, sizeof(*report));
   TrackState& st = h->st;
@@ -553,13 +550,13 @@ int pp_tracks_complete_image(pp_tracks_handle h, const pp_tracks_image_options* 
   CompleteSpec cspec;
   float device_ms = 0.f;
   if (any_point) {
-    TR(SpeculateComplete(h, subset.data(), o->complete_max_transitivity, max2, where, &cspec));
+    PP_TRY(SpeculateComplete(h, subset.data(), o->complete_max_transitivity, max2, where, &cspec));
     device_ms += cspec.device_ms;
   }
   ImageCall call(h, o, nullptr, false);
-  TR(call.Begin());
+  PP_TRY(call.Begin());
   std::vector<ImageLineResult> res;
-  TR(call.Find(work, o->max_transitivity, res, &call.device_ms));
+  PP_TRY(call.Find(work, o->max_transitivity, res, &call.device_ms));
   {
     std::vector<ImageLineResult*> items;
     uint64_t carried = 0;
@@ -568,7 +565,7 @@ int pp_tracks_complete_image(pp_tracks_handle h, const pp_tracks_image_options* 
       r.min_trials = carried = CompleteMinTrials(r.set.size(), carried);
       if (r.set.size() >= 3) items.push_back(&r);
     }
-    TR(call.Triangulate(items, &call.device_ms));
+    PP_TRY(call.Triangulate(items, &call.device_ms));
   }
   report->device_ms = device_ms + call.device_ms;
   const int32_t call_spec_launches = call.launches;
@@ -605,7 +602,7 @@ int pp_tracks_complete_image(pp_tracks_handle h, const pp_tracks_image_options* 
         return PP_OK;
       },
       [&](int p, int32_t l) { if (written < capacity) { event_point[written] = p; event_line[written] = l; } ++written; });
-  TR(ReplayError(cnt.error, where));
+  PP_TRY(ReplayError(cnt.error, where));
   report->num_changed = cnt.num_tris; report->num_entries = written; report->ransac_trials = cnt.trials;
   report->points_created = cnt.points_created; report->lines_continued = 0; report->lines_redone = cnt.lines_redone;
   report->fresh_launches = call.launches - call_spec_launches + fresh_complete_launches;

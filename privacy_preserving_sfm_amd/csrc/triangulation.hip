@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "ransac_host.hpp"
+#include "resource_pool.hpp"
 #include "tri_device.hpp"
 
 namespace ppsfm {
@@ -75,27 +76,21 @@ extern "C" int pp_triangulate_tracks(int device, int32_t num_tracks, const int32
   int32_t *d_ts = nullptr, *d_ov = nullptr, *d_vc = nullptr, *d_cm = nullptr, *d_cs = nullptr, *d_nt = nullptr;
   double *d_l = nullptr, *d_P = nullptr, *d_c = nullptr, *d_in = nullptr, *d_xyz = nullptr;
   uint8_t *d_s = nullptr, *d_m = nullptr;
-  hipStream_t s = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int rc = PP_OK;
-  auto cleanup = [&]() {
-    void* b[] = {d_ts, d_ov, d_vc, d_cm, d_cs, d_nt, d_l, d_P, d_c, d_in, d_xyz, d_s, d_m};
-    for (void* p : b) if (p) (void)hipFree(p);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (s) (void)hipStreamDestroy(s);
-  };
-  OnUnwind unwind{[&] { cleanup(); }};
-#define TRY(x) do { rc = (x); if (rc) { cleanup(); return rc; } } while (0)
-#define TRYH(x) do { if ((x) != hipSuccess) { SetLastError("pp_triangulate_tracks: %s failed", #x); cleanup(); return PP_ERR_HIP; } } while (0)
-  TRYH(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); TRYH(hipEventCreate(&ev0)); TRYH(hipEventCreate(&ev1));
-  TRY(DeviceAlloc(&d_ts, (size_t)num_tracks + 1)); TRY(DeviceAlloc(&d_ov, (size_t)N)); TRY(DeviceAlloc(&d_vc, (size_t)num_views)); TRY(DeviceAlloc(&d_cm, (size_t)num_cameras));
-  TRY(DeviceAlloc(&d_cs, (size_t)2 * num_cameras)); TRY(DeviceAlloc(&d_nt, (size_t)num_tracks)); TRY(DeviceAlloc(&d_l, (size_t)3 * N)); TRY(DeviceAlloc(&d_P, (size_t)12 * num_views));
-  TRY(DeviceAlloc(&d_c, (size_t)3 * num_views)); TRY(DeviceAlloc(&d_in, (size_t)kCamStride * num_cameras)); TRY(DeviceAlloc(&d_xyz, (size_t)3 * num_tracks));
-  TRY(DeviceAlloc(&d_s, (size_t)num_tracks)); TRY(DeviceAlloc(&d_m, (size_t)std::max<int64_t>(N, 1)));
-  TRY(Upload(d_ts, track_start, (size_t)num_tracks + 1, s)); TRY(Upload(d_ov, obs_view, (size_t)N, s)); TRY(Upload(d_vc, view_camera, (size_t)num_views, s));
-  TRY(Upload(d_cm, camera_model, (size_t)num_cameras, s)); TRY(Upload(d_cs, cam_size, (size_t)2 * num_cameras, s)); TRY(Upload(d_l, lines, (size_t)3 * N, s));
-  TRY(Upload(d_P, proj_matrices, (size_t)12 * num_views, s)); TRY(Upload(d_c, proj_centers, (size_t)3 * num_views, s)); TRY(Upload(d_in, intr, (size_t)kCamStride * num_cameras, s));
+  // the call's stream and events, then its blocks (plain hipMalloc): the blocks go first on every way out, and freeing them waits for the device
+  struct Timeline {
+    hipStream_t s = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    ~Timeline() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); if (s) (void)hipStreamDestroy(s); }
+  } tl;
+  DeviceBlocks scratch(false);
+  PP_HIP_TRY(hipStreamCreateWithFlags(&tl.s, hipStreamNonBlocking)); PP_HIP_TRY(hipEventCreate(&tl.ev0)); PP_HIP_TRY(hipEventCreate(&tl.ev1));
+  const hipStream_t s = tl.s;
+  const hipEvent_t ev0 = tl.ev0, ev1 = tl.ev1;
+  PP_TRY(scratch.Put(&d_ts, track_start, (size_t)num_tracks + 1, s)); PP_TRY(scratch.Put(&d_ov, obs_view, (size_t)N, s)); PP_TRY(scratch.Put(&d_vc, view_camera, (size_t)num_views, s));
+  PP_TRY(scratch.Put(&d_cm, camera_model, (size_t)num_cameras, s)); PP_TRY(scratch.Put(&d_cs, cam_size, (size_t)2 * num_cameras, s)); PP_TRY(scratch.Alloc(&d_nt, (size_t)num_tracks));
+  PP_TRY(scratch.Put(&d_l, lines, (size_t)3 * N, s)); PP_TRY(scratch.Put(&d_P, proj_matrices, (size_t)12 * num_views, s)); PP_TRY(scratch.Put(&d_c, proj_centers, (size_t)3 * num_views, s));
+  PP_TRY(scratch.Put(&d_in, intr, (size_t)kCamStride * num_cameras, s)); PP_TRY(scratch.Alloc(&d_xyz, (size_t)3 * num_tracks));
+  PP_TRY(scratch.Alloc(&d_s, (size_t)num_tracks)); PP_TRY(scratch.Alloc(&d_m, (size_t)std::max<int64_t>(N, 1)));
   a.T = num_tracks; a.track_start = d_ts; a.obs_view = d_ov; a.lines = d_l;
   a.m.view_camera = d_vc; a.m.camera_model = d_cm; a.m.cam_size = d_cs; a.m.P = d_P; a.m.centers = d_c; a.m.intr = d_in;
   a.m.min_tri_angle = o->min_tri_angle; a.m.max_residual = o->ransac.max_error * o->ransac.max_error; a.m.confidence = o->ransac.confidence;
@@ -105,16 +100,13 @@ extern "C" int pp_triangulate_tracks(int device, int32_t num_tracks, const int32
     a.m.max_num_trials = std::min<uint64_t>(o->ransac.max_num_trials, cap);
   }
   a.success = d_s; a.mask = d_m; a.xyz = d_xyz; a.num_trials = d_nt;
-  TRYH(hipEventRecord(ev0, s));
+  PP_HIP_TRY(hipEventRecord(ev0, s));
   hipLaunchKernelGGL(k_triangulate_tracks, dim3(CeilDiv(num_tracks, 64)), dim3(64), 0, s, a);
-  TRYH(hipGetLastError());
-  TRYH(hipEventRecord(ev1, s));
-  TRY(Download(success, d_s, (size_t)num_tracks, s)); TRY(Download(xyz, d_xyz, (size_t)3 * num_tracks, s)); TRY(Download(inlier_mask, d_m, (size_t)N, s));
-  TRY(Download(num_trials, d_nt, (size_t)num_tracks, s));
-  TRYH(hipStreamSynchronize(s));
-  if (device_ms) { float ms = 0; TRYH(hipEventElapsedTime(&ms, ev0, ev1)); *device_ms = ms; }
-#undef TRY
-#undef TRYH
-  cleanup();
+  PP_HIP_TRY(hipGetLastError());
+  PP_HIP_TRY(hipEventRecord(ev1, s));
+  PP_TRY(Download(success, d_s, (size_t)num_tracks, s)); PP_TRY(Download(xyz, d_xyz, (size_t)3 * num_tracks, s)); PP_TRY(Download(inlier_mask, d_m, (size_t)N, s));
+  PP_TRY(Download(num_trials, d_nt, (size_t)num_tracks, s));
+  PP_HIP_TRY(hipStreamSynchronize(s));
+  if (device_ms) { float ms = 0; PP_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1)); *device_ms = ms; }
   return PP_OK;
 } PP_API_CATCH("pp_triangulate_tracks")
