@@ -13,9 +13,9 @@
 // 3x4 mat-vec + 4 projections.  Kernel shape: ONE LANE PER HYPOTHESIS walking the tracks in index order —
 // track records are wave-uniform (scalar loads), and the MSAC score sum_i min(err_i, thr) is accumulated in
 // exactly the reference's order (ransac.h:291-299), so `score < best_score` comparisons see the same sums a
-// sequential CPU loop would.  The LO-MSAC control flow stays on the host, speculating a chunk of iterations at
-// a time (the sampler stream does not depend on results) and replaying the accept / LO / termination logic in
-// iteration order.  Host RNG = this toolchain's <random>, exactly as the reference uses it.
+// sequential CPU loop would.  The LO-MSAC control flow stays on the host (lomsac_host.hpp, std only), speculating a
+// chunk of iterations at a time and replaying the accept / LO / termination logic in iteration order over the
+// three device backends below.
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -32,6 +32,7 @@
 #include "p6l_device.hpp"   // Solve3, Det3x3
 #include "init_lsq.hpp"
 #include "small_eigen.hpp"
+#include "lomsac_host.hpp"
 
 namespace ppsfm {
 // std::max(e1, std::max(e2, std::max(e3, e4))) exactly as the reference nests it (initializer.cc:332, sfm2d.cc:316; std::max(a, b) = a < b ? b : a).  Finite
@@ -50,14 +51,19 @@ struct PlanarView {   // per-view constants
   double c0[4], c1[4];   // z_j(2) = r3_j . X + c0_j + c1_j * ty_j
 };
 
-}  // namespace ppsfm
-
-struct pp_planar_impl {
-  ppsfm::DeviceBlocks blocks{false};      // every device / pinned block of the handle (plain hipMalloc / hipHostMalloc)
+// what the three estimator handles carry alike (EstimatorOpen / EstimatorClose)
+struct EstimatorHandle {
+  DeviceBlocks blocks{false};      // every device / pinned block of the handle (plain hipMalloc / hipHostMalloc)
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;      // the bracket of BatchSolveScore's device time
   int32_t n = 0;
+  double* err = nullptr;       // n: the errors of the model evaluated last
+};
+
+}  // namespace ppsfm
+
+struct pp_planar_impl : ppsfm::EstimatorHandle {
   double* rec = nullptr;       // n x kRec
   double* lines = nullptr;     // 4 x n x 3
   ppsfm::PlanarView view;
@@ -65,19 +71,15 @@ struct pp_planar_impl {
   // work buffers
   int64_t cap = 0;
   int32_t* samples = nullptr;
-  double *offsets = nullptr, *scores = nullptr, *err = nullptr, *X = nullptr;
+  double *offsets = nullptr, *scores = nullptr, *X = nullptr;
   int32_t* inl = nullptr;
   double *d_poses = nullptr, *d_Rg = nullptr;
 };
 
-struct pp_fourview2d_impl {
-  ppsfm::DeviceBlocks blocks{false};      // every device / pinned block of the handle (plain hipMalloc / hipHostMalloc)
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int32_t n = 0;
+struct pp_fourview2d_impl : ppsfm::EstimatorHandle {
   double* x = nullptr;   // 4 x n x 2 unit bearings
   int64_t cap = 0;
-  double *cams = nullptr, *scores = nullptr, *err = nullptr, *X = nullptr;
+  double *cams = nullptr, *scores = nullptr, *X = nullptr;
   int32_t* inl = nullptr;
   int64_t hyp_cap = 0;     // minimal-solver batch buffers
   int32_t hyp_m = 0;
@@ -88,7 +90,6 @@ struct pp_fourview2d_impl {
   // model carries its points, as the reference's Reconstruction does): slot s = 24 camera doubles (pool_cams + 24 s), its MSAC score once somebody asked
   // for it (pool_scores + s), n x 2 points (chunks of kPoolChunk slots).  The host keeps a model as 24 doubles + its slot number; cameras and scores of
   // refined models come back in ONE copy per local optimisation.
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double *lsq_scale = nullptr, *lsq_Xc = nullptr, *xch = nullptr;
   int32_t* d_sample = nullptr;      // kSampleRing buffers of sample_cap ints
   int64_t sample_cap = 0;
@@ -105,17 +106,12 @@ struct pp_fourview2d_impl {
   int pending_score_slot = -1;      // a score whose kernel is launched behind the next shipment of errors (off the host's critical path)
 };
 
-struct pp_pose2d_impl {
-  ppsfm::DeviceBlocks blocks{false};      // every device / pinned block of the handle (plain hipMalloc / hipHostMalloc)
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int32_t n = 0;
+struct pp_pose2d_impl : ppsfm::EstimatorHandle {
   double *x = nullptr, *X = nullptr;   // n x 2 unit bearings, n x 2 points
   int64_t cap = 0;
   int32_t cap_m = 0;
   int32_t* samples = nullptr;
-  double *poses = nullptr, *scores = nullptr, *err = nullptr;
+  double *poses = nullptr, *scores = nullptr;
   int32_t* inl = nullptr;
 };
 
@@ -631,27 +627,82 @@ __global__ __launch_bounds__(256) void k_pose2d_evaluate(int n, const double* __
 }
 
 // ---- host helpers -------------------------------------------------------------------------------------
-// the MSAC sum in WaveMsac's order, so that a model scored on the host (ScoreModel, from downloaded errors) and in a batch
-// on the device gets the same bits
-static double TreeMsacScore(const double* err, int n, double thr) {
-  double acc[64];
-  for (int l = 0; l < 64; ++l) acc[l] = 0.0;
-  for (int i = 0; i < n; ++i) acc[i & 63] += std::min(err[i], thr);   // ransac.h:296 (a NaN error poisons the score)
-  for (int off = 32; off > 0; off >>= 1) {
-    double nxt[64];
-    for (int l = 0; l < 64; ++l) nxt[l] = acc[l] + acc[l ^ off];
-    for (int l = 0; l < 64; ++l) acc[l] = nxt[l];
-  }
-  return acc[0];
+// Work buffers that grow with the calls made on a handle: a group of device arrays of `cap` items each (x `cap_m` entries where a buffer holds one sample
+// per item; cap_m = nullptr where no buffer of the group does).  Grown to the maximum of what it was and what is asked for in every dimension, never
+// shrunk; the capacity reads 0 while the buffers are gone, so a failed allocation leaves a consistent handle.
+struct WorkBuffer { void** p; size_t item_bytes; bool per_sample_entry; };
+template <class T>
+static WorkBuffer Buf(T** p, size_t per_item, bool per_sample_entry = false) { return WorkBuffer{reinterpret_cast<void**>(p), per_item * sizeof(T), per_sample_entry}; }
+
+static int GrowWorkBuffers(DeviceBlocks& B, int64_t* cap, int32_t* cap_m, int64_t want, int32_t want_m, std::initializer_list<WorkBuffer> bufs) {
+  int32_t no_samples = 0;
+  if (!cap_m) { cap_m = &no_samples; want_m = 0; }
+  if (want <= *cap && want_m <= *cap_m) return PP_OK;
+  const int64_t c = std::max(want, *cap);
+  const int32_t m = std::max(want_m, *cap_m);
+  for (const WorkBuffer& b : bufs) B.Free(reinterpret_cast<char**>(b.p));
+  *cap = 0; *cap_m = 0;
+  for (const WorkBuffer& b : bufs) PP_TRY(B.Alloc(reinterpret_cast<char**>(b.p), (size_t)c * b.item_bytes * (b.per_sample_entry ? m : 1)));
+  *cap = c; *cap_m = m;
+  return PP_OK;
 }
 
-static int PlanarEnsure(pp_planar_impl* h, int64_t cap) {
-  if (cap <= h->cap) return PP_OK;
-  DeviceBlocks& B = h->blocks;
-  B.Free(&h->samples); B.Free(&h->offsets); B.Free(&h->scores); B.Free(&h->inl);
-  h->cap = 0;
-  PP_TRY(B.Alloc(&h->samples, (size_t)cap * 32)); PP_TRY(B.Alloc(&h->offsets, (size_t)cap * 3)); PP_TRY(B.Alloc(&h->scores, (size_t)cap)); PP_TRY(B.Alloc(&h->inl, (size_t)cap));
-  h->cap = cap;
+static int PlanarEnsure(pp_planar_impl* h, int64_t cap) {      // (samples: up to 32 indices each)
+  return GrowWorkBuffers(h->blocks, &h->cap, nullptr, cap, 0, {Buf(&h->samples, 32), Buf(&h->offsets, 3), Buf(&h->scores, 1), Buf(&h->inl, 1)});
+}
+static int Pose2dEnsure(pp_pose2d_impl* h, int64_t cap, int32_t m) {
+  return GrowWorkBuffers(h->blocks, &h->cap, &h->cap_m, cap, m, {Buf(&h->samples, 1, true), Buf(&h->poses, 6), Buf(&h->scores, 1), Buf(&h->inl, 1)});
+}
+static int FourViewEnsureScore(pp_fourview2d_impl* h, int64_t num) {
+  return GrowWorkBuffers(h->blocks, &h->cap, nullptr, num, 0, {Buf(&h->cams, 24), Buf(&h->scores, 1), Buf(&h->inl, 1)});
+}
+static int FourViewEnsureHyp(pp_fourview2d_impl* h, int64_t num, int32_t m) {      // the minimal solver's batch: 16 candidates a sample
+  return GrowWorkBuffers(h->blocks, &h->hyp_cap, &h->hyp_m, num, m,
+                         {Buf(&h->samples, 1, true), Buf(&h->counts, 1), Buf(&h->best_index, 1), Buf(&h->models, 16 * 24), Buf(&h->mscores, 16), Buf(&h->minl, 16),
+                          Buf(&h->best_cams, 24), Buf(&h->best_score, 1)});
+}
+
+static void PlanarLaunchSolve(pp_planar_impl* h, int64_t num, int32_t m) {      // h->samples (num x m) -> h->offsets
+  hipLaunchKernelGGL(k_planar_solve, dim3(CeilDiv(num, 64)), dim3(64), 0, h->stream, h->n, h->lines, h->d_poses, h->d_Rg, num, m, h->samples, h->offsets);
+}
+static void PlanarLaunchScore(pp_planar_impl* h, int num, double thr) {      // h->offsets -> h->scores, h->inl
+  hipLaunchKernelGGL(k_planar_score, dim3(CeilDiv(num, 4)), dim3(256), 0, h->stream, h->n, h->rec, h->view, num, h->offsets, thr, h->scores, h->inl);
+}
+static void Pose2dLaunchSolve(pp_pose2d_impl* h, int64_t num, int32_t m) {      // h->samples (num x m) -> h->poses
+  hipLaunchKernelGGL(k_pose2d_solve, dim3(CeilDiv(num, 64)), dim3(64), 0, h->stream, h->n, h->x, h->X, num, m, h->samples, h->poses);
+}
+static void Pose2dLaunchScore(pp_pose2d_impl* h, int num, double thr) {      // h->poses -> h->scores, h->inl
+  hipLaunchKernelGGL(k_pose2d_score, dim3(CeilDiv(num, 4)), dim3(256), 0, h->stream, h->n, h->x, h->X, num, h->poses, thr, h->scores, h->inl);
+}
+
+// samples up, solver, models back: pp_*_solve_batch behind its checks and its Ensure, and the NonMinimalSolver of the two host-error backends
+template <class H, class Launch>
+static int SolveBatch(H* h, const int32_t* samples, size_t num_indices, Launch&& launch, double* models, const double* d_models, size_t count) {
+  int rc = Upload(h->samples, samples, num_indices, h->stream); if (rc) return rc;
+  launch();
+  PP_HIP_TRY(hipGetLastError());
+  rc = Download(models, d_models, count, h->stream); if (rc) return rc;
+  PP_HIP_TRY(hipStreamSynchronize(h->stream));
+  return PP_OK;
+}
+// models up, score kernel, scores and inlier counts back: pp_*_score behind its checks and its Ensure
+template <class H, class Launch>
+static int ScoreBatch(H* h, double* d_models, const double* models, size_t count, Launch&& launch, int32_t num, double* msac, int32_t* inl) {
+  int rc = Upload(d_models, models, count, h->stream); if (rc) return rc;
+  launch();
+  PP_HIP_TRY(hipGetLastError());
+  rc = Download(msac, h->scores, (size_t)num, h->stream); if (rc) return rc;
+  rc = Download(inl, h->inl, (size_t)num, h->stream); if (rc) return rc;
+  PP_HIP_TRY(hipStreamSynchronize(h->stream));
+  return PP_OK;
+}
+
+// errors of the model evaluated last (and its points, where asked for) back: the tail of every evaluation
+static int ErrorsBack(EstimatorHandle* h, double* errors, double* X = nullptr, const double* d_X = nullptr, size_t x_count = 0) {
+  PP_HIP_TRY(hipGetLastError());
+  int rc = Download(errors, h->err, (size_t)h->n, h->stream); if (rc) return rc;
+  if (X) { rc = Download(X, d_X, x_count, h->stream); if (rc) return rc; }
+  PP_HIP_TRY(hipStreamSynchronize(h->stream));
   return PP_OK;
 }
 
@@ -666,41 +717,52 @@ static void CamsFromOffsets(const pp_planar_impl* h, const double* tt, double* c
   }
 }
 
-// LO-MSAC over the planar-offset solver: models are offset triples; all scoring happens on the device
-struct PlanarBackend {
+// GetInliers (ransac.h:308-322) from a model's errors: strict <, ascending
+static int InliersBelow(const std::vector<double>& err, int n, double t, std::vector<int>* inl) {
+  inl->clear();
+  for (int i = 0; i < n; ++i) if (err[i] < t) inl->push_back(i);
+  return (int)inl->size();
+}
+
+// What the planar and the pose backend of LoMsacRun share: models are a few doubles on the host, scored in batches on the device and one at a time from
+// errors downloaded to the host.  The estimator (Derived) supplies kMinSample, kNonMinSample, Solve, LeastSquares and
+//   int Ensure(int64_t num)                     the work buffers of a batch of `num` minimal samples
+//   void EnqueueSolveScore(uint32_t want)       minimal solver + score over h->samples
+//   double* DeviceModels()                      where that batch's models are
+//   int EnqueueEvaluate(const double* model)    h->err <- the errors of one model (its upload + the kernel)
+template <class Derived, class Handle, int kDimT>
+struct HostErrorBackend {
   static constexpr bool kDeferredScores = false;
-  static constexpr int kDim = 3, kMinSample = 3, kNonMinSample = 20;   // initializer.h: min_sample_size / non_minimal_sample_size
-  pp_planar_impl* h;
+  static constexpr int kDim = kDimT;
+  Handle* h;
   double thr;
   std::vector<double> err;
   int rc = PP_OK;
+  Derived& self() { return static_cast<Derived&>(*this); }
   int n() const { return h->n; }
-  void LeastSquares(const std::vector<int>&, double*) {}   // PlanarOffsetEstimator::LeastSquares returns immediately (initializer.cc:450-451)
   int BatchSolveScore(uint32_t want, const int32_t* samples, std::vector<double>* models, std::vector<double>* scores, double* dev_s) {
-    int r = PlanarEnsure(h, want); if (r) return r;
-    r = Upload(h->samples, samples, (size_t)want * 3, h->stream); if (r) return r;
+    int r = self().Ensure(want); if (r) return r;
+    r = Upload(h->samples, samples, (size_t)want * Derived::kMinSample, h->stream); if (r) return r;
     PP_HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_planar_solve, dim3(CeilDiv(want, 64)), dim3(64), 0, h->stream, h->n, h->lines, h->d_poses, h->d_Rg, (int64_t)want, 3, h->samples, h->offsets);
-    hipLaunchKernelGGL(k_planar_score, dim3(CeilDiv(want, 4)), dim3(256), 0, h->stream, h->n, h->rec, h->view, (int)want, h->offsets, thr, h->scores, h->inl);
+    self().EnqueueSolveScore(want);
     PP_HIP_TRY(hipGetLastError());
     PP_HIP_TRY(hipEventRecord(h->ev1, h->stream));
-    models->resize((size_t)want * 3); scores->resize(want);
-    r = Download(models->data(), h->offsets, models->size(), h->stream); if (r) return r;
+    models->resize((size_t)want * kDim); scores->resize(want);
+    r = Download(models->data(), self().DeviceModels(), models->size(), h->stream); if (r) return r;
     r = Download(scores->data(), h->scores, scores->size(), h->stream); if (r) return r;
     PP_HIP_TRY(hipStreamSynchronize(h->stream));
     float ms = 0; PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1)); *dev_s += ms * 1e-3;
     return PP_OK;
   }
-  double cached[3]; bool have_cached = false;      // (as Pose2dBackend: ScoreModel and the GetInliers behind it ask about the same model)
+  // the errors of the model evaluated last stay on the host: ScoreModel and the GetInliers that follows it in a local optimisation (ransac.h:337-406) ask
+  // about the SAME model - one launch, one copy, one synchronisation instead of two
+  double cached[kDim]; bool have_cached = false;
   int Evaluate(const double* model) {   // fills err (n)
     if (have_cached && std::memcmp(cached, model, sizeof(cached)) == 0 && (int)err.size() == h->n) return PP_OK;
     have_cached = false;
     err.resize(h->n);
-    hipLaunchKernelGGL(k_planar_evaluate, dim3(CeilDiv(h->n, 256)), dim3(256), 0, h->stream, h->n, h->rec, h->view, model[0], model[1], model[2],
-                       h->err, (double*)nullptr);
-    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-    if (hipMemcpyAsync(err.data(), h->err, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return PP_ERR_HIP;
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return PP_ERR_HIP;
+    if (const int r = self().EnqueueEvaluate(model)) return r;
+    if (const int r = ErrorsBack(h, err.data())) return r;
     std::memcpy(cached, model, sizeof(cached)); have_cached = true;
     return PP_OK;
   }
@@ -710,298 +772,53 @@ struct PlanarBackend {
   }
   int GetInliers(const double* model, double t, std::vector<int>* inl) {
     if ((rc = Evaluate(model))) return 0;
-    inl->clear();
-    for (int i = 0; i < h->n; ++i) if (err[i] < t) inl->push_back(i);
-    return (int)inl->size();
+    return InliersBelow(err, h->n, t, inl);
   }
+};
+
+// LO-MSAC over the planar-offset solver: models are offset triples; all scoring happens on the device
+struct PlanarBackend : HostErrorBackend<PlanarBackend, pp_planar_impl, 3> {
+  static constexpr int kMinSample = 3, kNonMinSample = 20;   // initializer.h: min_sample_size / non_minimal_sample_size
+  int Ensure(int64_t num) { return PlanarEnsure(h, num); }
+  void EnqueueSolveScore(uint32_t want) { PlanarLaunchSolve(h, want, 3); PlanarLaunchScore(h, (int)want, thr); }
+  double* DeviceModels() const { return h->offsets; }
+  int EnqueueEvaluate(const double* model) {
+    hipLaunchKernelGGL(k_planar_evaluate, dim3(CeilDiv(h->n, 256)), dim3(256), 0, h->stream, h->n, h->rec, h->view, model[0], model[1], model[2],
+                       h->err, (double*)nullptr);
+    return PP_OK;
+  }
+  void LeastSquares(const std::vector<int>&, double*) {}   // PlanarOffsetEstimator::LeastSquares returns immediately (initializer.cc:450-451)
   bool Solve(const std::vector<int>& sample, double* model) {
     const int m = (int)sample.size();
     if (m > 32) return false;
-    if ((rc = PlanarEnsure(h, 64))) return false;
-    if (hipMemcpyAsync(h->samples, sample.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = PP_ERR_HIP; return false; }
-    hipLaunchKernelGGL(k_planar_solve, dim3(1), dim3(64), 0, h->stream, h->n, h->lines, h->d_poses, h->d_Rg, (int64_t)1, m, h->samples, h->offsets);
-    if (hipMemcpyAsync(model, h->offsets, sizeof(double) * 3, hipMemcpyDeviceToHost, h->stream) != hipSuccess) { rc = PP_ERR_HIP; return false; }
-    if (hipStreamSynchronize(h->stream) != hipSuccess) { rc = PP_ERR_HIP; return false; }
+    if ((rc = PlanarEnsure(h, 64)) || (rc = SolveBatch(h, sample.data(), m, [&] { PlanarLaunchSolve(h, 1, m); }, model, h->offsets, 3))) return false;
     return std::isfinite(model[0]) && std::isfinite(model[1]) && std::isfinite(model[2]);
   }
 };
 
-static uint32_t NumRequiredIterations(double inlier_ratio, double prob_missing, int sample_size, uint32_t min_it, uint32_t max_it) {
-  if (inlier_ratio <= 0.0) return max_it;        // utils.h:110-132
-  if (inlier_ratio >= 1.0) return min_it;
-  const double p = 1.0 - std::pow(inlier_ratio, static_cast<double>(sample_size));
-  const double it = std::ceil(std::log(prob_missing) / std::log(p) + 0.5);
-  return std::max(min_it, std::min(static_cast<uint32_t>(it), max_it));
-}
-static void RandomShuffle(std::mt19937* rng, std::vector<int>* v) {   // utils.h:48-58
-  const int n = static_cast<int>(v->size());
-  for (int i = 0; i < n - 1; ++i) { std::uniform_int_distribution<int> d(i, n - 1); std::swap((*v)[i], (*v)[d(*rng)]); }
-}
-
-class UniformSampling {   // sampling.h:46-135
- public:
-  UniformSampling(unsigned seed, int num_data, int sample_size) : n_(num_data), k_(sample_size) {
-    rng_.seed(seed);
-    draw_ = static_cast<double>(num_data) / static_cast<double>(num_data - sample_size) < M_E;
-    dist_.param(std::uniform_int_distribution<int>::param_type(0, n_ - 1));
-  }
-  void Sample(int* out) {
-    if (draw_) {
-      for (int i = 0; i < k_; ++i) {
-        bool found = true;
-        while (found) { found = false; out[i] = dist_(rng_); for (int j = 0; j < i; ++j) if (out[j] == out[i]) { found = true; break; } }
-      }
-    } else {
-      std::vector<int> v(n_);
-      std::iota(v.begin(), v.end(), 0);
-      if (k_ != n_) RandomShuffle(&rng_, &v);
-      for (int i = 0; i < k_; ++i) out[i] = v[i];
-    }
-  }
- private:
-  std::mt19937 rng_; std::uniform_int_distribution<int> dist_; int n_, k_; bool draw_;
-};
-
-typedef std::array<double, 3> Offsets;
-
-// LocalOptimization (ransac.h:337-406) over a device backend.  Backend: kDim doubles per model, kMinSample,
-// kNonMinSample, n(), ScoreModel, GetInliers, Solve (NonMinimalSolver), LeastSquares, BatchSolveScore, rc.
-template <class Backend>
-static void LocalOptimization(const pp_lomsac_options& o, Backend& be, std::array<double, Backend::kDim>* best_min, double* score_best) {
-  typedef std::array<double, Backend::kDim> Model;
-  const int kN = be.n(), kMinNonMin = Backend::kNonMinSample, kMin = Backend::kMinSample;
-  if (kMinNonMin > kN) return;
-  const double thr = o.squared_inlier_threshold, mult = o.threshold_multiplier;
-  std::mt19937 rng; rng.seed(o.random_seed);
-  // ScoreModel + UpdateBestModel (ransac.h:399-404).  Nothing inside a local optimisation READS the best score or model - the loop's control flow depends on
-  // inlier lists and on whether the non-minimal solver found a model -, so a backend whose models live on the device (kDeferredScores) only enqueues the
-  // score here and the candidates are compared, in the order they were produced and with the same strict <, when the local optimisation is over.
-  struct Cand { double score; Model m; int ticket; };
-  std::vector<Cand> cand;
-  auto consider = [&](Model& m) {
-    if constexpr (Backend::kDeferredScores) { const int t = be.ScoreModelDeferred(m.data()); cand.push_back(Cand{0.0, m, t}); }
-    else { const double sc = be.ScoreModel(m.data()); if (sc < *score_best) { *score_best = sc; *best_min = m; } }
-  };
-  auto lsq_fit = [&](double thresh, Model* m) {   // LeastSquaresFit: the rng draws happen even where LeastSquares is a no-op
-    const int kSize = o.min_sample_multiplicator * kMin;
-    std::vector<int> inl;
-    const int ni = be.GetInliers(m->data(), thresh, &inl);
-    if (ni < kMin) return;
-    RandomShuffle(&rng, &inl);
-    inl.resize(std::min(kSize, ni));
-    be.LeastSquares(inl, m->data());
-  };
-  Model m_init = *best_min;
-  lsq_fit(thr * mult, &m_init);
-  consider(m_init);
-  std::vector<int> base;
-  be.GetInliers(m_init.data(), thr, &base);
-  const int kNonMin = std::max(kMinNonMin, std::min(kMin * o.non_min_sample_multiplier, static_cast<int>(base.size()) / 2));
-  for (int r = 0; r < o.num_lo_steps; ++r) {
-    std::vector<int> sample = base;
-    RandomShuffle(&rng, &sample);
-    sample.resize(kNonMin);     // vector::resize value-initialises missing entries, as RandomShuffleAndResize does
-    Model m_non_min;
-    if (!be.Solve(sample, m_non_min.data())) continue;
-    consider(m_non_min);
-    lsq_fit(thr, &m_non_min);
-    double thresh = mult * thr;
-    const double upd = (mult - 1.0) * thr / static_cast<int>(o.num_lsq_iterations - 1);
-    for (int i = 0; i < o.num_lsq_iterations; ++i) {
-      lsq_fit(thresh, &m_non_min);
-      consider(m_non_min);
-      thresh -= upd;
-    }
-  }
-  if constexpr (Backend::kDeferredScores) {
-    be.ResolveScores(&cand);
-    for (const Cand& c : cand) if (c.score < *score_best) { *score_best = c.score; *best_min = c.m; }
-  }
-}
-
-// LocallyOptimizedMSAC::EstimateModel (ransac.h:127-271): the minimal solves + scores of a chunk of iterations run on the
-// device in one batch, the bookkeeping is replayed on the host in iteration order
-template <class Backend>
-static int LoMsacRun(const pp_lomsac_options* o, Backend& be, pp_lomsac_report* rep, std::array<double, Backend::kDim>* best_out, std::vector<int>* inliers_out) {
-  typedef std::array<double, Backend::kDim> Model;
-  const auto t0 = std::chrono::steady_clock::now();
-  std::memset(rep, 0, sizeof(*rep));
-  rep->best_model_score = std::numeric_limits<double>::max();
-  const int kMin = Backend::kMinSample, kN = be.n();
-  Model best_model; best_model.fill(0.0);
-  Model best_min = best_model;
-  std::vector<int>& inliers = *inliers_out;
-  inliers.clear();
-  if (kMin > kN) { *best_out = best_model; return PP_OK; }
-  const double thr = o->squared_inlier_threshold;
-  const double kMax = std::numeric_limits<double>::max();
-  UniformSampling sampler(o->random_seed, kN, kMin);
-  uint32_t max_it = std::max(o->max_num_iterations, o->min_num_iterations);
-  double best_min_score = kMax;
-  auto refresh = [&]() {
-    rep->best_num_inliers = be.GetInliers(best_model.data(), thr, &inliers);
-    rep->inlier_ratio = static_cast<double>(rep->best_num_inliers) / static_cast<double>(kN);
-    max_it = NumRequiredIterations(rep->inlier_ratio, 1.0 - o->success_probability, kMin, o->min_num_iterations, o->max_num_iterations);
-  };
-  auto update_best = [&](double sc, const Model& m) { if (sc < rep->best_model_score) { rep->best_model_score = sc; best_model = m; } };
-  const uint32_t chunk = o->chunk_iterations ? o->chunk_iterations : 1024;
-  std::vector<int32_t> hs; std::vector<double> models, sc;
-  uint32_t it = 0;
-  double dev_s = 0;
-  while (it < max_it) {
-    const uint32_t want = std::min<uint32_t>(chunk, max_it - it);
-    hs.resize((size_t)want * kMin);
-    for (uint32_t i = 0; i < want; ++i) sampler.Sample(&hs[(size_t)kMin * i]);
-    const int rc = be.BatchSolveScore(want, hs.data(), &models, &sc, &dev_s);
-    if (rc) return rc;
-    rep->hypotheses_evaluated += want;
-    // replay of ransac.h:155-237 in iteration order; the sampler has already been advanced for the whole
-    // chunk, which is harmless because nothing after an early exit draws from it
-    for (uint32_t i = 0; i < want && it < max_it; ++i, ++it) {
-      if (it == o->lo_starting_iterations && best_min_score < kMax) {
-        ++rep->number_lo_iterations;
-        LocalOptimization(*o, be, &best_model, &rep->best_model_score);
-        refresh();
-      }
-      Model m;
-      bool finite = true;
-      for (int k = 0; k < Backend::kDim; ++k) { m[k] = models[(size_t)Backend::kDim * i + k]; finite = finite && std::isfinite(m[k]); }
-      if (!finite) continue;   // MinimalSolver returned 0 models
-      const double best_local = sc[i];
-      if (best_local < best_min_score || it == o->lo_starting_iterations) {
-        const bool kBestMin = best_local < best_min_score;
-        if (kBestMin) { best_min_score = best_local; best_min = m; update_best(best_min_score, best_min); }
-        const bool kRunLO = it >= o->lo_starting_iterations && best_min_score < kMax;
-        if (!kBestMin && !kRunLO) continue;
-        if (kRunLO) {
-          ++rep->number_lo_iterations;
-          double score = best_min_score;
-          LocalOptimization(*o, be, &best_min, &score);
-          update_best(score, best_min);
-        }
-        refresh();
-      }
-    }
-    if (be.rc) { SetLastError("LO-MSAC: device evaluation failed"); return be.rc; }
-  }
-  rep->num_iterations = it;
-  if (it <= o->lo_starting_iterations && rep->best_model_score < kMax) {
-    ++rep->number_lo_iterations;
-    LocalOptimization(*o, be, &best_model, &rep->best_model_score);
-    rep->best_num_inliers = be.GetInliers(best_model.data(), thr, &inliers);
-    rep->inlier_ratio = static_cast<double>(rep->best_num_inliers) / static_cast<double>(kN);
-  }
-  if (o->final_least_squares) {   // ransac.h:253-268
-    Model refined = best_model;
-    be.LeastSquares(inliers, refined.data());
-    const double score = be.ScoreModel(refined.data());
-    if (score < rep->best_model_score) {
-      rep->best_model_score = score; best_model = refined;
-      rep->best_num_inliers = be.GetInliers(best_model.data(), thr, &inliers);
-      rep->inlier_ratio = static_cast<double>(rep->best_num_inliers) / static_cast<double>(kN);
-    }
-  }
-  if (be.rc) { SetLastError("LO-MSAC: device evaluation failed"); return be.rc; }
-  *best_out = best_model;
-  rep->num_inlier_indices = (int32_t)inliers.size();
-  rep->device_time_s = dev_s;
-  rep->total_time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return PP_OK;
-}
-
-
-static int Pose2dEnsure(pp_pose2d_impl* h, int64_t cap, int32_t m) {
-  if (cap <= h->cap && m <= h->cap_m) return PP_OK;
-  DeviceBlocks& B = h->blocks;
-  B.Free(&h->samples); B.Free(&h->poses); B.Free(&h->scores); B.Free(&h->inl);
-  const int64_t c = std::max(cap, h->cap);
-  const int32_t mm = std::max(m, h->cap_m);
-  h->cap = 0; h->cap_m = 0;
-  PP_TRY(B.Alloc(&h->samples, (size_t)c * mm)); PP_TRY(B.Alloc(&h->poses, (size_t)c * 6)); PP_TRY(B.Alloc(&h->scores, (size_t)c)); PP_TRY(B.Alloc(&h->inl, (size_t)c));
-  h->cap = c; h->cap_m = mm;
-  return PP_OK;
-}
-
 // LO-MSAC over AbsolutePose2dEstimator: models are 2x3 poses; LeastSquares == NonMinimalSolver (sfm2d.h:141-143)
-struct Pose2dBackend {
-  static constexpr bool kDeferredScores = false;
-  static constexpr int kDim = 6, kMinSample = 3, kNonMinSample = 6;   // sfm2d.h:113-119
-  pp_pose2d_impl* h;
-  double thr;
-  std::vector<double> err;
-  int rc = PP_OK;
-  int n() const { return h->n; }
-  // the errors of the model evaluated last stay on the host: ScoreModel and the GetInliers that follows it in a local optimisation (ransac.h:337-406) ask
-  // about the SAME model - one launch, one copy, one synchronisation instead of two
-  double cached[6]; bool have_cached = false;
-  int Evaluate(const double* model) {
-    if (have_cached && std::memcmp(cached, model, sizeof(cached)) == 0 && (int)err.size() == h->n) return PP_OK;
-    have_cached = false;
-    err.resize(h->n);
-    if ((rc = Pose2dEnsure(h, 1, 3))) return rc;
+struct Pose2dBackend : HostErrorBackend<Pose2dBackend, pp_pose2d_impl, 6> {
+  static constexpr int kMinSample = 3, kNonMinSample = 6;   // sfm2d.h:113-119
+  int Ensure(int64_t num) { return Pose2dEnsure(h, num, 3); }
+  void EnqueueSolveScore(uint32_t want) { Pose2dLaunchSolve(h, want, 3); Pose2dLaunchScore(h, (int)want, thr); }
+  double* DeviceModels() const { return h->poses; }
+  int EnqueueEvaluate(const double* model) {
+    if (const int r = Pose2dEnsure(h, 1, 3)) return r;
     if (hipMemcpyAsync(h->poses, model, sizeof(double) * 6, hipMemcpyHostToDevice, h->stream) != hipSuccess) return PP_ERR_HIP;
     hipLaunchKernelGGL(k_pose2d_evaluate, dim3(CeilDiv(h->n, 256)), dim3(256), 0, h->stream, h->n, h->x, h->X, h->poses, h->err);
-    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
-    if (hipMemcpyAsync(err.data(), h->err, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return PP_ERR_HIP;
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return PP_ERR_HIP;
-    std::memcpy(cached, model, sizeof(cached)); have_cached = true;
     return PP_OK;
-  }
-  double ScoreModel(const double* model) {
-    if ((rc = Evaluate(model))) return std::numeric_limits<double>::max();
-    return TreeMsacScore(err.data(), h->n, thr);
-  }
-  int GetInliers(const double* model, double t, std::vector<int>* inl) {
-    if ((rc = Evaluate(model))) return 0;
-    inl->clear();
-    for (int i = 0; i < h->n; ++i) if (err[i] < t) inl->push_back(i);
-    return (int)inl->size();
   }
   bool Solve(const std::vector<int>& sample, double* model) {
     const int m = (int)sample.size();
     if (m < 1) return false;
-    if ((rc = Pose2dEnsure(h, 1, m))) return false;
-    if (hipMemcpyAsync(h->samples, sample.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = PP_ERR_HIP; return false; }
-    hipLaunchKernelGGL(k_pose2d_solve, dim3(1), dim3(64), 0, h->stream, h->n, h->x, h->X, (int64_t)1, m, h->samples, h->poses);
-    if (hipMemcpyAsync(model, h->poses, sizeof(double) * 6, hipMemcpyDeviceToHost, h->stream) != hipSuccess) { rc = PP_ERR_HIP; return false; }
-    if (hipStreamSynchronize(h->stream) != hipSuccess) { rc = PP_ERR_HIP; return false; }
+    if ((rc = Pose2dEnsure(h, 1, m)) || (rc = SolveBatch(h, sample.data(), m, [&] { Pose2dLaunchSolve(h, 1, m); }, model, h->poses, 6))) return false;
     return true;     // NonMinimalSolver always returns one model (sfm2d.cc:491-514)
   }
   void LeastSquares(const std::vector<int>& sample, double* model) { (void)Solve(sample, model); }
-  int BatchSolveScore(uint32_t want, const int32_t* samples, std::vector<double>* models, std::vector<double>* scores, double* dev_s) {
-    int r = Pose2dEnsure(h, want, 3); if (r) return r;
-    r = Upload(h->samples, samples, (size_t)want * 3, h->stream); if (r) return r;
-    PP_HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_pose2d_solve, dim3(CeilDiv(want, 64)), dim3(64), 0, h->stream, h->n, h->x, h->X, (int64_t)want, 3, h->samples, h->poses);
-    hipLaunchKernelGGL(k_pose2d_score, dim3(CeilDiv(want, 4)), dim3(256), 0, h->stream, h->n, h->x, h->X, (int)want, h->poses, thr, h->scores, h->inl);
-    PP_HIP_TRY(hipGetLastError());
-    PP_HIP_TRY(hipEventRecord(h->ev1, h->stream));
-    models->resize((size_t)want * 6); scores->resize(want);
-    r = Download(models->data(), h->poses, models->size(), h->stream); if (r) return r;
-    r = Download(scores->data(), h->scores, scores->size(), h->stream); if (r) return r;
-    PP_HIP_TRY(hipStreamSynchronize(h->stream));
-    float ms = 0; PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1)); *dev_s += ms * 1e-3;
-    return PP_OK;
-  }
 };
-
 
 // LO-MSAC over FourView2dEstimator.  A model = 4 cameras (24 doubles) + the index of its point array in the handle's
 // pool (-1: the points are the three-view triangulation of its cameras, what MinimalSolver produces).
-static int FourViewEnsureHyp(pp_fourview2d_impl* h, int64_t num, int32_t m) {
-  if (num <= h->hyp_cap && m <= h->hyp_m) return PP_OK;
-  DeviceBlocks& B = h->blocks;
-  B.Free(&h->samples); B.Free(&h->counts); B.Free(&h->best_index); B.Free(&h->models); B.Free(&h->mscores); B.Free(&h->best_cams); B.Free(&h->best_score); B.Free(&h->minl);
-  h->hyp_cap = 0; h->hyp_m = 0;
-  const int64_t cap = std::max<int64_t>(num, h->hyp_cap);
-  const int32_t mm = std::max(m, h->hyp_m);
-  PP_TRY(B.Alloc(&h->samples, (size_t)cap * mm)); PP_TRY(B.Alloc(&h->counts, (size_t)cap)); PP_TRY(B.Alloc(&h->best_index, (size_t)cap));
-  PP_TRY(B.Alloc(&h->models, (size_t)cap * 16 * 24)); PP_TRY(B.Alloc(&h->mscores, (size_t)cap * 16)); PP_TRY(B.Alloc(&h->minl, (size_t)cap * 16));
-  PP_TRY(B.Alloc(&h->best_cams, (size_t)cap * 24)); PP_TRY(B.Alloc(&h->best_score, (size_t)cap));
-  h->hyp_cap = cap; h->hyp_m = mm;
-  return PP_OK;
-}
-
 static int FourViewLaunchMinimal(pp_fourview2d_impl* h, int64_t num, int32_t m, const int32_t* samples, const double* frames) {
   for (int64_t i = 0; i < num * m; ++i) if (samples[i] < 0 || samples[i] >= h->n) { SetLastError("pp_fourview2d: sample index %d out of range", samples[i]); return PP_ERR_INVALID; }
   int rc = FourViewEnsureHyp(h, num, m); if (rc) return rc;
@@ -1188,8 +1005,7 @@ struct FourView2dBackend {
     inl->clear();
     const int s = Materialize(model);
     if (s < 0 || (rc = FetchErrors(s))) return 0;
-    for (int i = 0; i < h->n; ++i) if (err[i] < t) inl->push_back(i);
-    return (int)inl->size();
+    return InliersBelow(err, h->n, t, inl);
   }
   // MinimalSolver on `num` samples + score of every candidate + first strictly-smallest (what the RANSAC loop and
   // NonMinimalSolver both do with the <= 16 candidates of a sample): enqueued, results in h->best_cams / best_score
@@ -1287,6 +1103,49 @@ struct FourView2dBackend {
   void FreeSlots() { FourViewPoolReset(h); }
 };
 
+// ---- what the C entry points of the three estimators share ------------------------------------------------------
+// Opens a handle that has just been allocated: device check (`who` = the create function, for the message), stream, the two events.  Host vectors of a
+// create function are built BEFORE its handle, so that on an error return the handle's release - of plain device memory, which waits for the device -
+// comes first.
+static int EstimatorOpen(EstimatorHandle* h, const char* who, int device, int32_t n) {
+  int ndev = 0;
+  PP_HIP_TRY(hipGetDeviceCount(&ndev));
+  PP_REQUIRE(device >= 0 && device < ndev, "%s: device %d of %d", who, device, ndev);
+  PP_HIP_TRY(hipSetDevice(device));
+  h->device = device; h->n = n;
+  PP_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  PP_HIP_TRY(hipEventCreate(&h->ev0)); PP_HIP_TRY(hipEventCreate(&h->ev1));
+  return PP_OK;
+}
+// ... and closes it, whatever state its construction reached (nullptr: nothing to do)
+template <class H>
+static int EstimatorDestroy(H* h) {
+  if (!h) return PP_OK;
+  (void)hipSetDevice(h->device);
+  h->blocks.Release();      // (plain device memory: freeing it waits for the device)
+  if (h->ev0) (void)hipEventDestroy(h->ev0);
+  if (h->ev1) (void)hipEventDestroy(h->ev1);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+  return PP_OK;
+}
+
+// pp_*_lomsac: the option check (`who` = the entry point), the run, and the copy-out of the inliers
+static int LomsacCheck(bool have_arguments, const pp_lomsac_options* o, const char* who) {
+  PP_REQUIRE(have_arguments, "%s: null argument", who);
+  PP_REQUIRE(o->num_lsq_iterations >= 2 && o->num_lo_steps >= 0, "%s: bad options", who);
+  return PP_OK;
+}
+template <class Backend>
+static int LomsacRun(const pp_lomsac_options* o, Backend& be, pp_lomsac_report* rep, std::array<double, Backend::kDim>* best, std::vector<int>* inliers) {
+  const int rc = LoMsacRun(o, be, rep, best, inliers);
+  if (rc && be.rc) SetLastError("LO-MSAC: device evaluation failed");      // (a failed BatchSolveScore has said what failed)
+  return rc;
+}
+static void CopyInliers(const std::vector<int>& inliers, int32_t* inlier_indices) {
+  if (inlier_indices) for (size_t i = 0; i < inliers.size(); ++i) inlier_indices[i] = inliers[i];
+}
+
 }  // namespace ppsfm
 
 using namespace ppsfm;
@@ -1302,26 +1161,15 @@ void pp_lomsac_options_default(pp_lomsac_options* o) {
 }
 
 int pp_planar_destroy(pp_planar_handle h) try {
-  if (!h) return PP_OK;
-  (void)hipSetDevice(h->device);
-  h->blocks.Release();      // (plain device memory: freeing it waits for the device)
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return PP_OK;
+  return EstimatorDestroy(h);
 } PP_API_CATCH("pp_planar_destroy")
 
 int pp_planar_create(int32_t n, const double* poses, const double* lines, const double* Rg, int device, pp_planar_handle* out) try {
   PP_REQUIRE(out && n > 0 && poses && lines && Rg, "pp_planar_create: bad argument");
   *out = nullptr;
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "pp_planar_create: device %d of %d", device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
-  std::vector<double> rec((size_t)n * kRec);      // (before the handle: on an error return the handle's release - of plain device memory, which waits for the device - comes first)
+  std::vector<double> rec((size_t)n * kRec);      // (before the handle: EstimatorOpen)
   UnderConstruction<pp_planar_impl, pp_planar_destroy> h{new pp_planar_impl()};
-  h->device = device; h->n = n;
+  PP_TRY(EstimatorOpen(h.h, "pp_planar_create", device, n));
   std::memcpy(h->poses, poses, sizeof(h->poses));
   std::memcpy(h->Rg, Rg, sizeof(h->Rg));
   // per-view constants
@@ -1361,8 +1209,6 @@ int pp_planar_create(int32_t n, const double* poses, const double* lines, const 
     inv[6] = inv[2]; inv[7] = inv[5]; inv[8] = (AtA[0] * AtA[4] - AtA[1] * AtA[3]) / det;
     for (int c = 0; c < 3; ++c) for (int j = 0; j < 4; ++j) r[4 * c + j] = inv[3 * c] * A[3 * j] + inv[3 * c + 1] * A[3 * j + 1] + inv[3 * c + 2] * A[3 * j + 2];
   }
-  PP_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  PP_HIP_TRY(hipEventCreate(&h->ev0)); PP_HIP_TRY(hipEventCreate(&h->ev1));
   DeviceBlocks& B = h->blocks;
   PP_TRY(B.Put(&h->rec, rec.data(), rec.size(), h->stream)); PP_TRY(B.Put(&h->lines, lines, (size_t)12 * n, h->stream)); PP_TRY(B.Alloc(&h->err, (size_t)n)); PP_TRY(B.Alloc(&h->X, (size_t)3 * n));
   PP_TRY(B.Put(&h->d_poses, poses, 48, h->stream)); PP_TRY(B.Put(&h->d_Rg, Rg, 36, h->stream));
@@ -1376,81 +1222,51 @@ int pp_planar_solve_batch(pp_planar_handle h, int64_t num, int32_t sample_size, 
   if (num == 0) return PP_OK;
   for (int64_t i = 0; i < num * sample_size; ++i) PP_REQUIRE(samples[i] >= 0 && samples[i] < h->n, "pp_planar_solve_batch: sample index out of range");
   PP_HIP_TRY(hipSetDevice(h->device));
-  int rc = PlanarEnsure(h, num); if (rc) return rc;
-  rc = Upload(h->samples, samples, (size_t)num * sample_size, h->stream); if (rc) return rc;
-  hipLaunchKernelGGL(k_planar_solve, dim3(CeilDiv(num, 64)), dim3(64), 0, h->stream, h->n, h->lines, h->d_poses, h->d_Rg, num, sample_size, h->samples, h->offsets);
-  PP_HIP_TRY(hipGetLastError());
-  rc = Download(offsets, h->offsets, (size_t)num * 3, h->stream); if (rc) return rc;
-  PP_HIP_TRY(hipStreamSynchronize(h->stream));
-  return PP_OK;
+  PP_TRY(PlanarEnsure(h, num));
+  return SolveBatch(h, samples, (size_t)num * sample_size, [&] { PlanarLaunchSolve(h, num, sample_size); }, offsets, h->offsets, (size_t)num * 3);
 } PP_API_CATCH("pp_planar_solve_batch")
 
 int pp_planar_score(pp_planar_handle h, int32_t num, const double* offsets, double thr, double* msac, int32_t* inl) try {
   PP_REQUIRE(h && num >= 0 && (num == 0 || (offsets && msac && inl)), "pp_planar_score: bad argument");
   if (num == 0) return PP_OK;
   PP_HIP_TRY(hipSetDevice(h->device));
-  int rc = PlanarEnsure(h, num); if (rc) return rc;
-  rc = Upload(h->offsets, offsets, (size_t)num * 3, h->stream); if (rc) return rc;
-  hipLaunchKernelGGL(k_planar_score, dim3(CeilDiv(num, 4)), dim3(256), 0, h->stream, h->n, h->rec, h->view, num, h->offsets, thr, h->scores, h->inl);
-  PP_HIP_TRY(hipGetLastError());
-  rc = Download(msac, h->scores, (size_t)num, h->stream); if (rc) return rc;
-  rc = Download(inl, h->inl, (size_t)num, h->stream); if (rc) return rc;
-  PP_HIP_TRY(hipStreamSynchronize(h->stream));
-  return PP_OK;
+  PP_TRY(PlanarEnsure(h, num));
+  return ScoreBatch(h, h->offsets, offsets, (size_t)num * 3, [&] { PlanarLaunchScore(h, num, thr); }, num, msac, inl);
 } PP_API_CATCH("pp_planar_score")
 
 int pp_planar_evaluate(pp_planar_handle h, const double* offsets, double* errors, double* X, double* cams_out) try {
   PP_REQUIRE(h && offsets && errors, "pp_planar_evaluate: bad argument");
   PP_HIP_TRY(hipSetDevice(h->device));
   hipLaunchKernelGGL(k_planar_evaluate, dim3(CeilDiv(h->n, 256)), dim3(256), 0, h->stream, h->n, h->rec, h->view, offsets[0], offsets[1], offsets[2], h->err, h->X);
-  PP_HIP_TRY(hipGetLastError());
-  int rc = Download(errors, h->err, (size_t)h->n, h->stream); if (rc) return rc;
-  if (X) { rc = Download(X, h->X, (size_t)3 * h->n, h->stream); if (rc) return rc; }
-  PP_HIP_TRY(hipStreamSynchronize(h->stream));
+  PP_TRY(ErrorsBack(h, errors, X, h->X, (size_t)3 * h->n));
   if (cams_out) CamsFromOffsets(h, offsets, cams_out);
   return PP_OK;
 } PP_API_CATCH("pp_planar_evaluate")
 
 int pp_planar_lomsac(pp_planar_handle h, const pp_lomsac_options* o, pp_lomsac_report* rep, double* offsets_out, double* cams_out, int32_t* inlier_indices) try {
-  PP_REQUIRE(h && o && rep, "pp_planar_lomsac: null argument");
-  PP_REQUIRE(o->num_lsq_iterations >= 2 && o->num_lo_steps >= 0, "pp_planar_lomsac: bad options");
+  PP_TRY(LomsacCheck(h && o && rep, o, "pp_planar_lomsac"));
   PP_HIP_TRY(hipSetDevice(h->device));
-  PlanarBackend be{h, o->squared_inlier_threshold, {}, PP_OK};
-  Offsets best;
+  PlanarBackend be{{h, o->squared_inlier_threshold}};
+  std::array<double, 3> best;
   std::vector<int> inliers;
-  const int rc = LoMsacRun(o, be, rep, &best, &inliers);
-  if (rc) return rc;
-  if (inlier_indices) for (size_t i = 0; i < inliers.size(); ++i) inlier_indices[i] = inliers[i];
+  PP_TRY(LomsacRun(o, be, rep, &best, &inliers));
+  CopyInliers(inliers, inlier_indices);
   if (offsets_out) for (int k = 0; k < 3; ++k) offsets_out[k] = best[k];
   if (cams_out) CamsFromOffsets(h, best.data(), cams_out);
   return PP_OK;
 } PP_API_CATCH("pp_planar_lomsac")
 
-
 int pp_pose2d_destroy(pp_pose2d_handle h) try {
-  if (!h) return PP_OK;
-  (void)hipSetDevice(h->device);
-  h->blocks.Release();      // (plain device memory: freeing it waits for the device)
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return PP_OK;
+  return EstimatorDestroy(h);
 } PP_API_CATCH("pp_pose2d_destroy")
 
 int pp_pose2d_create(int32_t n, const double* x, const double* X, int device, pp_pose2d_handle* out) try {
   PP_REQUIRE(out && n > 0 && x && X, "pp_pose2d_create: bad argument");
   *out = nullptr;
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "pp_pose2d_create: device %d of %d", device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
-  std::vector<double> xn(x, x + (size_t)2 * n);      // (before the handle: on an error return the handle's release - of plain device memory, which waits for the device - comes first)
+  std::vector<double> xn(x, x + (size_t)2 * n);      // (before the handle: EstimatorOpen)
   UnderConstruction<pp_pose2d_impl, pp_pose2d_destroy> h{new pp_pose2d_impl()};
-  h->device = device; h->n = n;
+  PP_TRY(EstimatorOpen(h.h, "pp_pose2d_create", device, n));
   for (int i = 0; i < n; ++i) { const double nr = std::sqrt(xn[2 * i] * xn[2 * i] + xn[2 * i + 1] * xn[2 * i + 1]); xn[2 * i] /= nr; xn[2 * i + 1] /= nr; }   // sfm2d.h:104-109
-  PP_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  PP_HIP_TRY(hipEventCreate(&h->ev0)); PP_HIP_TRY(hipEventCreate(&h->ev1));
   PP_TRY(h->blocks.Put(&h->x, xn.data(), xn.size(), h->stream)); PP_TRY(h->blocks.Put(&h->X, X, (size_t)2 * n, h->stream)); PP_TRY(h->blocks.Alloc(&h->err, (size_t)n));
   PP_HIP_TRY(hipStreamSynchronize(h->stream));
   *out = h.release();
@@ -1462,27 +1278,16 @@ int pp_pose2d_solve_batch(pp_pose2d_handle h, int64_t num, int32_t sample_size, 
   if (num == 0) return PP_OK;
   for (int64_t i = 0; i < num * sample_size; ++i) PP_REQUIRE(samples[i] >= 0 && samples[i] < h->n, "pp_pose2d_solve_batch: sample index out of range");
   PP_HIP_TRY(hipSetDevice(h->device));
-  int rc = Pose2dEnsure(h, num, sample_size); if (rc) return rc;
-  rc = Upload(h->samples, samples, (size_t)num * sample_size, h->stream); if (rc) return rc;
-  hipLaunchKernelGGL(k_pose2d_solve, dim3(CeilDiv(num, 64)), dim3(64), 0, h->stream, h->n, h->x, h->X, num, sample_size, h->samples, h->poses);
-  PP_HIP_TRY(hipGetLastError());
-  rc = Download(poses, h->poses, (size_t)num * 6, h->stream); if (rc) return rc;
-  PP_HIP_TRY(hipStreamSynchronize(h->stream));
-  return PP_OK;
+  PP_TRY(Pose2dEnsure(h, num, sample_size));
+  return SolveBatch(h, samples, (size_t)num * sample_size, [&] { Pose2dLaunchSolve(h, num, sample_size); }, poses, h->poses, (size_t)num * 6);
 } PP_API_CATCH("pp_pose2d_solve_batch")
 
 int pp_pose2d_score(pp_pose2d_handle h, int32_t num, const double* poses, double thr, double* msac, int32_t* inl) try {
   PP_REQUIRE(h && num >= 0 && (num == 0 || (poses && msac && inl)), "pp_pose2d_score: bad argument");
   if (num == 0) return PP_OK;
   PP_HIP_TRY(hipSetDevice(h->device));
-  int rc = Pose2dEnsure(h, num, 3); if (rc) return rc;
-  rc = Upload(h->poses, poses, (size_t)num * 6, h->stream); if (rc) return rc;
-  hipLaunchKernelGGL(k_pose2d_score, dim3(CeilDiv(num, 4)), dim3(256), 0, h->stream, h->n, h->x, h->X, num, h->poses, thr, h->scores, h->inl);
-  PP_HIP_TRY(hipGetLastError());
-  rc = Download(msac, h->scores, (size_t)num, h->stream); if (rc) return rc;
-  rc = Download(inl, h->inl, (size_t)num, h->stream); if (rc) return rc;
-  PP_HIP_TRY(hipStreamSynchronize(h->stream));
-  return PP_OK;
+  PP_TRY(Pose2dEnsure(h, num, 3));
+  return ScoreBatch(h, h->poses, poses, (size_t)num * 6, [&] { Pose2dLaunchScore(h, num, thr); }, num, msac, inl);
 } PP_API_CATCH("pp_pose2d_score")
 
 int pp_pose2d_evaluate(pp_pose2d_handle h, const double* pose, double* errors) try {
@@ -1492,50 +1297,32 @@ int pp_pose2d_evaluate(pp_pose2d_handle h, const double* pose, double* errors) t
   if (!h->err) PP_TRY(h->blocks.Alloc(&h->err, (size_t)h->n));
   rc = Upload(h->poses, pose, 6, h->stream); if (rc) return rc;
   hipLaunchKernelGGL(k_pose2d_evaluate, dim3(CeilDiv(h->n, 256)), dim3(256), 0, h->stream, h->n, h->x, h->X, h->poses, h->err);
-  PP_HIP_TRY(hipGetLastError());
-  rc = Download(errors, h->err, (size_t)h->n, h->stream); if (rc) return rc;
-  PP_HIP_TRY(hipStreamSynchronize(h->stream));
-  return PP_OK;
+  return ErrorsBack(h, errors);
 } PP_API_CATCH("pp_pose2d_evaluate")
 
 int pp_pose2d_lomsac(pp_pose2d_handle h, const pp_lomsac_options* o, pp_lomsac_report* rep, double* pose_out, int32_t* inlier_indices) try {
-  PP_REQUIRE(h && o && rep, "pp_pose2d_lomsac: null argument");
-  PP_REQUIRE(o->num_lsq_iterations >= 2 && o->num_lo_steps >= 0, "pp_pose2d_lomsac: bad options");
+  PP_TRY(LomsacCheck(h && o && rep, o, "pp_pose2d_lomsac"));
   PP_HIP_TRY(hipSetDevice(h->device));
-  Pose2dBackend be{h, o->squared_inlier_threshold, {}, PP_OK};
+  Pose2dBackend be{{h, o->squared_inlier_threshold}};
   std::array<double, 6> best;
   std::vector<int> inliers;
-  const int rc = LoMsacRun(o, be, rep, &best, &inliers);
-  if (rc) return rc;
-  if (inlier_indices) for (size_t i = 0; i < inliers.size(); ++i) inlier_indices[i] = inliers[i];
+  PP_TRY(LomsacRun(o, be, rep, &best, &inliers));
+  CopyInliers(inliers, inlier_indices);
   if (pose_out) for (int k = 0; k < 6; ++k) pose_out[k] = best[k];
   return PP_OK;
 } PP_API_CATCH("pp_pose2d_lomsac")
 
 int pp_fourview2d_destroy(pp_fourview2d_handle h) try {
-  if (!h) return PP_OK;
-  (void)hipSetDevice(h->device);
-  h->blocks.Release();      // (plain device memory: freeing it waits for the device)
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return PP_OK;
+  return EstimatorDestroy(h);
 } PP_API_CATCH("pp_fourview2d_destroy")
 
 int pp_fourview2d_create(int32_t n, const double* x, int device, pp_fourview2d_handle* out) try {
   PP_REQUIRE(out && n > 0 && x, "pp_fourview2d_create: bad argument");
   *out = nullptr;
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "pp_fourview2d_create: device %d of %d", device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
-  std::vector<double> xn(x, x + (size_t)8 * n);      // (before the handle: on an error return the handle's release - of plain device memory, which waits for the device - comes first)
+  std::vector<double> xn(x, x + (size_t)8 * n);      // (before the handle: EstimatorOpen)
   UnderConstruction<pp_fourview2d_impl, pp_fourview2d_destroy> h{new pp_fourview2d_impl()};
-  h->device = device; h->n = n;
+  PP_TRY(EstimatorOpen(h.h, "pp_fourview2d_create", device, n));
   for (size_t i = 0; i < (size_t)4 * n; ++i) { const double nr = std::sqrt(xn[2 * i] * xn[2 * i] + xn[2 * i + 1] * xn[2 * i + 1]); xn[2 * i] /= nr; xn[2 * i + 1] /= nr; }   // sfm2d.h:62-67
-  PP_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  PP_HIP_TRY(hipEventCreate(&h->ev0)); PP_HIP_TRY(hipEventCreate(&h->ev1));
   PP_TRY(h->blocks.Put(&h->x, xn.data(), xn.size(), h->stream)); PP_TRY(h->blocks.Alloc(&h->err, (size_t)n)); PP_TRY(h->blocks.Alloc(&h->X, (size_t)2 * n));
   PP_HIP_TRY(hipStreamSynchronize(h->stream));
   *out = h.release();
@@ -1546,53 +1333,29 @@ int pp_fourview2d_score(pp_fourview2d_handle h, int32_t num, const double* cams,
   PP_REQUIRE(h && num >= 0 && (num == 0 || (cams && msac && inl)), "pp_fourview2d_score: bad argument");
   if (num == 0) return PP_OK;
   PP_HIP_TRY(hipSetDevice(h->device));
-  if (num > h->cap) {
-    DeviceBlocks& B = h->blocks;
-    B.Free(&h->cams); B.Free(&h->scores); B.Free(&h->inl);
-    h->cap = 0;
-    PP_TRY(B.Alloc(&h->cams, (size_t)num * 24)); PP_TRY(B.Alloc(&h->scores, (size_t)num)); PP_TRY(B.Alloc(&h->inl, (size_t)num));
-    h->cap = num;
-  }
-  int rc = Upload(h->cams, cams, (size_t)num * 24, h->stream); if (rc) return rc;
-  hipLaunchKernelGGL(k_fourview2d_score, dim3(CeilDiv(num, 4)), dim3(256), 0, h->stream, h->n, h->x, num, h->cams, thr, h->scores, h->inl);
-  PP_HIP_TRY(hipGetLastError());
-  rc = Download(msac, h->scores, (size_t)num, h->stream); if (rc) return rc;
-  rc = Download(inl, h->inl, (size_t)num, h->stream); if (rc) return rc;
-  PP_HIP_TRY(hipStreamSynchronize(h->stream));
-  return PP_OK;
+  PP_TRY(FourViewEnsureScore(h, num));
+  return ScoreBatch(h, h->cams, cams, (size_t)num * 24,
+                    [&] { hipLaunchKernelGGL(k_fourview2d_score, dim3(CeilDiv(num, 4)), dim3(256), 0, h->stream, h->n, h->x, num, h->cams, thr, h->scores, h->inl); },
+                    num, msac, inl);
 } PP_API_CATCH("pp_fourview2d_score")
 
 int pp_fourview2d_evaluate(pp_fourview2d_handle h, const double* cams, double* errors, double* X) try {
   PP_REQUIRE(h && cams && errors, "pp_fourview2d_evaluate: bad argument");
   PP_HIP_TRY(hipSetDevice(h->device));
-  if (h->cap < 1) {
-    PP_TRY(h->blocks.Alloc(&h->cams, 24)); PP_TRY(h->blocks.Alloc(&h->scores, 1)); PP_TRY(h->blocks.Alloc(&h->inl, 1));
-    h->cap = 1;
-  }
+  PP_TRY(FourViewEnsureScore(h, 1));
   int rc = Upload(h->cams, cams, 24, h->stream); if (rc) return rc;
   hipLaunchKernelGGL(k_fourview2d_evaluate, dim3(CeilDiv(h->n, 256)), dim3(256), 0, h->stream, h->n, h->x, h->cams, h->err, h->X);
-  PP_HIP_TRY(hipGetLastError());
-  rc = Download(errors, h->err, (size_t)h->n, h->stream); if (rc) return rc;
-  if (X) { rc = Download(X, h->X, (size_t)2 * h->n, h->stream); if (rc) return rc; }
-  PP_HIP_TRY(hipStreamSynchronize(h->stream));
-  return PP_OK;
+  return ErrorsBack(h, errors, X, h->X, (size_t)2 * h->n);
 } PP_API_CATCH("pp_fourview2d_evaluate")
-
 
 int pp_fourview2d_evaluate_points(pp_fourview2d_handle h, const double* cams, const double* X, double* errors) try {
   PP_REQUIRE(h && cams && X && errors, "pp_fourview2d_evaluate_points: bad argument");
   PP_HIP_TRY(hipSetDevice(h->device));
-  if (h->cap < 1) {
-    PP_TRY(h->blocks.Alloc(&h->cams, 24)); PP_TRY(h->blocks.Alloc(&h->scores, 1)); PP_TRY(h->blocks.Alloc(&h->inl, 1));
-    h->cap = 1;
-  }
+  PP_TRY(FourViewEnsureScore(h, 1));
   int rc = Upload(h->cams, cams, 24, h->stream); if (rc) return rc;
   rc = Upload(h->X, X, (size_t)2 * h->n, h->stream); if (rc) return rc;
   hipLaunchKernelGGL(k_fourview2d_errors_stored, dim3(CeilDiv(h->n, 256)), dim3(256), 0, h->stream, h->n, h->x, h->cams, h->X, h->err);
-  PP_HIP_TRY(hipGetLastError());
-  rc = Download(errors, h->err, (size_t)h->n, h->stream); if (rc) return rc;
-  PP_HIP_TRY(hipStreamSynchronize(h->stream));
-  return PP_OK;
+  return ErrorsBack(h, errors);
 } PP_API_CATCH("pp_fourview2d_evaluate_points")
 
 int pp_fourview2d_default_frames(double* frames) try {
@@ -1631,18 +1394,13 @@ int pp_fourview2d_nonminimal_batch(pp_fourview2d_handle h, int64_t num, int32_t 
   PP_REQUIRE(h && num >= 0 && sample_size >= 5 && (num == 0 || (samples && cams && msac_score)), "pp_fourview2d_nonminimal_batch: bad argument");
   if (num == 0) return PP_OK;
   PP_HIP_TRY(hipSetDevice(h->device));
-  int rc = FourViewLaunchMinimal(h, num, sample_size, samples, frames); if (rc) return rc;
-  hipLaunchKernelGGL(k_fourview2d_score, dim3(CeilDiv(num * 16, 4)), dim3(256), 0, h->stream, h->n, h->x, (int)(num * 16), h->models, threshold, h->mscores, h->minl);
-  hipLaunchKernelGGL(k_fourview2d_select, dim3(CeilDiv(num, 64)), dim3(64), 0, h->stream, num, h->counts, h->mscores, h->models, h->best_cams, h->best_score,
-                     h->best_index);
-  PP_HIP_TRY(hipGetLastError());
+  int rc = FourView2dBackend{h, threshold, frames, {}, PP_OK}.SolveBestAsync(num, sample_size, samples); if (rc) return rc;
   rc = Download(cams, h->best_cams, (size_t)num * 24, h->stream); if (rc) return rc;
   rc = Download(msac_score, h->best_score, (size_t)num, h->stream); if (rc) return rc;
   if (model_index) { rc = Download(model_index, h->best_index, (size_t)num, h->stream); if (rc) return rc; }
   PP_HIP_TRY(hipStreamSynchronize(h->stream));
   return PP_OK;
 } PP_API_CATCH("pp_fourview2d_nonminimal_batch")
-
 
 int pp_fourview2d_least_squares(pp_fourview2d_handle h, int32_t m, const int32_t* sample, double* cams_inout, double* X_inout) try {
   PP_REQUIRE(h && m >= 0 && (m == 0 || sample) && cams_inout && X_inout, "pp_fourview2d_least_squares: bad argument");
@@ -1672,8 +1430,7 @@ int pp_fourview2d_least_squares(pp_fourview2d_handle h, int32_t m, const int32_t
 
 int pp_fourview2d_lomsac(pp_fourview2d_handle h, const pp_lomsac_options* o, const double* frames, pp_lomsac_report* rep, double* cams_out, double* X_out,
                          int32_t* inlier_indices) try {
-  PP_REQUIRE(h && o && rep, "pp_fourview2d_lomsac: null argument");
-  PP_REQUIRE(o->num_lsq_iterations >= 2 && o->num_lo_steps >= 0, "pp_fourview2d_lomsac: bad options");
+  PP_TRY(LomsacCheck(h && o && rep, o, "pp_fourview2d_lomsac"));
   PP_HIP_TRY(hipSetDevice(h->device));
   double def[12];
   if (!frames) { pp_fourview2d_default_frames(def); frames = def; }
@@ -1682,7 +1439,7 @@ int pp_fourview2d_lomsac(pp_fourview2d_handle h, const pp_lomsac_options* o, con
   std::array<double, 25> best;
   std::vector<int> inliers;
   FourViewPoolReset(h);
-  rc = LoMsacRun(o, be, rep, &best, &inliers);
+  rc = LomsacRun(o, be, rep, &best, &inliers);
   if (!rc) rc = be.ModelCams(best.data());      // (a model refined by the final least squares: its cameras are still on the device)
   if (!rc && X_out) {     // the best model's points (its own if it was refined, the three-view triangulation otherwise)
     const double* Xd = be.ModelPoints(best.data());
@@ -1692,7 +1449,7 @@ int pp_fourview2d_lomsac(pp_fourview2d_handle h, const pp_lomsac_options* o, con
   }
   be.FreeSlots();
   if (rc) return rc;
-  if (inlier_indices) for (size_t i = 0; i < inliers.size(); ++i) inlier_indices[i] = inliers[i];
+  CopyInliers(inliers, inlier_indices);
   if (cams_out) for (int k = 0; k < 24; ++k) cams_out[k] = best[k];
   return PP_OK;
 } PP_API_CATCH("pp_fourview2d_lomsac")
