@@ -1,5 +1,5 @@
-// Internal state of a pp_ba_handle: device-resident problem structure, parameter blocks, the
-// materialised residual/Jacobian buffers of K1 and the normal-equation / Schur workspaces.
+// Internal state of a pp_ba_handle: device-resident problem structure (built on the host by the stages of ba_structure.hpp, put up by pp_ba_create:
+// ba_create.hip), parameter blocks, the materialised residual/Jacobian buffers of K1 and the normal-equation / Schur workspaces.
 //
 // HBM layout (all fp64 unless noted; M observations, C poses, P points, K intrinsics blocks):
 //   static   : line (a,b,c) as three SoA streams la/lb/lc [M] (coalesced 8 B/lane reads),
@@ -18,7 +18,7 @@
 #include <functional>
 #include <vector>
 
-#include "common.hpp"
+#include "common.hpp"      // (with ba_structure.hpp)
 #include "resource_pool.hpp"
 #include "switches.hpp"
 
@@ -33,8 +33,6 @@ __device__ __forceinline__ const double* RecT(const double* rec, size_t o) { ret
 __device__ __forceinline__ const double* RecJ(const double* rec, size_t o) { return rec + kRecStride * o + 6; }
 __device__ __forceinline__ const double* RecX(const double* rec, size_t o) { return rec + kRecStride * o + 18; }
 #endif
-// closes a T x T lower-triangular tile map under the fill-in of a Cholesky factorisation (in place); returns the number of non-zero tiles
-int SymbolicTileFill(int T, uint8_t* nz);
 // chain steps of the one-launch factorisation of a T x T tile map (closed under fill-in): the block columns on the longest dependency path when its
 // elimination tree has independent sub-trees (several chains, cholesky.hip), T otherwise; *chains (may be null): the number of chains
 int CholeskyChainSteps(int T, const uint8_t* nz, const Switches& sw, int* chains = nullptr);
@@ -213,8 +211,6 @@ int BaEnsureJacobianBuffers(pp_ba_impl* h, int jac_mode, int want_cam);
 int LaunchEval(pp_ba_impl* h, int jac_mode, int want_cam, bool loss_correct, const double* poses, const double* points,
                double* cost_slot, bool compact_cam = false);
 int LaunchCostOnly(pp_ba_impl* h, const double* poses, const double* points, const double* intr, double* cost_slot);
-constexpr int kGenChunk = 32;      // list entries per chunk of a generic block pair (256: twelve lanes walked a chunk for ~200 us with one wavefront per CU)
-constexpr int kIsumChunk = 2048;   // observations per chunk of a per-camera sum
 // variable-intrinsics part of the LM iteration (ba_intr.hip)
 int IntrSumsAfterEval(pp_ba_impl* h);                                   // column norms^2 -> cnI, gradient -> gc[6C..]
 int IntrScale(pp_ba_impl* h, int jacobi);                               // Jacobi scale of the intrinsics columns

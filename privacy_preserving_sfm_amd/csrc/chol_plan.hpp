@@ -101,7 +101,6 @@ inline int WholeFrom(int T) { return T >= 56 ? 2 : 3; }
 constexpr bool StepOwnsTile(int k, int r, int c) { return (r == k + 1 && c == k + 1) || (r == k + 2 && (c == k + 1 || c == k + 2)); }
 
 // Symbolic Cholesky on the tile graph: eliminating block column k couples every pair of rows that have a non-zero tile in it.
-// (SymbolicTileFill of ba_impl.hpp, which the other translation units call, is this function: cholesky.hip)
 inline int CloseTileMap(int T, uint8_t* nz) {
   for (int i = 0; i < T; ++i) nz[(size_t)i * T + i] = 1;
   std::vector<int> rows;

@@ -14,7 +14,7 @@
 //   task mode     (k_cholesky_tasks, 4 to 128 block columns, dense or block-sparse) the whole factorisation in ONE launch: a persistent chain
 //                 workgroup + one workgroup per item of a priority-sorted task list, per-tile dependency counters, mailbox
 //                 hand-offs - see "task mode" below; a block-sparse system whose elimination tree has independent sub-trees (a nested-dissection
-//                 order of the cameras, ba_eval.hip DissectBand) gets a chain workgroup per sub-tree - see "ChainRanges";
+//                 order of the cameras, image_ordering.hip DissectBand) gets a chain workgroup per sub-tree - see "ChainRanges";
 //   column mode   (k_column_step: 3 or more than 128 block columns, PPSFM_CHOL_MODE=columns, a task list that failed its host replay, and
 //                 after a fallback) one launch per block column, over every tile or, for a block-sparse system, over its non-zero tiles only
 //                 (the per-launch lists of EnsureSparseLists); captured into a graph once per bind and replayed.
@@ -1622,8 +1622,6 @@ __global__ __launch_bounds__(kPairThreads) void k_backsub_pairs(const double* __
 // (Four consecutive blocks per workgroup - 12 hand-offs between workgroups instead of 47, the hops inside a group through LDS - was
 // measured at 98 us against 62 us: the x_k of the group above arrive as a burst, and the 4 x 4 tiles they multiply (512 KB) have no
 // place on the CU to wait in, so their loads queue up behind each other on the critical path; see DESIGN.md.)
-// (the planner's CloseTileMap under the name the other translation units call it by: ba_impl.hpp)
-int SymbolicTileFill(int T, uint8_t* nz) { return CloseTileMap(T, nz); }
 
 enum class CholPath { Small, Tasks, Columns, SparseColumns };      // the launch path of a bound system (ChoosePath)
 
@@ -2050,7 +2048,7 @@ extern "C" int pp_dense_cholesky_solve(int32_t n, const double* A, const double*
       for (int i = 0; i < N; ++i)
         for (int j = 0; j <= i; ++j)
           if (h[(size_t)i * N + j] != 0.0) tile_nz[(size_t)(i / kNB) * T + j / kNB] = 1;
-      if (SymbolicTileFill(T, tile_nz.data()) == T * (T + 1) / 2) tile_nz.clear();      // (nothing to skip: dense)
+      if (CloseTileMap(T, tile_nz.data()) == T * (T + 1) / 2) tile_nz.clear();      // (nothing to skip: dense)
     }
   }
   PP_TRY(CholeskyBind(st, CholeskySystem{dS, N, n, dLinv, dL, dx, dflag, strm}, tile_nz.empty() ? nullptr : tile_nz.data()));

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/ppsfm_hip.h"
+#include "ba_structure.hpp"      // (std-only: kCamStride, the host stages of pp_ba_create)
 
 namespace ppsfm {
 
@@ -76,7 +77,6 @@ inline void ParallelFor(int nthreads, Body&& body) {
 }
 
 constexpr int kWave = 64;          // gfx950 wavefront
-constexpr int kCamStride = 12;     // doubles per intrinsics block (max kNumParams of the 11 models)
 
 template <typename T>
 inline int Upload(T* dst, const T* src, size_t count, hipStream_t s) {

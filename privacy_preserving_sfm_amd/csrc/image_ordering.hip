@@ -432,16 +432,9 @@ int PrivateIntrinsicsColumns(const pp_ba_problem_desc* d, IntrLayout layout) {
 // the variable intrinsics columns of a problem (pp_ba_create's layout: block k at intr_off[k])
 int CountVariableIntrinsics(const pp_ba_problem_desc* d) {
   if (!d->camera_const_mask) return 0;
-  const int C = d->num_poses, K = d->num_cameras;
-  std::vector<char> cam_used(K, 0);
-  for (int c = 0; c < C; ++c) cam_used[d->pose_camera[c]] = 1;
-  int NI = 0;
-  for (int k = 0; k < K; ++k) {
-    if (!cam_used[k]) continue;
-    const int np = CameraNumParams(d->camera_model[k]);
-    for (int j = 0; j < np; ++j) if (!((d->camera_const_mask[k] >> j) & 1)) ++NI;
-  }
-  return NI;
+  std::vector<int32_t> np;
+  for (int k = 0; k < d->num_cameras; ++k) np.push_back(CameraNumParams(d->camera_model[k]));
+  return LayOutIntrinsics(d->num_poses, d->num_cameras, d->pose_camera, np.data(), d->camera_const_mask).NI;
 }
 
 // Co-visibility of the variable images (two images are neighbours when a variable point is seen by both) as a bit matrix, filled point by point.
@@ -591,7 +584,7 @@ ImageOrdering ChooseImageOrdering(const pp_ba_problem_desc* d, int NI, const Swi
     for (int c = 0; c < C; ++c) { mark_t(W6 * at(c), W6 * at(c)); for (int c2 : adj[c]) if (c2 < c) mark_t(W6 * at(c), W6 * at(c2)); }
     for (int ti = tail0 / 64; ti <= (tail0 + NI_tail) / 64; ++ti)      // the shared intrinsics rows (they couple with every image) and the right-hand side's row
       for (int tj = 0; tj <= ti; ++tj) (*nz)[(size_t)ti * Tt + tj] = 1;
-    return SymbolicTileFill(Tt, nz->data());
+    return CloseTileMap(Tt, nz->data());
   };
   // what a candidate costs: the chain steps of its factorisation (the block columns on the longest dependency path when the block-sparse one-launch mode
   // takes it, all of them otherwise) - from the plan alone; the winner's list is verified below
@@ -716,7 +709,7 @@ extern "C" int pp_ba_plan_ordering(const pp_ba_problem_desc* d, int32_t* old_of_
         if ((d->covisibility[(size_t)i * C + j] || d->covisibility[(size_t)j * C + i]) && (nvp > 0 || !(d->pose_const && (d->pose_const[i] || d->pose_const[j])))) mark(W6 * at(i), W6 * at(j));
     for (int ti = tail0 / 64; ti <= (tail0 + NI_tail) / 64; ++ti) for (int tj = 0; tj <= ti; ++tj) nz[(size_t)ti * Tt + tj] = 1;
   }
-  const int nnz = SymbolicTileFill(Tt, nz.data());
+  const int nnz = CloseTileMap(Tt, nz.data());
   const bool sparse_path = Tt >= 8 && (int64_t)nnz * 10 <= (int64_t)Tt * (Tt + 1) / 2 * 7;
   int chains = 1;
   const int steps = sparse_path && Tt <= 128 ? CholeskyChainSteps(Tt, nz.data(), sw, &chains) : Tt;

@@ -1,7 +1,7 @@
 // The Schur pair lists of pp_ba_create, built on the device.
 //
 // For every pair of variable images (ci >= cj) that share a variable point: the (observation of ci, observation of cj) pairs, lists in (ci, cj)
-// order, a list's entries in (oi, oj) order (what k_schur_pairs / k_schur_blocks / the chunk kernels walk; csrc/ba_eval.hip builds the same lists on
+// order, a list's entries in (oi, oj) order (what k_schur_pairs / k_schur_blocks / the chunk kernels walk; csrc/ba_create.hip builds the same lists on
 // the host for small problems and as the fallback).  The mapper builds a new BundleAdjuster per global bundle adjustment
 // (src/sfm/incremental_mapper.cc:893-936), and on the host these lists were the largest part of a create (4-8 ms at 200k observations: 1.6 M visits of the
 // tracks for 0.7 M entries, memory-bound on one to eight host threads).  Here, with the by-point lists already uploaded:
@@ -338,12 +338,10 @@ void BuildPairListsOnHost(int C, int P, int64_t M, const int32_t* pt_start, cons
         for (size_t q = l0 + 1; q < l1 && sorted; ++q)
           sorted = pair_entries[2 * q - 2] < pair_entries[2 * q] || (pair_entries[2 * q - 2] == pair_entries[2 * q] && pair_entries[2 * q - 1] <= pair_entries[2 * q + 1]);
         if (!sorted) {
-          int64_t* le = reinterpret_cast<int64_t*>(pair_entries.data() + 2 * l0);      // (oi, oj) pairs as they lie: sorted as pairs
           std::vector<std::pair<int32_t, int32_t>> tmp(l1 - l0);
           for (size_t q = l0; q < l1; ++q) tmp[q - l0] = {pair_entries[2 * q], pair_entries[2 * q + 1]};
           std::sort(tmp.begin(), tmp.end());
           for (size_t q = l0; q < l1; ++q) { pair_entries[2 * q] = tmp[q - l0].first; pair_entries[2 * q + 1] = tmp[q - l0].second; }
-          (void)le;
         }
       }
     }
@@ -370,20 +368,12 @@ extern "C" int pp_ba_pair_lists_host(const pp_ba_problem_desc* d, int32_t thread
   PP_REQUIRE(C > 0 && P > 0 && M >= 0 && M < ((int64_t)1 << 31), "pp_ba_pair_lists_host: empty or oversized problem");
   for (int64_t o = 0; o < M; ++o)
     PP_REQUIRE(d->obs_pose[o] >= 0 && d->obs_pose[o] < C && d->obs_point[o] >= 0 && d->obs_point[o] < P, "pp_ba_pair_lists_host: observation %lld indexes out of range", (long long)o);
-  std::vector<int32_t> pt_start(P + 1, 0), pt_obs(M);      // CSR by point (counting sort keeps observation order inside a group), as pp_ba_create
-  for (int64_t o = 0; o < M; ++o) pt_start[d->obs_point[o] + 1]++;
-  for (int p = 0; p < P; ++p) pt_start[p + 1] += pt_start[p];
-  { std::vector<int32_t> f(pt_start.begin(), pt_start.end() - 1); for (int64_t o = 0; o < M; ++o) pt_obs[f[d->obs_point[o]]++] = (int32_t)o; }
+  std::vector<int32_t> pt_start, pt_obs;      // CSR by point, as pp_ba_create
+  GroupByKey(M, P, [d](int64_t o) { return d->obs_point[o]; }, &pt_start, &pt_obs);
   std::vector<uint8_t> list_const(C, 0), point_const(P, 0);
   if (d->pose_const) std::memcpy(list_const.data(), d->pose_const, C);
   if (d->point_const) std::memcpy(point_const.data(), d->point_const, P);
-  int64_t bound = 0;      // (pp_ba_create's 32-bit check)
-  for (int p = 0; p < P; ++p) {
-    if (point_const[p]) continue;
-    int64_t nv = 0;
-    for (int e = pt_start[p]; e < pt_start[p + 1]; ++e) nv += list_const[d->obs_pose[pt_obs[e]]] ? 0 : 1;
-    bound += nv * (nv - 1);
-  }
+  const int64_t bound = PairEntryBound(P, pt_start.data(), pt_obs.data(), d->obs_pose, list_const.data(), point_const.data());      // (pp_ba_create's 32-bit check)
   PP_REQUIRE(bound < ((int64_t)1 << 31) - 1, "pp_ba_pair_lists_host: %lld Schur pair entries exceed the 32-bit pair lists", (long long)bound);
   std::vector<int32_t> ps, pij, pe;
   int64_t total = 0;

@@ -22,15 +22,15 @@
 //   PPSFM_CHOL_PLAN_PRINT       set = on                     off              PrintPlan (chains, closed tile map)           debug
 //   PPSFM_BA_LINEAR_SOLVER      letter i|I iterative,        descriptor's     WillIterate (pp_ba_create, SetupOf)           A/B
 //                               d|D direct
-//   PPSFM_BA_SPARSE             atoi, 0 = off                on               pp_ba_create, SetupOf (block-sparse system)   A/B
+//   PPSFM_BA_SPARSE             atoi, 0 = off                on               BuildTileMap, SetupOf (block-sparse system)   A/B
 //   PPSFM_BA_ORDERING           letter n natural, r rcm,     by chain steps   SetupOf, ChooseImageOrdering                 A/B
 //                               b band (any case)
 //   PPSFM_BA_GRAPH_ND           atoi, 0 never / else always  by band cuts     ChooseImageOrdering (graph dissections)      A/B
 //   PPSFM_BA_INTR_LAYOUT        letter t|T tail              beside the pose  PrivateIntrinsicsColumns                     A/B
-//   PPSFM_BA_INTR_WIDE          atoi, 0 = off                on               pp_ba_create (k_schur_wide_* blocks)          A/B
+//   PPSFM_BA_INTR_WIDE          atoi, 0 = off                on               ApplyImageOrder (k_schur_wide_* blocks)       A/B
 //   PPSFM_BA_PAIR_LISTS         letter h|H host, d|D device  by size          PairListsOnDeviceEligible                    A/B
-//   PPSFM_BA_CHUNKED_PAIRS      atoi, 0 = off                on               pp_ba_create (chunked pair lists)             A/B
-//   PPSFM_BA_CHUNK_XCD          atoi, 0 = off                on               pp_ba_create (XCD run order of the chunks)    A/B
+//   PPSFM_BA_CHUNKED_PAIRS      atoi, 0 = off                on               ChunkPairLists (ba_structure.hpp)             A/B
+//   PPSFM_BA_CHUNK_XCD          atoi, 0 = off                on               ChunkPairLists (XCD run order of chunks)      A/B
 //   PPSFM_BA_FUSED_STEP         atoi, 0 = off                on               the LM loop (k_step_points)                  A/B
 //   PPSFM_BA_FUSED_TRIAL_COST   atoi, 0 = off                on               the LM loop (cost inside k_model_cost_apply)  A/B
 //   PPSFM_PCG_FUSED             atoi, 0 = off                on               PcgSolve (three-launch iteration)            A/B

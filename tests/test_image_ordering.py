@@ -1,5 +1,5 @@
 """The image order pp_ba_create gives the reduced camera system - reverse Cuthill-McKee, then a nested dissection of the band whose parts the one-launch
-factorisation runs side by side (csrc/ba_eval.hip: ReverseCuthillMcKee, DissectBand; csrc/cholesky.hip: PlanChains) - computed on the host alone through
+factorisation runs side by side (csrc/image_ordering.hip: ReverseCuthillMcKee, DissectBand; csrc/cholesky.hip: PlanChains) - computed on the host alone through
 pp_ba_plan_ordering.  What Ceres' SPARSE_SCHUR ordering does for the reference between 50 and 1000 images (src/optim/bundle_adjustment.cc:279-282); the
 numerics of the orders are covered on the GPU (tests/test_gpu_bundle_adjustment.py::test_sequence_scene_*)."""
 import numpy as np
