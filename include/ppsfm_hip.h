@@ -654,6 +654,53 @@ int pp_tracks_triangulate_image(pp_tracks_handle h, const pp_tracks_image_option
 int pp_tracks_complete_image(pp_tracks_handle h, const pp_tracks_image_options* options, int32_t image, pp_tracks_image_report* report,
                              int32_t* event_point, int32_t* event_line, int64_t capacity);
 
+/* ---- FindLocalBundle on a pp_tracks_handle (kernels K12a k_local_bundle_count, K12b k_local_bundle_angles) ---------------------------------------
+ * replaces IncrementalMapper::FindLocalBundle (sfm/incremental_mapper.cc:993-1160), the choice of the images that AdjustLocalBundle (:781-891) refines
+ * after every registered image, with CalculateTriangulationAngles (base/triangulation.cc:84-118) and Percentile (util/math.h:232-246).
+ * The device counts, for every other image, the track elements it shares with the points of the query image (one wavefront per line that has a
+ * point) and computes, per image that the sequential loop can ask for, the 75th-percentile triangulation angle over ALL points of the query image
+ * (one workgroup per image, a radix select over the bit patterns: exactly the value the nth_element of the reference leaves at the index, whatever the schedule).
+ * The host replays the sequential rest: the sort, the eight relaxing (angle, overlap) thresholds, the lazy angle, the fill-up.
+ * PINNED where the reference is unspecified: equal counts are ordered by ASCENDING IMAGE INDEX (the reference sorts what an unordered_map hands it);
+ * a NaN angle sorts above every number in the percentile, and a NaN percentile fails every comparison, as in the reference.
+ * The call does not change the handle's state.  ERRORS: PP_ERR_INVALID for an image index out of range, an UNREGISTERED query image (the reference
+ * CHECKs it), local_ba_num_images < 2 or local_ba_min_tri_angle < 0.                                                                            */
+typedef struct pp_local_bundle_options {
+  int32_t local_ba_num_images;      /* 6   (sfm/incremental_mapper.h:77) */
+  int32_t reserved_;
+  double  local_ba_min_tri_angle;   /* 6.0 degrees (:80) */
+} pp_local_bundle_options;
+void pp_local_bundle_options_default(pp_local_bundle_options* o);
+
+typedef struct pp_local_bundle_report {
+  int32_t num_points3D;       /* image.NumPoints3D(): lines of the image that have a point */
+  int32_t num_overlapping;    /* images sharing at least one track element */
+  int32_t num_selected;       /* size of the bundle */
+  int32_t angles_computed;    /* percentiles the device computed (speculation included) */
+  int32_t angles_used;        /* percentiles the sequential loop would have computed (lazy, :1102-1119) */
+  int32_t threshold_level;    /* last of the 8 selection thresholds reached, -1: early return (:1044) */
+  int32_t filled;             /* images taken by the fill-up at the end (:1141-1157) */
+  int32_t reserved_;
+  double device_ms, replay_ms, total_ms;
+} pp_local_bundle_report;
+
+/* bundle: the selected image indices IN THE REFERENCE'S ORDER (AdjustLocalBundle fixes the gauge on the last two);
+ * entries beyond bundle_capacity are not written (report->num_selected counts all).
+ * overlap_image / overlap_count / overlap_tri_angle (C each, any may be NULL): the sorted overlapping list,
+ * tri angle in radians, -1 where the sequential loop never asked for it. */
+int pp_tracks_find_local_bundle(pp_tracks_handle h, const pp_local_bundle_options* options, int32_t image,
+                                pp_local_bundle_report* report, int32_t* bundle, int32_t bundle_capacity,
+                                int32_t* overlap_image, int32_t* overlap_count, double* overlap_tri_angle);
+
+/* New poses / point positions / intrinsics on a live handle (after a bundle adjustment).
+ * Any of the three groups may be empty / NULL.  intr is K x PP_CAM_STRIDE together with camera_skip (K, NULL = none),
+ * re-decided by the caller.  The host state and the device copies change, the projection matrices (and the projection centres) are recomputed:
+ * every later pp_tracks_* call on the handle sees the new values, exactly as a handle created from the updated arrays would.
+ * ERRORS: PP_ERR_INVALID (an index out of range, a deleted point, a non-finite value, camera_skip without intr) leaves the handle as it was. */
+int pp_tracks_update(pp_tracks_handle h, int32_t num_images, const int32_t* image_idx, const double* poses /* x7 */,
+                     int32_t num_points, const int32_t* point_idx, const double* xyz /* x3 */,
+                     const double* intr, const uint8_t* camera_skip);
+
 /* ======================================================================================== *
  *  Four-view line initialisation (LO-MSAC)                                                   *
  *  replaces, for the out-of-plane-translation stage: ransac_lib::LocallyOptimizedMSAC<        *

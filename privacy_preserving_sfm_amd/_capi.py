@@ -132,6 +132,16 @@ class TracksImageReport(C.Structure):
                 ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class LocalBundleOptions(C.Structure):
+    _fields_ = [("local_ba_num_images", C.c_int32), ("reserved_", C.c_int32), ("local_ba_min_tri_angle", C.c_double)]
+
+
+class LocalBundleReport(C.Structure):
+    _fields_ = [("num_points3D", C.c_int32), ("num_overlapping", C.c_int32), ("num_selected", C.c_int32), ("angles_computed", C.c_int32),
+                ("angles_used", C.c_int32), ("threshold_level", C.c_int32), ("filled", C.c_int32), ("reserved_", C.c_int32),
+                ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -162,6 +172,7 @@ _EXPORTS = [
     "pp_triangulate_tracks", "pp_ba_filter_points", "pp_ba_filter_negative_depth", "pp_pose2d_create", "pp_pose2d_destroy", "pp_pose2d_solve_batch", "pp_pose2d_score", "pp_pose2d_evaluate", "pp_pose2d_lomsac",
     "pp_tracks_options_default", "pp_tracks_create", "pp_tracks_destroy", "pp_tracks_complete", "pp_tracks_merge", "pp_tracks_get_state",
     "pp_tracks_image_options_default", "pp_tracks_triangulate_image", "pp_tracks_complete_image",
+    "pp_local_bundle_options_default", "pp_tracks_find_local_bundle", "pp_tracks_update",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -263,6 +274,9 @@ def lib():
     L.pp_tracks_image_options_default.argtypes = [C.POINTER(TracksImageOptions)]
     L.pp_tracks_triangulate_image.argtypes = [C.c_void_p, C.POINTER(TracksImageOptions), C.c_int32, c_u8p, C.POINTER(TracksImageReport), c_ip, c_ip, C.c_int64]
     L.pp_tracks_complete_image.argtypes = [C.c_void_p, C.POINTER(TracksImageOptions), C.c_int32, C.POINTER(TracksImageReport), c_ip, c_ip, C.c_int64]
+    L.pp_local_bundle_options_default.argtypes = [C.POINTER(LocalBundleOptions)]
+    L.pp_tracks_find_local_bundle.argtypes = [C.c_void_p, C.POINTER(LocalBundleOptions), C.c_int32, C.POINTER(LocalBundleReport), c_ip, C.c_int32, c_ip, c_ip, c_dp]
+    L.pp_tracks_update.argtypes = [C.c_void_p, C.c_int32, c_ip, c_dp, C.c_int32, c_ip, c_dp, c_dp, c_u8p]
     L.pp_camera_image_to_world_threshold.argtypes = [C.c_int, c_dp, C.c_double, c_dp]
     _lib = L
     return L

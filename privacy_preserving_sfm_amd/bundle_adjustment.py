@@ -9,7 +9,9 @@ the arrays of `pp_ba_problem_desc`, and hands the solve to the device (`pp_ba_so
 
 Above it, the mapper's global refinement: `Reconstruction.Normalize` (base/reconstruction.cc:302-397), `AdjustGlobalBundle`
 (sfm/incremental_mapper.cc:893-939 with the option preset of controllers/incremental_mapper.cc:52-70, 221-243) and
-`IterativeGlobalRefinement` (controllers/incremental_mapper.cc:102-124).
+`IterativeGlobalRefinement` (controllers/incremental_mapper.cc:102-124); and the local one after every registered image: `FindLocalBundle`
+(sfm/incremental_mapper.cc:993-1160), `AdjustLocalBundle` (:781-891) and `IterativeLocalRefinement` (controllers/incremental_mapper.cc:72-100) on
+one `pp_tracks_handle` of an `incremental_triangulator.IncrementalTriangulator`.
 """
 import numpy as np
 
@@ -254,6 +256,11 @@ class Reconstruction:
             pid = point_ids[scene["obs_point"][o]]
             if od[o] and pid in self.points3D:
                 self.DeleteObservation(iid, idx)
+
+    def FilterPoints3DInImages(self, max_reproj_error, min_tri_angle, image_ids, device=0):
+        """Reconstruction::FilterPoints3DInImages (base/reconstruction.cc:412-426): FilterPoints3D over the points the lines of these images have"""
+        point3D_ids = set(line.Point3DId() for image_id in image_ids for line in self.images[image_id].lines if line.HasPoint3D())
+        return self.FilterPoints3D(max_reproj_error, min_tri_angle, point3D_ids, device=device)
 
     def FilterAllPoints3D(self, max_reproj_error, min_tri_angle, device=0):
         return self.FilterPoints3D(max_reproj_error, min_tri_angle, None, device=device)
@@ -699,6 +706,31 @@ class IncrementalMapperOptions:
         self.filter_max_reproj_error = 4.0
         self.filter_min_tri_angle = 1.5
         self.print_summary = True
+        # the local refinement (controllers/incremental_mapper.h, sfm/incremental_mapper.h:77-80, 98)
+        self.local_ba_num_images = 6
+        self.local_ba_min_tri_angle = 6.0
+        self.fix_existing_images = False
+        self.ba_local_max_num_iterations = 25
+        self.ba_local_max_refinements = 2
+        self.ba_local_max_refinement_change = 0.001
+
+    def LocalBundleAdjustment(self):
+        """controllers/incremental_mapper.cc:196-219"""
+        options = BundleAdjustmentOptions()
+        options.solver_options.function_tolerance = 0.0
+        options.solver_options.gradient_tolerance = 10.0
+        options.solver_options.parameter_tolerance = 0.0
+        options.solver_options.max_num_iterations = self.ba_local_max_num_iterations
+        options.solver_options.max_linear_solver_iterations = 100
+        options.solver_options.minimizer_progress_to_stdout = False
+        options.print_summary = self.print_summary
+        options.refine_focal_length = self.ba_refine_focal_length
+        options.refine_principal_point = self.ba_refine_principal_point
+        options.refine_extra_params = self.ba_refine_extra_params
+        options.min_num_residuals_for_multi_threading = self.ba_min_num_residuals_for_multi_threading
+        options.loss_function_scale = 1.0
+        options.loss_function_type = BundleAdjustmentOptions.SOFT_L1
+        return options
 
     def GlobalBundleAdjustment(self):
         """controllers/incremental_mapper.cc:221-243"""
@@ -808,3 +840,136 @@ def IterativeGlobalRefinement(reconstruction, mapper_options=None, device=0, tri
         if changed < options.ba_global_max_refinement_change:
             break
     return report
+
+
+# ---- the local refinement after every registered image (controllers/incremental_mapper.cc:72-100, sfm/incremental_mapper.cc:781-891, 993-1160) ----
+
+def _local_bundle_options(options):
+    from .device import local_bundle_options
+    return local_bundle_options(local_ba_num_images=int(options.local_ba_num_images), local_ba_min_tri_angle=float(options.local_ba_min_tri_angle))
+
+
+def FindLocalBundle(reconstruction, triangulator, options, image_id):
+    """IncrementalMapper::FindLocalBundle (sfm/incremental_mapper.cc:993-1160) on the device (pp_tracks_find_local_bundle) -> the image ids in the
+    reference's order.  Equal overlap counts are ordered by ascending image id.  `options`: local_ba_num_images, local_ba_min_tri_angle."""
+    assert triangulator.reconstruction_ is reconstruction
+    ses = triangulator._open(triangulator.Options())
+    try:
+        return ses.find_local_bundle(image_id, _local_bundle_options(options))[1]
+    finally:
+        ses.close()
+
+
+class LocalBundleAdjustmentReport:
+    """IncrementalMapper::LocalBundleAdjustmentReport (sfm/incremental_mapper.h:101-106), plus the bundle, the solver summary (None where nothing was
+    solved) and what the two filters deleted: `obs_deleted` (sorted (image_id, line_idx), those of deleted points included), `point_deleted`."""
+
+    def __init__(self):
+        self.num_merged_observations = self.num_completed_observations = self.num_filtered_observations = self.num_adjusted_observations = 0
+        self.local_bundle, self.summary = [], None
+        self.variable_point3D_ids = []
+        self.obs_deleted, self.point_deleted = [], []
+
+
+def LocalBundleAdjustmentConfig(reconstruction, options, image_id, local_bundle, point3D_ids, existing_image_ids=(), num_reg_images_per_camera=None):
+    """The BundleAdjustmentConfig of AdjustLocalBundle (sfm/incremental_mapper.cc:796-854) -> (config, variable point ids)"""
+    existing = set(existing_image_ids)
+    config = BundleAdjustmentConfig()
+    config.AddImage(image_id)
+    for local_image_id in local_bundle:
+        config.AddImage(local_image_id)
+    if options.fix_existing_images:
+        for local_image_id in local_bundle:
+            if local_image_id in existing:
+                config.SetConstantPose(local_image_id)
+    # the cameras stay constant where not all of their registered images are in the bundle
+    if num_reg_images_per_camera is None:
+        num_reg_images_per_camera = {}
+        for iid in reconstruction.RegImageIds():
+            if getattr(reconstruction.images[iid], "registered", True):
+                cid = reconstruction.images[iid].CameraId()
+                num_reg_images_per_camera[cid] = num_reg_images_per_camera.get(cid, 0) + 1
+    num_images_per_camera = {}
+    for iid in config.Images():
+        cid = reconstruction.Image(iid).CameraId()
+        num_images_per_camera[cid] = num_images_per_camera.get(cid, 0) + 1
+    for cid, n in num_images_per_camera.items():
+        if n < num_reg_images_per_camera[cid]:
+            config.SetConstantCamera(cid)
+    # the 7 gauge degrees of freedom
+    if len(local_bundle) == 1:
+        config.SetConstantPose(local_bundle[0])
+        config.SetConstantTvec(image_id, [0])
+    elif len(local_bundle) > 1:
+        image_id1, image_id2 = local_bundle[-1], local_bundle[-2]
+        config.SetConstantPose(image_id1)
+        if not options.fix_existing_images or image_id2 not in existing:
+            config.SetConstantTvec(image_id2, [0])
+    # new and short-track points are refined, long-track ones that have been through a filter are not
+    kMaxTrackLength = 15
+    variable = set()
+    for pid in point3D_ids:
+        point3D = reconstruction.Point3D(pid)
+        if not (point3D.error != -1.0) or len(point3D.track) <= kMaxTrackLength:      # !HasError() || Length() <= 15
+            config.AddVariablePoint(pid)
+            variable.add(pid)
+    return config, variable
+
+
+def AdjustLocalBundle(reconstruction, triangulator, options, ba_options, tri_options, image_id, point3D_ids, existing_image_ids=(),
+                      num_reg_images_per_camera=None, device=0):
+    """IncrementalMapper::AdjustLocalBundle (sfm/incremental_mapper.cc:781-891) -> LocalBundleAdjustmentReport.  ONE tracks handle serves
+    FindLocalBundle, then takes what the bundle adjustment changed (pp_tracks_update), then MergeTracks, CompleteTracks and CompleteImage; the two
+    filters run on the reconstruction afterwards.  `num_reg_images_per_camera` None: counted from the reconstruction's registered images."""
+    assert triangulator.reconstruction_ is reconstruction
+    report = LocalBundleAdjustmentReport()
+    point3D_ids = set(point3D_ids)
+    ses = triangulator._open(tri_options)
+    try:
+        triangulator.last_reports = []
+        report.local_bundle = local_bundle = ses.find_local_bundle(image_id, _local_bundle_options(options))[1]
+        if len(local_bundle) > 0:
+            config, variable = LocalBundleAdjustmentConfig(reconstruction, options, image_id, local_bundle, point3D_ids, existing_image_ids,
+                                                           num_reg_images_per_camera)
+            report.variable_point3D_ids = sorted(variable)
+            bundle_adjuster = BundleAdjuster(ba_options, config, device=device)
+            bundle_adjuster.Solve(reconstruction)
+            report.summary = bundle_adjuster.Summary()
+            report.num_adjusted_observations = (report.summary.num_residuals if report.summary is not None else 0) // 2
+            ses.update()
+            report.num_merged_observations = ses.merge(variable)[0]
+            report.num_completed_observations = ses.complete(variable)[0]
+            report.num_completed_observations += ses.complete_image(image_id)
+    finally:
+        ses.close()
+    obs_before, points_before = reconstruction._observations(), set(reconstruction.points3D)
+    filter_image_ids = set([image_id]) | set(local_bundle)
+    report.num_filtered_observations = reconstruction.FilterPoints3DInImages(options.filter_max_reproj_error, options.filter_min_tri_angle,
+                                                                            filter_image_ids, device=device)
+    report.num_filtered_observations += reconstruction.FilterPoints3D(options.filter_max_reproj_error, options.filter_min_tri_angle,
+                                                                     point3D_ids, device=device)      # (ids the first filter deleted are skipped)
+    report.obs_deleted = sorted(obs_before - reconstruction._observations())
+    report.point_deleted = sorted(points_before - set(reconstruction.points3D))
+    return report
+
+
+def IterativeLocalRefinement(reconstruction, triangulator, image_id, mapper_options=None, device=0):
+    """IterativeLocalRefinement (controllers/incremental_mapper.cc:72-100): up to `ba_local_max_refinements` rounds of AdjustLocalBundle on the
+    triangulator's modified points, the robust loss in the first round only, until a round changes less than `ba_local_max_refinement_change` of the
+    adjusted observations; ClearModifiedPoints3D at the end.  -> one LocalBundleAdjustmentReport per round (each with `changed`).  The triangulator's
+    options are `mapper_options.triangulation` when that exists, the reference's defaults otherwise."""
+    options = mapper_options or IncrementalMapperOptions()
+    tri_options = getattr(options, "triangulation", None) or triangulator.Options()
+    ba_options = options.LocalBundleAdjustment()
+    reports = []
+    for _ in range(options.ba_local_max_refinements):
+        report = AdjustLocalBundle(reconstruction, triangulator, options, ba_options, tri_options, image_id, triangulator.GetModifiedPoints3D(), device=device)
+        n = report.num_merged_observations + report.num_completed_observations + report.num_filtered_observations
+        # (the reference divides by zero adjusted observations without a check: inf or NaN, neither is < the bound)
+        report.changed = n / float(report.num_adjusted_observations) if report.num_adjusted_observations else (float("inf") if n else float("nan"))
+        reports.append(report)
+        if report.changed < options.ba_local_max_refinement_change:
+            break
+        ba_options.loss_function_type = BundleAdjustmentOptions.TRIVIAL
+    triangulator.ClearModifiedPoints3D()
+    return reports

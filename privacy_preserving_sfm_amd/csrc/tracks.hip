@@ -216,6 +216,10 @@ int pp_tracks_create(const pp_tracks_desc* d, int device, pp_tracks_handle* out)
   if (d->camera_skip) skip.assign(d->camera_skip, d->camera_skip + K);
   h->image_skip.resize((size_t)C);
   for (int c = 0; c < C; ++c) h->image_skip[(size_t)c] = skip[(size_t)d->pose_camera[c]];
+  h->pose_camera.assign(d->pose_camera, d->pose_camera + C);
+  h->poses.assign(d->poses, d->poses + (size_t)7 * C);
+  h->intr.assign(d->intr, d->intr + (size_t)kCamStride * K);
+  h->camera_skip = skip;
   PP_TRY(PoolStreamAcquire(&h->stream));
   PP_TRY(PoolEventAcquire(&h->ev0, true)); PP_TRY(PoolEventAcquire(&h->ev1, true));
   hipStream_t s = h->stream;
@@ -230,6 +234,7 @@ int pp_tracks_create(const pp_tracks_desc* d, int device, pp_tracks_handle* out)
   PP_TRY(put(&h->d_line_point, (const int32_t*)nullptr, (size_t)L));
   hipLaunchKernelGGL(k_tracks_proj, dim3(CeilDiv(C, 256)), dim3(256), 0, s, C, d_poses, d_proj);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { SetLastError("pp_tracks_create: upload failed"); return PP_ERR_HIP; }
+  h->d_poses = d_poses; h->d_proj = d_proj; h->d_intr = d_intr; h->d_skip = d_skip;
   h->dev.proj = d_proj; h->dev.intr = d_intr; h->dev.lines = d_lines; h->dev.pose_camera = d_pc; h->dev.camera_model = d_cm; h->dev.cam_size = d_cs;
   h->dev.line_image = d_li; h->dev.corr_start = d_c0; h->dev.corr_line = d_cl; h->dev.camera_skip = d_skip; h->dev.image_registered = d_reg;
   *out = h.release();
@@ -345,6 +350,46 @@ int pp_tracks_merge(pp_tracks_handle h, const pp_tracks_options* o, const uint8_
   report->total_ms = MsSince(t_begin);
   return PP_OK;
 } PP_API_CATCH("pp_tracks_merge")
+
+int pp_tracks_update(pp_tracks_handle h, int32_t num_images, const int32_t* image_idx, const double* poses, int32_t num_points, const int32_t* point_idx,
+                     const double* xyz, const double* intr, const uint8_t* camera_skip) try {
+  const char* where = "pp_tracks_update";
+  PP_REQUIRE(h && num_images >= 0 && num_points >= 0 && (num_images == 0 || (image_idx && poses)) && (num_points == 0 || (point_idx && xyz)) &&
+                 (intr || !camera_skip), "%s: bad argument", where);
+  TrackState& st = h->st;
+  const int C = h->C, K = h->K;
+  for (int32_t i = 0; i < num_images; ++i) {
+    PP_REQUIRE(image_idx[i] >= 0 && image_idx[i] < C, "%s: image %d of %d", where, image_idx[i], C);
+    for (int j = 0; j < 7; ++j) PP_REQUIRE(std::isfinite(poses[7 * (size_t)i + j]), "%s: the pose of image %d is not finite", where, image_idx[i]);
+  }
+  for (int32_t i = 0; i < num_points; ++i) {
+    PP_REQUIRE(point_idx[i] >= 0 && point_idx[i] < st.NumPoints(), "%s: point %d of %d", where, point_idx[i], st.NumPoints());
+    PP_REQUIRE(st.Exists(point_idx[i]), "%s: point %d is deleted", where, point_idx[i]);
+    for (int j = 0; j < 3; ++j) PP_REQUIRE(std::isfinite(xyz[3 * (size_t)i + j]), "%s: the position of point %d is not finite", where, point_idx[i]);
+  }
+  if (intr) for (size_t i = 0; i < (size_t)kCamStride * K; ++i) PP_REQUIRE(std::isfinite(intr[i]), "%s: an intrinsic parameter is not finite", where);
+  if (num_images == 0 && num_points == 0 && !intr) return PP_OK;
+  for (int32_t i = 0; i < num_points; ++i) std::copy(xyz + 3 * (size_t)i, xyz + 3 * (size_t)i + 3, st.points.begin() + 3 * (size_t)point_idx[i]);      // (the points go up with each call's state)
+  if (num_images == 0 && !intr) return PP_OK;
+  PP_HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  if (intr) {
+    h->intr.assign(intr, intr + (size_t)kCamStride * K);
+    h->camera_skip.assign((size_t)K, 0);
+    if (camera_skip) h->camera_skip.assign(camera_skip, camera_skip + K);
+    for (int c = 0; c < C; ++c) h->image_skip[(size_t)c] = h->camera_skip[(size_t)h->pose_camera[(size_t)c]];
+    PP_TRY(Upload(h->d_intr, h->intr.data(), h->intr.size(), s)); PP_TRY(Upload(h->d_skip, h->camera_skip.data(), (size_t)K, s));
+  }
+  if (num_images > 0) {
+    for (int32_t i = 0; i < num_images; ++i) std::copy(poses + 7 * (size_t)i, poses + 7 * (size_t)i + 7, h->poses.begin() + 7 * (size_t)image_idx[i]);
+    PP_TRY(Upload(h->d_poses, h->poses.data(), h->poses.size(), s));
+    hipLaunchKernelGGL(k_tracks_proj, dim3(CeilDiv(C, 256)), dim3(256), 0, s, C, h->d_poses, h->d_proj);
+    PP_HIP_TRY(hipGetLastError());
+    if (h->d_centers) PP_TRY(ComputeCenters(h));
+  }
+  PP_HIP_TRY(hipStreamSynchronize(s));      // (the host copies are the handle's own: nothing of the caller's is read after the return)
+  return PP_OK;
+} PP_API_CATCH("pp_tracks_update")
 
 int pp_tracks_get_state(pp_tracks_handle h, int32_t* num_points, int64_t* num_track_elements, int32_t* line_point, double* points, uint8_t* deleted,
                         int32_t* track_start, int32_t* track_line, int32_t point_capacity, int64_t element_capacity) try {

@@ -155,10 +155,15 @@ struct pp_tracks_impl {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   ppsfm::TrackState st;
   std::vector<uint8_t> image_skip;      // per image: its camera is flagged in camera_skip
+  std::vector<int32_t> pose_camera;     // C
+  std::vector<double> poses, intr;      // C x 7, K x kCamStride: the host copies pp_tracks_update edits and uploads whole
+  std::vector<uint8_t> camera_skip;     // K
+  double *d_poses = nullptr, *d_proj = nullptr, *d_intr = nullptr;      // the writable views of dev.proj / dev.intr / dev.camera_skip
+  uint8_t* d_skip = nullptr;
   ppsfm::DeviceBlocks blocks;     // the static device arrays and the pinned slots (pool blocks)
   ppsfm::TrackDev dev{};
   int32_t* d_line_point = nullptr;
-  double* d_centers = nullptr;    // C x 3 projection centres (K11b's triangulation-angle test)
+  double* d_centers = nullptr;    // C x 3 projection centres (K11b's triangulation-angle test, K12b)
   int32_t* pin = nullptr;         // pinned slots of the fresh-pair launches
   size_t pin_ints = 0;
 };
@@ -177,6 +182,10 @@ struct CallBlocks {
   template <typename T> int Alloc(T** p, size_t count) { return b.Alloc(p, std::max<size_t>(count, 1)); }
   template <typename T> int Put(T** p, const T* src, size_t count) { return b.Put(p, src, count, s, 1); }
 };
+
+// the C x 3 projection centres of the handle's projection matrices (tracks_image.hip): computed on first use, again after pp_tracks_update
+int ComputeCenters(pp_tracks_impl* h);
+inline int EnsureCenters(pp_tracks_impl* h) { return h->d_centers ? PP_OK : ComputeCenters(h); }
 
 // uploads the state at the start of a call; flat track CSR in start / elems (kept alive by the caller until the stream drains)
 inline int UploadState(pp_tracks_impl* h, CallBlocks& cb, const uint8_t* subset, std::vector<int32_t>& start, std::vector<int32_t>& elems, TrackDev* d) {

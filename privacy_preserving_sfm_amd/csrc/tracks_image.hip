@@ -33,6 +33,13 @@ __global__ __launch_bounds__(256) void k_image_centers(int C, const double* __re
   for (int i = 0; i < 3; ++i) centers[3 * (size_t)c + i] = -(P[i] * P[3] + P[4 + i] * P[7] + P[8 + i] * P[11]);
 }
 
+int ComputeCenters(pp_tracks_impl* h) {
+  if (!h->d_centers) PP_TRY(h->blocks.Alloc(&h->d_centers, std::max<size_t>((size_t)3 * h->C, 1)));
+  hipLaunchKernelGGL(k_image_centers, dim3(CeilDiv(h->C, 256)), dim3(256), 0, h->stream, h->C, h->dev.proj, h->d_centers);
+  PP_HIP_TRY(hipGetLastError());
+  return PP_OK;
+}
+
 struct FindArgs {
   int num_work;
   const int32_t* work_line;      // the reference lines
@@ -278,11 +285,7 @@ struct ImageCall {
 
   int Begin() {
     const TrackState& st = h->st;
-    if (!h->d_centers) {
-      PP_TRY(h->blocks.Alloc(&h->d_centers, std::max<size_t>((size_t)3 * h->C, 1)));
-      hipLaunchKernelGGL(k_image_centers, dim3(CeilDiv(h->C, 256)), dim3(256), 0, s, h->C, h->dev.proj, h->d_centers);
-      PP_HIP_TRY(hipGetLastError());
-    }
+    PP_TRY(EnsureCenters(h));
     points_cap = (size_t)st.NumPoints() + (size_t)h->L / 3 + 1;      // every new point takes at least three free lines
     PP_TRY(cb.Alloc(&d_points, 3 * points_cap));
     if (aligned) PP_TRY(cb.Put(&d_aligned, aligned, (size_t)h->L));

@@ -607,6 +607,16 @@ def tracks_image_options(**kw):
     return o
 
 
+def local_bundle_options(**kw):
+    o = _capi.LocalBundleOptions()
+    _capi.lib().pp_local_bundle_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
 _TRACKS_FIELDS = (("poses", np.float64, dp), ("pose_camera", np.int32, None), ("camera_model", np.int32, None), ("intr", np.float64, dp),
                   ("cam_size", np.int32, None), ("camera_skip", np.uint8, None), ("image_registered", np.uint8, None), ("lines", np.float64, dp),
                   ("line_image", np.int32, None), ("line_point", np.int32, None), ("corr_start", np.int32, None), ("corr_line", np.int32, None),
@@ -636,6 +646,7 @@ class TracksProblem:
         self._keep = []
         self._h = C.c_void_p()
         self.num_lines = int(len(flat["line_image"]))
+        self.num_images, self.num_cameras = int(np.shape(flat["poses"])[0]), int(np.shape(flat["intr"])[0])
         d = tracks_desc(flat, self._keep)
         check(_capi.lib().pp_tracks_create(C.byref(d), int(device), C.byref(self._h)))
 
@@ -701,6 +712,29 @@ class TracksProblem:
     def complete_image(self, image, options=None):
         """CompleteImage for image index `image` -> (report, events) as triangulate_image"""
         return self._image_call(_capi.lib().pp_tracks_complete_image, options, image)
+
+    def find_local_bundle(self, image, options=None):
+        """FindLocalBundle for image index `image` -> (report, bundle [n] image indices in the reference's order,
+        overlap dict(image [m], count [m], tri_angle [m] radians, -1 where the sequential loop never asked)).  The state does not change."""
+        o = options or local_bundle_options()
+        Cn = self.num_images
+        bundle, oi, oc, oa = np.zeros(Cn, dtype=np.int32), np.zeros(Cn, dtype=np.int32), np.zeros(Cn, dtype=np.int32), np.zeros(Cn)
+        rep = _capi.LocalBundleReport()
+        check(_capi.lib().pp_tracks_find_local_bundle(self._h, C.byref(o), int(image), C.byref(rep), ptr(bundle, _capi.c_ip), Cn, ptr(oi, _capi.c_ip),
+                                                      ptr(oc, _capi.c_ip), dp(oa)))
+        m = int(rep.num_overlapping)
+        return rep, bundle[: int(rep.num_selected)].copy(), dict(image=oi[:m].copy(), count=oc[:m].copy(), tri_angle=oa[:m].copy())
+
+    def update(self, image_idx=(), poses=None, point_idx=(), xyz=None, intr=None, camera_skip=None):
+        """New poses [n, 7] of the images image_idx, positions [m, 3] of the points point_idx, intrinsics [K, 12] with camera_skip [K] or None
+        (after a bundle adjustment); every later call sees them."""
+        ii = np.ascontiguousarray(image_idx, dtype=np.int32).reshape(-1); pi = np.ascontiguousarray(point_idx, dtype=np.int32).reshape(-1)
+        ps = None if len(ii) == 0 else f64(poses).reshape(len(ii), 7)
+        xs = None if len(pi) == 0 else f64(xyz).reshape(len(pi), 3)
+        it = None if intr is None else f64(intr).reshape(self.num_cameras, _capi.CAM_STRIDE)
+        sk = None if camera_skip is None else np.ascontiguousarray(camera_skip, dtype=np.uint8).reshape(self.num_cameras)
+        check(_capi.lib().pp_tracks_update(self._h, len(ii), ptr(ii, _capi.c_ip) if len(ii) else None, dp(ps), len(pi), ptr(pi, _capi.c_ip) if len(pi) else None,
+                                           dp(xs), dp(it), ptr(sk, _capi.c_u8p)))
 
     def state(self):
         """-> dict(line_point [L], points [P', 3], deleted [P'], track_start [P' + 1], track_line)"""

@@ -141,41 +141,27 @@ class IncrementalTriangulator:
         return tracks_options(merge_max_reproj_error=options.merge_max_reproj_error, complete_max_reproj_error=options.complete_max_reproj_error,
                               complete_max_transitivity=options.complete_max_transitivity)
 
+    def _open(self, options):
+        """-> _TracksSession: ONE TracksProblem over the flattened reconstruction, on which several operations run one after the other (each applies
+        its result to the reconstruction at once); close() it when done.  Internal: _run / _run_image and bundle_adjustment.AdjustLocalBundle."""
+        assert options.Check()
+        return _TracksSession(self, options)
+
     def _run(self, options, point3D_ids, complete, merge):
         assert options.Check()
         rec = self.reconstruction_
         self.last_reports = []
         if not rec.points3D:
             return 0, 0, [], []
-        flat, point_ids, line_ref = self.flatten(options)
-        wanted = None if point3D_ids is None else set(point3D_ids)
-        subset = None if wanted is None else np.array([p in wanted for p in point_ids], dtype=np.uint8)
-        o = self.device_options(options)
-        ids = list(point_ids)      # device index -> point id, new points appended as the merges are applied
         completed, merged, num_completed, num_merged = [], [], 0, 0
-        pb = TracksProblem(flat, device=self.device_)
+        ses = self._open(options)
         try:
             if complete:
-                rep, pairs = pb.complete(o, subset)
-                self.last_reports.append(rep)
-                num_completed = int(rep.num_changed)
-                for p, l in pairs:
-                    rec.AddObservation(ids[p], line_ref[l])
-                    self.modified_point3D_ids_.add(ids[p])
-                    completed.append((ids[p], line_ref[l]))
+                num_completed, completed = ses.complete(point3D_ids)
             if merge:
-                rep, merges = pb.merge(o, subset)
-                self.last_reports.append(rep)
-                num_merged = int(rep.num_changed)
-                for a, b, m in merges:
-                    new_id = rec.MergePoints3D(ids[a], ids[b])
-                    assert m == len(ids)
-                    self.modified_point3D_ids_.discard(ids[a]); self.modified_point3D_ids_.discard(ids[b])
-                    self.modified_point3D_ids_.add(new_id)
-                    merged.append((ids[a], ids[b], new_id))
-                    ids.append(new_id)
+                num_merged, merged = ses.merge(point3D_ids)
         finally:
-            pb.close()
+            ses.close()
         return num_completed, num_merged, completed, merged
 
     @staticmethod
@@ -187,36 +173,12 @@ class IncrementalTriangulator:
 
     def _run_image(self, options, image_id, complete):
         assert options.Check()
-        rec = self.reconstruction_
         self.last_reports = []
-        flat, point_ids, line_ref = self.flatten(options)
-        image = sorted(rec.images).index(image_id)
-        ids = list(point_ids)      # device index -> point id, new points appended as the events name them
-        pb = TracksProblem(flat, device=self.device_)
+        ses = self._open(options)
         try:
-            o = self.device_image_options(options)
-            rep, events = pb.complete_image(image, o) if complete else pb.triangulate_image(image, o, flat["line_aligned"])
-            points = pb.state()["points"] if rep.points_created else None
+            return ses.complete_image(image_id) if complete else ses.triangulate_image(image_id)
         finally:
-            pb.close()
-        self.last_reports.append(rep)
-        k = 0
-        while k < len(events):
-            p, l = int(events[k][0]), int(events[k][1])
-            if p < len(ids):
-                rec.AddObservation(ids[p], line_ref[l])
-                self.modified_point3D_ids_.add(ids[p])
-                k += 1
-                continue
-            assert p == len(ids)      # AddPoint3D: the whole track of the new point follows in track order
-            k1 = k
-            while k1 < len(events) and int(events[k1][0]) == p:
-                k1 += 1
-            new_id = rec.AddPoint3D(points[p], [line_ref[int(e[1])] for e in events[k:k1]])
-            ids.append(new_id)
-            self.modified_point3D_ids_.add(new_id)
-            k = k1
-        return int(rep.num_changed)
+            ses.close()
 
     def TriangulateImage(self, options, image_id):
         """sfm/incremental_triangulator.cc:63-121 (Find, Continue, Create) -> num_tris"""
@@ -242,6 +204,121 @@ class IncrementalTriangulator:
         """CompleteAllTracks then MergeAllTracks (controllers/incremental_mapper.cc:160-172) on ONE device handle:
         -> (num_completed, num_merged, [(point id, (image_id, line_idx))], [(id a, id b, new id)])"""
         return self._run(options, None, True, True)
+
+
+class _TracksSession:
+    """One open TracksProblem of an IncrementalTriangulator (IncrementalTriangulator._open): the flattening's id maps, and per operation the device call
+    and its application to the reconstruction.  `ids` maps a device point index to its point id; new points are appended as they are created."""
+
+    def __init__(self, triangulator, options):
+        self.t, self.options = triangulator, options
+        self.rec = triangulator.reconstruction_
+        self.flat, point_ids, self.line_ref = triangulator.flatten(options)
+        self.ids = list(point_ids)
+        self.image_ids = sorted(self.rec.images)
+        self.cam_ids = sorted(self.rec.cameras)
+        self.pb = TracksProblem(self.flat, device=triangulator.device_)
+
+    def close(self):
+        self.pb.close()
+
+    def _subset(self, point3D_ids):
+        if point3D_ids is None:
+            return None
+        wanted = set(point3D_ids)
+        return np.array([p in wanted for p in self.ids], dtype=np.uint8)
+
+    def complete(self, point3D_ids=None):
+        """CompleteTracks / CompleteAllTracks (None) -> (num_completed, [(point id, (image_id, line_idx))])"""
+        rec, t = self.rec, self.t
+        rep, pairs = self.pb.complete(t.device_options(self.options), self._subset(point3D_ids))
+        t.last_reports.append(rep)
+        completed = []
+        for p, l in pairs:
+            rec.AddObservation(self.ids[p], self.line_ref[l])
+            t.modified_point3D_ids_.add(self.ids[p])
+            completed.append((self.ids[p], self.line_ref[l]))
+        return int(rep.num_changed), completed
+
+    def merge(self, point3D_ids=None):
+        """MergeTracks / MergeAllTracks (None) -> (num_merged, [(id a, id b, new id)])"""
+        rec, t, ids = self.rec, self.t, self.ids
+        rep, merges = self.pb.merge(t.device_options(self.options), self._subset(point3D_ids))
+        t.last_reports.append(rep)
+        merged = []
+        for a, b, m in merges:
+            new_id = rec.MergePoints3D(ids[a], ids[b])
+            assert m == len(ids)
+            t.modified_point3D_ids_.discard(ids[a]); t.modified_point3D_ids_.discard(ids[b])
+            t.modified_point3D_ids_.add(new_id)
+            merged.append((ids[a], ids[b], new_id))
+            ids.append(new_id)
+        return int(rep.num_changed), merged
+
+    def _image(self, image_id, complete):
+        rec, t, ids, line_ref = self.rec, self.t, self.ids, self.line_ref
+        image = self.image_ids.index(image_id)
+        o = t.device_image_options(self.options)
+        rep, events = self.pb.complete_image(image, o) if complete else self.pb.triangulate_image(image, o, self.flat["line_aligned"])
+        points = self.pb.state()["points"] if rep.points_created else None
+        t.last_reports.append(rep)
+        k = 0
+        while k < len(events):
+            p, l = int(events[k][0]), int(events[k][1])
+            if p < len(ids):
+                rec.AddObservation(ids[p], line_ref[l])
+                t.modified_point3D_ids_.add(ids[p])
+                k += 1
+                continue
+            assert p == len(ids)      # AddPoint3D: the whole track of the new point follows in track order
+            k1 = k
+            while k1 < len(events) and int(events[k1][0]) == p:
+                k1 += 1
+            new_id = rec.AddPoint3D(points[p], [line_ref[int(e[1])] for e in events[k:k1]])
+            ids.append(new_id)
+            t.modified_point3D_ids_.add(new_id)
+            k = k1
+        return int(rep.num_changed)
+
+    def triangulate_image(self, image_id):
+        return self._image(image_id, False)
+
+    def complete_image(self, image_id):
+        return self._image(image_id, True)
+
+    def find_local_bundle(self, image_id, options):
+        """FindLocalBundle -> (report, image ids in the reference's order)"""
+        rep, bundle, _ = self.pb.find_local_bundle(self.image_ids.index(image_id), options)
+        self.t.last_reports.append(rep)
+        return rep, [self.image_ids[int(c)] for c in bundle]
+
+    def update(self):
+        """what a bundle adjustment changed in the reconstruction since the flattening (or the last update) goes to the handle: poses, positions of the
+        points that still exist, intrinsics with camera_skip decided again"""
+        rec, flat, o = self.rec, self.flat, self.options
+        poses = np.array([np.concatenate([rec.images[i].qvec, rec.images[i].tvec]) for i in self.image_ids]).reshape(-1, 7)
+        ii = np.flatnonzero((poses != flat["poses"]).any(axis=1)).astype(np.int32)
+        live = [(k, pid) for k, pid in enumerate(self.ids) if pid in rec.points3D]
+        npts = max(len(self.ids), flat["points"].shape[0])
+        if flat["points"].shape[0] < npts:      # points created since: their positions came from the handle itself
+            flat["points"] = np.concatenate([flat["points"].reshape(-1, 3), np.array([rec.points3D[pid].xyz if pid in rec.points3D else np.zeros(3)
+                                                                                       for pid in self.ids[flat["points"].shape[0]:]]).reshape(-1, 3)])
+        pi = np.array([k for k, pid in live if (rec.points3D[pid].xyz != flat["points"][k]).any()], dtype=np.int32)
+        xyz = np.array([rec.points3D[self.ids[k]].xyz for k in pi]).reshape(-1, 3)
+        intr = np.zeros_like(flat["intr"])
+        for k, cid in enumerate(self.cam_ids):
+            intr[k, : rec.cameras[cid].NumParams()] = rec.cameras[cid].params
+        skip = None
+        if (intr != flat["intr"]).any():
+            skip = np.array([rec.cameras[c].HasBogusParams(o.min_focal_length_ratio, o.max_focal_length_ratio, o.max_extra_param) for c in self.cam_ids], dtype=np.uint8)
+        else:
+            intr = None
+        self.pb.update(ii, poses[ii], pi, xyz, intr, skip)
+        flat["poses"] = poses
+        for k, x in zip(pi, xyz):
+            flat["points"][k] = x
+        if intr is not None:
+            flat["intr"], flat["camera_skip"] = intr, skip
 
 
 def reconstruction_from_completion_scene(scene):
