@@ -701,6 +701,81 @@ int pp_tracks_update(pp_tracks_handle h, int32_t num_images, const int32_t* imag
                      int32_t num_points, const int32_t* point_idx, const double* xyz /* x3 */,
                      const double* intr, const uint8_t* camera_skip);
 
+/* ---- FindNextImages / RegisterNextImage on a pp_tracks_handle (kernels K13a k_visible_points, K13b k_register_corrs) ------------------------------
+ * replaces IncrementalMapper::FindNextImages (sfm/incremental_mapper.cc:139-190) and the parts of RegisterNextImage (:570-760) around the pose
+ * refinement: the visibility gate (:585), the 2D-3D correspondence search (:601-647, FindTransitiveCorrespondences(..., 1) =
+ * base/correspondence_graph.cc:169-171), EstimateAbsolutePoseFromLines (estimators/pose.cc:52-94, the pp_pose_ransac code path on a pose handle
+ * whose correspondences K13b wrote on the device), the gates after it (:725) and the commit (:743-757).  One handle so spans a reconstruction
+ * from its first registered images to its last: find_next_images, estimate_image_pose, register_image, triangulate_image, find_local_bundle, update.
+ * A line is OBSERVED when its neighbour list is not empty (CorrespondenceGraph::Finalize, correspondence_graph.cc:58-65) and VISIBLE when at
+ * least one direct neighbour has a point (what Image::IncrementCorrespondenceHasPoint3D maintains, base/image.cc:91-98); the camera filter
+ * applies to the correspondence search only.
+ * PINNED where the reference is unspecified: images of equal rank are ordered by ASCENDING IMAGE INDEX (the reference sorts in the
+ * order of an unordered_map), as pp_tracks_find_local_bundle pins equal counts.
+ * THE CALLER does the pose refinement of :733-737 (RefineAbsolutePoseFromLines: a one-pose bundle adjustment, pp_ba_*) BETWEEN
+ * pp_tracks_estimate_image_pose and pp_tracks_register_image: its camera block belongs to the caller, who may share it between images and may
+ * refine it; a refined camera goes to the handle with pp_tracks_update.
+ * LINES AND POINTS are the handle's line and point indices.                                                                                      */
+typedef struct pp_next_image_options {   /* IncrementalMapper::Options, sfm/incremental_mapper.h */
+  int32_t abs_pose_min_num_inliers;      /* 30 */
+  int32_t max_reg_trials;                /* 3  */
+  int32_t image_selection_method;        /* 0 MAX_VISIBLE_POINTS_NUM, 1 MAX_VISIBLE_POINTS_RATIO; default 1 (sfm/incremental_mapper.h:110) */
+  int32_t reserved_;
+} pp_next_image_options;
+void pp_next_image_options_default(pp_next_image_options* o);
+
+typedef struct pp_next_image_report {
+  int32_t num_ranked;        /* images returned (both buckets); entries beyond `capacity` are not written */
+  int32_t num_first_bucket;  /* of them: never tried and not filtered (:178-179) */
+  int32_t num_unregistered;
+  int32_t reserved_;
+  double device_ms, replay_ms, total_ms;
+} pp_next_image_report;
+
+/* FindNextImages.  num_reg_trials (C, NULL = all 0) and filtered (C bytes, NULL = none) are the caller's num_reg_trials_ / filtered_images_.
+ * ranked: image indices, first bucket then second bucket; num_visible / num_observations (C each, may be NULL): NumVisiblePoints3D / NumObservations
+ * of EVERY image.  The handle does not change.  ERRORS: PP_ERR_INVALID for abs_pose_min_num_inliers <= 0, max_reg_trials < 0, an unknown method,
+ * a negative trial count. */
+int pp_tracks_find_next_images(pp_tracks_handle h, const pp_next_image_options* o, const int32_t* num_reg_trials, const uint8_t* filtered,
+                               pp_next_image_report* report, int32_t* ranked, int32_t capacity, int32_t* num_visible, int32_t* num_observations);
+
+/* pp_image_pose_report.failure: which `return false` of the reference was taken */
+enum { PP_REG_OK = 0, PP_REG_FEW_VISIBLE = 1 /* :585 */, PP_REG_FEW_CORRS = 2 /* :653-657 */, PP_REG_NO_INLIERS = 3 /* pose.cc:65 */,
+       PP_REG_ALIGNED = 4 /* pose.cc:71-83 */, PP_REG_NAN = 5 /* pose.cc:89 */, PP_REG_FEW_INLIERS = 6 /* :725 */ };
+
+typedef struct pp_image_pose_report {
+  int32_t failure;             /* PP_REG_*; 0: pose7 holds a pose */
+  int32_t num_visible;         /* image.NumVisiblePoints3D() */
+  int64_t num_corrs;           /* tri_corrs.size(); entries beyond `capacity` are not written (0 after PP_REG_FEW_VISIBLE: the search did not run) */
+  uint64_t num_trials;         /* RANSAC report */
+  int64_t num_inliers;
+  int32_t num_aligned_inliers;
+  int32_t reserved_;
+  double device_ms;            /* HIP-event time of K13b, the scan and the RANSAC's launches */
+  double replay_ms;            /* the host side of the RANSAC and the gates */
+  double total_ms;
+} pp_image_pose_report;
+
+/* RegisterNextImage :584-727: visibility gate, 2D-3D search, P6L RANSAC, the gates after it.  Does NOT change the handle.
+ * ransac: as the caller of :668-681 sets it (max_error through pp_camera_image_to_world_threshold).  line_aligned: L bytes, NULL = none.
+ * pose7: (qw,qx,qy,qz,tx,ty,tz) as RotationMatrixToQuaternion leaves it (written when the RANSAC had an inlier, also on a later gate's failure).
+ * corr_line / corr_point / inlier_mask: `capacity` entries each (corr_start[l + 1] - corr_start[l] summed over the image's lines always suffices);
+ * inlier_mask is all 0 unless the RANSAC succeeded.  ERRORS: PP_ERR_INVALID for an image out of range or REGISTERED (the reference CHECKs it),
+ * bad options, RANSACOptions::Check. */
+int pp_tracks_estimate_image_pose(pp_tracks_handle h, const pp_next_image_options* o, const pp_ransac_options* ransac, int32_t image,
+                                  const uint8_t* line_aligned /* L, NULL = none */, pp_image_pose_report* report, double* pose7,
+                                  int32_t* corr_line, int32_t* corr_point, uint8_t* inlier_mask, int64_t capacity);
+
+/* :743-757: the image becomes registered with `pose7`; the inlier correspondences (inlier_mask NULL = all) whose line has no point yet get their
+ * observation, in list order: the first inlier of a line gives it its point, a later one is skipped; two lines may join one point.
+ * event_point / event_line as pp_tracks_triangulate_image's events (one per AddObservation; *num_added counts all, those beyond `capacity` are not
+ * written).  Validated BEFORE anything changes (PP_ERR_INVALID leaves the handle as it was): the image exists and is not registered, every line
+ * belongs to it, every point exists and is not deleted, the pose is finite.  On success the host state and the device copies change as in
+ * pp_tracks_update (pose, projection matrix, projection centre) together with image_registered: every later pp_tracks_* call sees what a handle
+ * created from the updated arrays would. */
+int pp_tracks_register_image(pp_tracks_handle h, int32_t image, const double* pose7, int64_t n, const int32_t* corr_line, const int32_t* corr_point,
+                             const uint8_t* inlier_mask, int64_t* num_added, int32_t* event_point, int32_t* event_line, int64_t capacity);
+
 /* ======================================================================================== *
  *  Four-view line initialisation (LO-MSAC)                                                   *
  *  replaces, for the out-of-plane-translation stage: ransac_lib::LocallyOptimizedMSAC<        *

@@ -142,6 +142,23 @@ class LocalBundleReport(C.Structure):
                 ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class NextImageOptions(C.Structure):
+    _fields_ = [("abs_pose_min_num_inliers", C.c_int32), ("max_reg_trials", C.c_int32), ("image_selection_method", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class NextImageReport(C.Structure):
+    _fields_ = [("num_ranked", C.c_int32), ("num_first_bucket", C.c_int32), ("num_unregistered", C.c_int32), ("reserved_", C.c_int32),
+                ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+REG_OK, REG_FEW_VISIBLE, REG_FEW_CORRS, REG_NO_INLIERS, REG_ALIGNED, REG_NAN, REG_FEW_INLIERS = range(7)      # PP_REG_*
+
+
+class ImagePoseReport(C.Structure):
+    _fields_ = [("failure", C.c_int32), ("num_visible", C.c_int32), ("num_corrs", C.c_int64), ("num_trials", C.c_uint64), ("num_inliers", C.c_int64),
+                ("num_aligned_inliers", C.c_int32), ("reserved_", C.c_int32), ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -173,6 +190,7 @@ _EXPORTS = [
     "pp_tracks_options_default", "pp_tracks_create", "pp_tracks_destroy", "pp_tracks_complete", "pp_tracks_merge", "pp_tracks_get_state",
     "pp_tracks_image_options_default", "pp_tracks_triangulate_image", "pp_tracks_complete_image",
     "pp_local_bundle_options_default", "pp_tracks_find_local_bundle", "pp_tracks_update",
+    "pp_next_image_options_default", "pp_tracks_find_next_images", "pp_tracks_estimate_image_pose", "pp_tracks_register_image",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -277,6 +295,11 @@ def lib():
     L.pp_local_bundle_options_default.argtypes = [C.POINTER(LocalBundleOptions)]
     L.pp_tracks_find_local_bundle.argtypes = [C.c_void_p, C.POINTER(LocalBundleOptions), C.c_int32, C.POINTER(LocalBundleReport), c_ip, C.c_int32, c_ip, c_ip, c_dp]
     L.pp_tracks_update.argtypes = [C.c_void_p, C.c_int32, c_ip, c_dp, C.c_int32, c_ip, c_dp, c_dp, c_u8p]
+    L.pp_next_image_options_default.argtypes = [C.POINTER(NextImageOptions)]
+    L.pp_tracks_find_next_images.argtypes = [C.c_void_p, C.POINTER(NextImageOptions), c_ip, c_u8p, C.POINTER(NextImageReport), c_ip, C.c_int32, c_ip, c_ip]
+    L.pp_tracks_estimate_image_pose.argtypes = [C.c_void_p, C.POINTER(NextImageOptions), C.POINTER(RansacOptions), C.c_int32, c_u8p, C.POINTER(ImagePoseReport),
+                                                c_dp, c_ip, c_ip, c_u8p, C.c_int64]
+    L.pp_tracks_register_image.argtypes = [C.c_void_p, C.c_int32, c_dp, C.c_int64, c_ip, c_ip, c_u8p, C.POINTER(C.c_int64), c_ip, c_ip, C.c_int64]
     L.pp_camera_image_to_world_threshold.argtypes = [C.c_int, c_dp, C.c_double, c_dp]
     _lib = L
     return L

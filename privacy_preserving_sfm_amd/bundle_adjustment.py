@@ -283,8 +283,11 @@ class Reconstruction:
         return n
 
     def RegImageIds(self):
-        """every image of this data model is registered; the order of registration is the order of the ids"""
-        return sorted(self.images)
+        """The registered images in the order of their registration.  An image is registered unless it carries `registered = False`
+        (incremental_mapper.IncrementalMapper.RegisterNextImage turns it into True and numbers it with `reg_index`); the images that were registered
+        from the start come first, in the order of their ids."""
+        reg = [i for i in self.images if getattr(self.images[i], "registered", True)]
+        return sorted(reg, key=lambda i: (getattr(self.images[i], "reg_index", -1), i))
 
     def _observations(self):
         return set((iid, idx) for iid, image in self.images.items() for idx, l in enumerate(image.lines) if l.HasPoint3D())
@@ -713,6 +716,17 @@ class IncrementalMapperOptions:
         self.ba_local_max_num_iterations = 25
         self.ba_local_max_refinements = 2
         self.ba_local_max_refinement_change = 0.001
+        # choosing and registering the next image (sfm/incremental_mapper.h:62-95, 110)
+        self.abs_pose_max_error = 12.0
+        self.abs_pose_min_num_inliers = 30
+        self.abs_pose_min_inlier_ratio = 0.25
+        self.abs_pose_refine_focal_length = False
+        self.abs_pose_refine_extra_params = False
+        self.min_focal_length_ratio = 0.1
+        self.max_focal_length_ratio = 10.0
+        self.max_extra_param = 1.0
+        self.max_reg_trials = 3
+        self.image_selection_method = 1      # 0 MAX_VISIBLE_POINTS_NUM, 1 MAX_VISIBLE_POINTS_RATIO
 
     def LocalBundleAdjustment(self):
         """controllers/incremental_mapper.cc:196-219"""

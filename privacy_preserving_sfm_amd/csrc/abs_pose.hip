@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "p6l_device.hpp"
+#include "pose_device.hpp"
 #include "resource_pool.hpp"
 #include "ransac_host.hpp"
 
@@ -530,6 +531,31 @@ int pp_pose_create(int32_t n, const double* lines2D, const double* points3D, con
   *out = h.release();
   return PP_OK;
 } PP_API_CATCH("pp_pose_create")
+
+}  // extern "C"
+
+// A pose handle whose correspondences are written ON THE DEVICE (pose_device.hpp; K13b of register_image.hip): the six SoA streams and the aligned
+// flags are allocated as pp_pose_create allocates them and handed out writable, nothing is uploaded.  The caller fills all n entries of every
+// stream on a stream of its own and drains it before the first pp_pose_* call on the handle.
+int ppsfm::PoseCreateUnfilled(int32_t n, bool with_aligned, int device, pp_pose_handle* out, PoseStreams* streams) {
+  *out = nullptr;
+  PP_REQUIRE(n >= 0 && streams, "PoseCreateUnfilled: bad argument");
+  PP_HIP_TRY(hipSetDevice(device));
+  const size_t nn = std::max(n, 1);
+  UnderConstruction<pp_pose_impl, pp_pose_destroy> h{new pp_pose_impl()};
+  h->device = device; h->n = n;
+  PP_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  PP_HIP_TRY(hipEventCreate(&h->ev0)); PP_HIP_TRY(hipEventCreate(&h->ev1));
+  double** dst[6] = {&h->l0, &h->l1, &h->l2, &h->x0, &h->x1, &h->x2};
+  for (int c = 0; c < 6; ++c) PP_TRY(h->blocks.Alloc(dst[c], nn));
+  if (with_aligned && n > 0) PP_TRY(h->blocks.Alloc(&h->aligned, nn));
+  PP_TRY(h->blocks.Alloc(&h->best_key, 3 * 1024));
+  *streams = PoseStreams{h->l0, h->l1, h->l2, h->x0, h->x1, h->x2, h->aligned};
+  *out = h.release();
+  return PP_OK;
+}
+
+extern "C" {
 
 int pp_pose_residuals(pp_pose_handle h, int32_t num_models, const double* models, double* residuals_out) try {
   PP_REQUIRE(h && num_models >= 0 && (num_models == 0 || (models && residuals_out)), "pp_pose_residuals: bad argument");

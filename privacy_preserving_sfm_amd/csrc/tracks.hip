@@ -130,6 +130,14 @@ __global__ __launch_bounds__(64) void k_merge_pair(TrackDev d, int32_t* slot, in
 
 }  // namespace ppsfm
 
+int ppsfm::UploadPoses(pp_tracks_impl* h) {
+  PP_TRY(Upload(h->d_poses, h->poses.data(), h->poses.size(), h->stream));
+  hipLaunchKernelGGL(k_tracks_proj, dim3(CeilDiv(h->C, 256)), dim3(256), 0, h->stream, h->C, h->d_poses, h->d_proj);
+  PP_HIP_TRY(hipGetLastError());
+  if (h->d_centers) PP_TRY(ComputeCenters(h));
+  return PP_OK;
+}
+
 using namespace ppsfm;
 
 namespace {
@@ -234,7 +242,7 @@ int pp_tracks_create(const pp_tracks_desc* d, int device, pp_tracks_handle* out)
   PP_TRY(put(&h->d_line_point, (const int32_t*)nullptr, (size_t)L));
   hipLaunchKernelGGL(k_tracks_proj, dim3(CeilDiv(C, 256)), dim3(256), 0, s, C, d_poses, d_proj);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { SetLastError("pp_tracks_create: upload failed"); return PP_ERR_HIP; }
-  h->d_poses = d_poses; h->d_proj = d_proj; h->d_intr = d_intr; h->d_skip = d_skip;
+  h->d_poses = d_poses; h->d_proj = d_proj; h->d_intr = d_intr; h->d_skip = d_skip; h->d_registered = d_reg;
   h->dev.proj = d_proj; h->dev.intr = d_intr; h->dev.lines = d_lines; h->dev.pose_camera = d_pc; h->dev.camera_model = d_cm; h->dev.cam_size = d_cs;
   h->dev.line_image = d_li; h->dev.corr_start = d_c0; h->dev.corr_line = d_cl; h->dev.camera_skip = d_skip; h->dev.image_registered = d_reg;
   *out = h.release();
@@ -382,10 +390,7 @@ int pp_tracks_update(pp_tracks_handle h, int32_t num_images, const int32_t* imag
   }
   if (num_images > 0) {
     for (int32_t i = 0; i < num_images; ++i) std::copy(poses + 7 * (size_t)i, poses + 7 * (size_t)i + 7, h->poses.begin() + 7 * (size_t)image_idx[i]);
-    PP_TRY(Upload(h->d_poses, h->poses.data(), h->poses.size(), s));
-    hipLaunchKernelGGL(k_tracks_proj, dim3(CeilDiv(C, 256)), dim3(256), 0, s, C, h->d_poses, h->d_proj);
-    PP_HIP_TRY(hipGetLastError());
-    if (h->d_centers) PP_TRY(ComputeCenters(h));
+    PP_TRY(UploadPoses(h));
   }
   PP_HIP_TRY(hipStreamSynchronize(s));      // (the host copies are the handle's own: nothing of the caller's is read after the return)
   return PP_OK;

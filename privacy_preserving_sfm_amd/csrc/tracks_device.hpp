@@ -159,7 +159,7 @@ struct pp_tracks_impl {
   std::vector<double> poses, intr;      // C x 7, K x kCamStride: the host copies pp_tracks_update edits and uploads whole
   std::vector<uint8_t> camera_skip;     // K
   double *d_poses = nullptr, *d_proj = nullptr, *d_intr = nullptr;      // the writable views of dev.proj / dev.intr / dev.camera_skip
-  uint8_t* d_skip = nullptr;
+  uint8_t *d_skip = nullptr, *d_registered = nullptr;      // (d_registered: dev.image_registered, rewritten by pp_tracks_register_image)
   ppsfm::DeviceBlocks blocks;     // the static device arrays and the pinned slots (pool blocks)
   ppsfm::TrackDev dev{};
   int32_t* d_line_point = nullptr;
@@ -186,6 +186,9 @@ struct CallBlocks {
 // the C x 3 projection centres of the handle's projection matrices (tracks_image.hip): computed on first use, again after pp_tracks_update
 int ComputeCenters(pp_tracks_impl* h);
 inline int EnsureCenters(pp_tracks_impl* h) { return h->d_centers ? PP_OK : ComputeCenters(h); }
+
+// h->poses to the device, the projection matrices and (once computed) the projection centres again (tracks.hip); the caller drains the stream
+int UploadPoses(pp_tracks_impl* h);
 
 // uploads the state at the start of a call; flat track CSR in start / elems (kept alive by the caller until the stream drains)
 inline int UploadState(pp_tracks_impl* h, CallBlocks& cb, const uint8_t* subset, std::vector<int32_t>& start, std::vector<int32_t>& elems, TrackDev* d) {

@@ -617,6 +617,16 @@ def local_bundle_options(**kw):
     return o
 
 
+def next_image_options(**kw):
+    o = _capi.NextImageOptions()
+    _capi.lib().pp_next_image_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
 _TRACKS_FIELDS = (("poses", np.float64, dp), ("pose_camera", np.int32, None), ("camera_model", np.int32, None), ("intr", np.float64, dp),
                   ("cam_size", np.int32, None), ("camera_skip", np.uint8, None), ("image_registered", np.uint8, None), ("lines", np.float64, dp),
                   ("line_image", np.int32, None), ("line_point", np.int32, None), ("corr_start", np.int32, None), ("corr_line", np.int32, None),
@@ -647,6 +657,10 @@ class TracksProblem:
         self._h = C.c_void_p()
         self.num_lines = int(len(flat["line_image"]))
         self.num_images, self.num_cameras = int(np.shape(flat["poses"])[0]), int(np.shape(flat["intr"])[0])
+        self._max_image_corrs = 0      # the longest correspondence list an image's lines can give (pp_tracks_estimate_image_pose's capacity)
+        if self.num_lines:
+            per_line = np.diff(np.asarray(flat["corr_start"], dtype=np.int64))
+            self._max_image_corrs = int(np.bincount(np.asarray(flat["line_image"], dtype=np.int64), weights=per_line, minlength=self.num_images).max())
         d = tracks_desc(flat, self._keep)
         check(_capi.lib().pp_tracks_create(C.byref(d), int(device), C.byref(self._h)))
 
@@ -724,6 +738,49 @@ class TracksProblem:
                                                       ptr(oc, _capi.c_ip), dp(oa)))
         m = int(rep.num_overlapping)
         return rep, bundle[: int(rep.num_selected)].copy(), dict(image=oi[:m].copy(), count=oc[:m].copy(), tri_angle=oa[:m].copy())
+
+    def find_next_images(self, options=None, num_reg_trials=None, filtered=None):
+        """FindNextImages -> (report, ranked [n] image indices (first bucket, then second bucket), num_visible [C], num_observations [C]).
+        num_reg_trials [C] / filtered [C]: the caller's num_reg_trials_ / filtered_images_ (None: none).  The state does not change."""
+        o = options or next_image_options()
+        Cn = self.num_images
+        nt = None if num_reg_trials is None else np.ascontiguousarray(num_reg_trials, dtype=np.int32).reshape(Cn)
+        fi = None if filtered is None else np.ascontiguousarray(filtered, dtype=np.uint8).reshape(Cn)
+        ranked, vis, obs = np.zeros(Cn, dtype=np.int32), np.zeros(Cn, dtype=np.int32), np.zeros(Cn, dtype=np.int32)
+        rep = _capi.NextImageReport()
+        check(_capi.lib().pp_tracks_find_next_images(self._h, C.byref(o), ptr(nt, _capi.c_ip), ptr(fi, _capi.c_u8p), C.byref(rep), ptr(ranked, _capi.c_ip), Cn,
+                                                     ptr(vis, _capi.c_ip), ptr(obs, _capi.c_ip)))
+        return rep, ranked[: int(rep.num_ranked)].copy(), vis, obs
+
+    def estimate_image_pose(self, image, ransac, options=None, line_aligned=None):
+        """RegisterNextImage up to the pose refinement (visibility gate, 2D-3D search, P6L RANSAC, the gates) for the unregistered image index `image`
+        -> (report, pose [7] (qvec, tvec), corrs [n, 2] (line, point) in the reference's order, inlier_mask [n]).  report.failure says which
+        `return false` was taken (0: a pose was found).  ransac: a pp_ransac_options (device.ransac_options).  The state does not change."""
+        o = options or next_image_options()
+        al = None if line_aligned is None else np.ascontiguousarray(line_aligned, dtype=np.uint8)
+        assert al is None or len(al) == self.num_lines
+        cap = self._max_image_corrs
+        cl, cp, mask, pose = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.uint8), np.zeros(7)
+        rep = _capi.ImagePoseReport()
+        check(_capi.lib().pp_tracks_estimate_image_pose(self._h, C.byref(o), C.byref(ransac), int(image), ptr(al, _capi.c_u8p), C.byref(rep), dp(pose),
+                                                        ptr(cl, _capi.c_ip), ptr(cp, _capi.c_ip), ptr(mask, _capi.c_u8p), cap))
+        n = int(rep.num_corrs)
+        return rep, pose, np.stack([cl[:n], cp[:n]], axis=1), mask[:n].copy()
+
+    def register_image(self, image, pose, corrs, inlier_mask=None):
+        """The commit of RegisterNextImage: image index `image` becomes registered with pose [7]; the inliers of corrs [n, 2] (line, point) whose line
+        has no point yet get their observation -> events [m, 2] (point, line) in list order."""
+        pose = f64(pose).reshape(7)
+        corrs = np.ascontiguousarray(corrs, dtype=np.int32).reshape(-1, 2)
+        n = corrs.shape[0]
+        cl, cp = np.ascontiguousarray(corrs[:, 0]), np.ascontiguousarray(corrs[:, 1])
+        mask = None if inlier_mask is None else np.ascontiguousarray(inlier_mask, dtype=np.uint8).reshape(n)
+        ep, el = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        added = C.c_int64()
+        check(_capi.lib().pp_tracks_register_image(self._h, int(image), dp(pose), n, ptr(cl, _capi.c_ip) if n else None, ptr(cp, _capi.c_ip) if n else None,
+                                                   ptr(mask, _capi.c_u8p), C.byref(added), ptr(ep, _capi.c_ip), ptr(el, _capi.c_ip), n))
+        m = int(added.value)
+        return np.stack([ep[:m], el[:m]], axis=1)
 
     def update(self, image_idx=(), poses=None, point_idx=(), xyz=None, intr=None, camera_skip=None):
         """New poses [n, 7] of the images image_idx, positions [m, 3] of the points point_idx, intrinsics [K, 12] with camera_skip [K] or None

@@ -1,0 +1,112 @@
+"""Host mirror of the two steps of the reference's incremental mapper that pick and register an image (sfm/incremental_mapper.{h,cc}:
+`FindNextImages` :139-190, `RegisterNextImage` :570-760) on top of pp_tracks_find_next_images / pp_tracks_estimate_image_pose /
+pp_tracks_register_image (include/ppsfm_hip.h), with the state the reference keeps between them: `num_reg_trials_`, `filtered_images_`,
+`num_reg_images_per_camera_`.
+
+An unregistered image is an `Image` of `Reconstruction.images` with `registered = False` (an image without the attribute is registered).
+With `IncrementalTriangulator.TriangulateImage`, `bundle_adjustment.IterativeLocalRefinement` and `IterativeGlobalRefinement` this is the
+reference's per-image sequence (controllers/incremental_mapper.cc:420-520).  Images of equal rank are tried in ascending id (the reference leaves it
+to a hash table).  `FilterImages` / de-registration, `RegisterInitialLineImages` and the focal-length estimation (never enabled on the
+reference's line path) are not mirrored: `filtered_images_` is the caller's to fill."""
+import copy
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from .bundle_adjustment import IncrementalMapperOptions
+from .device import next_image_options, ransac_options
+from .estimators import AbsolutePoseRefinementOptions, RefineAbsolutePoseFromLines
+
+
+def ImageToWorldThreshold(camera, threshold_px):
+    """Camera::ImageToWorldThreshold (base/camera_models.h:533-543)"""
+    out = C.c_double()
+    _capi.check(_capi.lib().pp_camera_image_to_world_threshold(camera.model_id, _capi.dp(_capi.f64(camera.params)), float(threshold_px),
+                                                               C.cast(C.byref(out), _capi.c_dp)))
+    return out.value
+
+
+class IncrementalMapper:
+    def __init__(self, correspondence_graph, reconstruction, triangulator, database_cameras=None, device=0):
+        """database_cameras: {camera id: params} as the database holds them (the camera-reset branch of :686-694 restores them); default: the
+        parameters the cameras have now."""
+        assert triangulator.reconstruction_ is reconstruction and triangulator.correspondence_graph_ is correspondence_graph
+        self.correspondence_graph_, self.reconstruction_, self.triangulator_, self.device_ = correspondence_graph, reconstruction, triangulator, device
+        self.database_cameras_ = {cid: np.array(cam.params, dtype=np.float64) for cid, cam in reconstruction.cameras.items()}
+        if database_cameras:
+            self.database_cameras_.update({cid: np.array(p, dtype=np.float64) for cid, p in database_cameras.items()})
+        self.num_reg_trials_ = {}
+        self.filtered_images_ = set()
+        self.num_reg_images_per_camera_ = {}
+        reg = reconstruction.RegImageIds()
+        for image_id in reg:
+            cid = reconstruction.images[image_id].CameraId()
+            self.num_reg_images_per_camera_[cid] = self.num_reg_images_per_camera_.get(cid, 0) + 1
+        self._next_reg_index = max([getattr(reconstruction.images[i], "reg_index", -1) for i in reg], default=-1) + 1
+        self.ransac_seed = 0              # util/random.h:46 kDefaultPRNGSeed
+        self.last_report = None           # the pp_image_pose_report of the last RegisterNextImage
+        self.last_refinement = None       # its refinement's solver summary
+
+    def _tri_options(self, options):
+        o = copy.copy(getattr(options, "triangulation", None) or self.triangulator_.Options())
+        o.min_focal_length_ratio, o.max_focal_length_ratio, o.max_extra_param = options.min_focal_length_ratio, options.max_focal_length_ratio, options.max_extra_param
+        return o
+
+    @staticmethod
+    def _device_options(options):
+        assert options.abs_pose_max_error > 0 and options.abs_pose_min_num_inliers > 0 and 0 <= options.abs_pose_min_inlier_ratio <= 1      # Options::Check
+        return next_image_options(abs_pose_min_num_inliers=int(options.abs_pose_min_num_inliers), max_reg_trials=int(options.max_reg_trials),
+                                  image_selection_method=int(options.image_selection_method))
+
+    def FindNextImages(self, options=None):
+        """-> the ids of the unregistered images worth trying, best first; the images that were tried or filtered before come after the others"""
+        options = options or IncrementalMapperOptions()
+        ses = self.triangulator_._open(self._tri_options(options))
+        try:
+            return ses.find_next_images(self._device_options(options), self.num_reg_trials_, self.filtered_images_)[1]
+        finally:
+            ses.close()
+
+    def RegisterNextImage(self, options, image_id):
+        """-> True when the image was registered: its pose estimated (P6L RANSAC on the device over the 2D-3D correspondences found on the device),
+        refined (RefineAbsolutePoseFromLines) and committed with the observations of its inliers.  False leaves the reconstruction as it was, except
+        the trial count, a camera reset by :691 and - as in the reference - the image's pose when the estimate itself succeeded (:721)."""
+        options = options or IncrementalMapperOptions()
+        rec = self.reconstruction_
+        assert len(rec.RegImageIds()) >= 2
+        image = rec.Image(image_id)
+        camera = rec.Camera(image.CameraId())
+        assert not getattr(image, "registered", True), "Image cannot be registered multiple times"
+        self.num_reg_trials_[image_id] = self.num_reg_trials_.get(image_id, 0) + 1      # (:582)
+        ransac = ransac_options(max_error=ImageToWorldThreshold(camera, options.abs_pose_max_error), min_inlier_ratio=options.abs_pose_min_inlier_ratio,
+                                min_num_trials=100, max_num_trials=10000, confidence=0.99999, seed=self.ransac_seed)      # (:673-681)
+        ses = self.triangulator_._open(self._tri_options(options))
+        try:
+            rep, pose, corrs, mask, lines2D, points3D = ses.estimate_image_pose(image_id, self._device_options(options), ransac)
+            self.last_report, self.last_refinement = rep, None
+            if rep.failure in (_capi.REG_FEW_VISIBLE, _capi.REG_FEW_CORRS):
+                return False
+            refinement_options = AbsolutePoseRefinementOptions()      # (:683-714: every branch of the line path leaves both refine flags false)
+            refinement_options.print_summary = False
+            if self.num_reg_images_per_camera_.get(image.CameraId(), 0) > 0 and \
+                    camera.HasBogusParams(options.min_focal_length_ratio, options.max_focal_length_ratio, options.max_extra_param):
+                camera.params = self.database_cameras_[image.CameraId()].copy()      # previously refined camera has bogus parameters: reset (:691)
+                ses.update()
+            if rep.failure in (_capi.REG_NO_INLIERS, _capi.REG_ALIGNED):
+                return False
+            image.qvec, image.tvec = pose[:4].copy(), pose[4:].copy()      # (pose.cc:86-87: written before the NaN test and before :725)
+            if rep.failure != _capi.REG_OK:
+                return False
+            usable, self.last_refinement = RefineAbsolutePoseFromLines(refinement_options, mask, lines2D, points3D, image.qvec, image.tvec, camera,
+                                                                       device=self.device_)
+            if not usable:
+                return False
+            ses.update()      # (a refined camera; the pose goes with the commit)
+            ses.register_image(image_id, image.qvec, image.tvec, corrs, mask)
+        finally:
+            ses.close()
+        image.reg_index = self._next_reg_index
+        self._next_reg_index += 1
+        self.num_reg_images_per_camera_[image.CameraId()] = self.num_reg_images_per_camera_.get(image.CameraId(), 0) + 1      # RegisterImageEvent
+        return True

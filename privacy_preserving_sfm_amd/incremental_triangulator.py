@@ -82,6 +82,9 @@ class IncrementalTriangulator:
         self.modified_point3D_ids_ = set()
         self.last_reports = []      # the pp_tracks_report of every device call of the last driver call
 
+    def AddModifiedPoint3D(self, point3D_id):
+        self.modified_point3D_ids_.add(point3D_id)
+
     def GetModifiedPoints3D(self):
         rec = self.reconstruction_
         return set(p for p in self.modified_point3D_ids_ if p in rec.points3D)      # "assume that all other points were deleted"
@@ -291,6 +294,42 @@ class _TracksSession:
         rep, bundle, _ = self.pb.find_local_bundle(self.image_ids.index(image_id), options)
         self.t.last_reports.append(rep)
         return rep, [self.image_ids[int(c)] for c in bundle]
+
+    def find_next_images(self, options, num_reg_trials=None, filtered_images=()):
+        """FindNextImages on the handle -> (report, image ids: first bucket, then second bucket).  options: a device.next_image_options;
+        num_reg_trials {image id: trials}, filtered_images: ids (the mapper's num_reg_trials_ / filtered_images_)"""
+        trials = np.array([(num_reg_trials or {}).get(i, 0) for i in self.image_ids], dtype=np.int32)
+        filtered = np.array([i in filtered_images for i in self.image_ids], dtype=np.uint8)
+        rep, ranked, _, _ = self.pb.find_next_images(options, trials, filtered)
+        self.t.last_reports.append(rep)
+        return rep, [self.image_ids[int(c)] for c in ranked]
+
+    def estimate_image_pose(self, image_id, options, ransac):
+        """RegisterNextImage up to the pose refinement -> (report, pose [7], corrs [n, 2] (handle line, handle point), inlier_mask [n],
+        lines2D [n, 3], points3D [n, 3]: the arrays RefineAbsolutePoseFromLines takes).  The reconstruction does not change."""
+        rep, pose, corrs, mask = self.pb.estimate_image_pose(self.image_ids.index(image_id), ransac, options, self.flat["line_aligned"])
+        self.t.last_reports.append(rep)
+        lines2D = self.flat["lines"][corrs[:, 0]].reshape(-1, 3)
+        points3D = np.array([self.rec.points3D[self.ids[int(p)]].xyz for p in corrs[:, 1]], dtype=np.float64).reshape(-1, 3)
+        return rep, pose, corrs, mask, lines2D, points3D
+
+    def register_image(self, image_id, qvec, tvec, corrs, inlier_mask):
+        """the commit of RegisterNextImage on the handle AND the reconstruction: the image registered at (qvec, tvec), one AddObservation per event
+        -> [(point id, (image_id, line_idx))]"""
+        rec, t = self.rec, self.t
+        c = self.image_ids.index(image_id)
+        pose = np.concatenate([np.asarray(qvec, dtype=np.float64), np.asarray(tvec, dtype=np.float64)])
+        events = self.pb.register_image(c, pose, corrs, inlier_mask)
+        image = rec.images[image_id]
+        image.qvec, image.tvec, image.registered = pose[:4].copy(), pose[4:].copy(), True
+        self.flat["poses"][c] = pose
+        self.flat["image_registered"][c] = 1
+        out = []
+        for p, l in events:
+            rec.AddObservation(self.ids[int(p)], self.line_ref[int(l)])
+            t.AddModifiedPoint3D(self.ids[int(p)])      # (:754)
+            out.append((self.ids[int(p)], self.line_ref[int(l)]))
+        return out
 
     def update(self):
         """what a bundle adjustment changed in the reconstruction since the flattening (or the last update) goes to the handle: poses, positions of the
