@@ -776,6 +776,46 @@ int pp_tracks_estimate_image_pose(pp_tracks_handle h, const pp_next_image_option
 int pp_tracks_register_image(pp_tracks_handle h, int32_t image, const double* pose7, int64_t n, const int32_t* corr_line, const int32_t* corr_point,
                              const uint8_t* inlier_mask, int64_t* num_added, int32_t* event_point, int32_t* event_line, int64_t capacity);
 
+/* ---- Point filters and image de-registration on a pp_tracks_handle (kernels K14a k_track_filter, K14b k_track_depth) ------------------------------
+ * replaces, on the live handle, Reconstruction::FilterPoints3D / FilterPoints3DInImages / FilterAllPoints3D (base/reconstruction.cc:412-439, 594-719),
+ * FilterObservationsWithNegativeDepth (:442-460), FilterImages (:462-484) and DeRegisterImage (:285-300), with DeleteObservation's rule that a track of
+ * at most three elements takes its point with it (:264-267).  pp_ba_filter_points / pp_ba_filter_negative_depth state the same rules on a pp_ba_handle;
+ * these run on the tracks, projection matrices and projection centres the tracks handle already holds, so the mapper neither flattens the model nor
+ * builds a second problem to filter it, and the handle stays valid afterwards: one handle serves a reconstruction from its first images to its last.
+ * K14a: one wavefront per point - the line error of every track element, the deletion rules of the two point filters, then the triangulation angle over
+ * the pairs of surviving elements.  K14b: one lane per line - HasPointPositiveDepth.  The host applies the verdicts (csrc/tracks_filter_replay.hpp).
+ * EVENTS, in the order the reference's Reconstruction sees them: (p, l) for a DeleteObservation that removed ONE element, (p, -1) for a DeletePoint3D
+ * (a point a filter rule deleted, or the rest of a track that fell to three elements).  Events beyond `capacity` are not written (num_entries counts them all).
+ * The point filter visits the points in ascending index and a point's elements in track order; a point the rules delete gives one (p, -1) event.
+ * A DELETED point (merged away, filtered earlier) inside a subset is skipped, as the reference skips an id that no longer exists.
+ * AFTER any of the three calls every later pp_tracks_* call, pp_tracks_get_state included, behaves as on a handle created from the resulting arrays.
+ * ERRORS: PP_ERR_INVALID (a null argument, a negative option, both subsets given, an image_order that is not exactly the registered images, each once) is
+ * decided before anything changes and leaves the handle as it was; any other error is as pp_tracks_complete's (destroy the handle).              */
+typedef struct pp_tracks_filter_report {
+  int64_t num_filtered;                /* the reference's return value */
+  int64_t num_points_deleted, num_observations_deleted;   /* the latter: track elements removed, those of deleted points included */
+  int64_t num_entries;
+  int32_t points_tested, images_filtered;
+  double device_ms, replay_ms, total_ms;
+} pp_tracks_filter_report;
+
+/* FilterPoints3D over point_subset (P' bytes over the CURRENT points), FilterPoints3DInImages over image_subset (C bytes: the points with a track element
+ * in a flagged image), FilterAllPoints3D when both are NULL.  point_error (P', may be NULL): Point3D::Error of the points the filter kept, -1 elsewhere. */
+int pp_tracks_filter_points(pp_tracks_handle h, const pp_filter_options* o, const uint8_t* line_aligned /* L, NULL = none */,
+                            const uint8_t* point_subset /* P' or NULL */, const uint8_t* image_subset /* C or NULL */,
+                            pp_tracks_filter_report* report, int32_t* event_point, int32_t* event_line, int64_t capacity,
+                            double* point_error /* P', -1 where not set; may be NULL */);
+/* FilterObservationsWithNegativeDepth.  image_order: the registered images in the order of their registration (the order of the reference's loop); the
+ * lines of an image are visited in ascending index.  A flagged line whose point an earlier deletion of the call removed is not counted. */
+int pp_tracks_filter_negative_depth(pp_tracks_handle h, const int32_t* image_order, int32_t num_registered,
+                                    pp_tracks_filter_report* report, int32_t* event_point, int32_t* event_line, int64_t capacity);
+/* FilterImages: the registered images, in image_order, that have no line with a point or whose camera is flagged in camera_skip are collected, then
+ * de-registered in that order (every observation deleted, image_registered cleared on the host and on the device).  filtered_images (C entries) receives
+ * them; report->images_filtered = report->num_filtered counts them.  A host pass over the lines: no kernel.  The kMinNumImages gate of
+ * IncrementalMapper::FilterImages is the caller's. */
+int pp_tracks_filter_images(pp_tracks_handle h, const int32_t* image_order, int32_t num_registered, int32_t* filtered_images /* C */,
+                            pp_tracks_filter_report* report, int32_t* event_point, int32_t* event_line, int64_t capacity);
+
 /* ======================================================================================== *
  *  Four-view line initialisation (LO-MSAC)                                                   *
  *  replaces, for the out-of-plane-translation stage: ransac_lib::LocallyOptimizedMSAC<        *

@@ -159,6 +159,11 @@ class ImagePoseReport(C.Structure):
                 ("num_aligned_inliers", C.c_int32), ("reserved_", C.c_int32), ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class TracksFilterReport(C.Structure):
+    _fields_ = [("num_filtered", C.c_int64), ("num_points_deleted", C.c_int64), ("num_observations_deleted", C.c_int64), ("num_entries", C.c_int64),
+                ("points_tested", C.c_int32), ("images_filtered", C.c_int32), ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -191,6 +196,7 @@ _EXPORTS = [
     "pp_tracks_image_options_default", "pp_tracks_triangulate_image", "pp_tracks_complete_image",
     "pp_local_bundle_options_default", "pp_tracks_find_local_bundle", "pp_tracks_update",
     "pp_next_image_options_default", "pp_tracks_find_next_images", "pp_tracks_estimate_image_pose", "pp_tracks_register_image",
+    "pp_tracks_filter_points", "pp_tracks_filter_negative_depth", "pp_tracks_filter_images",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -300,6 +306,9 @@ def lib():
     L.pp_tracks_estimate_image_pose.argtypes = [C.c_void_p, C.POINTER(NextImageOptions), C.POINTER(RansacOptions), C.c_int32, c_u8p, C.POINTER(ImagePoseReport),
                                                 c_dp, c_ip, c_ip, c_u8p, C.c_int64]
     L.pp_tracks_register_image.argtypes = [C.c_void_p, C.c_int32, c_dp, C.c_int64, c_ip, c_ip, c_u8p, C.POINTER(C.c_int64), c_ip, c_ip, C.c_int64]
+    L.pp_tracks_filter_points.argtypes = [C.c_void_p, C.POINTER(FilterOptions), c_u8p, c_u8p, c_u8p, C.POINTER(TracksFilterReport), c_ip, c_ip, C.c_int64, c_dp]
+    L.pp_tracks_filter_negative_depth.argtypes = [C.c_void_p, c_ip, C.c_int32, C.POINTER(TracksFilterReport), c_ip, c_ip, C.c_int64]
+    L.pp_tracks_filter_images.argtypes = [C.c_void_p, c_ip, C.c_int32, c_ip, C.POINTER(TracksFilterReport), c_ip, c_ip, C.c_int64]
     L.pp_camera_image_to_world_threshold.argtypes = [C.c_int, c_dp, C.c_double, c_dp]
     _lib = L
     return L

@@ -282,6 +282,15 @@ class Reconstruction:
                 self.DeleteObservation(iid, idx)
         return n
 
+    def DeRegisterImage(self, image_id):
+        """The bookkeeping half of Reconstruction::DeRegisterImage (base/reconstruction.cc:285-300): the image leaves the registered ones (`registered`
+        False, `reg_index` dropped).  Its observations are deleted by the events of pp_tracks_filter_images, which the caller applies
+        (incremental_triangulator._TracksSession.filter_images)."""
+        image = self.images[image_id]
+        image.registered = False
+        if hasattr(image, "reg_index"):
+            del image.reg_index
+
     def RegImageIds(self):
         """The registered images in the order of their registration.  An image is registered unless it carries `registered = False`
         (incremental_mapper.IncrementalMapper.RegisterNextImage turns it into True and numbers it with `reg_index`); the images that were registered
@@ -790,18 +799,37 @@ def GlobalBundleAdjustmentConfig(reconstruction):
     return config
 
 
-def AdjustGlobalBundle(reconstruction, ba_options, device=0, summary_out=None):
+def _live_session(reconstruction, triangulator=None, options=None):
+    """the live session of an active `with triangulator.Session(...)` over this reconstruction (brought up to date with the reconstruction's values), or
+    None.  The session registers itself on the reconstruction (`_session_triangulator`), so a call that was not handed the triangulator finds it too and
+    cannot delete observations behind the handle's back."""
+    triangulator = getattr(reconstruction, "_session_triangulator", None) or triangulator
+    if triangulator is None or triangulator._live is None:
+        return None
+    assert triangulator.reconstruction_ is reconstruction
+    return triangulator._open(options or triangulator._live.options)
+
+
+def AdjustGlobalBundle(reconstruction, ba_options, device=0, summary_out=None, triangulator=None):
     """IncrementalMapper::AdjustGlobalBundle (sfm/incremental_mapper.cc:893-939): negative-depth filter, all images with the gauge fixed, solve,
-    Normalize.  Returns the solve's success; `summary_out` (a list) receives the solver summary.  `fix_existing_images` is not mirrored."""
-    reconstruction.FilterObservationsWithNegativeDepth(device=device)
+    Normalize.  Returns the solve's success; `summary_out` (a list) receives the solver summary.  `fix_existing_images` is not mirrored.
+    Inside a `with triangulator.Session(...)` the filter runs on the session's handle (pp_tracks_filter_negative_depth, with DeleteObservation's
+    "a track of three takes its point" rule, which `Reconstruction.DeleteObservation` and so the path outside a session do not have) and the handle
+    receives what the solve and Normalize changed; an active session over this reconstruction is found with or without `triangulator`."""
+    live = _live_session(reconstruction, triangulator)
+    if live is not None:
+        live.filter_negative_depth()
+    else:
+        reconstruction.FilterObservationsWithNegativeDepth(device=device)
     bundle_adjuster = BundleAdjuster(ba_options, GlobalBundleAdjustmentConfig(reconstruction), device=device)
     ok = bundle_adjuster.Solve(reconstruction)
     if summary_out is not None:
         summary_out.append(bundle_adjuster.Summary())
-    if not ok:
-        return False
-    reconstruction.Normalize()
-    return True
+    if ok:
+        reconstruction.Normalize()
+    if live is not None:
+        live.update()
+    return bool(ok)
 
 
 class GlobalRefinementReport:
@@ -818,15 +846,18 @@ class GlobalRefinementReport:
         self.obs_deleted, self.point_deleted = [], []
         self.num_completed, self.num_merged, self.completed, self.merged = [], [], [], []
         self.initial = None
+        self.num_filtered_images = 0      # the closing FilterImages' count (with a mapper)
 
 
-def IterativeGlobalRefinement(reconstruction, mapper_options=None, device=0, triangulator=None):
+def IterativeGlobalRefinement(reconstruction, mapper_options=None, device=0, triangulator=None, mapper=None):
     """IterativeGlobalRefinement (controllers/incremental_mapper.cc:102-124): up to `ba_global_max_refinements` rounds of AdjustGlobalBundle,
     CompleteAndMergeTracks and FilterAllPoints3D, until a round changes less than `ba_global_max_refinement_change` of the observations.
     `triangulator` (an incremental_triangulator.IncrementalTriangulator over this reconstruction; its options are `mapper_options.triangulation`
     when that exists, the reference's defaults otherwise) does CompleteAndMergeTracks before the loop and in every round between the bundle adjustment and
-    the filter.  Without one that step is left out and `changed` counts filtered observations only, as before.  The closing FilterImages is the image
-    bookkeeping's work, which this package does not mirror."""
+    the filter.  Without one that step is left out and `changed` counts filtered observations only, as before.  `mapper` (an
+    incremental_mapper.IncrementalMapper over this reconstruction): the closing FilterImages (:122) is its `FilterImages(mapper_options)`; its count goes to
+    `report.num_filtered_images`.  Inside a `with triangulator.Session(...)` the negative-depth filter and FilterAllPoints3D run on the session's handle
+    (pp_tracks_filter_*) instead of flattening the reconstruction into a throw-away problem each."""
     options = mapper_options or IncrementalMapperOptions()
     report = GlobalRefinementReport()
     tri_options = None
@@ -836,14 +867,19 @@ def IterativeGlobalRefinement(reconstruction, mapper_options=None, device=0, tri
     for _ in range(options.ba_global_max_refinements):
         num_observations = reconstruction.ComputeNumObservations()
         summaries = []
-        AdjustGlobalBundle(reconstruction, GlobalBundleAdjustmentOptions(len(reconstruction.RegImageIds()), options), device=device, summary_out=summaries)
+        AdjustGlobalBundle(reconstruction, GlobalBundleAdjustmentOptions(len(reconstruction.RegImageIds()), options), device=device, summary_out=summaries,
+                           triangulator=triangulator)
         num_changed = 0
         if triangulator is not None:
             nc, nm, completed, merged = triangulator.CompleteAndMergeAllTracks(tri_options)
             report.num_completed.append(nc); report.num_merged.append(nm); report.completed.append(completed); report.merged.append(merged)
             num_changed = nc + nm
         obs_before, points_before = reconstruction._observations(), set(reconstruction.points3D)
-        num_filtered = reconstruction.FilterAllPoints3D(options.filter_max_reproj_error, options.filter_min_tri_angle, device=device)
+        live = _live_session(reconstruction, triangulator, tri_options)
+        if live is not None:
+            num_filtered = live.filter_points(options.filter_max_reproj_error, options.filter_min_tri_angle)
+        else:
+            num_filtered = reconstruction.FilterAllPoints3D(options.filter_max_reproj_error, options.filter_min_tri_angle, device=device)
         changed = float(num_changed + num_filtered) / num_observations if num_observations else 0.0
         report.num_rounds += 1
         report.summaries.append(summaries[0] if summaries else None)
@@ -853,6 +889,8 @@ def IterativeGlobalRefinement(reconstruction, mapper_options=None, device=0, tri
         report.point_deleted.append(sorted(points_before - set(reconstruction.points3D)))
         if changed < options.ba_global_max_refinement_change:
             break
+    if mapper is not None:
+        report.num_filtered_images = mapper.FilterImages(options)
     return report
 
 
@@ -934,7 +972,8 @@ def AdjustLocalBundle(reconstruction, triangulator, options, ba_options, tri_opt
                       num_reg_images_per_camera=None, device=0):
     """IncrementalMapper::AdjustLocalBundle (sfm/incremental_mapper.cc:781-891) -> LocalBundleAdjustmentReport.  ONE tracks handle serves
     FindLocalBundle, then takes what the bundle adjustment changed (pp_tracks_update), then MergeTracks, CompleteTracks and CompleteImage; the two
-    filters run on the reconstruction afterwards.  `num_reg_images_per_camera` None: counted from the reconstruction's registered images."""
+    filters run on the reconstruction afterwards - or, inside a `with triangulator.Session(...)`, on that same handle (pp_tracks_filter_points), which
+    stays valid for the next step.  `num_reg_images_per_camera` None: counted from the reconstruction's registered images."""
     assert triangulator.reconstruction_ is reconstruction
     report = LocalBundleAdjustmentReport()
     point3D_ids = set(point3D_ids)
@@ -958,6 +997,12 @@ def AdjustLocalBundle(reconstruction, triangulator, options, ba_options, tri_opt
         ses.close()
     obs_before, points_before = reconstruction._observations(), set(reconstruction.points3D)
     filter_image_ids = set([image_id]) | set(local_bundle)
+    if ses.live:
+        report.num_filtered_observations = ses.filter_points(options.filter_max_reproj_error, options.filter_min_tri_angle, image_ids=filter_image_ids)
+        report.num_filtered_observations += ses.filter_points(options.filter_max_reproj_error, options.filter_min_tri_angle, point3D_ids=point3D_ids)
+        report.obs_deleted = sorted(obs_before - reconstruction._observations())
+        report.point_deleted = sorted(points_before - set(reconstruction.points3D))
+        return report
     report.num_filtered_observations = reconstruction.FilterPoints3DInImages(options.filter_max_reproj_error, options.filter_min_tri_angle,
                                                                             filter_image_ids, device=device)
     report.num_filtered_observations += reconstruction.FilterPoints3D(options.filter_max_reproj_error, options.filter_min_tri_angle,

@@ -46,16 +46,6 @@ __global__ __launch_bounds__(256) void k_proj_centers(int C, const double* __res
   for (int i = 0; i < 3; ++i) centers[3 * (size_t)c + i] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);
 }
 
-__device__ __forceinline__ double TriangulationAngle(const double* c1, const double* c2, double X0, double X1, double X2) {
-  const double b2 = (c1[0] - c2[0]) * (c1[0] - c2[0]) + (c1[1] - c2[1]) * (c1[1] - c2[1]) + (c1[2] - c2[2]) * (c1[2] - c2[2]);
-  const double r1 = (X0 - c1[0]) * (X0 - c1[0]) + (X1 - c1[1]) * (X1 - c1[1]) + (X2 - c1[2]) * (X2 - c1[2]);
-  const double r2 = (X0 - c2[0]) * (X0 - c2[0]) + (X1 - c2[1]) * (X1 - c2[1]) + (X2 - c2[2]) * (X2 - c2[2]);
-  const double den = 2.0 * sqrt(r1 * r2);
-  if (den == 0.0) return 0.0;
-  const double ang = fabs(acos((r1 + r2 - b2) / den));
-  return fmin(ang, 3.14159265358979323846 - ang);
-}
-
 // per point: both point filters over its track (the observations of the point in problem order)
 __global__ __launch_bounds__(256) void k_filter_points(int P, const int32_t* __restrict__ pt_start, const int32_t* __restrict__ pt_obs, const int32_t* __restrict__ obs_pose,
                                                        const uint8_t* __restrict__ obs_aligned, const double* __restrict__ err2, const double* __restrict__ centers,

@@ -33,4 +33,16 @@ __device__ __forceinline__ double SquaredPixelLineError(double px, double py, do
   return (ix - jx) * (ix - jx) + (iy - jy) * (iy - jy);
 }
 
+// CalculateTriangulationAngle (reference src/base/triangulation.cc:59-82) at the projection centres c1, c2: the point filters of ba_filter.hip (K7b) and
+// tracks_filter.hip (K14a) decide on the same arithmetic
+__device__ __forceinline__ double TriangulationAngle(const double* c1, const double* c2, double X0, double X1, double X2) {
+  const double b2 = (c1[0] - c2[0]) * (c1[0] - c2[0]) + (c1[1] - c2[1]) * (c1[1] - c2[1]) + (c1[2] - c2[2]) * (c1[2] - c2[2]);
+  const double r1 = (X0 - c1[0]) * (X0 - c1[0]) + (X1 - c1[1]) * (X1 - c1[1]) + (X2 - c1[2]) * (X2 - c1[2]);
+  const double r2 = (X0 - c2[0]) * (X0 - c2[0]) + (X1 - c2[1]) * (X1 - c2[1]) + (X2 - c2[2]) * (X2 - c2[2]);
+  const double den = 2.0 * sqrt(r1 * r2);
+  if (den == 0.0) return 0.0;
+  const double ang = fabs(acos((r1 + r2 - b2) / den));
+  return fmin(ang, 3.14159265358979323846 - ang);
+}
+
 }  // namespace ppsfm

@@ -782,6 +782,42 @@ class TracksProblem:
         m = int(added.value)
         return np.stack([ep[:m], el[:m]], axis=1)
 
+    def _filter_call(self, fn, args, trailing=()):
+        cap = self.num_lines + self.num_points()[0]      # a line loses its point once, a point is deleted once
+        ep, el = np.zeros(max(cap, 1), dtype=np.int32), np.zeros(max(cap, 1), dtype=np.int32)
+        rep = _capi.TracksFilterReport()
+        check(fn(self._h, *args, C.byref(rep), ptr(ep, _capi.c_ip), ptr(el, _capi.c_ip), cap, *trailing))
+        n = int(rep.num_entries)
+        return rep, np.stack([ep[:n], el[:n]], axis=1)
+
+    def filter_points(self, max_reproj_error, min_tri_angle_deg, line_aligned=None, point_subset=None, image_subset=None):
+        """FilterPoints3D (point_subset [P'] flags) / FilterPoints3DInImages (image_subset [C] flags) / FilterAllPoints3D (neither) on the handle
+        -> (report, events [n, 2]: (point, line) for one deleted observation, (point, -1) for a deleted point, in the reference's order,
+        point_error [P']: Point3D.error of the points the filter kept, -1 elsewhere)"""
+        o = _capi.FilterOptions(float(max_reproj_error), float(min_tri_angle_deg))
+        al = None if line_aligned is None else np.ascontiguousarray(line_aligned, dtype=np.uint8)
+        assert al is None or len(al) == self.num_lines
+        P = self.num_points()[0]
+        sub = self._subset(point_subset)
+        img = None if image_subset is None else np.ascontiguousarray(image_subset, dtype=np.uint8)
+        assert (sub is None or len(sub) == P) and (img is None or len(img) == self.num_images)
+        pe = np.full(max(P, 1), -1.0)
+        rep, events = self._filter_call(_capi.lib().pp_tracks_filter_points, (C.byref(o), ptr(al, _capi.c_u8p), ptr(sub, _capi.c_u8p), ptr(img, _capi.c_u8p)),
+                                        trailing=(dp(pe),))
+        return rep, events, pe[:P]
+
+    def filter_negative_depth(self, image_order):
+        """FilterObservationsWithNegativeDepth; image_order: the registered image indices in registration order -> (report, events as filter_points)"""
+        order = np.ascontiguousarray(image_order, dtype=np.int32).reshape(-1)
+        return self._filter_call(_capi.lib().pp_tracks_filter_negative_depth, (ptr(order, _capi.c_ip) if len(order) else None, len(order)))
+
+    def filter_images(self, image_order):
+        """FilterImages: the registered images without a point or with a flagged camera are de-registered -> (report, events, filtered image indices)"""
+        order = np.ascontiguousarray(image_order, dtype=np.int32).reshape(-1)
+        out = np.zeros(max(self.num_images, 1), dtype=np.int32)
+        rep, events = self._filter_call(_capi.lib().pp_tracks_filter_images, (ptr(order, _capi.c_ip) if len(order) else None, len(order), ptr(out, _capi.c_ip)))
+        return rep, events, out[: int(rep.images_filtered)].copy()
+
     def update(self, image_idx=(), poses=None, point_idx=(), xyz=None, intr=None, camera_skip=None):
         """New poses [n, 7] of the images image_idx, positions [m, 3] of the points point_idx, intrinsics [K, 12] with camera_skip [K] or None
         (after a bundle adjustment); every later call sees them."""

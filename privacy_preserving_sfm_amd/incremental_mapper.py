@@ -6,8 +6,10 @@ pp_tracks_register_image (include/ppsfm_hip.h), with the state the reference kee
 An unregistered image is an `Image` of `Reconstruction.images` with `registered = False` (an image without the attribute is registered).
 With `IncrementalTriangulator.TriangulateImage`, `bundle_adjustment.IterativeLocalRefinement` and `IterativeGlobalRefinement` this is the
 reference's per-image sequence (controllers/incremental_mapper.cc:420-520).  Images of equal rank are tried in ascending id (the reference leaves it
-to a hash table).  `FilterImages` / de-registration, `RegisterInitialLineImages` and the focal-length estimation (never enabled on the
-reference's line path) are not mirrored: `filtered_images_` is the caller's to fill."""
+to a hash table).  `FilterPoints` (:965-970) and `FilterImages` (:941-963, with `DeRegisterImageEvent` :1177-1192) run on the tracks handle
+(pp_tracks_filter_points / pp_tracks_filter_images) and fill `filtered_images_`.  Inside `with triangulator.Session(options):` every step here and in
+bundle_adjustment's refinement loops shares ONE handle.  `RegisterInitialLineImages` and the focal-length estimation (never enabled on the reference's
+line path) are not mirrored."""
 import copy
 import ctypes as C
 
@@ -67,6 +69,36 @@ class IncrementalMapper:
             return ses.find_next_images(self._device_options(options), self.num_reg_trials_, self.filtered_images_)[1]
         finally:
             ses.close()
+
+    def FilterPoints(self, options=None):
+        """IncrementalMapper::FilterPoints (:965-970): FilterAllPoints3D -> num_filtered"""
+        options = options or IncrementalMapperOptions()
+        ses = self.triangulator_._open(self._tri_options(options))
+        try:
+            return ses.filter_points(options.filter_max_reproj_error, options.filter_min_tri_angle)
+        finally:
+            ses.close()
+
+    def FilterImages(self, options=None):
+        """IncrementalMapper::FilterImages (:941-963): nothing while fewer than 20 images are registered; then the registered images without a point or with
+        bogus camera parameters are de-registered, counted out of `num_reg_images_per_camera_` (DeRegisterImageEvent) and remembered in
+        `filtered_images_` -> their number"""
+        options = options or IncrementalMapperOptions()
+        rec = self.reconstruction_
+        kMinNumImages = 20
+        if len(rec.RegImageIds()) < kMinNumImages:
+            return 0
+        ses = self.triangulator_._open(self._tri_options(options))
+        try:
+            image_ids = ses.filter_images()
+        finally:
+            ses.close()
+        for image_id in image_ids:
+            cid = rec.images[image_id].CameraId()
+            assert self.num_reg_images_per_camera_.get(cid, 0) > 0
+            self.num_reg_images_per_camera_[cid] -= 1
+            self.filtered_images_.add(image_id)
+        return len(image_ids)
 
     def RegisterNextImage(self, options, image_id):
         """-> True when the image was registered: its pose estimated (P6L RANSAC on the device over the 2D-3D correspondences found on the device),

@@ -3,7 +3,8 @@
 (base/correspondence_graph.h `FindCorrespondences`), on top of pp_tracks_* (include/ppsfm_hip.h).
 
 Each call flattens the reconstruction (`flatten`), hands it to the device and applies what comes back through `Reconstruction.AddObservation` /
-`Reconstruction.MergePoints3D`.  The reference visits the points in the order of an unordered_set; here the order is ASCENDING POINT ID.
+`Reconstruction.MergePoints3D` - unless a `Session` is active (`with triangulator.Session(options):`), in which case ONE handle serves every call until the
+block ends, the mapper's filters and de-registration included (pp_tracks_filter_*).  The reference visits the points in the order of an unordered_set; here the order is ASCENDING POINT ID.
 `TriangulateImage` and `CompleteImage` (the two places where the reference creates points) visit the lines of the image in ascending index, as the
 reference does.  `Retriangulate` (commented out in the reference) is not mirrored."""
 import numpy as np
@@ -81,6 +82,7 @@ class IncrementalTriangulator:
         self.correspondence_graph_, self.reconstruction_, self.device_ = correspondence_graph, reconstruction, device
         self.modified_point3D_ids_ = set()
         self.last_reports = []      # the pp_tracks_report of every device call of the last driver call
+        self._live = None           # the session of an active `with self.Session(...)`
 
     def AddModifiedPoint3D(self, point3D_id):
         self.modified_point3D_ids_.add(point3D_id)
@@ -148,7 +150,21 @@ class IncrementalTriangulator:
         """-> _TracksSession: ONE TracksProblem over the flattened reconstruction, on which several operations run one after the other (each applies
         its result to the reconstruction at once); close() it when done.  Internal: _run / _run_image and bundle_adjustment.AdjustLocalBundle."""
         assert options.Check()
+        if self._live is not None:
+            return self._live.reopen(options)
         return _TracksSession(self, options)
+
+    def Session(self, options=None):
+        """`with triangulator.Session(options) as ses:` - ONE TracksProblem for everything inside the block: while it is active `_open` hands out this live
+        session (brought up to date with the reconstruction's poses, positions and intrinsics first) and the inner close() calls do nothing, so
+        FindNextImages, RegisterNextImage, TriangulateImage, the local and global refinement and the mapper's filters run on one handle, from the first
+        images of a reconstruction to its last.  Inside the block the points and observations of the reconstruction change through this module,
+        bundle_adjustment's refinement functions (which find the active session through the reconstruction, with or without `triangulator=`) and the mapper
+        only: a direct `Reconstruction.Filter*` / `DeleteObservation` / `DeletePoint3D` call would change the model behind the handle's back.
+        EVERY `_open` inside the block still costs O(images + points) on the host: `update()` compares every pose, position and intrinsic parameter with what
+        the handle holds and sends the ones that differ.
+        A call whose options differ from the session's in a field the handle baked in (the camera_skip thresholds) raises ValueError."""
+        return _LiveSession(self, options or self.Options())
 
     def _run(self, options, point3D_ids, complete, merge):
         assert options.Check()
@@ -222,8 +238,53 @@ class _TracksSession:
         self.cam_ids = sorted(self.rec.cameras)
         self.pb = TracksProblem(self.flat, device=triangulator.device_)
 
+    live = False      # True: the session of a `with triangulator.Session(...)`, which outlives the call that opened it
+
     def close(self):
         self.pb.close()
+
+    def _apply_deletions(self, events):
+        """the events of a pp_tracks_filter_* call on the reconstruction: (p, -1) deletes the point, (p, l) removes that one element"""
+        rec = self.rec
+        for p, l in events:
+            if l < 0:
+                rec.DeletePoint3D(self.ids[int(p)])
+            else:
+                rec.DeleteObservation(*self.line_ref[int(l)])
+
+    def filter_points(self, max_reproj_error, min_tri_angle, point3D_ids=None, image_ids=None):
+        """Reconstruction::FilterPoints3D (point3D_ids) / FilterPoints3DInImages (image_ids) / FilterAllPoints3D (neither) on the handle and, through its
+        events, on the reconstruction; Point3D.error is set on the points the filter kept -> num_filtered"""
+        assert point3D_ids is None or image_ids is None
+        images = None if image_ids is None else np.array([i in set(image_ids) for i in self.image_ids], dtype=np.uint8)
+        rep, events, point_error = self.pb.filter_points(max_reproj_error, min_tri_angle, self.flat["line_aligned"], self._subset(point3D_ids), images)
+        self.t.last_reports.append(rep)
+        self._apply_deletions(events)
+        for k in np.flatnonzero(point_error != -1.0):
+            self.rec.points3D[self.ids[int(k)]].error = float(point_error[k])
+        return int(rep.num_filtered)
+
+    def _image_order(self):
+        index = {i: c for c, i in enumerate(self.image_ids)}
+        return [index[i] for i in self.rec.RegImageIds()]
+
+    def filter_negative_depth(self):
+        """Reconstruction::FilterObservationsWithNegativeDepth, the images in rec.RegImageIds() order -> num_filtered"""
+        rep, events = self.pb.filter_negative_depth(self._image_order())
+        self.t.last_reports.append(rep)
+        self._apply_deletions(events)
+        return int(rep.num_filtered)
+
+    def filter_images(self):
+        """Reconstruction::FilterImages with the thresholds of the session's options -> the ids of the de-registered images, in order"""
+        rep, events, filtered = self.pb.filter_images(self._image_order())
+        self.t.last_reports.append(rep)
+        self._apply_deletions(events)
+        out = [self.image_ids[int(c)] for c in filtered]
+        for c, image_id in zip(filtered, out):
+            self.rec.DeRegisterImage(image_id)
+            self.flat["image_registered"][int(c)] = 0
+        return out
 
     def _subset(self, point3D_ids):
         if point3D_ids is None:
@@ -336,7 +397,10 @@ class _TracksSession:
         points that still exist, intrinsics with camera_skip decided again"""
         rec, flat, o = self.rec, self.flat, self.options
         poses = np.array([np.concatenate([rec.images[i].qvec, rec.images[i].tvec]) for i in self.image_ids]).reshape(-1, 7)
-        ii = np.flatnonzero((poses != flat["poses"]).any(axis=1)).astype(np.int32)
+        changed = (poses != flat["poses"]).any(axis=1)
+        if self.live:      # (a failed RegisterNextImage may leave a non-finite pose on its unregistered image, pose.cc:86-89: no kernel reads it, the handle refuses it)
+            changed &= np.isfinite(poses).all(axis=1) | flat["image_registered"].astype(bool)
+        ii = np.flatnonzero(changed).astype(np.int32)
         live = [(k, pid) for k, pid in enumerate(self.ids) if pid in rec.points3D]
         npts = max(len(self.ids), flat["points"].shape[0])
         if flat["points"].shape[0] < npts:      # points created since: their positions came from the handle itself
@@ -358,6 +422,44 @@ class _TracksSession:
             flat["points"][k] = x
         if intr is not None:
             flat["intr"], flat["camera_skip"] = intr, skip
+
+
+class _LiveTracksSession(_TracksSession):
+    live = True
+
+    def close(self):      # (the inner calls' close(): the handle lives until the `with` block ends)
+        pass
+
+    def reopen(self, options):
+        baked = ("min_focal_length_ratio", "max_focal_length_ratio", "max_extra_param")
+        if any(getattr(options, f) != getattr(self.baked_options, f) for f in baked):
+            raise ValueError("the options differ from the session's in %s, which the handle's camera_skip was decided with" %
+                             [f for f in baked if getattr(options, f) != getattr(self.baked_options, f)])
+        self.options = options
+        self.update()      # what changed in the reconstruction's values since the last call (a bundle adjustment, Normalize, a camera reset)
+        return self
+
+
+class _LiveSession:
+    """the context manager of IncrementalTriangulator.Session"""
+
+    def __init__(self, triangulator, options):
+        assert options.Check()
+        self.t, self.options, self.ses = triangulator, options, None
+
+    def __enter__(self):
+        assert self.t._live is None, "a Session is active already"
+        self.ses = _LiveTracksSession(self.t, self.options)
+        self.ses.baked_options = self.options
+        self.t._live = self.ses
+        self.t.reconstruction_._session_triangulator = self.t      # (bundle_adjustment's refinement functions find the session without being handed it)
+        return self.ses
+
+    def __exit__(self, *exc):
+        self.t._live = None
+        self.t.reconstruction_._session_triangulator = None
+        self.ses.pb.close()
+        return False
 
 
 def reconstruction_from_completion_scene(scene):
