@@ -816,6 +816,61 @@ int pp_tracks_filter_negative_depth(pp_tracks_handle h, const int32_t* image_ord
 int pp_tracks_filter_images(pp_tracks_handle h, const int32_t* image_order, int32_t num_registered, int32_t* filtered_images /* C */,
                             pp_tracks_filter_report* report, int32_t* event_point, int32_t* event_line, int64_t capacity);
 
+/* ---- The image sets of RegisterInitialLineImages on a pp_tracks_handle (kernels K15 k_initial_tracks<count / fill>, k_initial_keys) -------------
+ * replaces the search for the image quadruples worth a four-view solve in IncrementalMapper::RegisterInitialLineImages (sfm/incremental_mapper.cc:199-435):
+ * assemble_tracks (:265-290) over every line of the check images with the alignment filter (:326-332), the de-duplication the reference leaves to a
+ * map from image set to a set of feature-index quadruples per class (:243-250, :353-359), the qualifying rule (:393-409), the ranking (:416-423) and the truncation to
+ * max_num_init_tries sets (:434-435).  The console histograms (:365-383) are not mirrored.  The four-view solve itself is pp_fourview2d_lomsac /
+ * pp_planar_lomsac below; the commit is pp_tracks_register_image with n = 0, then pp_tracks_triangulate_image, pp_tracks_complete, pp_tracks_merge: the
+ * handle serves a reconstruction from ZERO registered images (P = 0 points, image_registered all 0) to its last.
+ * A line r of a check image keeps the neighbours n with line_aligned[n] == line_aligned[r] whose image is in the subset; every index triple i < j < k of that
+ * list for which the four images (r's and the three neighbours') are pairwise different is one TRACK: the four handle line numbers ordered by image index.
+ * Identical tracks reached from several lines count once; the graph need not be symmetric.  A SET is the four image indices of a track; it QUALIFIES with
+ * at least min_num_aligned_tracks aligned AND at least min_num_random_tracks unaligned unique tracks (and at least one of each).
+ * The device counts the triples (one wavefront per line), scans, writes them as 16-byte records, sorts and de-duplicates them, keys them by image set
+ * and run-length encodes the keys; the host ranks the runs (csrc/initial_sets_replay.hpp).
+ * PINNED where the reference is unspecified (its sort is not a stable one): sets of equal aligned count are ordered by ASCENDING IMAGE SET, lexicographic over
+ * the image indices, as pp_tracks_find_next_images and pp_tracks_find_local_bundle pin equal ranks.
+ * LIMITS: the set key packs four image indices of 15 bits: at most 32768 images; max_candidates at most 2^31 - 1.
+ * The call does not change the handle and reads nothing of its state.
+ * ERRORS: PP_ERR_INVALID - decided before any device work, and before the handle is read where only the other arguments are wrong - for a null handle,
+ * options, report, line_aligned or check_images, num_check <= 0, a check image that is negative, repeated, out of range or outside the subset, a negative
+ * option, capacity > 0 without track_lines, max_num_sets > 0 without the four set arrays, more than 32768 images; and, after the count and BEFORE the
+ * records are allocated, for more candidate tracks than max_candidates (pp_last_error names both numbers; the handle stays usable).              */
+typedef struct pp_init_sets_options {
+  int32_t min_num_aligned_tracks;   /* 20 (sfm/incremental_mapper.cc:396) */
+  int32_t min_num_random_tracks;    /* 20 (:397) */
+  int32_t max_num_sets;             /* 10 (max_num_init_tries, :434) */
+  int32_t reserved_;
+  int64_t max_candidates;           /* 1 << 24: tracks before de-duplication, 16 bytes each and as much again for the sort */
+} pp_init_sets_options;
+void pp_init_sets_options_default(pp_init_sets_options* o);
+
+typedef struct pp_init_sets_report {
+  int64_t num_candidates;           /* tracks emitted before de-duplication */
+  int64_t num_aligned_tracks;       /* unique tracks of aligned lines, over all sets */
+  int64_t num_random_tracks;        /* unique tracks of unaligned lines */
+  int64_t num_track_entries;        /* tracks of the returned sets = track_start[2 * num_returned]: the capacity that holds them all */
+  int32_t num_aligned_sets;         /* distinct sets with an aligned track */
+  int32_t num_random_sets;          /* distinct sets with an unaligned track */
+  int32_t num_qualified;
+  int32_t num_returned;             /* min(num_qualified, max_num_sets) */
+  int32_t num_work_lines;           /* lines of the check images that keep at least three neighbours: the wavefronts of K15 */
+  int32_t overflow_lines;           /* of them: the filtered list is longer than the on-chip list (64) and went through global memory */
+  double device_ms, replay_ms, total_ms;
+} pp_init_sets_report;
+
+/* line_aligned: L bytes, FeatureLine::IsAligned per line.  image_subset: C bytes, NULL = all (the reference's aligned_db_cache: the images that own an
+ * aligned line).  check_images: handle image indices, each at most once, inside the subset (the reference draws up to ten).
+ * set_images (x4, ascending), set_num_aligned, set_num_random: max_num_sets entries each, best set first.  track_start: 2 * max_num_sets + 1 entries, a CSR
+ * over track_lines with two segments per set, the aligned tracks and then the unaligned ones, each in ascending lexicographic order of the four line numbers -
+ * the order in which the reference hands the lines to the solver (:459-481).  track_lines: x4 handle line numbers per track, in the order of set_images;
+ * tracks beyond `capacity` are not written (report->num_track_entries counts them all). */
+int pp_tracks_find_initial_sets(pp_tracks_handle h, const pp_init_sets_options* options, const uint8_t* line_aligned /* L */,
+                                const uint8_t* image_subset /* C or NULL */, const int32_t* check_images, int32_t num_check,
+                                pp_init_sets_report* report, int32_t* set_images /* x4 */, int32_t* set_num_aligned, int32_t* set_num_random,
+                                int64_t* track_start, int32_t* track_lines /* x4 */, int64_t capacity);
+
 /* ======================================================================================== *
  *  Four-view line initialisation (LO-MSAC)                                                   *
  *  replaces, for the out-of-plane-translation stage: ransac_lib::LocallyOptimizedMSAC<        *

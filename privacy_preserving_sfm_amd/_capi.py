@@ -164,6 +164,17 @@ class TracksFilterReport(C.Structure):
                 ("points_tested", C.c_int32), ("images_filtered", C.c_int32), ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class InitSetsOptions(C.Structure):
+    _fields_ = [("min_num_aligned_tracks", C.c_int32), ("min_num_random_tracks", C.c_int32), ("max_num_sets", C.c_int32), ("reserved_", C.c_int32),
+                ("max_candidates", C.c_int64)]
+
+
+class InitSetsReport(C.Structure):
+    _fields_ = [("num_candidates", C.c_int64), ("num_aligned_tracks", C.c_int64), ("num_random_tracks", C.c_int64), ("num_track_entries", C.c_int64),
+                ("num_aligned_sets", C.c_int32), ("num_random_sets", C.c_int32), ("num_qualified", C.c_int32), ("num_returned", C.c_int32),
+                ("num_work_lines", C.c_int32), ("overflow_lines", C.c_int32), ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -197,6 +208,7 @@ _EXPORTS = [
     "pp_local_bundle_options_default", "pp_tracks_find_local_bundle", "pp_tracks_update",
     "pp_next_image_options_default", "pp_tracks_find_next_images", "pp_tracks_estimate_image_pose", "pp_tracks_register_image",
     "pp_tracks_filter_points", "pp_tracks_filter_negative_depth", "pp_tracks_filter_images",
+    "pp_init_sets_options_default", "pp_tracks_find_initial_sets",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -309,6 +321,9 @@ def lib():
     L.pp_tracks_filter_points.argtypes = [C.c_void_p, C.POINTER(FilterOptions), c_u8p, c_u8p, c_u8p, C.POINTER(TracksFilterReport), c_ip, c_ip, C.c_int64, c_dp]
     L.pp_tracks_filter_negative_depth.argtypes = [C.c_void_p, c_ip, C.c_int32, C.POINTER(TracksFilterReport), c_ip, c_ip, C.c_int64]
     L.pp_tracks_filter_images.argtypes = [C.c_void_p, c_ip, C.c_int32, c_ip, C.POINTER(TracksFilterReport), c_ip, c_ip, C.c_int64]
+    L.pp_init_sets_options_default.argtypes = [C.POINTER(InitSetsOptions)]
+    L.pp_tracks_find_initial_sets.argtypes = [C.c_void_p, C.POINTER(InitSetsOptions), c_u8p, c_u8p, c_ip, C.c_int32, C.POINTER(InitSetsReport), c_ip, c_ip, c_ip,
+                                              C.POINTER(C.c_int64), c_ip, C.c_int64]
     L.pp_camera_image_to_world_threshold.argtypes = [C.c_int, c_dp, C.c_double, c_dp]
     _lib = L
     return L

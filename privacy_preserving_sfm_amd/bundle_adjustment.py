@@ -87,11 +87,18 @@ class Camera:
 
 
 class Image:
-    def __init__(self, image_id, camera_id, qvec, tvec, lines=()):
+    def __init__(self, image_id, camera_id, qvec, tvec, lines=(), gravity=None):
         self.image_id, self.camera_id = image_id, camera_id
         self.qvec = np.asarray(qvec, dtype=np.float64).copy()
         self.tvec = np.asarray(tvec, dtype=np.float64).copy()
         self.lines = list(lines)
+        self.gravity = None if gravity is None else np.asarray(gravity, dtype=np.float64).copy()      # base/image.h GravityDirection(), camera frame
+
+    def HasGravity(self):
+        return getattr(self, "gravity", None) is not None
+
+    def GravityDirection(self):
+        return self.gravity
 
     def CameraId(self):
         return self.camera_id
@@ -736,6 +743,10 @@ class IncrementalMapperOptions:
         self.max_extra_param = 1.0
         self.max_reg_trials = 3
         self.image_selection_method = 1      # 0 MAX_VISIBLE_POINTS_NUM, 1 MAX_VISIBLE_POINTS_RATIO
+        # the four initial images (sfm/incremental_mapper.h:52-59; IncrementalMapperOptions::Mapper() passes them on unchanged)
+        self.init_min_num_inliers = 20
+        self.init_max_error = 5.0            # pixels
+        self.init_min_tri_angle = 2.0        # degrees
 
     def LocalBundleAdjustment(self):
         """controllers/incremental_mapper.cc:196-219"""

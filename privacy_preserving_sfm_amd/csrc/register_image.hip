@@ -166,19 +166,6 @@ int CheckNextImageOptions(const pp_next_image_options* o, const char* where) {
   return PP_OK;
 }
 
-struct EventTimer {
-  pp_tracks_impl* h;
-  float ms = 0.f;
-  int Begin() { PP_HIP_TRY(hipEventRecord(h->ev0, h->stream)); return PP_OK; }
-  int End() { PP_HIP_TRY(hipEventRecord(h->ev1, h->stream)); return PP_OK; }
-  int Add() {      // after the stream has drained
-    float t = 0.f;
-    PP_HIP_TRY(hipEventElapsedTime(&t, h->ev0, h->ev1));
-    ms += t;
-    return PP_OK;
-  }
-};
-
 struct PoseHandleGuard {
   pp_pose_handle p = nullptr;
   ~PoseHandleGuard() { if (p) (void)pp_pose_destroy(p); }

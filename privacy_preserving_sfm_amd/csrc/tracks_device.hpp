@@ -183,6 +183,20 @@ struct CallBlocks {
   template <typename T> int Put(T** p, const T* src, size_t count) { return b.Put(p, src, count, s, 1); }
 };
 
+// HIP-event time of the spans between Begin() and End() on the handle's stream (K13, K15), summed
+struct EventTimer {
+  pp_tracks_impl* h;
+  float ms = 0.f;
+  int Begin() { PP_HIP_TRY(hipEventRecord(h->ev0, h->stream)); return PP_OK; }
+  int End() { PP_HIP_TRY(hipEventRecord(h->ev1, h->stream)); return PP_OK; }
+  int Add() {      // after the stream has drained
+    float t = 0.f;
+    PP_HIP_TRY(hipEventElapsedTime(&t, h->ev0, h->ev1));
+    ms += t;
+    return PP_OK;
+  }
+};
+
 // the C x 3 projection centres of the handle's projection matrices (tracks_image.hip): computed on first use, again after pp_tracks_update
 int ComputeCenters(pp_tracks_impl* h);
 inline int EnsureCenters(pp_tracks_impl* h) { return h->d_centers ? PP_OK : ComputeCenters(h); }

@@ -627,6 +627,16 @@ def next_image_options(**kw):
     return o
 
 
+def init_sets_options(**kw):
+    o = _capi.InitSetsOptions()
+    _capi.lib().pp_init_sets_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
 _TRACKS_FIELDS = (("poses", np.float64, dp), ("pose_camera", np.int32, None), ("camera_model", np.int32, None), ("intr", np.float64, dp),
                   ("cam_size", np.int32, None), ("camera_skip", np.uint8, None), ("image_registered", np.uint8, None), ("lines", np.float64, dp),
                   ("line_image", np.int32, None), ("line_point", np.int32, None), ("corr_start", np.int32, None), ("corr_line", np.int32, None),
@@ -781,6 +791,35 @@ class TracksProblem:
                                                    ptr(mask, _capi.c_u8p), C.byref(added), ptr(ep, _capi.c_ip), ptr(el, _capi.c_ip), n))
         m = int(added.value)
         return np.stack([ep[:m], el[:m]], axis=1)
+
+    def find_initial_sets(self, line_aligned, check_images, image_subset=None, options=None, capacity=None):
+        """The image sets of RegisterInitialLineImages worth a four-view solve, over the lines of the image indices `check_images`
+        -> (report, sets: best first, each dict(images [4], num_aligned, num_random, aligned [a, 4], random [r, 4]: handle line numbers per track in the
+        order of `images`, each list in ascending lexicographic order)).  line_aligned [L] flags; image_subset [C] flags or None = all.
+        capacity: tracks to make room for (None: a first guess, and a second call when the report asks for more; a given capacity is not grown -
+        the lists then hold what fitted).  The state does not change; a handle without points or registered images will do."""
+        o = options or init_sets_options()
+        al = np.ascontiguousarray(line_aligned, dtype=np.uint8).reshape(-1)
+        assert len(al) == self.num_lines
+        sub = None if image_subset is None else np.ascontiguousarray(image_subset, dtype=np.uint8).reshape(self.num_images)
+        chk = np.ascontiguousarray(check_images, dtype=np.int32).reshape(-1)
+        ns = int(o.max_num_sets)
+        cap = 1 << 14 if capacity is None else int(capacity)
+        while True:
+            si, sa, sr = np.zeros((max(ns, 1), 4), dtype=np.int32), np.zeros(max(ns, 1), dtype=np.int32), np.zeros(max(ns, 1), dtype=np.int32)
+            ts, tl = np.zeros(2 * max(ns, 1) + 1, dtype=np.int64), np.zeros((max(cap, 1), 4), dtype=np.int32)
+            rep = _capi.InitSetsReport()
+            check(_capi.lib().pp_tracks_find_initial_sets(self._h, C.byref(o), ptr(al, _capi.c_u8p), ptr(sub, _capi.c_u8p), ptr(chk, _capi.c_ip) if len(chk) else None,
+                                                          len(chk), C.byref(rep), ptr(si, _capi.c_ip), ptr(sa, _capi.c_ip), ptr(sr, _capi.c_ip),
+                                                          ts.ctypes.data_as(C.POINTER(C.c_int64)), ptr(tl, _capi.c_ip), cap))
+            if capacity is not None or rep.num_track_entries <= cap:
+                break
+            cap = int(rep.num_track_entries)
+        sets = []
+        for k in range(int(rep.num_returned)):
+            a0, a1, r1 = (min(int(x), cap) for x in ts[2 * k: 2 * k + 3])
+            sets.append(dict(images=si[k].copy(), num_aligned=int(sa[k]), num_random=int(sr[k]), aligned=tl[a0:a1].copy(), random=tl[a1:r1].copy()))
+        return rep, sets
 
     def _filter_call(self, fn, args, trailing=()):
         cap = self.num_lines + self.num_points()[0]      # a line loses its point once, a point is deleted once

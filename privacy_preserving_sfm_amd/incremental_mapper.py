@@ -1,15 +1,21 @@
-"""Host mirror of the two steps of the reference's incremental mapper that pick and register an image (sfm/incremental_mapper.{h,cc}:
-`FindNextImages` :139-190, `RegisterNextImage` :570-760) on top of pp_tracks_find_next_images / pp_tracks_estimate_image_pose /
-pp_tracks_register_image (include/ppsfm_hip.h), with the state the reference keeps between them: `num_reg_trials_`, `filtered_images_`,
-`num_reg_images_per_camera_`.
+"""Host mirror of the steps of the reference's incremental mapper that pick and register images (sfm/incremental_mapper.{h,cc}:
+`RegisterInitialLineImages` :192-568, `FindNextImages` :139-190, `RegisterNextImage` :570-760) on top of pp_tracks_find_initial_sets /
+pp_tracks_find_next_images / pp_tracks_estimate_image_pose / pp_tracks_register_image (include/ppsfm_hip.h), with the state the reference keeps between
+them: `num_reg_trials_`, `filtered_images_`, `num_reg_images_per_camera_`.
+
+`RegisterInitialLineImages` takes a reconstruction from ZERO registered images to four: the image sets worth trying come from the device
+(pp_tracks_find_initial_sets), each is handed to `initializer.initialize_reconstruction` (LO-MSAC on the device), the best one is committed on the same
+handle and triangulated.  The images that own a gravity-aligned line need `Image.gravity`.  Pinned where the reference is unspecified: sets of equal
+aligned count in ascending image set, the four images registered in ascending id, the check images drawn from `random_seed` (the reference seeds from the
+wall clock).  Its console histograms (:365-383) are not mirrored.
 
 An unregistered image is an `Image` of `Reconstruction.images` with `registered = False` (an image without the attribute is registered).
 With `IncrementalTriangulator.TriangulateImage`, `bundle_adjustment.IterativeLocalRefinement` and `IterativeGlobalRefinement` this is the
 reference's per-image sequence (controllers/incremental_mapper.cc:420-520).  Images of equal rank are tried in ascending id (the reference leaves it
 to a hash table).  `FilterPoints` (:965-970) and `FilterImages` (:941-963, with `DeRegisterImageEvent` :1177-1192) run on the tracks handle
 (pp_tracks_filter_points / pp_tracks_filter_images) and fill `filtered_images_`.  Inside `with triangulator.Session(options):` every step here and in
-bundle_adjustment's refinement loops shares ONE handle.  `RegisterInitialLineImages` and the focal-length estimation (never enabled on the reference's
-line path) are not mirrored."""
+bundle_adjustment's refinement loops shares ONE handle, from the first image to the last.  The focal-length estimation (never enabled on the reference's
+line path) is not mirrored."""
 import copy
 import ctypes as C
 
@@ -17,8 +23,11 @@ import numpy as np
 
 from . import _capi
 from .bundle_adjustment import IncrementalMapperOptions
-from .device import next_image_options, ransac_options
-from .estimators import AbsolutePoseRefinementOptions, RefineAbsolutePoseFromLines
+from .device import init_sets_options, next_image_options, ransac_options
+from .estimators import AbsolutePoseRefinementOptions, RefineAbsolutePoseFromLines, RotationMatrixToQuaternion
+from .initializer import InitOptions, initialize_reconstruction
+
+kMaxNumCheckImages = 10      # sfm/incremental_mapper.cc:303
 
 
 def ImageToWorldThreshold(camera, threshold_px):
@@ -49,6 +58,7 @@ class IncrementalMapper:
         self.ransac_seed = 0              # util/random.h:46 kDefaultPRNGSeed
         self.last_report = None           # the pp_image_pose_report of the last RegisterNextImage
         self.last_refinement = None       # its refinement's solver summary
+        self.last_init = None             # what the last RegisterInitialLineImages saw: dict(report, check_image_ids, sets, chosen)
 
     def _tri_options(self, options):
         o = copy.copy(getattr(options, "triangulation", None) or self.triangulator_.Options())
@@ -99,6 +109,81 @@ class IncrementalMapper:
             self.num_reg_images_per_camera_[cid] -= 1
             self.filtered_images_.add(image_id)
         return len(image_ids)
+
+    def AlignedImageIds(self):
+        """the images that own at least one gravity-aligned line, ascending: the reference's aligned_db_cache (controllers/incremental_mapper.cc:400-418)"""
+        rec = self.reconstruction_
+        return [i for i in sorted(rec.images) if any(l.IsAligned() for l in rec.images[i].lines)]
+
+    @staticmethod
+    def ChooseCheckImages(image_ids, random_seed=0):
+        """:295-309 - up to ten distinct images of the sorted ids.  With at most ten the reference's draw-until-ten-distinct loop yields all of them;
+        beyond that it draws from a generator seeded with the wall clock: PINNED here to numpy.random.RandomState(random_seed), returned ascending."""
+        image_ids = sorted(image_ids)
+        if len(image_ids) <= kMaxNumCheckImages:
+            return image_ids
+        rng = np.random.RandomState(random_seed)
+        return sorted(int(i) for i in rng.choice(np.array(image_ids), kMaxNumCheckImages, replace=False))
+
+    def RegisterInitialLineImages(self, options=None, check_image_ids=None, random_seed=0):
+        """IncrementalMapper::RegisterInitialLineImages (:192-568) -> True when four images were registered and triangulated.  False (no qualified image
+        set, no set gave poses, or fewer than init_min_num_inliers inliers) leaves the reconstruction as it was.  `self.last_init` keeps the device report,
+        the check images, per tried set its images, counts, success and inlier ratio, and the chosen set."""
+        options = options or IncrementalMapperOptions()
+        rec = self.reconstruction_
+        assert len(rec.RegImageIds()) == 0, "CHECK_EQ(reconstruction_->NumRegImages(), 0)"
+        assert options.init_min_num_inliers > 0 and options.init_max_error > 0 and options.init_min_tri_angle >= 0      # Options::Check (:78-80)
+        subset = self.AlignedImageIds()
+        missing = [i for i in subset if not rec.images[i].HasGravity()]
+        if missing:
+            raise ValueError("RegisterInitialLineImages needs the gravity direction of every image with an aligned line; missing for image ids %s" % missing)
+        check_ids = self.ChooseCheckImages(subset, random_seed) if check_image_ids is None else list(check_image_ids)
+        self.last_init = dict(report=None, check_image_ids=list(check_ids), sets=[], chosen=None)
+        if not check_ids:
+            return False
+        tri_options = self.triangulator_.Options()      # (:555: DEFAULT triangulator options, whatever the caller's are - the reference's quirk)
+        live = self.triangulator_._live      # (the camera thresholds a handle bakes in: the active session's, else the caller's; the defaults are equal)
+        baked = live.baked_options if live is not None else options
+        tri_options.min_focal_length_ratio, tri_options.max_focal_length_ratio, tri_options.max_extra_param = \
+            baked.min_focal_length_ratio, baked.max_focal_length_ratio, baked.max_extra_param
+        ses = self.triangulator_._open(tri_options)
+        try:
+            rep, sets = ses.find_initial_sets(init_sets_options(), check_ids, subset)
+            self.last_init["report"] = rep
+            best, best_inlier_ratio, best_inliers = None, 0.0, 0
+            for s in sets:      # (:436-531)
+                ids = s["image_ids"]
+                tracks = s["aligned"] + s["random"]      # (:459-481: the aligned tracks first)
+                lines = [np.array([rec.images[i].lines[idx].Line() for (i, idx) in (t[v] for t in tracks)]).reshape(-1, 3) for v in range(4)]
+                aligned = [np.arange(len(tracks)) < len(s["aligned"])] * 4
+                gravity = [rec.images[i].GravityDirection() for i in ids]
+                init_options = InitOptions()
+                init_options.min_num_inliers, init_options.min_tri_angle = options.init_min_num_inliers, options.init_min_tri_angle
+                init_options.max_error = min(ImageToWorldThreshold(rec.Camera(rec.images[i].CameraId()), options.init_max_error) for i in ids)      # (:488-497)
+                ok, poses, inlier_ratio = initialize_reconstruction(lines, aligned, gravity, init_options, device=self.device_, random_seed=random_seed)
+                ok = bool(ok and poses is not None and len(poses) > 0)
+                self.last_init["sets"].append(dict(image_ids=list(ids), num_aligned=s["num_aligned"], num_random=s["num_random"], success=ok,
+                                                   inlier_ratio=float(inlier_ratio)))
+                if ok and inlier_ratio > best_inlier_ratio:      # (:506, strictly greater)
+                    best, best_inlier_ratio = (ids, np.array(poses)), inlier_ratio
+                    best_inliers = int(inlier_ratio * len(lines[0]))
+            if best is None or best_inliers < options.init_min_num_inliers:      # (:533-541)
+                return False
+            self.last_init["chosen"] = list(best[0])
+            for image_id, pose in sorted(zip(*best), key=lambda x: x[0]):      # (:543-552; PINNED: ascending image id, the reference walks an unordered_map)
+                image = rec.images[image_id]
+                ses.register_image(image_id, RotationMatrixToQuaternion(pose[:, :3]), pose[:, 3], np.zeros((0, 2), dtype=np.int32), None)
+                image.reg_index = self._next_reg_index
+                self._next_reg_index += 1
+                self.num_reg_images_per_camera_[image.CameraId()] = self.num_reg_images_per_camera_.get(image.CameraId(), 0) + 1      # RegisterImageEvent
+            for image_id in rec.RegImageIds():      # (:557-559)
+                ses.triangulate_image(image_id)
+            if rec.points3D:      # (:562-563; CompleteAllTracks / MergeAllTracks of an empty model do nothing)
+                ses.complete(None)
+                ses.merge(None)
+        finally:
+            ses.close()
+        return True
 
     def RegisterNextImage(self, options, image_id):
         """-> True when the image was registered: its pose estimated (P6L RANSAC on the device over the 2D-3D correspondences found on the device),

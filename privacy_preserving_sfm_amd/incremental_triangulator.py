@@ -365,6 +365,20 @@ class _TracksSession:
         self.t.last_reports.append(rep)
         return rep, [self.image_ids[int(c)] for c in ranked]
 
+    def find_initial_sets(self, options, check_image_ids, subset_image_ids=None):
+        """The image-set search of RegisterInitialLineImages on the handle -> (report, sets: best first, each dict(image_ids [4] ascending, num_aligned,
+        num_random, aligned, random: per track its four (image_id, line_idx) in the order of image_ids)).  options: a device.init_sets_options;
+        subset_image_ids: the reference's aligned_db_cache (None: every image).  Nothing changes."""
+        index = {i: c for c, i in enumerate(self.image_ids)}
+        subset = None if subset_image_ids is None else np.array([i in set(subset_image_ids) for i in self.image_ids], dtype=np.uint8)
+        rep, found = self.pb.find_initial_sets(self.flat["line_aligned"], [index[i] for i in check_image_ids], subset, options)
+        self.t.last_reports.append(rep)
+        sets = []
+        for s in found:
+            tracks = {name: [[self.line_ref[int(l)] for l in track] for track in s[name]] for name in ("aligned", "random")}
+            sets.append(dict(image_ids=[self.image_ids[int(c)] for c in s["images"]], num_aligned=s["num_aligned"], num_random=s["num_random"], **tracks))
+        return rep, sets
+
     def estimate_image_pose(self, image_id, options, ransac):
         """RegisterNextImage up to the pose refinement -> (report, pose [7], corrs [n, 2] (handle line, handle point), inlier_mask [n],
         lines2D [n, 3], points3D [n, 3]: the arrays RefineAbsolutePoseFromLines takes).  The reconstruction does not change."""
