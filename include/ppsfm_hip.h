@@ -871,6 +871,58 @@ int pp_tracks_find_initial_sets(pp_tracks_handle h, const pp_init_sets_options* 
                                 pp_init_sets_report* report, int32_t* set_images /* x4 */, int32_t* set_num_aligned, int32_t* set_num_random,
                                 int64_t* track_start, int32_t* track_lines /* x4 */, int64_t capacity);
 
+/* ---- BundleAdjuster::SetUp on a pp_tracks_handle (kernels K16 k_bundle_lines, k_bundle_tracks<count / fill>, k_bundle_first, k_bundle_gather) ------
+ * replaces the flattening of the model in front of every bundle adjustment, BundleAdjuster::SetUp (optim/bundle_adjustment.cc:326-542: AddImageToProblem
+ * :348-435, AddPointToProblem :437-488, ParameterizeCameras :490-528, ParameterizePoints :530-542): which observations, poses, points and cameras a
+ * BundleAdjustmentConfig puts into the problem, in which order, and which of them are constant.  The arrays are those of pp_ba_problem_desc.
+ * THE STREAM of observations: pass A - the lines l in ascending handle line number with image_flags[line_image[l]] & PP_BUNDLE_IMAGE and a point (the
+ * images of the config in ascending index, their lines in line order); pass B - the points of variable_points, then those of constant_points, in the
+ * order given: a point listed before is skipped, so is one whose observations of pass A already equal its track length; of every other one the track
+ * elements, in track order, whose image is NOT in the config.  A pose / point / camera gets the next index when the stream (for cameras: the pose list)
+ * first names it; a config image without an observation gets no pose.  The poses of pass A come first: num_config_poses of them.
+ * CONSTANT: a pose of pass B, or of an image flagged PP_BUNDLE_CONST_POSE; a point whose track is longer than its observations in the problem, or that
+ * constant_points lists (wherever else it is listed); a camera - mask 0xFFFF - when camera_subset_mask is NULL, when camera_const flags it, or when no
+ * config image WITH an observation uses it; a variable camera gets its camera_subset_mask entry as given.  pose_tvec_mask is the caller's for a variable
+ * pose of the config, else 0.
+ * The device flags, counts and scans the lines, walks the listed tracks (one wavefront per point), ranks points and images by first appearance and gathers
+ * the line coefficients (from the L x 3 the handle keeps on the device) and the positions; the host validates, de-duplicates the point lists and does
+ * what is image- or camera-sized (csrc/bundle_setup_replay.hpp).  Integer atomics whose result is order-free only: the output does not depend on the
+ * schedule.
+ * bad_line: the reference CHECKs the direction of every line of pass A (CHECK_NEAR(line.head<2>().norm(), 1.0, 1e-6), :373).  pp_tracks_create already
+ * REFUSES a line that fails this test (with sqrt(a^2 + b^2) for the norm), so no handle holds one: the device runs the test with hypot(a, b) all the same,
+ * and bad_line can differ from -1 only for a norm within one rounding of the bound.  A line it names is reported, not an error of the call: the arrays
+ * are filled all the same.
+ * The call never changes the handle.  num_obs == 0 is a valid result.
+ * CAPACITIES: the current number of track elements always suffices for obs_capacity, the current number of points for point_capacity
+ * (pp_tracks_get_state); a smaller one is compared with the exact need, counted on the host.
+ * ERRORS: PP_ERR_INVALID before any device work, with the outputs untouched: a null argument (tvec_const_mask, camera_const, camera_subset_mask may be
+ * NULL; a point list only with a count of 0), a listed point that is out of range, deleted or has an empty track, an image of the config that is not
+ * registered, a capacity that is too small. */
+enum { PP_BUNDLE_IMAGE = 1, PP_BUNDLE_CONST_POSE = 2 };
+typedef struct pp_bundle_config {
+  const uint8_t*  image_flags;        /* C: PP_BUNDLE_IMAGE = in the config; PP_BUNDLE_CONST_POSE = !refine_extrinsics || HasConstantPose */
+  const uint8_t*  tvec_const_mask;    /* C, NULL = none: bits as pp_ba_problem_desc (ignored for a constant pose) */
+  const uint8_t*  camera_const;       /* K, NULL = none: BundleAdjustmentConfig::SetConstantCamera */
+  const uint16_t* camera_subset_mask; /* K: constant-parameter bits a VARIABLE camera gets (from the refine_* flags);
+                                         NULL = no refine flag set, every camera constant */
+  const int32_t*  variable_points;    /* handle point indices IN THE ORDER VISITED (the mirror passes them sorted by id) */
+  const int32_t*  constant_points;
+  int32_t num_variable_points, num_constant_points;
+} pp_bundle_config;
+
+typedef struct pp_bundle_setup_report {
+  int64_t num_obs, num_config_obs;    /* M; those of pass A */
+  int32_t num_poses, num_config_poses, num_points, num_cameras;
+  int64_t bad_line;                   /* first config line (ascending) with | |(a,b)| - 1 | > 1e-6 (CHECK_NEAR, .cc:373); -1 none */
+  double device_ms, replay_ms, total_ms;
+} pp_bundle_setup_report;
+
+int pp_tracks_bundle_setup(pp_tracks_handle h, const pp_bundle_config* cfg, pp_bundle_setup_report* report,
+    double* lines /* M x 3 */, int32_t* obs_pose, int32_t* obs_point, int32_t* obs_line /* handle line of each observation */, int64_t obs_capacity,
+    int32_t* pose_image /* handle image of each pose */, uint8_t* pose_const, uint8_t* pose_tvec_mask, int32_t* pose_camera, /* C entries each */
+    int32_t* point_index /* handle point of each problem point */, uint8_t* point_const, double* points /* x 3 */, int32_t point_capacity,
+    int32_t* camera_index /* handle camera of each problem camera, K entries */, uint16_t* camera_const_mask /* K */);
+
 /* ======================================================================================== *
  *  Four-view line initialisation (LO-MSAC)                                                   *
  *  replaces, for the out-of-plane-translation stage: ransac_lib::LocallyOptimizedMSAC<        *

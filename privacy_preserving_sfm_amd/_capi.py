@@ -175,6 +175,20 @@ class InitSetsReport(C.Structure):
                 ("num_work_lines", C.c_int32), ("overflow_lines", C.c_int32), ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class BundleConfig(C.Structure):
+    _fields_ = [("image_flags", c_u8p), ("tvec_const_mask", c_u8p), ("camera_const", c_u8p), ("camera_subset_mask", c_u16p),
+                ("variable_points", c_ip), ("constant_points", c_ip), ("num_variable_points", C.c_int32), ("num_constant_points", C.c_int32)]
+
+
+class BundleSetupReport(C.Structure):
+    _fields_ = [("num_obs", C.c_int64), ("num_config_obs", C.c_int64), ("num_poses", C.c_int32), ("num_config_poses", C.c_int32),
+                ("num_points", C.c_int32), ("num_cameras", C.c_int32), ("bad_line", C.c_int64),
+                ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+PP_BUNDLE_IMAGE, PP_BUNDLE_CONST_POSE = 1, 2
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -208,7 +222,7 @@ _EXPORTS = [
     "pp_local_bundle_options_default", "pp_tracks_find_local_bundle", "pp_tracks_update",
     "pp_next_image_options_default", "pp_tracks_find_next_images", "pp_tracks_estimate_image_pose", "pp_tracks_register_image",
     "pp_tracks_filter_points", "pp_tracks_filter_negative_depth", "pp_tracks_filter_images",
-    "pp_init_sets_options_default", "pp_tracks_find_initial_sets",
+    "pp_init_sets_options_default", "pp_tracks_find_initial_sets", "pp_tracks_bundle_setup",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -324,6 +338,8 @@ def lib():
     L.pp_init_sets_options_default.argtypes = [C.POINTER(InitSetsOptions)]
     L.pp_tracks_find_initial_sets.argtypes = [C.c_void_p, C.POINTER(InitSetsOptions), c_u8p, c_u8p, c_ip, C.c_int32, C.POINTER(InitSetsReport), c_ip, c_ip, c_ip,
                                               C.POINTER(C.c_int64), c_ip, C.c_int64]
+    L.pp_tracks_bundle_setup.argtypes = [C.c_void_p, C.POINTER(BundleConfig), C.POINTER(BundleSetupReport), c_dp, c_ip, c_ip, c_ip, C.c_int64,
+                                         c_ip, c_u8p, c_u8p, c_ip, c_ip, c_u8p, c_dp, C.c_int32, c_ip, c_u16p]
     L.pp_camera_image_to_world_threshold.argtypes = [C.c_int, c_dp, C.c_double, c_dp]
     _lib = L
     return L

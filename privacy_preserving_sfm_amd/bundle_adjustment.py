@@ -621,11 +621,49 @@ class BundleAdjuster:
                      loss_type=int(opt.loss_function_type), loss_scale=float(opt.loss_function_scale))
         return scene, pose_index, point_index, cam_index
 
-    def Solve(self, reconstruction):
+    def flatten_on(self, session):
+        """`flatten(session.rec)` from an open tracks session (incremental_triangulator._TracksSession) instead of a loop over the model: SetUp on the
+        handle (pp_tracks_bundle_setup) gives the observations, the index arrays, the constant flags and the positions; the poses and the intrinsics
+        come from the reconstruction (O(poses + cameras)).  The same (scene, pose_index, point_index, cam_index), array for array and in the same
+        order, or None.  The handle must hold the reconstruction's current positions (`session.update()` after whatever changed them)."""
+        opt, cfg = self.options_, self.config_
+        reconstruction = session.rec
+        for iid in sorted(cfg.Images()):
+            reconstruction.Image(iid).NormalizeQvec()
+        rep, out, pose_ids, point_ids, cam_ids = session.bundle_setup(cfg, opt)
+        if rep.bad_line >= 0:
+            raise ValueError("CHECK_NEAR(line.head<2>().norm(), 1.0, 1e-6) failed")   # :373
+        if rep.num_obs == 0:
+            return None
+        pose_index = {iid: k for k, iid in enumerate(pose_ids)}
+        point_index = {pid: k for k, pid in enumerate(point_ids)}
+        cam_index = {cid: k for k, cid in enumerate(cam_ids)}
+        C, K = len(pose_ids), len(cam_ids)
+        poses = np.zeros((C, 7))
+        for k, iid in enumerate(pose_ids):
+            image = reconstruction.Image(iid)
+            poses[k, :4], poses[k, 4:] = image.qvec, image.tvec
+        intr = np.zeros((K, _capi.CAM_STRIDE)); camera_model = np.zeros(K, dtype=np.int32)
+        for k, cid in enumerate(cam_ids):
+            cam = reconstruction.Camera(cid)
+            intr[k, : cam.NumParams()] = cam.params
+            camera_model[k] = cam.ModelId()
+        scene = dict(lines=out["lines"], obs_pose=out["obs_pose"], obs_point=out["obs_point"], pose_camera=out["pose_camera"], camera_model=camera_model,
+                     poses=poses, points=out["points"], intr=intr, pose_const=out["pose_const"], tvec_const_mask=out["pose_tvec_mask"],
+                     point_const=out["point_const"], camera_const_mask=out["camera_const_mask"],
+                     loss_type=int(opt.loss_function_type), loss_scale=float(opt.loss_function_scale))
+        return scene, pose_index, point_index, cam_index
+
+    def Solve(self, reconstruction, session=None):
+        """`session`: an open tracks session over this reconstruction whose handle is up to date; without one, the live session of an active
+        `with triangulator.Session(...)` is used when there is one.  Either way the problem comes from `flatten_on`; else from `flatten`."""
         assert reconstruction is not None
         assert not self._used, "Cannot use the same BundleAdjuster multiple times"
         self._used = True
-        flat = self.flatten(reconstruction)
+        if session is None:
+            session = _live_session(reconstruction)
+        assert session is None or session.rec is reconstruction
+        flat = self.flatten(reconstruction) if session is None else self.flatten_on(session)
         if flat is None:            # problem_->NumResiduals() == 0
             return False
         scene, pose_index, point_index, cam_index = flat
@@ -833,7 +871,7 @@ def AdjustGlobalBundle(reconstruction, ba_options, device=0, summary_out=None, t
     else:
         reconstruction.FilterObservationsWithNegativeDepth(device=device)
     bundle_adjuster = BundleAdjuster(ba_options, GlobalBundleAdjustmentConfig(reconstruction), device=device)
-    ok = bundle_adjuster.Solve(reconstruction)
+    ok = bundle_adjuster.Solve(reconstruction, session=live)      # (inside a session: set up on its handle, which the filter above left current)
     if summary_out is not None:
         summary_out.append(bundle_adjuster.Summary())
     if ok:
@@ -997,7 +1035,7 @@ def AdjustLocalBundle(reconstruction, triangulator, options, ba_options, tri_opt
                                                            num_reg_images_per_camera)
             report.variable_point3D_ids = sorted(variable)
             bundle_adjuster = BundleAdjuster(ba_options, config, device=device)
-            bundle_adjuster.Solve(reconstruction)
+            bundle_adjuster.Solve(reconstruction, session=ses)      # (the problem is set up on the handle FindLocalBundle just ran on)
             report.summary = bundle_adjuster.Summary()
             report.num_adjusted_observations = (report.summary.num_residuals if report.summary is not None else 0) // 2
             ses.update()

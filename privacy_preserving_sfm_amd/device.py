@@ -821,6 +821,42 @@ class TracksProblem:
             sets.append(dict(images=si[k].copy(), num_aligned=int(sa[k]), num_random=int(sr[k]), aligned=tl[a0:a1].copy(), random=tl[a1:r1].copy()))
         return rep, sets
 
+    def bundle_setup(self, image_flags, tvec_const_mask=None, camera_const=None, camera_subset_mask=None, variable_points=(), constant_points=(),
+                     obs_capacity=None, point_capacity=None):
+        """BundleAdjuster::SetUp on the handle (pp_tracks_bundle_setup) -> (report, dict(lines [M, 3], obs_pose [M], obs_point [M], obs_line [M],
+        pose_image [C'], pose_const, pose_tvec_mask, pose_camera, point_index [P''], point_const, points [P'', 3], camera_index [K'],
+        camera_const_mask)): the arrays of a pp_ba_problem_desc and, per pose / point / camera of the problem, its handle index.
+        image_flags [C]: _capi.PP_BUNDLE_IMAGE | PP_BUNDLE_CONST_POSE; tvec_const_mask [C], camera_const [K], camera_subset_mask [K] or None;
+        the point lists in the order they are to be visited.  The state does not change."""
+        Cn, Kn = self.num_images, self.num_cameras
+        fl = np.ascontiguousarray(image_flags, dtype=np.uint8).reshape(Cn)
+        tm = None if tvec_const_mask is None else np.ascontiguousarray(tvec_const_mask, dtype=np.uint8).reshape(Cn)
+        cc = None if camera_const is None else np.ascontiguousarray(camera_const, dtype=np.uint8).reshape(Kn)
+        cs = None if camera_subset_mask is None else np.ascontiguousarray(camera_subset_mask, dtype=np.uint16).reshape(Kn)
+        vp = np.ascontiguousarray(variable_points, dtype=np.int32).reshape(-1); cp = np.ascontiguousarray(constant_points, dtype=np.int32).reshape(-1)
+        if obs_capacity is None or point_capacity is None:
+            P, T = self.num_points()
+            obs_capacity = T if obs_capacity is None else obs_capacity
+            point_capacity = P if point_capacity is None else point_capacity
+        M, Pn = max(int(obs_capacity), 1), max(int(point_capacity), 1)
+        cfg = _capi.BundleConfig(ptr(fl, _capi.c_u8p), ptr(tm, _capi.c_u8p), ptr(cc, _capi.c_u8p), ptr(cs, _capi.c_u16p), ptr(vp, _capi.c_ip) if len(vp) else None,
+                                 ptr(cp, _capi.c_ip) if len(cp) else None, len(vp), len(cp))
+        lines, obs_pose, obs_point, obs_line = np.zeros((M, 3)), np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32)
+        pose_image, pose_const, pose_tvec = np.zeros(max(Cn, 1), dtype=np.int32), np.zeros(max(Cn, 1), dtype=np.uint8), np.zeros(max(Cn, 1), dtype=np.uint8)
+        pose_camera = np.zeros(max(Cn, 1), dtype=np.int32)
+        point_index, point_const, points = np.zeros(Pn, dtype=np.int32), np.zeros(Pn, dtype=np.uint8), np.zeros((Pn, 3))
+        camera_index, camera_mask = np.zeros(max(Kn, 1), dtype=np.int32), np.zeros(max(Kn, 1), dtype=np.uint16)
+        rep = _capi.BundleSetupReport()
+        ip = _capi.c_ip
+        check(_capi.lib().pp_tracks_bundle_setup(self._h, C.byref(cfg), C.byref(rep), dp(lines), ptr(obs_pose, ip), ptr(obs_point, ip), ptr(obs_line, ip),
+                                                 int(obs_capacity), ptr(pose_image, ip), ptr(pose_const, _capi.c_u8p), ptr(pose_tvec, _capi.c_u8p),
+                                                 ptr(pose_camera, ip), ptr(point_index, ip), ptr(point_const, _capi.c_u8p), dp(points), int(point_capacity),
+                                                 ptr(camera_index, ip), ptr(camera_mask, _capi.c_u16p)))
+        m, c, p, k = int(rep.num_obs), int(rep.num_poses), int(rep.num_points), int(rep.num_cameras)
+        return rep, dict(lines=lines[:m], obs_pose=obs_pose[:m], obs_point=obs_point[:m], obs_line=obs_line[:m], pose_image=pose_image[:c],
+                         pose_const=pose_const[:c], pose_tvec_mask=pose_tvec[:c], pose_camera=pose_camera[:c], point_index=point_index[:p],
+                         point_const=point_const[:p], points=points[:p], camera_index=camera_index[:k], camera_const_mask=camera_mask[:k])
+
     def _filter_call(self, fn, args, trailing=()):
         cap = self.num_lines + self.num_points()[0]      # a line loses its point once, a point is deleted once
         ep, el = np.zeros(max(cap, 1), dtype=np.int32), np.zeros(max(cap, 1), dtype=np.int32)

@@ -379,6 +379,45 @@ class _TracksSession:
             sets.append(dict(image_ids=[self.image_ids[int(c)] for c in s["images"]], num_aligned=s["num_aligned"], num_random=s["num_random"], **tracks))
         return rep, sets
 
+    def _point_indices(self):
+        """{point id: handle index}; `ids` only grows, so the map is extended by what was appended since the last call"""
+        index = self.__dict__.setdefault("_index_of_point", {})
+        done = self.__dict__.get("_index_of_point_len", 0)
+        for k in range(done, len(self.ids)):
+            index[self.ids[k]] = k
+        self._index_of_point_len = len(self.ids)
+        return index
+
+    def bundle_setup(self, config, options):
+        """BundleAdjuster::SetUp on the handle (pp_tracks_bundle_setup) for a BundleAdjustmentConfig and BundleAdjustmentOptions
+        -> (report, arrays as TracksProblem.bundle_setup's, pose image ids, point ids, camera ids - each in problem order).  The point lists go sorted
+        by point id, as BundleAdjuster.flatten visits them.  The handle must hold the reconstruction's current positions (`update()`)."""
+        rec = self.rec
+        image_index = {i: c for c, i in enumerate(self.image_ids)}
+        flags, tmask = np.zeros(len(self.image_ids), dtype=np.uint8), np.zeros(len(self.image_ids), dtype=np.uint8)
+        for iid in config.Images():
+            c = image_index[iid]
+            flags[c] = _capi.PP_BUNDLE_IMAGE | (_capi.PP_BUNDLE_CONST_POSE if (not options.refine_extrinsics) or config.HasConstantPose(iid) else 0)
+            if config.HasConstantTvec(iid):
+                tmask[c] = sum(1 << i for i in config.ConstantTvec(iid))
+        camera_const = np.array([config.IsConstantCamera(cid) for cid in self.cam_ids], dtype=np.uint8)
+        subset = None
+        if options.refine_focal_length or options.refine_principal_point or options.refine_extra_params:
+            subset = np.zeros(len(self.cam_ids), dtype=np.uint16)
+            for k, cid in enumerate(self.cam_ids):
+                cam = rec.cameras[cid]
+                idxs = ([] if options.refine_focal_length else list(cam.FocalLengthIdxs())) + \
+                       ([] if options.refine_principal_point else list(cam.PrincipalPointIdxs())) + \
+                       ([] if options.refine_extra_params else list(cam.ExtraParamsIdxs()))
+                subset[k] = sum(1 << i for i in idxs)
+        point_index = self._point_indices()
+        variable = [point_index[p] for p in sorted(config.VariablePoints())]
+        constant = [point_index[p] for p in sorted(config.ConstantPoints())]
+        rep, out = self.pb.bundle_setup(flags, tmask, camera_const, subset, variable, constant)
+        self.last_bundle_setup_report = rep      # (kept apart from the triangulator's last_reports, whose sequence per driver call is fixed)
+        return (rep, out, [self.image_ids[int(c)] for c in out["pose_image"]], [self.ids[int(p)] for p in out["point_index"]],
+                [self.cam_ids[int(k)] for k in out["camera_index"]])
+
     def estimate_image_pose(self, image_id, options, ransac):
         """RegisterNextImage up to the pose refinement -> (report, pose [7], corrs [n, 2] (handle line, handle point), inlier_mask [n],
         lines2D [n, 3], points3D [n, 3]: the arrays RefineAbsolutePoseFromLines takes).  The reconstruction does not change."""
