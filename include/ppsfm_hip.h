@@ -1040,6 +1040,54 @@ int pp_fourview2d_least_squares(pp_fourview2d_handle h, int32_t sample_size, con
 int pp_fourview2d_lomsac(pp_fourview2d_handle h, const pp_lomsac_options* options, const double* frames, pp_lomsac_report* report,
                          double* cams_out, double* X_out, int32_t* inlier_indices);
 
+/* ======================================================================================== *
+ *  SIFT descriptor matching (K17)                                                           *
+ *  replaces: MatchSiftFeaturesCPUBruteForce (feature/sift.cc:54-143, 170-203, 957-970), the  *
+ *  exact rule behind SiftCPUFeatureMatcher / SiftGPUFeatureMatcher (feature/matching.cc)     *
+ * ======================================================================================== */
+
+/* SiftMatchingOptions (feature/sift.h:117-145), the fields the brute-force rule reads.  max_num_matches is not among them: it only truncates the
+ * inputs of the reference's SiftGPU path, MatchSiftFeaturesCPUBruteForce never reads it and neither does this library. */
+typedef struct pp_sift_match_options {
+  double max_ratio;        /* 0.8: a match is rejected when acos(best) >= max_ratio * acos(second), in float as the reference computes it */
+  double max_distance;     /* 0.7: a match is rejected when acos(best) > max_distance                                                    */
+  int32_t cross_check;     /* 1:   keep (i, j) only when j's best match is i                                                             */
+  int32_t min_num_matches; /* 15:  a pair with fewer matches gets an empty list (feature/matching.cc:196-198, 414-416)                   */
+  int64_t workspace_bytes; /* cap of the device workspace of one internal batch of pairs; 0 = the default (256 MiB).  A pair that needs
+                              more on its own still runs, alone.                                                                         */
+} pp_sift_match_options;
+void pp_sift_match_options_default(pp_sift_match_options* o);
+
+typedef struct pp_sift_match_report {
+  int64_t num_matches;       /* over all pairs                                  */
+  int32_t num_pairs_emptied; /* pairs with 1 .. min_num_matches - 1 matches     */
+  int32_t num_batches;       /* internal batches the pair list was processed in */
+  double device_ms, total_ms;
+} pp_sift_match_report;
+
+typedef struct pp_sift_impl* pp_sift_handle;
+/* The descriptors of num_images images, uploaded once: descriptors is total x 128 uint8 row-major (FeatureDescriptors), image k owns the rows
+ * desc_start[k] .. desc_start[k + 1] (desc_start has num_images + 1 entries, starts at 0 and does not decrease; an image with no descriptor is valid). */
+int pp_sift_create(int32_t num_images, const int64_t* desc_start, const uint8_t* descriptors, int device, pp_sift_handle* out);
+int pp_sift_destroy(pp_sift_handle h);
+/* MatchSiftFeaturesCPUBruteForce for every listed pair (pairs: num_pairs x 2 image indices), the same matches in the same order: the pairs of
+ * pair p are matches[2 * match_start[p] .. 2 * match_start[p + 1]) as (feature of the first image, feature of the second), ascending in the first.
+ * A pair (i, i) and a pair listed twice are matched like any other: dropping them is the caller's job, as in SiftFeatureMatcher::Match.
+ * capacity counts matches (pairs of int32): the sum over the pairs of min(N1, N2) always suffices with cross_check, the sum of N1 without it.  A smaller
+ * capacity is compared with the exact need after the device work; too small is PP_ERR_INVALID and match_start, matches and the report are untouched.
+ * Pairs are processed in internal batches whose workspace - 12 bytes per feature of both images of a pair for the top-2 results, 8 bytes per possible
+ * match for the batch's output - stays below options->workspace_bytes.  One pair occupies only part of the device (a workgroup per 128 features and
+ * direction): batches of pairs are the intended use. */
+int pp_sift_match_pairs(pp_sift_handle h, const pp_sift_match_options* options, int64_t num_pairs, const int32_t* pairs, pp_sift_match_report* report,
+                        int64_t* match_start, int32_t* matches, int64_t capacity);
+/* The one-way scan of image1's features against image2's (K17a alone), N1 entries each: best = the largest dist, best_j = the lowest index that attains
+ * it (-1: no positive dist), second = the second largest with multiplicity.  For tests and for a caller with another rule on top. */
+int pp_sift_top2(pp_sift_handle h, int32_t image1, int32_t image2, int32_t* best_j, int32_t* best, int32_t* second);
+/* The integers the device compares (host only, needs no device): the distance rule passes iff best >= d_min (and best >= 1), the ratio rule iff
+ * min(second, 262144) <= table[min(best, 262144) - d_min] (-1: never).  *count = 262144 - d_min + 1 entries; table may be NULL to ask for the count,
+ * else capacity >= *count.  PP_ERR_INTERNAL when this host's acosf is not monotonic (csrc/sift_match_replay.hpp). */
+int pp_sift_match_thresholds(const pp_sift_match_options* options, int32_t* d_min, int32_t* table, int64_t capacity, int64_t* count);
+
 #ifdef __cplusplus
 }
 #endif

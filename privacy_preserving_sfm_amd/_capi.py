@@ -189,6 +189,15 @@ class BundleSetupReport(C.Structure):
 PP_BUNDLE_IMAGE, PP_BUNDLE_CONST_POSE = 1, 2
 
 
+class SiftMatchOptions(C.Structure):
+    _fields_ = [("max_ratio", C.c_double), ("max_distance", C.c_double), ("cross_check", C.c_int32), ("min_num_matches", C.c_int32),
+                ("workspace_bytes", C.c_int64)]
+
+
+class SiftMatchReport(C.Structure):
+    _fields_ = [("num_matches", C.c_int64), ("num_pairs_emptied", C.c_int32), ("num_batches", C.c_int32), ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -223,6 +232,7 @@ _EXPORTS = [
     "pp_next_image_options_default", "pp_tracks_find_next_images", "pp_tracks_estimate_image_pose", "pp_tracks_register_image",
     "pp_tracks_filter_points", "pp_tracks_filter_negative_depth", "pp_tracks_filter_images",
     "pp_init_sets_options_default", "pp_tracks_find_initial_sets", "pp_tracks_bundle_setup",
+    "pp_sift_match_options_default", "pp_sift_create", "pp_sift_destroy", "pp_sift_match_pairs", "pp_sift_top2", "pp_sift_match_thresholds",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -340,6 +350,13 @@ def lib():
                                               C.POINTER(C.c_int64), c_ip, C.c_int64]
     L.pp_tracks_bundle_setup.argtypes = [C.c_void_p, C.POINTER(BundleConfig), C.POINTER(BundleSetupReport), c_dp, c_ip, c_ip, c_ip, C.c_int64,
                                          c_ip, c_u8p, c_u8p, c_ip, c_ip, c_u8p, c_dp, C.c_int32, c_ip, c_u16p]
+    L.pp_sift_match_options_default.argtypes = [C.POINTER(SiftMatchOptions)]
+    L.pp_sift_match_options_default.restype = None
+    L.pp_sift_create.argtypes = [C.c_int32, C.POINTER(C.c_int64), c_u8p, C.c_int, C.POINTER(C.c_void_p)]
+    L.pp_sift_destroy.argtypes = [C.c_void_p]
+    L.pp_sift_match_pairs.argtypes = [C.c_void_p, C.POINTER(SiftMatchOptions), C.c_int64, c_ip, C.POINTER(SiftMatchReport), C.POINTER(C.c_int64), c_ip, C.c_int64]
+    L.pp_sift_top2.argtypes = [C.c_void_p, C.c_int32, C.c_int32, c_ip, c_ip, c_ip]
+    L.pp_sift_match_thresholds.argtypes = [C.POINTER(SiftMatchOptions), c_ip, c_ip, C.c_int64, C.POINTER(C.c_int64)]
     L.pp_camera_image_to_world_threshold.argtypes = [C.c_int, c_dp, C.c_double, c_dp]
     _lib = L
     return L

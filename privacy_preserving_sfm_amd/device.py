@@ -913,3 +913,82 @@ class TracksProblem:
         check(_capi.lib().pp_tracks_get_state(self._h, C.byref(n), C.byref(t), ptr(lp, _capi.c_ip), dp(pts), ptr(dele, _capi.c_u8p), ptr(ts, _capi.c_ip),
                                               ptr(tl, _capi.c_ip), P, T))
         return dict(line_point=lp, points=pts, deleted=dele, track_start=ts, track_line=tl)
+
+
+def sift_match_options(**kw):
+    o = _capi.SiftMatchOptions()
+    _capi.lib().pp_sift_match_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def sift_match_thresholds(options=None):
+    """-> (d_min, table): the integers the device compares (pp_sift_match_thresholds; host only)"""
+    o = options or sift_match_options()
+    d_min, count = C.c_int32(), C.c_int64()
+    check(_capi.lib().pp_sift_match_thresholds(C.byref(o), C.byref(d_min), None, 0, C.byref(count)))
+    table = np.zeros(count.value, dtype=np.int32)
+    check(_capi.lib().pp_sift_match_thresholds(C.byref(o), C.byref(d_min), ptr(table, _capi.c_ip), count.value, C.byref(count)))
+    return d_min.value, table
+
+
+class SiftMatcher:
+    """pp_sift_handle: the descriptors ([N_k, 128] uint8 each) of a list of images on the device; match_pairs() is MatchSiftFeaturesCPUBruteForce for a
+    list of pairs of positions in that list, top2() the one-way scan underneath it."""
+
+    def __init__(self, descriptors_by_image, device=0):
+        self._h = C.c_void_p()
+        arrays = []
+        for d in descriptors_by_image:
+            d = np.asarray(d)
+            if d.dtype != np.uint8 or (d.size and (d.ndim != 2 or d.shape[1] != 128)):
+                raise ValueError("descriptors are [N, 128] uint8 arrays")
+            arrays.append(np.ascontiguousarray(d).reshape(-1, 128))
+        self.num_features = [int(a.shape[0]) for a in arrays]
+        self.num_images = len(arrays)
+        start = np.zeros(self.num_images + 1, dtype=np.int64)
+        start[1:] = np.cumsum(self.num_features)
+        flat = np.concatenate(arrays) if arrays else np.zeros((0, 128), dtype=np.uint8)
+        flat = np.ascontiguousarray(flat, dtype=np.uint8)
+        check(_capi.lib().pp_sift_create(self.num_images, ptr(start, C.POINTER(C.c_int64)), ptr(flat, _capi.c_u8p) if flat.size else None, int(device),
+                                         C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            _capi.lib().pp_sift_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def capacity(self, pairs, cross_check=True):
+        """the number of matches that always suffices for these pairs"""
+        n = self.num_features
+        return int(sum(min(n[a], n[b]) if cross_check else (n[a] if n[b] else 0) for a, b in pairs))
+
+    def match_pairs(self, pairs, options=None, capacity=None):
+        """-> (report, list of [n_p, 2] int32 arrays, one per pair, in the reference's order)"""
+        o = options or sift_match_options()
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        num = int(pr.shape[0])
+        if num and (pr.min() < 0 or pr.max() >= self.num_images):
+            raise ValueError("a pair names an image that is not there")
+        cap = self.capacity(pr, bool(o.cross_check)) if capacity is None else int(capacity)
+        start, out = np.zeros(num + 1, dtype=np.int64), np.zeros((max(cap, 1), 2), dtype=np.int32)
+        rep = _capi.SiftMatchReport()
+        check(_capi.lib().pp_sift_match_pairs(self._h, C.byref(o), num, ptr(pr, _capi.c_ip) if num else None, C.byref(rep), ptr(start, C.POINTER(C.c_int64)),
+                                              ptr(out, _capi.c_ip), cap))
+        return rep, [out[start[p]:start[p + 1]].copy() for p in range(num)]
+
+    def top2(self, image1, image2):
+        """-> (best_j, best, second), [N1] int32 each: K17a for the direction image1 -> image2"""
+        n1 = self.num_features[image1]
+        bj, b, s = (np.zeros(max(n1, 1), dtype=np.int32) for _ in range(3))
+        check(_capi.lib().pp_sift_top2(self._h, int(image1), int(image2), ptr(bj, _capi.c_ip), ptr(b, _capi.c_ip), ptr(s, _capi.c_ip)))
+        return bj[:n1], b[:n1], s[:n1]

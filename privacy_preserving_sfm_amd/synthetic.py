@@ -446,3 +446,37 @@ def make_completion_scene(num_cams, num_points, track, seed=0, withheld=0.25, sp
                corr_start=corr_start, corr_line=corr_line, points=np.array(points), cam_size=np.tile(np.array([[width, height]], dtype=np.int32), (base["intr"].shape[0], 1)),
                withheld_lines=sorted(withheld_lines), split_pairs=split_pairs, false_edge_list=false_list)
     return out
+
+
+def sift_like_descriptors(rng, n, base=None, noise=0.0):
+    """n SIFT-like descriptors [n, 128] uint8: gamma-distributed vectors (or copies of `base`, unit rows, with Gaussian noise of relative size `noise`, folded back to non-negative), normalised, clamped at 0.2, renormalised,
+    times 512, rounded, capped at 255 - the normalisation of the reference's extractor (L2, feature/sift.cc:925-955)"""
+    v = rng.gamma(0.6, 1.0, size=(n, 128)) if base is None else np.abs(base + noise * rng.normal(0.0, 1.0, size=(n, 128)) / np.sqrt(128.0))
+    v /= np.maximum(np.linalg.norm(v, axis=1, keepdims=True), 1e-12)
+    v = np.minimum(v, 0.2)
+    v /= np.maximum(np.linalg.norm(v, axis=1, keepdims=True), 1e-12)
+    return np.minimum(np.rint(512.0 * v), 255).astype(np.uint8)
+
+
+def make_descriptor_pair(n1, n2, shared, noise, seed, duplicates=0, zero_rows=0):
+    """Two descriptor sets for the SIFT matcher (K17): `shared` features of the first image reappear in the second as noisy copies at permuted positions,
+    the rest of both is unrelated.  `duplicates` rows of the second image are exact copies of another of its rows (a tie on the maximum: the lowest
+    index wins and second == best), `zero_rows` rows of each image are all zero (no match at all).
+    -> dict(d1 [n1, 128] uint8, d2 [n2, 128] uint8, truth [shared, 2] = (row of d1, row of d2))"""
+    if shared > min(n1, n2):
+        raise ValueError("shared exceeds an image's feature count")
+    rng = np.random.default_rng(seed)
+    unit = rng.gamma(0.6, 1.0, size=(n1, 128))
+    unit /= np.maximum(np.linalg.norm(unit, axis=1, keepdims=True), 1e-12)
+    d1 = sift_like_descriptors(rng, n1, base=unit)
+    d2 = sift_like_descriptors(rng, n2)
+    rows1, rows2 = rng.permutation(n1)[:shared], rng.permutation(n2)[:shared]
+    if shared:
+        d2[rows2] = sift_like_descriptors(rng, shared, base=unit[rows1], noise=noise)
+    for _ in range(min(duplicates, max(n2 - 1, 0))):
+        a, b = rng.choice(n2, size=2, replace=False)
+        d2[b] = d2[a]
+    for d, n in ((d1, n1), (d2, n2)):
+        if zero_rows and n:
+            d[rng.choice(n, size=min(zero_rows, n), replace=False)] = 0
+    return dict(d1=d1, d2=d2, truth=np.stack([rows1, rows2], axis=1).astype(np.int32))
