@@ -1088,6 +1088,52 @@ int pp_sift_top2(pp_sift_handle h, int32_t image1, int32_t image2, int32_t* best
  * else capacity >= *count.  PP_ERR_INTERNAL when this host's acosf is not monotonic (csrc/sift_match_replay.hpp). */
 int pp_sift_match_thresholds(const pp_sift_match_options* options, int32_t* d_min, int32_t* table, int64_t capacity, int64_t* count);
 
+/* ======================================================================================== *
+ *  Correspondence graph from the match lists (K18)                                          *
+ *  replaces: the match loop of DatabaseCache::Load (base/database_cache.cc:82-191) and       *
+ *  CorrespondenceGraph::AddCorrespondences / Finalize (base/correspondence_graph.cc:56-163), *
+ *  up to the corr_start / corr_line CSR of pp_tracks_desc                                    *
+ * ======================================================================================== */
+
+typedef struct pp_corr_graph_report {
+  int64_t num_pairs_used;         /* pairs with MORE than min_num_matches matches, self pairs included                                   */
+  int64_t num_pairs_ignored;      /* the others                                                                                          */
+  int64_t num_matches_in;         /* match_start[num_pairs]                                                                              */
+  int64_t num_matches_accepted;   /* matches that entered the graph: the CSR has twice as many entries                                   */
+  int64_t num_matches_bad_index;  /* matches of used pairs (self pairs apart) skipped for a line index that does not exist               */
+  int64_t num_matches_duplicate;  /* ... skipped because a line already corresponded to the other image                                  */
+  int64_t num_pairs_replayed;     /* used pairs whose valid matches repeat indices on BOTH sides: decided by the host's sequential loop  */
+  double device_ms, replay_ms, total_ms;
+} pp_corr_graph_report;
+
+typedef struct pp_corr_graph_impl* pp_corr_graph_handle;
+/* num_images images in ascending image-id order with their line counts (0 is valid).  Line x of image k is global line
+ * line_start[k] + x, line_start the exclusive scan of num_lines: the numbering of pp_tracks_desc as IncrementalTriangulator.flatten makes it. */
+int pp_corr_graph_create(int32_t num_images, const int32_t* num_lines, int device, pp_corr_graph_handle* out);
+int pp_corr_graph_destroy(pp_corr_graph_handle h);
+/* Builds the graph of the given match lists; it replaces the handle's previous one.  pairs: num_pairs x 2 image POSITIONS, in any order and either
+ * orientation; the matches of pair p are matches[2 * match_start[p] .. 2 * match_start[p + 1]) as (line of the first image, line of the second) - the
+ * layout pp_sift_match_pairs writes.  A pair is stored under its smaller image first and the pairs are applied in ascending (image1, image2); a pair is
+ * USED iff it has more than min_num_matches matches (counted before any is skipped); a used pair (k, k) marks k connected and adds nothing.  A match
+ * with an index out of range (negative included) is skipped, and so is one whose line already corresponds to the other image - the sequential rule of
+ * AddCorrespondences, which the device applies as "first occurrence on both sides" and the host replays for the pairs where that differs
+ * (csrc/corr_graph_replay.hpp).  The neighbours of a line come in the order of the used pairs that contributed them; the result is the same from run to run.
+ * ERRORS: PP_ERR_INVALID before any device work, the previous graph untouched, for: a null argument, a negative min_num_matches, an image position out
+ * of range, the same unordered pair listed twice, match_start[0] != 0 or a decreasing match_start, 2^31 matches or more.  PP_ERR_INVALID after the count,
+ * the previous graph still untouched, when twice the accepted matches do not fit int32 (the CSR of pp_tracks_desc). */
+int pp_corr_graph_build(pp_corr_graph_handle h, int32_t min_num_matches, int64_t num_pairs, const int32_t* pairs, const int64_t* match_start,
+                        const int32_t* matches, pp_corr_graph_report* report);
+/* The sizes of the last build: the global lines L and the CSR entries.  Either pointer may be NULL.  PP_ERR_INVALID before the first build. */
+int pp_corr_graph_num_entries(pp_corr_graph_handle h, int64_t* num_lines, int64_t* num_entries);
+/* The last build.  corr_start L + 1, corr_line `capacity` entries of room, image_connected / image_num_observations / image_num_correspondences
+ * num_images each: connected = the image belongs to a used pair; observations = its lines with at least one neighbour (0: Finalize drops the image
+ * from the graph, it stays connected); correspondences = its accepted matches.  Any pointer may be NULL.  PP_ERR_INVALID, nothing written, when
+ * corr_line is given and capacity is too small, and before the first build. */
+int pp_corr_graph_get(pp_corr_graph_handle h, int32_t* corr_start, int32_t* corr_line, int64_t capacity, uint8_t* image_connected,
+                      int32_t* image_num_observations, int32_t* image_num_correspondences);
+/* The accepted matches of every pair of the last build, in its input order (num_pairs entries); 0 for a pair that was not used and for a self pair. */
+int pp_corr_graph_pair_counts(pp_corr_graph_handle h, int32_t* pair_num_correspondences);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,12 @@ class SiftMatchReport(C.Structure):
     _fields_ = [("num_matches", C.c_int64), ("num_pairs_emptied", C.c_int32), ("num_batches", C.c_int32), ("device_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class CorrGraphReport(C.Structure):
+    _fields_ = [("num_pairs_used", C.c_int64), ("num_pairs_ignored", C.c_int64), ("num_matches_in", C.c_int64), ("num_matches_accepted", C.c_int64),
+                ("num_matches_bad_index", C.c_int64), ("num_matches_duplicate", C.c_int64), ("num_pairs_replayed", C.c_int64),
+                ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -233,6 +239,7 @@ _EXPORTS = [
     "pp_tracks_filter_points", "pp_tracks_filter_negative_depth", "pp_tracks_filter_images",
     "pp_init_sets_options_default", "pp_tracks_find_initial_sets", "pp_tracks_bundle_setup",
     "pp_sift_match_options_default", "pp_sift_create", "pp_sift_destroy", "pp_sift_match_pairs", "pp_sift_top2", "pp_sift_match_thresholds",
+    "pp_corr_graph_create", "pp_corr_graph_destroy", "pp_corr_graph_build", "pp_corr_graph_num_entries", "pp_corr_graph_get", "pp_corr_graph_pair_counts",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -357,6 +364,12 @@ def lib():
     L.pp_sift_match_pairs.argtypes = [C.c_void_p, C.POINTER(SiftMatchOptions), C.c_int64, c_ip, C.POINTER(SiftMatchReport), C.POINTER(C.c_int64), c_ip, C.c_int64]
     L.pp_sift_top2.argtypes = [C.c_void_p, C.c_int32, C.c_int32, c_ip, c_ip, c_ip]
     L.pp_sift_match_thresholds.argtypes = [C.POINTER(SiftMatchOptions), c_ip, c_ip, C.c_int64, C.POINTER(C.c_int64)]
+    L.pp_corr_graph_create.argtypes = [C.c_int32, c_ip, C.c_int, C.POINTER(C.c_void_p)]
+    L.pp_corr_graph_destroy.argtypes = [C.c_void_p]
+    L.pp_corr_graph_build.argtypes = [C.c_void_p, C.c_int32, C.c_int64, c_ip, C.POINTER(C.c_int64), c_ip, C.POINTER(CorrGraphReport)]
+    L.pp_corr_graph_num_entries.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.pp_corr_graph_get.argtypes = [C.c_void_p, c_ip, c_ip, C.c_int64, c_u8p, c_ip, c_ip]
+    L.pp_corr_graph_pair_counts.argtypes = [C.c_void_p, c_ip]
     L.pp_camera_image_to_world_threshold.argtypes = [C.c_int, c_dp, C.c_double, c_dp]
     _lib = L
     return L

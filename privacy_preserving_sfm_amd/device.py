@@ -992,3 +992,68 @@ class SiftMatcher:
         bj, b, s = (np.zeros(max(n1, 1), dtype=np.int32) for _ in range(3))
         check(_capi.lib().pp_sift_top2(self._h, int(image1), int(image2), ptr(bj, _capi.c_ip), ptr(b, _capi.c_ip), ptr(s, _capi.c_ip)))
         return bj[:n1], b[:n1], s[:n1]
+
+
+class CorrGraphBuilder:
+    """pp_corr_graph_handle: the images of a problem (their line counts, in ascending image-id order) on the device; build() turns match lists into the
+    corr_start / corr_line CSR of pp_tracks_desc by the rules of DatabaseCache::Load and CorrespondenceGraph::AddCorrespondences, get() reads it back."""
+
+    def __init__(self, num_lines_by_image, device=0):
+        self._h = C.c_void_p()
+        self.num_lines = np.ascontiguousarray(num_lines_by_image, dtype=np.int32).reshape(-1)
+        self.num_images = int(self.num_lines.shape[0])
+        self.line_start = np.zeros(self.num_images + 1, dtype=np.int64)
+        self.line_start[1:] = np.cumsum(self.num_lines, dtype=np.int64)
+        self.num_pairs = None
+        check(_capi.lib().pp_corr_graph_create(self.num_images, ptr(self.num_lines, _capi.c_ip) if self.num_images else None, int(device), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            _capi.lib().pp_corr_graph_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def build(self, pairs, matches, min_num_matches=15):
+        """pairs: [num_pairs, 2] image positions; matches: one [n_p, 2] array per pair, or (match_start [num_pairs + 1], flat [n, 2]) as
+        pp_sift_match_pairs writes them -> report"""
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        num = int(pr.shape[0])
+        if isinstance(matches, tuple):
+            start = np.ascontiguousarray(matches[0], dtype=np.int64).reshape(-1)
+            flat = np.ascontiguousarray(matches[1], dtype=np.int32).reshape(-1, 2)
+        else:
+            arrays = [np.asarray(m, dtype=np.int32).reshape(-1, 2) for m in matches]
+            start = np.zeros(num + 1, dtype=np.int64)
+            start[1:] = np.cumsum([a.shape[0] for a in arrays], dtype=np.int64)
+            flat = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0, 2), dtype=np.int32))
+        if start.shape[0] != num + 1:
+            raise ValueError("one match list per pair")
+        rep = _capi.CorrGraphReport()
+        check(_capi.lib().pp_corr_graph_build(self._h, int(min_num_matches), num, ptr(pr, _capi.c_ip) if num else None, ptr(start, C.POINTER(C.c_int64)),
+                                              ptr(flat, _capi.c_ip) if flat.size else None, C.byref(rep)))
+        self.num_pairs = num
+        return rep
+
+    def get(self):
+        """the last build -> dict(corr_start [L + 1], corr_line [E], image_connected, image_num_observations, image_num_correspondences [num_images])"""
+        L, E = C.c_int64(), C.c_int64()
+        check(_capi.lib().pp_corr_graph_num_entries(self._h, C.byref(L), C.byref(E)))
+        n = max(self.num_images, 1)
+        corr_start, corr_line = np.zeros(L.value + 1, dtype=np.int32), np.zeros(max(E.value, 1), dtype=np.int32)
+        connected, obs, corrs = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        check(_capi.lib().pp_corr_graph_get(self._h, ptr(corr_start, _capi.c_ip), ptr(corr_line, _capi.c_ip), E.value, ptr(connected, _capi.c_u8p),
+                                            ptr(obs, _capi.c_ip), ptr(corrs, _capi.c_ip)))
+        k = self.num_images
+        return dict(corr_start=corr_start, corr_line=corr_line[:E.value], image_connected=connected[:k], image_num_observations=obs[:k],
+                    image_num_correspondences=corrs[:k])
+
+    def pair_counts(self):
+        """the accepted matches per pair of the last build, in its input order"""
+        out = np.zeros(max(self.num_pairs or 0, 1), dtype=np.int32)
+        check(_capi.lib().pp_corr_graph_pair_counts(self._h, ptr(out, _capi.c_ip)))
+        return out[:self.num_pairs or 0]

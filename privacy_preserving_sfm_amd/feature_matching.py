@@ -5,11 +5,12 @@ the pairs of `ExhaustiveFeatureMatcher::Run` (feature/matching.cc:436-498), `Sif
 
 The privacy-preserving pipeline has no geometric verification: what the matcher emits goes unchanged into the database and from there into the graph.
 Feature extraction, the SQLite database and the sequential / spatial / transitive pair selections are not mirrored.  There is no host fall-back for the
-match itself: every call needs the device."""
+match itself: every call needs the device.  The graph has both forms: `build_correspondence_graph` on the host, dict-based, and
+`build_correspondence_graph_on_device` (pp_corr_graph_*, K18), which returns the same graph as arrays."""
 import numpy as np
 
-from .device import SiftMatcher, sift_match_options
-from .incremental_triangulator import CorrespondenceGraph
+from .device import CorrGraphBuilder, SiftMatcher, sift_match_options
+from .incremental_triangulator import CorrespondenceGraph, FlatCorrespondenceGraph
 
 
 class SiftMatchingOptions:
@@ -83,6 +84,7 @@ class FeatureMatcher:
         self.image_ids_ = sorted(descriptors_by_image_id)
         self._index = {i: k for k, i in enumerate(self.image_ids_)}
         self._workspace_bytes = workspace_bytes
+        self._device = device
         self._matcher = SiftMatcher([descriptors_by_image_id[i] for i in self.image_ids_], device=device)
         self.last_report = None
 
@@ -107,6 +109,11 @@ class FeatureMatcher:
                                              self.options_.device_options(workspace_bytes=self._workspace_bytes))
         self.last_report = rep
         return {pair: m for pair, m in zip(kept, out)}
+
+    def MatchToGraph(self, image_pairs, num_lines_by_image, min_num_matches=15):
+        """Match, then build_correspondence_graph_on_device on its output -> (FlatCorrespondenceGraph, the sorted ids of the connected images).
+        min_num_matches is the mapper's option (a pair is used with MORE matches), not the matcher's of the same name."""
+        return build_correspondence_graph_on_device(self.Match(image_pairs), num_lines_by_image, min_num_matches, device=self._device)
 
 
 def build_correspondence_graph(matches, num_lines_by_image, min_num_matches=15):
@@ -139,3 +146,26 @@ def build_correspondence_graph(matches, num_lines_by_image, min_num_matches=15):
             graph.AddCorrespondence(id1, x1, id2, x2)
             graph.AddCorrespondence(id2, x2, id1, x1)
     return graph, connected
+
+
+def build_correspondence_graph_on_device(matches, num_lines_by_image, min_num_matches=15, device=0, report=None):
+    """build_correspondence_graph on the device (pp_corr_graph_build, K18): the same arguments, the same graph - as arrays.
+    -> (incremental_triangulator.FlatCorrespondenceGraph over the images of num_lines_by_image, the sorted ids of the connected images).  A pair that
+    names an image without an entry in num_lines_by_image is ignored.  report: a list the pp_corr_graph_report is appended to."""
+    image_ids = sorted(num_lines_by_image)
+    index = {i: k for k, i in enumerate(image_ids)}
+    pairs, lists = [], []
+    for (id1, id2), m in matches.items():
+        if id1 in index and id2 in index:
+            pairs.append((index[id1], index[id2]))
+            lists.append(m)
+    builder = CorrGraphBuilder([num_lines_by_image[i] for i in image_ids], device=device)
+    try:
+        rep = builder.build(pairs, lists, min_num_matches)
+        out = builder.get()
+    finally:
+        builder.close()
+    if report is not None:
+        report.append(rep)
+    graph = FlatCorrespondenceGraph(image_ids, builder.num_lines, out["corr_start"], out["corr_line"], out["image_connected"])
+    return graph, [i for i, c in zip(image_ids, out["image_connected"]) if c]

@@ -53,6 +53,142 @@ class CorrespondenceGraph:
         corrs = self.FindCorrespondences(image_id, line_idx)
         return len(corrs) == 1 and len(self.FindCorrespondences(*corrs[0])) == 1
 
+    # the per-image and per-pair queries of base/correspondence_graph.h:40-74, as they answer after Finalize
+
+    def NumObservationsForImage(self, image_id):
+        """lines of the image with at least one correspondence"""
+        return sum(1 for (i, _), c in self._corrs.items() if i == image_id and c)
+
+    def ExistsImage(self, image_id):
+        """Finalize erases an image without an observation (base/correspondence_graph.cc:56-71)"""
+        return self.NumObservationsForImage(image_id) > 0
+
+    def NumCorrespondencesForImage(self, image_id):
+        return sum(len(c) for (i, _), c in self._corrs.items() if i == image_id)
+
+    def FindCorrespondencesBetweenImages(self, image_id1, image_id2):
+        """base/correspondence_graph.cc:226-250 -> [(line_idx1, line_idx2)], ascending in line_idx1"""
+        lines = sorted(x for (i, x) in self._corrs if i == image_id1)
+        return [(x1, x2) for x1 in lines for (i2, x2) in self._corrs[(image_id1, x1)] if i2 == image_id2]
+
+    def NumCorrespondencesBetweenImages(self, image_id1, image_id2):
+        return len(self.FindCorrespondencesBetweenImages(image_id1, image_id2))
+
+
+class FlatCorrespondenceGraph:
+    """The same graph as arrays, the form pp_corr_graph_build leaves it in (include/ppsfm_hip.h, K18): the images in ascending id with their line counts,
+    line x of the k-th image is global line line_start[k] + x, and the correspondences of global line l are corr_line[corr_start[l] : corr_start[l + 1]] in
+    the order AddCorrespondences appended them.  Every query answers what CorrespondenceGraph answers, in the same order."""
+
+    def __init__(self, image_ids, num_lines, corr_start, corr_line, image_connected=None):
+        self.image_ids = [int(i) for i in image_ids]
+        if sorted(set(self.image_ids)) != self.image_ids:
+            raise ValueError("image_ids must ascend")
+        self.num_lines = np.asarray(num_lines, dtype=np.int64).reshape(-1)
+        self.line_start = np.zeros(len(self.image_ids) + 1, dtype=np.int64)
+        self.line_start[1:] = np.cumsum(self.num_lines)
+        self.corr_start = np.asarray(corr_start, dtype=np.int64).reshape(-1)
+        self.corr_line = np.asarray(corr_line, dtype=np.int64).reshape(-1)
+        if len(self.num_lines) != len(self.image_ids) or len(self.corr_start) != self.line_start[-1] + 1 or self.corr_start[-1] != len(self.corr_line):
+            raise ValueError("the arrays do not describe one graph")
+        self.image_connected = None if image_connected is None else np.asarray(image_connected, dtype=bool).reshape(-1)
+        self._index = {i: k for k, i in enumerate(self.image_ids)}
+
+    @classmethod
+    def from_graph(cls, graph, num_lines_by_image):
+        """the arrays of a CorrespondenceGraph over the images of {image_id: number of lines}"""
+        image_ids = sorted(num_lines_by_image)
+        offset, total = {}, 0
+        for i in image_ids:
+            offset[i] = total
+            total += num_lines_by_image[i]
+        corr_start, corr_line = np.zeros(total + 1, dtype=np.int64), []
+        for i in image_ids:
+            for x in range(num_lines_by_image[i]):
+                corr_line.extend(offset[i2] + x2 for (i2, x2) in graph.FindCorrespondences(i, x))
+                corr_start[offset[i] + x + 1] = len(corr_line)
+        return cls(image_ids, [num_lines_by_image[i] for i in image_ids], corr_start, corr_line)
+
+    def _line(self, image_id, line_idx):
+        k = self._index.get(image_id)
+        if k is None or not 0 <= line_idx < self.num_lines[k]:
+            return -1
+        return int(self.line_start[k]) + int(line_idx)
+
+    def _refs(self, lines):
+        """global lines -> [(image_id, line_idx)]"""
+        lines = np.asarray(lines, dtype=np.int64)
+        k = np.searchsorted(self.line_start, lines, side="right") - 1      # (an image without lines shares its start with the next: the last one wins)
+        return [(self.image_ids[int(a)], int(b)) for a, b in zip(k, lines - self.line_start[k])]
+
+    def FindCorrespondences(self, image_id, line_idx):
+        l = self._line(image_id, line_idx)
+        if l < 0:
+            return []
+        return self._refs(self.corr_line[self.corr_start[l]:self.corr_start[l + 1]])
+
+    FindTransitiveCorrespondences = CorrespondenceGraph.FindTransitiveCorrespondences
+    IsTwoViewObservation = CorrespondenceGraph.IsTwoViewObservation
+
+    def NumObservationsForImage(self, image_id):
+        k = self._index.get(image_id)
+        if k is None:
+            return 0
+        s = self.corr_start[self.line_start[k]:self.line_start[k + 1] + 1]
+        return int(np.count_nonzero(s[1:] > s[:-1]))
+
+    def ExistsImage(self, image_id):
+        return self.NumObservationsForImage(image_id) > 0
+
+    def NumCorrespondencesForImage(self, image_id):
+        k = self._index.get(image_id)
+        if k is None:
+            return 0
+        return int(self.corr_start[self.line_start[k + 1]] - self.corr_start[self.line_start[k]])
+
+    def FindCorrespondencesBetweenImages(self, image_id1, image_id2):
+        k1, k2 = self._index.get(image_id1), self._index.get(image_id2)
+        if k1 is None or k2 is None:
+            return []
+        l0, l1 = self.line_start[k1], self.line_start[k1 + 1]
+        e0, e1 = self.corr_start[l0], self.corr_start[l1]
+        nb = self.corr_line[e0:e1]
+        owner = np.repeat(np.arange(l0, l1), np.diff(self.corr_start[l0:l1 + 1]))
+        keep = (nb >= self.line_start[k2]) & (nb < self.line_start[k2 + 1])
+        return [(int(a), int(b)) for a, b in zip(owner[keep] - l0, nb[keep] - self.line_start[k2])]
+
+    def NumCorrespondencesBetweenImages(self, image_id1, image_id2):
+        return len(self.FindCorrespondencesBetweenImages(image_id1, image_id2))
+
+    def remapped_csr(self, image_ids, num_lines):
+        """(corr_start [L' + 1], corr_line) int32 in the line numbering of ANOTHER image list (ascending ids, their line counts): a line of an image this
+        graph does not hold has no neighbour, a neighbour in an image the list does not hold is dropped.  Vectorised: no loop over lines."""
+        num_lines = np.asarray(num_lines, dtype=np.int64).reshape(-1)
+        start = np.zeros(len(image_ids) + 1, dtype=np.int64)
+        start[1:] = np.cumsum(num_lines)
+        there = np.array([self._index.get(i, -1) for i in image_ids], dtype=np.int64)      # position here of every image of the list
+        both = there >= 0
+        if (num_lines[both] != self.num_lines[there[both]]).any():
+            raise ValueError("an image has another number of lines than the correspondence graph was built with")
+        # their line -> ours, our line -> theirs (-1: not held)
+        to_ours = np.full(int(start[-1]), -1, dtype=np.int64)
+        to_theirs = np.full(int(self.line_start[-1]), -1, dtype=np.int64)
+        image_of = np.repeat(np.arange(len(image_ids)), num_lines)
+        held = both[image_of]
+        mine = np.arange(int(start[-1]))[held]
+        ours = mine - start[image_of[held]] + self.line_start[there[image_of[held]]]
+        to_ours[mine], to_theirs[ours] = ours, mine
+        src = np.where(to_ours >= 0, to_ours, 0)
+        degree = np.where(to_ours >= 0, self.corr_start[src + 1] - self.corr_start[src], 0)
+        owner = np.repeat(np.arange(int(start[-1])), degree)
+        first = np.cumsum(degree) - degree
+        entry = self.corr_start[src][owner] + (np.arange(int(degree.sum())) - first[owner])
+        nb = to_theirs[self.corr_line[entry]]
+        keep = nb >= 0
+        corr_start = np.zeros(int(start[-1]) + 1, dtype=np.int32)
+        corr_start[1:] = np.cumsum(np.bincount(owner[keep], minlength=int(start[-1])))
+        return corr_start, nb[keep].astype(np.int32)
+
 
 class IncrementalTriangulator:
     class Options:
@@ -114,14 +250,18 @@ class IncrementalTriangulator:
         lines, line_image, line_point = np.zeros((L, 3)), np.zeros(L, dtype=np.int32), np.full(L, -1, dtype=np.int32)
         line_aligned = np.zeros(L, dtype=np.uint8)
         corr_start, corr_line = np.zeros(L + 1, dtype=np.int32), []
+        flat_graph = isinstance(graph, FlatCorrespondenceGraph)      # the arrays are taken as they are, remapped to this reconstruction's images
         for c, iid in enumerate(image_ids):
             for idx, fl in enumerate(rec.images[iid].lines):
                 l = offset[iid] + idx
                 lines[l], line_image[l], line_aligned[l] = fl.Line(), c, fl.IsAligned()
                 if fl.HasPoint3D():
                     line_point[l] = point_index[fl.Point3DId()]
-                corr_line.extend(offset[i2] + x2 for (i2, x2) in graph.FindCorrespondences(iid, idx) if i2 in offset)
-                corr_start[l + 1] = len(corr_line)
+                if not flat_graph:
+                    corr_line.extend(offset[i2] + x2 for (i2, x2) in graph.FindCorrespondences(iid, idx) if i2 in offset)
+                    corr_start[l + 1] = len(corr_line)
+        if flat_graph:
+            corr_start, corr_line = graph.remapped_csr(image_ids, [len(rec.images[i].lines) for i in image_ids])
         track_start, track_line = np.zeros(len(point_ids) + 1, dtype=np.int32), []
         for k, pid in enumerate(point_ids):
             track_line.extend(offset[iid] + idx for (iid, idx) in rec.points3D[pid].track)
