@@ -54,6 +54,12 @@ int pp_camera_num_params(int model_id);
 /* pixel threshold -> normalised-plane threshold: BaseCameraModel::ImageToWorldThreshold
  * (base/camera_models.h:533-543), used for RANSACOptions::max_error (sfm/incremental_mapper.cc:673-675) */
 int pp_camera_image_to_world_threshold(int model_id, const double* params, double threshold_px, double* out);
+/* n pixels xy (n x 2) -> normalised coordinates uv (n x 2): every model's ImageToWorld (base/camera_models.h) - closed form for the pinhole models
+ * and FOV (Undistortion, :1176-1210), BaseCameraModel::IterativeUndistortion (:547-588) restated for the others.  Host only, needs no device.
+ * PP_ERR_INVALID for an unknown model or a null pointer. */
+int pp_camera_image_to_world(int model_id, const double* params, int64_t n, const double* xy, double* uv);
+/* the other direction, uv (n x 2) -> xy (n x 2): WorldToImage, the code the device evaluates residuals with, on the host */
+int pp_camera_world_to_image(int model_id, const double* params, int64_t n, const double* uv, double* xy);
 
 /* ======================================================================================== *
  *  Bundle adjustment                                                                        *
@@ -1133,6 +1139,49 @@ int pp_corr_graph_get(pp_corr_graph_handle h, int32_t* corr_start, int32_t* corr
                       int32_t* image_num_observations, int32_t* image_num_correspondences);
 /* The accepted matches of every pair of the last build, in its input order (num_pairs entries); 0 for a pair that was not used and for a self pair. */
 int pp_corr_graph_pair_counts(pp_corr_graph_handle h, int32_t* pair_num_correspondences);
+
+/* ======================================================================================== *
+ *  Line features from keypoints (K19)                                                       *
+ *  replaces: the line generation of LineFeatureWriterThread::Run                             *
+ *  (feature/extraction.cc:437-505); the detector and the descriptor stay outside            *
+ * ======================================================================================== */
+
+typedef struct pp_line_features_desc {
+  int32_t num_images, num_cameras;
+  const int32_t* image_ids;       /* num_images: the generator is keyed by them, not by the position in the batch                */
+  const int64_t* kp_start;        /* num_images + 1: keypoint f of image k is global keypoint (= line) kp_start[k] + f; [0] = 0    */
+  const float* keypoints;         /* L x 2 pixel (x, y), L = kp_start[num_images]                                                */
+  const int32_t* image_camera;    /* num_images: index into the camera arrays                                                    */
+  const int32_t* camera_model;    /* num_cameras model ids                                                                       */
+  const double* intr;             /* num_cameras x PP_CAM_STRIDE                                                                 */
+  const uint8_t* has_gravity;     /* num_images; NULL = no image has one                                                         */
+  const double* gravity;          /* num_images x 3, read where has_gravity is set: Image::GravityDirection(), camera frame        */
+} pp_line_features_desc;
+
+typedef struct pp_line_features_options {
+  double aligned_line_ratio;      /* 0.5 (feature/extraction.cc:160-162); in [0, 1]                                               */
+  uint64_t seed;                  /* of the counter-based generator (csrc/line_features_replay.hpp); 0                            */
+} pp_line_features_options;
+void pp_line_features_options_default(pp_line_features_options* o);
+
+typedef struct pp_line_features_report {
+  int64_t num_lines;                   /* L                                                                                      */
+  int64_t num_aligned;                 /* lines through the gravity direction                                                    */
+  int64_t num_images_without_gravity;  /* they get random lines only (the reference prints a warning)                            */
+  int64_t num_degenerate;              /* lines whose first two components have a zero or non-finite norm: written as computed   */
+  int64_t num_newton_exhausted;        /* keypoints whose undistortion ran all 100 Newton iterations                             */
+  double device_ms;
+} pp_line_features_report;
+
+/* One line per keypoint: the keypoint widened to double and undistorted with its image's camera to (u, v); d = the image's gravity direction for the
+ * aligned features, else a random vector in [-1, 1)^3; the line is d x (u, v, 1) divided by the norm of its first two components.  An image with
+ * gravity aligns the n features with the smallest generator key, n the smallest count with double(n) / double(N) >= aligned_line_ratio; an image
+ * without gravity aligns none.  Every draw is a function of (seed, image id, feature index) alone: the same image gets the same lines in any batch.
+ * lines_out L x 3, aligned_out L bytes, dirs_out NULL or L x 3 (the d of every line).
+ * ERRORS: PP_ERR_INVALID before any device work for a null argument, a ratio outside [0, 1] (NaN included), kp_start[0] != 0 or a decreasing kp_start,
+ * 2^31 keypoints or more, a camera index out of range, an unknown camera model, a non-finite intrinsic parameter or gravity component. */
+int pp_line_features_from_keypoints(const pp_line_features_desc* desc, const pp_line_features_options* options, int device, double* lines_out,
+                                    uint8_t* aligned_out, double* dirs_out, pp_line_features_report* report);
 
 #ifdef __cplusplus
 }

@@ -204,6 +204,21 @@ class CorrGraphReport(C.Structure):
                 ("device_ms", C.c_double), ("replay_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class LineFeaturesDesc(C.Structure):
+    _fields_ = [("num_images", C.c_int32), ("num_cameras", C.c_int32), ("image_ids", c_ip), ("kp_start", C.POINTER(C.c_int64)),
+                ("keypoints", C.POINTER(C.c_float)), ("image_camera", c_ip), ("camera_model", c_ip), ("intr", c_dp), ("has_gravity", c_u8p),
+                ("gravity", c_dp)]
+
+
+class LineFeaturesOptions(C.Structure):
+    _fields_ = [("aligned_line_ratio", C.c_double), ("seed", C.c_uint64)]
+
+
+class LineFeaturesReport(C.Structure):
+    _fields_ = [("num_lines", C.c_int64), ("num_aligned", C.c_int64), ("num_images_without_gravity", C.c_int64), ("num_degenerate", C.c_int64),
+                ("num_newton_exhausted", C.c_int64), ("device_ms", C.c_double)]
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -222,6 +237,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32
 
 _EXPORTS = [
     "pp_last_error", "pp_device_count", "pp_debug_raise", "pp_camera_num_params", "pp_camera_image_to_world_threshold",
+    "pp_camera_image_to_world", "pp_camera_world_to_image",
     "pp_ba_options_default", "pp_ba_create", "pp_ba_destroy", "pp_ba_set_parameters", "pp_ba_get_parameters",
     "pp_ba_eval", "pp_ba_eval_host_view", "pp_ba_eval_device", "pp_ba_solve", "pp_ba_get_trace", "pp_ba_get_structure", "pp_ba_get_intrinsics_layout", "pp_ba_plan_ordering", "pp_ba_pair_lists_host", "pp_ba_covisibility", "pp_ba_get_create_profile", "pp_ba_reduced_system", "pp_ba_covariance", "pp_ba_set_allreduce", "pp_ba_set_communicator", "pp_comm_unique_id", "pp_comm_create", "pp_comm_destroy",
     "pp_comm_allreduce",
@@ -240,6 +256,7 @@ _EXPORTS = [
     "pp_init_sets_options_default", "pp_tracks_find_initial_sets", "pp_tracks_bundle_setup",
     "pp_sift_match_options_default", "pp_sift_create", "pp_sift_destroy", "pp_sift_match_pairs", "pp_sift_top2", "pp_sift_match_thresholds",
     "pp_corr_graph_create", "pp_corr_graph_destroy", "pp_corr_graph_build", "pp_corr_graph_num_entries", "pp_corr_graph_get", "pp_corr_graph_pair_counts",
+    "pp_line_features_options_default", "pp_line_features_from_keypoints",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -371,6 +388,12 @@ def lib():
     L.pp_corr_graph_get.argtypes = [C.c_void_p, c_ip, c_ip, C.c_int64, c_u8p, c_ip, c_ip]
     L.pp_corr_graph_pair_counts.argtypes = [C.c_void_p, c_ip]
     L.pp_camera_image_to_world_threshold.argtypes = [C.c_int, c_dp, C.c_double, c_dp]
+    L.pp_camera_image_to_world.argtypes = [C.c_int, c_dp, C.c_int64, c_dp, c_dp]
+    L.pp_camera_world_to_image.argtypes = [C.c_int, c_dp, C.c_int64, c_dp, c_dp]
+    L.pp_line_features_options_default.argtypes = [C.POINTER(LineFeaturesOptions)]
+    L.pp_line_features_options_default.restype = None
+    L.pp_line_features_from_keypoints.argtypes = [C.POINTER(LineFeaturesDesc), C.POINTER(LineFeaturesOptions), C.c_int, c_dp, c_u8p, c_dp,
+                                                  C.POINTER(LineFeaturesReport)]
     _lib = L
     return L
 

@@ -69,6 +69,20 @@ class Camera:
         first = 3 if self.model_id in (0, 2, 3, 8, 9) else 4
         return list(range(first, len(self.params)))
 
+    def _map(self, entry, points):
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        flat = np.ascontiguousarray(pts.reshape(-1, 2))
+        out = np.zeros_like(flat)
+        _capi.check(entry(self.model_id, _capi.dp(_capi.f64(self.params)), flat.shape[0], _capi.dp(flat), _capi.dp(out)))
+        return out.reshape(pts.shape)
+
+    def ImageToWorld(self, image_points):
+        """Camera::ImageToWorld (base/camera.cc): pixel (x, y) or [N, 2] -> normalised (u, v), on the host through pp_camera_image_to_world"""
+        return self._map(_capi.lib().pp_camera_image_to_world, image_points)
+
+    def WorldToImage(self, world_points):
+        """Camera::WorldToImage: normalised (u, v) or [N, 2] -> pixel (x, y), on the host through pp_camera_world_to_image"""
+        return self._map(_capi.lib().pp_camera_world_to_image, world_points)
 
     def HasBogusParams(self, min_focal_length_ratio, max_focal_length_ratio, max_extra_param):
         """Camera::HasBogusParams (base/camera.cc:186-192, base/camera_models.h:473-531): principal point outside the image, a focal length

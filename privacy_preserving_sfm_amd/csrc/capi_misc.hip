@@ -71,6 +71,18 @@ int pp_camera_image_to_world_threshold(int model_id, const double* params, doubl
   return PP_OK;
 } PP_API_CATCH("pp_camera_image_to_world_threshold")
 
+int pp_camera_image_to_world(int model_id, const double* params, int64_t n, const double* xy, double* uv) try {
+  PP_REQUIRE(params && CameraNumParams(model_id) > 0 && n >= 0 && (n == 0 || (xy && uv)), "pp_camera_image_to_world: bad argument");
+  for (int64_t i = 0; i < n; ++i) ImageToWorld(model_id, params, xy[2 * i], xy[2 * i + 1], &uv[2 * i], &uv[2 * i + 1]);
+  return PP_OK;
+} PP_API_CATCH("pp_camera_image_to_world")
+
+int pp_camera_world_to_image(int model_id, const double* params, int64_t n, const double* uv, double* xy) try {
+  PP_REQUIRE(params && CameraNumParams(model_id) > 0 && n >= 0 && (n == 0 || (xy && uv)), "pp_camera_world_to_image: bad argument");
+  for (int64_t i = 0; i < n; ++i) WorldToImage(model_id, params, uv[2 * i], uv[2 * i + 1], &xy[2 * i], &xy[2 * i + 1]);
+  return PP_OK;
+} PP_API_CATCH("pp_camera_world_to_image")
+
 void pp_ba_options_default(pp_ba_options* o) {
   if (!o) return;
   o->max_num_iterations = 100;                // optim/bundle_adjustment.h:86

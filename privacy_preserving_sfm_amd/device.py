@@ -1057,3 +1057,62 @@ class CorrGraphBuilder:
         out = np.zeros(max(self.num_pairs or 0, 1), dtype=np.int32)
         check(_capi.lib().pp_corr_graph_pair_counts(self._h, ptr(out, _capi.c_ip)))
         return out[:self.num_pairs or 0]
+
+
+def line_features_options(**kw):
+    o = _capi.LineFeaturesOptions()
+    _capi.lib().pp_line_features_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+class LineFeatureGenerator:
+    """pp_line_features_from_keypoints: keypoints of a batch of images, undistorted with their cameras, to one line each (K19).  Owns nothing between
+    calls; generate() is the call."""
+
+    def __init__(self, device=0):
+        self.device = int(device)
+
+    def generate(self, image_ids, kp_start, keypoints, image_camera, camera_model, intr, has_gravity=None, gravity=None, aligned_line_ratio=0.5,
+                 seed=0, want_dirs=True):
+        """-> dict(lines [L, 3], aligned [L] uint8, dirs [L, 3] or None, report)"""
+        ids = np.ascontiguousarray(image_ids, dtype=np.int32).reshape(-1)
+        num_images = int(ids.shape[0])
+        start = np.ascontiguousarray(kp_start, dtype=np.int64).reshape(-1)
+        if start.shape[0] != num_images + 1:
+            raise ValueError("kp_start has num_images + 1 entries")
+        kp = np.ascontiguousarray(keypoints, dtype=np.float32).reshape(-1, 2)
+        cam = np.ascontiguousarray(image_camera, dtype=np.int32).reshape(-1)
+        model = np.ascontiguousarray(camera_model, dtype=np.int32).reshape(-1)
+        num_cameras = int(model.shape[0])
+        params = np.ascontiguousarray(intr, dtype=np.float64).reshape(num_cameras, _capi.CAM_STRIDE)
+        if cam.shape[0] != num_images:
+            raise ValueError("one camera index per image")
+        hg = None if has_gravity is None else np.ascontiguousarray(np.asarray(has_gravity, dtype=bool), dtype=np.uint8).reshape(-1)
+        gv = None if gravity is None else np.ascontiguousarray(gravity, dtype=np.float64).reshape(num_images, 3)
+        if hg is not None and hg.shape[0] != num_images:
+            raise ValueError("one has_gravity flag per image")
+        L = max(int(start[-1]), 0)
+        if kp.shape[0] < L:
+            raise ValueError("kp_start names %d keypoints, %d given" % (L, kp.shape[0]))
+        desc = _capi.LineFeaturesDesc()
+        desc.num_images, desc.num_cameras = num_images, num_cameras
+        desc.image_ids = ptr(ids, _capi.c_ip) if num_images else None
+        desc.kp_start = ptr(start, C.POINTER(C.c_int64))
+        desc.keypoints = ptr(kp, C.POINTER(C.c_float)) if kp.size else None
+        desc.image_camera = ptr(cam, _capi.c_ip) if num_images else None
+        desc.camera_model = ptr(model, _capi.c_ip) if num_cameras else None
+        desc.intr = dp(params) if num_cameras else None
+        desc.has_gravity = ptr(hg, _capi.c_u8p) if hg is not None and num_images else None
+        desc.gravity = dp(gv) if gv is not None and num_images else None
+        opt = line_features_options(aligned_line_ratio=float(aligned_line_ratio), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+        lines = np.zeros((max(L, 1), 3))
+        aligned = np.zeros(max(L, 1), dtype=np.uint8)
+        dirs = np.zeros((max(L, 1), 3)) if want_dirs else None
+        rep = _capi.LineFeaturesReport()
+        check(_capi.lib().pp_line_features_from_keypoints(C.byref(desc), C.byref(opt), self.device, dp(lines), ptr(aligned, _capi.c_u8p), dp(dirs),
+                                                          C.byref(rep)))
+        return dict(lines=lines[:L], aligned=aligned[:L], dirs=None if dirs is None else dirs[:L], report=rep)
