@@ -49,6 +49,10 @@ int pp_device_count(int* count);
  * it - kind 0 bad_alloc, 1 runtime_error, 2 a non-standard exception, 3 bad_alloc in a worker thread of a host builder,
  * 4 length_error of an over-sized vector, 5 system_error: PP_ERR_NOMEM for 0 / 3 / 4, PP_ERR_INTERNAL otherwise.  Host only. */
 int pp_debug_raise(int kind);
+/* Test hook of the library's exclusive scan (csrc/scan.hpp): the host arrays in0 (and in1, or both in1 and out1 null) of n >= 0 elements of
+ * elem_bytes (4: int32, 8: int64) are uploaded, scanned on `device` by the call the stages make - both arrays side by side in one call - and
+ * downloaded: out[i] = in[0] + ... + in[i - 1] for i <= n, so each out holds n + 1 elements, the total last. */
+int pp_debug_exclusive_scan(int device, int elem_bytes, int64_t n, const void* in0, void* out0, const void* in1, void* out1);
 /* number of intrinsic parameters of a camera model id (base/camera_models.h:189-349); -1 if unknown */
 int pp_camera_num_params(int model_id);
 /* pixel threshold -> normalised-plane threshold: BaseCameraModel::ImageToWorldThreshold

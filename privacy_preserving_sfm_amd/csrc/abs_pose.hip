@@ -26,6 +26,7 @@
 #include "pose_device.hpp"
 #include "resource_pool.hpp"
 #include "ransac_host.hpp"
+#include "scan.hpp"
 
 struct pp_pose_impl {
   int device = 0;
@@ -114,55 +115,40 @@ __device__ __forceinline__ double SquaredLineError(const double* __restrict__ P,
 // ---- K4: flat model list + LDS-tiled correspondences ----------------------------------------------
 // exclusive scan of num_models -> flat list of model slots (h*8+s), total in *total_out.  Three small launches: per-block
 // counts (block b owns the hypotheses [b, b+1) * span), a one-block scan of those, then every block scans its own span again
-// and writes its slots (one block walking a million hypotheses took 2.1 ms).
+// and writes its slots (one block walking a million hypotheses took 2.1 ms).  The scans inside a block are BlockExclusiveScan (scan.hpp).
 constexpr int kFlattenThreads = 1024;
-__device__ __forceinline__ int FlattenLocalScan(int64_t h0, int64_t h1, const int32_t* __restrict__ num_models, int* part, int* local_out) {
-  const int tid = threadIdx.x;
+// thread t of a block that owns [h0, h1) takes the span [*t0, *t1) of it; returns the models of the spans below its own, *block_total = those of all
+__device__ __forceinline__ int FlattenSpanOffset(int64_t h0, int64_t h1, const int32_t* __restrict__ num_models, int* wave_total, int64_t* t0, int64_t* t1,
+                                                 int* block_total) {
   const int64_t chunk = (h1 - h0 + kFlattenThreads - 1) / kFlattenThreads;
-  const int64_t t0 = h0 + tid * chunk, t1 = (t0 + chunk < h1) ? t0 + chunk : h1;
+  *t0 = h0 + threadIdx.x * chunk; *t1 = (*t0 + chunk < h1) ? *t0 + chunk : h1;
   int local = 0;
-  for (int64_t h = t0; h < t1; ++h) local += num_models[h];
-  part[tid] = local;
-  __syncthreads();
-  for (int off = 1; off < kFlattenThreads; off <<= 1) {   // Hillis-Steele inclusive scan
-    const int v = (tid >= off) ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  *local_out = local;
-  return part[tid] - local;          // exclusive prefix of this thread within the block
+  for (int64_t h = *t0; h < *t1; ++h) local += num_models[h];
+  return BlockExclusiveScan<kFlattenThreads, int>(local, wave_total, block_total);
 }
 __global__ __launch_bounds__(kFlattenThreads) void k_flatten_count(int64_t num_hyp, int64_t span, const int32_t* __restrict__ num_models, int32_t* __restrict__ block_sums) {
-  __shared__ int part[kFlattenThreads];
+  __shared__ int wave_total[kFlattenThreads / kWave];
   const int64_t h0 = blockIdx.x * span, h1 = (h0 + span < num_hyp) ? h0 + span : num_hyp;
-  int local;
-  FlattenLocalScan(h0, h1 > h0 ? h1 : h0, num_models, part, &local);
-  if (threadIdx.x == kFlattenThreads - 1) block_sums[blockIdx.x] = part[kFlattenThreads - 1];
+  int64_t t0, t1;
+  int total;
+  (void)FlattenSpanOffset(h0, h1 > h0 ? h1 : h0, num_models, wave_total, &t0, &t1, &total);
+  if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 __global__ __launch_bounds__(kFlattenThreads) void k_flatten_offsets(int nblocks, int32_t* __restrict__ block_sums, int32_t* __restrict__ total_out) {
-  __shared__ int part[kFlattenThreads];
+  __shared__ int wave_total[kFlattenThreads / kWave];
   const int tid = threadIdx.x;
-  const int v0 = tid < nblocks ? block_sums[tid] : 0;
-  part[tid] = v0;
-  __syncthreads();
-  for (int off = 1; off < kFlattenThreads; off <<= 1) {
-    const int v = (tid >= off) ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  if (tid < nblocks) block_sums[tid] = part[tid] - v0;     // exclusive
-  if (tid == kFlattenThreads - 1) *total_out = part[kFlattenThreads - 1];
+  int total;
+  const int below = BlockExclusiveScan<kFlattenThreads, int>(tid < nblocks ? block_sums[tid] : 0, wave_total, &total);
+  if (tid < nblocks) block_sums[tid] = below;
+  if (tid == 0) *total_out = total;
 }
 __global__ __launch_bounds__(kFlattenThreads) void k_flatten_fill(int64_t num_hyp, int64_t span, const int32_t* __restrict__ num_models,
                                                                   const int32_t* __restrict__ block_offsets, int32_t* __restrict__ flat) {
-  __shared__ int part[kFlattenThreads];
+  __shared__ int wave_total[kFlattenThreads / kWave];
   const int64_t h0 = blockIdx.x * span, h1 = (h0 + span < num_hyp) ? h0 + span : num_hyp;
-  int local;
-  int pos = block_offsets[blockIdx.x] + FlattenLocalScan(h0, h1 > h0 ? h1 : h0, num_models, part, &local);
-  const int64_t chunk = ((h1 > h0 ? h1 : h0) - h0 + kFlattenThreads - 1) / kFlattenThreads;
-  const int64_t t0 = h0 + threadIdx.x * chunk, t1 = (t0 + chunk < h1) ? t0 + chunk : h1;
+  int64_t t0, t1;
+  int total;
+  int pos = block_offsets[blockIdx.x] + FlattenSpanOffset(h0, h1 > h0 ? h1 : h0, num_models, wave_total, &t0, &t1, &total);
   for (int64_t h = t0; h < t1; ++h) {
     const int nm = num_models[h];
     for (int sidx = 0; sidx < nm; ++sidx) flat[pos++] = (int32_t)(h * 8 + sidx);

@@ -6,11 +6,8 @@
 // pass B (the out-of-config track elements of the listed points, point by point in the order given, each track in track order).
 // K16 k_bundle_lines        one lane per line: flag[l] = the line is an observation of pass A; an integer atomicAdd into count_a[point]; the norm test of
 //                           :373 with an integer atomicMin of the line number for bad_line.
-//     k_bundle_scan         exclusive int scan: one workgroup per scan, each thread a contiguous span.  Scanned are the flags of pass A over L, the counts of
-//                           pass B over the listed points, and the two first-appearance flag arrays over M, side by side in one launch.  Up to 4096
-//                           elements it takes the array itself; a longer one goes in tiles of 1024: k_bundle_tile_sums (one workgroup per tile),
-//                           k_bundle_scan over the tile sums, k_bundle_tile_scan (each workgroup scans its tile from its offset: four consecutive
-//                           elements per thread, a shuffle scan per wavefront, the wavefronts' totals through LDS).
+//     LaunchExclusiveScan   (scan.hpp) the exclusive int scans: the flags of pass A over L, the counts of pass B over the listed points, and the two
+//                           first-appearance flag arrays over M as two jobs of one call, side by side in the same launches.
 //     k_bundle_tracks       <fill = false> counts, <fill = true> writes.  ONE WAVEFRONT PER LISTED POINT: a point whose count_a equals its track length is
 //                           skipped; of the others the track is walked in 64-element chunks in track order, a ballot ranks the elements whose image is
 //                           not in the config.
@@ -25,6 +22,7 @@
 #include <cstring>
 
 #include "bundle_setup_replay.hpp"
+#include "scan.hpp"
 #include "tracks_device.hpp"
 
 namespace ppsfm {
@@ -67,89 +65,6 @@ __global__ __launch_bounds__(256) void k_bundle_lines(TrackDev d, BundleArgs a) 
   atomicAdd(&a.count_a[p], 1);
   const double la = d.lines[3 * l], lb = d.lines[3 * l + 1];
   if (fabs(hypot(la, lb) - 1.0) > 1e-6) atomicMin(a.bad_line, (int)l);
-}
-
-constexpr int kBundleScanThreads = 1024;
-
-// out[i] = sum of in[0 .. i), out[n] = the sum of all: one workgroup per scan, thread t the span [t * chunk, (t + 1) * chunk).  A grid of two runs two
-// independent scans of the same length side by side (workgroup 1 takes in1 / out1).
-__global__ __launch_bounds__(kBundleScanThreads) void k_bundle_scan(int64_t n, const int32_t* __restrict__ in0, int32_t* __restrict__ out0,
-                                                                    const int32_t* __restrict__ in1, int32_t* __restrict__ out1) {
-  __shared__ int32_t part[kBundleScanThreads];
-  const int tid = threadIdx.x;
-  const int32_t* __restrict__ in = blockIdx.x == 0 ? in0 : in1;
-  int32_t* __restrict__ out = blockIdx.x == 0 ? out0 : out1;
-  const int64_t chunk = (n + kBundleScanThreads - 1) / kBundleScanThreads;
-  const int64_t t0r = (int64_t)tid * chunk;
-  const int64_t t0 = t0r < n ? t0r : n, t1 = t0 + chunk < n ? t0 + chunk : n;
-  int32_t local = 0;
-  for (int64_t i = t0; i < t1; ++i) local += in[i];
-  part[tid] = local;
-  __syncthreads();
-  for (int off = 1; off < kBundleScanThreads; off <<= 1) {      // Hillis-Steele inclusive scan
-    const int32_t v = tid >= off ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int32_t pos = part[tid] - local;
-  for (int64_t i = t0; i < t1; ++i) { const int32_t v = in[i]; out[i] = pos; pos += v; }
-  if (tid == kBundleScanThreads - 1) out[n] = part[kBundleScanThreads - 1];
-}
-
-// A longer array is scanned in tiles: every workgroup sums its tile, ONE workgroup scans the tile sums (k_bundle_scan), every workgroup scans its tile from
-// its offset.  blockIdx.y selects one of two independent scans of the same length.
-constexpr int kBundleTile = 1024;                // elements per workgroup: 256 threads x 4 consecutive ones
-constexpr int64_t kBundleDirectScan = 4096;      // up to here k_bundle_scan takes the array itself
-
-struct BundleScan {
-  const int32_t* in;      // n
-  int32_t* out;           // n + 1
-  int32_t* tile_sum;      // tiles
-  int32_t* tile_off;      // tiles + 1
-};
-
-__global__ __launch_bounds__(256) void k_bundle_tile_sums(int64_t n, BundleScan s0, BundleScan s1) {
-  __shared__ int32_t wave_sum[4];
-  const BundleScan s = blockIdx.y == 0 ? s0 : s1;
-  const int tid = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * kBundleTile;
-  int32_t v = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int64_t i = base + tid + 256 * k;
-    if (i < n) v += s.in[i];
-  }
-  v = WaveSumInt(v);
-  if ((tid & 63) == 0) wave_sum[tid >> 6] = v;
-  __syncthreads();
-  if (tid == 0) s.tile_sum[blockIdx.x] = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
-}
-
-__global__ __launch_bounds__(256) void k_bundle_tile_scan(int64_t n, int64_t tiles, BundleScan s0, BundleScan s1) {
-  __shared__ int32_t wave_total[4];
-  const BundleScan s = blockIdx.y == 0 ? s0 : s1;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int64_t i0 = (int64_t)blockIdx.x * kBundleTile + 4 * tid;
-  int32_t v[4], sum = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { v[j] = i0 + j < n ? s.in[i0 + j] : 0; sum += v[j]; }
-  int32_t inclusive = sum;      // over the threads of the wavefront
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int32_t o = __shfl_up(inclusive, off, 64);
-    if (lane >= off) inclusive += o;
-  }
-  if (lane == 63) wave_total[w] = inclusive;
-  __syncthreads();
-  int32_t pos = s.tile_off[blockIdx.x] + inclusive - sum;
-  for (int k = 0; k < w; ++k) pos += wave_total[k];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (i0 + j < n) s.out[i0 + j] = pos;
-    pos += v[j];
-  }
-  if (blockIdx.x == 0 && tid == 0) s.out[n] = s.tile_off[tiles];
 }
 
 template <bool kFill>
@@ -231,27 +146,6 @@ __global__ __launch_bounds__(256) void k_bundle_gather(TrackDev d, BundleArgs a)
 
 using namespace ppsfm;
 
-namespace {
-
-// out[i] = sum of in[0 .. i), out[n] = the total, for one array of n ints or for two side by side (in1 / out1 not null); n >= 1
-int LaunchBundleScan(CallBlocks& cb, hipStream_t s, int64_t n, const int32_t* in0, int32_t* out0, const int32_t* in1 = nullptr, int32_t* out1 = nullptr) {
-  const unsigned scans = in1 ? 2 : 1;
-  if (n <= kBundleDirectScan) {
-    hipLaunchKernelGGL(k_bundle_scan, dim3(scans), dim3(kBundleScanThreads), 0, s, n, in0, out0, in1, out1);
-    return PP_OK;
-  }
-  const int64_t tiles = (n + kBundleTile - 1) / kBundleTile;
-  BundleScan p[2] = {{in0, out0, nullptr, nullptr}, {in1, out1, nullptr, nullptr}};
-  for (unsigned k = 0; k < scans; ++k) { PP_TRY(cb.Alloc(&p[k].tile_sum, (size_t)tiles)); PP_TRY(cb.Alloc(&p[k].tile_off, (size_t)tiles + 1)); }
-  hipLaunchKernelGGL(k_bundle_tile_sums, dim3((unsigned)tiles, scans), dim3(256), 0, s, n, p[0], p[1]);
-  hipLaunchKernelGGL(k_bundle_scan, dim3(scans), dim3(kBundleScanThreads), 0, s, tiles, (const int32_t*)p[0].tile_sum, p[0].tile_off, (const int32_t*)p[1].tile_sum,
-                     p[1].tile_off);
-  hipLaunchKernelGGL(k_bundle_tile_scan, dim3((unsigned)tiles, scans), dim3(256), 0, s, n, tiles, p[0], p[1]);
-  return PP_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int pp_tracks_bundle_setup(pp_tracks_handle h, const pp_bundle_config* cfg, pp_bundle_setup_report* report, double* lines, int32_t* obs_pose,
@@ -315,13 +209,16 @@ int pp_tracks_bundle_setup(pp_tracks_handle h, const pp_bundle_config* cfg, pp_b
   PP_HIP_TRY(hipMemsetAsync(a.pos_b, 0, ((size_t)Q + 1) * sizeof(int32_t), s));
   PP_HIP_TRY(hipMemsetAsync(a.first_point, 0xFF, (size_t)P * sizeof(unsigned), s)); PP_HIP_TRY(hipMemsetAsync(a.first_image, 0xFF, (size_t)C * sizeof(unsigned), s));
   PP_TRY(Upload(a.bad_line, &none, 1, s));
+  int32_t* d_scan = nullptr;      // the scratch of both scans: they follow each other on the stream
+  PP_TRY(cb.Alloc(&d_scan, std::max(ScanScratchCount(L), ScanScratchCount(Q))));
+  const ScanJob<int32_t> scan_a{a.flag_a, a.pos_a, a.pos_a + L}, scan_b{a.listed_count, a.pos_b, a.pos_b + Q};
   // the counts: pass A over the lines, pass B over the listed points
   PP_TRY(timer.Begin());
   hipLaunchKernelGGL(k_bundle_lines, dim3(CeilDiv(L, 256)), dim3(256), 0, s, d, a);
-  PP_TRY(LaunchBundleScan(cb, s, L, a.flag_a, a.pos_a));
+  LaunchExclusiveScan(s, L, &scan_a, 1, d_scan);
   if (Q > 0) {
     hipLaunchKernelGGL(k_bundle_tracks<false>, dim3((unsigned)Q), dim3(64), 0, s, d, a);
-    PP_TRY(LaunchBundleScan(cb, s, Q, a.listed_count, a.pos_b));
+    LaunchExclusiveScan(s, Q, &scan_b, 1, d_scan);
   }
   PP_HIP_TRY(hipGetLastError());
   PP_TRY(timer.End());
@@ -343,6 +240,8 @@ int pp_tracks_bundle_setup(pp_tracks_handle h, const pp_bundle_config* cfg, pp_b
   PP_TRY(cb.Alloc(&a.lines, 3 * (size_t)M)); PP_TRY(cb.Alloc(&a.obs_pose, (size_t)M)); PP_TRY(cb.Alloc(&a.obs_point, (size_t)M));
   PP_TRY(cb.Alloc(&a.point_index, (size_t)a.point_cap)); PP_TRY(cb.Alloc(&a.point_const, (size_t)a.point_cap)); PP_TRY(cb.Alloc(&a.points, 3 * (size_t)a.point_cap));
   PP_TRY(cb.Alloc(&a.pose_image, (size_t)a.pose_cap));
+  int32_t* d_ranks = nullptr;
+  PP_TRY(cb.Alloc(&d_ranks, 2 * ScanScratchCount(M)));
   PP_HIP_TRY(hipMemsetAsync(a.obs_line, 0, (size_t)M * sizeof(int32_t), s));      // (an entry a fill left out would still name a line and a point that exist)
   PP_HIP_TRY(hipMemsetAsync(a.obs_key, 0, (size_t)M * sizeof(int32_t), s));
   const unsigned grid_m = (unsigned)CeilDiv(M, 256);
@@ -351,7 +250,8 @@ int pp_tracks_bundle_setup(pp_tracks_handle h, const pp_bundle_config* cfg, pp_b
   if (M_b > 0) hipLaunchKernelGGL(k_bundle_tracks<true>, dim3((unsigned)Q), dim3(64), 0, s, d, a);
   hipLaunchKernelGGL(k_bundle_first, dim3(grid_m), dim3(256), 0, s, d, a);
   hipLaunchKernelGGL(k_bundle_first_flags, dim3(grid_m), dim3(256), 0, s, d, a);
-  PP_TRY(LaunchBundleScan(cb, s, M, a.flag_point, a.rank_point, a.flag_image, a.rank_image));
+  const ScanJob<int32_t> ranks[2] = {{a.flag_point, a.rank_point, a.rank_point + M}, {a.flag_image, a.rank_image, a.rank_image + M}};
+  LaunchExclusiveScan(s, M, ranks, 2, d_ranks);
   hipLaunchKernelGGL(k_bundle_gather, dim3(grid_m), dim3(256), 0, s, d, a);
   PP_HIP_TRY(hipGetLastError());
   PP_TRY(timer.End());

@@ -1,4 +1,4 @@
-// Small non-kernel entry points of the C ABI: error string, defaults, camera helpers, sampler.
+// Small entry points of the C ABI: error string, defaults, camera helpers, sampler, the test hooks.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -10,6 +10,8 @@
 #include "camera_models.hpp"
 #include "common.hpp"
 #include "ransac_host.hpp"
+#include "resource_pool.hpp"
+#include "scan.hpp"
 
 namespace ppsfm {
 static thread_local char g_last_error[1024] = "";
@@ -32,6 +34,34 @@ int ApiExceptionToCode(const char* where) {
 
 using namespace ppsfm;
 
+namespace {
+
+template <typename T>
+int DebugExclusiveScan(int64_t n, const void* const* in, void* const* out, int num_jobs) {
+  DeviceBlocks blocks;
+  hipStream_t s = nullptr;
+  auto run = [&]() -> int {
+    ScanJob<T> jobs[2] = {};
+    T* scratch = nullptr;
+    for (int k = 0; k < num_jobs; ++k) {
+      T *d_in = nullptr, *d_out = nullptr;
+      PP_TRY(blocks.Put(&d_in, static_cast<const T*>(in[k]), (size_t)n, s, 1)); PP_TRY(blocks.Alloc(&d_out, (size_t)n + 1));
+      jobs[k] = ScanJob<T>{d_in, d_out, d_out + n};
+    }
+    PP_TRY(blocks.Alloc(&scratch, (size_t)num_jobs * ScanScratchCount(n)));
+    LaunchExclusiveScan(s, n, jobs, num_jobs, scratch);
+    PP_HIP_TRY(hipGetLastError());
+    for (int k = 0; k < num_jobs; ++k) PP_TRY(Download(static_cast<T*>(out[k]), (const T*)jobs[k].out, (size_t)n + 1, s));
+    return PP_OK;
+  };
+  const int rc = run();
+  const hipError_t e = hipStreamSynchronize(s);      // before the blocks go back, on every way out
+  if (rc == PP_OK) PP_HIP_TRY(e);
+  return rc;
+}
+
+}  // namespace
+
 extern "C" {
 
 const char* pp_last_error(void) { return LastError(); }
@@ -51,6 +81,24 @@ int pp_debug_raise(int kind) try {
   }
   return PP_OK;
 } PP_API_CATCH("pp_debug_raise")
+
+// Test hook of scan.hpp (tests/test_gpu_exclusive_scan.py): host arrays of n elements of elem_bytes (4: int32, 8: int64) up, LaunchExclusiveScan as the
+// stages call it - two jobs side by side when in1 / out1 are given -, n + 1 elements down into each out, the total last.
+int pp_debug_exclusive_scan(int device, int elem_bytes, int64_t n, const void* in0, void* out0, const void* in1, void* out1) try {
+  const char* where = "pp_debug_exclusive_scan";
+  PP_REQUIRE(elem_bytes == 4 || elem_bytes == 8, "%s: elem_bytes is %d, not 4 or 8", where, elem_bytes);
+  PP_REQUIRE(n >= 0 && n < 0x7FFFFFFFll, "%s: n is %lld", where, (long long)n);
+  PP_REQUIRE(out0 && (n == 0 || in0), "%s: null array", where);
+  PP_REQUIRE((in1 != nullptr) == (out1 != nullptr), "%s: the second job needs both in1 and out1", where);
+  int ndev = 0;
+  PP_HIP_TRY(hipGetDeviceCount(&ndev));
+  PP_REQUIRE(device >= 0 && device < ndev, "%s: device %d of %d", where, device, ndev);
+  PP_HIP_TRY(hipSetDevice(device));
+  const void* const in[2] = {in0, in1};
+  void* const out[2] = {out0, out1};
+  const int num_jobs = out1 ? 2 : 1;
+  return elem_bytes == 4 ? DebugExclusiveScan<int32_t>(n, in, out, num_jobs) : DebugExclusiveScan<int64_t>(n, in, out, num_jobs);
+} PP_API_CATCH("pp_debug_exclusive_scan")
 
 int pp_device_count(int* count) try {
   PP_REQUIRE(count, "pp_device_count: null");

@@ -99,6 +99,11 @@ __device__ __forceinline__ double WaveSum(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+__device__ __forceinline__ int WaveSumInt(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
 
 // The same total without the LDS crossbar (ds_bpermute: two per step and double, and four wavefronts of a workgroup queue up on
 // it): quad / half-row / row exchanges as DPP moves (VALU rate), the four row totals by v_readlane.  A different, equally fixed

@@ -9,7 +9,7 @@
 // K18b k_corr_accept   one lane per match: its pair (a binary search in match_start), accepted = valid, first on side 1 and first on side 2.
 //                      The host then reads the per-pair repeats and overwrites the flags of the pairs CorrNeedsReplay names with CorrReplayPair's.
 // K18c k_corr_count    one lane per match: the degree of both lines (atomicAdd of 1: a count) and the accepted matches per pair.
-// K18d k_scan_*        corr_start = the exclusive scan of the degrees: blocks of 2048, their totals by one workgroup, the totals added back.
+// K18d                 corr_start = the exclusive scan of the degrees, the number of entries last (LaunchExclusiveScan, scan.hpp).
 // K18e k_corr_scatter  one lane per accepted match: a slot in each line's range from an atomic cursor; (pair rank, neighbour, owner) go to the slot.
 // K18f k_corr_order    one lane per slot: its place is the number of entries of the same line with a smaller pair rank - a line has at most one neighbour
 //                      per pair, so the ranks of a list are distinct and the places a permutation.  corr_line is written in pair order whatever slots the
@@ -20,13 +20,12 @@
 
 #include "corr_graph_replay.hpp"
 #include "resource_pool.hpp"
+#include "scan.hpp"
 
 namespace ppsfm {
 
 constexpr int kCorrTile = 4096;          // line indices per LDS table of k_corr_first
 constexpr int kCorrBlock = 256;
-constexpr int kScanPerThread = 8;
-constexpr int kScanBlock = kCorrBlock * kScanPerThread;      // 2048 items per workgroup of k_scan_local
 
 struct CorrPairDev {       // one input pair, as stored
   int32_t swapped;         // the input's columns are (x2, x1)
@@ -36,12 +35,6 @@ struct CorrPairDev {       // one input pair, as stored
 };
 
 struct CorrWork { int32_t pair, tile; };
-
-__device__ __forceinline__ int CorrWaveSum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(kCorrBlock) void k_corr_first(const CorrWork* __restrict__ work, const CorrPairDev* __restrict__ plan, const int64_t* __restrict__ mstart,
                                                            const int32_t* __restrict__ matches, uint8_t* __restrict__ dup1, uint8_t* __restrict__ dup2,
@@ -78,7 +71,7 @@ __global__ __launch_bounds__(kCorrBlock) void k_corr_first(const CorrWork* __res
       if ((uint32_t)(x2 - t0) < (uint32_t)kCorrTile) { const int d = first2[x2 - t0] != i; dup2[m0 + i] = (uint8_t)d; r2 += d; }
     }
   }
-  r1 = CorrWaveSum(r1); r2 = CorrWaveSum(r2); bad = CorrWaveSum(bad);
+  r1 = WaveSumInt(r1); r2 = WaveSumInt(r2); bad = WaveSumInt(bad);
   if ((tid & 63) == 0) { atomicAdd(&red[0], r1); atomicAdd(&red[1], r2); atomicAdd(&red[2], bad); }
   __syncthreads();
   // every tile of the pair saw every match: the bad indices are counted by tile 0 alone
@@ -126,56 +119,6 @@ __global__ __launch_bounds__(kCorrBlock) void k_corr_count(int64_t num_matches, 
   }
 }
 
-// out[i] = the exclusive scan of in[0 .. n) inside blocks of kScanBlock; block_sum[b] = the block's total
-__global__ __launch_bounds__(kCorrBlock) void k_scan_local(int64_t n, const int32_t* __restrict__ in, int32_t* __restrict__ out, int32_t* __restrict__ block_sum) {
-  __shared__ int32_t part[kCorrBlock];
-  const int tid = threadIdx.x;
-  const int64_t i0 = (int64_t)blockIdx.x * kScanBlock + (int64_t)tid * kScanPerThread;
-  int32_t v[kScanPerThread], local = 0;
-#pragma unroll
-  for (int k = 0; k < kScanPerThread; ++k) { v[k] = i0 + k < n ? in[i0 + k] : 0; local += v[k]; }
-  part[tid] = local;
-  __syncthreads();
-  for (int o = 1; o < kCorrBlock; o <<= 1) {      // Hillis-Steele inclusive scan
-    const int32_t t = tid >= o ? part[tid - o] : 0;
-    __syncthreads();
-    part[tid] += t;
-    __syncthreads();
-  }
-  int32_t pos = part[tid] - local;
-#pragma unroll
-  for (int k = 0; k < kScanPerThread; ++k) { if (i0 + k < n) out[i0 + k] = pos; pos += v[k]; }
-  if (tid == kCorrBlock - 1) block_sum[blockIdx.x] = part[tid];
-}
-
-// one workgroup: block_sum[0 .. nb) to its exclusive scan in place, block_sum[nb] = the total
-__global__ __launch_bounds__(kCorrBlock) void k_scan_sums(int32_t nb, int32_t* __restrict__ block_sum) {
-  __shared__ int32_t part[kCorrBlock];
-  const int tid = threadIdx.x;
-  const int32_t chunk = (nb + kCorrBlock - 1) / kCorrBlock;
-  const int32_t t0 = min(tid * chunk, nb), t1 = min(t0 + chunk, nb);
-  int32_t local = 0;
-  for (int32_t b = t0; b < t1; ++b) local += block_sum[b];
-  part[tid] = local;
-  __syncthreads();
-  for (int o = 1; o < kCorrBlock; o <<= 1) {
-    const int32_t t = tid >= o ? part[tid - o] : 0;
-    __syncthreads();
-    part[tid] += t;
-    __syncthreads();
-  }
-  int32_t pos = part[tid] - local;
-  for (int32_t b = t0; b < t1; ++b) { const int32_t c = block_sum[b]; block_sum[b] = pos; pos += c; }
-  if (tid == kCorrBlock - 1) block_sum[nb] = part[tid];
-}
-
-// out[0 .. n) gets its block's offset, out[n] the total
-__global__ __launch_bounds__(kCorrBlock) void k_scan_add(int64_t n, int32_t nb, int32_t* __restrict__ out, const int32_t* __restrict__ block_sum) {
-  const int64_t i = (int64_t)blockIdx.x * kCorrBlock + threadIdx.x;
-  if (i < n) out[i] += block_sum[i / kScanBlock];
-  else if (i == n) out[i] = block_sum[nb];
-}
-
 __global__ __launch_bounds__(kCorrBlock) void k_corr_scatter(int64_t num_matches, int64_t num_entries, const CorrPairDev* __restrict__ plan,
                                                              const int32_t* __restrict__ matches, const int32_t* __restrict__ pair_of,
                                                              const uint8_t* __restrict__ accepted, int32_t* __restrict__ cursor, int32_t* __restrict__ slot_rank,
@@ -211,7 +154,7 @@ __global__ __launch_bounds__(kCorrBlock) void k_corr_image(const int32_t* __rest
   __syncthreads();
   int n = 0;
   for (int32_t l = l0 + tid; l < l1; l += kCorrBlock) n += corr_start[l + 1] > corr_start[l];
-  n = CorrWaveSum(n);
+  n = WaveSumInt(n);
   if ((tid & 63) == 0) atomicAdd(&red, n);
   __syncthreads();
   if (tid == 0) { num_observations[blockIdx.x] = red; num_correspondences[blockIdx.x] = corr_start[l1] - corr_start[l0]; }
@@ -297,7 +240,7 @@ int pp_corr_graph_create(int32_t num_images, const int32_t* num_lines, int devic
     PP_REQUIRE(num_lines[k] >= 0, "%s: image %d has a negative line count", where, k);
     total += num_lines[k];
   }
-  PP_REQUIRE(total < 0x7FFFFFFFll - kScanBlock, "%s: too many lines", where);
+  PP_REQUIRE(total < 0x7FFFFFFFll - kScanTile, "%s: too many lines", where);
   int ndev = 0;
   PP_HIP_TRY(hipGetDeviceCount(&ndev));
   PP_REQUIRE(device >= 0 && device < ndev, "%s: device %d of %d", where, device, ndev);
@@ -351,16 +294,15 @@ int pp_corr_graph_build(pp_corr_graph_handle h, int32_t min_num_matches, int64_t
   CorrPairDev* d_plan = nullptr;
   CorrWork* d_work = nullptr;
   int64_t* d_mstart = nullptr;
-  int32_t *d_matches = nullptr, *d_cls = nullptr, *d_pair_of = nullptr, *d_degree = nullptr, *d_pair_acc = nullptr, *d_block_sum = nullptr, *d_cursor = nullptr;
+  int32_t *d_matches = nullptr, *d_cls = nullptr, *d_pair_of = nullptr, *d_degree = nullptr, *d_pair_acc = nullptr, *d_scan = nullptr, *d_cursor = nullptr;
   int32_t *d_slot_rank = nullptr, *d_slot_line = nullptr, *d_slot_owner = nullptr, *d_img_obs = nullptr, *d_img_corr = nullptr;
   uint8_t *d_dup1 = nullptr, *d_dup2 = nullptr, *d_acc = nullptr;
-  const int32_t nb = CeilDiv(L, kScanBlock);
   PP_TRY(cb.Put(&d_plan, dev.data(), dev.size())); PP_TRY(cb.Put(&d_work, work.data(), work.size()));
   PP_TRY(cb.Put(&d_mstart, match_start, (size_t)num_pairs + 1)); PP_TRY(cb.Put(&d_matches, matches, 2 * (size_t)M));
   PP_TRY(cb.Zeros(&d_cls, 3 * (size_t)num_pairs)); PP_TRY(cb.Zeros(&d_pair_acc, (size_t)num_pairs));
   PP_TRY(cb.Zeros(&d_dup1, (size_t)M)); PP_TRY(cb.Zeros(&d_dup2, (size_t)M)); PP_TRY(cb.Zeros(&d_acc, (size_t)M));
   PP_TRY(cb.Alloc(&d_pair_of, (size_t)M));
-  PP_TRY(cb.Zeros(&d_degree, (size_t)L + 1)); PP_TRY(cb.Alloc(&d_block_sum, (size_t)nb + 1)); PP_TRY(cb.Alloc(&d_cursor, (size_t)L + 1));
+  PP_TRY(cb.Zeros(&d_degree, (size_t)L + 1)); PP_TRY(cb.Alloc(&d_scan, ScanScratchCount(L))); PP_TRY(cb.Alloc(&d_cursor, (size_t)L + 1));
   PP_TRY(cb.Alloc(&d_img_obs, (size_t)h->num_images)); PP_TRY(cb.Alloc(&d_img_corr, (size_t)h->num_images));
   PP_TRY(h->blocks.Alloc(&fresh.start, (size_t)L + 1));
 
@@ -409,9 +351,8 @@ int pp_corr_graph_build(pp_corr_graph_handle h, int32_t min_num_matches, int64_t
   if (M > 0)
     hipLaunchKernelGGL(k_corr_count, dim3(CeilDiv(M, kCorrBlock)), dim3(kCorrBlock), 0, s, M, (const CorrPairDev*)d_plan, (const int32_t*)d_matches,
                        (const int32_t*)d_pair_of, (const uint8_t*)d_acc, d_degree, d_pair_acc);
-  if (nb > 0) hipLaunchKernelGGL(k_scan_local, dim3((unsigned)nb), dim3(kCorrBlock), 0, s, L, (const int32_t*)d_degree, fresh.start, d_block_sum);
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kCorrBlock), 0, s, nb, d_block_sum);
-  hipLaunchKernelGGL(k_scan_add, dim3(CeilDiv(L + 1, kCorrBlock)), dim3(kCorrBlock), 0, s, L, nb, fresh.start, (const int32_t*)d_block_sum);
+  const ScanJob<int32_t> degrees{d_degree, fresh.start, fresh.start + L};
+  LaunchExclusiveScan(s, L, &degrees, 1, d_scan);
   PP_HIP_TRY(hipGetLastError());
   PP_HIP_TRY(hipEventRecord(h->ev1, s));
   std::vector<int32_t> pair_acc((size_t)num_pairs, 0);

@@ -11,7 +11,7 @@
 //                        and keeps a triple when the four images (the line's and the three neighbours') are pairwise different.  The count form adds up an
 //                        int64 per line; the fill form writes the four line numbers ORDERED BY IMAGE INDEX as one 16-byte record at offset[line] + a rank
 //                        handed out by an LDS counter (the order inside a line's span is free: the records are sorted next).
-//    k_initial_scan      exclusive int64 scan of the counts: one workgroup, each thread a contiguous span.
+//                        The counts are scanned as int64 (LaunchExclusiveScan, scan.hpp), the total last.
 //    k_initial_keys      one lane per unique record: the set key (initial_sets_replay.hpp) from line_image and the alignment flag of its first line.
 // Between them rocPRIM's device primitives: merge_sort of the records (lexicographic over the four line numbers), unique, radix_sort_pairs by set key
 // (stable: inside a set and class the lexicographic order stays - the order in which the reference hands the lines to the solver), run_length_encode.
@@ -24,6 +24,7 @@
 #include <rocprim/device/device_select.hpp>
 
 #include "initial_sets_replay.hpp"
+#include "scan.hpp"
 #include "tracks_device.hpp"
 
 namespace ppsfm {
@@ -130,30 +131,6 @@ __global__ __launch_bounds__(64) void k_initial_tracks(TrackDev d, InitArgs a) {
   }
 }
 
-constexpr int kInitScanThreads = 1024;
-
-// out[i] = sum of in[0 .. i), out[n] = the sum of all: one workgroup, thread t the span [t * chunk, (t + 1) * chunk)
-__global__ __launch_bounds__(kInitScanThreads) void k_initial_scan(int n, const int64_t* __restrict__ in, int64_t* __restrict__ out) {
-  __shared__ int64_t part[kInitScanThreads];
-  const int tid = threadIdx.x;
-  const int chunk = (n + kInitScanThreads - 1) / kInitScanThreads;
-  const int64_t t0r = (int64_t)tid * chunk;
-  const int t0 = t0r < n ? (int)t0r : n, t1 = t0 + chunk < n ? t0 + chunk : n;
-  int64_t local = 0;
-  for (int i = t0; i < t1; ++i) local += in[i];
-  part[tid] = local;
-  __syncthreads();
-  for (int off = 1; off < kInitScanThreads; off <<= 1) {      // Hillis-Steele inclusive scan
-    const int64_t v = tid >= off ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int64_t pos = part[tid] - local;
-  for (int i = t0; i < t1; ++i) { const int64_t v = in[i]; out[i] = pos; pos += v; }
-  if (tid == kInitScanThreads - 1) out[n] = part[kInitScanThreads - 1];
-}
-
 __global__ __launch_bounds__(256) void k_initial_keys(unsigned int n, const InitRecord* __restrict__ rec, const int32_t* __restrict__ line_image,
                                                       const uint8_t* __restrict__ line_aligned, uint64_t* __restrict__ key) {
   const unsigned int t = blockIdx.x * 256u + threadIdx.x;
@@ -253,16 +230,18 @@ int pp_tracks_find_initial_sets(pp_tracks_handle h, const pp_init_sets_options* 
   InitArgs a{};
   a.N = N;
   int32_t* d_work = nullptr;
-  int64_t *d_goff = nullptr, *d_offset = nullptr;
+  int64_t *d_goff = nullptr, *d_offset = nullptr, *d_scan = nullptr;
   uint8_t *d_aligned = nullptr, *d_subset = nullptr;
   PP_TRY(cb.Put(&d_work, work.data(), (size_t)N)); PP_TRY(cb.Put(&d_goff, goff.data(), (size_t)N));
   PP_TRY(cb.Put(&d_aligned, line_aligned, (size_t)h->L));
   if (image_subset) PP_TRY(cb.Put(&d_subset, image_subset, (size_t)C));
   PP_TRY(cb.Alloc(&a.glist, 2 * (size_t)gtotal)); PP_TRY(cb.Alloc(&a.count, (size_t)N)); PP_TRY(cb.Alloc(&d_offset, (size_t)N + 1));
+  PP_TRY(cb.Alloc(&d_scan, ScanScratchCount(N)));
   a.work_line = d_work; a.glist_off = d_goff; a.line_aligned = d_aligned; a.subset = d_subset; a.offset = d_offset;
   PP_TRY(timer.Begin());
   hipLaunchKernelGGL(k_initial_tracks<false>, dim3((unsigned)N), dim3(64), 0, s, d, a);
-  hipLaunchKernelGGL(k_initial_scan, dim3(1), dim3(kInitScanThreads), 0, s, N, (const int64_t*)a.count, d_offset);
+  const ScanJob<int64_t> offsets{a.count, d_offset, d_offset + N};
+  LaunchExclusiveScan(s, N, &offsets, 1, d_scan);
   PP_HIP_TRY(hipGetLastError());
   PP_TRY(timer.End());
   int64_t total = 0;

@@ -35,12 +35,6 @@ struct LfImageDev {
 
 struct LfTileDev { int32_t image, first; };          // keypoints first .. first + 63 of the image
 
-__device__ __forceinline__ int LfWaveSum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(kLfBlock) void k_lf_select(const int32_t* __restrict__ todo, const LfImageDev* __restrict__ images, uint64_t* __restrict__ threshold) {
   __shared__ int32_t part[kLfWaves][16];
   const int32_t img = todo[blockIdx.x];
@@ -60,7 +54,7 @@ __global__ __launch_bounds__(kLfBlock) void k_lf_select(const int32_t* __restric
       for (int b = 0; b < 16; ++b) cnt[b] += d == b;
     }
 #pragma unroll
-    for (int b = 0; b < 16; ++b) cnt[b] = LfWaveSum(cnt[b]);
+    for (int b = 0; b < 16; ++b) cnt[b] = WaveSumInt(cnt[b]);
     if ((tid & (kWave - 1)) == 0) {
 #pragma unroll
       for (int b = 0; b < 16; ++b) part[tid / kWave][b] = cnt[b];

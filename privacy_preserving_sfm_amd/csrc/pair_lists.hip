@@ -7,7 +7,7 @@
 // tracks for 0.7 M entries, memory-bound on one to eight host threads).  Here, with the by-point lists already uploaded:
 //   k_pl_count    a thread per entry of the by-point lists: its point's other observers with an image <= its own -> one atomic add per entry into a
 //                 C x C table of list lengths (low contention: the entries of one list come from different points)
-//   scan          exclusive scan of the table = the lists' starts (three launches: per-span sums, their scan, the spans again)
+//   scan          exclusive scan of the table = the lists' starts (LaunchExclusiveScan, scan.hpp)
 //   k_pl_fill     the same walk: position = atomic add on the list's fill counter -> (oi, oj) written into the list - in arrival order
 //   k_pl_rank     a thread per ENTRY: its rank among the entries of its list by (oi, oj) (the pairs of a list are distinct) = its place in the sorted list,
 //                 written to a second buffer - which makes the result independent of the atomics' order (a thread per LIST with an insertion sort took 0.8 ms
@@ -23,71 +23,12 @@
 
 #include "ba_impl.hpp"
 #include "resource_pool.hpp"
+#include "scan.hpp"
 
 namespace ppsfm {
 namespace {
 
-constexpr int kScanThreads = 1024;
 constexpr int kMaxSortedList = 2048;
-
-// exclusive scan of n int32 (n <= kScanThreads * kScanThreads * span): per-span sums, their scan, the spans again
-__device__ __forceinline__ int SpanLocalScan(int64_t i0, int64_t i1, const int32_t* __restrict__ in, int* part, int* local_out) {
-  const int tid = threadIdx.x;
-  const int64_t chunk = (i1 - i0 + kScanThreads - 1) / kScanThreads;
-  const int64_t t0 = i0 + tid * chunk, t1 = (t0 + chunk < i1) ? t0 + chunk : i1;
-  int local = 0;
-  for (int64_t i = t0; i < t1; ++i) local += in[i];
-  part[tid] = local;
-  __syncthreads();
-  for (int off = 1; off < kScanThreads; off <<= 1) {   // Hillis-Steele inclusive scan
-    const int v = (tid >= off) ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  *local_out = local;
-  return part[tid] - local;
-}
-__global__ __launch_bounds__(kScanThreads) void k_pl_scan_sums(int64_t n, int64_t span, const int32_t* __restrict__ in, int32_t* __restrict__ block_sums) {
-  __shared__ int part[kScanThreads];
-  const int64_t i0 = blockIdx.x * span, i1 = (i0 + span < n) ? i0 + span : n;
-  int local;
-  (void)SpanLocalScan(i0, i1 > i0 ? i1 : i0, in, part, &local);
-  if (threadIdx.x == kScanThreads - 1) block_sums[blockIdx.x] = part[kScanThreads - 1];
-}
-__global__ __launch_bounds__(kScanThreads) void k_pl_scan_offsets(int nblocks, int32_t* __restrict__ block_sums, int32_t* __restrict__ total_out) {
-  __shared__ int part[kScanThreads];
-  const int tid = threadIdx.x;
-  const int v0 = tid < nblocks ? block_sums[tid] : 0;
-  part[tid] = v0;
-  __syncthreads();
-  for (int off = 1; off < kScanThreads; off <<= 1) {
-    const int v = (tid >= off) ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  if (tid < nblocks) block_sums[tid] = part[tid] - v0;     // exclusive
-  if (tid == kScanThreads - 1) *total_out = part[kScanThreads - 1];
-}
-__global__ __launch_bounds__(kScanThreads) void k_pl_scan_write(int64_t n, int64_t span, const int32_t* __restrict__ in, const int32_t* __restrict__ block_offsets,
-                                                                int32_t* __restrict__ out) {
-  __shared__ int part[kScanThreads];
-  const int64_t i0 = blockIdx.x * span, i1r = (i0 + span < n) ? i0 + span : n, i1 = i1r > i0 ? i1r : i0;
-  int local;
-  int pos = block_offsets[blockIdx.x] + SpanLocalScan(i0, i1, in, part, &local);
-  const int64_t chunk = (i1 - i0 + kScanThreads - 1) / kScanThreads;
-  const int64_t t0 = i0 + threadIdx.x * chunk, t1 = (t0 + chunk < i1) ? t0 + chunk : i1;
-  for (int64_t i = t0; i < t1; ++i) { const int v = in[i]; out[i] = pos; pos += v; }
-}
-struct ScanScratch { int32_t* block_sums; int32_t* total; };
-void ExclusiveScan(const int32_t* in, int32_t* out, int64_t n, const ScanScratch& sc, hipStream_t s) {
-  const int nblocks = (int)std::min<int64_t>(kScanThreads, (n + 4095) / 4096);
-  const int64_t span = (n + nblocks - 1) / nblocks;
-  hipLaunchKernelGGL(k_pl_scan_sums, dim3(nblocks), dim3(kScanThreads), 0, s, n, span, in, sc.block_sums);
-  hipLaunchKernelGGL(k_pl_scan_offsets, dim3(1), dim3(kScanThreads), 0, s, nblocks, sc.block_sums, sc.total);
-  hipLaunchKernelGGL(k_pl_scan_write, dim3(nblocks), dim3(kScanThreads), 0, s, n, span, in, (const int32_t*)sc.block_sums, out);
-}
 
 // the image of every entry of the by-point lists, -1 for a constant pose or a constant point (such entries take part in no list)
 __global__ __launch_bounds__(256) void k_pl_images(int64_t M, const int32_t* __restrict__ pt_obs, const int32_t* __restrict__ obs_pose, const int32_t* __restrict__ obs_point,
@@ -209,22 +150,22 @@ int BuildPairListsOnDevice(int C, int64_t M, const int32_t* d_pt_start, const in
   DeviceBlocks scratch;      // the call's own blocks; the sorted lists are `owner`'s from the moment they exist
   int32_t *pt_pose, *count, *fill, *start, *flag, *small;
   PP_TRY(scratch.Alloc(&pt_pose, (size_t)M)); PP_TRY(scratch.Alloc(&count, (size_t)K)); PP_TRY(scratch.Alloc(&fill, (size_t)K)); PP_TRY(scratch.Alloc(&start, (size_t)K + 1));
-  PP_TRY(scratch.Alloc(&flag, (size_t)K)); PP_TRY(scratch.Alloc(&small, kScanThreads + 8));
-  ScanScratch sc{small, small + kScanThreads};
-  int32_t* d_max = small + kScanThreads + 1;
-  int32_t* d_lists = small + kScanThreads + 2;
+  const size_t scan_count = ScanScratchCount(K);      // `small`: the scratch of the two scans, then the total of entries, the longest list, the number of lists
+  PP_TRY(scratch.Alloc(&flag, (size_t)K)); PP_TRY(scratch.Alloc(&small, scan_count + 3));
+  int32_t *d_total = small + scan_count, *d_max = d_total + 1, *d_lists = d_total + 2;
   auto fail = [&](hipError_t e) { SetLastError("pair lists on the device: %s", hipGetErrorString(e)); return PP_ERR_HIP; };
   hipError_t e;
   if ((e = hipMemsetAsync(count, 0, sizeof(int32_t) * K, s)) != hipSuccess) return fail(e);
   if ((e = hipMemsetAsync(fill, 0, sizeof(int32_t) * K, s)) != hipSuccess) return fail(e);
-  if ((e = hipMemsetAsync(small, 0, sizeof(int32_t) * (kScanThreads + 8), s)) != hipSuccess) return fail(e);
+  if ((e = hipMemsetAsync(d_total, 0, sizeof(int32_t) * 3, s)) != hipSuccess) return fail(e);
   const dim3 gm((unsigned)((M + 255) / 256)), gk((unsigned)((K + 255) / 256));
   hipLaunchKernelGGL(k_pl_images, gm, dim3(256), 0, s, M, d_pt_obs, d_obs_pose, d_obs_point, d_pose_const, d_point_const, pt_pose);
   hipLaunchKernelGGL(k_pl_walk<false>, gm, dim3(256), 0, s, M, C, d_pt_start, d_pt_obs, d_obs_point, (const int32_t*)pt_pose, count, (const int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
-  ExclusiveScan(count, start, K, sc, s);
+  const ScanJob<int32_t> starts{count, start, d_total};
+  LaunchExclusiveScan(s, K, &starts, 1, small);
   hipLaunchKernelGGL(k_pl_max, dim3(256), dim3(256), 0, s, K, (const int32_t*)count, d_max);
   int32_t host2[2] = {0, 0};      // total entries, longest list
-  if ((e = hipMemcpyAsync(&host2[0], sc.total, sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);
+  if ((e = hipMemcpyAsync(&host2[0], d_total, sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);
   if ((e = hipMemcpyAsync(&host2[1], d_max, sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e);
   const int64_t E = host2[0];
@@ -240,8 +181,8 @@ int BuildPairListsOnDevice(int C, int64_t M, const int32_t* d_pt_start, const in
                      (const long long*)arrival, (long long*)entries);
   hipLaunchKernelGGL(k_pl_flags, gk, dim3(256), 0, s, K, (const int32_t*)count, flag);
   // non-empty lists in key order: rank = exclusive scan of the flags (into `fill`, free again), their number in d_lists
-  ScanScratch sc2{small, d_lists};
-  ExclusiveScan(flag, fill, K, sc2, s);
+  const ScanJob<int32_t> ranks{flag, fill, d_lists};
+  LaunchExclusiveScan(s, K, &ranks, 1, small);
   int32_t lists = 0;
   if ((e = hipMemcpyAsync(&lists, d_lists, sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e);
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e);

@@ -16,8 +16,7 @@
 //                         flagged, and no earlier kept neighbour OF THIS LINE has the same point: inside a chunk DropLaterDuplicates, across chunks
 //                         the list of accepted points - in LDS up to kRegList entries, for a longer neighbour list in a segment of global memory
 //                         the host sized by that list (it cannot overflow).  The count form also says whether the line is visible.
-//     k_register_scan     exclusive scan of the counts in ascending line index: one workgroup, each thread a contiguous span (an image has thousands
-//                         of lines at most: k_pl_scan_*'s three launches are for millions of entries).
+//                         The counts are scanned in ascending line index (LaunchExclusiveScan, scan.hpp).
 //                         The fill form writes, at offset[line] + rank, the pair (line, point), the six SoA streams and the aligned flag straight into
 //                         the buffers of a pose handle (pose_device.hpp): only the pair list travels to the host.
 // No kernel here waits for another workgroup.
@@ -25,6 +24,7 @@
 
 #include "pose_device.hpp"
 #include "register_replay.hpp"
+#include "scan.hpp"
 #include "tracks_device.hpp"
 
 namespace ppsfm {
@@ -128,30 +128,6 @@ __global__ __launch_bounds__(64) void k_register_corrs(TrackDev d, RegArgs a) {
       if (any) atomicAdd(a.visible, 1);
     }
   }
-}
-
-constexpr int kRegScanThreads = 1024;
-
-// out[i] = sum of in[0 .. i), *total = the sum of all: one workgroup, thread t the span [t * chunk, (t + 1) * chunk)
-__global__ __launch_bounds__(kRegScanThreads) void k_register_scan(int n, const int32_t* __restrict__ in, int32_t* __restrict__ out, int32_t* __restrict__ total) {
-  __shared__ int part[kRegScanThreads];
-  const int tid = threadIdx.x;
-  const int chunk = (n + kRegScanThreads - 1) / kRegScanThreads;
-  const int64_t t0r = (int64_t)tid * chunk;
-  const int t0 = t0r < n ? (int)t0r : n, t1 = t0 + chunk < n ? t0 + chunk : n;
-  int local = 0;
-  for (int i = t0; i < t1; ++i) local += in[i];
-  part[tid] = local;
-  __syncthreads();
-  for (int off = 1; off < kRegScanThreads; off <<= 1) {      // Hillis-Steele inclusive scan
-    const int v = tid >= off ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int pos = part[tid] - local;
-  for (int i = t0; i < t1; ++i) { const int v = in[i]; out[i] = pos; pos += v; }
-  if (tid == kRegScanThreads - 1) *total = part[kRegScanThreads - 1];
 }
 
 }  // namespace ppsfm
@@ -272,17 +248,19 @@ int pp_tracks_estimate_image_pose(pp_tracks_handle h, const pp_next_image_option
   d.points = d_points;
   RegArgs a{};
   a.N = N;
-  int32_t *d_work = nullptr, *d_offset = nullptr, *d_tot = nullptr;
+  int32_t *d_work = nullptr, *d_offset = nullptr, *d_tot = nullptr, *d_scan = nullptr;
   int64_t* d_goff = nullptr;
   uint8_t* d_aligned = nullptr;
   PP_TRY(cb.Put(&d_work, work.data(), (size_t)N)); PP_TRY(cb.Put(&d_goff, goff.data(), (size_t)N));
   PP_TRY(cb.Alloc(&a.glist, (size_t)gtotal)); PP_TRY(cb.Alloc(&a.count, (size_t)N)); PP_TRY(cb.Alloc(&d_offset, (size_t)N)); PP_TRY(cb.Alloc(&d_tot, 2));
+  PP_TRY(cb.Alloc(&d_scan, ScanScratchCount(N)));
   if (line_aligned) PP_TRY(cb.Put(&d_aligned, line_aligned, (size_t)h->L));
   a.work_line = d_work; a.glist_off = d_goff; a.visible = d_tot + 1; a.offset = d_offset; a.line_aligned = d_aligned;
   PP_HIP_TRY(hipMemsetAsync(d_tot, 0, 2 * sizeof(int32_t), s));
   PP_TRY(timer.Begin());
   hipLaunchKernelGGL(k_register_corrs<false>, dim3((unsigned)N), dim3(64), 0, s, d, a);
-  hipLaunchKernelGGL(k_register_scan, dim3(1), dim3(kRegScanThreads), 0, s, N, (const int32_t*)a.count, d_offset, d_tot);
+  const ScanJob<int32_t> offsets{a.count, d_offset, d_tot};
+  LaunchExclusiveScan(s, N, &offsets, 1, d_scan);
   PP_HIP_TRY(hipGetLastError());
   PP_TRY(timer.End());
   int32_t tot[2] = {0, 0};      // entries, visible lines

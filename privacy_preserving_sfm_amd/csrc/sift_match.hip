@@ -16,13 +16,14 @@
 // K17b k_sift_decide   one lane per (pair, direction, feature): best >= 1, best >= d_min, min(second, 2^18) <= table[min(best, 2^18) - d_min]; writes the
 //                      one-way match (or -1) over best_j.
 // K17c k_sift_emit     one workgroup per pair: the cross-check, a count, then - after k_sift_offsets, one workgroup, has applied min_num_matches and scanned
-//                      the counts of the batch - the same ordered compaction again (a workgroup scan over i in chunks of 256) writing (i, j) behind the
+//                      the counts of the batch (BlockExclusiveScan, scan.hpp) - the same ordered compaction again (a workgroup scan over i in chunks of 256) writing (i, j) behind the
 //                      pair's offset.
 // No atomics, no kernel waits for another workgroup: the output does not depend on the schedule.
 #include <chrono>
 #include <cstring>
 
 #include "resource_pool.hpp"
+#include "scan.hpp"
 #include "sift_match_replay.hpp"
 
 namespace ppsfm {
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(256) void k_sift_emit(const SiftPair* __restrict__ 
 // one workgroup: count[p] < min_num_matches -> 0 (emptied counts those that had any), start = the exclusive scan of the counts, start[n] the total
 __global__ __launch_bounds__(256) void k_sift_offsets(int32_t n, int32_t* __restrict__ count, int32_t min_num_matches, int32_t* __restrict__ start,
                                                       int32_t* __restrict__ emptied) {
-  __shared__ int32_t part[256], gone[256];
+  __shared__ int32_t wave_total[4], gone[4];
   const int tid = threadIdx.x;
   const int32_t chunk = (n + 255) / 256;
   const int32_t t0 = min(tid * chunk, n), t1 = min(t0 + chunk, n);
@@ -208,17 +209,12 @@ __global__ __launch_bounds__(256) void k_sift_offsets(int32_t n, int32_t* __rest
     if (c < min_num_matches) { dropped += c > 0; c = 0; count[p] = 0; }
     local += c;
   }
-  part[tid] = local; gone[tid] = dropped;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {      // Hillis-Steele inclusive scan
-    const int32_t v = tid >= o ? part[tid - o] : 0, g = tid >= o ? gone[tid - o] : 0;
-    __syncthreads();
-    part[tid] += v; gone[tid] += g;
-    __syncthreads();
-  }
-  int32_t pos = part[tid] - local;
+  dropped = WaveSumInt(dropped);
+  if ((tid & 63) == 0) gone[tid >> 6] = dropped;      // (read behind the scan's barrier)
+  int32_t total;
+  int32_t pos = BlockExclusiveScan<256>(local, wave_total, &total);
   for (int32_t p = t0; p < t1; ++p) { start[p] = pos; pos += count[p]; }
-  if (tid == 255) { start[n] = part[255]; *emptied = gone[255]; }
+  if (tid == 0) { start[n] = total; *emptied = gone[0] + gone[1] + gone[2] + gone[3]; }
 }
 
 }  // namespace ppsfm

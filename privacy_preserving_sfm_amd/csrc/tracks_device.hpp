@@ -38,12 +38,6 @@ __device__ __forceinline__ double TrackLineError(const TrackDev& d, double X0, d
   return SquaredPixelLineError(px, py, pz, ln[0], ln[1], ln[2], d.camera_model[k], d.intr + (size_t)kCamStride * k, d.cam_size + 2 * k);
 }
 
-__device__ __forceinline__ int WaveSumInt(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // lanes whose key an earlier lane of `mask` also holds leave the mask: the first holder in lane order stays
 __device__ __forceinline__ unsigned long long DropLaterDuplicates(unsigned long long mask, int key, int lane) {
   if (__popcll(mask) < 2) return mask;

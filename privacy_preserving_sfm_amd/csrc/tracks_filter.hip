@@ -27,12 +27,6 @@ struct TrackFilterArgs {
   uint8_t* elem_flag;            // one per track element, aligned with track_start / track_line
 };
 
-__device__ __forceinline__ double WaveSumDouble(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(64) void k_track_filter(TrackDev d, TrackFilterArgs a) {
   const int p = blockIdx.x, lane = threadIdx.x;
   if (p >= d.P) return;
@@ -65,7 +59,7 @@ __global__ __launch_bounds__(64) void k_track_filter(TrackDev d, TrackFilterArgs
     non_aligned = non_aligned || __ballot(free_line) != 0;
   }
   ndel = WaveSumInt(ndel);
-  sum = WaveSumDouble(sum);
+  sum = WaveSum(sum);
   if (!non_aligned || len < 3 || ndel >= len - 3) {      // reconstruction.cc:673-689, :705-707 (a track of exactly 3 never survives)
     if (lane == 0) a.verdict[p] = kFilterDeletedByTrack;
     return;

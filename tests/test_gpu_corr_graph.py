@@ -6,7 +6,8 @@ The kernels' real edges, which the shapes straddle:
          the wave sums of k_corr_first and k_corr_image
   256    a workgroup: every kernel covers matches, entries or lines in blocks of 256; k_corr_first and k_corr_image stride a pair's matches / an image's
          lines by 256
-  2048   a block of the degree scan (k_scan_local): the edge problem has more than two blocks of lines, so block totals are scanned and added back
+  1024   a tile of the degree scan (LaunchExclusiveScan, csrc/scan.hpp): the edge problem has more than 4096 lines, so the tile sums are scanned and every
+         tile starts from its offset
   4096   the LDS first-occurrence table of k_corr_first (kCorrTile): an image of 4097 lines puts a pair on two tiles, with first occurrences and repeats
          on both sides of the tile edge
 Images of 1, 63, 64, 65 and 257 lines, one of 0 lines and one of 4097 share one problem.  A line's neighbour list has no edge of its own - k_corr_order
