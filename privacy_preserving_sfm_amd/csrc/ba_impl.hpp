@@ -32,6 +32,17 @@ constexpr int kRecStride = 24;
 __device__ __forceinline__ const double* RecT(const double* rec, size_t o) { return rec + kRecStride * o; }
 __device__ __forceinline__ const double* RecJ(const double* rec, size_t o) { return rec + kRecStride * o + 6; }
 __device__ __forceinline__ const double* RecX(const double* rec, size_t o) { return rec + kRecStride * o + 18; }
+// K1's rows of one observation: the camera-side Jacobian (2 x 6) and the point-side Jacobian (2 x 3), as 16-byte loads
+__device__ __forceinline__ void LoadJp(const double* __restrict__ Jpose, int o, double jp[12]) {
+  const double2* p = reinterpret_cast<const double2*>(Jpose + (size_t)12 * o);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { const double2 v = p[i]; jp[2 * i] = v.x; jp[2 * i + 1] = v.y; }
+}
+__device__ __forceinline__ void LoadJx(const double* __restrict__ Jpoint, int o, double jx[6]) {
+  const double2* p = reinterpret_cast<const double2*>(Jpoint + (size_t)6 * o);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { const double2 v = p[i]; jx[2 * i] = v.x; jx[2 * i + 1] = v.y; }
+}
 #endif
 // chain steps of the one-launch factorisation of a T x T tile map (closed under fill-in): the block columns on the longest dependency path when its
 // elimination tree has independent sub-trees (several chains, cholesky.hip), T otherwise; *chains (may be null): the number of chains
@@ -253,6 +264,24 @@ int BaAssembleUndamped(pp_ba_impl* h, const pp_ba_options* o, bool evaluate);
 // the group exchange of a point-sharded handle (ba_solver.hip): true inside a group; in-place reduction of `count` doubles on the handle's stream
 bool BaInGroup(const pp_ba_impl* h);
 int BaGroupReduce(pp_ba_impl* h, double* ptr, int64_t count, int op);
+// one exchange = Begin .. End: several BaGroupReduce calls in between become ONE RCCL launch (no-ops with a host callback).  An error return in
+// between must not leave the ncclGroupStart open (the communicator would be unusable for every later call): the scope closes it on every path
+struct GroupScope {
+  pp_ba_impl* h; bool open = false;
+  explicit GroupScope(pp_ba_impl* hh) : h(hh) {}
+  int Begin();
+  int End();
+  ~GroupScope();
+};
+// The tile pattern of a block-sparse reduced system is built from THIS rank's pair lists.  In a point-sharded group the all-reduced
+// system has the union of every rank's co-visibility: a tile whose shared points all live on another rank is non-zero after the
+// exchange, and a rank that skipped it would factor a different matrix than its peers (replicated poses diverging between ranks).
+// So the block-sparse path is only taken outside a group; attaching / detaching a communicator or callback switches it.
+// (inside a point-sharded group only when the tile map is the group's: built from the union co-visibility every rank was given, pp_ba_problem_desc::covisibility)
+inline bool BaSparseActive(const pp_ba_impl* h) { return h->sparse_tiles && (!BaInGroup(h) || h->structure_from_covisibility); }
+// K3a (ba_schur.hip): the damped reduced system for `radius` into h->S (lower triangle + rhs row; an iterative handle: its diagonal blocks and its
+// right-hand side), exchanged over the group; refresh_diagonal: the LM diagonal clamp(diag(J_s^T J_s), dmin, dmax) is taken anew in the same launches
+int BaAssembleReducedSystem(pp_ba_impl* h, double radius, bool refresh_diagonal = false, double dmin = 0.0, double dmax = 0.0);
 // matrix-free PCG on the implicit Schur complement (ba_pcg.hip)
 int PcgEnsureBuffers(pp_ba_impl* h);
 int PcgSolve(pp_ba_impl* h, double radius, int max_iterations, double eta, int* iterations);

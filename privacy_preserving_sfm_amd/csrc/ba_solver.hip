@@ -7,22 +7,12 @@
 //   K2   k_reduce             U_c = sum J_c^T J_c (6x6), g_c = J_c^T r   one WORKGROUP per image,
 //                             27 running sums per lane, butterfly + fixed-order LDS reduction (no atomics)
 //                             V_p (3x3), g_p                              one lane per point (same launch)
-//   K3a  k_prepare            one launch, two roles: per point (V_p + D_p^2)^-1 and V^-1 b_p for the current trust-region radius; per
-//                             observation the 192-byte record (J_pt V^-1 | scaled J_pose | J_pt) of the gather, its point's inverse
-//                             block recomputed on the spot (the same 72 bytes gathered: no dependence between the roles)
-//        k_schur_self_rhs     per image (one workgroup): diagonal block of S = U + D_c^2 - sum_p W V^-1 W^T and the
-//                             reduced right-hand side b_c - sum W V^-1 b_p
-//        k_schur_pairs        off-diagonal blocks by GATHER: six lanes per 6x6 block pair (i,j), ten pairs per
-//                             wavefront, each walking the precomputed list of observation pairs that share a point
-//                             (pairs ordered by list length) — deterministic, no fp64 atomics
+//   K3a  BaAssembleReducedSystem   the damped reduced camera system S for the current trust-region radius: k_prepare, k_schur_*  (ba_schur.hip)
 //   K3b  CholeskySolve        dense fp64 MFMA Cholesky of S (cholesky.hip)
 //   K3c  k_step_points        point steps, -(J d)^T (r + J d / 2), the trial point x (+) d (quaternion Plus) and the COST at the trial point in one
 //                             pass over the observations (four lanes per point; every observation applies the step to its own pose).
 //                             With variable intrinsics or a host-callback group: k_backsub_points, k_model_cost_apply and K1 in
 //                             cost-only mode at the stored trial point instead
-// Columns of constant blocks (constant pose, SubsetParameterization of tvec, constant points) keep
-// their slot but get Jacobi scale 0, so their step is exactly 0 and their diagonal is 1.
-//
 // The trust-region logic restates Ceres' published Levenberg-Marquardt strategy (radius update,
 // Jacobi scaling fixed at the first point, clamped LM diagonal, invalid/unsuccessful step handling),
 // see DESIGN.md §LM; Ceres itself is third-party and not part of /root/reference.
@@ -41,40 +31,21 @@
 
 namespace ppsfm {
 
-constexpr double kBig = 1e100;  // diagonal of the augmented rhs row: large enough that BIG - y^T y > 0
-
-struct Jrow {  // one observation's scaled camera-side Jacobian (2 x 6) and point-side Jacobian (2 x 3)
-  double jp[12];
-  double jx[6];
-};
-
-__device__ __forceinline__ void LoadJp(const double* __restrict__ Jpose, int o, double jp[12]) {
-  const double2* p = reinterpret_cast<const double2*>(Jpose + (size_t)12 * o);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) { const double2 v = p[i]; jp[2 * i] = v.x; jp[2 * i + 1] = v.y; }
-}
-__device__ __forceinline__ void LoadJx(const double* __restrict__ Jpoint, int o, double jx[6]) {
-  const double2* p = reinterpret_cast<const double2*>(Jpoint + (size_t)6 * o);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { const double2 v = p[i]; jx[2 * i] = v.x; jx[2 * i + 1] = v.y; }
-}
-
 // ---- K2 ---------------------------------------------------------------------------------------
 __device__ __forceinline__ void PoseReduceBody(int c, const int32_t* __restrict__ pose_start, const int32_t* __restrict__ pose_obs,
                                                const double* __restrict__ Jpose, const double* __restrict__ r,
                                                double* __restrict__ U, double* __restrict__ gc) {
   // one WORKGROUP per image: its observations are strided over 256 lanes, wave sums by DPP row exchanges + v_readlane (WaveSumDpp:
   // the 27 ds_bpermute butterflies of four wavefronts queued up on the LDS crossbar), the four wave totals are added in wave order
-  // through LDS (fixed order: deterministic).  k_reduce 22.0 -> 16.0 us at 500 images x 400 observations (rocprofv3) with the two
-  // changes; the same two changes in SchurSelfRhsBody / k_pcg_images bought nothing (they share their launch with, or are as long
+  // through LDS (fixed order: deterministic; WorkgroupSum4).  k_reduce 22.0 -> 16.0 us at 500 images x 400 observations (rocprofv3) with the two
+  // changes; the same two changes in SchurSelfBody (ba_schur.hip) / k_pcg_images bought nothing (they share their launch with, or are as long
   // as, a gather that is the bound) and cost k_schur_blocks 2 us of occupancy: not applied there.
   __shared__ double red[4][27];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  double u[21], g[6];
+  double run[27];      // the upper triangle of U_c, then g_c
+  double* u = run;
+  double* g = run + 21;
 #pragma unroll
-  for (int i = 0; i < 21; ++i) u[i] = 0.0;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) g[i] = 0.0;
+  for (int i = 0; i < 27; ++i) run[i] = 0.0;
   // two observations per lane and round, both index loads and then both rows in flight together (an image has ~400 observations: one
   // round; one observation per round was two dependent round trips per round, twice)
   auto add = [&](const double (&jp)[12], double r0, double r1) {
@@ -111,28 +82,15 @@ __device__ __forceinline__ void PoseReduceBody(int c, const int32_t* __restrict_
       add(jq, q0, q1);
     }
   }
-#pragma unroll
-  for (int i = 0; i < 21; ++i) u[i] = WaveSumDpp(u[i]);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) g[i] = WaveSumDpp(g[i]);
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 21; ++i) red[wv][i] = u[i];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) red[wv][21 + i] = g[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < 27) {
-    const int i = threadIdx.x;
-    const double v = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
-    if (i >= 21) {
-      gc[6 * (size_t)c + (i - 21)] = v;
-    } else {
-      int a = 0, rem = i;
-      while (rem >= 6 - a) { rem -= 6 - a; ++a; }
-      const int b = a + rem;
-      U[36 * (size_t)c + 6 * a + b] = v; U[36 * (size_t)c + 6 * b + a] = v;
-    }
+  double v;
+  if (!WorkgroupSum4(run, red, &v)) return;
+  const int i = threadIdx.x;
+  if (i >= 21) {
+    gc[6 * (size_t)c + (i - 21)] = v;
+  } else {
+    int a, b;
+    UpperTriangleIndex<6>(i, &a, &b);
+    U[36 * (size_t)c + 6 * a + b] = v; U[36 * (size_t)c + 6 * b + a] = v;
   }
 }
 
@@ -210,526 +168,6 @@ __global__ __launch_bounds__(256) void k_lm_diagonal(int C, int P, const double*
     const double s = scale_p[i];
     diag_p[i] = fmin(fmax(s * s * V[6 * (size_t)p + di], dmin), dmax);
   }
-}
-
-// ---- K3a --------------------------------------------------------------------------------------
-// kWithDiagonal: also refreshes the LM diagonal (k_lm_diagonal's work: the pose part by the first 6C threads, a point's
-// three entries by its own thread) — one launch less on every accepted step; grid covers max(P, 6C) threads then
-// (s (V + D^2 / radius) s)^-1 of one point, D^2 = its LM diagonal: vi = the six entries of the symmetric inverse; returns the determinant
-__device__ __forceinline__ double PointBlockInverse(const double* __restrict__ v, double s0, double s1, double s2, double d0, double d1, double d2,
-                                                    double inv_radius, double (&vi)[6]) {
-  const double a = s0 * s0 * v[0] + d0 * inv_radius, b = s0 * s1 * v[1], c = s0 * s2 * v[2];
-  const double d = s1 * s1 * v[3] + d1 * inv_radius, e = s1 * s2 * v[4];
-  const double f = s2 * s2 * v[5] + d2 * inv_radius;
-  const double c00 = d * f - e * e, c01 = c * e - b * f, c02 = b * e - c * d;
-  const double det = a * c00 + b * c01 + c * c02;
-  const double id = 1.0 / det;
-  vi[0] = c00 * id; vi[1] = c01 * id; vi[2] = c02 * id;
-  vi[3] = (a * f - c * c) * id; vi[4] = (b * c - a * e) * id; vi[5] = (a * d - b * b) * id;
-  return det;
-}
-__device__ __forceinline__ double LmDiagonalEntry(double scale, double jtj, double dmin, double dmax) { return fmin(fmax(scale * scale * jtj, dmin), dmax); }
-
-template <bool kWithDiagonal>
-__device__ __forceinline__ void PointPrepareBody(int block, int P, const double* __restrict__ V, const double* __restrict__ gp,
-                                                 const double* __restrict__ scale_p, double* __restrict__ diag_p,
-                                                 const uint8_t* __restrict__ point_const, double inv_radius,
-                                                 double* __restrict__ Vinv, double* __restrict__ vb, int32_t* __restrict__ flag,
-                                                 int C, const double* __restrict__ U, const double* __restrict__ scale_c, double dmin, double dmax,
-                                                 double* __restrict__ diag_c) {
-  const int p = block * 256 + threadIdx.x;
-  if (kWithDiagonal) {
-    if (p < 6 * C) {
-      const int c = p / 6, j = p % 6;
-      diag_c[p] = LmDiagonalEntry(scale_c[p], U[36 * (size_t)c + 7 * j], dmin, dmax);
-    }
-    if (p < P) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int di = j == 0 ? 0 : (j == 1 ? 3 : 5);
-        diag_p[3 * p + j] = LmDiagonalEntry(scale_p[3 * p + j], V[6 * (size_t)p + di], dmin, dmax);
-      }
-    }
-  }
-  if (p >= P) return;
-  double* vi = Vinv + 6 * (size_t)p;
-  double* vbp = vb + 3 * (size_t)p;
-  if (point_const[p]) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) vi[i] = 0.0;
-    vbp[0] = vbp[1] = vbp[2] = 0.0;
-    return;
-  }
-  const double s0 = scale_p[3 * p], s1 = scale_p[3 * p + 1], s2 = scale_p[3 * p + 2];
-  double w[6];
-  const double det = PointBlockInverse(V + 6 * (size_t)p, s0, s1, s2, diag_p[3 * p], diag_p[3 * p + 1], diag_p[3 * p + 2], inv_radius, w);
-  if (!(det > 0.0) || !isfinite(det)) { atomicOr(flag, 2); }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) vi[i] = w[i];
-  const double b0 = -s0 * gp[3 * p], b1 = -s1 * gp[3 * p + 1], b2 = -s2 * gp[3 * p + 2];
-  vbp[0] = w[0] * b0 + w[1] * b1 + w[2] * b2;
-  vbp[1] = w[1] * b0 + w[3] * b1 + w[4] * b2;
-  vbp[2] = w[2] * b0 + w[4] * b1 + w[5] * b2;
-}
-
-struct SchurArgs {
-  int C, N, rhs_row;
-  const int32_t *pose_start, *pose_obs, *obs_point;
-  const double *Jpose, *Jpoint, *U, *gc, *Vinv, *vb, *scale_c, *scale_p, *diag_c;
-  double inv_radius;
-  double* S;
-  int add_diagonal;  // group rank 0 adds U + D^2 (point-sharded multi-GPU: the sum over ranks must contain it once)
-  // iterative handles (ba_pcg.hip) have no N x N system: the diagonal blocks go to Sd [C][36] and the reduced rhs to rhs_out [6C]
-  double* Sd = nullptr;
-  double* rhs_out = nullptr;
-  // position in S of every column of the parameter vectors (pose c: columns 6c .. 6c+5 of the vectors; pp_ba_impl::spos): 6c unless every image carries its
-  // own variable intrinsics beside its pose columns
-  const int32_t* spos = nullptr;
-};
-
-// per observation and per attempt: the scaled Jacobian rows the Schur gather needs, ONE 192-byte record (ba_impl.hpp, kRecStride):
-//   [ T_o = J_pt,o s_p (V+D^2)^-1 s_p (2 x 3) | J_pose,o diag(s_c) (2 x 6) | J_pt,o (2 x 3) ]      so that  G_oo' = T_o J_pt,o'^T
-// The records of a workgroup's 256 observations are staged through LDS and written as one contiguous 48 KB slab with fully
-// coalesced 16-byte stores (as K1 does; one lane writing 16-byte pieces at a record stride touched 48 cache lines per store).
-// The point's inverse block is computed HERE, per observation, from V / the scales / the LM diagonal (PointBlockInverse: the arithmetic of
-// the point role) instead of being read back from Vinv: the same 72 bytes gathered per observation, and no dependence on the point role -
-// the two run in ONE launch (k_prepare).  kWithDiagonal: the LM diagonal is being refreshed in this launch: taken from V as well.
-template <bool kWithDiagonal>
-__device__ __forceinline__ void ObsPrepareBody(int block, int64_t M, const int32_t* __restrict__ obs_pose, const int32_t* __restrict__ obs_point,
-                                               const double* __restrict__ Jpose, const double* __restrict__ Jpoint,
-                                               const double* __restrict__ V, const double* __restrict__ diag_p, const uint8_t* __restrict__ point_const,
-                                               double inv_radius, double dmin, double dmax, const double* __restrict__ scale_c,
-                                               const double* __restrict__ scale_p, double* __restrict__ rec) {
-  __shared__ __attribute__((aligned(16))) double sR[256 * kRecStride];
-  const int tid = threadIdx.x;
-  const int64_t o0 = (int64_t)block * 256, o = o0 + tid;
-  if (o < M) {
-    const int c = obs_pose[o], p = obs_point[o];
-    double jp[12], jx[6];
-    LoadJp(Jpose, (int)o, jp);
-    LoadJx(Jpoint, (int)o, jx);
-    double2* jo = reinterpret_cast<double2*>(sR + kRecStride * tid + 6);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const int j0 = (2 * i) % 6, j1 = (2 * i + 1) % 6;
-      jo[i] = make_double2(jp[2 * i] * scale_c[6 * c + j0], jp[2 * i + 1] * scale_c[6 * c + j1]);
-    }
-    const double s0 = scale_p[3 * p], s1 = scale_p[3 * p + 1], s2 = scale_p[3 * p + 2];
-    double vi[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (!point_const[p]) {
-      const double* v = V + 6 * (size_t)p;
-      double d0, d1, d2;
-      if (kWithDiagonal) { d0 = LmDiagonalEntry(s0, v[0], dmin, dmax); d1 = LmDiagonalEntry(s1, v[3], dmin, dmax); d2 = LmDiagonalEntry(s2, v[5], dmin, dmax); }
-      else { d0 = diag_p[3 * p]; d1 = diag_p[3 * p + 1]; d2 = diag_p[3 * p + 2]; }
-      (void)PointBlockInverse(v, s0, s1, s2, d0, d1, d2, inv_radius, vi);
-    }
-    const double v00 = vi[0] * s0 * s0, v01 = vi[1] * s0 * s1, v02 = vi[2] * s0 * s2, v11 = vi[3] * s1 * s1, v12 = vi[4] * s1 * s2,
-                 v22 = vi[5] * s2 * s2;
-    double t[6];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      t[3 * r + 0] = jx[3 * r] * v00 + jx[3 * r + 1] * v01 + jx[3 * r + 2] * v02;
-      t[3 * r + 1] = jx[3 * r] * v01 + jx[3 * r + 1] * v11 + jx[3 * r + 2] * v12;
-      t[3 * r + 2] = jx[3 * r] * v02 + jx[3 * r + 1] * v12 + jx[3 * r + 2] * v22;
-    }
-    double2* to = reinterpret_cast<double2*>(sR + kRecStride * tid);
-    double2* xo = reinterpret_cast<double2*>(sR + kRecStride * tid + 18);
-    to[0] = make_double2(t[0], t[1]); to[1] = make_double2(t[2], t[3]); to[2] = make_double2(t[4], t[5]);
-    xo[0] = make_double2(jx[0], jx[1]); xo[1] = make_double2(jx[2], jx[3]); xo[2] = make_double2(jx[4], jx[5]);
-  }
-  __syncthreads();
-  const int64_t left = M - o0;
-  const int n2 = (left < 256 ? (int)left : 256) * (kRecStride / 2);     // double2 chunks of the slab
-  double2* dr = reinterpret_cast<double2*>(rec + (size_t)kRecStride * o0);
-  const double2* sr = reinterpret_cast<const double2*>(sR);
-#pragma unroll
-  for (int it = 0; it < kRecStride / 2; ++it) {
-    const int idx = it * 256 + tid;
-    if (idx < n2) dr[idx] = sr[idx];
-  }
-}
-
-// point role (the first point_blocks workgroups) and observation role in ONE launch: neither reads what the other writes
-template <bool kWithDiagonal>
-__global__ __launch_bounds__(256) void k_prepare(int point_blocks, int P, const double* __restrict__ V, const double* __restrict__ gp, const double* __restrict__ scale_p,
-                                                 double* __restrict__ diag_p, const uint8_t* __restrict__ point_const, double inv_radius, double* __restrict__ Vinv,
-                                                 double* __restrict__ vb, int32_t* __restrict__ flag, int C, const double* __restrict__ U,
-                                                 const double* __restrict__ scale_c, double dmin, double dmax, double* __restrict__ diag_c, int64_t M,
-                                                 const int32_t* __restrict__ obs_pose, const int32_t* __restrict__ obs_point, const double* __restrict__ Jpose,
-                                                 const double* __restrict__ Jpoint, double* __restrict__ rec, int obs_blocks, double* __restrict__ zS, int zN,
-                                                 const int32_t* __restrict__ ztiles) {
-  if ((int)blockIdx.x < point_blocks)
-    PointPrepareBody<kWithDiagonal>(blockIdx.x, P, V, gp, scale_p, diag_p, point_const, inv_radius, Vinv, vb, flag, C, U, scale_c, dmin, dmax, diag_c);
-  else if ((int)blockIdx.x < point_blocks + obs_blocks)
-    ObsPrepareBody<kWithDiagonal>((int)blockIdx.x - point_blocks, M, obs_pose, obs_point, Jpose, Jpoint, V, diag_p, point_const, inv_radius, dmin, dmax, scale_c, scale_p, rec);
-  else {
-    // third role (block-sparse systems): clears the listed 64x64 tiles of S - the factorisation fills exactly these, all others stay zero for good (a launch
-    // of its own, 6 us, before this one until the sequence scenes made the rest of the iteration count)
-    const int zt = (int)blockIdx.x - point_blocks - obs_blocks;
-    const int ti = ztiles[2 * zt], tj = ztiles[2 * zt + 1];
-    double2* base = reinterpret_cast<double2*>(zS + (size_t)ti * 64 * zN + (size_t)tj * 64);
-    for (int idx = threadIdx.x; idx < 64 * 32; idx += 256) base[(size_t)(idx >> 5) * (zN / 2) + (idx & 31)] = make_double2(0.0, 0.0);
-  }
-}
-
-// the augmented corner and the identity padding
-// Per image, ONE workgroup (4 wavefronts, observations strided over 256 lanes, wave butterfly + fixed-order LDS sum):
-//   diagonal 6x6 block   U_s + D^2 - sum_{o of this image} J_o^T G_oo J_o            (identity on constant columns)
-//   reduced rhs          b_c - sum_{o in c} J_c,o^T (J_p,o (V^-1 b_p))               -> row rhs_row of S
-// (both walk the same observation list and the same 96-byte records; they used to be two wavefront-per-image kernels
-// of ~25 us each)
-__device__ __forceinline__ void SchurSelfRhsBody(const SchurArgs& a, const double* __restrict__ rec, int c) {
-  __shared__ double red[4][27];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (c == 0 && threadIdx.x < 64 && !a.Sd) {     // the corner of the augmented system: BIG at (rhs_row, rhs_row), identity padding below
-    const int j = a.rhs_row + threadIdx.x;
-    if (j < a.N) {
-      if (threadIdx.x > 0) a.S[(size_t)j * a.N + j] = 1.0;
-      else if (a.add_diagonal) a.S[(size_t)j * a.N + j] = kBig;
-    }
-  }
-  double u[21], acc[6];
-#pragma unroll
-  for (int i = 0; i < 21; ++i) u[i] = 0.0;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) acc[i] = 0.0;
-  for (int e = a.pose_start[c] + (int)threadIdx.x; e < a.pose_start[c + 1]; e += 256) {
-    const int o = a.pose_obs[e];
-    const int p = a.obs_point[o];
-    double jp[12], q[12];
-    {      // the whole record: [T_o | J_pose,o diag(s_c) | J_pt,o]
-      const double2* p = reinterpret_cast<const double2*>(RecT(rec, (size_t)o));
-#pragma unroll
-      for (int i = 0; i < 3; ++i) { const double2 v = p[i]; q[2 * i] = v.x; q[2 * i + 1] = v.y; }
-#pragma unroll
-      for (int i = 0; i < 6; ++i) { const double2 v = p[3 + i]; jp[2 * i] = v.x; jp[2 * i + 1] = v.y; }
-#pragma unroll
-      for (int i = 0; i < 3; ++i) { const double2 v = p[9 + i]; q[6 + 2 * i] = v.x; q[6 + 2 * i + 1] = v.y; }
-    }
-    const double g00 = q[0] * q[6] + q[1] * q[7] + q[2] * q[8], g01 = q[0] * q[9] + q[1] * q[10] + q[2] * q[11];
-    const double g10 = q[3] * q[6] + q[4] * q[7] + q[5] * q[8], g11 = q[3] * q[9] + q[4] * q[10] + q[5] * q[11];
-    int idx = 0;
-#pragma unroll
-    for (int x = 0; x < 6; ++x) {
-      const double h0 = jp[x] * g00 + jp[6 + x] * g10, h1 = jp[x] * g01 + jp[6 + x] * g11;
-#pragma unroll
-      for (int y = x; y < 6; ++y) u[idx++] += h0 * jp[y] + h1 * jp[6 + y];
-    }
-    const double w0 = a.scale_p[3 * p] * a.vb[3 * (size_t)p], w1 = a.scale_p[3 * p + 1] * a.vb[3 * (size_t)p + 1],
-                 w2 = a.scale_p[3 * p + 2] * a.vb[3 * (size_t)p + 2];
-    const double t0 = q[6] * w0 + q[7] * w1 + q[8] * w2, t1 = q[9] * w0 + q[10] * w1 + q[11] * w2;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) acc[j] += jp[j] * t0 + jp[6 + j] * t1;    // already scaled by s_c (JpS)
-  }
-#pragma unroll
-  for (int i = 0; i < 21; ++i) u[i] = WaveSumDpp(u[i]);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) acc[i] = WaveSumDpp(acc[i]);
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 21; ++i) red[wv][i] = u[i];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) red[wv][21 + i] = acc[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < 27) {
-    const int i = threadIdx.x;
-    const double sum = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
-    if (i >= 21) {
-      const int j = i - 21;
-      const double s = a.scale_c[6 * c + j];
-      const double own = a.add_diagonal ? -s * a.gc[6 * (size_t)c + j] : 0.0;
-      if (a.Sd) a.rhs_out[6 * (size_t)c + j] = own - sum;
-      else a.S[(size_t)a.rhs_row * a.N + a.spos[6 * c] + j] = own - sum;
-    } else {
-      int x = 0, rem = i;
-      while (rem >= 6 - x) { rem -= 6 - x; ++x; }
-      const int y = x + rem;
-      const double sa = a.scale_c[6 * c + x], sb = a.scale_c[6 * c + y];
-      double v = 0.0;
-      if (a.add_diagonal) {
-        v = sa * sb * a.U[36 * (size_t)c + 6 * x + y];
-        if (x == y) v = (sa == 0.0) ? 1.0 : v + a.diag_c[6 * c + x] * a.inv_radius;
-      }
-      v -= sum;
-      if (a.Sd) { a.Sd[36 * (size_t)c + 6 * x + y] = v; a.Sd[36 * (size_t)c + 6 * y + x] = v; }
-      else {
-        const int sp = a.spos[6 * c];
-        a.S[(size_t)(sp + x) * a.N + sp + y] = v;
-        a.S[(size_t)(sp + y) * a.N + sp + x] = v;
-      }
-    }
-  }
-}
-
-// Off-diagonal blocks: S_ij -= sum over observation pairs sharing a point of J_i^T (T_oi J_pt,oj^T) J_j.
-// SIX LANES PER BLOCK PAIR (lane = one row of the 6x6 block), ten pairs per wavefront: the lists are short (5.6
-// entries per pair on the 500-camera scene, 124k pairs), so a wavefront per pair was all fixed cost and latency
-// (122 us); here a wavefront walks ten lists at once and the six lanes of a pair read the same 96-byte records
-// (one transaction).  Entries are summed in list order: deterministic, no atomics.
-template <bool kStore>      // kStore: the block is written, not accumulated into (pp_ba_impl::pairs_complete)
-__device__ __forceinline__ void SchurPairsBody(const SchurArgs& a, const double* __restrict__ rec,
-                                               int64_t num_pairs, const int32_t* __restrict__ pair_start,
-                                               const int32_t* __restrict__ pair_ij, const int32_t* __restrict__ pair_entries, int64_t block) {
-  const int lane = threadIdx.x & 63;
-  const int slot = lane / 6, ar = lane % 6;
-  const int64_t wave = block * 4 + (threadIdx.x >> 6);
-  const int64_t pr = wave * 10 + slot;
-  if (slot >= 10 || pr >= num_pairs) return;
-  const int bi = pair_ij[2 * pr], bj = pair_ij[2 * pr + 1];
-  const int e0 = pair_start[2 * pr], e1 = pair_start[2 * pr + 1];    // (first, last + 1), pairs ordered by list length
-  double acc[6] = {0, 0, 0, 0, 0, 0};
-  int2 next = e0 < e1 ? *reinterpret_cast<const int2*>(pair_entries + 2 * (size_t)e0) : make_int2(0, 0);
-  for (int e = e0; e < e1; ++e) {
-    const int2 oo = next;
-    if (e + 1 < e1) next = *reinterpret_cast<const int2*>(pair_entries + 2 * (size_t)(e + 1));   // the next entry's indices travel with this entry's records
-    const double2* qi = reinterpret_cast<const double2*>(RecT(rec, (size_t)oo.x));       // T_oi (2x3)
-    const double2* qj = reinterpret_cast<const double2*>(RecX(rec, (size_t)oo.y));       // J_pt,oj (2x3)
-    const double2* pj = reinterpret_cast<const double2*>(RecJ(rec, (size_t)oo.y));
-    const double2 t0 = qi[0], t1 = qi[1], t2 = qi[2];
-    const double2 x0 = qj[0], x1 = qj[1], x2 = qj[2];
-    const double pi0 = RecJ(rec, (size_t)oo.x)[ar], pi1 = RecJ(rec, (size_t)oo.x)[6 + ar];
-    // G = T X^T : T rows (t0.x t0.y t1.x | t1.y t2.x t2.y), X rows (x0.x x0.y x1.x | x1.y x2.x x2.y)
-    const double g00 = t0.x * x0.x + t0.y * x0.y + t1.x * x1.x, g01 = t0.x * x1.y + t0.y * x2.x + t1.x * x2.y;
-    const double g10 = t1.y * x0.x + t2.x * x0.y + t2.y * x1.x, g11 = t1.y * x1.y + t2.x * x2.x + t2.y * x2.y;
-    const double h0 = pi0 * g00 + pi1 * g10, h1 = pi0 * g01 + pi1 * g11;
-    const double2 j0 = pj[0], j1 = pj[1], j2 = pj[2], j3 = pj[3], j4 = pj[4], j5 = pj[5];   // rows: (j0 j1 j2), (j3 j4 j5)
-    acc[0] += h0 * j0.x + h1 * j3.x; acc[1] += h0 * j0.y + h1 * j3.y;
-    acc[2] += h0 * j1.x + h1 * j4.x; acc[3] += h0 * j1.y + h1 * j4.y;
-    acc[4] += h0 * j2.x + h1 * j5.x; acc[5] += h0 * j2.y + h1 * j5.y;
-  }
-  double2* dst = reinterpret_cast<double2*>(a.S + (size_t)(a.spos[6 * bi] + ar) * a.N + a.spos[6 * bj]);
-  double2 d0 = make_double2(0.0, 0.0), d1 = d0, d2 = d0;
-  if (!kStore) { d0 = dst[0]; d1 = dst[1]; d2 = dst[2]; }
-  d0.x -= acc[0]; d0.y -= acc[1]; d1.x -= acc[2]; d1.y -= acc[3]; d2.x -= acc[4]; d2.y -= acc[5];
-  dst[0] = d0; dst[1] = d1; dst[2] = d2;
-}
-
-__global__ __launch_bounds__(256) void k_schur_self_rhs(SchurArgs a, const double* __restrict__ rec) {
-  SchurSelfRhsBody(a, rec, blockIdx.x);
-}
-template <bool kStore>
-__global__ __launch_bounds__(256) void k_schur_pairs(SchurArgs a, const double* __restrict__ rec, int64_t num_pairs,
-                                                     const int32_t* __restrict__ pair_start, const int32_t* __restrict__ pair_ij,
-                                                     const int32_t* __restrict__ pair_entries) {
-  SchurPairsBody<kStore>(a, rec, num_pairs, pair_start, pair_ij, pair_entries, blockIdx.x);
-}
-// store mode: the diagonal blocks + rhs (first C workgroups) and the off-diagonal blocks write disjoint parts of S and read the
-// same records — one launch, the ~500 per-image workgroups run under the pair gather instead of before it
-__global__ __launch_bounds__(256) void k_schur_blocks(SchurArgs a, const double* __restrict__ rec, int64_t num_pairs,
-                                                      const int32_t* __restrict__ pair_start, const int32_t* __restrict__ pair_ij,
-                                                      const int32_t* __restrict__ pair_entries) {
-  if ((int)blockIdx.x < a.C) SchurSelfRhsBody(a, rec, blockIdx.x);
-  else SchurPairsBody<true>(a, rec, num_pairs, pair_start, pair_ij, pair_entries, (int64_t)blockIdx.x - a.C);
-}
-
-// ---- every image with variable intrinsics of its own beside its pose columns (pp_ba_impl::intr_wide_nv = NV; image_ordering.hip PrivateIntrinsicsColumns) ----
-// The image's 6 + NV columns are ONE block of the reduced system, J_w,o = [J_pose,o diag(s_c) | J_intr,o diag(s_k)] (2 x W, W = 6 + NV: the record's pose rows and
-// the compact scaled rows of JkS), and the blocks are those of the pose gather with wider rows:
-//   diagonal   S_cc = U_c + D^2 (pose part, as SchurSelfRhsBody) + sum_{o of c} J_w^T J_w (every entry with an intrinsics column) - sum_o J_w^T G_oo J_w
-//   off it     S_ij -= sum over the pair list of (i, j) of J_w,oi^T (T_oi X_oj^T) J_w,oj          (the lists of pp_ba_create, every image listed whatever its pose)
-//   rhs        -s g - sum_o J_w^T (J_pt,o (V^-1 b_p))
-// instead of the block-pair lists of ba_intr.hip (k_intr_L / k_schur_gen / k_intr_kk / k_intr_sums<1>: built for cameras SHARED between images; a camera per
-// image gave 250 000 twelve-lane pairs of one chunk - 0.46 ms per assembly at 500 images / 200k observations against 0.11 for the pose blocks).
-template <int NV>
-__global__ __launch_bounds__(256) void k_schur_wide_self(SchurArgs a, const double* __restrict__ rec, const double* __restrict__ JkS,
-                                                         const int32_t* __restrict__ pose_camera, const int32_t* __restrict__ intr_off) {
-  constexpr int W = 6 + NV, NU = W * (W + 1) / 2;
-  __shared__ double red[4][NU + W];
-  const int c = blockIdx.x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (c == 0 && threadIdx.x < 64) {     // the corner of the augmented system: BIG at (rhs_row, rhs_row), identity padding below
-    const int j = a.rhs_row + threadIdx.x;
-    if (j < a.N) {
-      if (threadIdx.x > 0) a.S[(size_t)j * a.N + j] = 1.0;
-      else if (a.add_diagonal) a.S[(size_t)j * a.N + j] = kBig;
-    }
-  }
-  double u[NU], acc[W];
-#pragma unroll
-  for (int i = 0; i < NU; ++i) u[i] = 0.0;
-#pragma unroll
-  for (int i = 0; i < W; ++i) acc[i] = 0.0;
-  for (int e = a.pose_start[c] + (int)threadIdx.x; e < a.pose_start[c + 1]; e += 256) {
-    const int o = a.pose_obs[e];
-    const int p = a.obs_point[o];
-    double j0[W], j1[W], q[12];
-    {
-      const double2* r2 = reinterpret_cast<const double2*>(RecT(rec, (size_t)o));
-#pragma unroll
-      for (int i = 0; i < 3; ++i) { const double2 v = r2[i]; q[2 * i] = v.x; q[2 * i + 1] = v.y; }
-#pragma unroll
-      for (int i = 0; i < 3; ++i) { const double2 v = r2[3 + i]; j0[2 * i] = v.x; j0[2 * i + 1] = v.y; }
-#pragma unroll
-      for (int i = 0; i < 3; ++i) { const double2 v = r2[6 + i]; j1[2 * i] = v.x; j1[2 * i + 1] = v.y; }
-#pragma unroll
-      for (int i = 0; i < 3; ++i) { const double2 v = r2[9 + i]; q[6 + 2 * i] = v.x; q[6 + 2 * i + 1] = v.y; }
-      const double2* k2 = reinterpret_cast<const double2*>(JkS + (size_t)2 * kCamStride * o);
-#pragma unroll
-      for (int i = 0; i < NV / 2; ++i) { const double2 v0 = k2[i], v1 = k2[kCamStride / 2 + i]; j0[6 + 2 * i] = v0.x; j0[7 + 2 * i] = v0.y; j1[6 + 2 * i] = v1.x; j1[7 + 2 * i] = v1.y; }
-    }
-    const double g00 = q[0] * q[6] + q[1] * q[7] + q[2] * q[8], g01 = q[0] * q[9] + q[1] * q[10] + q[2] * q[11];
-    const double g10 = q[3] * q[6] + q[4] * q[7] + q[5] * q[8], g11 = q[3] * q[9] + q[4] * q[10] + q[5] * q[11];
-    int idx = 0;
-#pragma unroll
-    for (int x = 0; x < W; ++x) {
-      const double h0 = j0[x] * g00 + j1[x] * g10, h1 = j0[x] * g01 + j1[x] * g11;
-      const double d0 = h0 - j0[x], d1 = h1 - j1[x];      // (G - I): the direct term J^T J of every entry with an intrinsics column (the pose part's is U)
-#pragma unroll
-      for (int y = x; y < W; ++y) u[idx++] += (y < 6) ? h0 * j0[y] + h1 * j1[y] : d0 * j0[y] + d1 * j1[y];
-    }
-    const double w0 = a.scale_p[3 * p] * a.vb[3 * (size_t)p], w1 = a.scale_p[3 * p + 1] * a.vb[3 * (size_t)p + 1],
-                 w2 = a.scale_p[3 * p + 2] * a.vb[3 * (size_t)p + 2];
-    const double t0 = q[6] * w0 + q[7] * w1 + q[8] * w2, t1 = q[9] * w0 + q[10] * w1 + q[11] * w2;
-#pragma unroll
-    for (int j = 0; j < W; ++j) acc[j] += j0[j] * t0 + j1[j] * t1;
-  }
-#pragma unroll
-  for (int i = 0; i < NU; ++i) u[i] = WaveSumDpp(u[i]);
-#pragma unroll
-  for (int i = 0; i < W; ++i) acc[i] = WaveSumDpp(acc[i]);
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < NU; ++i) red[wv][i] = u[i];
-#pragma unroll
-    for (int i = 0; i < W; ++i) red[wv][NU + i] = acc[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < NU + W) {
-    const int i = threadIdx.x;
-    const double sum = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
-    const int sp = a.spos[6 * c];
-    const int ioff = 6 * a.C + intr_off[pose_camera[c]];      // the image's intrinsics columns in the parameter vectors
-    if (i >= NU) {
-      const int j = i - NU;
-      const int v = j < 6 ? 6 * c + j : ioff + j - 6;
-      const double own = a.add_diagonal ? -a.scale_c[v] * a.gc[v] : 0.0;
-      a.S[(size_t)a.rhs_row * a.N + sp + j] = own - sum;
-    } else {
-      int x = 0, rem = i;
-      while (rem >= W - x) { rem -= W - x; ++x; }
-      const int y = x + rem;
-      double v = 0.0;
-      if (a.add_diagonal) {
-        if (y < 6) {
-          const double sa = a.scale_c[6 * c + x], sb = a.scale_c[6 * c + y];
-          v = sa * sb * a.U[36 * (size_t)c + 6 * x + y];
-          if (x == y) v = (sa == 0.0) ? 1.0 : v + a.diag_c[6 * c + x] * a.inv_radius;
-        } else if (x == y) v = a.diag_c[ioff + x - 6] * a.inv_radius;
-      }
-      v -= sum;
-      a.S[(size_t)(sp + x) * a.N + sp + y] = v;
-      a.S[(size_t)(sp + y) * a.N + sp + x] = v;
-    }
-  }
-}
-// W = 6 + NV lanes per block pair (lane = one row of the W x W block), 64 / W pairs per wavefront; entries summed in list order (deterministic, no atomics),
-// the block accumulated into S - or, kStore, written (every pair of images has a list, pp_ba_impl::pairs_complete: S needs no clearing)
-template <int NV, bool kStore>
-__global__ __launch_bounds__(256) void k_schur_wide_pairs(SchurArgs a, const double* __restrict__ rec, const double* __restrict__ JkS, int64_t num_pairs,
-                                                          const int32_t* __restrict__ pair_start, const int32_t* __restrict__ pair_ij,
-                                                          const int32_t* __restrict__ pair_entries) {
-  constexpr int W = 6 + NV, kSlots = 64 / W;
-  const int lane = threadIdx.x & 63;
-  const int slot = lane / W, ar = lane % W;
-  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t pr = wave * kSlots + slot;
-  if (slot >= kSlots || pr >= num_pairs) return;
-  const int bi = pair_ij[2 * pr], bj = pair_ij[2 * pr + 1];
-  const int e0 = pair_start[2 * pr], e1 = pair_start[2 * pr + 1];    // (first, last + 1), pairs ordered by list length
-  double acc[W];
-#pragma unroll
-  for (int i = 0; i < W; ++i) acc[i] = 0.0;
-  int2 next = e0 < e1 ? *reinterpret_cast<const int2*>(pair_entries + 2 * (size_t)e0) : make_int2(0, 0);
-  for (int e = e0; e < e1; ++e) {
-    const int2 oo = next;
-    if (e + 1 < e1) next = *reinterpret_cast<const int2*>(pair_entries + 2 * (size_t)(e + 1));
-    const double2* qi = reinterpret_cast<const double2*>(RecT(rec, (size_t)oo.x));       // T_oi (2x3)
-    const double2* qj = reinterpret_cast<const double2*>(RecX(rec, (size_t)oo.y));       // J_pt,oj (2x3)
-    const double2* pj = reinterpret_cast<const double2*>(RecJ(rec, (size_t)oo.y));
-    const double2* kj = reinterpret_cast<const double2*>(JkS + (size_t)2 * kCamStride * oo.y);
-    const double2 t0 = qi[0], t1 = qi[1], t2 = qi[2];
-    const double2 x0 = qj[0], x1 = qj[1], x2 = qj[2];
-    const double* ri = ar < 6 ? RecJ(rec, (size_t)oo.x) + ar : JkS + (size_t)2 * kCamStride * oo.x + (ar - 6);      // this lane's row of J_w,oi^T: (ri[0], ri[stride])
-    const double pi0 = ri[0], pi1 = ri[ar < 6 ? 6 : kCamStride];
-    const double g00 = t0.x * x0.x + t0.y * x0.y + t1.x * x1.x, g01 = t0.x * x1.y + t0.y * x2.x + t1.x * x2.y;
-    const double g10 = t1.y * x0.x + t2.x * x0.y + t2.y * x1.x, g11 = t1.y * x1.y + t2.x * x2.x + t2.y * x2.y;
-    const double h0 = pi0 * g00 + pi1 * g10, h1 = pi0 * g01 + pi1 * g11;
-    const double2 j0 = pj[0], j1 = pj[1], j2 = pj[2], j3 = pj[3], j4 = pj[4], j5 = pj[5];   // rows: (j0 j1 j2), (j3 j4 j5)
-    acc[0] += h0 * j0.x + h1 * j3.x; acc[1] += h0 * j0.y + h1 * j3.y;
-    acc[2] += h0 * j1.x + h1 * j4.x; acc[3] += h0 * j1.y + h1 * j4.y;
-    acc[4] += h0 * j2.x + h1 * j5.x; acc[5] += h0 * j2.y + h1 * j5.y;
-#pragma unroll
-    for (int b = 0; b < NV / 2; ++b) {
-      const double2 k0 = kj[b], k1 = kj[kCamStride / 2 + b];
-      acc[6 + 2 * b] += h0 * k0.x + h1 * k1.x; acc[7 + 2 * b] += h0 * k0.y + h1 * k1.y;
-    }
-  }
-  double2* dst = reinterpret_cast<double2*>(a.S + (size_t)(a.spos[6 * bi] + ar) * a.N + a.spos[6 * bj]);
-#pragma unroll
-  for (int b = 0; b < W / 2; ++b) { double2 d = kStore ? make_double2(0.0, 0.0) : dst[b]; d.x -= acc[2 * b]; d.y -= acc[2 * b + 1]; dst[b] = d; }
-}
-
-// Few images, many shared points (the mapper's local bundle adjustment: 6 images, src/sfm/incremental_mapper.cc:813-858): fifteen block pairs with
-// lists of hundreds of entries, each walked by six lanes - 134 us of a 190 us LM iteration at 6 images / 2004 observations.  When a list is longer
-// than 64 entries (pp_ba_create) the lists are cut into chunks of 32: the same six lanes per CHUNK (SchurPairsBody's arithmetic on a sub-range),
-// partial blocks to memory, then every block = the sum of its chunks in chunk order (k_schur_chunk_reduce) - deterministic, no atomics.
-__device__ __forceinline__ void SchurChunksBody(const double* __restrict__ rec, int num_chunks, const int32_t* __restrict__ chunk, const int32_t* __restrict__ pair_entries,
-                                                double* __restrict__ partials, int64_t block) {
-  const int lane = threadIdx.x & 63;
-  const int slot = lane / 6, ar = lane % 6;
-  const int64_t ch = (block * 4 + (threadIdx.x >> 6)) * 10 + slot;
-  if (slot >= 10 || ch >= num_chunks) return;
-  const int e0 = chunk[3 * ch + 1], e1 = chunk[3 * ch + 2];
-  double acc[6] = {0, 0, 0, 0, 0, 0};
-  int2 next = e0 < e1 ? *reinterpret_cast<const int2*>(pair_entries + 2 * (size_t)e0) : make_int2(0, 0);
-  for (int e = e0; e < e1; ++e) {
-    const int2 oo = next;
-    if (e + 1 < e1) next = *reinterpret_cast<const int2*>(pair_entries + 2 * (size_t)(e + 1));
-    const double2* qi = reinterpret_cast<const double2*>(RecT(rec, (size_t)oo.x));
-    const double2* qj = reinterpret_cast<const double2*>(RecX(rec, (size_t)oo.y));
-    const double2* pj = reinterpret_cast<const double2*>(RecJ(rec, (size_t)oo.y));
-    const double2 t0 = qi[0], t1 = qi[1], t2 = qi[2];
-    const double2 x0 = qj[0], x1 = qj[1], x2 = qj[2];
-    const double pi0 = RecJ(rec, (size_t)oo.x)[ar], pi1 = RecJ(rec, (size_t)oo.x)[6 + ar];
-    const double g00 = t0.x * x0.x + t0.y * x0.y + t1.x * x1.x, g01 = t0.x * x1.y + t0.y * x2.x + t1.x * x2.y;
-    const double g10 = t1.y * x0.x + t2.x * x0.y + t2.y * x1.x, g11 = t1.y * x1.y + t2.x * x2.x + t2.y * x2.y;
-    const double h0 = pi0 * g00 + pi1 * g10, h1 = pi0 * g01 + pi1 * g11;
-    const double2 j0 = pj[0], j1 = pj[1], j2 = pj[2], j3 = pj[3], j4 = pj[4], j5 = pj[5];
-    acc[0] += h0 * j0.x + h1 * j3.x; acc[1] += h0 * j0.y + h1 * j3.y;
-    acc[2] += h0 * j1.x + h1 * j4.x; acc[3] += h0 * j1.y + h1 * j4.y;
-    acc[4] += h0 * j2.x + h1 * j5.x; acc[5] += h0 * j2.y + h1 * j5.y;
-  }
-  double2* dst = reinterpret_cast<double2*>(partials + 36 * (size_t)chunk[3 * ch] + 6 * ar);      // (the chunk's id: the processing order is pp_ba_create's, see "L2 locality of the chunk kernel")
-  dst[0] = make_double2(acc[0], acc[1]); dst[1] = make_double2(acc[2], acc[3]); dst[2] = make_double2(acc[4], acc[5]);
-}
-// the per-image part (first C workgroups) and the chunks in one launch
-__global__ __launch_bounds__(256) void k_schur_self_chunks(SchurArgs a, const double* __restrict__ rec, int num_chunks, const int32_t* __restrict__ chunk,
-                                                           const int32_t* __restrict__ pair_entries, double* __restrict__ partials) {
-  if ((int)blockIdx.x < a.C) SchurSelfRhsBody(a, rec, blockIdx.x);
-  else SchurChunksBody(rec, num_chunks, chunk, pair_entries, partials, (int64_t)blockIdx.x - a.C);
-}
-template <bool kStore>      // kStore: the block is written, not accumulated into (pp_ba_impl::pairs_complete)
-__global__ __launch_bounds__(256) void k_schur_chunk_reduce(SchurArgs a, int64_t num_pairs, const int32_t* __restrict__ pair_ij, const int32_t* __restrict__ pair_chunk,
-                                                            const double* __restrict__ partials) {
-  const int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (it >= 36 * num_pairs) return;
-  const int64_t pr = it / 36;
-  const int el = (int)(it % 36);
-  const int c0 = pair_chunk[pr], c1 = pair_chunk[pr + 1];
-  if (c0 == c1 && !kStore) return;
-  double sum = 0.0;
-  int ch = c0;
-  for (; ch + 8 <= c1; ch += 8) {      // eight partials in flight, added in chunk order (a load per addition was 0.3 us per chunk: 14 us for the 42 chunks of a 334-entry list)
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = partials[36 * (size_t)(ch + u) + el];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) sum += v[u];
-  }
-  for (; ch < c1; ++ch) sum += partials[36 * (size_t)ch + el];
-  double* dst = a.S + (size_t)(a.spos[6 * pair_ij[2 * pr]] + el / 6) * a.N + a.spos[6 * pair_ij[2 * pr + 1]] + el % 6;
-  *dst = (kStore ? 0.0 : *dst) - sum;
 }
 
 // ---- K3c --------------------------------------------------------------------------------------
@@ -1199,13 +637,6 @@ __global__ __launch_bounds__(256) void k_norms_partial(int C, int P, const doubl
 }
 
 // ---- host driver ----------------------------------------------------------------------------------
-static bool InGroup(const pp_ba_impl* h) { return h->comm != nullptr || h->allreduce != nullptr; }
-// The tile pattern of a block-sparse reduced system is built from THIS rank's pair lists.  In a point-sharded group the all-reduced
-// system has the union of every rank's co-visibility: a tile whose shared points all live on another rank is non-zero after the
-// exchange, and a rank that skipped it would factor a different matrix than its peers (replicated poses diverging between ranks).
-// So the block-sparse path is only taken outside a group; attaching / detaching a communicator or callback switches it.
-// (inside a point-sharded group only when the tile map is the group's: built from the union co-visibility every rank was given, pp_ba_problem_desc::covisibility)
-static bool SparseActive(const pp_ba_impl* h) { return h->sparse_tiles && (!InGroup(h) || h->structure_from_covisibility); }
 // (re)binds the factorisation to the handle's current state: the tile map (or none) and the solved-tile array of the one-launch path
 // (allocated only when that path can run: N x N doubles, 7 GB at 5000 images)
 static int ApplyLinearSolverStructure(pp_ba_impl* h) {
@@ -1218,7 +649,7 @@ static int ApplyLinearSolverStructure(pp_ba_impl* h) {
   // (the solution comes out in the reduced system's column order: the vectors' order unless the intrinsics sit beside their images' pose columns)
   const CholeskySystem sys{h->S, h->N, h->n_red, h->Linv, h->Lfac, h->spos_identity ? h->step_c : h->step_s, h->d_flag, h->stream};
   bool new_map = false;
-  { const int rc = CholeskyBind(h->chol, sys, SparseActive(h) ? h->tile_nz.data() : nullptr, &new_map); if (rc) return rc; }
+  { const int rc = CholeskyBind(h->chol, sys, BaSparseActive(h) ? h->tile_nz.data() : nullptr, &new_map); if (rc) return rc; }
   // whatever an earlier factorisation left outside the tiles the new structure rewrites
   if (new_map) PP_HIP_TRY(hipMemsetAsync(h->S, 0, sizeof(double) * (size_t)h->N * h->N, h->stream));
   return PP_OK;
@@ -1257,16 +688,6 @@ __global__ __launch_bounds__(256) void k_gather_step(int n, const int32_t* __res
   if (v < n) step[v] = x[spos[v]];
 }
 
-static SchurArgs MakeSchurArgs(pp_ba_impl* h, double radius) {
-  SchurArgs a;
-  a.C = h->C; a.N = h->N; a.rhs_row = h->n_red;
-  a.pose_start = h->pose_start; a.pose_obs = h->pose_obs; a.obs_point = h->obs_point;
-  a.Jpose = h->Jpose; a.Jpoint = h->Jpoint; a.U = h->U; a.gc = h->gc; a.Vinv = h->Vinv; a.vb = h->vb;
-  a.scale_c = h->scale_c; a.scale_p = h->scale_p; a.diag_c = h->diag_c;
-  a.inv_radius = 1.0 / radius; a.S = h->S; a.add_diagonal = h->group_rank == 0 ? 1 : 0;
-  a.spos = h->spos;
-  return a;
-}
 static StepArgs MakeStepArgs(pp_ba_impl* h) {
   StepArgs a;
   a.C = h->C; a.P = h->P; a.M = h->M;
@@ -1277,7 +698,9 @@ static StepArgs MakeStepArgs(pp_ba_impl* h) {
   return a;
 }
 
-static int GroupReduce(pp_ba_impl* h, double* ptr, int64_t count, int op) {
+// the group exchange (declared in ba_impl.hpp: the assembly and the PCG loop use it too)
+bool BaInGroup(const pp_ba_impl* h) { return h->comm != nullptr || h->allreduce != nullptr; }
+int BaGroupReduce(pp_ba_impl* h, double* ptr, int64_t count, int op) {
   if (h->comm) return CommAllReduce(h->comm, ptr, count, op, h->stream);      // stream-ordered: no host synchronisation
   if (!h->allreduce) return PP_OK;
   PP_HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1285,48 +708,15 @@ static int GroupReduce(pp_ba_impl* h, double* ptr, int64_t count, int op) {
   if (rc) { SetLastError("allreduce callback returned %d", rc); return PP_ERR_INVALID; }
   return PP_OK;
 }
-bool BaInGroup(const pp_ba_impl* h) { return InGroup(h); }
-int BaGroupReduce(pp_ba_impl* h, double* ptr, int64_t count, int op) { return GroupReduce(h, ptr, count, op); }
-// several GroupReduce calls of one exchange become ONE RCCL launch (no-ops with a host callback)
-static int GroupBegin(pp_ba_impl* h) { return h->comm ? CommGroupStart() : PP_OK; }
 static int GroupEnd(pp_ba_impl* h) { return h->comm ? CommGroupEnd() : PP_OK; }
-// one exchange = GroupBegin .. GroupEnd; an error return in between must not leave the ncclGroupStart open (the communicator
-// would be unusable for every later call): the scope closes it on every path
-struct GroupScope {
-  pp_ba_impl* h; bool open = false;
-  explicit GroupScope(pp_ba_impl* hh) : h(hh) {}
-  int Begin() { const int rc = GroupBegin(h); open = rc == PP_OK; return rc; }
-  int End() { open = false; return GroupEnd(h); }
-  ~GroupScope() { if (open) (void)GroupEnd(h); }
-};
+int GroupScope::Begin() { const int rc = h->comm ? CommGroupStart() : PP_OK; open = rc == PP_OK; return rc; }
+int GroupScope::End() { open = false; return GroupEnd(h); }
+GroupScope::~GroupScope() { if (open) (void)GroupEnd(h); }
 // The failure bits (d_flag[0]: 1 = pivot, 2 = point block, 4 = a bounded wait of the one-launch factorisation ran out) are rank-local,
 // the decisions they drive (invalid step, retry with per-column launches) issue collectives: every rank of a group must take the same
 // one.  The bits travel as a double through the unused device slot kTicketSlot, MAX-reduced with the scalars of the trial step.
 __global__ void k_flag_to_scalar(const int32_t* __restrict__ flag, double* __restrict__ slot) { *slot = (double)(*flag & 7); }
 __global__ void k_scalar_to_flag(const double* __restrict__ slot, int32_t* __restrict__ flag) { const int v = (int)*slot; if (v) atomicOr(flag, v); }
-
-// lower triangle + rhs row of S (rows 0 .. n_red, row r = r + 1 entries) <-> a contiguous buffer: the group exchange moves
-// (n+1)(n+2)/2 doubles (36 MB at 500 images) instead of the (n+1) x N rectangle (72 MB)
-__global__ __launch_bounds__(256) void k_pack_lower(const double* __restrict__ S, int N, int rows, double* __restrict__ packed, int unpack, double* __restrict__ Sout) {
-  const int r = blockIdx.y;
-  const size_t base = (size_t)r * (r + 1) / 2;
-  for (int c = blockIdx.x * 256 + threadIdx.x; c <= r && r < rows; c += gridDim.x * 256) {
-    if (unpack) Sout[(size_t)r * N + c] = packed[base + c];
-    else packed[base + c] = S[(size_t)r * N + c];
-  }
-}
-
-// the same for a block-sparse system (a group whose ranks were created with the union co-visibility: the same tile map everywhere): only the non-zero
-// 64 x 64 tiles travel - 12 MB instead of 36 at banded cfg 3 ("exploit block sparsity of S when cameras don't co-observe")
-__global__ __launch_bounds__(256) void k_pack_tiles(const double* __restrict__ S, int N, const int32_t* __restrict__ tiles, double* __restrict__ packed, int unpack, double* __restrict__ Sout) {
-  const int ti = tiles[2 * blockIdx.x], tj = tiles[2 * blockIdx.x + 1];
-  double2* pk = reinterpret_cast<double2*>(packed + (size_t)blockIdx.x * 64 * 64);
-  for (int idx = threadIdx.x; idx < 64 * 32; idx += 256) {
-    const size_t at = ((size_t)ti * 64 + (idx >> 5)) * N + (size_t)tj * 64 + 2 * (idx & 31);
-    if (unpack) *reinterpret_cast<double2*>(Sout + at) = pk[idx];
-    else pk[idx] = *reinterpret_cast<const double2*>(S + at);
-  }
-}
 
 // K1 (Jacobian) + K2 at the current parameters; leaves cost in scal[kCost]
 // fold_cost: the cost partials are summed by the LaunchNorms call that follows (fold = 1) instead of a kernel of their own
@@ -1338,13 +728,13 @@ static int EvaluateAndReduce(pp_ba_impl* h, bool fold_cost = false) {
                      h->Jpoint, h->r, h->U, h->gc, h->V, h->gp);
   PP_HIP_TRY(hipGetLastError());
   if ((rc = IntrSumsAfterEval(h))) return rc;
-  if (InGroup(h)) {      // the per-pose blocks (and the intrinsics sums) of all shards: one exchange
+  if (BaInGroup(h)) {      // the per-pose blocks (and the intrinsics sums) of all shards: one exchange
     GroupScope g(h);
     if ((rc = g.Begin())) return rc;
-    if ((rc = GroupReduce(h, h->U, 36 * (int64_t)h->C, PP_REDUCE_SUM))) return rc;
-    if ((rc = GroupReduce(h, h->gc, (int64_t)h->n_red, PP_REDUCE_SUM))) return rc;
-    if (h->NI > 0 && (rc = GroupReduce(h, h->cnI, (int64_t)h->NI, PP_REDUCE_SUM))) return rc;
-    if (!fold_cost && (rc = GroupReduce(h, h->scal + kCost, 1, PP_REDUCE_SUM))) return rc;
+    if ((rc = BaGroupReduce(h, h->U, 36 * (int64_t)h->C, PP_REDUCE_SUM))) return rc;
+    if ((rc = BaGroupReduce(h, h->gc, (int64_t)h->n_red, PP_REDUCE_SUM))) return rc;
+    if (h->NI > 0 && (rc = BaGroupReduce(h, h->cnI, (int64_t)h->NI, PP_REDUCE_SUM))) return rc;
+    if (!fold_cost && (rc = BaGroupReduce(h, h->scal + kCost, 1, PP_REDUCE_SUM))) return rc;
     if ((rc = g.End())) return rc;
   }
   return PP_OK;
@@ -1366,7 +756,7 @@ static int LaunchNorms(pp_ba_impl* h, bool with_step, int fold = 0, double* host
     hipLaunchKernelGGL(k_norms_intr, dim3(1), dim3(kNormsIntrThreads), 0, h->stream, h->K, h->C, h->intr_off, h->intr_nv, h->cam_np, h->intr, h->gc, h->scale_c,
                        with_step ? h->step_c : nullptr, h->scal, h->group_rank == 0 ? 1 : 0, host_slot, ticket);
   PP_HIP_TRY(hipGetLastError());
-  if (InGroup(h)) {
+  if (BaInGroup(h)) {
     // one exchange for the scalars of this evaluation: the gradient max norm as a max; |step|^2 and |x|^2 as sums (the point
     // parts are sharded, the replicated pose / intrinsics parts were counted on rank 0 only: parameter_tolerance sees the
     // same global norms on every rank); the sums this call folded (cost, or candidate cost + model cost change) as sums
@@ -1375,117 +765,14 @@ static int LaunchNorms(pp_ba_impl* h, bool with_step, int fold = 0, double* host
     {
       GroupScope g(h);
       if ((rc = g.Begin())) return rc;
-      if ((rc = GroupReduce(h, h->scal + kGradMax, 1, PP_REDUCE_MAX))) return rc;
-      if ((rc = GroupReduce(h, h->scal + kStepNorm2, 2, PP_REDUCE_SUM))) return rc;          // kStepNorm2, kXNorm2 are adjacent
-      if (fold == 1 && (rc = GroupReduce(h, h->scal + kCost, 1, PP_REDUCE_SUM))) return rc;
-      if (fold == 2 && (rc = GroupReduce(h, h->scal + kCostCand, 2, PP_REDUCE_SUM))) return rc;   // kCostCand, kModelChange are adjacent
-      if (with_step && (rc = GroupReduce(h, h->scal + kTicketSlot, 1, PP_REDUCE_MAX))) return rc;    // the failure bits: every rank sees the worst
+      if ((rc = BaGroupReduce(h, h->scal + kGradMax, 1, PP_REDUCE_MAX))) return rc;
+      if ((rc = BaGroupReduce(h, h->scal + kStepNorm2, 2, PP_REDUCE_SUM))) return rc;          // kStepNorm2, kXNorm2 are adjacent
+      if (fold == 1 && (rc = BaGroupReduce(h, h->scal + kCost, 1, PP_REDUCE_SUM))) return rc;
+      if (fold == 2 && (rc = BaGroupReduce(h, h->scal + kCostCand, 2, PP_REDUCE_SUM))) return rc;   // kCostCand, kModelChange are adjacent
+      if (with_step && (rc = BaGroupReduce(h, h->scal + kTicketSlot, 1, PP_REDUCE_MAX))) return rc;    // the failure bits: every rank sees the worst
       if ((rc = g.End())) return rc;
     }
     if (with_step) hipLaunchKernelGGL(k_scalar_to_flag, dim3(1), dim3(1), 0, h->stream, h->scal + kTicketSlot, h->d_flag);
-    PP_HIP_TRY(hipGetLastError());
-  }
-  return PP_OK;
-}
-
-// the group exchange's packed copy of S holds at least `count` doubles (grown, never shrunk; the old content is not kept)
-static int EnsureSpack(pp_ba_impl* h, int64_t count) {
-  if (h->Spack_cap >= count) return PP_OK;
-  h->blocks.Free(&h->Spack);
-  h->Spack_cap = 0;
-  PP_TRY(h->blocks.Alloc(&h->Spack, (size_t)count));
-  h->Spack_cap = count;
-  return PP_OK;
-}
-
-// assemble the damped reduced system for `radius` into S (lower triangle + rhs row)
-static int AssembleReducedSystem(pp_ba_impl* h, double radius, bool refresh_diagonal = false, double dmin = 0.0, double dmax = 0.0) {
-  hipStream_t s = h->stream;
-  // The factorisation overwrites S with L (fill-in included), so blocks without a pair list must be cleared again;
-  // when every block has one (dense scenes), the assembly kernels rewrite the whole lower triangle and the padding
-  // rows keep their zeros (cleared once at allocation): no 72 MB clear, no read-modify-write in k_schur_pairs.
-  // (variable intrinsics: beside their images' pose columns they are part of the images' blocks, all of which are rewritten (k_schur_wide_*); behind the pose
-  // columns - the vectors' order - their rows are cleared, a few rows, and the pose part is stored as without them; other layouts clear S)
-  const bool store_blocks = h->pairs_complete && !h->iterative && !InGroup(h) && (h->NI == 0 || h->intr_wide_nv > 0 || h->spos_identity);
-  const int zero_tiles = (!store_blocks && !h->iterative && SparseActive(h)) ? h->num_nz_tiles : 0;      // (only the tiles anything is written to: k_prepare's third role)
-  if (!store_blocks && !h->iterative && !zero_tiles) PP_HIP_TRY(hipMemsetAsync(h->S, 0, sizeof(double) * (size_t)h->N * h->N, s));
-  if (store_blocks && h->NI > 0 && h->spos_identity) PP_HIP_TRY(hipMemsetAsync(h->S + (size_t)6 * h->C * h->N, 0, sizeof(double) * (size_t)h->NI * h->N, s));
-  {      // (V + D^2 / radius)^-1, V^-1 b_p per point and the per-observation records: one launch
-    const int point_blocks = CeilDiv(refresh_diagonal ? std::max(h->P, 6 * h->C) : h->P, 256);
-    const dim3 grid(point_blocks + h->num_partials + zero_tiles);
-    hipLaunchKernelGGL(refresh_diagonal ? k_prepare<true> : k_prepare<false>, grid, dim3(256), 0, s, point_blocks, h->P, h->V, h->gp, h->scale_p, h->diag_p, h->point_const,
-                       1.0 / radius, h->Vinv, h->vb, h->d_flag, h->C, h->U, h->scale_c, dmin, dmax, h->diag_c, h->M, h->obs_pose, h->obs_point, h->Jpose, h->Jpoint, h->JpS,
-                       h->num_partials, h->S, h->N, (const int32_t*)h->nz_tile_list);
-  }
-  SchurArgs a = MakeSchurArgs(h, radius);
-  if (h->iterative) { a.Sd = h->pcg_Sd; a.rhs_out = h->pcg_b; }
-  if (h->iterative) {      // the diagonal blocks (preconditioner) and the reduced right-hand side; S itself is applied from the records
-    hipLaunchKernelGGL(k_schur_self_rhs, dim3(h->C), dim3(256), 0, s, a, h->JpS);
-    PP_HIP_TRY(hipGetLastError());
-    if (InGroup(h)) {      // every shard's part of the diagonal blocks and of the right-hand side (rank 0 carries U + D^2 and -g)
-      GroupScope g(h);
-      int rc;
-      if ((rc = g.Begin())) return rc;
-      if ((rc = GroupReduce(h, h->pcg_Sd, 36 * (int64_t)h->C, PP_REDUCE_SUM))) return rc;
-      if ((rc = GroupReduce(h, h->pcg_b, 6 * (int64_t)h->C, PP_REDUCE_SUM))) return rc;
-      if ((rc = g.End())) return rc;
-    }
-    { const int rc = IntrAssemble(h, 1.0 / radius, a.add_diagonal); if (rc) return rc; }      // (variable intrinsics: their diagonal blocks and their part of the right-hand side)
-    if (InGroup(h) && h->NI > 0) {      // the per-camera sums of every shard: the compact diagonal blocks (the preconditioner's) and the intrinsics rows of the right-hand side
-      GroupScope g(h);
-      int rc;
-      if ((rc = g.Begin())) return rc;
-      if ((rc = GroupReduce(h, h->pcg_Scomp, 12 * (int64_t)h->NI, PP_REDUCE_SUM))) return rc;
-      if ((rc = GroupReduce(h, h->pcg_b + 6 * (size_t)h->C, (int64_t)h->NI, PP_REDUCE_SUM))) return rc;
-      if ((rc = g.End())) return rc;
-    }
-    return PP_OK;
-  }
-  if (h->pairs_chunked && h->num_pairs > 0) {      // long lists (few images, many shared points): chunks of the lists, then the blocks from their chunks
-    hipLaunchKernelGGL(k_schur_self_chunks, dim3(h->C + CeilDiv(h->small_num_chunks, 40)), dim3(256), 0, s, a, h->JpS, h->small_num_chunks, h->small_chunk, h->pair_entries,
-                       h->small_partials);
-    const dim3 grid(CeilDiv(36 * h->num_pairs, 256));
-    if (store_blocks) hipLaunchKernelGGL(k_schur_chunk_reduce<true>, grid, dim3(256), 0, s, a, h->num_pairs, h->pair_ij, h->small_pair_chunk, h->small_partials);
-    else hipLaunchKernelGGL(k_schur_chunk_reduce<false>, grid, dim3(256), 0, s, a, h->num_pairs, h->pair_ij, h->small_pair_chunk, h->small_partials);
-  } else if (h->intr_wide_nv > 0) {      // every image's 6 + n_v columns as one block: the pose gather with wider rows
-    { const int rc = IntrScaledJacobians(h); if (rc) return rc; }
-    const int W = 6 + h->intr_wide_nv;
-    const dim3 gp((unsigned)CeilDiv(h->num_pairs, (int64_t)(4 * (64 / W))));
-#define PP_WIDE(NV) do { \
-      hipLaunchKernelGGL(k_schur_wide_self<NV>, dim3(h->C), dim3(256), 0, s, a, h->JpS, h->JkS_intr, h->pose_camera, h->intr_off); \
-      if (h->num_pairs > 0) { \
-        if (store_blocks) hipLaunchKernelGGL((k_schur_wide_pairs<NV, true>), gp, dim3(256), 0, s, a, h->JpS, h->JkS_intr, h->num_pairs, h->pair_start, h->pair_ij, h->pair_entries); \
-        else hipLaunchKernelGGL((k_schur_wide_pairs<NV, false>), gp, dim3(256), 0, s, a, h->JpS, h->JkS_intr, h->num_pairs, h->pair_start, h->pair_ij, h->pair_entries); } } while (0)
-    switch (h->intr_wide_nv) { case 2: PP_WIDE(2); break; case 4: PP_WIDE(4); break; case 6: PP_WIDE(6); break; default: PP_WIDE(8); break; }
-#undef PP_WIDE
-  } else if (store_blocks && h->num_pairs > 0) {
-    hipLaunchKernelGGL(k_schur_blocks, dim3(h->C + CeilDiv(h->num_pairs, 40)), dim3(256), 0, s, a, h->JpS, h->num_pairs, h->pair_start, h->pair_ij,
-                       h->pair_entries);
-  } else {
-    hipLaunchKernelGGL(k_schur_self_rhs, dim3(h->C), dim3(256), 0, s, a, h->JpS);
-    if (h->num_pairs > 0)
-      hipLaunchKernelGGL(k_schur_pairs<false>, dim3(CeilDiv(h->num_pairs, 40)), dim3(256), 0, s, a, h->JpS, h->num_pairs, h->pair_start, h->pair_ij,
-                         h->pair_entries);
-  }
-  PP_HIP_TRY(hipGetLastError());
-  { const int rc = IntrAssemble(h, 1.0 / radius, a.add_diagonal); if (rc) return rc; }
-  if (InGroup(h) && SparseActive(h) && h->nz_tile_list && h->num_nz_tiles > 0) {      // the non-zero tiles, packed (every rank has the group's tile map)
-    const int64_t count = (int64_t)h->num_nz_tiles * 64 * 64;
-    if (const int rc = EnsureSpack(h, count)) return rc;
-    hipLaunchKernelGGL(k_pack_tiles, dim3(h->num_nz_tiles), dim3(256), 0, s, h->S, h->N, (const int32_t*)h->nz_tile_list, h->Spack, 0, (double*)nullptr);
-    const int rc = GroupReduce(h, h->Spack, count, PP_REDUCE_SUM);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_pack_tiles, dim3(h->num_nz_tiles), dim3(256), 0, s, (const double*)nullptr, h->N, (const int32_t*)h->nz_tile_list, h->Spack, 1, h->S);
-    PP_HIP_TRY(hipGetLastError());
-  } else if (InGroup(h)) {      // lower triangle + rhs row, packed: half the bytes of the rectangle on the wire (RCCL or the host callback)
-    const int rows = h->n_red + 1;
-    const int64_t count = (int64_t)rows * (rows + 1) / 2;
-    if (const int rc = EnsureSpack(h, count)) return rc;
-    const dim3 grid(std::max(1, std::min(64, CeilDiv(rows, 256))), rows);
-    hipLaunchKernelGGL(k_pack_lower, grid, dim3(256), 0, s, h->S, h->N, rows, h->Spack, 0, (double*)nullptr);
-    const int rc = GroupReduce(h, h->Spack, count, PP_REDUCE_SUM);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_pack_lower, grid, dim3(256), 0, s, (const double*)nullptr, h->N, rows, h->Spack, 1, h->S);
     PP_HIP_TRY(hipGetLastError());
   }
   return PP_OK;
@@ -1569,7 +856,7 @@ static StepPlan MakeStepPlan(const pp_ba_impl* h, const pp_ba_options* o) {
   StepPlan p;
   p.fold = h->allreduce == nullptr;
   p.speculate = h->allreduce == nullptr;
-  p.direct = p.speculate && !InGroup(h) && h->h_scal_dev != nullptr;
+  p.direct = p.speculate && !BaInGroup(h) && h->h_scal_dev != nullptr;
   p.fused_trial_cost = p.fold && (h->NI == 0 || h->sw.ba_fused_step) && h->sw.ba_fused_trial_cost;
   p.fused_step = p.fused_trial_cost && h->sw.ba_fused_step;
   p.phase_timings = o->phase_timings != 0;
@@ -1584,7 +871,7 @@ static int EnqueueTrialStep(pp_ba_impl* h, const pp_ba_options* o, const StepPla
   const int grid_obs = h->num_partials;
   int rc;
   if (refresh_diagonal && (rc = IntrDiagonal(h, o->min_lm_diagonal, o->max_lm_diagonal))) return rc;
-  if ((rc = AssembleReducedSystem(h, radius, refresh_diagonal, o->min_lm_diagonal, o->max_lm_diagonal))) return rc;
+  if ((rc = BaAssembleReducedSystem(h, radius, refresh_diagonal, o->min_lm_diagonal, o->max_lm_diagonal))) return rc;
   timer.Mark(PP_BA_T_SCHUR);
   if (h->iterative) {
     int cg = 0;
@@ -1623,7 +910,7 @@ static int EnqueueTrialStep(pp_ba_impl* h, const pp_ba_options* o, const StepPla
   if (!plan.fused_trial_cost && (rc = LaunchCostOnly(h, h->poses_c, h->points_c, h->NI > 0 ? h->intr_c : nullptr, plan.fold ? nullptr : h->scal + kCostCand))) return rc;
   PP_HIP_TRY(hipGetLastError());
   if (h->allreduce) {      // (host callback: the two sums exist before the norms kernel here; with RCCL the norms call reduces what it folded)
-    if ((rc = GroupReduce(h, h->scal + kCostCand, 2, PP_REDUCE_SUM))) return rc;   // kCostCand, kModelChange are adjacent
+    if ((rc = BaGroupReduce(h, h->scal + kCostCand, 2, PP_REDUCE_SUM))) return rc;   // kCostCand, kModelChange are adjacent
   }
   *ticket = plan.direct ? ++h->ticket_seq : 0;
   if ((rc = LaunchNorms(h, true, plan.fold ? 2 : 0, plan.direct ? h->h_scal_dev : nullptr, *ticket))) return rc;
@@ -1748,7 +1035,7 @@ int BaAssembleUndamped(pp_ba_impl* h, const pp_ba_options* o, bool evaluate) {
   }
   PP_HIP_TRY(hipMemsetAsync(h->diag_c, 0, sizeof(double) * (size_t)h->n_red, h->stream));
   PP_HIP_TRY(hipMemsetAsync(h->diag_p, 0, sizeof(double) * 3 * (size_t)h->P, h->stream));
-  return AssembleReducedSystem(h, HUGE_VAL);      // 1 / radius == 0.0
+  return BaAssembleReducedSystem(h, HUGE_VAL);      // 1 / radius == 0.0
 }
 
 }  // namespace ppsfm
@@ -1843,11 +1130,11 @@ int pp_ba_get_structure(pp_ba_handle h, int32_t* info) try {
   info[1] = h->nnz_tiles_natural >= 0 ? h->nnz_tiles_natural : h->num_nz_tiles;
   info[2] = h->num_nz_tiles;
   info[3] = h->pose_new_of_old.empty() ? 0 : 1;
-  info[4] = SparseActive(h) ? 1 : 0;
+  info[4] = BaSparseActive(h) ? 1 : 0;
   info[5] = h->iterative ? 1 : 0;
   // the chains of the one-launch factorisation (several: a nested-dissection order whose sub-trees are factorised side by side) and its chain steps
   info[6] = 1; info[7] = T;
-  if (SparseActive(h) && T >= 4 && T <= 128 && !h->tile_nz.empty()) {
+  if (BaSparseActive(h) && T >= 4 && T <= 128 && !h->tile_nz.empty()) {
     if (h->structure_steps < 0) h->structure_steps = CholeskyChainSteps(T, h->tile_nz.data(), h->sw, &h->structure_chains);      // (planned once per handle; the plan itself is cached per tile map)
     info[6] = h->structure_chains; info[7] = h->structure_steps;
   }
@@ -1888,7 +1175,7 @@ int pp_ba_reduced_system(pp_ba_handle h, const pp_ba_options* o, double radius, 
   hipLaunchKernelGGL(k_lm_diagonal, dim3(grid), dim3(256), 0, h->stream, h->C, h->P, h->U, h->V, h->scale_c, h->scale_p, o->min_lm_diagonal,
                      o->max_lm_diagonal, h->diag_c, h->diag_p);
   if ((rc = IntrDiagonal(h, o->min_lm_diagonal, o->max_lm_diagonal))) return rc;
-  if ((rc = AssembleReducedSystem(h, radius))) return rc;
+  if ((rc = BaAssembleReducedSystem(h, radius))) return rc;
   const int n = h->n_red;
   *n_out = n;
   if (S) {
@@ -1931,7 +1218,7 @@ int pp_ba_solve(pp_ba_handle h, const pp_ba_options* o, pp_ba_summary* sum) try 
   {
     PhaseTimer timer(h, plan.phase_timings);
     if ((rc = EvaluateAndScale(h, o, plan.fold, timer))) return rc;
-    if (!InGroup(h) && h->h_scal_dev != nullptr) {      // the scalars reach the host without the copy engine when nothing else touches them after the norms kernel
+    if (!BaInGroup(h) && h->h_scal_dev != nullptr) {      // the scalars reach the host without the copy engine when nothing else touches them after the norms kernel
       const unsigned long long ticket = ++h->ticket_seq;
       if ((rc = LaunchNorms(h, false, plan.fold ? 1 : 0, h->h_scal_dev, ticket))) return rc;
       if ((rc = WaitTicket(h, ticket))) return rc;

@@ -455,7 +455,7 @@ inline void BuildIntrinsicsLists(BaStructure* st) {
     BuildPointCameraGroups(*st, &cam, &start, &obs); BuildDiagonalLists(*st, cam, start, obs, st->gen);
   } else if (st->intr_wide_nv > 0) {
     // every image carries its own intrinsics beside its pose columns: its 6 + n_v columns are ONE block, assembled by the pose blocks' own gather over the
-    // pair lists with wider rows (k_schur_wide_self / k_schur_wide_pairs, ba_solver.hip) - no lists of their own
+    // pair lists with wider rows (k_schur_wide_self / k_schur_wide_pairs, ba_schur.hip) - no lists of their own
     st->gen.pair_chunk.push_back(0);
   } else {
     BuildFactoredLists(st);

@@ -128,6 +128,32 @@ __device__ __forceinline__ double WaveSumDpp(double v) {
   return (r0 + r1) + (r2 + r3);
 }
 
+// The N running values of every lane summed over a workgroup of FOUR wavefronts in a fixed order: wavefront sums (WaveSumDpp), lane 0 of each
+// wavefront stores its totals, one barrier, thread i < N gets *sum = ((r0 + r1) + r2) + r3 of value i and true (the other threads false).
+// red: the kernel's one __shared__ array; v is left holding the wavefront totals.
+template <int N>
+__device__ __forceinline__ bool WorkgroupSum4(double (&v)[N], double (&red)[4][N], double* sum) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = WaveSumDpp(v[i]);
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) red[wv][i] = v[i];
+  }
+  __syncthreads();
+  const int i = threadIdx.x;
+  if (i >= N) return false;
+  *sum = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
+  return true;
+}
+// entry i of the upper triangle of a W x W matrix, rows one after the other ((0,0) .. (0,W-1), (1,1) ..): its row *x and column *y >= *x
+template <int W>
+__device__ __forceinline__ void UpperTriangleIndex(int i, int* x, int* y) {
+  int a = 0, rem = i;
+  while (rem >= W - a) { rem -= W - a; ++a; }
+  *x = a; *y = a + rem;
+}
+
 // sum / maximum over each 16-lane row (every lane of a row ends with its row's value): the DPP part of the above
 __device__ __forceinline__ double RowSumDpp(double v) {
   v += DppMove<0xB1>(v); v += DppMove<0x4E>(v); v += DppMove<0x141>(v); v += DppMove<0x140>(v);

@@ -500,7 +500,7 @@ def test_sequence_scene_with_variable_intrinsics_takes_the_block_sparse_path(ora
 @pytest.mark.parametrize("model,const_bits,nv", [(2, 0b0110, 2), (2, 0, 4), (1, 0b1100, 2), (4, 0b00001100, 6), (4, 0, 8)])
 def test_camera_per_image_wide_blocks_equal_the_general_block_pairs(oracle, monkeypatch, model, const_bits, nv):
     """A camera per image with n_v variable parameters beside its pose columns: the image's 6 + n_v columns are assembled as ONE block by the pose gather with
-    wider rows (ba_solver.hip k_schur_wide_self / k_schur_wide_pairs, n_v = 2, 4, 6, 8) instead of the block-pair lists built for shared cameras
+    wider rows (ba_schur.hip k_schur_wide_self / k_schur_wide_pairs, n_v = 2, 4, 6, 8) instead of the block-pair lists built for shared cameras
     (ba_intr.hip; PPSFM_BA_INTR_WIDE=0 keeps them).  The same reduced system to rounding - with constant poses in the middle of the sequence (their
     intrinsics still couple with their neighbours': every image is listed), constant points (direct terms only) and a point seen twice by one image -
     and the oracle's system and solve (bundle_adjustment.cc:490-528)."""
