@@ -13,19 +13,19 @@
 //   k_pcg_points   per point (four lanes):   a_p = sum_{o in p} J_p,o^T (J^_c,o v_c(o))
 //   k_pcg_images   per image (one workgroup): (S v)_c = sum_{o in c} J^_c,o^T (J^_c,o v_c - T_o a_p(o)) + d_c v_c, and v_c . (S v)_c
 // both HBM/L2-bound gathers of 144 of a record's 192 bytes per observation (algorithmic: 2 x 144 B per observation and product).
-// The vector updates, dot products (fixed order: deterministic) and the termination test of an iteration: k_pcg_wide_a / _b (many
-// workgroups, two launches).  The host enqueues a few iterations at a time and reads the state back; once the loop has ended the kernels
-// already in the stream return at their first instruction.  That four-launch form is what point-sharded groups and variable intrinsics run.
+// The vector updates and dot products (fixed order: deterministic) of an iteration: k_pcg_step (many workgroups); the termination test and
+// the new direction: k_pcg_wide_b (a second launch).  The host enqueues a few iterations at a time and reads the state back; once the loop
+// has ended the kernels already in the stream return at their first instruction.  That four-launch form (k_pcg_points, k_pcg_images,
+// k_pcg_step, k_pcg_wide_b) is what point-sharded groups and variable intrinsics run.
 // DEFAULT otherwise: three launches per iteration (k_pcg_points_q, k_pcg_images_q, k_pcg_step - see below): the product kernels take the
-// decision and form the direction themselves.  PPSFM_PCG_FUSED=0 selects the four-launch form (tests compare the two).
+// decision and form the direction themselves, k_pcg_wide_b is not launched.  PPSFM_PCG_FUSED=0 selects the four-launch form (tests compare
+// the two).  Both forms share the rules of the loop (PcgAdvance) and the vector step (k_pcg_step); each sums in its own fixed order.
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
-#include <thread>
 
 #include "ba_impl.hpp"
+#include "host_ticket.hpp"
 #include "resource_pool.hpp"
 
 namespace ppsfm {
@@ -33,21 +33,17 @@ namespace ppsfm {
 constexpr int kResidualResetPeriod = 10;      // ConjugateGradientsSolver::Options::residual_reset_period
 enum { kPcgRunning = 0, kPcgConverged = 1, kPcgNoConvergence = 2, kPcgFailure = 3 };
 
-// inverse of the two 3x3 diagonal blocks (rotation tangent, translation) of every image's 6x6 diagonal block of S
-__global__ __launch_bounds__(256) void k_pcg_block_inverse(int C, const double* __restrict__ Sd, double* __restrict__ binv, int32_t* __restrict__ flag) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 2 * C) return;
-  const int c = i >> 1, h = i & 1;
-  const double* B = Sd + 36 * (size_t)c + 21 * h;      // rows 3h.., columns 3h..
-  const double a = B[0], b = B[1], cc = B[2], d = B[7], e = B[8], f = B[14];
+// inverse of a symmetric 3x3 block that sits in a 6x6 row-major diagonal block of S (D: its first entry; rotation tangent: rows 0.., translation:
+// rows 3..).  false: the block is not positive, or not finite
+__device__ __forceinline__ bool InverseSym3(const double* __restrict__ D, double* o) {
+  const double a = D[0], b = D[1], cc = D[2], d = D[7], e = D[8], f = D[14];
   const double c00 = d * f - e * e, c01 = cc * e - b * f, c02 = b * e - cc * d;
   const double det = a * c00 + b * c01 + cc * c02;
-  if (!(det > 0.0) || !isfinite(det)) atomicOr(flag, 1);
   const double id = 1.0 / det;
-  double* o = binv + 18 * (size_t)c + 9 * h;
   o[0] = c00 * id; o[1] = c01 * id; o[2] = c02 * id;
   o[3] = c01 * id; o[4] = (a * f - cc * cc) * id; o[5] = (b * cc - a * e) * id;
   o[6] = c02 * id; o[7] = (b * cc - a * e) * id; o[8] = (a * d - b * b) * id;
+  return det > 0.0 && isfinite(det);
 }
 
 __global__ __launch_bounds__(256) void k_pcg_points(int P, const int32_t* __restrict__ pt_start, const int32_t* __restrict__ pt_obs,
@@ -136,14 +132,15 @@ __global__ __launch_bounds__(256) void k_pcg_images(int C, const int32_t* __rest
 }
 
 // ---- the vector step over MANY workgroups (a single workgroup was 12.5 us at 1100 images and 30 us at 4000 - the longest kernel of an
-// iteration there).  Two launches, a thread per 3 x 3 parameter block:
-//   k_pcg_wide_a   alpha = rho / (p . S p) from the per-image parts (every workgroup sums them itself, in the same order: the same
+// iteration there).  A thread per 3 x 3 parameter block:
+//   k_pcg_step     alpha = rho / (p . S p) from the per-image parts (every workgroup sums them itself, in the same order: the same
 //                  bits everywhere, no exchange), x += alpha p, r -= alpha q (or the explicit residual), z = M^-1 r, and this
-//                  workgroup's parts of Q = -x . (b + r) / ... and of r . z
-//   k_pcg_wide_b   every workgroup sums the parts, takes the termination decision (ConjugateGradientsSolver's tests, in its order) and updates its
+//                  workgroup's parts of Q = -x . (b + r) / ... and of r . z; at the start of a solve also M^-1 itself
+//   k_pcg_wide_b   (four-launch form) every workgroup sums the parts, takes the termination decision (PcgAdvance) and updates its
 //                  slice of the direction p = z + beta p
-// The state is read by every workgroup of a launch and written by workgroup 0 of k_pcg_wide_b: it ping-pongs between two copies (a
-// workgroup dispatched late must not find the NEXT iteration's state), the host tracks which one is current.
+// The state is read by every workgroup of a launch and written by workgroup 0 of k_pcg_wide_b (of k_pcg_images_q in the three-launch
+// form): it ping-pongs between two copies (a workgroup dispatched late must not find the NEXT iteration's state), the host tracks which
+// one is current.
 constexpr int kWideThreads = 256;
 // Variable intrinsics on the iterative path (bundle_adjustment.cc:283-286 with :490-528): the NI intrinsics columns follow the 6 C pose columns in
 // every vector of the loop.  Their part of the operator, matrix-free like the rest:
@@ -153,7 +150,7 @@ constexpr int kWideThreads = 256;
 //                  wavefront per camera adds the chunks in order and forms the camera's part of v . S v
 // The preconditioner's intrinsics blocks (SCHUR_JACOBI: one block per parameter block) are the diagonal blocks S_kk, assembled per trial radius
 // from the (k, k) pair lists alone (IntrAssemble into pcg_Scomp) and inverted by k_pcg_intr_inverse; the vector step treats a camera's block in
-// one thread (workgroups behind the pose workgroups of k_pcg_wide_a / _b).  The four-launch form of the loop runs these (7 launches per iteration).
+// one thread (workgroups behind the pose workgroups of k_pcg_step<true> / k_pcg_wide_b).  The four-launch form of the loop runs these (7 launches per iteration).
 struct PcgIntr {
   int K = 0, pose_blocks = 1 << 30;      // cameras; the workgroups before the intrinsics' ones
   const int32_t* intr_off = nullptr; const int32_t* intr_nv = nullptr;
@@ -280,172 +277,27 @@ __device__ __forceinline__ double WideBlockSum(double v, double* red) {      // 
   __syncthreads();
   return ((red[0] + red[1]) + red[2]) + red[3];
 }
-// mode 0: start (x = 0, r = b); 1: after q = S p of iteration `it`; 2: after q = S x (explicit residual).  part: 4 doubles per workgroup
-// [Q part (mode 0: |b|^2 part) | r . z part | status | alpha]
-__global__ __launch_bounds__(kWideThreads) void k_pcg_wide_a(int mode, int it, int C, const double* __restrict__ b, double* __restrict__ x, double* __restrict__ r,
-                                                             double* __restrict__ z, const double* __restrict__ p, const double* __restrict__ q,
-                                                             const double* __restrict__ binv, const double* __restrict__ dotp, const PcgState* __restrict__ st,
-                                                             double* __restrict__ part, PcgIntr in) {
-  __shared__ double red[4];
-  const PcgState s = *st;
-  if (mode != 0 && (s.done || s.iter != it)) return;
-  const int tid = threadIdx.x;
-  double alpha = 0.0;
-  int status = kPcgRunning;
-  if (mode == 1) {
-    double pq = 0.0;
-    for (int c = tid; c < C + in.K; c += kWideThreads) pq += dotp[c];      // (per image, then per camera with variable intrinsics)
-    pq = WideBlockSum(pq, red);
-    if (!(pq > 0.0) || isinf(pq)) status = isnan(pq) ? kPcgFailure : kPcgNoConvergence;      // indefinite direction: the iterate so far is the answer
-    else { alpha = s.rho / pq; if (isinf(alpha)) status = kPcgFailure; }
-  }
-  const bool reset = mode == 1 && (it % kResidualResetPeriod) == 0;
-  const int g = blockIdx.x * kWideThreads + tid;      // parameter block: rows 3 g .. 3 g + 2
-  double s0 = 0.0, s1 = 0.0;
-  if ((int)blockIdx.x >= in.pose_blocks) {
-    // ---- the intrinsics blocks (variable intrinsics): a thread per camera, the rows of its block one after the other
-    const int k = ((int)blockIdx.x - in.pose_blocks) * kWideThreads + tid;
-    const int off = k < in.K ? in.intr_off[k] : -1;
-    if (off >= 0 && status == kPcgRunning) {
-      const int nv = in.intr_nv[k];
-      const size_t i0 = 6 * (size_t)C + off;
-      double rn[12], xn[12];
-      for (int j = 0; j < nv; ++j) {
-        const double bj = b[i0 + j];
-        if (mode == 0) { xn[j] = 0.0; rn[j] = bj; x[i0 + j] = 0.0; s0 += bj * bj; }
-        else if (mode == 1) { xn[j] = x[i0 + j] + alpha * p[i0 + j]; x[i0 + j] = xn[j]; rn[j] = reset ? 0.0 : r[i0 + j] - alpha * q[i0 + j]; }
-        else { xn[j] = x[i0 + j]; rn[j] = bj - q[i0 + j]; }
-        if (!reset && mode != 0) s0 -= xn[j] * (bj + rn[j]);
-      }
-      if (!reset) {
-        for (int a = 0; a < nv; ++a) {
-          const double* B = in.binvI + 12 * (size_t)(off + a);
-          double zv = 0.0;
-          for (int j = 0; j < nv; ++j) zv += B[j] * rn[j];
-          z[i0 + a] = zv; r[i0 + a] = rn[a];
-          s1 += rn[a] * zv;
-        }
-      }
-    }
-  } else if (g < 2 * C && status == kPcgRunning) {
-    const size_t i = 3 * (size_t)g;
-    double xv[3], rv[3], bv[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) bv[k] = b[i + k];
-    if (mode == 0) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { xv[k] = 0.0; rv[k] = bv[k]; x[i + k] = 0.0; s0 += bv[k] * bv[k]; }
-    } else if (mode == 1) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { xv[k] = x[i + k] + alpha * p[i + k]; x[i + k] = xv[k]; }
-      if (!reset) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) rv[k] = r[i + k] - alpha * q[i + k];
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { xv[k] = x[i + k]; rv[k] = bv[k] - q[i + k]; }
-    }
-    if (!reset) {
-      if (mode != 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) s0 -= xv[k] * (bv[k] + rv[k]);
-      }
-      const double* B = binv + 9 * (size_t)g;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double zv = B[3 * k] * rv[0] + B[3 * k + 1] * rv[1] + B[3 * k + 2] * rv[2];
-        z[i + k] = zv; r[i + k] = rv[k];
-        s1 += rv[k] * zv;
-      }
-    }
-  }
-  s0 = WideBlockSum(s0, red);
-  s1 = WideBlockSum(s1, red);
-  if (tid == 0) { double* o = part + 4 * (size_t)blockIdx.x; o[0] = s0; o[1] = s1; o[2] = (double)status; o[3] = alpha; }
-}
-// mode 0: start; 1: an iteration's end; 3: after the x-only step of a residual-reset iteration (only carries a failure of that step over)
-__global__ __launch_bounds__(kWideThreads) void k_pcg_wide_b(int mode, int it, int C, int G, const double* __restrict__ z, double* __restrict__ p,
-                                                             const double* __restrict__ part, const PcgState* __restrict__ st, PcgState* __restrict__ st_out,
-                                                             double eta, int max_iterations, int32_t* __restrict__ flag, PcgIntr in) {
-  __shared__ double red[4];
-  PcgState s = *st;
-  const int tid = threadIdx.x;
-  const bool writer = blockIdx.x == 0 && tid == 0;
-  if (mode != 0 && (s.done || s.iter != it)) { if (writer) *st_out = s; return; }      // (both copies say "done" from here on)
-  auto finish = [&](int status) {
-    if (writer) { s.done = 1; s.status = status; *st_out = s; if (status == kPcgFailure) atomicOr(flag, 1); }
-  };
-  double a0 = 0.0, a1 = 0.0;
-  for (int w = tid; w < G; w += kWideThreads) { a0 += part[4 * (size_t)w]; a1 += part[4 * (size_t)w + 1]; }
-  a0 = WideBlockSum(a0, red);
-  a1 = WideBlockSum(a1, red);
-  const int status = (int)part[2];
-  s.alpha = part[3];
-  if (status != kPcgRunning) { finish(status); return; }
-  if (mode == 3) { if (writer) *st_out = s; return; }
-  double beta = 0.0;
-  if (mode == 0) {
-    s.iter = 1; s.done = 0; s.status = kPcgRunning; s.rho = 1.0; s.Q0 = 0.0; s.norm_b = sqrt(a0); s.alpha = 0.0;
-    if (!(a0 > 0.0)) { s.iter = 0; finish(a0 == 0.0 ? kPcgConverged : kPcgFailure); return; }
-  } else {
-    const double zeta = it * (a0 - s.Q0) / a0;
-    if (zeta < eta) { finish(kPcgConverged); return; }
-    if (it >= max_iterations) { finish(kPcgNoConvergence); return; }
-    s.Q0 = a0; s.iter = it + 1;
-  }
-  const double rho = a1;
-  if (rho == 0.0 || isinf(rho) || isnan(rho)) { finish(kPcgFailure); return; }
-  if (mode != 0) {
-    beta = rho / s.rho;
-    if (beta == 0.0 || isinf(beta) || isnan(beta)) { finish(kPcgFailure); return; }
-  }
-  const int g = blockIdx.x * kWideThreads + tid;
-  if ((int)blockIdx.x >= in.pose_blocks) {      // the intrinsics blocks
-    const int k = ((int)blockIdx.x - in.pose_blocks) * kWideThreads + tid;
-    const int off = k < in.K ? in.intr_off[k] : -1;
-    if (off >= 0) {
-      const size_t i0 = 6 * (size_t)C + off;
-      for (int j = 0; j < in.intr_nv[k]; ++j) p[i0 + j] = (mode == 0) ? z[i0 + j] : z[i0 + j] + beta * p[i0 + j];
-    }
-  } else if (g < 2 * C) {
-    const size_t i = 3 * (size_t)g;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) p[i + k] = (mode == 0) ? z[i + k] : z[i + k] + beta * p[i + k];
-  }
-  s.rho = rho;
-  if (writer) *st_out = s;
-}
-
-// ---- THREE launches per iteration (the default outside point-sharded groups).  k_pcg_wide_b is gone: the decision it took and the
-// direction it wrote are taken by the product kernels themselves.
-//   k_pcg_points_q     every wavefront sums the parts of Q and r . z k_pcg_step left (the same order everywhere: the same bits, no
-//                      exchange), takes the termination decision and beta, and forms the direction of the images it touches on the
-//                      fly: p_c = z_c + beta p_old,c (both vectors are L2 resident: 53 KB at 1100 images)
-//   k_pcg_images_q     the same decision, p_c once more for ITS image - stored: the direction buffer ping-pongs, like the state that workgroup 0
-//                      writes - then (S p)_c and the image's part of p . S p
-//   k_pcg_step         alpha, x, r, z = M^-1 r, parts (k_pcg_wide_a with every load issued before the first workgroup sum; at the
-//                      start of a solve it also inverts the diagonal blocks: k_pcg_block_inverse folded in)
-// and the index walks are one level shorter: (observation, image) pairs per point-list entry and (observation, point) pairs per image-list
-// entry (k_pcg_entries, built once per handle), two, four or eight records of a point in flight by the mean track.  The kernels of an iteration are
-// bound by the LATENCY of their dependent loads (344 + 1100 + 9 workgroups at 1100 images, a few microseconds each), not by bytes.
+// ---- the rules of the loop (ConjugateGradientsSolver's tests, in its order): written once, for both forms.  The callers differ in who sums the parts
+// k_pcg_step left - part: 4 doubles per workgroup [Q part (start: |b|^2 part) | r . z part | status | alpha] - and in what order.
 struct PcgDecision { PcgState s; double beta; int run; int failed; };
 
-// The decision k_pcg_wide_b took after iteration it_prev (0: the start of a solve), by one wavefront for itself.
-__device__ __forceinline__ PcgDecision PcgDecide(int it_prev, int G, const double* __restrict__ part, const PcgState* __restrict__ st, double eta,
-                                                 int max_iterations) {
+// (status, alpha) of the vector step that has just run: a step that ended the loop (indefinite direction, overflow) ends it here.  Alone, this is what
+// follows the x-only step of a residual-reset iteration.
+__device__ __forceinline__ PcgDecision PcgCarryOver(const PcgState& s, int status, double alpha) {
   PcgDecision d;
-  d.s = *st; d.beta = 0.0; d.run = 0; d.failed = 0;
-  const int lane = threadIdx.x & 63;
-  double a0 = 0.0, a1 = 0.0;
-  for (int w = lane; w < G; w += 64) { a0 += part[4 * (size_t)w]; a1 += part[4 * (size_t)w + 1]; }
-  const int status = (int)part[2];
-  const double alpha = part[3];
-  if (it_prev != 0 && (d.s.done || d.s.iter != it_prev)) return d;      // (ended before: both copies of the state keep saying so)
-  a0 = WaveSum(a0); a1 = WaveSum(a1);
-  auto finish = [&](int st_code) { d.s.done = 1; d.s.status = st_code; d.failed = st_code == kPcgFailure; };
+  d.s = s; d.beta = 0.0; d.run = 0; d.failed = 0;
   d.s.alpha = alpha;
-  if (status != kPcgRunning) { finish(status); return d; }
+  if (status != kPcgRunning) { d.s.done = 1; d.s.status = status; d.failed = status == kPcgFailure; return d; }
+  d.run = 1;
+  return d;
+}
+// The decision after iteration it_prev (0: the start of a solve) from the totals a0 (Q; at the start |b|^2) and a1 (r . z): the state as it is from
+// here on, beta of the next direction, run = the loop goes on.
+__device__ __forceinline__ PcgDecision PcgAdvance(const PcgState& s, int it_prev, double a0, double a1, int status, double alpha, double eta, int max_iterations) {
+  PcgDecision d = PcgCarryOver(s, status, alpha);
+  if (!d.run) return d;
+  d.run = 0;
+  auto finish = [&](int st_code) { d.s.done = 1; d.s.status = st_code; d.failed = st_code == kPcgFailure; };
   if (it_prev == 0) {
     d.s.iter = 1; d.s.done = 0; d.s.status = kPcgRunning; d.s.rho = 1.0; d.s.Q0 = 0.0; d.s.norm_b = sqrt(a0); d.s.alpha = 0.0;
     if (!(a0 > 0.0)) { d.s.iter = 0; finish(a0 == 0.0 ? kPcgConverged : kPcgFailure); return d; }
@@ -465,17 +317,71 @@ __device__ __forceinline__ PcgDecision PcgDecide(int it_prev, int G, const doubl
   d.run = 1;
   return d;
 }
-// the x-only step of a residual-reset iteration left (status, alpha) in the parts: carries a failure of that step over (k_pcg_wide_b's mode 3)
-__device__ __forceinline__ PcgDecision PcgCarry(int it, const double* __restrict__ part, const PcgState* __restrict__ st) {
-  PcgDecision d;
-  d.s = *st; d.beta = 0.0; d.run = 0; d.failed = 0;
+
+// mode 0: start (it = 0); 1: an iteration's end; 3: after the x-only step of a residual-reset iteration (only carries a failure of that step over)
+__global__ __launch_bounds__(kWideThreads) void k_pcg_wide_b(int mode, int it, int C, int G, const double* __restrict__ z, double* __restrict__ p,
+                                                             const double* __restrict__ part, const PcgState* __restrict__ st, PcgState* __restrict__ st_out,
+                                                             double eta, int max_iterations, int32_t* __restrict__ flag, PcgIntr in) {
+  __shared__ double red[4];
+  const PcgState s = *st;
+  const int tid = threadIdx.x;
+  const bool writer = blockIdx.x == 0 && tid == 0;
+  if (mode != 0 && (s.done || s.iter != it)) { if (writer) *st_out = s; return; }      // (both copies say "done" from here on)
+  double a0 = 0.0, a1 = 0.0;
+  for (int w = tid; w < G; w += kWideThreads) { a0 += part[4 * (size_t)w]; a1 += part[4 * (size_t)w + 1]; }
+  a0 = WideBlockSum(a0, red);
+  a1 = WideBlockSum(a1, red);
   const int status = (int)part[2];
   const double alpha = part[3];
-  if (d.s.done || d.s.iter != it) return d;
-  d.s.alpha = alpha;
-  if (status != kPcgRunning) { d.s.done = 1; d.s.status = status; d.failed = status == kPcgFailure; return d; }
-  d.run = 1;
-  return d;
+  const PcgDecision d = mode == 3 ? PcgCarryOver(s, status, alpha) : PcgAdvance(s, it, a0, a1, status, alpha, eta, max_iterations);
+  if (writer) { *st_out = d.s; if (d.failed) atomicOr(flag, 1); }
+  if (!d.run || mode == 3) return;
+  const int g = blockIdx.x * kWideThreads + tid;
+  if ((int)blockIdx.x >= in.pose_blocks) {      // the intrinsics blocks
+    const int k = ((int)blockIdx.x - in.pose_blocks) * kWideThreads + tid;
+    const int off = k < in.K ? in.intr_off[k] : -1;
+    if (off >= 0) {
+      const size_t i0 = 6 * (size_t)C + off;
+      for (int j = 0; j < in.intr_nv[k]; ++j) p[i0 + j] = (mode == 0) ? z[i0 + j] : z[i0 + j] + d.beta * p[i0 + j];
+    }
+  } else if (g < 2 * C) {
+    const size_t i = 3 * (size_t)g;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[i + k] = (mode == 0) ? z[i + k] : z[i + k] + d.beta * p[i + k];
+  }
+}
+
+// ---- THREE launches per iteration (the default outside point-sharded groups).  k_pcg_wide_b is not launched: the decision it takes and the
+// direction it writes are taken by the product kernels themselves.
+//   k_pcg_points_q     every wavefront sums the parts of Q and r . z k_pcg_step left (the same order everywhere: the same bits, no
+//                      exchange), takes the termination decision and beta, and forms the direction of the images it touches on the
+//                      fly: p_c = z_c + beta p_old,c (both vectors are L2 resident: 53 KB at 1100 images)
+//   k_pcg_images_q     the same decision, p_c once more for ITS image - stored: the direction buffer ping-pongs, like the state that workgroup 0
+//                      writes - then (S p)_c and the image's part of p . S p
+//   k_pcg_step         alpha, x, r, z = M^-1 r, parts (the vector step of both forms, see there)
+// and the index walks are one level shorter: (observation, image) pairs per point-list entry and (observation, point) pairs per image-list
+// entry (k_pcg_entries, built once per handle), two, four or eight records of a point in flight by the mean track.  The kernels of an iteration are
+// bound by the LATENCY of their dependent loads (344 + 1100 + 9 workgroups at 1100 images, a few microseconds each), not by bytes.
+// The decision after iteration it_prev (0: the start of a solve), by one wavefront for itself (k_pcg_wide_b's, with the parts summed by lanes).
+__device__ __forceinline__ PcgDecision PcgDecide(int it_prev, int G, const double* __restrict__ part, const PcgState* __restrict__ st, double eta,
+                                                 int max_iterations) {
+  const PcgState s = *st;
+  const int lane = threadIdx.x & 63;
+  double a0 = 0.0, a1 = 0.0;
+  for (int w = lane; w < G; w += 64) { a0 += part[4 * (size_t)w]; a1 += part[4 * (size_t)w + 1]; }
+  const int status = (int)part[2];
+  const double alpha = part[3];
+  if (it_prev != 0 && (s.done || s.iter != it_prev)) return PcgDecision{s, 0.0, 0, 0};      // (ended before: both copies of the state keep saying so)
+  a0 = WaveSum(a0); a1 = WaveSum(a1);
+  return PcgAdvance(s, it_prev, a0, a1, status, alpha, eta, max_iterations);
+}
+// the x-only step of a residual-reset iteration left (status, alpha) in the parts: carries a failure of that step over (k_pcg_wide_b's mode 3)
+__device__ __forceinline__ PcgDecision PcgCarry(int it, const double* __restrict__ part, const PcgState* __restrict__ st) {
+  const PcgState s = *st;
+  const int status = (int)part[2];
+  const double alpha = part[3];
+  if (s.done || s.iter != it) return PcgDecision{s, 0.0, 0, 0};
+  return PcgCarryOver(s, status, alpha);
 }
 // has the loop ended before this launch (the test PcgDecide / PcgCarry begin with)?  One load, asked for together with the list entry: a launch enqueued
 // beyond the loop's end leaves after ONE round trip instead of after the record fetch it would never use
@@ -686,11 +592,40 @@ __global__ __launch_bounds__(kImagesQThreads) void k_pcg_images_q(int C, const i
   }
 }
 
-// k_pcg_wide_a with the loads first, and the block inverses at the start of a solve (mode 0)
+// the vector step of camera k's intrinsics block (variable intrinsics): the rows of the block one after the other
+__device__ __forceinline__ void PcgStepIntrBlock(int mode, bool reset, double alpha, int C, int k, const PcgIntr& in, const double* __restrict__ b, double* __restrict__ x,
+                                                 double* __restrict__ r, double* __restrict__ z, const double* __restrict__ p, const double* __restrict__ q, double& s0, double& s1) {
+  const int off = k < in.K ? in.intr_off[k] : -1;
+  if (off < 0) return;
+  const int nv = in.intr_nv[k];
+  const size_t i0 = 6 * (size_t)C + off;
+  double rn[12], xn[12];
+  for (int j = 0; j < nv; ++j) {
+    const double bj = b[i0 + j];
+    if (mode == 0) { xn[j] = 0.0; rn[j] = bj; x[i0 + j] = 0.0; s0 += bj * bj; }
+    else if (mode == 1) { xn[j] = x[i0 + j] + alpha * p[i0 + j]; x[i0 + j] = xn[j]; rn[j] = reset ? 0.0 : r[i0 + j] - alpha * q[i0 + j]; }
+    else { xn[j] = x[i0 + j]; rn[j] = bj - q[i0 + j]; }
+    if (!reset && mode != 0) s0 -= xn[j] * (bj + rn[j]);
+  }
+  if (!reset) {
+    for (int a = 0; a < nv; ++a) {
+      const double* B = in.binvI + 12 * (size_t)(off + a);
+      double zv = 0.0;
+      for (int j = 0; j < nv; ++j) zv += B[j] * rn[j];
+      z[i0 + a] = zv; r[i0 + a] = rn[a];
+      s1 += rn[a] * zv;
+    }
+  }
+}
+
+// The vector step of both forms.  mode 0: start (x = 0, r = b, and the inverses of the diagonal blocks Sd -> binv); 1: after q = S p of iteration `it`;
+// 2: after q = S x (explicit residual).  Every load is issued before the first workgroup sum.  kIntr: the intrinsics blocks as well - a thread per camera,
+// in workgroups behind the pose workgroups - and the cameras' parts of p . S p behind the images'.
+template <bool kIntr>
 __global__ __launch_bounds__(kWideThreads) void k_pcg_step(int mode, int it, int C, const double* __restrict__ Sd, const double* __restrict__ b, double* __restrict__ x,
                                                            double* __restrict__ r, double* __restrict__ z, const double* __restrict__ p, const double* __restrict__ q,
                                                            double* __restrict__ binv, const double* __restrict__ dotp, const PcgState* __restrict__ st,
-                                                           double* __restrict__ part, int32_t* __restrict__ flag) {
+                                                           double* __restrict__ part, int32_t* __restrict__ flag, PcgIntr in) {
   __shared__ double red[4];
   __shared__ double red2[4][2];
   const int tid = threadIdx.x;
@@ -701,7 +636,7 @@ __global__ __launch_bounds__(kWideThreads) void k_pcg_step(int mode, int it, int
   PcgState s;
   if (mode != 0) s = *st;
   double pq = 0.0;
-  if (mode == 1) { for (int c = tid; c < C; c += kWideThreads) pq += dotp[c]; }
+  if (mode == 1) { for (int c = tid; c < C + (kIntr ? in.K : 0); c += kWideThreads) pq += dotp[c]; }
   double bv[3], xv[3] = {0, 0, 0}, rv[3] = {0, 0, 0}, pv[3] = {0, 0, 0}, qv[3] = {0, 0, 0}, B[9];
 #pragma unroll
   for (int k = 0; k < 3; ++k) bv[k] = b[i + k];
@@ -715,17 +650,10 @@ __global__ __launch_bounds__(kWideThreads) void k_pcg_step(int mode, int it, int
 #pragma unroll
     for (int k = 0; k < 3; ++k) { pv[k] = p[i + k]; rv[k] = r[i + k]; }
   }
-  if (mode == 0) {      // the inverse of this parameter block's 3 x 3 diagonal block of S (rotation tangent / translation), as k_pcg_block_inverse forms it
+  if (mode == 0) {      // the inverse of this parameter block's 3 x 3 diagonal block of S (rotation tangent / translation)
     const int c = (active ? g : 0) >> 1, hh = g & 1;
-    const double* D = Sd + 36 * (size_t)c + 21 * hh;
-    const double a = D[0], bb = D[1], cc = D[2], dd = D[7], e = D[8], f = D[14];
-    const double c00 = dd * f - e * e, c01 = cc * e - bb * f, c02 = bb * e - cc * dd;
-    const double det = a * c00 + bb * c01 + cc * c02;
-    if (active && (!(det > 0.0) || !isfinite(det))) atomicOr(flag, 1);
-    const double id = 1.0 / det;
-    B[0] = c00 * id; B[1] = c01 * id; B[2] = c02 * id;
-    B[3] = c01 * id; B[4] = (a * f - cc * cc) * id; B[5] = (bb * cc - a * e) * id;
-    B[6] = c02 * id; B[7] = (bb * cc - a * e) * id; B[8] = (a * dd - bb * bb) * id;
+    const bool good = InverseSym3(Sd + 36 * (size_t)c + 21 * hh, B);
+    if (active && !good) atomicOr(flag, 1);
     if (active) {
 #pragma unroll
       for (int k = 0; k < 9; ++k) binv[9 * (size_t)g + k] = B[k];
@@ -741,7 +669,9 @@ __global__ __launch_bounds__(kWideThreads) void k_pcg_step(int mode, int it, int
   }
   const bool reset = mode == 1 && (it % kResidualResetPeriod) == 0;
   double s0 = 0.0, s1 = 0.0;
-  if (active && status == kPcgRunning) {
+  if (kIntr && (int)blockIdx.x >= in.pose_blocks) {
+    if (status == kPcgRunning) PcgStepIntrBlock(mode, reset, alpha, C, ((int)blockIdx.x - in.pose_blocks) * kWideThreads + tid, in, b, x, r, z, p, q, s0, s1);
+  } else if (active && status == kPcgRunning) {
     if (mode == 0) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) { xv[k] = 0.0; rv[k] = bv[k]; x[i + k] = 0.0; s0 += bv[k] * bv[k]; }
@@ -769,7 +699,7 @@ __global__ __launch_bounds__(kWideThreads) void k_pcg_step(int mode, int it, int
       }
     }
   }
-  s0 = WaveSum(s0); s1 = WaveSum(s1);      // (both sums behind ONE pair of barriers; the order of k_pcg_wide_a's two workgroup sums)
+  s0 = WaveSum(s0); s1 = WaveSum(s1);      // (both sums behind ONE pair of barriers; the order of WideBlockSum)
   __syncthreads();
   if ((tid & 63) == 0) { red2[tid >> 6][0] = s0; red2[tid >> 6][1] = s1; }
   __syncthreads();
@@ -801,31 +731,33 @@ int PcgEnsureBuffers(pp_ba_impl* h) {
   return PP_OK;
 }
 
-// S x = b for the system k_schur_self_rhs (compact) + k_prepare have set up for `radius`; x -> h->step_c (scaled space).
-// Synchronises the stream (the loop's length is data dependent).  *iterations: conjugate-gradient iterations run.
-// the host's wait for k_pcg_decide: a busy spin on the ticket for as long as such a look can reasonably take (PPSFM_TICKET_SPIN_US, default 1500 us,
-// 0 = never spin), then naps; after 2 s the stream is synchronised once (a failed launch would otherwise wait forever)
+// the host's wait for k_pcg_decide (host_ticket.hpp; PPSFM_TICKET_SPIN_US, default 1500 us; 0 = never spin: the stream is synchronised instead)
 static int WaitPcgTicket(pp_ba_impl* h, int32_t ticket) {
   const long spin_us = h->sw.ticket_spin_us;
-  const volatile int32_t* t = &h->pcg_state_host->pad_;
-  if (spin_us == 0) { PP_HIP_TRY(hipStreamSynchronize(h->stream)); }
-  const auto t0 = std::chrono::steady_clock::now();
-  for (unsigned spins = 0; *t != ticket; ++spins) {
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-    __builtin_ia32_pause();
-#endif
-    if ((spins & 0xFF) != 0xFF) continue;
-    const auto waited = std::chrono::steady_clock::now() - t0;
-    if (waited > std::chrono::seconds(2)) {
-      PP_HIP_TRY(hipStreamSynchronize(h->stream));
-      if (*t != ticket) { SetLastError("pp_ba_solve: the conjugate-gradient state never arrived"); return PP_ERR_HIP; }
-      break;
-    }
-    if (waited > std::chrono::microseconds(spin_us)) std::this_thread::sleep_for(std::chrono::microseconds(50));
+  hipError_t e = hipSuccess;
+  switch (WaitHostTicket(&h->pcg_state_host->pad_, ticket, spin_us, [&] { return (e = hipStreamSynchronize(h->stream)) == hipSuccess; }, spin_us == 0)) {
+    case TicketWait::kArrived: return PP_OK;
+    case TicketWait::kSyncFailed: SetLastError("pp_ba_solve: hipStreamSynchronize failed while waiting for the conjugate-gradient state: %s", hipGetErrorString(e)); break;
+    case TicketWait::kNeverArrived: SetLastError("pp_ba_solve: the conjugate-gradient state never arrived"); break;
   }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return PP_OK;
+  return PP_ERR_HIP;
 }
+
+// When the host looks at the loop's state.  Iterations enqueued before the first look: what the previous solve of this handle needed, + 1 (consecutive
+// LM iterations take about the same number of CG iterations - ~6 at 1100 images with eta = 0.1 - and every iteration enqueued beyond the end is launches
+// of kernels that return at once plus the wait for them: a fixed first batch of 8 was ~10 % of such an LM iteration).  Longer than last time: look
+// again soon, then less and less often.  every_iteration (a point-sharded group): every iteration enqueued beyond the end is a real collective of 6 C
+// doubles on every rank - look after each one.
+struct PcgLooks {
+  int batch, next;
+  bool every_iteration;
+  PcgLooks(int last_iterations, bool every) : batch(last_iterations > 0 ? std::min(32, last_iterations + 1) : 8), next(batch), every_iteration(every) {}
+  bool Now(int it, int cap) const { return it == next || it == cap; }
+  void After(int it) {
+    batch = every_iteration ? 1 : (it == next && next > batch ? std::min(32, batch * 2) : 2);
+    next = it + batch;
+  }
+};
 
 static int PcgFinishCount(pp_ba_impl* h, int* iterations) {
   const PcgState* hs = h->pcg_state_host;
@@ -835,61 +767,75 @@ static int PcgFinishCount(pp_ba_impl* h, int* iterations) {
   return PP_OK;
 }
 
-// The three-launch loop (the default outside point-sharded groups).
+// the vector step of both forms (p: the direction of this iteration; st: the current copy of the state)
+static void LaunchStep(pp_ba_impl* h, int G, const PcgIntr& in, int mode, int it, const double* p, const PcgState* st) {
+  auto* k = in.K > 0 ? k_pcg_step<true> : k_pcg_step<false>;
+  hipLaunchKernelGGL(k, dim3(G), dim3(kWideThreads), 0, h->stream, mode, it, h->C, h->pcg_Sd, h->pcg_b, h->step_c, h->pcg_r, h->pcg_z, p, h->pcg_q, h->pcg_binv, h->pcg_dot, st,
+                     h->pcg_part, h->d_flag, in);
+}
+
+// what a product of the three-launch form needs beside the vector: the loop's constants and the current copies of the state (cur) and of the direction (pc)
+struct PcgFusedLoop {
+  pp_ba_impl* h;
+  double inv_radius, eta;
+  int max_iterations, G;
+  // quads per point (a record each per round): 2 up to a mean track of 2.5, 4 up to 4.5, 8 beyond (two records in flight per quad with half the
+  // quads: 11.3 us against 9.1 - the early exit waits for both)
+  int qp;
+  int cur = 0, pc = 0;
+};
+template <bool kDir, int kQuads>
+static void LaunchPointsQ(const PcgFusedLoop& L, const double* v, const double* p_old, int it) {
+  pp_ba_impl* h = L.h;
+  hipLaunchKernelGGL((k_pcg_points_q<kDir, kQuads>), dim3(CeilDiv(4 * kQuads * (int64_t)h->P, kPointsQThreads)), dim3(kPointsQThreads), 0, h->stream, h->P, h->pt_start,
+                     reinterpret_cast<const int2*>(h->pcg_pt_entry), h->JpS, v, p_old, h->pcg_a, h->pcg_state + L.cur, h->pcg_part, L.G, it, L.eta, L.max_iterations);
+}
+// kDir: pcg_q = S (z + beta p) after the decision on iteration `it`, v = z; else pcg_q = S v
+template <bool kDir>
+static void LaunchProductQ(PcgFusedLoop& L, const double* v, int it) {
+  pp_ba_impl* h = L.h;
+  const size_t n = 6 * (size_t)h->C;
+  const double* p_old = h->pcg_p + (size_t)L.pc * n;
+  double* p_new = h->pcg_p + (size_t)(L.pc ^ 1) * n;
+  if (L.qp == 8) LaunchPointsQ<kDir, 8>(L, v, p_old, it); else if (L.qp == 4) LaunchPointsQ<kDir, 4>(L, v, p_old, it); else LaunchPointsQ<kDir, 2>(L, v, p_old, it);
+  hipLaunchKernelGGL((k_pcg_images_q<kDir>), dim3(h->C), dim3(kImagesQThreads), 0, h->stream, h->C, h->pose_start, reinterpret_cast<const int2*>(h->pcg_pose_entry), h->JpS, v, p_old,
+                     p_new, h->pcg_a, h->scale_c, h->diag_c, L.inv_radius, h->pcg_q, h->pcg_dot, h->pcg_state + L.cur, h->pcg_state + (L.cur ^ 1), h->pcg_part, L.G, it, L.eta,
+                     L.max_iterations, h->d_flag);
+  if (kDir) L.pc ^= 1;
+  L.cur ^= 1;
+}
+
+// The three-launch loop (the default outside point-sharded groups): the product kernels take the decision and form the direction themselves.
 static int PcgFusedRun(pp_ba_impl* h, double inv_radius, int max_iterations, double eta, int* iterations) {
-  hipStream_t s = h->stream;
-  const int n = 6 * h->C, C = h->C;
-  const int G = CeilDiv(2 * (int64_t)C, kWideThreads);
+  const size_t n = 6 * (size_t)h->C;
+  const int G = CeilDiv(2 * (int64_t)h->C, kWideThreads);
   const int cap = std::max(1, max_iterations);
   PcgState* hs = h->pcg_state_host;
-  int batch = h->pcg_last_iterations > 0 ? std::min(32, h->pcg_last_iterations + 1) : 8;
-  int next_look = batch;
-  // ---- three launches per iteration: the product kernels take the decision and form the direction themselves ----
-  const int2* pt_entry = reinterpret_cast<const int2*>(h->pcg_pt_entry);
-  const int2* pose_entry = reinterpret_cast<const int2*>(h->pcg_pose_entry);
-  // quads per point (a record each per round): 2 up to a mean track of 2.5, 4 up to 4.5, 8 beyond (two records in flight per quad with half
-  // the quads: 11.3 us against 9.1 - the early exit waits for both)
-  const int qp = h->M > (int64_t)h->P * 9 / 2 ? 8 : (h->M > (int64_t)h->P * 5 / 2 ? 4 : 2);
-  const dim3 gq(CeilDiv(4 * qp * (int64_t)h->P, kPointsQThreads)), gi(C);
-  int cur = 0, pc = 0;      // current copy of the state / of the direction
-  auto step = [&](int mode, int it) {
-    hipLaunchKernelGGL(k_pcg_step, dim3(G), dim3(kWideThreads), 0, s, mode, it, C, h->pcg_Sd, h->pcg_b, h->step_c, h->pcg_r, h->pcg_z, h->pcg_p + (size_t)pc * n, h->pcg_q,
-                       h->pcg_binv, h->pcg_dot, h->pcg_state + cur, h->pcg_part, h->d_flag);
-  };
-  auto product = [&](bool dir, const double* v, int it) {      // dir: pcg_q = S (z + beta p) after the decision on iteration `it`; else pcg_q = S v
-    const double* p_old = h->pcg_p + (size_t)pc * n;
-    double* p_new = h->pcg_p + (size_t)(pc ^ 1) * n;
-#define PP_POINTS_Q(D, L) hipLaunchKernelGGL((k_pcg_points_q<D, L>), gq, dim3(kPointsQThreads), 0, s, h->P, h->pt_start, pt_entry, h->JpS, v, p_old, h->pcg_a, h->pcg_state + cur, h->pcg_part, G, \
-                                           it, eta, max_iterations)
-#define PP_IMAGES_Q(D) hipLaunchKernelGGL((k_pcg_images_q<D>), gi, dim3(kImagesQThreads), 0, s, C, h->pose_start, pose_entry, h->JpS, v, p_old, p_new, h->pcg_a, h->scale_c, h->diag_c, inv_radius, \
-                                        h->pcg_q, h->pcg_dot, h->pcg_state + cur, h->pcg_state + (cur ^ 1), h->pcg_part, G, it, eta, max_iterations, h->d_flag)
-    if (dir) { if (qp == 8) PP_POINTS_Q(true, 8); else if (qp == 4) PP_POINTS_Q(true, 4); else PP_POINTS_Q(true, 2); PP_IMAGES_Q(true); pc ^= 1; }
-    else { if (qp == 8) PP_POINTS_Q(false, 8); else if (qp == 4) PP_POINTS_Q(false, 4); else PP_POINTS_Q(false, 2); PP_IMAGES_Q(false); }
-#undef PP_POINTS_Q
-#undef PP_IMAGES_Q
-    cur ^= 1;
-  };
-  hs->done = 0; hs->iter = 0; hs->status = kPcgRunning;
+  PcgLooks looks(h->pcg_last_iterations, false);
+  PcgFusedLoop L{h, inv_radius, eta, max_iterations, G, h->M > (int64_t)h->P * 9 / 2 ? 8 : (h->M > (int64_t)h->P * 5 / 2 ? 4 : 2)};
+  const PcgIntr none;
+  auto step = [&](int mode, int it) { LaunchStep(h, G, none, mode, it, h->pcg_p + (size_t)L.pc * n, h->pcg_state + L.cur); };
   step(0, 0);
   for (int it = 1; it <= cap; ++it) {
-    product(true, h->pcg_z, it - 1);
+    LaunchProductQ<true>(L, h->pcg_z, it - 1);
     step(1, it);
-    if (it % kResidualResetPeriod == 0) { product(false, h->step_c, it); step(2, it); }
-    if (it == next_look || it == cap) {
+    if (it % kResidualResetPeriod == 0) { LaunchProductQ<false>(L, h->step_c, it); step(2, it); }
+    if (looks.Now(it, cap)) {
       // (the state goes straight into the pinned block the host reads: no copy in between)
       const int32_t ticket = ++h->pcg_ticket == 0 ? ++h->pcg_ticket : h->pcg_ticket;
       hs->pad_ = 0;
-      hipLaunchKernelGGL(k_pcg_decide, dim3(1), dim3(64), 0, s, it, G, h->pcg_part, h->pcg_state + cur, hs, eta, max_iterations, h->d_flag, ticket);
+      hipLaunchKernelGGL(k_pcg_decide, dim3(1), dim3(64), 0, h->stream, it, G, h->pcg_part, h->pcg_state + L.cur, hs, eta, max_iterations, h->d_flag, ticket);
       PP_HIP_TRY(hipGetLastError());
-      { const int rcw = WaitPcgTicket(h, ticket); if (rcw) return rcw; }
+      PP_TRY(WaitPcgTicket(h, ticket));
       if (hs->done) break;
-      batch = it == next_look && next_look > batch ? std::min(32, batch * 2) : 2;
-      next_look = it + batch;
+      looks.After(it);
     }
   }
   return PcgFinishCount(h, iterations);
 }
 
+// S x = b for the system k_schur_self_rhs (compact) + k_prepare have set up for `radius`; x -> h->step_c (scaled space).
+// Synchronises the stream (the loop's length is data dependent).  *iterations: conjugate-gradient iterations run.
 int PcgSolve(pp_ba_impl* h, double radius, int max_iterations, double eta, int* iterations) {
   hipStream_t s = h->stream;
   const int n = h->n_red, C = h->C;
@@ -901,24 +847,16 @@ int PcgSolve(pp_ba_impl* h, double radius, int max_iterations, double eta, int* 
   PcgIntr in;
   if (intr) { in.K = h->K; in.pose_blocks = Gp; in.intr_off = h->intr_off; in.intr_nv = h->intr_nv; in.binvI = h->pcg_binvI; }
   const int cap = std::max(1, max_iterations);
-  // iterations enqueued before the first look at the state: what the previous solve of this handle needed, + 1 (consecutive LM iterations take about
-  // the same number of CG iterations - ~6 at 1100 images with eta = 0.1 - and every iteration enqueued beyond the end is launches of kernels that
-  // return at once plus the wait for them: a fixed first batch of 8 was ~10 % of such an LM iteration); then doubling
-  int batch = h->pcg_last_iterations > 0 ? std::min(32, h->pcg_last_iterations + 1) : 8;
-  int next_look = batch;
   PcgState* hs = h->pcg_state_host;
   hs->done = 0; hs->iter = 0; hs->status = kPcgRunning;
   if (!group && !intr && h->sw.pcg_fused) return PcgFusedRun(h, inv_radius, max_iterations, eta, iterations);
-  hipLaunchKernelGGL(k_pcg_block_inverse, dim3(CeilDiv(2 * C, 256)), dim3(256), 0, s, C, h->pcg_Sd, h->pcg_binv, h->d_flag);
+  PcgLooks looks(h->pcg_last_iterations, group);
   if (intr) hipLaunchKernelGGL(k_pcg_intr_inverse, dim3(CeilDiv(h->K, 64)), dim3(64), 0, s, h->K, h->intr_off, h->intr_nv, h->pcg_Scomp, h->pcg_binvI, h->d_flag);
-  // the vector step: many workgroups (k_pcg_wide_a / _b, two launches) - 1100 images: 2460 -> 2860 LM it/s against the one-workgroup
+  // the vector step: many workgroups (k_pcg_step / k_pcg_wide_b, two launches) - 1100 images: 2460 -> 2860 LM it/s against the one-workgroup
   // kernel (12.5 us per step; 29.6 us at 4000 images, where it was the longest kernel of an iteration, against 6.1 + 4.4 us); 600 images
   // +6 %.  In a point-sharded group p . S p belongs to the all-reduced product: k_pcg_dot forms its per-image parts after the exchange.
   int cur = 0;      // which copy of the state is current (ping-pong)
-  auto wide_a = [&](int mode, int it) {
-    hipLaunchKernelGGL(k_pcg_wide_a, dim3(G), dim3(kWideThreads), 0, s, mode, it, C, h->pcg_b, h->step_c, h->pcg_r, h->pcg_z, h->pcg_p, h->pcg_q, h->pcg_binv, h->pcg_dot,
-                       h->pcg_state + cur, h->pcg_part, in);
-  };
+  auto wide_a = [&](int mode, int it) { LaunchStep(h, G, in, mode, it, h->pcg_p, h->pcg_state + cur); };
   auto wide_b = [&](int mode, int it) {
     hipLaunchKernelGGL(k_pcg_wide_b, dim3(G), dim3(kWideThreads), 0, s, mode, it, C, G, h->pcg_z, h->pcg_p, h->pcg_part, h->pcg_state + cur, h->pcg_state + (cur ^ 1), eta,
                        max_iterations, h->d_flag, in);
@@ -961,23 +899,15 @@ int PcgSolve(pp_ba_impl* h, double radius, int max_iterations, double eta, int* 
       if (rc_group) { (void)hipStreamSynchronize(s); return rc_group; }
       wide_a(2, it); wide_b(1, it);
     }
-    if (it == next_look || it == cap) {
+    if (looks.Now(it, cap)) {
       PP_HIP_TRY(hipGetLastError());
       PP_HIP_TRY(hipMemcpyAsync(hs, h->pcg_state + cur, sizeof(PcgState), hipMemcpyDeviceToHost, s));
       PP_HIP_TRY(hipStreamSynchronize(s));
       if (hs->done) break;
-      batch = it == next_look && next_look > batch ? std::min(32, batch * 2) : 2;      // (longer than last time: look again soon, then less and less often)
-      if (group) batch = 1;      // (in a group every iteration enqueued beyond the end is a real collective of 6 C doubles on every rank: look after each one)
-      next_look = it + batch;
+      looks.After(it);
     }
   }
-  if (!hs->done) {      // (cap not a multiple of the batch and the loop still running: cannot happen - the cap ends it - but never trust a loop)
-    PP_HIP_TRY(hipMemcpyAsync(hs, h->pcg_state + cur, sizeof(PcgState), hipMemcpyDeviceToHost, s));
-    PP_HIP_TRY(hipStreamSynchronize(s));
-  }
-  if (iterations) *iterations = hs->iter;
-  h->pcg_last_iterations = hs->iter;
-  return PP_OK;
+  return PcgFinishCount(h, iterations);      // (the look at it == cap has seen the end: the cap ends the loop)
 }
 
 }  // namespace ppsfm

@@ -16,14 +16,13 @@
 // The trust-region logic restates Ceres' published Levenberg-Marquardt strategy (radius update,
 // Jacobi scaling fixed at the first point, clamped LM diagonal, invalid/unsuccessful step handling),
 // see DESIGN.md §LM; Ceres itself is third-party and not part of /root/reference.
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 
 #include "ba_impl.hpp"
+#include "host_ticket.hpp"
 #include "lm_policy.hpp"
 #include "resource_pool.hpp"
 #include "line_residual.hpp"
@@ -789,26 +788,14 @@ static int ReadScalars(pp_ba_impl* h) {
 // core per GPU, so after that the thread sleeps between polls (50 us naps: < 0.1 % of such an iteration).  Bounded: after ~2 s
 // without the ticket the stream is synchronised once and the ticket re-checked (a failed launch would otherwise wait forever).
 static int WaitTicket(pp_ba_impl* h, unsigned long long ticket) {
-  const long spin_us = h->sw.ticket_spin_us;
   const volatile unsigned long long* t = reinterpret_cast<const volatile unsigned long long*>(h->h_scal) + kTicketSlot;
-  const auto t0 = std::chrono::steady_clock::now();
-  bool synced = false;
-  for (unsigned spins = 0; *t != ticket; ++spins) {
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-    __builtin_ia32_pause();
-#endif
-    if ((spins & 0xFF) != 0xFF) continue;
-    const auto waited = std::chrono::steady_clock::now() - t0;
-    if (waited > std::chrono::seconds(2) && !synced) {
-      PP_HIP_TRY(hipStreamSynchronize(h->stream));
-      synced = true;
-      if (*t != ticket) { SetLastError("pp_ba_solve: the trial step's scalars never arrived"); return PP_ERR_HIP; }
-      break;
-    }
-    if (waited > std::chrono::microseconds(spin_us)) std::this_thread::sleep_for(std::chrono::microseconds(50));
+  hipError_t e = hipSuccess;
+  switch (WaitHostTicket(t, ticket, h->sw.ticket_spin_us, [&] { return (e = hipStreamSynchronize(h->stream)) == hipSuccess; })) {
+    case TicketWait::kArrived: return PP_OK;
+    case TicketWait::kSyncFailed: SetLastError("pp_ba_solve: hipStreamSynchronize failed while waiting for the trial step's scalars: %s", hipGetErrorString(e)); break;
+    case TicketWait::kNeverArrived: SetLastError("pp_ba_solve: the trial step's scalars never arrived"); break;
   }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return PP_OK;
+  return PP_ERR_HIP;
 }
 static int32_t HostFlag(const pp_ba_impl* h) { int32_t f; std::memcpy(&f, h->h_scal + kNumScalars - 1, sizeof(f)); return f; }
 

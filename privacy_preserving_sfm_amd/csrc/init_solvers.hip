@@ -18,8 +18,6 @@
 // three device backends below.
 #include <algorithm>
 #include <array>
-#include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -28,6 +26,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "host_ticket.hpp"
 #include "resource_pool.hpp"
 #include "p6l_device.hpp"   // Solve3, Det3x3
 #include "init_lsq.hpp"
@@ -892,20 +891,9 @@ struct FourView2dBackend {
   volatile unsigned long long* PinnedTicket() const { return reinterpret_cast<volatile unsigned long long*>(PinnedErr() + h->n + 32); }
   // the host's wait for a shipment (k_fv2d_ship): a spin on the pinned ticket; after ~2 s the stream is synchronised once and the ticket looked at again
   int WaitTicket(unsigned long long ticket) {
-    const volatile unsigned long long* t = PinnedTicket();
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0; *t != ticket; ++spins) {
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-      __builtin_ia32_pause();
-#endif
-      if ((spins & 0xFFF) != 0xFFF) continue;
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-        if (hipStreamSynchronize(h->stream) != hipSuccess || *t != ticket) { SetLastError("pp_fourview2d: a model's errors never arrived"); return PP_ERR_HIP; }
-        break;
-      }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return PP_OK;
+    if (WaitHostTicket(PinnedTicket(), ticket, -1, [&] { return hipStreamSynchronize(h->stream) == hipSuccess; }) == TicketWait::kArrived) return PP_OK;
+    SetLastError("pp_fourview2d: a model's errors never arrived");
+    return PP_ERR_HIP;
   }
   int FlushScore() {      // the deferred score kernel of ScoreAsync (h->err still holds that model's errors: every EvaluateAsync of another model flushes first)
     if (h->pending_score_slot < 0) return PP_OK;

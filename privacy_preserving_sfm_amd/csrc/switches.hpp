@@ -34,7 +34,7 @@
 //   PPSFM_BA_FUSED_STEP         atoi, 0 = off                on               the LM loop (k_step_points)                  A/B
 //   PPSFM_BA_FUSED_TRIAL_COST   atoi, 0 = off                on               the LM loop (cost inside k_model_cost_apply)  A/B
 //   PPSFM_PCG_FUSED             atoi, 0 = off                on               PcgSolve (three-launch iteration)            A/B
-//   PPSFM_TICKET_SPIN_US        atol, microseconds           1500             WaitTicket, WaitPcgTicket (busy spin)        fallback
+//   PPSFM_TICKET_SPIN_US        atol, microseconds           1500             WaitTicket, WaitPcgTicket (host_ticket.hpp)  fallback
 //   PPSFM_PCG_LOG               set = on                     off              PcgFinishCount (CG iterations per solve)     debug
 //   PPSFM_ORDER_DEBUG           set = on                     off              ChooseImageOrdering (laps, candidates)       debug
 //   PPSFM_CREATE_DEBUG          set = on                     off              pp_ba_create (host time per phase)           debug

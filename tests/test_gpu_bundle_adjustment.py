@@ -983,7 +983,7 @@ def test_iterative_schur_pcg_follows_the_oracle(oracle, loss, fused, track, monk
     explicit matrix.  Inexact steps: the LM trajectories agree iteration by iteration, and so do the conjugate-gradient counts.
     fused (PPSFM_PCG_FUSED, the default): three launches per iteration, the product kernels take the decision and form the direction themselves -
     four lanes per record, eight / four / two records of a point in flight (tracks of 6 / 3 / 2); PPSFM_PCG_FUSED=0: the vector step of an iteration
-    spread over many workgroups (k_pcg_wide_a / _b, two launches and a ping-pong state: the form a point-sharded group runs)."""
+    spread over many workgroups (k_pcg_step / k_pcg_wide_b, two launches and a ping-pong state: the form a point-sharded group runs)."""
     from privacy_preserving_sfm_amd.device import BAProblem, ba_options
     monkeypatch.setenv("PPSFM_PCG_FUSED", fused)
     sc = synthetic.make_ba_scene(60, {6: 1500, 3: 3000, 2: 6000}[track], track, seed=0xC0FFEE + 21, model=2, window=12)
