@@ -35,15 +35,6 @@ struct EvalArgs {
   double loss_scale;
 };
 
-__device__ __forceinline__ void BlockPartialSum(double v, double* partials) {
-  __shared__ double wsum[4];
-  v = WaveSum(v);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) wsum[wave] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
 // MODE 0: residual/cost only; 1: tangent pose Jacobian (2x6); 2: ambient pose Jacobian (2x7)
 // The Jacobian rows (96/112 + 48 bytes per observation) are staged through LDS so that the workgroup
 // writes its contiguous 36 KB slab with fully coalesced 16-byte stores instead of 9 strided stores per lane.

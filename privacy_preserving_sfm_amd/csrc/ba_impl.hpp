@@ -43,6 +43,30 @@ __device__ __forceinline__ void LoadJx(const double* __restrict__ Jpoint, int o,
 #pragma unroll
   for (int i = 0; i < 3; ++i) { const double2 v = p[i]; jx[2 * i] = v.x; jx[2 * i + 1] = v.y; }
 }
+// A workgroup's (four wavefronts) part of a sum over the observations -> partials[blockIdx.x]: WaveSum's butterfly, the four wave totals through LDS,
+// (w0 + w1) + (w2 + w3).  K1's cost partials (ba_eval.hip) and the step kernels' (ba_step.hip) are THIS sum: the cost at the trial point inside a step
+// kernel equals the cost-only evaluation's bit for bit because of it.
+__device__ __forceinline__ void BlockPartialSum(double v, double* partials) {
+  __shared__ double wsum[4];
+  v = WaveSum(v);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) wsum[wave] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+// two values behind ONE barrier, each as above; partials1 == nullptr (workgroup-uniform): the second value is not summed
+__device__ __forceinline__ void BlockPartialSum(double v0, double* partials0, double v1, double* partials1) {
+  __shared__ double wsum[2][4];
+  v0 = WaveSum(v0);
+  if (partials1) v1 = WaveSum(v1);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { wsum[0][wave] = v0; wsum[1][wave] = v1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partials0[blockIdx.x] = (wsum[0][0] + wsum[0][1]) + (wsum[0][2] + wsum[0][3]);
+    if (partials1) partials1[blockIdx.x] = (wsum[1][0] + wsum[1][1]) + (wsum[1][2] + wsum[1][3]);
+  }
+}
 #endif
 // chain steps of the one-launch factorisation of a T x T tile map (closed under fill-in): the block columns on the longest dependency path when its
 // elimination tree has independent sub-trees (several chains, cholesky.hip), T otherwise; *chains (may be null): the number of chains
@@ -170,7 +194,7 @@ struct pp_ba_impl {
   double *U = nullptr, *gc = nullptr, *V = nullptr, *gp = nullptr, *Vinv = nullptr, *vb = nullptr;
   double *scale_c = nullptr, *scale_p = nullptr, *diag_c = nullptr, *diag_p = nullptr;
   double *S = nullptr, *Linv = nullptr, *Lfac = nullptr, *step_c = nullptr, *step_p = nullptr;
-  double *JpS = nullptr, *Q = nullptr, *norm_part = nullptr;   // JpS: the per-attempt gather records (kRecStride doubles per observation; Q unused), norm partials
+  double *JpS = nullptr, *norm_part = nullptr;   // JpS: the per-attempt gather records (kRecStride doubles per observation), norm partials
   int32_t N = 0;      // padded order of S (multiple of 64), rhs row index = 6*C
   double* scal = nullptr;   // device scalars
   double* h_scal = nullptr; // pinned host mirror
@@ -282,6 +306,17 @@ inline bool BaSparseActive(const pp_ba_impl* h) { return h->sparse_tiles && (!Ba
 // K3a (ba_schur.hip): the damped reduced system for `radius` into h->S (lower triangle + rhs row; an iterative handle: its diagonal blocks and its
 // right-hand side), exchanged over the group; refresh_diagonal: the LM diagonal clamp(diag(J_s^T J_s), dmin, dmax) is taken anew in the same launches
 int BaAssembleReducedSystem(pp_ba_impl* h, double radius, bool refresh_diagonal = false, double dmin = 0.0, double dmax = 0.0);
+// K2, K3c and the norms (ba_step.hip): the kernels only - the group exchange around them is the driver's (ba_solver.hip)
+int BaReduceNormalEquations(pp_ba_impl* h);                     // K2 at the current point: U, gc, V, gp from K1's rows
+int BaJacobiScale(pp_ba_impl* h, int jacobi);                   // scale_c, scale_p of the pose and point columns from U, V
+int BaLmDiagonal(pp_ba_impl* h, double dmin, double dmax);      // their clamped LM diagonal (a solve takes it inside the assembly)
+int BaGatherStep(pp_ba_impl* h);                                // step_c from the linear solve's step_s when the reduced system has a column order of its own
+// The step kernels of a trial step: k_step_points (fused_step) or k_backsub_points + k_model_cost_apply, behind the trial intrinsics; fused_trial_cost: the
+// cost at the trial point by the same launch; sum_model_cost: the model-cost partials summed by a launch of their own (otherwise the norms kernel folds them)
+int BaLaunchStepKernels(pp_ba_impl* h, bool fused_step, bool fused_trial_cost, bool sum_model_cost);
+// fold: 0 nothing; 1 K1's cost partials -> scal[kCost]; 2 K1's cost partials -> scal[kCostCand] and the model-cost partials -> scal[kModelChange] (the trial
+// step).  host_slot: the last kernel hands the scalars to this pinned host address itself, and then `ticket` (0: none)
+int BaLaunchNorms(pp_ba_impl* h, bool with_step, int fold, double* host_slot, unsigned long long ticket);
 // matrix-free PCG on the implicit Schur complement (ba_pcg.hip)
 int PcgEnsureBuffers(pp_ba_impl* h);
 int PcgSolve(pp_ba_impl* h, double radius, int max_iterations, double eta, int* iterations);

@@ -1,4 +1,4 @@
-// K3a: the Schur assembly of an LM attempt - from K2's blocks (U, g_c, V, g_p: ba_solver.hip) and the trust-region radius to the damped reduced camera
+// K3a: the Schur assembly of an LM attempt - from K2's blocks (U, g_c, V, g_p: ba_step.hip) and the trust-region radius to the damped reduced camera
 // system S (lower triangle + rhs row) that K3b factorises, or an iterative handle's diagonal blocks and right-hand side (ba_pcg.hip).
 //
 //   k_prepare            one launch, two roles: per point (V_p + D_p^2)^-1 and V^-1 b_p for the current trust-region radius; per
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void k_prepare(int point_blocks, int P, const 
 //   diagonal block       U_s + D^2 - sum_{o of this image} J_o^T G_oo J_o            (identity on constant columns)
 //   reduced rhs          b_c - sum_{o in c} J_c,o^T (J_p,o (V^-1 b_p))               -> row rhs_row of S
 // (both walk the same observation list and the same records; they used to be two wavefront-per-image kernels of ~25 us each), and by image 0 the
-// augmented corner and the identity padding.  (What was tried here after k_reduce: the remark at PoseReduceBody, ba_solver.hip.)
+// augmented corner and the identity padding.  (What was tried here after k_reduce: the remark at PoseReduceBody, ba_step.hip.)
 // NV = 0: the 6 x 6 pose block; an iterative handle (a.Sd) gets the blocks in Sd [C][36] and the rhs in rhs_out [6C] instead.
 // NV > 0: every image with NV variable intrinsics of its own beside its pose columns (pp_ba_impl::intr_wide_nv; image_ordering.hip PrivateIntrinsicsColumns).
 // The image's W = 6 + NV columns are ONE block of the reduced system, J_w,o = [J_pose,o diag(s_c) | J_intr,o diag(s_k)] (2 x W: the record's pose rows and
