@@ -18,7 +18,7 @@
 #include <functional>
 #include <vector>
 
-#include "common.hpp"      // (with ba_structure.hpp)
+#include "common.hpp"      // (with ba_structure.hpp and, through it, chol_plan.hpp: CholWorkspace)
 #include "resource_pool.hpp"
 #include "switches.hpp"
 
@@ -69,7 +69,7 @@ __device__ __forceinline__ void BlockPartialSum(double v0, double* partials0, do
 }
 #endif
 // chain steps of the one-launch factorisation of a T x T tile map (closed under fill-in): the block columns on the longest dependency path when its
-// elimination tree has independent sub-trees (several chains, cholesky.hip), T otherwise; *chains (may be null): the number of chains
+// elimination tree has independent sub-trees (several chains, chol_plan.hpp "ChainRanges"), T otherwise; *chains (may be null): the number of chains
 int CholeskyChainSteps(int T, const uint8_t* nz, const Switches& sw, int* chains = nullptr);
 // the same from the chain plan alone (no task list is built or replayed): what a candidate image order costs (image_ordering.hip)
 int CholeskyPlanSteps(int T, const uint8_t* nz, const Switches& sw, int* chains = nullptr);
@@ -252,12 +252,9 @@ int IntrScale(pp_ba_impl* h, int jacobi);                               // Jacob
 int IntrDiagonal(pp_ba_impl* h, double dmin, double dmax);              // clamped LM diagonal of the intrinsics columns
 int IntrScaledJacobians(pp_ba_impl* h);      // JkS_intr of the current linearisation and scales (k_intr_prepare)
 int IntrAssemble(pp_ba_impl* h, double inv_radius, int add_diagonal);   // rows 6C.. of S and of the rhs (after k_prepare)
-// dense Cholesky of the augmented reduced system (cholesky.hip)
-// doubles in the Cholesky workspace `Linv_ws` for an N x N system (N a multiple of 64): the 64x64 inverses of the diagonal
-// factors and two X staging tiles
-// L_kk^-1 blocks (= the M_k mailboxes), three more mailbox arrays of T + 1 slots (X, D, solved X), the progress counters of task mode
-// ... and the pair inverses / pair couplings of the paired back substitution (one + four tiles per pair of block columns)
-inline size_t CholeskyWorkspaceDoubles(int N) { return (size_t)(4 * (N / 64) + 3) * 64 * 64 + 8192 + (size_t)(N / 128 + 1) * 5 * 64 * 64; }
+// dense Cholesky of the augmented reduced system (cholesky.hip: the driver; chol_columns.hpp, chol_tasks.hpp, chol_backsub.hpp: its kernels)
+// doubles in the Cholesky workspace `Linv_ws` for an N x N system (N a multiple of 64); what lies where in it: CholWorkspace (chol_plan.hpp)
+inline size_t CholeskyWorkspaceDoubles(int N) { return CholWorkspace(N / 64).total; }
 std::recursive_mutex& DeviceSetupMutex();      // held while a handle allocates / uploads / captures its graph: none of that may run beside another host thread's capture
 // The system a CholeskyState factorises: S (N x N, rhs in row rhs_row), the workspace Linv_ws, Lfac (N x N solved tiles of the one-launch path,
 // where its factor ends up; null = per-column launches only), the solution x, the failure flags, the stream

@@ -1,7 +1,7 @@
-// Building blocks of the blocked fp64 Cholesky on 64x64 LDS tiles (row stride kLS), shared by the dense factorisation (cholesky.hip)
-// and k_small_cholesky: the 16-column register panel, the in-block trailing
-// update and tile inverses on the matrix cores (PotrfPanels), tile <-> LDS moves, the product-form triangular solve (SolveTile) and
-// the rank-64 tile updates.  See cholesky.hip for the measurements behind each of them.
+// Building blocks of the blocked fp64 Cholesky on 64x64 LDS tiles (row stride kLS), shared by the kernels of the dense factorisation
+// (chol_columns.hpp, chol_tasks.hpp, chol_backsub.hpp) and k_small_cholesky (cholesky.hip): the 16-column register panel, the in-block trailing
+// update and tile inverses on the matrix cores (PotrfPanels), tile <-> LDS moves, the product-form triangular solve (SolveTile),
+// the rank-64 tile updates, the super-tile products and the "not ready" pattern.  See cholesky.hip and those headers for the measurements behind them.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -310,20 +310,11 @@ __device__ __forceinline__ void TileStore2(double* dst, int tid, int it, double2
 // launch has rewritten this way; tiles that are written exactly once per launch (the solved tiles in their own array, the M_k,
 // the per-step staging tiles) cannot be stale in any L2 and keep the plain, L2-cached loads.
 __device__ __forceinline__ double LoadCoherent(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <bool kCoh>
-__device__ __forceinline__ double2 TileLoad2T(const double* __restrict__ src, int ld, int tid, int it) {
-  if (!kCoh) return TileLoad2(src, ld, tid, it);
+__device__ __forceinline__ double2 TileLoad2Coherent(const double* __restrict__ src, int ld, int tid, int it) {
   const int idx = tid + kPanelThreads * it, r = idx >> 5, c2 = idx & 31;
   const double* p = src + (size_t)r * ld + 2 * c2;
   return make_double2(LoadCoherent(p), LoadCoherent(p + 1));
 }
-template <bool kCoh>
-__device__ __forceinline__ void LoadTileT(double* dst, const double* __restrict__ src, int ld, int tid) {
-  const double2 a0 = TileLoad2T<kCoh>(src, ld, tid, 0), a1 = TileLoad2T<kCoh>(src, ld, tid, 1);
-  TileStore2(dst, tid, 0, a0); TileStore2(dst, tid, 1, a1);
-}
-template <bool kCoh>
-__device__ __forceinline__ double LoadS(const double* p) { return kCoh ? LoadCoherent(p) : *p; }
 __device__ __forceinline__ void LoadTile(double* dst, const double* __restrict__ src, int ld, int tid) {
   const double2 a0 = TileLoad2(src, ld, tid, 0), a1 = TileLoad2(src, ld, tid, 1);
   TileStore2(dst, tid, 0, a0); TileStore2(dst, tid, 1, a1);
@@ -349,6 +340,27 @@ __device__ __forceinline__ void StoreTile(double* __restrict__ dst, const double
     const double2 v = *reinterpret_cast<const double2*>(src + r * kLS + 2 * c2);
     StoreThrough(dst + (size_t)r * ld + 2 * c2, v.x);
     StoreThrough(dst + (size_t)r * ld + 2 * c2 + 1, v.y);
+  }
+}
+
+// Values that are their own ready flags (the mailbox slots of task mode, the x of the back substitutions): a slot is preset to an all-ones NaN
+// pattern, the producer stores write-through, the consumer polls with agent-scope loads until the pattern is gone.  A result that happens to be
+// the pattern (only a NaN can be) is stored as another NaN.
+constexpr unsigned long long kNotReady = 0xFFFFFFFFFFFFFFFFull;
+constexpr unsigned long long kNotReadyNaN = 0x7FF8000000000000ull;
+
+// A wavefront's 32x32 piece of a 128x128 super-tile update C -= A B^T (SyrkSuperTiles, UpdateSuperTile): 2x2 MFMA tiles, so every operand fetched
+// from LDS feeds two MFMAs.  ar / br: this lane's rows of the two 128x64 operand panels in LDS (tile a / b of the piece 16 rows apart).
+// (The load of the piece's 2x2x4 values of C and their write-through store stay written out in both callers: as shared helpers they changed
+// the register allocation of k_cholesky_tasks, which sits at its 128-VGPR cap.)
+__device__ __forceinline__ void SuperTileProducts(v4f64 (&p)[2][2], const double* ar, const double* br) {
+#pragma unroll
+  for (int kk = 0; kk < 16; ++kk) {
+    const double a0v = ar[4 * kk], a1v = ar[16 * kLS + 4 * kk], b0v = br[4 * kk], b1v = br[16 * kLS + 4 * kk];
+    p[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0v, b0v, p[0][0], 0, 0, 0);
+    p[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0v, b1v, p[0][1], 0, 0, 0);
+    p[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1v, b0v, p[1][0], 0, 0, 0);
+    p[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1v, b1v, p[1][1], 0, 0, 0);
   }
 }
 

@@ -1,5 +1,6 @@
-// The task planner of the one-launch Cholesky factorisation (cholesky.hip: k_cholesky_tasks), host only and free of any device API: the vocabulary the
-// kernel shares with it (chain ranges, the counter layout, ChainTask and the accessors of its packed fields), the chains of a tile map (PlanChains), the
+// The task planner of the one-launch Cholesky factorisation (chol_tasks.hpp: k_cholesky_tasks), host only and free of any device API: the vocabulary the
+// kernel shares with it (chain ranges, the counter layout, ChainTask and the accessors of its packed fields), the layout of the workspace every launch
+// path takes its pointers from (CholWorkspace), the chains of a tile map (PlanChains), the
 // priority-sorted task list of a plan (BuildTaskList), the host replay that decides whether a list may be launched at all (TaskListWaitsAreMet) and the
 // per-column row / super-tile lists of the block-sparse per-column launches (BuildSparseColumnLists).
 // Includes the standard library and switches.hpp only: g++ -std=c++17 compiles it on its own, and tests/chol_plan_host_driver.cpp runs it under
@@ -49,7 +50,24 @@ constexpr int kMaxSuper = kMaxSteps / 2 + 1;
 constexpr int kScratchCounters = 2048;      // counters of the per-chain accumulation sequences (several chains, see ChainRanges), handed out by the host
 enum { cSol0 = 8, cVer0 = cSol0 + kMaxChains * kMaxSteps, cSub0 = cVer0 + kMaxSuper * kMaxSuper, cScratch0 = cSub0 + kMaxSuper * kMaxSuper,
        kNumCounters = cScratch0 + kScratchCounters };      // sol: one set of row counters per chain (cSol0 + chain x kMaxSteps + row)
-static_assert(kNumCounters * sizeof(int32_t) <= 8192 * sizeof(double), "counters exceed their part of the workspace (CholeskyWorkspaceDoubles)");
+
+// The workspace `Linv_ws` of one factorisation of T block columns: where each part starts, in doubles, and the total - the one place that knows.
+//   Minv[T]     the 64 x 64 row-major inverses L_kk^-1 = the M_k mailboxes of task mode (solves, back substitution, CholeskyFactor)
+//   xs[T+1]     the chain's X tile per step (per-column mode uses slots k & 1 in turn; task mode: one mailbox per step)
+//   ds[T+1], xsol[T+1]   the D and solved-X mailboxes of task mode
+//   counters    kNumCounters int32 (the progress counters of task mode) in kCounterDoubles doubles
+//   Pw[npairs], Zw[4 npairs]   pair inverses and pair couplings of the paired back substitution, npairs = BacksubNumPairs(T) <= T / 2 + 1 (what is reserved)
+// The MailDoubles() in front of the counters are the mailbox slots: what k_potrf64 presets to the "not ready" pattern.
+struct CholWorkspace {
+  static constexpr size_t kTile = 64 * 64, kCounterDoubles = 8192;
+  size_t Minv, xs, ds, xsol, counters, Pw, Zw, total;
+  constexpr explicit CholWorkspace(int T)
+      : Minv(0), xs(Minv + (size_t)T * kTile), ds(xs + (size_t)(T + 1) * kTile), xsol(ds + (size_t)(T + 1) * kTile), counters(xsol + (size_t)(T + 1) * kTile),
+        Pw(counters + kCounterDoubles), Zw(Pw + (size_t)BacksubNumPairs(T) * kTile), total(Pw + (size_t)(T / 2 + 1) * 5 * kTile) {}
+  constexpr size_t MailDoubles() const { return counters; }
+};
+static_assert(kNumCounters * sizeof(int32_t) <= CholWorkspace::kCounterDoubles * sizeof(double), "the counters exceed their part of the workspace");
+static_assert(CholWorkspace(kMaxSteps).Zw + 4 * (size_t)BacksubNumPairs(kMaxSteps) * CholWorkspace::kTile <= CholWorkspace(kMaxSteps).total, "the pairs exceed theirs");
 enum { kTaskPrepX = 1, kTaskPrepD = 2, kTaskSolve = 3, kTaskUpdate = 4, kTaskPairPrep = 5, kTaskMerge = 6 };      // pair prep: a = pair, b = part (paired back substitution)
 // solve: a = block row; update: a = I, b = J | part << 8 | parts << 12 | target << 16: a PART of super-tile (I,J) - parts = 2: block row
 // 2I + part (both block columns); parts = 4: the one 64x64 tile (2I + part / 2, 2J + part % 2).  The part that brings the

@@ -2,7 +2,7 @@
 // g++ -std=c++17 -Wall -Wextra -fsanitize=address,undefined compiles it; it includes the planner header and nothing else of the project.
 // stdin: one structure per line, "<name> <T> <max_chains> dense" (no tile map: the list a dense solve builds) or "<name> <T> <max_chains> <T*T x 0|1>"
 // (a lower-triangular tile map, row-major; max_chains 0: as many as the structure has) - what pp_cholesky_task_list / pp_cholesky_task_plan take.
-// stdout: the counter layout once, then per structure the chains, time, rho1, the closed map, the replay's verdict, the 16 words of every task and
+// stdout: the counter layout once, the workspace layout (CholWorkspace) for T = 1 .. 160, then per structure the chains, time, rho1, the closed map, the replay's verdict, the 16 words of every task and
 // the per-column lists of the block-sparse per-column launches.
 #include <cstdio>
 #include <iostream>
@@ -28,6 +28,12 @@ int main() {
   const ChainTask packed{kTaskUpdate, 0, 0, PackUpdate(64, 3, kPartsTwoPanels, 1234), 0, 0, 0, PackFlags(true, 15), 0, 0, 0, 0, {0, 0, 0, 0}};
   std::printf("packed %d %d %d %d %d %d b %d flags %d\n", TaskSuperColumn(packed.b), TaskPart(packed.b), TaskParts(packed.b), TaskTarget(packed.b), TaskFirstOfChain(packed.flags) ? 1 : 0, TaskChain(packed.flags),
               (int)packed.b, (int)packed.flags);
+  // the workspace layout for T = 1 .. 160 block columns (both sides of kMaxSteps), in doubles
+  std::printf("wsconst kTile %zu kCounterDoubles %zu kNumCounters %d\n", CholWorkspace::kTile, CholWorkspace::kCounterDoubles, (int)kNumCounters);
+  for (int T = 1; T <= 160; ++T) {
+    const CholWorkspace w(T);
+    std::printf("ws %d %zu %zu %zu %zu %zu %zu %zu %zu %zu %d\n", T, w.Minv, w.xs, w.ds, w.xsol, w.counters, w.Pw, w.Zw, w.total, w.MailDoubles(), BacksubNumPairs(T));
+  }
   const PlanSwitches ps;
   std::string line;
   while (std::getline(std::cin, line)) {

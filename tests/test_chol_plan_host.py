@@ -35,8 +35,10 @@ def dump(tmp_path_factory):
     head, structs, cur = {}, {}, None
     for line in out.stdout.splitlines():
         tok = line.split()
-        if tok[0] in ("layout", "packed"):
+        if tok[0] in ("layout", "packed", "wsconst"):
             head[tok[0]] = tok[1:]
+        elif tok[0] == "ws":
+            head.setdefault("ws", []).append([int(t) for t in tok[1:]])
         elif tok[0] == "struct":
             cur = structs.setdefault(tok[1], {"T": int(tok[2]), "tasks": []})
         elif tok[0] == "end":
@@ -67,6 +69,29 @@ def test_counter_layout_and_packed_fields(dump):
     assert (layout["cVer0"], layout["cSub0"]) == (order.C_VER0, order.C_SUB0)
     assert layout["cScratch0"] == order.C_SUB0 + order.MAX_SUPER * order.MAX_SUPER and layout["kPartsTwoPanels"] == 8
     assert dump[1]["packed"] == ["64", "3", "8", "1234", "1", "15", "b", str(64 | 3 << 8 | 8 << 12 | 1234 << 16), "flags", str(1 | 15 << 4)]
+
+
+def test_workspace_layout(dump):
+    """CholWorkspace (csrc/chol_plan.hpp), the one description of the Cholesky workspace, for T = 1 .. 160 block columns (both sides of kMaxSteps = 128):
+    the parts follow each other without overlap - M[T], X[T+1], D[T+1], solved X[T+1] in 64 x 64 tiles, the counters, the pair inverses [npairs] and
+    pair couplings [4 npairs] - tiles start on tile boundaries, the counter part holds kNumCounters int32, the pairs end inside the total, and the total
+    is the size every caller has allocated so far, written out"""
+    const = dict(zip(dump[1]["wsconst"][0::2], (int(v) for v in dump[1]["wsconst"][1::2])))
+    tile = 64 * 64
+    assert const["kTile"] == tile and const["kNumCounters"] * 4 <= const["kCounterDoubles"] * 8
+    rows = dump[1]["ws"]
+    assert [r[0] for r in rows] == list(range(1, 161))
+    for T, Minv, xs, ds, xsol, counters, Pw, Zw, total, mail, npairs in rows:
+        assert npairs == ((T - 3) // 2 if T >= 7 else 0), T
+        starts = [Minv, xs, ds, xsol, counters, Pw, Zw]
+        sizes = [T * tile, (T + 1) * tile, (T + 1) * tile, (T + 1) * tile, const["kCounterDoubles"], npairs * tile, 4 * npairs * tile]
+        assert Minv == 0 and all(s % tile == 0 for s in starts), T
+        assert all(a < b for a, b in zip(starts[:5], starts[1:5] + [Pw])) and Pw <= Zw, T      # increasing (Pw == Zw where there are no pairs)
+        for (a, n), b in zip(zip(starts, sizes), starts[1:] + [total]):      # disjoint: every part ends where the next one starts, or before
+            assert a + n <= b, T
+        assert mail == counters == (4 * T + 3) * tile, T      # the mailbox slots k_potrf64 presets
+        assert Pw + 5 * npairs * tile <= total, T
+        assert total == (4 * T + 3) * 4096 + 8192 + (T // 2 + 1) * 5 * 4096, T
 
 
 def test_header_plans_what_the_library_plans(dump, default_switches):

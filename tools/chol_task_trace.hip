@@ -1,7 +1,8 @@
 // Timeline of ONE task-mode factorisation (k_cholesky_tasks) at cfg-3 size (T = 47): wall_clock64 stamps (100 MHz) per block
 // column of the chain workgroup (wait begin / work begin / end), the prep tasks and the first / last bulk task.
 // Build + run (GPU box):  hipcc -O3 -std=c++17 --offload-arch=gfx950 tools/chol_task_trace.hip \
-//     privacy_preserving_sfm_amd/csrc/capi_misc.hip -o /tmp/chol_task_trace && /tmp/chol_task_trace
+//     privacy_preserving_sfm_amd/csrc/capi_misc.hip privacy_preserving_sfm_amd/csrc/resource_pool.hip privacy_preserving_sfm_amd/csrc/switches.hip \
+//     -o /tmp/chol_task_trace && /tmp/chol_task_trace
 #define PP_CHOL_TRACE 1
 #ifndef PP_CHOL_SRC      // (A/B on one box against another revision of the file: -DPP_CHOL_SRC='"_ab/cholesky_base.inc"', see tools/ab_chain.sh)
 #define PP_CHOL_SRC "../privacy_preserving_sfm_amd/csrc/cholesky.hip"
@@ -149,10 +150,9 @@ int main(int argc, char** argv) {
   }
   if (argc > 3) {      // the chain workgroup ALONE: mailboxes still hold the previous run's X / D / M tiles, so it never waits
     using namespace ppsfm;
-    const size_t tile = 64 * 64;
-    Mailboxes mb;
-    mb.Minv = ws; mb.xs = ws + (size_t)T * tile; mb.ds = mb.xs + (size_t)(T + 1) * tile; mb.xsol = mb.ds + (size_t)(T + 1) * tile;
-    int32_t* ctr = reinterpret_cast<int32_t*>(mb.xsol + (size_t)(T + 1) * tile);
+    const CholWorkspace lay(T);
+    const Mailboxes mb = MailboxesOf(ws, lay);
+    int32_t* ctr = reinterpret_cast<int32_t*>(ws + lay.counters);
     const int nburn_arg = argc > 4 ? atoi(argv[4]) : 0;
     const int exps[] = {1, 2, 3, 4, 7, 8, 16, 0, 0, 0, 0, 0, 0};
     const int burns[] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 7, 63, 255, nburn_arg};
@@ -163,7 +163,7 @@ int main(int argc, char** argv) {
       hipMemcpyToSymbol(HIP_SYMBOL(ppsfm::g_chol_exp), &e, sizeof(e));
       hipMemcpy(S, h.data(), sizeof(double) * N * N, hipMemcpyHostToDevice);
       hipDeviceSynchronize();
-      hipLaunchKernelGGL(k_potrf64, dim3(1), dim3(kPanelThreads), 0, s, S, N, ws, mb.xs, flag, x, L, ctr, (int)kNumCounters, ws, (long long)((size_t)(4 * T + 3) * tile), OneChain(T));
+      hipLaunchKernelGGL(k_potrf64, dim3(1), dim3(kPanelThreads), 0, s, S, N, mb.Minv, mb.xs, flag, x, L, ctr, (int)kNumCounters, mb.Minv, (long long)lay.MailDoubles(), OneChain(T));
       hipEventRecord(e0, s);
       hipLaunchKernelGGL(k_cholesky_tasks, dim3(1 + nburn), dim3(kPanelThreads), 0, s, S, L, N, T, mb, flag, ctr, (const ChainTask*)nullptr, (const uint8_t*)nullptr, OneChain(T), (double*)nullptr);
       hipEventRecord(e1, s); hipEventSynchronize(e1);
