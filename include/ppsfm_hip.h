@@ -299,8 +299,8 @@ int pp_ba_reduced_system(pp_ba_handle h, const pp_ba_options* options, double ra
  *   H = J^T J, J the LOSS-CORRECTED Jacobian in the tangent coordinates of pp_ba_eval (jac_mode 0: 3 rotation-tangent + 3 tvec coordinates per pose, in that
  *   order); no Levenberg-Marquardt damping enters and the solver's Jacobi scaling is undone.  No sigma^2 factor is applied: the caller scales, as with Ceres.
  *   With the points eliminated, S = U - W V^-1 W^T:  Cov(pose i, pose j) = (S^-1)_ij,  Cov(point p) = V_p^-1 + (V_p^-1 W_p^T) S^-1 (W_p V_p^-1).
- *   Variable intrinsics stay in S, so the pose and point blocks are the correct marginals; the intrinsics' own blocks and the pose-point cross blocks are not
- *   returned.
+ *   Variable intrinsics stay in S, so the pose and point blocks are the correct marginals; the intrinsics' own blocks and the cross blocks (pose-point, point-point,
+ *   pose-intrinsics) come from pp_ba_covariance_blocks below.
  * pose_i / pose_j (num_pose_pairs each) and point_ids (num_points) are indices in the CALLER's image and point order whatever order the handle uses inside.
  * pose_cov: num_pose_pairs x 36, block q row-major = Cov(delta_i, delta_j) (the block of (j, i) is its transpose); point_cov: num_points x 9.
  * Constant blocks follow Ceres' convention: a constant pose has zero rows and columns, a constant tvec component a zero row and column, a constant point a
@@ -320,6 +320,24 @@ int pp_ba_covariance(pp_ba_handle h, const pp_ba_options* options,
                      int32_t num_pose_pairs, const int32_t* pose_i, const int32_t* pose_j, double* pose_cov /* pairs x 36, row-major */,
                      int32_t num_points, const int32_t* point_ids, double* point_cov /* points x 9 */,
                      pp_ba_covariance_info* info /* may be NULL */);
+
+/* The covariance block of ANY pair of parameter blocks (what ceres::Covariance::Compute takes as its list of block pairs): poses, the intrinsics
+ * blocks and points, in any of the six combinations.  The same H, the same undamped factorisation, tangent coordinates, scaling (none: no sigma^2) and
+ * side effects (none beyond the per-evaluation scratch; a pp_ba_solve after it is bit-identical) as pp_ba_covariance; with x = (c, p) the camera-side
+ * columns (poses, variable intrinsics) and the points, Z = L^-1 of S = L L^T and Y_p = Z (W_p V_p^-1):
+ *   Cov(c_a, c_b) = Z[:, a]^T Z[:, b],   Cov(c_a, point p) = -Z[:, a]^T Y_p,   Cov(point p, point q) = Y_p^T Y_q  (+ V_p^-1 when p == q).
+ * blocks[q] = (kind_a, index_a, kind_b, index_b), indices in the CALLER's order: PP_COV_POSE an image (6 rows: 3 rotation-tangent, 3 tvec),
+ * PP_COV_INTRINSICS a row of pp_ba_problem_desc's intrinsics array (12 rows: the block's parameter slots in parameter order), PP_COV_POINT a point
+ * (3 rows).  out: block q is row-major w(a_q) x w(b_q) and starts at the sum of w(a) w(b) over the blocks before it; capacity = doubles out can hold.
+ * Constant blocks follow pp_ba_covariance (a constant pose, tvec component or point: zero rows and columns); a constant intrinsics parameter, a slot
+ * beyond the camera model's parameter count and a block with nothing variable have zero rows and columns too.
+ * Errors: PP_ERR_INVALID, before any device work, for a NULL handle or options, an unknown kind, an index out of range and a capacity below the total;
+ * for an iterative or a group-attached handle; PP_ERR_NUMERIC when the undamped system is not positive definite - the handle solves as usual afterwards.
+ * num_blocks == 0: PP_OK, nothing is computed (info, when given, is zeroed).  Device memory beyond pp_ba_covariance's: the request and the output. */
+enum { PP_COV_POSE = 0, PP_COV_INTRINSICS = 1, PP_COV_POINT = 2 };      /* widths 6, 12, 3 */
+typedef struct pp_cov_block { int32_t kind_a, index_a, kind_b, index_b; } pp_cov_block;
+int pp_ba_covariance_blocks(pp_ba_handle h, const pp_ba_options* options, int64_t num_blocks, const pp_cov_block* blocks,
+                            double* out, int64_t capacity /* doubles */, pp_ba_covariance_info* info /* may be NULL */);
 
 /* Multi-GPU hook: one BA whose POINTS (with their observations) are sharded across the
  * ranks of a group; poses/intrinsics are replicated.  Each rank creates its handle from its own shard

@@ -249,6 +249,21 @@ class BundleAdjustmentProblem {
     for (int32_t i = 0; i < C_; ++i) pairs.emplace_back(i, i);
     return Covariance(options, pairs, pose_cov, point_ids, point_cov, info);
   }
+  // pp_ba_covariance_blocks: the covariance block of every listed pair of parameter blocks (PP_COV_POSE 6 rows, PP_COV_INTRINSICS 12, PP_COV_POINT 3; indices
+  // in the descriptor's order).  *out is sized here: block q row-major w(a_q) x w(b_q) at CovarianceBlockOffsets(blocks)[q].  Returns and throws as Covariance.
+  static std::vector<int64_t> CovarianceBlockOffsets(const std::vector<pp_cov_block>& blocks) {
+    const auto width = [](int32_t kind) { return kind == PP_COV_POSE ? 6 : kind == PP_COV_INTRINSICS ? 12 : 3; };
+    std::vector<int64_t> offsets(blocks.size() + 1, 0);
+    for (size_t q = 0; q < blocks.size(); ++q) offsets[q + 1] = offsets[q] + width(blocks[q].kind_a) * width(blocks[q].kind_b);
+    return offsets;
+  }
+  bool CovarianceBlocks(const pp_ba_options& options, const std::vector<pp_cov_block>& blocks, std::vector<double>* out, pp_ba_covariance_info* info = nullptr) {
+    out->assign(static_cast<size_t>(CovarianceBlockOffsets(blocks).back()), 0.0);
+    const int rc = pp_ba_covariance_blocks(h_, &options, static_cast<int64_t>(blocks.size()), blocks.data(), out->data(), static_cast<int64_t>(out->size()), info);
+    if (rc == PP_ERR_NUMERIC) return false;
+    Check(rc);
+    return true;
+  }
   pp_ba_handle handle() const { return h_; }
 
  private:

@@ -76,6 +76,15 @@ class BACovarianceInfo(C.Structure):
     _fields_ = [("n", C.c_int32), ("path", C.c_int32), ("device_ms", C.c_double), ("reserved", C.c_double * 2)]
 
 
+class CovBlock(C.Structure):
+    """pp_cov_block: one requested pair of parameter blocks of pp_ba_covariance_blocks"""
+    _fields_ = [("kind_a", C.c_int32), ("index_a", C.c_int32), ("kind_b", C.c_int32), ("index_b", C.c_int32)]
+
+
+COV_POSE, COV_INTRINSICS, COV_POINT = 0, 1, 2
+COV_WIDTH = {COV_POSE: 6, COV_INTRINSICS: 12, COV_POINT: 3}
+
+
 class RansacOptions(C.Structure):
     _fields_ = [("max_error", C.c_double), ("min_inlier_ratio", C.c_double), ("confidence", C.c_double),
                 ("dyn_num_trials_multiplier", C.c_double), ("min_num_trials", C.c_uint64), ("max_num_trials", C.c_uint64),
@@ -239,7 +248,7 @@ _EXPORTS = [
     "pp_last_error", "pp_device_count", "pp_debug_raise", "pp_debug_exclusive_scan", "pp_camera_num_params", "pp_camera_image_to_world_threshold",
     "pp_camera_image_to_world", "pp_camera_world_to_image",
     "pp_ba_options_default", "pp_ba_create", "pp_ba_destroy", "pp_ba_set_parameters", "pp_ba_get_parameters",
-    "pp_ba_eval", "pp_ba_eval_host_view", "pp_ba_eval_device", "pp_ba_solve", "pp_ba_get_trace", "pp_ba_get_structure", "pp_ba_get_intrinsics_layout", "pp_ba_plan_ordering", "pp_ba_pair_lists_host", "pp_ba_covisibility", "pp_ba_get_create_profile", "pp_ba_reduced_system", "pp_ba_covariance", "pp_ba_set_allreduce", "pp_ba_set_communicator", "pp_comm_unique_id", "pp_comm_create", "pp_comm_destroy",
+    "pp_ba_eval", "pp_ba_eval_host_view", "pp_ba_eval_device", "pp_ba_solve", "pp_ba_get_trace", "pp_ba_get_structure", "pp_ba_get_intrinsics_layout", "pp_ba_plan_ordering", "pp_ba_pair_lists_host", "pp_ba_covisibility", "pp_ba_get_create_profile", "pp_ba_reduced_system", "pp_ba_covariance", "pp_ba_covariance_blocks", "pp_ba_set_allreduce", "pp_ba_set_communicator", "pp_comm_unique_id", "pp_comm_create", "pp_comm_destroy",
     "pp_comm_allreduce",
     "pp_ba_get_timings", "pp_pool_trim", "pp_pool_stats", "pp_dense_cholesky_solve", "pp_cholesky_task_list", "pp_cholesky_task_list_sparse", "pp_cholesky_task_plan",
     "pp_pose_create", "pp_pose_destroy", "pp_pose_residuals", "pp_pose_score", "pp_pose_support_sequential",
@@ -298,6 +307,7 @@ def lib():
     L.pp_ba_get_create_profile.argtypes = [C.c_void_p, c_dp]
     L.pp_ba_reduced_system.argtypes = [C.c_void_p, C.POINTER(BAOptions), C.c_double, c_ip, c_dp, c_dp, C.c_int64]
     L.pp_ba_covariance.argtypes = [C.c_void_p, C.POINTER(BAOptions), C.c_int32, c_ip, c_ip, c_dp, C.c_int32, c_ip, c_dp, C.POINTER(BACovarianceInfo)]
+    L.pp_ba_covariance_blocks.argtypes = [C.c_void_p, C.POINTER(BAOptions), C.c_int64, C.POINTER(CovBlock), c_dp, C.c_int64, C.POINTER(BACovarianceInfo)]
     L.pp_ba_set_allreduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
     L.pp_ba_set_communicator.argtypes = [C.c_void_p, C.c_void_p]
     L.pp_comm_unique_id.argtypes = [c_u8p]

@@ -732,6 +732,34 @@ class BundleAdjuster:
             pb.close()
         return ({k: pc[q] for q, k in enumerate(image_ids)}, {p: xc[q] for q, p in enumerate(pids)})
 
+    def CovarianceBlocks(self, reconstruction, blocks):
+        """The covariance block of every listed pair of parameter blocks (ceres::Covariance::Compute's list of block pairs): blocks = pairs (key_a, key_b),
+        a key ("image", image_id) - 6 rows: 3 rotation, 3 tvec -, ("camera", camera_id) - the camera's NumParams() parameters - or ("point", point3D_id).
+        Returns {(key_a, key_b): w_a x w_b array}.  Conventions, refusals and errors as Covariance, which it leaves as it is."""
+        flat = self.flatten(reconstruction)
+        if flat is None:
+            return {}
+        scene, pose_index, point_index, cam_index = flat
+        index = {"image": ("pose", pose_index), "camera": ("intrinsics", cam_index), "point": ("point", point_index)}
+        keys = [(tuple(a), tuple(b)) for a, b in blocks]
+        for key in keys:
+            for what, _ in key:
+                if what not in index:
+                    raise ValueError("CovarianceBlocks: unknown key %r (image, camera, point)" % (what,))
+        request = [tuple((index[what][0], index[what][1][i]) for what, i in key) for key in keys]
+        kMaxNumImagesDirectSparseSolver = 1000
+        if self.config_.NumImages() > kMaxNumImagesDirectSparseSolver:
+            raise ValueError("CovarianceBlocks needs the direct solver's reduced camera system: at most %d images" % kMaxNumImagesDirectSparseSolver)
+        pb = BAProblem(scene, device=self.device_, linear_solver=_capi.LINEAR_SOLVER_DIRECT)
+        try:
+            out = pb.covariance_blocks(request)
+        finally:
+            pb.close()
+
+        def rows(side):      # a camera side keeps the parameters its model has
+            return reconstruction.Camera(side[1]).NumParams() if side[0] == "camera" else None
+        return {key: out[q][:rows(key[0]), :rows(key[1])] for q, key in enumerate(keys)}
+
     @staticmethod
     def write_back(reconstruction, flat, poses, points, intr):
         """the solved parameters of `flatten()`'s problem into the reconstruction: the variable blocks only"""

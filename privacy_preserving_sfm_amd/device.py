@@ -80,6 +80,24 @@ def plan_ordering(scene, linear_solver=0, ordering=_capi.ORDERING_AUTO):
                      block_columns=int(info[5]), block_sparse=bool(info[6]), intrinsics_columns=int(info[7]))
 
 
+_COV_KINDS = {"pose": _capi.COV_POSE, "intrinsics": _capi.COV_INTRINSICS, "point": _capi.COV_POINT}
+
+
+def _cov_block_request(blocks):
+    """((kind, index), (kind, index)) pairs -> (pp_cov_block array, [(w_a, w_b)], offsets [len + 1]: block q at offsets[q] .. offsets[q + 1] of the output)"""
+    blocks = list(blocks)
+    req = (_capi.CovBlock * max(1, len(blocks)))()
+    shapes, offsets = [], [0]
+    for q, ((ka, ia), (kb, ib)) in enumerate(blocks):
+        for k in (ka, kb):
+            if k not in _COV_KINDS:
+                raise ValueError("covariance_blocks: block %d has the unknown kind %r (pose, intrinsics, point)" % (q, k))
+        req[q] = _capi.CovBlock(_COV_KINDS[ka], int(ia), _COV_KINDS[kb], int(ib))
+        shapes.append((_capi.COV_WIDTH[_COV_KINDS[ka]], _capi.COV_WIDTH[_COV_KINDS[kb]]))
+        offsets.append(offsets[-1] + shapes[-1][0] * shapes[-1][1])
+    return req, shapes, offsets
+
+
 class BAProblem:
     """Device-resident bundle adjustment problem (one per sub-model / GPU).
 
@@ -219,6 +237,19 @@ class BAProblem:
         check(_capi.lib().pp_ba_covariance(self._h, C.byref(o), len(pi), ptr(pi, _capi.c_ip), ptr(pj, _capi.c_ip), dp(pc), len(ids), ptr(ids, _capi.c_ip), dp(xc),
                                            C.byref(info)))
         return (pc, xc, info) if return_info else (pc, xc)
+
+    def covariance_blocks(self, blocks, options=None, return_info=False):
+        """pp_ba_covariance_blocks at the current parameters: the covariance block of every requested pair of parameter blocks.
+        blocks: sequence of ((kind, index), (kind, index)), kind "pose" (an image of the scene, 6 rows: 3 rotation, 3 tvec), "intrinsics" (a row of the
+        scene's intr, 12 rows: its parameter slots) or "point" (3 rows).  Returns a list of arrays of shape (w_a, w_b), in request order; zero rows and
+        columns for what is constant.  No sigma^2 factor is applied.  return_info: also the BACovarianceInfo (n, path, device_ms)."""
+        o = options or ba_options()
+        req, shapes, offsets = _cov_block_request(blocks)
+        out = np.zeros(offsets[-1])
+        info = _capi.BACovarianceInfo()
+        check(_capi.lib().pp_ba_covariance_blocks(self._h, C.byref(o), len(shapes), req, dp(out), out.size, C.byref(info)))
+        res = [out[offsets[q]:offsets[q + 1]].reshape(shapes[q]).copy() for q in range(len(shapes))]
+        return (res, info) if return_info else res
 
     def timings(self):
         ms = np.zeros(len(_capi.BA_T_NAMES)); calls = np.zeros(len(_capi.BA_T_NAMES), dtype=np.int32)
