@@ -1205,6 +1205,51 @@ typedef struct pp_line_features_report {
 int pp_line_features_from_keypoints(const pp_line_features_desc* desc, const pp_line_features_options* options, int device, double* lines_out,
                                     uint8_t* aligned_out, double* dirs_out, pp_line_features_report* report);
 
+/* ======================================================================================== *
+ *  Image-pair selection (K20)                                                               *
+ *  replaces: the neighbour search of SpatialFeatureMatcher::Run (feature/matching.cc:       *
+ *  705-768) and the candidate walk of one iteration of TransitiveFeatureMatcher::Run        *
+ *  (:818-869); the sequential selection is closed-form host code (feature_matching.py)      *
+ * ======================================================================================== */
+
+typedef struct pp_pairs_report {
+  int64_t num_pairs;        /* the pairs of the result                                                                                       */
+  int64_t num_candidates;   /* spatial: num_locations^2 distances per pass; transitive: the (a, b, c) walks, the sum of degree(b)^2          */
+  double device_ms;         /* the kernels, by events                                                                                        */
+  double total_ms;          /* the call: checks, uploads, the kernels, the two waits for a count                                             */
+} pp_pairs_report;
+
+typedef struct pp_pairs_impl* pp_pairs_handle;
+/* A handle keeps the result of its last selection on the device, so that asking for its size and fetching it compute nothing again.  A new handle holds
+ * an empty result. */
+int pp_pairs_create(int device, pp_pairs_handle* out);
+int pp_pairs_destroy(pp_pairs_handle h);
+/* The nearest neighbours of every location among all of them: xyz num_locations x 3 floats, knn = min(max_num_neighbors, num_locations).  The squared
+ * distance is ((d0*d0) + d1*d1) + d2*d2 in float with every operation rounded on its own (never fused); the candidates of a query are ordered by
+ * (squared distance, location index) ascending; of the first knn the query itself is dropped where it is among them, and the list is cut at the first
+ * squared distance > (float)(max_distance * max_distance).  The result is the pairs (query, neighbour) as location indices, query by query in that
+ * order, with the squared distances beside them: a fixed function of the input, bit for bit.
+ * Every 1 <= knn <= num_locations is served.  Up to max_num_neighbors = 256 one selection round per query finds the list (about 6 to 9 passes over the
+ * locations); above it the round is repeated for every further 256 ranks, so the cost grows with ceil(knn / 256).
+ * ERRORS: PP_ERR_INVALID before any device work, the previous result untouched, for: a null argument, a negative num_locations or 2^31 - 1 or more, a
+ * coordinate that is not finite, max_num_neighbors <= 0, max_distance <= 0 (NaN included).  PP_ERR_INVALID after the count and before anything is
+ * written, the previous result still untouched, for a result of 2^31 - 1 pairs or more. */
+int pp_pairs_spatial(pp_pairs_handle h, int64_t num_locations, const float* xyz, int32_t max_num_neighbors, double max_distance, pp_pairs_report* report);
+/* One iteration of the transitive selection over num_images image positions.  matched_pairs (num_matched x 2) are the pairs with a non-empty match
+ * list: they make the adjacency, in either orientation, repeats allowed.  tried_pairs (num_tried x 2) are the pairs that have been matched before with
+ * whatever outcome.  The matched pairs are UNIONED into the tried ones: a caller may, but need not, list a matched pair among the tried.  The result is
+ * every {a, c}, a != c, with a common neighbour that is not tried, as (a, c) with a < c, ascending in (a, c); no distances.  The images are walked in
+ * chunks of 32768 positions, any num_images is served.
+ * ERRORS: PP_ERR_INVALID before any device work, the previous result untouched, for: a null argument, a negative count, a position outside
+ * [0, num_images), 2^30 listed pairs or more.  PP_ERR_INVALID after the count, the previous result still untouched, for 2^31 - 1 pairs or more. */
+int pp_pairs_transitive(pp_pairs_handle h, int32_t num_images, int64_t num_matched, const int32_t* matched_pairs, int64_t num_tried,
+                        const int32_t* tried_pairs, pp_pairs_report* report);
+/* The size of the last result (0 for a new handle). */
+int pp_pairs_num(pp_pairs_handle h, int64_t* n);
+/* The last result: pairs n x 2 int32 positions, sqdist n floats; `capacity` pairs of room in each.  Either pointer may be NULL; sqdist must be NULL
+ * after a transitive selection that found pairs.  PP_ERR_INVALID, nothing written, when capacity is too small. */
+int pp_pairs_get(pp_pairs_handle h, int32_t* pairs, float* sqdist, int64_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,10 @@ class LineFeaturesReport(C.Structure):
                 ("num_newton_exhausted", C.c_int64), ("device_ms", C.c_double)]
 
 
+class PairsReport(C.Structure):
+    _fields_ = [("num_pairs", C.c_int64), ("num_candidates", C.c_int64), ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -266,6 +270,7 @@ _EXPORTS = [
     "pp_sift_match_options_default", "pp_sift_create", "pp_sift_destroy", "pp_sift_match_pairs", "pp_sift_top2", "pp_sift_match_thresholds",
     "pp_corr_graph_create", "pp_corr_graph_destroy", "pp_corr_graph_build", "pp_corr_graph_num_entries", "pp_corr_graph_get", "pp_corr_graph_pair_counts",
     "pp_line_features_options_default", "pp_line_features_from_keypoints",
+    "pp_pairs_create", "pp_pairs_destroy", "pp_pairs_spatial", "pp_pairs_transitive", "pp_pairs_num", "pp_pairs_get",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -405,6 +410,12 @@ def lib():
     L.pp_line_features_options_default.restype = None
     L.pp_line_features_from_keypoints.argtypes = [C.POINTER(LineFeaturesDesc), C.POINTER(LineFeaturesOptions), C.c_int, c_dp, c_u8p, c_dp,
                                                   C.POINTER(LineFeaturesReport)]
+    L.pp_pairs_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.pp_pairs_destroy.argtypes = [C.c_void_p]
+    L.pp_pairs_spatial.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_int32, C.c_double, C.POINTER(PairsReport)]
+    L.pp_pairs_transitive.argtypes = [C.c_void_p, C.c_int32, C.c_int64, c_ip, C.c_int64, c_ip, C.POINTER(PairsReport)]
+    L.pp_pairs_num.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.pp_pairs_get.argtypes = [C.c_void_p, c_ip, C.POINTER(C.c_float), C.c_int64]
     _lib = L
     return L
 

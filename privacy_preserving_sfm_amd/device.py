@@ -1090,6 +1090,56 @@ class CorrGraphBuilder:
         return out[:self.num_pairs or 0]
 
 
+class PairSelector:
+    """pp_pairs_handle (K20): spatial() and transitive() select image pairs on the device and return them; the handle keeps the last result."""
+
+    def __init__(self, device=0):
+        self._h = C.c_void_p()
+        check(_capi.lib().pp_pairs_create(int(device), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            _capi.lib().pp_pairs_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def num(self):
+        n = C.c_int64()
+        check(_capi.lib().pp_pairs_num(self._h, C.byref(n)))
+        return n.value
+
+    def get(self, want_sqdist=True):
+        """the last result -> (pairs [n, 2] int32 positions, sqdist [n] float32 or None)"""
+        n = self.num()
+        pairs = np.zeros((max(n, 1), 2), dtype=np.int32)
+        sqdist = np.zeros(max(n, 1), dtype=np.float32) if want_sqdist else None
+        check(_capi.lib().pp_pairs_get(self._h, ptr(pairs, _capi.c_ip), ptr(sqdist, C.POINTER(C.c_float)), n))
+        return pairs[:n], None if sqdist is None else sqdist[:n]
+
+    def spatial(self, xyz, max_num_neighbors, max_distance):
+        """xyz [m, 3] float32 -> (report, pairs [n, 2] of location indices, sqdist [n] float32)"""
+        loc = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        rep = _capi.PairsReport()
+        check(_capi.lib().pp_pairs_spatial(self._h, int(loc.shape[0]), ptr(loc, C.POINTER(C.c_float)) if loc.size else None, int(max_num_neighbors),
+                                           float(max_distance), C.byref(rep)))
+        pairs, sqdist = self.get()
+        return rep, pairs, sqdist
+
+    def transitive(self, num_images, matched_pairs, tried_pairs=()):
+        """matched_pairs / tried_pairs [k, 2] image positions (the matched ones count as tried) -> (report, pairs [n, 2], a < c, ascending)"""
+        matched = np.ascontiguousarray(matched_pairs, dtype=np.int32).reshape(-1, 2)
+        tried = np.ascontiguousarray(tried_pairs, dtype=np.int32).reshape(-1, 2)
+        rep = _capi.PairsReport()
+        check(_capi.lib().pp_pairs_transitive(self._h, int(num_images), int(matched.shape[0]), ptr(matched, _capi.c_ip) if matched.size else None,
+                                              int(tried.shape[0]), ptr(tried, _capi.c_ip) if tried.size else None, C.byref(rep)))
+        return rep, self.get(want_sqdist=False)[0]
+
+
 def line_features_options(**kw):
     o = _capi.LineFeaturesOptions()
     _capi.lib().pp_line_features_options_default(C.byref(o))
