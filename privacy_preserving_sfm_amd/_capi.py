@@ -425,6 +425,17 @@ def check(rc):
         raise PPError(rc, lib().pp_last_error().decode(errors="replace"))
 
 
+def options(struct_type, default_fn_name, **kw):
+    """struct_type as its pp_*_options_default fills it, then the fields named by keyword; a name the struct does not have raises AttributeError(name)"""
+    o = struct_type()
+    getattr(lib(), default_fn_name)(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
 def f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 

@@ -24,15 +24,12 @@
 #include "common.hpp"
 #include "p6l_device.hpp"
 #include "pose_device.hpp"
-#include "resource_pool.hpp"
+#include "device_handle.hpp"
 #include "ransac_host.hpp"
 #include "scan.hpp"
 
-struct pp_pose_impl {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ppsfm::DeviceBlocks blocks{false};      // every device and pinned block below (plain hipMalloc / hipHostMalloc)
+struct pp_pose_impl : ppsfm::DeviceHandle {
+  pp_pose_impl() : DeviceHandle(false) {}      // blocks: every device and pinned block below (plain hipMalloc / hipHostMalloc)
   int32_t n = 0;
   double *l0 = nullptr, *l1 = nullptr, *l2 = nullptr, *x0 = nullptr, *x1 = nullptr, *x2 = nullptr;
   uint8_t* aligned = nullptr;
@@ -482,13 +479,7 @@ using namespace ppsfm;
 extern "C" {
 
 int pp_pose_destroy(pp_pose_handle h) try {
-  if (!h) return PP_OK;
-  (void)hipSetDevice(h->device);
-  h->blocks.Release();      // (plain device memory: freeing it waits for the device)
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;      // (~DeviceHandle)
   return PP_OK;
 } PP_API_CATCH("pp_pose_destroy")
 
@@ -497,18 +488,14 @@ int pp_pose_create(int32_t n, const double* lines2D, const double* points3D, con
   PP_REQUIRE(out, "pp_pose_create: null out");
   *out = nullptr;
   PP_REQUIRE(n >= 0 && (n == 0 || (lines2D && points3D)), "pp_pose_create: bad argument");
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "pp_pose_create: device %d of %d", device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
+  PP_TRY(UseDevice("pp_pose_create", device));
   const size_t nn = std::max(n, 1);
   std::vector<double> soa(6 * nn, 0.0);      // (before the handle: on an error return the handle's release - of plain device memory, which waits for the device - comes first)
   for (int i = 0; i < n; ++i)
     for (int c = 0; c < 3; ++c) { soa[c * nn + i] = lines2D[3 * i + c]; soa[(3 + c) * nn + i] = points3D[3 * i + c]; }
   UnderConstruction<pp_pose_impl, pp_pose_destroy> h{new pp_pose_impl()};
-  h->device = device; h->n = n;
-  PP_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  PP_HIP_TRY(hipEventCreate(&h->ev0)); PP_HIP_TRY(hipEventCreate(&h->ev1));
+  h->n = n;
+  PP_TRY(h->Open(device));
   double** dst[6] = {&h->l0, &h->l1, &h->l2, &h->x0, &h->x1, &h->x2};
   for (int c = 0; c < 6; ++c) PP_TRY(h->blocks.Put(dst[c], soa.data() + c * nn, nn, h->stream));
   if (aligned && n > 0) PP_TRY(h->blocks.Put(&h->aligned, aligned, (size_t)n, h->stream, nn));
@@ -529,9 +516,8 @@ int ppsfm::PoseCreateUnfilled(int32_t n, bool with_aligned, int device, pp_pose_
   PP_HIP_TRY(hipSetDevice(device));
   const size_t nn = std::max(n, 1);
   UnderConstruction<pp_pose_impl, pp_pose_destroy> h{new pp_pose_impl()};
-  h->device = device; h->n = n;
-  PP_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  PP_HIP_TRY(hipEventCreate(&h->ev0)); PP_HIP_TRY(hipEventCreate(&h->ev1));
+  h->n = n;
+  PP_TRY(h->Open(device));
   double** dst[6] = {&h->l0, &h->l1, &h->l2, &h->x0, &h->x1, &h->x2};
   for (int c = 0; c < 6; ++c) PP_TRY(h->blocks.Alloc(dst[c], nn));
   if (with_aligned && n > 0) PP_TRY(h->blocks.Alloc(&h->aligned, nn));

@@ -6,7 +6,7 @@
 #include <cstring>
 
 #include "ba_impl.hpp"
-#include "resource_pool.hpp"
+#include "device_handle.hpp"
 #include "camera_models.hpp"
 using namespace ppsfm;
 
@@ -107,10 +107,7 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   for (int k = 0; k < K; ++k) st.cam_np.push_back(CameraNumParams(d->camera_model[k]));
   st.intr = LayOutIntrinsics(C, K, d->pose_camera, st.cam_np.data(), d->camera_const_mask);
   const int NI = st.intr.NI; st.n_red = 6 * C + NI;
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "pp_ba_create: device %d of %d", device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
+  PP_TRY(UseDevice("pp_ba_create", device));
 
   const auto t_create0 = std::chrono::steady_clock::now();
   const ppsfm::Switches sw = ppsfm::ReadSwitches();      // (the handle's snapshot: nothing reads the environment after this)

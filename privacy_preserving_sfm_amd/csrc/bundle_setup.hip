@@ -190,8 +190,8 @@ int pp_tracks_bundle_setup(pp_tracks_handle h, const pp_bundle_config* cfg, pp_b
   if (L == 0 || P == 0) return finish(0.0);      // no line has a point
   PP_HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  EventTimer timer{h};
-  CallBlocks cb(s);
+  StreamTimer timer(*h);
+  CallScratch cb(s);
   std::vector<int32_t> start, elems;
   TrackDev d;
   PP_TRY(UploadState(h, cb, nullptr, start, elems, &d));

@@ -10,7 +10,7 @@
 #include "camera_models.hpp"
 #include "common.hpp"
 #include "ransac_host.hpp"
-#include "resource_pool.hpp"
+#include "device_handle.hpp"
 #include "scan.hpp"
 
 namespace ppsfm {
@@ -90,10 +90,7 @@ int pp_debug_exclusive_scan(int device, int elem_bytes, int64_t n, const void* i
   PP_REQUIRE(n >= 0 && n < 0x7FFFFFFFll, "%s: n is %lld", where, (long long)n);
   PP_REQUIRE(out0 && (n == 0 || in0), "%s: null array", where);
   PP_REQUIRE((in1 != nullptr) == (out1 != nullptr), "%s: the second job needs both in1 and out1", where);
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "%s: device %d of %d", where, device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
+  PP_TRY(UseDevice(where, device));
   const void* const in[2] = {in0, in1};
   void* const out[2] = {out0, out1};
   const int num_jobs = out1 ? 2 : 1;

@@ -15,11 +15,10 @@
 //                      per pair, so the ranks of a list are distinct and the places a permutation.  corr_line is written in pair order whatever slots the
 //                      atomics handed out; nothing in the result depends on the schedule.
 // K18g k_corr_image    one workgroup per image: lines with a neighbour, and the image's CSR entries.
-#include <chrono>
 #include <cstring>
 
 #include "corr_graph_replay.hpp"
-#include "resource_pool.hpp"
+#include "device_handle.hpp"
 #include "scan.hpp"
 
 namespace ppsfm {
@@ -162,13 +161,9 @@ __global__ __launch_bounds__(kCorrBlock) void k_corr_image(const int32_t* __rest
 
 }  // namespace ppsfm
 
-struct pp_corr_graph_impl {
-  int device = 0;
+struct pp_corr_graph_impl : ppsfm::DeviceHandle {      // blocks: line_start and the last build's CSR
   int32_t num_images = 0;
   std::vector<int32_t> num_lines, line_start;      // num_images, num_images + 1
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ppsfm::DeviceBlocks blocks;                      // line_start and the last build's CSR
   int32_t* d_line_start = nullptr;
   // the last build
   bool built = false;
@@ -183,24 +178,6 @@ struct pp_corr_graph_impl {
 using namespace ppsfm;
 
 namespace {
-
-using CorrClock = std::chrono::steady_clock;
-double CorrMsSince(CorrClock::time_point t0) { return std::chrono::duration<double, std::milli>(CorrClock::now() - t0).count(); }
-
-// pool blocks of one build, returned after the stream has drained on every way out
-struct CorrScratch {
-  hipStream_t s;
-  DeviceBlocks b;
-  explicit CorrScratch(hipStream_t stream) : s(stream) {}
-  ~CorrScratch() { (void)hipStreamSynchronize(s); }
-  template <typename T> int Alloc(T** p, size_t count) { return b.Alloc(p, count > 0 ? count : 1); }
-  template <typename T> int Zeros(T** p, size_t count) {
-    PP_TRY(Alloc(p, count));
-    PP_HIP_TRY(hipMemsetAsync(*p, 0, (count > 0 ? count : 1) * sizeof(T), s));
-    return PP_OK;
-  }
-  template <typename T> int Put(T** p, const T* src, size_t count) { return b.Put(p, src, count, s, 1); }
-};
 
 // the CSR of a build in the handle's blocks: given back unless the build completes
 struct CorrFresh {
@@ -219,14 +196,7 @@ struct CorrFresh {
 extern "C" {
 
 int pp_corr_graph_destroy(pp_corr_graph_handle h) try {
-  if (!h) return PP_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  h->blocks.Release();
-  if (h->ev0) PoolEventRelease(h->ev0, true);
-  if (h->ev1) PoolEventRelease(h->ev1, true);
-  if (h->stream) PoolStreamRelease(h->stream);
-  delete h;
+  delete h;      // (~DeviceHandle)
   return PP_OK;
 } PP_API_CATCH("pp_corr_graph_destroy")
 
@@ -241,17 +211,13 @@ int pp_corr_graph_create(int32_t num_images, const int32_t* num_lines, int devic
     total += num_lines[k];
   }
   PP_REQUIRE(total < 0x7FFFFFFFll - kScanTile, "%s: too many lines", where);
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "%s: device %d of %d", where, device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
+  PP_TRY(UseDevice(where, device));
   UnderConstruction<pp_corr_graph_impl, pp_corr_graph_destroy> h{new pp_corr_graph_impl()};
-  h->device = device; h->num_images = num_images;
+  h->num_images = num_images;
   h->num_lines.assign(num_lines, num_lines + num_images);
   h->line_start.assign((size_t)num_images + 1, 0);
   for (int32_t k = 0; k < num_images; ++k) h->line_start[(size_t)k + 1] = h->line_start[(size_t)k] + num_lines[k];
-  PP_TRY(PoolStreamAcquire(&h->stream));
-  PP_TRY(PoolEventAcquire(&h->ev0, true)); PP_TRY(PoolEventAcquire(&h->ev1, true));
+  PP_TRY(h->Open(device));
   PP_TRY(h->blocks.Put(&h->d_line_start, h->line_start.data(), h->line_start.size(), h->stream, 1));
   PP_HIP_TRY(hipStreamSynchronize(h->stream));
   *out = h.release();
@@ -263,7 +229,7 @@ int pp_corr_graph_build(pp_corr_graph_handle h, int32_t min_num_matches, int64_t
   const char* where = "pp_corr_graph_build";
   PP_REQUIRE(h && match_start && report, "%s: null argument", where);
   PP_REQUIRE(num_pairs >= 0 && num_pairs < 0x7FFFFFFFll && (num_pairs == 0 || pairs), "%s: bad argument", where);
-  const auto t_begin = CorrClock::now();
+  const auto t_begin = Clock::now();
   std::vector<CorrPairPlan> plan;
   std::vector<uint8_t> connected;
   int64_t num_ranked = 0;
@@ -290,7 +256,7 @@ int pp_corr_graph_build(pp_corr_graph_handle h, int32_t min_num_matches, int64_t
   PP_HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   CorrFresh fresh{&h->blocks};
-  CorrScratch cb(s);
+  CallScratch cb(s);
   CorrPairDev* d_plan = nullptr;
   CorrWork* d_work = nullptr;
   int64_t* d_mstart = nullptr;
@@ -306,9 +272,9 @@ int pp_corr_graph_build(pp_corr_graph_handle h, int32_t min_num_matches, int64_t
   PP_TRY(cb.Alloc(&d_img_obs, (size_t)h->num_images)); PP_TRY(cb.Alloc(&d_img_corr, (size_t)h->num_images));
   PP_TRY(h->blocks.Alloc(&fresh.start, (size_t)L + 1));
 
-  float device_ms = 0.f, part_ms = 0.f;
+  StreamTimer timer(*h);
   double replay_ms = 0.0;
-  PP_HIP_TRY(hipEventRecord(h->ev0, s));
+  PP_TRY(timer.Begin());
   if (!work.empty())
     hipLaunchKernelGGL(k_corr_first, dim3((unsigned)work.size()), dim3(kCorrBlock), 0, s, (const CorrWork*)d_work, (const CorrPairDev*)d_plan,
                        (const int64_t*)d_mstart, (const int32_t*)d_matches, d_dup1, d_dup2, d_cls);
@@ -316,17 +282,16 @@ int pp_corr_graph_build(pp_corr_graph_handle h, int32_t min_num_matches, int64_t
     hipLaunchKernelGGL(k_corr_accept, dim3(CeilDiv(M, kCorrBlock)), dim3(kCorrBlock), 0, s, M, (int32_t)num_pairs, (const CorrPairDev*)d_plan,
                        (const int64_t*)d_mstart, (const int32_t*)d_matches, (const uint8_t*)d_dup1, (const uint8_t*)d_dup2, d_pair_of, d_acc);
   PP_HIP_TRY(hipGetLastError());
-  PP_HIP_TRY(hipEventRecord(h->ev1, s));
+  PP_TRY(timer.End());
   std::vector<int32_t> cls(3 * (size_t)num_pairs, 0);
   PP_TRY(Download(cls.data(), d_cls, cls.size(), s));
   PP_HIP_TRY(hipStreamSynchronize(s));
-  PP_HIP_TRY(hipEventElapsedTime(&part_ms, h->ev0, h->ev1));
-  device_ms += part_ms;
+  PP_TRY(timer.Add());
 
   // the pairs the parallel rule is not the greedy one for: the literal loop, its flags over the device's
   int64_t replayed = 0, bad_index = 0, in_graph_pairs = 0;
   {
-    const auto t_replay = CorrClock::now();
+    const auto t_replay = Clock::now();
     std::vector<std::vector<uint8_t>> flags;
     std::vector<int32_t> stored;
     for (int64_t p = 0; p < num_pairs; ++p) {
@@ -344,22 +309,21 @@ int pp_corr_graph_build(pp_corr_graph_handle h, int32_t min_num_matches, int64_t
       ++replayed;
     }
     if (replayed) PP_HIP_TRY(hipStreamSynchronize(s));
-    replay_ms = CorrMsSince(t_replay);
+    replay_ms = MsSince(t_replay);
   }
 
-  PP_HIP_TRY(hipEventRecord(h->ev0, s));
+  PP_TRY(timer.Begin());
   if (M > 0)
     hipLaunchKernelGGL(k_corr_count, dim3(CeilDiv(M, kCorrBlock)), dim3(kCorrBlock), 0, s, M, (const CorrPairDev*)d_plan, (const int32_t*)d_matches,
                        (const int32_t*)d_pair_of, (const uint8_t*)d_acc, d_degree, d_pair_acc);
   const ScanJob<int32_t> degrees{d_degree, fresh.start, fresh.start + L};
   LaunchExclusiveScan(s, L, &degrees, 1, d_scan);
   PP_HIP_TRY(hipGetLastError());
-  PP_HIP_TRY(hipEventRecord(h->ev1, s));
+  PP_TRY(timer.End());
   std::vector<int32_t> pair_acc((size_t)num_pairs, 0);
   PP_TRY(Download(pair_acc.data(), d_pair_acc, pair_acc.size(), s));
   PP_HIP_TRY(hipStreamSynchronize(s));
-  PP_HIP_TRY(hipEventElapsedTime(&part_ms, h->ev0, h->ev1));
-  device_ms += part_ms;
+  PP_TRY(timer.Add());
   int64_t accepted = 0;
   for (int64_t p = 0; p < num_pairs; ++p) accepted += pair_acc[(size_t)p];
   // (2 * accepted <= 2 * M < 2^32: the degrees cannot have wrapped past a positive int32 total unnoticed - the check is on the exact count)
@@ -368,7 +332,7 @@ int pp_corr_graph_build(pp_corr_graph_handle h, int32_t min_num_matches, int64_t
 
   PP_TRY(h->blocks.Alloc(&fresh.line, (size_t)E));
   PP_TRY(cb.Alloc(&d_slot_rank, (size_t)E)); PP_TRY(cb.Alloc(&d_slot_line, (size_t)E)); PP_TRY(cb.Alloc(&d_slot_owner, (size_t)E));
-  PP_HIP_TRY(hipEventRecord(h->ev0, s));
+  PP_TRY(timer.Begin());
   if (E > 0) {
     PP_HIP_TRY(hipMemcpyAsync(d_cursor, fresh.start, ((size_t)L + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(k_corr_scatter, dim3(CeilDiv(M, kCorrBlock)), dim3(kCorrBlock), 0, s, M, E, (const CorrPairDev*)d_plan, (const int32_t*)d_matches,
@@ -380,14 +344,13 @@ int pp_corr_graph_build(pp_corr_graph_handle h, int32_t min_num_matches, int64_t
     hipLaunchKernelGGL(k_corr_image, dim3((unsigned)h->num_images), dim3(kCorrBlock), 0, s, (const int32_t*)h->d_line_start, (const int32_t*)fresh.start,
                        d_img_obs, d_img_corr);
   PP_HIP_TRY(hipGetLastError());
-  PP_HIP_TRY(hipEventRecord(h->ev1, s));
+  PP_TRY(timer.End());
   std::vector<int32_t> img_obs((size_t)h->num_images, 0), img_corr((size_t)h->num_images, 0);
   int32_t total_entries = -1;
   PP_TRY(Download(img_obs.data(), d_img_obs, img_obs.size(), s)); PP_TRY(Download(img_corr.data(), d_img_corr, img_corr.size(), s));
   PP_TRY(Download(&total_entries, fresh.start + L, 1, s));
   PP_HIP_TRY(hipStreamSynchronize(s));
-  PP_HIP_TRY(hipEventElapsedTime(&part_ms, h->ev0, h->ev1));
-  device_ms += part_ms;
+  PP_TRY(timer.Add());
   if ((int64_t)total_entries != E) { SetLastError("%s: the degrees sum to %d, the accepted matches to %lld entries", where, total_entries, (long long)E); return PP_ERR_INTERNAL; }
 
   // the build is complete: it replaces the handle's graph
@@ -401,7 +364,7 @@ int pp_corr_graph_build(pp_corr_graph_handle h, int32_t min_num_matches, int64_t
   report->num_matches_in = M; report->num_matches_accepted = accepted; report->num_matches_bad_index = bad_index;
   report->num_matches_duplicate = in_graph_pairs - bad_index - accepted;
   report->num_pairs_replayed = replayed;
-  report->device_ms = device_ms; report->replay_ms = replay_ms; report->total_ms = CorrMsSince(t_begin);
+  report->device_ms = timer.ms; report->replay_ms = replay_ms; report->total_ms = MsSince(t_begin);
   return PP_OK;
 } PP_API_CATCH("pp_corr_graph_build")
 

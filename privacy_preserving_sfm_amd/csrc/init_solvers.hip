@@ -27,7 +27,7 @@
 
 #include "common.hpp"
 #include "host_ticket.hpp"
-#include "resource_pool.hpp"
+#include "device_handle.hpp"
 #include "p6l_device.hpp"   // Solve3, Det3x3
 #include "init_lsq.hpp"
 #include "small_eigen.hpp"
@@ -50,12 +50,10 @@ struct PlanarView {   // per-view constants
   double c0[4], c1[4];   // z_j(2) = r3_j . X + c0_j + c1_j * ty_j
 };
 
-// what the three estimator handles carry alike (EstimatorOpen / EstimatorClose)
-struct EstimatorHandle {
-  DeviceBlocks blocks{false};      // every device / pinned block of the handle (plain hipMalloc / hipHostMalloc)
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;      // the bracket of BatchSolveScore's device time
+// what the three estimator handles carry alike.  blocks: every device / pinned block of the handle (plain hipMalloc / hipHostMalloc); ev0 / ev1: the
+// bracket of BatchSolveScore's device time
+struct EstimatorHandle : DeviceHandle {
+  EstimatorHandle() : DeviceHandle(false) {}
   int32_t n = 0;
   double* err = nullptr;       // n: the errors of the model evaluated last
 };
@@ -742,15 +740,17 @@ struct HostErrorBackend {
   int BatchSolveScore(uint32_t want, const int32_t* samples, std::vector<double>* models, std::vector<double>* scores, double* dev_s) {
     int r = self().Ensure(want); if (r) return r;
     r = Upload(h->samples, samples, (size_t)want * Derived::kMinSample, h->stream); if (r) return r;
-    PP_HIP_TRY(hipEventRecord(h->ev0, h->stream));
+    StreamTimer timer(*h);
+    PP_TRY(timer.Begin());
     self().EnqueueSolveScore(want);
     PP_HIP_TRY(hipGetLastError());
-    PP_HIP_TRY(hipEventRecord(h->ev1, h->stream));
+    PP_TRY(timer.End());
     models->resize((size_t)want * kDim); scores->resize(want);
     r = Download(models->data(), self().DeviceModels(), models->size(), h->stream); if (r) return r;
     r = Download(scores->data(), h->scores, scores->size(), h->stream); if (r) return r;
     PP_HIP_TRY(hipStreamSynchronize(h->stream));
-    float ms = 0; PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1)); *dev_s += ms * 1e-3;
+    PP_TRY(timer.Add());
+    *dev_s += timer.ms * 1e-3;
     return PP_OK;
   }
   // the errors of the model evaluated last stay on the host: ScoreModel and the GetInliers that follows it in a local optimisation (ransac.h:337-406) ask
@@ -1020,12 +1020,13 @@ struct FourView2dBackend {
     return PP_OK;
   }
   int BatchSolveScore(uint32_t want, const int32_t* samples, std::vector<double>* models, std::vector<double>* scores, double* dev_s) {
-    PP_HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    const int r = SolveBest(want, kMinSample, samples, models, scores);
-    if (r) return r;
-    PP_HIP_TRY(hipEventRecord(h->ev1, h->stream));
-    PP_HIP_TRY(hipEventSynchronize(h->ev1));
-    float ms = 0; PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1)); *dev_s += ms * 1e-3;
+    StreamTimer timer(*h);
+    PP_TRY(timer.Begin());
+    PP_TRY(SolveBest(want, kMinSample, samples, models, scores));
+    PP_TRY(timer.End());
+    PP_HIP_TRY(hipEventSynchronize(timer.ev1));
+    PP_TRY(timer.Add());
+    *dev_s += timer.ms * 1e-3;
     return PP_OK;
   }
   // NonMinimalSolver (sfm2d.cc:446-467): the winner of the sample's candidates becomes a pooled model with its score; ONE synchronisation brings back
@@ -1092,31 +1093,8 @@ struct FourView2dBackend {
 };
 
 // ---- what the C entry points of the three estimators share ------------------------------------------------------
-// Opens a handle that has just been allocated: device check (`who` = the create function, for the message), stream, the two events.  Host vectors of a
-// create function are built BEFORE its handle, so that on an error return the handle's release - of plain device memory, which waits for the device -
-// comes first.
-static int EstimatorOpen(EstimatorHandle* h, const char* who, int device, int32_t n) {
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "%s: device %d of %d", who, device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
-  h->device = device; h->n = n;
-  PP_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  PP_HIP_TRY(hipEventCreate(&h->ev0)); PP_HIP_TRY(hipEventCreate(&h->ev1));
-  return PP_OK;
-}
-// ... and closes it, whatever state its construction reached (nullptr: nothing to do)
-template <class H>
-static int EstimatorDestroy(H* h) {
-  if (!h) return PP_OK;
-  (void)hipSetDevice(h->device);
-  h->blocks.Release();      // (plain device memory: freeing it waits for the device)
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return PP_OK;
-}
+// Host vectors of a create function are built BEFORE its handle, so that on an error return the handle's release - of plain device memory, which waits
+// for the device - comes first.
 
 // pp_*_lomsac: the option check (`who` = the entry point), the run, and the copy-out of the inliers
 static int LomsacCheck(bool have_arguments, const pp_lomsac_options* o, const char* who) {
@@ -1149,15 +1127,18 @@ void pp_lomsac_options_default(pp_lomsac_options* o) {
 }
 
 int pp_planar_destroy(pp_planar_handle h) try {
-  return EstimatorDestroy(h);
+  delete h;      // (~DeviceHandle)
+  return PP_OK;
 } PP_API_CATCH("pp_planar_destroy")
 
 int pp_planar_create(int32_t n, const double* poses, const double* lines, const double* Rg, int device, pp_planar_handle* out) try {
   PP_REQUIRE(out && n > 0 && poses && lines && Rg, "pp_planar_create: bad argument");
   *out = nullptr;
-  std::vector<double> rec((size_t)n * kRec);      // (before the handle: EstimatorOpen)
+  PP_TRY(UseDevice("pp_planar_create", device));
+  std::vector<double> rec((size_t)n * kRec);      // (before the handle)
   UnderConstruction<pp_planar_impl, pp_planar_destroy> h{new pp_planar_impl()};
-  PP_TRY(EstimatorOpen(h.h, "pp_planar_create", device, n));
+  h->n = n;
+  PP_TRY(h->Open(device));
   std::memcpy(h->poses, poses, sizeof(h->poses));
   std::memcpy(h->Rg, Rg, sizeof(h->Rg));
   // per-view constants
@@ -1245,15 +1226,18 @@ int pp_planar_lomsac(pp_planar_handle h, const pp_lomsac_options* o, pp_lomsac_r
 } PP_API_CATCH("pp_planar_lomsac")
 
 int pp_pose2d_destroy(pp_pose2d_handle h) try {
-  return EstimatorDestroy(h);
+  delete h;      // (~DeviceHandle)
+  return PP_OK;
 } PP_API_CATCH("pp_pose2d_destroy")
 
 int pp_pose2d_create(int32_t n, const double* x, const double* X, int device, pp_pose2d_handle* out) try {
   PP_REQUIRE(out && n > 0 && x && X, "pp_pose2d_create: bad argument");
   *out = nullptr;
-  std::vector<double> xn(x, x + (size_t)2 * n);      // (before the handle: EstimatorOpen)
+  PP_TRY(UseDevice("pp_pose2d_create", device));
+  std::vector<double> xn(x, x + (size_t)2 * n);      // (before the handle)
   UnderConstruction<pp_pose2d_impl, pp_pose2d_destroy> h{new pp_pose2d_impl()};
-  PP_TRY(EstimatorOpen(h.h, "pp_pose2d_create", device, n));
+  h->n = n;
+  PP_TRY(h->Open(device));
   for (int i = 0; i < n; ++i) { const double nr = std::sqrt(xn[2 * i] * xn[2 * i] + xn[2 * i + 1] * xn[2 * i + 1]); xn[2 * i] /= nr; xn[2 * i + 1] /= nr; }   // sfm2d.h:104-109
   PP_TRY(h->blocks.Put(&h->x, xn.data(), xn.size(), h->stream)); PP_TRY(h->blocks.Put(&h->X, X, (size_t)2 * n, h->stream)); PP_TRY(h->blocks.Alloc(&h->err, (size_t)n));
   PP_HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1301,15 +1285,18 @@ int pp_pose2d_lomsac(pp_pose2d_handle h, const pp_lomsac_options* o, pp_lomsac_r
 } PP_API_CATCH("pp_pose2d_lomsac")
 
 int pp_fourview2d_destroy(pp_fourview2d_handle h) try {
-  return EstimatorDestroy(h);
+  delete h;      // (~DeviceHandle)
+  return PP_OK;
 } PP_API_CATCH("pp_fourview2d_destroy")
 
 int pp_fourview2d_create(int32_t n, const double* x, int device, pp_fourview2d_handle* out) try {
   PP_REQUIRE(out && n > 0 && x, "pp_fourview2d_create: bad argument");
   *out = nullptr;
-  std::vector<double> xn(x, x + (size_t)8 * n);      // (before the handle: EstimatorOpen)
+  PP_TRY(UseDevice("pp_fourview2d_create", device));
+  std::vector<double> xn(x, x + (size_t)8 * n);      // (before the handle)
   UnderConstruction<pp_fourview2d_impl, pp_fourview2d_destroy> h{new pp_fourview2d_impl()};
-  PP_TRY(EstimatorOpen(h.h, "pp_fourview2d_create", device, n));
+  h->n = n;
+  PP_TRY(h->Open(device));
   for (size_t i = 0; i < (size_t)4 * n; ++i) { const double nr = std::sqrt(xn[2 * i] * xn[2 * i] + xn[2 * i + 1] * xn[2 * i + 1]); xn[2 * i] /= nr; xn[2 * i + 1] /= nr; }   // sfm2d.h:62-67
   PP_TRY(h->blocks.Put(&h->x, xn.data(), xn.size(), h->stream)); PP_TRY(h->blocks.Alloc(&h->err, (size_t)n)); PP_TRY(h->blocks.Alloc(&h->X, (size_t)2 * n));
   PP_HIP_TRY(hipStreamSynchronize(h->stream));

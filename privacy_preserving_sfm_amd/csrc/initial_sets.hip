@@ -147,7 +147,7 @@ namespace {
 
 // one rocPRIM primitive: the size query, the temporary block, the call
 template <typename Call>
-int WithTemporary(CallBlocks& cb, const char* what, Call&& call) {
+int WithTemporary(CallScratch& cb, const char* what, Call&& call) {
   size_t bytes = 0;
   hipError_t e = call(nullptr, bytes);
   if (e == hipSuccess) {
@@ -224,8 +224,8 @@ int pp_tracks_find_initial_sets(pp_tracks_handle h, const pp_init_sets_options* 
   if (N == 0) return finish();
   PP_HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  EventTimer timer{h};
-  CallBlocks cb(s);
+  StreamTimer timer(*h);
+  CallScratch cb(s);
   const TrackDev d = h->dev;
   InitArgs a{};
   a.N = N;

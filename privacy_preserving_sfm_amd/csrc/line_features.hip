@@ -16,7 +16,7 @@
 
 #include "camera_models.hpp"
 #include "line_features_replay.hpp"
-#include "resource_pool.hpp"
+#include "device_handle.hpp"
 
 namespace ppsfm {
 
@@ -118,24 +118,6 @@ __global__ __launch_bounds__(kLfBlock) void k_lf_lines(int32_t num_tiles, const 
 
 using namespace ppsfm;
 
-namespace {
-
-// the pool blocks, the stream and the events of one call: the stream drains before anything goes back
-struct LfCall {
-  hipStream_t s = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  DeviceBlocks b;
-  ~LfCall() {
-    if (s) (void)hipStreamSynchronize(s);
-    b.Release();
-    if (ev0) PoolEventRelease(ev0, true);
-    if (ev1) PoolEventRelease(ev1, true);
-    if (s) PoolStreamRelease(s);
-  }
-};
-
-}  // namespace
-
 extern "C" {
 
 void pp_line_features_options_default(pp_line_features_options* o) {
@@ -183,14 +165,10 @@ int pp_line_features_from_keypoints(const pp_line_features_desc* desc, const pp_
     for (int64_t f = 0; f < N; f += kLfTile) tiles.push_back(LfTileDev{k, (int32_t)f});
   }
 
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "%s: device %d of %d", where, device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
-  LfCall call;
-  PP_TRY(PoolStreamAcquire(&call.s));
-  PP_TRY(PoolEventAcquire(&call.ev0, true)); PP_TRY(PoolEventAcquire(&call.ev1, true));
-  hipStream_t s = call.s;
+  PP_TRY(UseDevice(where, device));
+  DeviceHandle call;      // the pool blocks, the stream and the events of this call
+  PP_TRY(call.Open(device));
+  hipStream_t s = call.stream;
   LfImageDev* d_images = nullptr;
   LfTileDev* d_tiles = nullptr;
   int32_t *d_todo = nullptr, *d_model = nullptr;
@@ -198,16 +176,17 @@ int pp_line_features_from_keypoints(const pp_line_features_desc* desc, const pp_
   float* d_kp = nullptr;
   double *d_intr = nullptr, *d_gravity = nullptr, *d_lines = nullptr, *d_dirs = nullptr;
   uint8_t *d_hg = nullptr, *d_flags = nullptr;
-  PP_TRY(call.b.Put(&d_images, images.data(), images.size(), s, 1)); PP_TRY(call.b.Put(&d_tiles, tiles.data(), tiles.size(), s, 1));
-  PP_TRY(call.b.Put(&d_todo, todo.data(), todo.size(), s, 1)); PP_TRY(call.b.Put(&d_model, desc->camera_model, (size_t)K, s, 1));
-  PP_TRY(call.b.Put(&d_intr, desc->intr, (size_t)K * kCamStride, s, 1)); PP_TRY(call.b.Put(&d_kp, desc->keypoints, 2 * (size_t)L, s, 1));
-  PP_TRY(call.b.Put(&d_hg, has_gravity.data(), has_gravity.size(), s, 1)); PP_TRY(call.b.Put(&d_gravity, gravity.data(), gravity.size(), s, 1));
-  PP_TRY(call.b.Alloc(&d_thr, (size_t)std::max(I, 1))); PP_TRY(call.b.Alloc(&d_lines, 3 * (size_t)std::max<int64_t>(L, 1)));
-  PP_TRY(call.b.Alloc(&d_flags, (size_t)std::max<int64_t>(L, 1)));
-  if (dirs_out) PP_TRY(call.b.Alloc(&d_dirs, 3 * (size_t)std::max<int64_t>(L, 1)));
+  PP_TRY(call.blocks.Put(&d_images, images.data(), images.size(), s, 1)); PP_TRY(call.blocks.Put(&d_tiles, tiles.data(), tiles.size(), s, 1));
+  PP_TRY(call.blocks.Put(&d_todo, todo.data(), todo.size(), s, 1)); PP_TRY(call.blocks.Put(&d_model, desc->camera_model, (size_t)K, s, 1));
+  PP_TRY(call.blocks.Put(&d_intr, desc->intr, (size_t)K * kCamStride, s, 1)); PP_TRY(call.blocks.Put(&d_kp, desc->keypoints, 2 * (size_t)L, s, 1));
+  PP_TRY(call.blocks.Put(&d_hg, has_gravity.data(), has_gravity.size(), s, 1)); PP_TRY(call.blocks.Put(&d_gravity, gravity.data(), gravity.size(), s, 1));
+  PP_TRY(call.blocks.Alloc(&d_thr, (size_t)std::max(I, 1))); PP_TRY(call.blocks.Alloc(&d_lines, 3 * (size_t)std::max<int64_t>(L, 1)));
+  PP_TRY(call.blocks.Alloc(&d_flags, (size_t)std::max<int64_t>(L, 1)));
+  if (dirs_out) PP_TRY(call.blocks.Alloc(&d_dirs, 3 * (size_t)std::max<int64_t>(L, 1)));
   PP_HIP_TRY(hipMemsetAsync(d_thr, 0, (size_t)std::max(I, 1) * sizeof(uint64_t), s));
 
-  PP_HIP_TRY(hipEventRecord(call.ev0, s));
+  StreamTimer timer(call);
+  PP_TRY(timer.Begin());
   if (!todo.empty())
     hipLaunchKernelGGL(k_lf_select, dim3((unsigned)todo.size()), dim3(kLfBlock), 0, s, (const int32_t*)d_todo, (const LfImageDev*)d_images, d_thr);
   if (!tiles.empty())
@@ -215,14 +194,13 @@ int pp_line_features_from_keypoints(const pp_line_features_desc* desc, const pp_
                        (const LfImageDev*)d_images, (const uint64_t*)d_thr, (const float*)d_kp, (const int32_t*)d_model, (const double*)d_intr,
                        (const uint8_t*)d_hg, (const double*)d_gravity, d_lines, d_dirs, d_flags);
   PP_HIP_TRY(hipGetLastError());
-  PP_HIP_TRY(hipEventRecord(call.ev1, s));
+  PP_TRY(timer.End());
   std::vector<uint8_t> flags((size_t)L);
   PP_TRY(Download(lines_out, d_lines, 3 * (size_t)L, s));
   if (dirs_out) PP_TRY(Download(dirs_out, d_dirs, 3 * (size_t)L, s));
   PP_TRY(Download(flags.data(), d_flags, (size_t)L, s));
   PP_HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  PP_HIP_TRY(hipEventElapsedTime(&ms, call.ev0, call.ev1));
+  PP_TRY(timer.Add());
 
   std::memset(report, 0, sizeof(*report));
   for (int64_t l = 0; l < L; ++l) {
@@ -230,7 +208,7 @@ int pp_line_features_from_keypoints(const pp_line_features_desc* desc, const pp_
     aligned_out[l] = f & 1;
     report->num_aligned += f & 1; report->num_degenerate += (f >> 1) & 1; report->num_newton_exhausted += (f >> 2) & 1;
   }
-  report->num_lines = L; report->num_images_without_gravity = without_gravity; report->device_ms = ms;
+  report->num_lines = L; report->num_images_without_gravity = without_gravity; report->device_ms = timer.ms;
   return PP_OK;
 } PP_API_CATCH("pp_line_features_from_keypoints")
 

@@ -130,7 +130,7 @@ int pp_tracks_find_local_bundle(pp_tracks_handle h, const pp_local_bundle_option
     device_ms += ms;
     return PP_OK;
   };
-  CallBlocks cb(s);
+  CallScratch cb(s);
   std::vector<int32_t> start, elems, count((size_t)C, 0);
   TrackDev d;
   PP_TRY(UploadState(h, cb, nullptr, start, elems, &d));

@@ -18,11 +18,10 @@
 //                        lanes; the tried neighbours of a are cleared; the set bits are counted.
 // K20f                   the exclusive scan of the counts.
 // K20g k_transitive<true>    the same walk, the set bits written in ascending order from the image's offset: (a, c) ascending.
-#include <chrono>
 #include <cstring>
 
 #include "pair_selection_replay.hpp"
-#include "resource_pool.hpp"
+#include "device_handle.hpp"
 #include "scan.hpp"
 
 namespace ppsfm {
@@ -207,11 +206,7 @@ __global__ __launch_bounds__(kPairsBlock) void k_transitive(int32_t num_images, 
 
 }  // namespace ppsfm
 
-struct pp_pairs_impl {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ppsfm::DeviceBlocks blocks;      // the last result
+struct pp_pairs_impl : ppsfm::DeviceHandle {      // blocks: the last result
   int64_t num_pairs = 0;
   int32_t* d_pairs = nullptr;      // num_pairs x 2
   float* d_sqdist = nullptr;       // num_pairs; null after a transitive selection
@@ -221,24 +216,6 @@ struct pp_pairs_impl {
 using namespace ppsfm;
 
 namespace {
-
-using PairsClock = std::chrono::steady_clock;
-double PairsMsSince(PairsClock::time_point t0) { return std::chrono::duration<double, std::milli>(PairsClock::now() - t0).count(); }
-
-// pool blocks of one call, returned after the stream has drained on every way out
-struct PairsScratch {
-  hipStream_t s;
-  DeviceBlocks b;
-  explicit PairsScratch(hipStream_t stream) : s(stream) {}
-  ~PairsScratch() { (void)hipStreamSynchronize(s); }
-  template <typename T> int Alloc(T** p, size_t count) { return b.Alloc(p, count > 0 ? count : 1); }
-  template <typename T> int Zeros(T** p, size_t count) {
-    PP_TRY(Alloc(p, count));
-    PP_HIP_TRY(hipMemsetAsync(*p, 0, (count > 0 ? count : 1) * sizeof(T), s));
-    return PP_OK;
-  }
-  template <typename T> int Put(T** p, const T* src, size_t count) { return b.Put(p, src, count, s, 1); }
-};
 
 // a result in the handle's blocks: given back unless the call completes
 struct PairsFresh {
@@ -262,15 +239,12 @@ void PairsAdopt(pp_pairs_impl* h, PairsFresh* fresh, int64_t n, bool has_sqdist)
 }
 
 // stops the clock of one device stage and reads the total behind the scanned counts
-int PairsStageTotal(pp_pairs_impl* h, const int64_t* d_total, int64_t* total, float* device_ms) {
-  float part_ms = 0.f;
+int PairsStageTotal(StreamTimer* timer, const int64_t* d_total, int64_t* total) {
   PP_HIP_TRY(hipGetLastError());
-  PP_HIP_TRY(hipEventRecord(h->ev1, h->stream));
-  if (d_total) PP_TRY(Download(total, d_total, 1, h->stream));
-  PP_HIP_TRY(hipStreamSynchronize(h->stream));
-  PP_HIP_TRY(hipEventElapsedTime(&part_ms, h->ev0, h->ev1));
-  *device_ms += part_ms;
-  return PP_OK;
+  PP_TRY(timer->End());
+  if (d_total) PP_TRY(Download(total, d_total, 1, timer->stream));
+  PP_HIP_TRY(hipStreamSynchronize(timer->stream));
+  return timer->Add();
 }
 
 }  // namespace
@@ -278,14 +252,7 @@ int PairsStageTotal(pp_pairs_impl* h, const int64_t* d_total, int64_t* total, fl
 extern "C" {
 
 int pp_pairs_destroy(pp_pairs_handle h) try {
-  if (!h) return PP_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  h->blocks.Release();
-  if (h->ev0) PoolEventRelease(h->ev0, true);
-  if (h->ev1) PoolEventRelease(h->ev1, true);
-  if (h->stream) PoolStreamRelease(h->stream);
-  delete h;
+  delete h;      // (~DeviceHandle)
   return PP_OK;
 } PP_API_CATCH("pp_pairs_destroy")
 
@@ -293,14 +260,9 @@ int pp_pairs_create(int device, pp_pairs_handle* out) try {
   const char* where = "pp_pairs_create";
   PP_REQUIRE(out, "%s: null argument", where);
   *out = nullptr;
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "%s: device %d of %d", where, device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
+  PP_TRY(UseDevice(where, device));
   UnderConstruction<pp_pairs_impl, pp_pairs_destroy> h{new pp_pairs_impl()};
-  h->device = device;
-  PP_TRY(PoolStreamAcquire(&h->stream));
-  PP_TRY(PoolEventAcquire(&h->ev0, true)); PP_TRY(PoolEventAcquire(&h->ev1, true));
+  PP_TRY(h->Open(device));
   *out = h.release();
   return PP_OK;
 } PP_API_CATCH("pp_pairs_create")
@@ -308,7 +270,7 @@ int pp_pairs_create(int device, pp_pairs_handle* out) try {
 int pp_pairs_spatial(pp_pairs_handle h, int64_t num_locations, const float* xyz, int32_t max_num_neighbors, double max_distance, pp_pairs_report* report) try {
   const char* where = "pp_pairs_spatial";
   PP_REQUIRE(h && report, "%s: null argument", where);
-  const auto t_begin = PairsClock::now();
+  const auto t_begin = Clock::now();
   const std::string wrong = PairsCheckSpatial(num_locations, xyz, max_num_neighbors, max_distance);
   PP_REQUIRE(wrong.empty(), "%s: %s", where, wrong.c_str());
   const int32_t m = (int32_t)num_locations, knn = (int32_t)std::min<int64_t>(max_num_neighbors, num_locations);
@@ -317,32 +279,32 @@ int pp_pairs_spatial(pp_pairs_handle h, int64_t num_locations, const float* xyz,
   PP_HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   PairsFresh fresh{&h->blocks};
-  PairsScratch cb(s);
+  CallScratch cb(s);
   float* d_xyz = nullptr;
   int64_t *d_count = nullptr, *d_offset = nullptr, *d_scan = nullptr;
   int64_t total = 0;
-  float device_ms = 0.f;
+  StreamTimer timer(*h);
   if (m > 0) {
     PP_TRY(cb.Put(&d_xyz, xyz, 3 * (size_t)m));
     PP_TRY(cb.Alloc(&d_count, (size_t)m)); PP_TRY(cb.Alloc(&d_offset, (size_t)m + 1)); PP_TRY(cb.Alloc(&d_scan, ScanScratchCount(m)));
-    PP_HIP_TRY(hipEventRecord(h->ev0, s));
+    PP_TRY(timer.Begin());
     hipLaunchKernelGGL(k_spatial_count, dim3((unsigned)m), dim3(kPairsBlock), 0, s, m, knn, cut, (const float*)d_xyz, d_count);
     const ScanJob<int64_t> counts{d_count, d_offset, d_offset + m};
     LaunchExclusiveScan(s, (int64_t)m, &counts, 1, d_scan);
-    PP_TRY(PairsStageTotal(h, d_offset + m, &total, &device_ms));
+    PP_TRY(PairsStageTotal(&timer, d_offset + m, &total));
     PP_REQUIRE(total >= 0 && total < kPairsMaxResult, "%s: %lld pairs, the result is limited to 2^31 - 1", where, (long long)total);
     PP_TRY(h->blocks.Alloc(&fresh.pairs, 2 * (size_t)total)); PP_TRY(h->blocks.Alloc(&fresh.sqdist, (size_t)total));
     if (total > 0) {
-      PP_HIP_TRY(hipEventRecord(h->ev0, s));
+      PP_TRY(timer.Begin());
       hipLaunchKernelGGL(k_spatial_fill, dim3((unsigned)m), dim3(kPairsBlock), 0, s, m, knn, cut, (const float*)d_xyz, (const int64_t*)d_offset, fresh.pairs,
                          fresh.sqdist);
-      PP_TRY(PairsStageTotal(h, nullptr, nullptr, &device_ms));
+      PP_TRY(PairsStageTotal(&timer, nullptr, nullptr));
     }
   }
   PairsAdopt(h, &fresh, total, true);
   std::memset(report, 0, sizeof(*report));
   report->num_pairs = total; report->num_candidates = (int64_t)m * m;
-  report->device_ms = device_ms; report->total_ms = PairsMsSince(t_begin);
+  report->device_ms = timer.ms; report->total_ms = MsSince(t_begin);
   return PP_OK;
 } PP_API_CATCH("pp_pairs_spatial")
 
@@ -350,7 +312,7 @@ int pp_pairs_transitive(pp_pairs_handle h, int32_t num_images, int64_t num_match
                         pp_pairs_report* report) try {
   const char* where = "pp_pairs_transitive";
   PP_REQUIRE(h && report, "%s: null argument", where);
-  const auto t_begin = PairsClock::now();
+  const auto t_begin = Clock::now();
   const std::string wrong = PairsCheckTransitive(num_images, num_matched, matched_pairs, num_tried, tried_pairs);
   PP_REQUIRE(wrong.empty(), "%s: %s", where, wrong.c_str());
   const int64_t N = num_images, M = num_matched, T = num_matched + num_tried;
@@ -358,9 +320,9 @@ int pp_pairs_transitive(pp_pairs_handle h, int32_t num_images, int64_t num_match
   PP_HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   PairsFresh fresh{&h->blocks};
-  PairsScratch cb(s);
+  CallScratch cb(s);
   int64_t total = 0;
-  float device_ms = 0.f;
+  StreamTimer timer(*h);
   if (N > 0 && M > 0) {
     // the matched pairs first, the tried ones behind them: the first M make the adjacency, all T the pairs that are done
     std::vector<int32_t> listed(2 * (size_t)T);
@@ -374,7 +336,7 @@ int pp_pairs_transitive(pp_pairs_handle h, int32_t num_images, int64_t num_match
     PP_TRY(cb.Alloc(&d_madj, 2 * (size_t)M)); PP_TRY(cb.Alloc(&d_tadj, 2 * (size_t)T));
     PP_TRY(cb.Alloc(&d_count, (size_t)N)); PP_TRY(cb.Alloc(&d_offset, (size_t)N + 1)); PP_TRY(cb.Alloc(&d_scan, ScanScratchCount(N)));
     int32_t *d_mstart = d_start, *d_tstart = d_start + N + 1;
-    PP_HIP_TRY(hipEventRecord(h->ev0, s));
+    PP_TRY(timer.Begin());
     hipLaunchKernelGGL(k_pairs_degree, dim3(CeilDiv(M, kPairsBlock)), dim3(kPairsBlock), 0, s, M, (const int32_t*)d_listed, d_degree);
     hipLaunchKernelGGL(k_pairs_degree, dim3(CeilDiv(T, kPairsBlock)), dim3(kPairsBlock), 0, s, T, (const int32_t*)d_listed, d_degree + N);
     const ScanJob<int32_t> degrees[2] = {{d_degree, d_mstart, d_mstart + N}, {d_degree + N, d_tstart, d_tstart + N}};
@@ -386,20 +348,20 @@ int pp_pairs_transitive(pp_pairs_handle h, int32_t num_images, int64_t num_match
                        (const int32_t*)d_tstart, (const int32_t*)d_tadj, d_count, (const int64_t*)nullptr, (int32_t*)nullptr);
     const ScanJob<int64_t> counts{d_count, d_offset, d_offset + N};
     LaunchExclusiveScan(s, N, &counts, 1, d_scan);
-    PP_TRY(PairsStageTotal(h, d_offset + N, &total, &device_ms));
+    PP_TRY(PairsStageTotal(&timer, d_offset + N, &total));
     PP_REQUIRE(total >= 0 && total < kPairsMaxResult, "%s: %lld pairs, the result is limited to 2^31 - 1", where, (long long)total);
     PP_TRY(h->blocks.Alloc(&fresh.pairs, 2 * (size_t)total));
     if (total > 0) {
-      PP_HIP_TRY(hipEventRecord(h->ev0, s));
+      PP_TRY(timer.Begin());
       hipLaunchKernelGGL(k_transitive<true>, dim3((unsigned)N), dim3(kPairsBlock), 0, s, num_images, (const int32_t*)d_mstart, (const int32_t*)d_madj,
                          (const int32_t*)d_tstart, (const int32_t*)d_tadj, (int64_t*)nullptr, (const int64_t*)d_offset, fresh.pairs);
-      PP_TRY(PairsStageTotal(h, nullptr, nullptr, &device_ms));
+      PP_TRY(PairsStageTotal(&timer, nullptr, nullptr));
     }
   }
   PairsAdopt(h, &fresh, total, false);
   std::memset(report, 0, sizeof(*report));
   report->num_pairs = total; report->num_candidates = TransitiveVisited(num_images, num_matched, matched_pairs);
-  report->device_ms = device_ms; report->total_ms = PairsMsSince(t_begin);
+  report->device_ms = timer.ms; report->total_ms = MsSince(t_begin);
   return PP_OK;
 } PP_API_CATCH("pp_pairs_transitive")
 

@@ -171,12 +171,12 @@ int pp_tracks_find_next_images(pp_tracks_handle h, const pp_next_image_options* 
   if (h->L > 0) {
     PP_HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    CallBlocks cb(s);
+    CallScratch cb(s);
     int32_t* d_counts = nullptr;
     PP_TRY(cb.Alloc(&d_counts, 2 * (size_t)C));
     PP_TRY(Upload(h->d_line_point, st.line_point.data(), (size_t)h->L, s));
     PP_HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * (size_t)C * sizeof(int32_t), s));
-    EventTimer t{h};
+    StreamTimer t(*h);
     PP_TRY(t.Begin());
     hipLaunchKernelGGL(k_visible_points, dim3(CeilDiv(h->L, 256)), dim3(256), 0, s, h->L, C, h->dev.line_image, h->dev.corr_start, h->dev.corr_line,
                        (const int32_t*)h->d_line_point, d_counts, d_counts + C);
@@ -236,9 +236,9 @@ int pp_tracks_estimate_image_pose(pp_tracks_handle h, const pp_next_image_option
   PP_REQUIRE(max_corrs < 0x7FFFFFFF, "%s: too many correspondences", where);
   PP_HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  EventTimer timer{h};
+  StreamTimer timer(*h);
   PoseHandleGuard pose;      // (destroyed after the call's blocks have drained the stream: declared first)
-  CallBlocks cb(s);
+  CallScratch cb(s);
   TrackDev d = h->dev;
   d.P = st.NumPoints();
   PP_TRY(Upload(h->d_line_point, st.line_point.data(), (size_t)h->L, s));

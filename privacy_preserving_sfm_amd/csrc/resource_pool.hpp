@@ -1,4 +1,4 @@
-// Recycled HIP resources of the bundle-adjustment handles: device blocks, pinned host blocks, streams and events.
+// Recycled HIP resources of the handles and of the calls without one: device blocks, pinned host blocks, streams and events.
 //
 // The mapper builds a NEW BundleAdjuster for every image it registers (src/sfm/incremental_mapper.cc:813-858, 6 images; the global one at
 // controllers/incremental_mapper.cc:497-504 as the model grows): pp_ba_create / pp_ba_destroy sit in its inner loop.  Measured on MI355X for a
@@ -42,6 +42,7 @@ class DeviceBlocks {
   // one block back early (a buffer that is regrown); *p = nullptr.  A pointer this owner does not hold is a programming error.
   template <class T> void Free(T** p) { FreeBlock(*p); *p = nullptr; }
   void Release();      // everything, in allocation order
+  bool pooled() const { return pooled_; }
 
  private:
   int AllocBytes(void** p, size_t bytes, bool pinned);

@@ -19,10 +19,9 @@
 //                      the counts of the batch (BlockExclusiveScan, scan.hpp) - the same ordered compaction again (a workgroup scan over i in chunks of 256) writing (i, j) behind the
 //                      pair's offset.
 // No atomics, no kernel waits for another workgroup: the output does not depend on the schedule.
-#include <chrono>
 #include <cstring>
 
-#include "resource_pool.hpp"
+#include "device_handle.hpp"
 #include "scan.hpp"
 #include "sift_match_replay.hpp"
 
@@ -219,13 +218,9 @@ __global__ __launch_bounds__(256) void k_sift_offsets(int32_t n, int32_t* __rest
 
 }  // namespace ppsfm
 
-struct pp_sift_impl {
-  int device = 0;
+struct pp_sift_impl : ppsfm::DeviceHandle {      // blocks: the descriptors, their offsets and the threshold table
   int32_t num_images = 0;
   std::vector<int64_t> desc_start;      // num_images + 1
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ppsfm::DeviceBlocks blocks;           // the descriptors, their offsets and the threshold table
   int8_t* d_desc = nullptr;             // total x 128, d - 128
   int32_t* d_off = nullptr;             // total
   // the thresholds of the last options used, on the host and on the device
@@ -239,9 +234,6 @@ struct pp_sift_impl {
 using namespace ppsfm;
 
 namespace {
-
-using SiftClock = std::chrono::steady_clock;
-double SiftMsSince(SiftClock::time_point t0) { return std::chrono::duration<double, std::milli>(SiftClock::now() - t0).count(); }
 
 int CheckSiftOptions(const pp_sift_match_options* o, const char* where) {
   PP_REQUIRE(o, "%s: null options", where);
@@ -278,29 +270,6 @@ void AppendWork(const pp_sift_impl* h, int32_t query, int32_t scanned, int32_t o
     work->push_back(SiftWork{(int32_t)h->desc_start[(size_t)query], nq, (int32_t)h->desc_start[(size_t)scanned], ns, i0, out0});
 }
 
-struct SiftEvents {
-  pp_sift_impl* h;
-  float ms = 0.f;
-  int Begin() { PP_HIP_TRY(hipEventRecord(h->ev0, h->stream)); return PP_OK; }
-  int End() { PP_HIP_TRY(hipEventRecord(h->ev1, h->stream)); return PP_OK; }
-  int Add() {      // after the stream has drained
-    float t = 0.f;
-    PP_HIP_TRY(hipEventElapsedTime(&t, h->ev0, h->ev1));
-    ms += t;
-    return PP_OK;
-  }
-};
-
-// pool blocks of one batch, returned after the stream has drained on every way out
-struct SiftBatchBlocks {
-  hipStream_t s;
-  DeviceBlocks b;
-  explicit SiftBatchBlocks(hipStream_t stream) : s(stream) {}
-  ~SiftBatchBlocks() { (void)hipStreamSynchronize(s); }
-  template <typename T> int Alloc(T** p, size_t count) { return b.Alloc(p, count > 0 ? count : 1); }
-  template <typename T> int Put(T** p, const T* src, size_t count) { return b.Put(p, src, count, s, 1); }
-};
-
 // what a pair can emit at most
 int64_t SiftMatchBound(int32_t n1, int32_t n2, bool cross_check) { return cross_check ? std::min(n1, n2) : (n2 > 0 ? n1 : 0); }
 
@@ -328,14 +297,7 @@ int pp_sift_match_thresholds(const pp_sift_match_options* options, int32_t* d_mi
 } PP_API_CATCH("pp_sift_match_thresholds")
 
 int pp_sift_destroy(pp_sift_handle h) try {
-  if (!h) return PP_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  h->blocks.Release();
-  if (h->ev0) PoolEventRelease(h->ev0, true);
-  if (h->ev1) PoolEventRelease(h->ev1, true);
-  if (h->stream) PoolStreamRelease(h->stream);
-  delete h;
+  delete h;      // (~DeviceHandle)
   return PP_OK;
 } PP_API_CATCH("pp_sift_destroy")
 
@@ -349,15 +311,11 @@ int pp_sift_create(int32_t num_images, const int64_t* desc_start, const uint8_t*
   const int64_t total = desc_start[num_images];
   PP_REQUIRE(total < 0x7FFFFFFFll - kSiftRowTile, "%s: too many descriptors", where);
   PP_REQUIRE(total == 0 || descriptors, "%s: null descriptors", where);
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "%s: device %d of %d", where, device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
+  PP_TRY(UseDevice(where, device));
   UnderConstruction<pp_sift_impl, pp_sift_destroy> h{new pp_sift_impl()};
-  h->device = device; h->num_images = num_images;
+  h->num_images = num_images;
   h->desc_start.assign(desc_start, desc_start + num_images + 1);
-  PP_TRY(PoolStreamAcquire(&h->stream));
-  PP_TRY(PoolEventAcquire(&h->ev0, true)); PP_TRY(PoolEventAcquire(&h->ev1, true));
+  PP_TRY(h->Open(device));
   hipStream_t s = h->stream;
   uint8_t* d_raw = nullptr;
   PP_TRY(h->blocks.Put(&d_raw, descriptors, (size_t)total * kSiftDim, s, 16));
@@ -377,7 +335,7 @@ int pp_sift_top2(pp_sift_handle h, int32_t image1, int32_t image2, int32_t* best
   if (n1 == 0) return PP_OK;
   PP_HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  SiftBatchBlocks cb(s);
+  CallScratch cb(s);
   std::vector<SiftWork> work;
   AppendWork(h, image1, image2, 0, &work);
   SiftWork* d_work = nullptr;
@@ -401,7 +359,7 @@ int pp_sift_match_pairs(pp_sift_handle h, const pp_sift_match_options* options, 
   for (int64_t p = 0; p < num_pairs; ++p)
     PP_REQUIRE(pairs[2 * p] >= 0 && pairs[2 * p] < h->num_images && pairs[2 * p + 1] >= 0 && pairs[2 * p + 1] < h->num_images, "%s: pair %lld names image (%d, %d) of %d",
                where, (long long)p, pairs[2 * p], pairs[2 * p + 1], h->num_images);
-  const auto t_begin = SiftClock::now();
+  const auto t_begin = Clock::now();
   PP_HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   PP_TRY(EnsureThresholds(h, options, where));
@@ -409,7 +367,7 @@ int pp_sift_match_pairs(pp_sift_handle h, const pp_sift_match_options* options, 
   const int64_t cap_bytes = options->workspace_bytes > 0 ? options->workspace_bytes : kSiftDefaultWorkspace;
   std::vector<int64_t> starts((size_t)num_pairs + 1, 0);
   std::vector<int32_t> all;      // the matches of the batches so far, flat
-  SiftEvents timer{h};
+  StreamTimer timer(*h);
   int32_t batches = 0, emptied_total = 0;
   std::vector<SiftWork> work;
   std::vector<SiftPair> batch;
@@ -432,7 +390,7 @@ int pp_sift_match_pairs(pp_sift_handle h, const pp_sift_match_options* options, 
     }
     const int32_t np = (int32_t)(p1 - p0);
     ++batches;
-    SiftBatchBlocks cb(s);
+    CallScratch cb(s);
     SiftWork* d_work = nullptr;
     SiftPair* d_pairs = nullptr;
     int32_t *d_j = nullptr, *d_best = nullptr, *d_second = nullptr, *d_count = nullptr, *d_start = nullptr, *d_emptied = nullptr, *d_out = nullptr;
@@ -475,7 +433,7 @@ int pp_sift_match_pairs(pp_sift_handle h, const pp_sift_match_options* options, 
   std::copy(all.begin(), all.end(), matches);
   std::memset(report, 0, sizeof(*report));
   report->num_matches = need; report->num_pairs_emptied = emptied_total; report->num_batches = batches;
-  report->device_ms = timer.ms; report->total_ms = SiftMsSince(t_begin);
+  report->device_ms = timer.ms; report->total_ms = MsSince(t_begin);
   return PP_OK;
 } PP_API_CATCH("pp_sift_match_pairs")
 

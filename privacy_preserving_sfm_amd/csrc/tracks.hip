@@ -158,13 +158,7 @@ void pp_tracks_options_default(pp_tracks_options* o) {
 }
 
 int pp_tracks_destroy(pp_tracks_handle h) try {
-  if (!h) return PP_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  h->blocks.Release();
-  PoolEventRelease(h->ev0, true); PoolEventRelease(h->ev1, true);
-  PoolStreamRelease(h->stream);
-  delete h;
+  delete h;      // (~DeviceHandle)
   return PP_OK;
 } PP_API_CATCH("pp_tracks_destroy")
 
@@ -202,12 +196,9 @@ int pp_tracks_create(const pp_tracks_desc* d, int device, pp_tracks_handle* out)
       }
     for (int64_t l = 0; l < L; ++l) PP_REQUIRE((d->line_point[l] >= 0) == (seen[(size_t)l] != 0), "pp_tracks_create: line %lld has a point but is in no track", (long long)l);
   }
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "pp_tracks_create: device %d of %d", device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
+  PP_TRY(UseDevice("pp_tracks_create", device));
   UnderConstruction<pp_tracks_impl, pp_tracks_destroy> h{new pp_tracks_impl()};
-  h->device = device; h->C = C; h->K = K; h->L = L; h->E = E;
+  h->C = C; h->K = K; h->L = L; h->E = E;
   TrackState& st = h->st;
   st.L = L;
   st.line_image.assign(d->line_image, d->line_image + L);
@@ -228,8 +219,7 @@ int pp_tracks_create(const pp_tracks_desc* d, int device, pp_tracks_handle* out)
   h->poses.assign(d->poses, d->poses + (size_t)7 * C);
   h->intr.assign(d->intr, d->intr + (size_t)kCamStride * K);
   h->camera_skip = skip;
-  PP_TRY(PoolStreamAcquire(&h->stream));
-  PP_TRY(PoolEventAcquire(&h->ev0, true)); PP_TRY(PoolEventAcquire(&h->ev1, true));
+  PP_TRY(h->Open(device));
   hipStream_t s = h->stream;
   auto put = [&](auto** p, const auto* src, size_t count) { return h->blocks.Put(p, src, count, s, 1); };
   double *d_poses = nullptr, *d_proj = nullptr, *d_intr = nullptr, *d_lines = nullptr;
@@ -294,7 +284,7 @@ int pp_tracks_merge(pp_tracks_handle h, const pp_tracks_options* o, const uint8_
   std::vector<uint8_t> over((size_t)P0), pool_ok;
   unsigned long long counters[2] = {0, 0};
   TrackDev d;
-  CallBlocks cb(s);      // (the state arrays stay up for the fresh-pair launches)
+  CallScratch cb(s);      // (the state arrays stay up for the fresh-pair launches)
   PP_TRY(UploadState(h, cb, point_subset, start, elems, &d));
   {
     MergeArgs a{};

@@ -2,14 +2,13 @@
 // the device view of a pp_tracks_handle, K10a k_complete_tracks, the handle itself and the speculative completion of a set of points.
 #pragma once
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <type_traits>
 #include <vector>
 
 #include "line_error.hpp"
-#include "resource_pool.hpp"
+#include "device_handle.hpp"
 #include "tracks_replay.hpp"
 
 namespace ppsfm {
@@ -142,11 +141,9 @@ __global__ __launch_bounds__(64) void k_complete_tracks(TrackDev d, CompleteArgs
 
 }  // namespace ppsfm
 
-struct pp_tracks_impl {
-  int device = 0, C = 0, K = 0;
+struct pp_tracks_impl : ppsfm::DeviceHandle {      // blocks: the static device arrays and the pinned slots (pool blocks)
+  int C = 0, K = 0;
   int64_t L = 0, E = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   ppsfm::TrackState st;
   std::vector<uint8_t> image_skip;      // per image: its camera is flagged in camera_skip
   std::vector<int32_t> pose_camera;     // C
@@ -154,7 +151,6 @@ struct pp_tracks_impl {
   std::vector<uint8_t> camera_skip;     // K
   double *d_poses = nullptr, *d_proj = nullptr, *d_intr = nullptr;      // the writable views of dev.proj / dev.intr / dev.camera_skip
   uint8_t *d_skip = nullptr, *d_registered = nullptr;      // (d_registered: dev.image_registered, rewritten by pp_tracks_register_image)
-  ppsfm::DeviceBlocks blocks;     // the static device arrays and the pinned slots (pool blocks)
   ppsfm::TrackDev dev{};
   int32_t* d_line_point = nullptr;
   double* d_centers = nullptr;    // C x 3 projection centres (K11b's triangulation-angle test, K12b)
@@ -164,33 +160,6 @@ struct pp_tracks_impl {
 
 namespace ppsfm {
 
-using Clock = std::chrono::steady_clock;
-inline double MsSince(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-
-// pool blocks of one call (at least one element each), returned after the stream has drained on every way out (`b` is destroyed after the body)
-struct CallBlocks {
-  hipStream_t s;
-  DeviceBlocks b;
-  explicit CallBlocks(hipStream_t stream) : s(stream) {}
-  ~CallBlocks() { (void)hipStreamSynchronize(s); }
-  template <typename T> int Alloc(T** p, size_t count) { return b.Alloc(p, std::max<size_t>(count, 1)); }
-  template <typename T> int Put(T** p, const T* src, size_t count) { return b.Put(p, src, count, s, 1); }
-};
-
-// HIP-event time of the spans between Begin() and End() on the handle's stream (K13, K15), summed
-struct EventTimer {
-  pp_tracks_impl* h;
-  float ms = 0.f;
-  int Begin() { PP_HIP_TRY(hipEventRecord(h->ev0, h->stream)); return PP_OK; }
-  int End() { PP_HIP_TRY(hipEventRecord(h->ev1, h->stream)); return PP_OK; }
-  int Add() {      // after the stream has drained
-    float t = 0.f;
-    PP_HIP_TRY(hipEventElapsedTime(&t, h->ev0, h->ev1));
-    ms += t;
-    return PP_OK;
-  }
-};
-
 // the C x 3 projection centres of the handle's projection matrices (tracks_image.hip): computed on first use, again after pp_tracks_update
 int ComputeCenters(pp_tracks_impl* h);
 inline int EnsureCenters(pp_tracks_impl* h) { return h->d_centers ? PP_OK : ComputeCenters(h); }
@@ -199,7 +168,7 @@ inline int EnsureCenters(pp_tracks_impl* h) { return h->d_centers ? PP_OK : Comp
 int UploadPoses(pp_tracks_impl* h);
 
 // uploads the state at the start of a call; flat track CSR in start / elems (kept alive by the caller until the stream drains)
-inline int UploadState(pp_tracks_impl* h, CallBlocks& cb, const uint8_t* subset, std::vector<int32_t>& start, std::vector<int32_t>& elems, TrackDev* d) {
+inline int UploadState(pp_tracks_impl* h, CallScratch& cb, const uint8_t* subset, std::vector<int32_t>& start, std::vector<int32_t>& elems, TrackDev* d) {
   const TrackState& st = h->st;
   const int P = st.NumPoints();
   start.assign((size_t)P + 1, 0);
@@ -250,7 +219,7 @@ inline int SpeculateComplete(pp_tracks_impl* h, const uint8_t* point_subset, int
   count.assign((size_t)P, 0); seg.assign((size_t)P, 0); over.assign((size_t)P, 0); second_of.assign((size_t)P, -1);
   float ms_total = 0.f;
   {
-    CallBlocks cb(s);
+    CallScratch cb(s);
     TrackDev d;
     PP_TRY(UploadState(h, cb, point_subset, start, elems, &d));
     CompleteArgs a{};

@@ -154,7 +154,7 @@ int pp_tracks_filter_points(pp_tracks_handle h, const pp_filter_options* o, cons
   std::vector<double> error((size_t)P);
   {
     PP_TRY(EnsureCenters(h));
-    CallBlocks cb(s);
+    CallScratch cb(s);
     TrackDev d;
     PP_TRY(UploadState(h, cb, point_subset, start, elems, &d));
     const size_t T = elems.size();
@@ -206,7 +206,7 @@ int pp_tracks_filter_negative_depth(pp_tracks_handle h, const int32_t* image_ord
   hipStream_t s = h->stream;
   std::vector<uint8_t> flag((size_t)h->L);
   {
-    CallBlocks cb(s);
+    CallScratch cb(s);
     double* d_points = nullptr;
     uint8_t* d_flag = nullptr;
     PP_TRY(Upload(h->d_line_point, st.line_point.data(), (size_t)h->L, s));

@@ -272,7 +272,7 @@ struct ImageCall {
   const uint8_t* aligned;
   bool create;                 // TriangulateImage (Create) / CompleteImage
   hipStream_t s;
-  CallBlocks cb;               // blocks that live for the whole call
+  CallScratch cb;               // blocks that live for the whole call
   TrackDev d{};
   double* d_points = nullptr;
   uint8_t* d_aligned = nullptr;
@@ -320,7 +320,7 @@ struct ImageCall {
     const size_t W = work.size();
     out.assign(W, ImageLineResult());
     if (W == 0) return PP_OK;
-    CallBlocks lb(s);
+    CallScratch lb(s);
     int64_t direct = 0, maxc = 0;
     for (const int32_t l : work) { const int64_t c = st.corr_start[(size_t)l + 1] - st.corr_start[(size_t)l]; direct += c + 1; maxc = std::max(maxc, c); }
     FindArgs a{};
@@ -402,7 +402,7 @@ struct ImageCall {
   int Triangulate(const std::vector<ImageLineResult*>& items, float* ms_acc) {
     const size_t S = items.size();
     if (S == 0) return PP_OK;
-    CallBlocks lb(s);
+    CallScratch lb(s);
     std::vector<int32_t> start(S + 1, 0), flat;
     std::vector<unsigned long long> mt(S);
     for (size_t i = 0; i < S; ++i) {

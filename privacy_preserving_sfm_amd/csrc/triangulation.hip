@@ -11,7 +11,7 @@
 #include <algorithm>
 
 #include "ransac_host.hpp"
-#include "resource_pool.hpp"
+#include "device_handle.hpp"
 #include "tri_device.hpp"
 
 namespace ppsfm {
@@ -68,24 +68,15 @@ extern "C" int pp_triangulate_tracks(int device, int32_t num_tracks, const int32
   for (int64_t i = 0; i < N; ++i) PP_REQUIRE(obs_view[i] >= 0 && obs_view[i] < num_views, "pp_triangulate_tracks: view index out of range");
   for (int v = 0; v < num_views; ++v) PP_REQUIRE(view_camera[v] >= 0 && view_camera[v] < num_cameras, "pp_triangulate_tracks: camera index out of range");
   for (int k = 0; k < num_cameras; ++k) PP_REQUIRE(pp_camera_num_params(camera_model[k]) > 0, "pp_triangulate_tracks: unknown camera model");
-  int ndev = 0;
-  PP_HIP_TRY(hipGetDeviceCount(&ndev));
-  PP_REQUIRE(device >= 0 && device < ndev, "pp_triangulate_tracks: device %d of %d", device, ndev);
-  PP_HIP_TRY(hipSetDevice(device));
+  PP_TRY(UseDevice("pp_triangulate_tracks", device));
   TriArgs a{};
   int32_t *d_ts = nullptr, *d_ov = nullptr, *d_vc = nullptr, *d_cm = nullptr, *d_cs = nullptr, *d_nt = nullptr;
   double *d_l = nullptr, *d_P = nullptr, *d_c = nullptr, *d_in = nullptr, *d_xyz = nullptr;
   uint8_t *d_s = nullptr, *d_m = nullptr;
-  // the call's stream and events, then its blocks (plain hipMalloc): the blocks go first on every way out, and freeing them waits for the device
-  struct Timeline {
-    hipStream_t s = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~Timeline() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); if (s) (void)hipStreamDestroy(s); }
-  } tl;
-  DeviceBlocks scratch(false);
-  PP_HIP_TRY(hipStreamCreateWithFlags(&tl.s, hipStreamNonBlocking)); PP_HIP_TRY(hipEventCreate(&tl.ev0)); PP_HIP_TRY(hipEventCreate(&tl.ev1));
-  const hipStream_t s = tl.s;
-  const hipEvent_t ev0 = tl.ev0, ev1 = tl.ev1;
+  DeviceHandle call(false);      // the call's stream, events and blocks (plain hipMalloc)
+  PP_TRY(call.Open(device));
+  const hipStream_t s = call.stream;
+  DeviceBlocks& scratch = call.blocks;
   PP_TRY(scratch.Put(&d_ts, track_start, (size_t)num_tracks + 1, s)); PP_TRY(scratch.Put(&d_ov, obs_view, (size_t)N, s)); PP_TRY(scratch.Put(&d_vc, view_camera, (size_t)num_views, s));
   PP_TRY(scratch.Put(&d_cm, camera_model, (size_t)num_cameras, s)); PP_TRY(scratch.Put(&d_cs, cam_size, (size_t)2 * num_cameras, s)); PP_TRY(scratch.Alloc(&d_nt, (size_t)num_tracks));
   PP_TRY(scratch.Put(&d_l, lines, (size_t)3 * N, s)); PP_TRY(scratch.Put(&d_P, proj_matrices, (size_t)12 * num_views, s)); PP_TRY(scratch.Put(&d_c, proj_centers, (size_t)3 * num_views, s));
@@ -100,13 +91,15 @@ extern "C" int pp_triangulate_tracks(int device, int32_t num_tracks, const int32
     a.m.max_num_trials = std::min<uint64_t>(o->ransac.max_num_trials, cap);
   }
   a.success = d_s; a.mask = d_m; a.xyz = d_xyz; a.num_trials = d_nt;
-  PP_HIP_TRY(hipEventRecord(ev0, s));
+  StreamTimer timer(call);
+  PP_TRY(timer.Begin());
   hipLaunchKernelGGL(k_triangulate_tracks, dim3(CeilDiv(num_tracks, 64)), dim3(64), 0, s, a);
   PP_HIP_TRY(hipGetLastError());
-  PP_HIP_TRY(hipEventRecord(ev1, s));
+  PP_TRY(timer.End());
   PP_TRY(Download(success, d_s, (size_t)num_tracks, s)); PP_TRY(Download(xyz, d_xyz, (size_t)3 * num_tracks, s)); PP_TRY(Download(inlier_mask, d_m, (size_t)N, s));
   PP_TRY(Download(num_trials, d_nt, (size_t)num_tracks, s));
   PP_HIP_TRY(hipStreamSynchronize(s));
-  if (device_ms) { float ms = 0; PP_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1)); *device_ms = ms; }
+  PP_TRY(timer.Add());
+  if (device_ms) *device_ms = timer.ms;
   return PP_OK;
 } PP_API_CATCH("pp_triangulate_tracks")

@@ -8,23 +8,11 @@ from ._capi import (BAOptions, BAProblemDesc, BASummary, RansacOptions, RansacRe
 
 
 def ba_options(**kw):
-    o = BAOptions()
-    _capi.lib().pp_ba_options_default(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _capi.options(_capi.BAOptions, "pp_ba_options_default", **kw)
 
 
 def ransac_options(**kw):
-    o = RansacOptions()
-    _capi.lib().pp_ransac_options_default(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _capi.options(_capi.RansacOptions, "pp_ransac_options_default", **kw)
 
 
 def _ba_desc(scene, keep, linear_solver=0, ordering=_capi.ORDERING_AUTO):
@@ -98,7 +86,26 @@ def _cov_block_request(blocks):
     return req, shapes, offsets
 
 
-class BAProblem:
+class _Handle:
+    """A C handle and its end: close() gives it to the subclass's pp_*_destroy once, __del__ closes what was left open."""
+    _destroy = None
+
+    def __init__(self):
+        self._h = C.c_void_p()
+
+    def close(self):
+        if self._h:
+            getattr(_capi.lib(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BAProblem(_Handle):
     """Device-resident bundle adjustment problem (one per sub-model / GPU).
 
     `scene` is a dict of flat arrays (see privacy_preserving_sfm_amd.synthetic.make_ba_scene):
@@ -106,10 +113,11 @@ class BAProblem:
     points [P,3], intr [K,12], pose_const [C], tvec_const_mask [C], point_const [P],
     camera_const_mask [K], loss_type, loss_scale.
     """
+    _destroy = "pp_ba_destroy"
 
     def __init__(self, scene, device=0, linear_solver=0, ordering=_capi.ORDERING_AUTO):
         L = _capi.lib()
-        self._h = C.c_void_p()
+        super().__init__()
         self._keep = []
         # linear_solver: 0 = by image count like BundleAdjuster::Solve (> 1000 images: ITERATIVE_SCHUR + SCHUR_JACOBI), 1 = direct, 2 = iterative
         # ordering: PP_ORDERING_AUTO (2, this mirror's default - Ceres orders without being asked) = the library may renumber the images internally (reverse Cuthill-McKee, nested dissection: when it makes the factor sparser / its
@@ -138,17 +146,6 @@ class BAProblem:
         ms = np.zeros(6)
         check(_capi.lib().pp_ba_get_create_profile(self._h, dp(ms)))
         return dict(ordering=float(ms[0]), pair_lists=float(ms[1]), structure=float(ms[2]), upload=float(ms[3]), task_plan=float(ms[4]), total=float(ms[5]))
-
-    def close(self):
-        if self._h:
-            _capi.lib().pp_ba_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_parameters(self, poses=None, points=None, intr=None):
         poses = None if poses is None else f64(poses)
@@ -297,9 +294,10 @@ class BAProblem:
         check(_capi.lib().pp_ba_set_allreduce(self._h, C.cast(self._ar, C.c_void_p), None, int(group_rank), int(group_size)))
 
 
-class Communicator:
+class Communicator(_Handle):
     """RCCL communicator of one point-sharded BA group (pp_comm_*): `unique_id()` on the group's rank 0, the 128 bytes sent to
     the other ranks by any means, then `Communicator(id, num_ranks, rank, device)` on every rank of the group."""
+    _destroy = "pp_comm_destroy"
 
     @staticmethod
     def unique_id():
@@ -308,7 +306,7 @@ class Communicator:
         return buf
 
     def __init__(self, unique_id, num_ranks, rank, device=0):
-        self._h = C.c_void_p()
+        super().__init__()
         uid = np.ascontiguousarray(unique_id, dtype=np.uint8)
         assert uid.size == 128
         self.rank, self.size = int(rank), int(num_ranks)
@@ -317,32 +315,17 @@ class Communicator:
     def allreduce(self, device_ptr, count, op=0):
         check(_capi.lib().pp_comm_allreduce(self._h, C.c_void_p(int(device_ptr)), int(count), int(op)))
 
-    def close(self):
-        if self._h:
-            _capi.lib().pp_comm_destroy(self._h)
-            self._h = C.c_void_p()
 
-
-class PoseProblem:
+class PoseProblem(_Handle):
     """Device-resident 2D-line / 3D-point correspondences of one image (X, Y of the Estimator concept)."""
+    _destroy = "pp_pose_destroy"
 
     def __init__(self, lines2D, points3D, aligned=None, device=0):
-        self._h = C.c_void_p()
+        super().__init__()
         lines2D, points3D = f64(lines2D), f64(points3D)
         self.n = int(lines2D.shape[0])
         al = None if aligned is None else np.ascontiguousarray(aligned, dtype=np.uint8)
         check(_capi.lib().pp_pose_create(self.n, dp(lines2D), dp(points3D), ptr(al, _capi.c_u8p), int(device), C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            _capi.lib().pp_pose_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def residuals(self, models):
         models = f64(models).reshape(-1, 12)
@@ -414,35 +397,19 @@ def dense_cholesky_solve(A, b, device=0, repeat=1):
 
 
 def lomsac_options(**kw):
-    o = _capi.LoMsacOptions()
-    _capi.lib().pp_lomsac_options_default(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _capi.options(_capi.LoMsacOptions, "pp_lomsac_options_default", **kw)
 
 
-class PlanarOffsetProblem:
+class PlanarOffsetProblem(_Handle):
     """Device-resident PlanarOffsetEstimator (init/initializer.h:72-98): poses [4,3,4], lines [4,n,3], Rg [4,3,3]."""
+    _destroy = "pp_planar_destroy"
 
     def __init__(self, poses, lines, Rg, device=0):
-        self._h = C.c_void_p()
+        super().__init__()
         poses, lines, Rg = f64(poses).reshape(4, 12), f64(lines), f64(Rg).reshape(4, 9)
         self.n = int(lines.shape[1])
         assert lines.shape == (4, self.n, 3)
         check(_capi.lib().pp_planar_create(self.n, dp(poses), dp(lines), dp(Rg), int(device), C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            _capi.lib().pp_planar_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def solve_batch(self, samples):
         samples = np.ascontiguousarray(samples, dtype=np.int32)
@@ -470,26 +437,16 @@ class PlanarOffsetProblem:
         return rep, off, cams.reshape(4, 3, 4), idx[: rep.num_inlier_indices].copy()
 
 
-class Pose2dProblem:
+class Pose2dProblem(_Handle):
     """Device-resident AbsolutePose2dEstimator (init/sfm2d.h:99-143): bearings x [n,2], points X [n,2]."""
+    _destroy = "pp_pose2d_destroy"
 
     def __init__(self, x, X, device=0):
-        self._h = C.c_void_p()
+        super().__init__()
         x, X = f64(x), f64(X)
         self.n = int(x.shape[0])
         assert x.shape == (self.n, 2) and X.shape == (self.n, 2)
         check(_capi.lib().pp_pose2d_create(self.n, dp(x), dp(X), int(device), C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            _capi.lib().pp_pose2d_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def solve_batch(self, samples):
         samples = np.ascontiguousarray(samples, dtype=np.int32)
@@ -511,26 +468,16 @@ class Pose2dProblem:
         return rep, pose, idx[: rep.num_inlier_indices].copy()
 
 
-class FourView2dProblem:
+class FourView2dProblem(_Handle):
     """Device-resident bearings of FourView2dEstimator (init/sfm2d.h:48-97): x [4,n,2]."""
+    _destroy = "pp_fourview2d_destroy"
 
     def __init__(self, x, device=0):
-        self._h = C.c_void_p()
+        super().__init__()
         x = f64(x)
         self.n = int(x.shape[1])
         assert x.shape == (4, self.n, 2)
         check(_capi.lib().pp_fourview2d_create(self.n, dp(x), int(device), C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            _capi.lib().pp_fourview2d_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def score(self, cams, threshold):
         cams = f64(cams).reshape(-1, 24)
@@ -595,11 +542,7 @@ def camera_num_params(model_id):
 def triangulation_options(min_tri_angle=0.0, residual_type=0, **ransac_kw):
     o = _capi.TriangulationOptions()
     o.min_tri_angle = float(min_tri_angle); o.residual_type = int(residual_type)
-    _capi.lib().pp_ransac_options_default(C.byref(o.ransac))
-    for k, v in ransac_kw.items():
-        if not hasattr(o.ransac, k):
-            raise AttributeError(k)
-        setattr(o.ransac, k, v)
+    o.ransac = _capi.options(_capi.RansacOptions, "pp_ransac_options_default", **ransac_kw)
     return o
 
 
@@ -619,53 +562,23 @@ def triangulate_tracks(track_start, lines, obs_view, proj_matrices, proj_centers
 
 
 def tracks_options(**kw):
-    o = _capi.TracksOptions()
-    _capi.lib().pp_tracks_options_default(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _capi.options(_capi.TracksOptions, "pp_tracks_options_default", **kw)
 
 
 def tracks_image_options(**kw):
-    o = _capi.TracksImageOptions()
-    _capi.lib().pp_tracks_image_options_default(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _capi.options(_capi.TracksImageOptions, "pp_tracks_image_options_default", **kw)
 
 
 def local_bundle_options(**kw):
-    o = _capi.LocalBundleOptions()
-    _capi.lib().pp_local_bundle_options_default(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _capi.options(_capi.LocalBundleOptions, "pp_local_bundle_options_default", **kw)
 
 
 def next_image_options(**kw):
-    o = _capi.NextImageOptions()
-    _capi.lib().pp_next_image_options_default(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _capi.options(_capi.NextImageOptions, "pp_next_image_options_default", **kw)
 
 
 def init_sets_options(**kw):
-    o = _capi.InitSetsOptions()
-    _capi.lib().pp_init_sets_options_default(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _capi.options(_capi.InitSetsOptions, "pp_init_sets_options_default", **kw)
 
 
 _TRACKS_FIELDS = (("poses", np.float64, dp), ("pose_camera", np.int32, None), ("camera_model", np.int32, None), ("intr", np.float64, dp),
@@ -690,12 +603,13 @@ def tracks_desc(flat, keep):
     return d
 
 
-class TracksProblem:
+class TracksProblem(_Handle):
     """pp_tracks_handle: the flattened state of the triangulator on the device; complete() / merge() advance it, state() reads it."""
+    _destroy = "pp_tracks_destroy"
 
     def __init__(self, flat, device=0):
         self._keep = []
-        self._h = C.c_void_p()
+        super().__init__()
         self.num_lines = int(len(flat["line_image"]))
         self.num_images, self.num_cameras = int(np.shape(flat["poses"])[0]), int(np.shape(flat["intr"])[0])
         self._max_image_corrs = 0      # the longest correspondence list an image's lines can give (pp_tracks_estimate_image_pose's capacity)
@@ -704,17 +618,6 @@ class TracksProblem:
             self._max_image_corrs = int(np.bincount(np.asarray(flat["line_image"], dtype=np.int64), weights=per_line, minlength=self.num_images).max())
         d = tracks_desc(flat, self._keep)
         check(_capi.lib().pp_tracks_create(C.byref(d), int(device), C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            _capi.lib().pp_tracks_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def num_points(self):
         n, t = C.c_int32(), C.c_int64()
@@ -947,13 +850,7 @@ class TracksProblem:
 
 
 def sift_match_options(**kw):
-    o = _capi.SiftMatchOptions()
-    _capi.lib().pp_sift_match_options_default(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _capi.options(_capi.SiftMatchOptions, "pp_sift_match_options_default", **kw)
 
 
 def sift_match_thresholds(options=None):
@@ -966,12 +863,13 @@ def sift_match_thresholds(options=None):
     return d_min.value, table
 
 
-class SiftMatcher:
+class SiftMatcher(_Handle):
     """pp_sift_handle: the descriptors ([N_k, 128] uint8 each) of a list of images on the device; match_pairs() is MatchSiftFeaturesCPUBruteForce for a
     list of pairs of positions in that list, top2() the one-way scan underneath it."""
+    _destroy = "pp_sift_destroy"
 
     def __init__(self, descriptors_by_image, device=0):
-        self._h = C.c_void_p()
+        super().__init__()
         arrays = []
         for d in descriptors_by_image:
             d = np.asarray(d)
@@ -986,17 +884,6 @@ class SiftMatcher:
         flat = np.ascontiguousarray(flat, dtype=np.uint8)
         check(_capi.lib().pp_sift_create(self.num_images, ptr(start, C.POINTER(C.c_int64)), ptr(flat, _capi.c_u8p) if flat.size else None, int(device),
                                          C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            _capi.lib().pp_sift_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def capacity(self, pairs, cross_check=True):
         """the number of matches that always suffices for these pairs"""
@@ -1025,29 +912,19 @@ class SiftMatcher:
         return bj[:n1], b[:n1], s[:n1]
 
 
-class CorrGraphBuilder:
+class CorrGraphBuilder(_Handle):
     """pp_corr_graph_handle: the images of a problem (their line counts, in ascending image-id order) on the device; build() turns match lists into the
     corr_start / corr_line CSR of pp_tracks_desc by the rules of DatabaseCache::Load and CorrespondenceGraph::AddCorrespondences, get() reads it back."""
+    _destroy = "pp_corr_graph_destroy"
 
     def __init__(self, num_lines_by_image, device=0):
-        self._h = C.c_void_p()
+        super().__init__()
         self.num_lines = np.ascontiguousarray(num_lines_by_image, dtype=np.int32).reshape(-1)
         self.num_images = int(self.num_lines.shape[0])
         self.line_start = np.zeros(self.num_images + 1, dtype=np.int64)
         self.line_start[1:] = np.cumsum(self.num_lines, dtype=np.int64)
         self.num_pairs = None
         check(_capi.lib().pp_corr_graph_create(self.num_images, ptr(self.num_lines, _capi.c_ip) if self.num_images else None, int(device), C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            _capi.lib().pp_corr_graph_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def build(self, pairs, matches, min_num_matches=15):
         """pairs: [num_pairs, 2] image positions; matches: one [n_p, 2] array per pair, or (match_start [num_pairs + 1], flat [n, 2]) as
@@ -1090,23 +967,13 @@ class CorrGraphBuilder:
         return out[:self.num_pairs or 0]
 
 
-class PairSelector:
+class PairSelector(_Handle):
     """pp_pairs_handle (K20): spatial() and transitive() select image pairs on the device and return them; the handle keeps the last result."""
+    _destroy = "pp_pairs_destroy"
 
     def __init__(self, device=0):
-        self._h = C.c_void_p()
+        super().__init__()
         check(_capi.lib().pp_pairs_create(int(device), C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            _capi.lib().pp_pairs_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def num(self):
         n = C.c_int64()
@@ -1141,13 +1008,7 @@ class PairSelector:
 
 
 def line_features_options(**kw):
-    o = _capi.LineFeaturesOptions()
-    _capi.lib().pp_line_features_options_default(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _capi.options(_capi.LineFeaturesOptions, "pp_line_features_options_default", **kw)
 
 
 class LineFeatureGenerator:

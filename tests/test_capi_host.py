@@ -266,3 +266,59 @@ def test_covisibility_entry_point_checks_its_camera_arrays():
     d3.camera_const_mask = None      # no mask: the camera arrays are not needed
     d3.pose_camera = None
     assert L.pp_ba_covisibility(C.byref(d3), out.ctypes.data_as(_capi.c_u8p)) == _capi.PP_OK
+
+
+# (builder in device.py, its struct in _capi, the C function that fills the defaults, one field and a value that is not its default)
+_OPTION_BUILDERS = [
+    ("ba_options", "BAOptions", "pp_ba_options_default", "max_num_iterations", 7),
+    ("ransac_options", "RansacOptions", "pp_ransac_options_default", "max_error", 2.5),
+    ("lomsac_options", "LoMsacOptions", "pp_lomsac_options_default", "num_lo_steps", 3),
+    ("tracks_options", "TracksOptions", "pp_tracks_options_default", "complete_max_transitivity", 3),
+    ("tracks_image_options", "TracksImageOptions", "pp_tracks_image_options_default", "create_max_angle_error", 1.5),
+    ("local_bundle_options", "LocalBundleOptions", "pp_local_bundle_options_default", "local_ba_num_images", 4),
+    ("next_image_options", "NextImageOptions", "pp_next_image_options_default", "max_reg_trials", 2),
+    ("init_sets_options", "InitSetsOptions", "pp_init_sets_options_default", "max_num_sets", 9),
+    ("sift_match_options", "SiftMatchOptions", "pp_sift_match_options_default", "min_num_matches", 3),
+    ("line_features_options", "LineFeaturesOptions", "pp_line_features_options_default", "seed", 5),
+]
+
+
+def _struct_bytes(s):
+    return bytes(memoryview(s).cast("B"))
+
+
+@pytest.mark.parametrize("builder,struct,default_fn,field,value", _OPTION_BUILDERS)
+def test_option_builder(builder, struct, default_fn, field, value):
+    """every *_options(**kw) of device.py: without arguments the struct as the C default function fills it (compared as bytes), a field set by keyword
+    reads back, a keyword the struct does not have raises AttributeError naming it"""
+    from privacy_preserving_sfm_amd import _capi, device
+    build = getattr(device, builder)
+    expected = getattr(_capi, struct)()
+    getattr(_capi.lib(), default_fn)(C.byref(expected))
+    got = build()
+    assert type(got) is type(expected) and _struct_bytes(got) == _struct_bytes(expected)
+    assert getattr(expected, field) != value
+    o = build(**{field: value})
+    assert getattr(o, field) == value
+    setattr(expected, field, value)
+    assert _struct_bytes(o) == _struct_bytes(expected)      # (and nothing else moved)
+    with pytest.raises(AttributeError) as e:
+        build(**{field: value, "no_such_field": 1})
+    assert e.value.args == ("no_such_field",)
+
+
+def test_triangulation_options_builder():
+    """triangulation_options: two fields of its own, every other keyword is a field of the nested RANSAC options"""
+    from privacy_preserving_sfm_amd import _capi
+    from privacy_preserving_sfm_amd.device import triangulation_options
+    expected = _capi.TriangulationOptions()
+    _capi.lib().pp_ransac_options_default(C.byref(expected.ransac))
+    assert _struct_bytes(triangulation_options()) == _struct_bytes(expected)
+    assert expected.ransac.max_error != 3.0 and expected.ransac.min_num_trials != 17
+    o = triangulation_options(min_tri_angle=0.25, residual_type=1, max_error=3.0, min_num_trials=17)
+    assert (o.min_tri_angle, o.residual_type, o.ransac.max_error, o.ransac.min_num_trials) == (0.25, 1, 3.0, 17)
+    expected.min_tri_angle, expected.residual_type, expected.ransac.max_error, expected.ransac.min_num_trials = 0.25, 1, 3.0, 17
+    assert _struct_bytes(o) == _struct_bytes(expected)
+    with pytest.raises(AttributeError) as e:
+        triangulation_options(max_error=3.0, no_such_field=1)
+    assert e.value.args == ("no_such_field",)

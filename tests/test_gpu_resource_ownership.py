@@ -3,6 +3,7 @@ what they were before it was built - whatever the handle allocated lazily in bet
 the intrinsics lists, the chunked pair lists, the block-sparse tile list, the packed system of a group exchange, the covariance's scratch) and also when
 pp_ba_create refuses the problem half way.  Deltas, not zeros: a fixture of the session may hold a handle."""
 import ctypes as C
+import functools
 import re
 
 import numpy as np
@@ -11,7 +12,9 @@ import pytest
 import mixed_models as mm
 import tracks_image_scenes as scenes
 from privacy_preserving_sfm_amd import _capi, synthetic
-from privacy_preserving_sfm_amd.device import BAProblem, TracksProblem, _ba_desc, ba_options, tracks_image_options, tracks_options
+from privacy_preserving_sfm_amd.device import (BAProblem, CorrGraphBuilder, FourView2dProblem, LineFeatureGenerator, PairSelector, PlanarOffsetProblem,
+                                               Pose2dProblem, PoseProblem, SiftMatcher, TracksProblem, _ba_desc, ba_options, device_count, tracks_image_options,
+                                               tracks_options, triangulate_tracks, triangulation_options)
 from privacy_preserving_sfm_amd.incremental_triangulator import IncrementalTriangulator
 
 pytestmark = pytest.mark.gpu
@@ -171,4 +174,139 @@ def test_refused_create_gives_everything_back(monkeypatch, lists):
     text = _capi.lib().pp_last_error().decode()
     m = re.search(r"images (\d+) and (\d+) share a point", text)
     assert m and m.group(1) != m.group(2) and all(0 <= int(g) < 6 for g in m.groups()), text
+    assert _live() == before
+
+
+def test_sift_handle():
+    rng = np.random.default_rng(18)
+    descriptors = [rng.integers(0, 256, size=(n, 128), dtype=np.uint8) for n in (3, 2)]
+    before = _live()
+    m = SiftMatcher(descriptors)
+    try:
+        assert _live()[0] > before[0]
+        _, out = m.match_pairs([(0, 1)])
+        assert len(out) == 1 and out[0].shape[1] == 2
+    finally:
+        m.close()
+    assert _live() == before
+    m.close()                                                   # a second close is harmless
+    assert _live() == before
+
+
+def test_corr_graph_handle():
+    before = _live()
+    g = CorrGraphBuilder([2, 2])
+    try:
+        assert _live()[0] > before[0]
+        rep = g.build([(0, 1)], [np.array([[0, 1]], dtype=np.int32)], min_num_matches=0)
+        assert rep.num_matches_accepted == 1
+        assert list(g.get()["corr_start"]) == [0, 1, 1, 1, 2]   # line 0 of image 0 and line 1 of image 1 see each other
+    finally:
+        g.close()
+    assert _live() == before
+    g.close()
+    assert _live() == before
+
+
+def test_pairs_handle():
+    xyz = np.array([[0, 0, 0], [1, 0, 0], [0, 2, 0]], dtype=np.float32)
+    before = _live()
+    sel = PairSelector()
+    try:
+        assert _live() == before                                # a fresh handle holds no blocks
+        _, pairs, sqdist = sel.spatial(xyz, 2, 10.0)
+        assert len(pairs) == 3 and len(sqdist) == 3             # every location and its one neighbour besides itself
+        assert _live() == (before[0] + 2, before[1])            # the result: pairs and distances (the call's scratch went back)
+        _, pairs = sel.transitive(3, [(0, 1), (1, 2)])
+        assert [tuple(p) for p in pairs] == [(0, 2)]
+        assert _live() == (before[0] + 1, before[1])            # the new result replaced the first one: pairs alone
+    finally:
+        sel.close()
+    assert _live() == before
+    sel.close()
+    assert _live() == before
+
+
+def _refuse_handle(cls, *args):
+    """entry(device) -> (code, out handle) of the create function behind cls(*args, device=device)"""
+    def entry(device):
+        obj = cls.__new__(cls)
+        with pytest.raises(_capi.PPError) as e:
+            obj.__init__(*args, device=device)
+        return e.value.code, obj._h
+    return entry
+
+
+def _refuse_call(call):
+    def entry(device):
+        with pytest.raises(_capi.PPError) as e:
+            call(device)
+        return e.value.code, None
+    return entry
+
+
+def _tiny_tracks_flat():
+    """one image, one camera, no lines, no points"""
+    return dict(poses=np.array([[1.0, 0, 0, 0, 0, 0, 0]]), pose_camera=[0], camera_model=[2], intr=_tiny_intr(), cam_size=[[100, 100]], lines=np.zeros((0, 3)),
+                line_image=[], line_point=[], corr_start=[0], corr_line=[], points=np.zeros((0, 3)), track_start=[0], track_line=[])
+
+
+def _tiny_intr():
+    intr = np.zeros((1, _capi.CAM_STRIDE))
+    intr[0, :3] = [100.0, 50.0, 50.0]                           # SIMPLE_RADIAL: f, cx, cy, k
+    return intr
+
+
+def _tiny_triangulation(device):
+    P = np.tile(np.hstack([np.eye(3), np.zeros((3, 1))]).reshape(1, 12), (3, 1))
+    return triangulate_tracks([0, 3], np.tile([1.0, 0, 0], (3, 1)), [0, 1, 2], P, np.zeros((3, 3)), [0, 0, 0], [2], _tiny_intr(), [[100, 100]],
+                              triangulation_options(max_error=1.0), device=device)
+
+
+def _tiny_line_features(device):
+    return LineFeatureGenerator(device=device).generate([1], [0, 1], [[10.0, 10.0]], [0], [2], _tiny_intr())
+
+
+def _tiny_scan(device):
+    a, out = np.arange(5, dtype=np.int32), np.zeros(6, dtype=np.int32)
+    _capi.check(_capi.lib().pp_debug_exclusive_scan(device, 4, 5, a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), None, None))
+
+
+@functools.lru_cache(maxsize=None)
+def _device_entries():
+    rng = np.random.default_rng(3)
+    eye = np.tile(np.eye(3), (4, 1, 1))
+    return {
+        "pp_ba_create": _refuse_handle(BAProblem, synthetic.make_ba_scene(6, 200, 6)),
+        "pp_pose_create": _refuse_handle(PoseProblem, rng.normal(size=(6, 3)), rng.normal(size=(6, 3))),
+        "pp_planar_create": _refuse_handle(PlanarOffsetProblem, np.tile(np.eye(3, 4), (4, 1, 1)), rng.normal(size=(4, 5, 3)), eye),
+        "pp_pose2d_create": _refuse_handle(Pose2dProblem, rng.normal(size=(5, 2)), rng.normal(size=(5, 2))),
+        "pp_fourview2d_create": _refuse_handle(FourView2dProblem, rng.normal(size=(4, 5, 2))),
+        "pp_tracks_create": _refuse_handle(TracksProblem, _tiny_tracks_flat()),
+        "pp_sift_create": _refuse_handle(SiftMatcher, [np.zeros((1, 128), dtype=np.uint8)]),
+        "pp_corr_graph_create": _refuse_handle(CorrGraphBuilder, [2, 2]),
+        "pp_pairs_create": _refuse_handle(PairSelector),
+        "pp_triangulate_tracks": _refuse_call(_tiny_triangulation),
+        "pp_line_features_from_keypoints": _refuse_call(_tiny_line_features),
+        "pp_debug_exclusive_scan": _refuse_call(_tiny_scan),
+    }
+
+
+DEVICE_ENTRIES = ("pp_ba_create", "pp_pose_create", "pp_planar_create", "pp_pose2d_create", "pp_fourview2d_create", "pp_tracks_create", "pp_sift_create",
+                  "pp_corr_graph_create", "pp_pairs_create", "pp_triangulate_tracks", "pp_line_features_from_keypoints", "pp_debug_exclusive_scan")
+
+
+@pytest.mark.parametrize("which", ["count", "minus_one"])
+@pytest.mark.parametrize("entry", DEVICE_ENTRIES)
+def test_refused_device(entry, which):
+    """every entry that takes a device refuses one the process does not have in the same words, after its argument checks (the arguments here are valid)
+    and before it takes anything: PP_ERR_INVALID, "<entry>: device <d> of <count>", a null handle, the pool as it was.  Nothing is launched."""
+    count = device_count()
+    device = count if which == "count" else -1
+    call = _device_entries()[entry]
+    before = _live()
+    code, handle = call(device)
+    assert code == _capi.PP_ERR_INVALID
+    assert _capi.lib().pp_last_error().decode() == "%s: device %d of %d" % (entry, device, count)
+    assert not handle
     assert _live() == before
