@@ -1250,6 +1250,81 @@ int pp_pairs_num(pp_pairs_handle h, int64_t* n);
  * after a transitive selection that found pairs.  PP_ERR_INVALID, nothing written, when capacity is too small. */
 int pp_pairs_get(pp_pairs_handle h, int32_t* pairs, float* sqdist, int64_t capacity);
 
+/* ======================================================================================== *
+ *  SIFT keypoints and descriptors (K21)                                                     *
+ *  replaces: ExtractSiftFeaturesCPU (feature/sift.cc:399-573) over VLFeat's vl_sift_*       *
+ *  (lib/VLFeat/sift.c) for one grey image; the covariant extractor, domain-size pooling     *
+ *  and SiftGPU's rule are absent                                                            *
+ * ======================================================================================== */
+
+typedef struct pp_sift_extract_options {
+  int32_t max_num_features;      /* 8192: levels are dropped from the finest one up, whole (sift.cc:534-546)                                   */
+  int32_t first_octave;          /* -1: the image is doubled first; -8 .. 8                                                                     */
+  int32_t num_octaves;           /* 4; 1 .. 32 (the reference's "as many as fit" for a negative count is absent)                                */
+  int32_t octave_resolution;     /* 3 levels per octave; 1 .. 32                                                                                */
+  double peak_threshold;         /* 0.02 / 3                                                                                                    */
+  double edge_threshold;         /* 10                                                                                                          */
+  int32_t max_num_orientations;  /* 2: the FIRST local maxima of the orientation histogram in bin order; 1 .. 4                                 */
+  int32_t upright;               /* 0; else one orientation 0 per keypoint                                                                      */
+  int32_t normalization;         /* 0 L1_ROOT, 1 L2                                                                                             */
+  int32_t phase_timings;         /* 0; else the stream is drained between the phases and phase_ms of the report is filled                       */
+} pp_sift_extract_options;
+void pp_sift_extract_options_default(pp_sift_extract_options* o);
+
+#define PP_SIFT_MAX_OCTAVES 32
+typedef struct pp_sift_extract_report {
+  int32_t num_octaves;
+  int32_t num_levels;              /* the per-level containers of the reference: one per run of keypoints of one DoG level of one octave        */
+  int32_t first_level_to_keep;     /* the first container that max_num_features keeps                                                          */
+  int32_t reserved_;
+  int64_t num_keypoints;           /* refined keypoints, with or without an orientation                                                         */
+  int64_t num_features_found;      /* features (keypoint, orientation) of all containers                                                        */
+  int64_t num_features;            /* features kept = *num                                                                                      */
+  int64_t num_two_orientations;    /* keypoints that gave more than one feature                                                                 */
+  int64_t num_moved;               /* candidates whose refinement moved them                                                                    */
+  int64_t num_rejected_peak, num_rejected_edge, num_rejected_offset, num_rejected_bounds;      /* candidates by the first test they failed     */
+  int64_t num_windows_cut;         /* descriptors whose window the image border cut                                                             */
+  int64_t num_descriptors_skipped; /* descriptors whose keypoint failed vl_sift_calc_keypoint_descriptor's bounds check: 128 zeros here         */
+  int32_t octave_width[PP_SIFT_MAX_OCTAVES], octave_height[PP_SIFT_MAX_OCTAVES];
+  int32_t octave_candidates[PP_SIFT_MAX_OCTAVES], octave_keypoints[PP_SIFT_MAX_OCTAVES];
+  double phase_ms[5];              /* pyramid, detection, gradient, orientation, descriptor: by events, with phase_timings                      */
+  double device_ms;                /* all kernels and copies between them, by events                                                            */
+  double total_ms;                 /* the call                                                                                                  */
+} pp_sift_extract_report;
+
+typedef struct pp_sift_extractor_impl* pp_sift_extractor_handle;
+/* A handle owns a stream and a workspace that grows to the largest image it has seen; it keeps the pyramid of its last extraction for the stage
+ * readers below. */
+int pp_sift_extractor_create(int device, pp_sift_extractor_handle* out);
+int pp_sift_extractor_destroy(pp_sift_extractor_handle h);
+/* grey: width x height uint8, row-major.  keypoints: capacity x 4 floats (x, y, scale, orientation) as FeatureKeypoint(x + 0.5f, y + 0.5f, sigma,
+ * angle) holds them; descriptors: NULL or capacity x 128 bytes in UBC order; both in the reference's order, line index = keypoint index =
+ * descriptor row.  The result is a fixed function of the input, bit for bit: keypoints, angles and the float descriptor before the last
+ * normalisation equal the reference's CPU path (every sum in its order, nothing contracted; exp, pow, sin and cos are evaluated by the host's libm).
+ * ABSENT, UNPINNED: the last normalisation of the reference sums with Eigen's reduction; here the L1 norm (the squared L2 norm) is the float32 sum
+ * over the 128 entries from first to last.  A build of the reference can differ from this by one unit in a uint8 entry, and only where 512 v lies
+ * within an ulp of a rounding tie.  A descriptor the reference leaves unwritten (its keypoint fails the descriptor's bounds check) is 128 zeros.
+ * CAPACITY: the need is known after the device work; with capacity too small PP_ERR_INVALID, keypoints and descriptors untouched; *num is the
+ * number of features either way.
+ * ERRORS: PP_ERR_INVALID before any device work for: a null argument (descriptors may be NULL), a non-positive size, max_num_features,
+ * octave_resolution, peak_threshold, edge_threshold or max_num_orientations not positive (NaN included), max_num_orientations > 4, an unknown
+ * normalization, num_octaves or first_octave outside their range, a last octave without a pixel, a first octave of 2^30 pixels or more (int32
+ * indexing of its gradient), a negative capacity. */
+int pp_sift_extract(pp_sift_extractor_handle h, const pp_sift_extract_options* options, int32_t width, int32_t height, const uint8_t* grey,
+                    pp_sift_extract_report* report, int64_t capacity, float* keypoints, uint8_t* descriptors, int64_t* num);
+/* Stage readers of the LAST extraction of the handle (tests, and locating a difference).  kind 0 the Gaussian level, 1 the DoG level, 2 the gradient
+ * (modulus, angle pairs: 2 floats per pixel); octave first_octave .. ; level s_min = -1 .. (Gaussian up to octave_resolution + 1, DoG one fewer,
+ * gradient 0 .. octave_resolution - 1).  out: capacity floats; *width, *height the octave's size.  PP_ERR_INVALID without an extraction, for a
+ * level that does not exist (an octave under 2 x 2 has no gradient) or a capacity too small. */
+int pp_sift_extract_stage(pp_sift_extractor_handle h, int32_t kind, int32_t octave, int32_t level, float* out, int64_t capacity, int32_t* width,
+                          int32_t* height);
+/* the unrefined candidates (x, y, level) of one octave in scan order: capacity x 3; *num either way */
+int pp_sift_extract_candidates(pp_sift_extractor_handle h, int32_t octave, int32_t* xys, int64_t capacity, int64_t* num);
+/* Every feature found, BEFORE the max_num_features cut (the kept ones are the last *num of pp_sift_extract): raw capacity x 128 floats, the descriptor
+ * in VLFeat's bin order before the last normalisation (all zero after an extraction without descriptors); octave_level capacity x 2 (octave, DoG
+ * level); angles capacity doubles.  Any of the three may be NULL; *num either way. */
+int pp_sift_extract_features(pp_sift_extractor_handle h, float* raw, int32_t* octave_level, double* angles, int64_t capacity, int64_t* num);
+
 #ifdef __cplusplus
 }
 #endif

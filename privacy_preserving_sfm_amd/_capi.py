@@ -232,6 +232,28 @@ class PairsReport(C.Structure):
     _fields_ = [("num_pairs", C.c_int64), ("num_candidates", C.c_int64), ("device_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+SIFT_MAX_OCTAVES = 32      # PP_SIFT_MAX_OCTAVES
+SIFT_L1_ROOT, SIFT_L2 = 0, 1
+SIFT_STAGE_GAUSSIAN, SIFT_STAGE_DOG, SIFT_STAGE_GRADIENT = 0, 1, 2
+SIFT_PHASES = ("pyramid", "detection", "gradient", "orientation", "descriptor")
+
+
+class SiftExtractOptions(C.Structure):
+    _fields_ = [("max_num_features", C.c_int32), ("first_octave", C.c_int32), ("num_octaves", C.c_int32), ("octave_resolution", C.c_int32),
+                ("peak_threshold", C.c_double), ("edge_threshold", C.c_double), ("max_num_orientations", C.c_int32), ("upright", C.c_int32),
+                ("normalization", C.c_int32), ("phase_timings", C.c_int32)]
+
+
+class SiftExtractReport(C.Structure):
+    _fields_ = [("num_octaves", C.c_int32), ("num_levels", C.c_int32), ("first_level_to_keep", C.c_int32), ("reserved_", C.c_int32),
+                ("num_keypoints", C.c_int64), ("num_features_found", C.c_int64), ("num_features", C.c_int64), ("num_two_orientations", C.c_int64),
+                ("num_moved", C.c_int64), ("num_rejected_peak", C.c_int64), ("num_rejected_edge", C.c_int64), ("num_rejected_offset", C.c_int64),
+                ("num_rejected_bounds", C.c_int64), ("num_windows_cut", C.c_int64), ("num_descriptors_skipped", C.c_int64),
+                ("octave_width", C.c_int32 * SIFT_MAX_OCTAVES), ("octave_height", C.c_int32 * SIFT_MAX_OCTAVES),
+                ("octave_candidates", C.c_int32 * SIFT_MAX_OCTAVES), ("octave_keypoints", C.c_int32 * SIFT_MAX_OCTAVES),
+                ("phase_ms", C.c_double * 5), ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -271,6 +293,8 @@ _EXPORTS = [
     "pp_corr_graph_create", "pp_corr_graph_destroy", "pp_corr_graph_build", "pp_corr_graph_num_entries", "pp_corr_graph_get", "pp_corr_graph_pair_counts",
     "pp_line_features_options_default", "pp_line_features_from_keypoints",
     "pp_pairs_create", "pp_pairs_destroy", "pp_pairs_spatial", "pp_pairs_transitive", "pp_pairs_num", "pp_pairs_get",
+    "pp_sift_extract_options_default", "pp_sift_extractor_create", "pp_sift_extractor_destroy", "pp_sift_extract", "pp_sift_extract_stage",
+    "pp_sift_extract_candidates", "pp_sift_extract_features",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -416,6 +440,15 @@ def lib():
     L.pp_pairs_transitive.argtypes = [C.c_void_p, C.c_int32, C.c_int64, c_ip, C.c_int64, c_ip, C.POINTER(PairsReport)]
     L.pp_pairs_num.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.pp_pairs_get.argtypes = [C.c_void_p, c_ip, C.POINTER(C.c_float), C.c_int64]
+    L.pp_sift_extract_options_default.argtypes = [C.POINTER(SiftExtractOptions)]
+    L.pp_sift_extract_options_default.restype = None
+    L.pp_sift_extractor_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.pp_sift_extractor_destroy.argtypes = [C.c_void_p]
+    L.pp_sift_extract.argtypes = [C.c_void_p, C.POINTER(SiftExtractOptions), C.c_int32, C.c_int32, c_u8p, C.POINTER(SiftExtractReport), C.c_int64,
+                                  C.POINTER(C.c_float), c_u8p, C.POINTER(C.c_int64)]
+    L.pp_sift_extract_stage.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int64, c_ip, c_ip]
+    L.pp_sift_extract_candidates.argtypes = [C.c_void_p, C.c_int32, c_ip, C.c_int64, C.POINTER(C.c_int64)]
+    L.pp_sift_extract_features.argtypes = [C.c_void_p, C.POINTER(C.c_float), c_ip, c_dp, C.c_int64, C.POINTER(C.c_int64)]
     _lib = L
     return L
 

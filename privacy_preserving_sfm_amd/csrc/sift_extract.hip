@@ -1,0 +1,605 @@
+// K21 - SIFT keypoints and descriptors of one grey image: ExtractSiftFeaturesCPU (reference src/feature/sift.cc:399-573, over VLFeat's vl_sift_*) on
+// the device, the same output bit for bit.  The arithmetic of every pixel and keypoint is sift_core.hpp, the host's share (libm, the level
+// containers, the max_num_features cut) sift_extract_replay.hpp; this file is the kernels around the former and the C ABI.  No kernel uses an atomic
+// or waits for another workgroup: every list comes out in the reference's order by count, scan (scan.hpp) and scatter.
+// K21a k_sift_load / k_sift_upsample / k_sift_downsample   the first level of an octave from the bytes, or from the octave before
+// K21b k_sift_convolve   one pass of _vl_sift_smooth: the column convolution with the transposed write.  A workgroup takes a 32 x 32 tile of
+//                        outputs: the 32 + 2 W input rows of its 32 columns are staged in LDS (reads along the rows, the ends clamped - padding by
+//                        continuity), then one lane per output pixel walks its 2 W + 1 taps down the staged column in the reference's order.  The
+//                        lanes of a wavefront take consecutive rows, so the write of out[x * h + y] is contiguous - and that makes the second pass,
+//                        which reads the transposed image along ITS rows, contiguous as well.  The LDS pitch of 33 keeps the 32 lanes on 32 banks.
+// K21c k_sift_dog, k_sift_gradient   one lane per pixel
+// K21d k_sift_detect_count / _scatter   a workgroup per row (level, y): the 26-neighbour test, the row's count; after the scan over the rows the same
+//                        test again with a workgroup scan per 256 pixels, so the candidates land in (level, y, x) order
+// K21e k_sift_refine     one lane per candidate; the host keeps the survivors in order and evaluates pow for their sigma
+// K21f k_sift_orient     one lane per keypoint walking its window in the reference's order (the histogram is a sequential double sum)
+// K21g k_sift_describe   one lane per feature: the 4 x 4 x 8 float accumulation in the reference's order straight into the feature's row of the raw
+//                        descriptors, then the last normalisation to bytes.  The long pole at thousands of features; a wavefront per keypoint with a
+//                        fixed-order fold is the follow-up.
+#include <cstring>
+
+#include "device_handle.hpp"
+#include "scan.hpp"
+#include "sift_extract_replay.hpp"
+
+namespace ppsfm {
+
+using namespace sift;
+
+constexpr int kSiftBlock = 256;
+constexpr int kSiftTile = 32;                   // outputs per side of a convolution tile
+constexpr int kSiftPitch = kSiftTile + 1;
+constexpr int kSiftLaneBlock = 64;              // the lane-per-item kernels: few items, many workgroups
+
+__global__ __launch_bounds__(kSiftBlock) void k_sift_load(int64_t n, const uint8_t* __restrict__ grey, float* __restrict__ im) {
+  const int64_t i = (int64_t)blockIdx.x * kSiftBlock + threadIdx.x;
+  if (i < n) im[i] = PixelFromByte(grey[i]);
+}
+
+// copy_and_upsample_rows: dst[X * h + y], X < 2 w
+__global__ __launch_bounds__(kSiftBlock) void k_sift_upsample(float* __restrict__ dst, const float* __restrict__ src, int w, int h) {
+  const int64_t i = (int64_t)blockIdx.x * kSiftBlock + threadIdx.x;
+  if (i >= 2 * (int64_t)w * h) return;
+  const int X = (int)(i / h), y = (int)(i % h);
+  dst[i] = UpsampleRowValue(src + (int64_t)y * w, w, X);
+}
+
+// dst (nw x nh) = every d-th pixel of every d-th row of src (rows of w)
+__global__ __launch_bounds__(kSiftBlock) void k_sift_downsample(float* __restrict__ dst, const float* __restrict__ src, int w, int nw, int nh, int d) {
+  const int64_t i = (int64_t)blockIdx.x * kSiftBlock + threadIdx.x;
+  if (i >= (int64_t)nw * nh) return;
+  const int x = (int)(i % nw), y = (int)(i / nw);
+  dst[i] = src[(int64_t)(y * d) * w + (int64_t)x * d];
+}
+
+__global__ __launch_bounds__(kSiftBlock) void k_sift_convolve(float* __restrict__ dst, const float* __restrict__ src, int w, int h,
+                                                              const float* __restrict__ taps, int W) {
+  extern __shared__ float lds[];
+  float* tile = lds;                                        // (32 + 2 W) rows of 33
+  float* tp = lds + (kSiftTile + 2 * W) * kSiftPitch;       // 2 W + 1 taps
+  const int tid = threadIdx.x;
+  const int x0 = blockIdx.x * kSiftTile, y0 = blockIdx.y * kSiftTile;
+  const int rows = kSiftTile + 2 * W;
+  for (int i = tid; i < rows * kSiftTile; i += kSiftBlock) {
+    const int r = i >> 5, c = i & 31;
+    int p = y0 - W + r;
+    p = p < 0 ? 0 : (p > h - 1 ? h - 1 : p);
+    const int xx = x0 + c < w ? x0 + c : w - 1;
+    tile[r * kSiftPitch + c] = src[(int64_t)p * w + xx];
+  }
+  for (int i = tid; i < 2 * W + 1; i += kSiftBlock) tp[i] = taps[i];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kSiftTile * kSiftTile / kSiftBlock; ++k) {
+    const int o = tid + kSiftBlock * k;
+    const int ly = o & 31, lx = o >> 5;
+    const int x = x0 + lx, y = y0 + ly;
+    if (x < w && y < h) dst[(int64_t)x * h + y] = ConvolveTaps(tile + ly * kSiftPitch + lx, kSiftPitch, tp, 2 * W + 1);
+  }
+}
+
+// dog[j] = octave[j + lev] - octave[j] over the levels laid end to end
+__global__ __launch_bounds__(kSiftBlock) void k_sift_dog(float* __restrict__ dog, const float* __restrict__ octave, int64_t lev, int64_t n) {
+  const int64_t j = (int64_t)blockIdx.x * kSiftBlock + threadIdx.x;
+  if (j < n) dog[j] = octave[j + lev] - octave[j];
+}
+
+// levels: the Gaussian levels s_min + 1 .. s_max - 2, end to end
+__global__ __launch_bounds__(kSiftBlock) void k_sift_gradient(float* __restrict__ grad, const float* __restrict__ levels, int w, int h, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * kSiftBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t lev = (int64_t)w * h;
+  const int64_t s = i / lev, r = i % lev;
+  float mod, ang;
+  GradientAt(levels + s * lev, w, h, (int)(r % w), (int)(r / w), &mod, &ang);
+  grad[2 * i] = mod;      // (two stores: a level of odd size leaves the next one's pairs off an 8-byte boundary)
+  grad[2 * i + 1] = ang;
+}
+
+// row = (level - (s_min + 1)) * h + y; dog1 = the DoG level s_min + 1
+__global__ __launch_bounds__(kSiftBlock) void k_sift_detect_count(const float* __restrict__ dog1, int w, int h, double threshold, int32_t* __restrict__ row_count) {
+  __shared__ int32_t wave_total[kSiftBlock / kWave];
+  const int row = blockIdx.x, y = row % h;
+  const int64_t lev = (int64_t)w * h;
+  int32_t cnt = 0;
+  if (y >= 1 && y <= h - 2) {
+    const float* base = dog1 + (int64_t)(row / h) * lev + (int64_t)y * w;
+    for (int x = 1 + threadIdx.x; x < w - 1; x += kSiftBlock) cnt += IsExtremum(base + x, w, (int)lev, threshold);
+  }
+  int32_t all;
+  (void)BlockExclusiveScan<kSiftBlock>(cnt, wave_total, &all);
+  if (threadIdx.x == 0) row_count[row] = all;
+}
+
+__global__ __launch_bounds__(kSiftBlock) void k_sift_detect_scatter(const float* __restrict__ dog1, int w, int h, int s_first, double threshold,
+                                                                    const int32_t* __restrict__ row_count, const int32_t* __restrict__ row_start,
+                                                                    int32_t* __restrict__ cand) {
+  __shared__ int32_t wave_total[kSiftBlock / kWave];
+  const int row = blockIdx.x, y = row % h;
+  if (row_count[row] == 0) return;      // (the whole workgroup)
+  const int64_t lev = (int64_t)w * h;
+  const float* base = dog1 + (int64_t)(row / h) * lev + (int64_t)y * w;
+  int32_t at = row_start[row];
+  for (int x0 = 1; x0 < w - 1; x0 += kSiftBlock) {
+    const int x = x0 + threadIdx.x;
+    const int32_t flag = x < w - 1 && IsExtremum(base + x, w, (int)lev, threshold);
+    int32_t all;
+    const int32_t pos = BlockExclusiveScan<kSiftBlock>(flag, wave_total, &all);
+    if (flag) {
+      int32_t* c = cand + 3 * (int64_t)(at + pos);
+      c[0] = x; c[1] = y; c[2] = s_first + row / h;
+    }
+    at += all;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kSiftLaneBlock) void k_sift_refine(int32_t n, const int32_t* __restrict__ cand, const float* __restrict__ dog, int w, int h, int s_min,
+                                                               int s_max, double tp, double te, Refined* __restrict__ out) {
+  const int32_t i = blockIdx.x * kSiftLaneBlock + threadIdx.x;
+  if (i >= n) return;
+  out[i] = RefineCandidate(dog, w, h, s_min, s_max, cand[3 * (int64_t)i], cand[3 * (int64_t)i + 1], cand[3 * (int64_t)i + 2], tp, te);
+}
+
+// grad: the octave's gradient levels s_min + 1 .. end to end
+__global__ __launch_bounds__(kSiftLaneBlock) void k_sift_orient(int32_t n, const Keypoint* __restrict__ keys, const float* __restrict__ grad, int w, int h, int s_min,
+                                                               int s_max, double xper, const double* __restrict__ expn, int32_t* __restrict__ num_angles,
+                                                               double* __restrict__ angles) {
+  const int32_t i = blockIdx.x * kSiftLaneBlock + threadIdx.x;
+  if (i >= n) return;
+  const Keypoint k = keys[i];
+  double a[kMaxAngles] = {0, 0, 0, 0};
+  const int64_t level = (int64_t)(k.is - s_min - 1) * 2 * ((int64_t)w * h);      // (Orientations reads nothing when is is out of range: clamp the pointer)
+  const bool in_range = k.is >= s_min + 1 && k.is <= s_max - 2;
+  num_angles[i] = Orientations(grad + (in_range ? level : 0), w, h, s_min, s_max, k, xper, expn, a);
+#pragma unroll
+  for (int j = 0; j < kMaxAngles; ++j) angles[kMaxAngles * (int64_t)i + j] = a[j];
+}
+
+struct SiftFeature {
+  int32_t key, reserved_;
+  double angle, sin_angle, cos_angle;      // the host's libm
+};
+
+__global__ __launch_bounds__(kSiftLaneBlock) void k_sift_describe(int32_t n, const SiftFeature* __restrict__ feats, const Keypoint* __restrict__ keys,
+                                                                 const float* __restrict__ grad, int w, int h, int s_min, int s_max, double xper,
+                                                                 const double* __restrict__ expn, int normalization, float* __restrict__ raw,
+                                                                 uint8_t* __restrict__ bytes, DescriptorWindow* __restrict__ window) {
+  const int32_t f = blockIdx.x * kSiftLaneBlock + threadIdx.x;
+  if (f >= n) return;
+  const SiftFeature q = feats[f];
+  const Keypoint k = keys[q.key];
+  const bool in_range = k.is >= s_min + 1 && k.is <= s_max - 2;
+  const int64_t level = (int64_t)(k.is - s_min - 1) * 2 * ((int64_t)w * h);
+  float* row = raw + (int64_t)kDescBins * f;
+  window[f] = Descriptor(grad + (in_range ? level : 0), w, h, s_min, s_max, k, xper, q.angle, q.sin_angle, q.cos_angle, expn, row);
+  FinishDescriptor(row, normalization, bytes + (int64_t)kDescBins * f);
+}
+
+struct SiftOctave {
+  int32_t o = 0, w = 0, h = 0;
+  bool has_grad = false;
+  size_t gauss = 0, dog = 0, grad = 0;      // offsets into the pyramid, in floats
+  std::vector<int32_t> cand;                // the unrefined candidates of the last extraction
+};
+
+}  // namespace ppsfm
+
+struct pp_sift_extractor_impl : ppsfm::DeviceHandle {
+  // the workspace: grows, never shrinks
+  float* pyramid = nullptr;       size_t cap_pyramid = 0;       // every octave's Gaussian, DoG and gradient levels + the transposed temporary
+  float* image = nullptr;         uint8_t* grey = nullptr;      size_t cap_image = 0;
+  int32_t* rows = nullptr;        size_t cap_rows = 0;          // row counts, row starts, the total, the scan's scratch
+  int32_t* cand = nullptr;        ppsfm::sift::Refined* refined = nullptr;      size_t cap_cand = 0;
+  ppsfm::sift::Keypoint* keys = nullptr;      int32_t* num_angles = nullptr;      double* angles = nullptr;      size_t cap_keys = 0;
+  ppsfm::SiftFeature* feats = nullptr;      float* raw = nullptr;      uint8_t* bytes = nullptr;      ppsfm::sift::DescriptorWindow* window = nullptr;      size_t cap_feats = 0;
+  double* expn = nullptr;
+  float* taps = nullptr;          size_t cap_taps = 0;
+  // the last extraction
+  bool extracted = false;
+  ppsfm::sift::Geometry geom{};
+  std::vector<ppsfm::SiftOctave> octaves;
+  std::vector<float> last_raw;
+  std::vector<int32_t> last_octave_level;
+  std::vector<double> last_angles;
+};
+
+using namespace ppsfm;
+
+namespace {
+
+// a buffer of the workspace regrown to at least `count` elements (the old block goes back: the stream has drained whenever this is called with
+// work outstanding on it - see the call sites)
+template <class T>
+int Grow(DeviceBlocks& b, T** p, size_t* cap, size_t count) {
+  if (*p && *cap >= count) return PP_OK;
+  if (*p) b.Free(p);
+  *cap = 0;
+  PP_TRY(b.Alloc(p, count));
+  *cap = count;
+  return PP_OK;
+}
+template <class T>
+int GrowBeside(DeviceBlocks& b, T** p, bool regrow, size_t count) {      // a buffer that shares another one's capacity
+  if (*p && !regrow) return PP_OK;
+  if (*p) b.Free(p);
+  return b.Alloc(p, count);
+}
+
+Options FromC(const pp_sift_extract_options& c) {
+  Options o;
+  o.max_num_features = c.max_num_features; o.first_octave = c.first_octave; o.num_octaves = c.num_octaves; o.octave_resolution = c.octave_resolution;
+  o.peak_threshold = c.peak_threshold; o.edge_threshold = c.edge_threshold; o.max_num_orientations = c.max_num_orientations; o.upright = c.upright;
+  o.normalization = c.normalization;
+  return o;
+}
+
+}  // namespace
+
+extern "C" {
+
+void pp_sift_extract_options_default(pp_sift_extract_options* o) {
+  if (!o) return;
+  const Options d;      // feature/sift.h:46-104
+  o->max_num_features = d.max_num_features; o->first_octave = d.first_octave; o->num_octaves = d.num_octaves; o->octave_resolution = d.octave_resolution;
+  o->peak_threshold = d.peak_threshold; o->edge_threshold = d.edge_threshold; o->max_num_orientations = d.max_num_orientations; o->upright = d.upright;
+  o->normalization = d.normalization; o->phase_timings = 0;
+}
+
+int pp_sift_extractor_destroy(pp_sift_extractor_handle h) try {
+  delete h;      // (~DeviceHandle)
+  return PP_OK;
+} PP_API_CATCH("pp_sift_extractor_destroy")
+
+int pp_sift_extractor_create(int device, pp_sift_extractor_handle* out) try {
+  const char* where = "pp_sift_extractor_create";
+  PP_REQUIRE(out, "%s: null argument", where);
+  *out = nullptr;
+  PP_TRY(UseDevice(where, device));
+  UnderConstruction<pp_sift_extractor_impl, pp_sift_extractor_destroy> h{new pp_sift_extractor_impl()};
+  PP_TRY(h->Open(device));
+  const std::vector<double> table = ExpnTable();
+  PP_TRY(h->blocks.Put(&h->expn, table.data(), table.size(), h->stream));
+  PP_HIP_TRY(hipStreamSynchronize(h->stream));      // (table is on this frame)
+  *out = h.release();
+  return PP_OK;
+} PP_API_CATCH("pp_sift_extractor_create")
+
+int pp_sift_extract(pp_sift_extractor_handle h, const pp_sift_extract_options* options, int32_t width, int32_t height, const uint8_t* grey,
+                    pp_sift_extract_report* report, int64_t capacity, float* keypoints, uint8_t* descriptors, int64_t* num) try {
+  const char* where = "pp_sift_extract";
+  PP_REQUIRE(options && grey && report && num && keypoints, "%s: null argument", where);
+  PP_REQUIRE(capacity >= 0, "%s: negative capacity", where);
+  const auto t_begin = Clock::now();
+  const Options opt = FromC(*options);
+  const std::string wrong = CheckOptions(opt, width, height);
+  PP_REQUIRE(wrong.empty(), "%s: %s", where, wrong.c_str());
+  PP_REQUIRE(h, "%s: null handle", where);
+  const Geometry g = MakeGeometry(opt);
+  const int L = g.levels(), num_grad = g.S;      // Gaussian levels; gradient levels s_min + 1 .. s_max - 2
+
+  // the filters, one after the other: [0] the first octave's first level (or none), [1] a later octave's (none with the reference's geometry), then
+  // the levels s_min + 1 .. s_max
+  struct Filter { size_t offset; int W; };
+  std::vector<float> taps;
+  std::vector<Filter> filters;
+  auto add_filter = [&](double sigma) {
+    if (!(sigma > 0.0)) { filters.push_back(Filter{0, 0}); return; }
+    const std::vector<float> t = GaussTaps(sigma);
+    filters.push_back(Filter{taps.size(), (int)t.size() / 2});
+    taps.insert(taps.end(), t.begin(), t.end());
+  };
+  add_filter(FirstLevelSigma(g, true));
+  add_filter(FirstLevelSigma(g, false));
+  for (int s = g.s_min + 1; s <= g.s_max; ++s) add_filter(LevelSigma(g, s));
+  for (const Filter& f : filters) PP_REQUIRE(f.W <= kMaxFilterHalfWidth, "%s: a filter of half width %d", where, f.W);
+
+  // the octaves and their places in the pyramid
+  std::vector<SiftOctave> octaves((size_t)g.O);
+  size_t total = 0;
+  for (int q = 0; q < g.O; ++q) {
+    SiftOctave& oc = octaves[(size_t)q];
+    oc.o = g.o_min + q;
+    oc.w = ShiftLeft(width, -oc.o); oc.h = ShiftLeft(height, -oc.o);
+    oc.has_grad = oc.w >= 2 && oc.h >= 2;
+    const size_t lev = (size_t)oc.w * oc.h;
+    oc.gauss = total; total += lev * (size_t)L;
+    oc.dog = total; total += lev * (size_t)(L - 1);
+    oc.grad = total; total += 2 * lev * (size_t)num_grad;
+  }
+  const size_t nel0 = (size_t)octaves[0].w * octaves[0].h;
+  const size_t temp_offset = total;
+  total += nel0;
+  int max_rows = 1;
+  for (const SiftOctave& oc : octaves) max_rows = std::max(max_rows, g.S * oc.h);
+  const size_t rows_need = 2 * (size_t)max_rows + 2 + ScanScratchCount(max_rows);
+
+  PP_HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  h->extracted = false;
+  PP_TRY(Grow(h->blocks, &h->pyramid, &h->cap_pyramid, total));
+  {
+    const bool regrow = !h->image || h->cap_image < (size_t)width * height;
+    PP_TRY(Grow(h->blocks, &h->image, &h->cap_image, (size_t)width * height));
+    PP_TRY(GrowBeside(h->blocks, &h->grey, regrow, h->cap_image));
+  }
+  PP_TRY(Grow(h->blocks, &h->rows, &h->cap_rows, rows_need));
+  PP_TRY(Grow(h->blocks, &h->taps, &h->cap_taps, taps.size()));
+  PP_TRY(Upload(h->taps, taps.data(), taps.size(), s));
+  PP_TRY(Upload(h->grey, grey, (size_t)width * height, s));
+
+  StreamTimer timer(*h);
+  double phase_ms[5] = {0, 0, 0, 0, 0};
+  enum { kPyramid = 0, kDetect = 1, kGradient = 2, kOrient = 3, kDescribe = 4 };
+  // the span since the last Begin() belongs to `phase`: close it (the stream is drained) and open the next one
+  auto close_span = [&](int phase) -> int {
+    PP_HIP_TRY(hipGetLastError());
+    PP_TRY(timer.End());
+    PP_HIP_TRY(hipStreamSynchronize(s));
+    const float before = timer.ms;
+    PP_TRY(timer.Add());
+    phase_ms[phase] += (double)(timer.ms - before);
+    return timer.Begin();
+  };
+  auto phase_boundary = [&](int phase) -> int { return options->phase_timings ? close_span(phase) : PP_OK; };
+  auto grid = [](int64_t n, int block) { return dim3((unsigned)std::max<int64_t>(CeilDiv(n, block), 1)); };
+  auto smooth = [&](float* out, const float* in, int w, int hgt, const Filter& f) {
+    float* temp = h->pyramid + temp_offset;
+    const size_t lds = ((size_t)(kSiftTile + 2 * f.W) * kSiftPitch + 2 * (size_t)f.W + 1) * sizeof(float);
+    hipLaunchKernelGGL(k_sift_convolve, dim3((unsigned)CeilDiv(w, kSiftTile), (unsigned)CeilDiv(hgt, kSiftTile)), dim3(kSiftBlock), lds, s, temp, in, w, hgt,
+                       (const float*)(h->taps + f.offset), f.W);
+    hipLaunchKernelGGL(k_sift_convolve, dim3((unsigned)CeilDiv(hgt, kSiftTile), (unsigned)CeilDiv(w, kSiftTile)), dim3(kSiftBlock), lds, s, out, (const float*)temp, hgt, w,
+                       (const float*)(h->taps + f.offset), f.W);
+  };
+
+  HostResult R;      // the containers of the reference, filled octave by octave
+  std::vector<Refined> refined;
+  std::vector<Keypoint> keys;
+  std::vector<int32_t> num_angles, is_of_key, used;
+  std::vector<double> angles;
+  std::vector<SiftFeature> feats;
+  std::vector<DescriptorWindow> window;
+  std::memset(report, 0, sizeof(*report));
+
+  PP_TRY(timer.Begin());
+  hipLaunchKernelGGL(k_sift_load, grid((int64_t)width * height, kSiftBlock), dim3(kSiftBlock), 0, s, (int64_t)width * height, (const uint8_t*)h->grey, h->image);
+  for (int q = 0; q < g.O; ++q) {
+    SiftOctave& oc = octaves[(size_t)q];
+    const int w = oc.w, hgt = oc.h;
+    const int64_t lev = (int64_t)w * hgt;
+    float* gauss = h->pyramid + oc.gauss;
+    float* dog = h->pyramid + oc.dog;
+    float* grad = h->pyramid + oc.grad;
+    float* temp = h->pyramid + temp_offset;
+    // ---- the octave's first level
+    if (q == 0) {
+      if (g.o_min < 0) {
+        hipLaunchKernelGGL(k_sift_upsample, grid(2 * (int64_t)width * height, kSiftBlock), dim3(kSiftBlock), 0, s, temp, (const float*)h->image, width, height);
+        hipLaunchKernelGGL(k_sift_upsample, grid(4 * (int64_t)width * height, kSiftBlock), dim3(kSiftBlock), 0, s, gauss, (const float*)temp, height, 2 * width);
+        for (int d = -1; d > g.o_min; --d) {      // (the reference's arguments, as they stand)
+          const int dw = width << -d, dh = height << -d;
+          hipLaunchKernelGGL(k_sift_upsample, grid(2 * (int64_t)dw * dh, kSiftBlock), dim3(kSiftBlock), 0, s, temp, (const float*)gauss, dw, dh);
+          hipLaunchKernelGGL(k_sift_upsample, grid(4 * (int64_t)dw * dh, kSiftBlock), dim3(kSiftBlock), 0, s, gauss, (const float*)temp, dw, 2 * dh);
+        }
+      } else {
+        hipLaunchKernelGGL(k_sift_downsample, grid(lev, kSiftBlock), dim3(kSiftBlock), 0, s, gauss, (const float*)h->image, width, w, hgt, 1 << g.o_min);
+      }
+    } else {
+      const SiftOctave& prev = octaves[(size_t)q - 1];
+      const int s_best = std::min(g.s_min + g.S, g.s_max);
+      const float* from = h->pyramid + prev.gauss + (size_t)(s_best - g.s_min) * ((size_t)prev.w * prev.h);
+      hipLaunchKernelGGL(k_sift_downsample, grid(lev, kSiftBlock), dim3(kSiftBlock), 0, s, gauss, from, prev.w, w, hgt, 2);
+    }
+    const Filter& f0 = filters[q == 0 ? 0 : 1];
+    if (f0.W > 0) smooth(gauss, gauss, w, hgt, f0);
+    for (int lvl = 1; lvl < L; ++lvl) smooth(gauss + (size_t)lvl * lev, gauss + (size_t)(lvl - 1) * lev, w, hgt, filters[(size_t)lvl + 1]);
+    hipLaunchKernelGGL(k_sift_dog, grid(lev * (L - 1), kSiftBlock), dim3(kSiftBlock), 0, s, dog, (const float*)gauss, lev, lev * (L - 1));
+    PP_TRY(phase_boundary(kPyramid));
+    if (oc.has_grad)
+      hipLaunchKernelGGL(k_sift_gradient, grid(lev * num_grad, kSiftBlock), dim3(kSiftBlock), 0, s, grad, (const float*)(gauss + lev), w, hgt, lev * num_grad);
+    PP_TRY(phase_boundary(kGradient));
+    // ---- detection: count per row, scan, scatter, refine
+    const int rows = g.S * hgt;
+    int32_t* row_count = h->rows;
+    int32_t* row_start = h->rows + max_rows;
+    int32_t* d_total = h->rows + 2 * (size_t)max_rows;
+    int32_t* scan_scratch = h->rows + 2 * (size_t)max_rows + 2;
+    const double threshold = 0.8 * opt.peak_threshold;
+    int32_t num_cand = 0;
+    if (w >= 3 && hgt >= 3) {
+      hipLaunchKernelGGL(k_sift_detect_count, dim3((unsigned)rows), dim3(kSiftBlock), 0, s, (const float*)(dog + lev), w, hgt, threshold, row_count);
+      const ScanJob<int32_t> job{row_count, row_start, d_total};
+      LaunchExclusiveScan<int32_t>(s, rows, &job, 1, scan_scratch);
+      PP_TRY(Download(&num_cand, (const int32_t*)d_total, 1, s));
+      PP_TRY(close_span(kDetect));
+    }
+    oc.cand.assign(3 * (size_t)num_cand, 0);
+    refined.assign((size_t)num_cand, Refined{});
+    if (num_cand > 0) {
+      {      // (the stream has drained)
+        const bool regrow = !h->cand || h->cap_cand < (size_t)num_cand;
+        const size_t want = std::max<size_t>((size_t)num_cand, 2 * h->cap_cand);
+        if (regrow) { if (h->cand) h->blocks.Free(&h->cand); h->cap_cand = 0; PP_TRY(h->blocks.Alloc(&h->cand, 3 * want)); h->cap_cand = want; }
+        PP_TRY(GrowBeside(h->blocks, &h->refined, regrow, h->cap_cand));
+      }
+      hipLaunchKernelGGL(k_sift_detect_scatter, dim3((unsigned)rows), dim3(kSiftBlock), 0, s, (const float*)(dog + lev), w, hgt, g.s_min + 1, threshold,
+                         (const int32_t*)row_count, (const int32_t*)row_start, h->cand);
+      hipLaunchKernelGGL(k_sift_refine, grid(num_cand, kSiftLaneBlock), dim3(kSiftLaneBlock), 0, s, num_cand, (const int32_t*)h->cand, (const float*)dog, w, hgt, g.s_min,
+                         g.s_max, opt.peak_threshold, opt.edge_threshold, h->refined);
+      PP_TRY(Download(oc.cand.data(), (const int32_t*)h->cand, oc.cand.size(), s));
+      PP_TRY(Download(refined.data(), (const Refined*)h->refined, refined.size(), s));
+      PP_TRY(close_span(kDetect));
+    }
+    OctaveCounts counts{w, hgt, num_cand, 0, 0, 0, 0, 0, 0};
+    keys.clear();
+    for (const Refined& r : refined) {
+      counts.moved += r.moves > 0;
+      counts.reject_peak += r.reject == 1; counts.reject_edge += r.reject == 2; counts.reject_offset += r.reject == 3; counts.reject_bounds += r.reject == 4;
+      if (r.good) keys.push_back(MakeKeypoint(r, oc.o, g));
+    }
+    counts.num_keypoints = (int32_t)keys.size();
+    R.octaves.push_back(counts);
+    const size_t K = keys.size();
+    if (K == 0) continue;
+    // ---- orientations
+    const double xper = std::ldexp(1.0, oc.o);
+    {
+      const bool regrow = !h->keys || h->cap_keys < K;
+      const size_t want = std::max<size_t>(K, 2 * h->cap_keys);
+      if (regrow) { if (h->keys) h->blocks.Free(&h->keys); h->cap_keys = 0; PP_TRY(h->blocks.Alloc(&h->keys, want)); h->cap_keys = want; }
+      PP_TRY(GrowBeside(h->blocks, &h->num_angles, regrow, h->cap_keys));
+      PP_TRY(GrowBeside(h->blocks, &h->angles, regrow, kMaxAngles * h->cap_keys));
+    }
+    if (!opt.upright || descriptors) PP_TRY(Upload(h->keys, keys.data(), K, s));      // (each of the two kernels that read them ends in a drained stream)
+    num_angles.assign(K, 1);
+    angles.assign(kMaxAngles * K, 0.0);
+    if (!opt.upright) {
+      hipLaunchKernelGGL(k_sift_orient, grid((int64_t)K, kSiftLaneBlock), dim3(kSiftLaneBlock), 0, s, (int32_t)K, (const Keypoint*)h->keys, (const float*)grad, w, hgt, g.s_min,
+                         g.s_max, xper, (const double*)h->expn, h->num_angles, h->angles);
+      PP_TRY(Download(num_angles.data(), (const int32_t*)h->num_angles, K, s));
+      PP_TRY(Download(angles.data(), (const double*)h->angles, kMaxAngles * K, s));
+      PP_TRY(close_span(kOrient));
+    }
+    // ---- the features of the octave, and their descriptors
+    is_of_key.resize(K); used.resize(K);
+    feats.clear();
+    for (size_t i = 0; i < K; ++i) {
+      is_of_key[i] = keys[i].is;
+      used[i] = std::min(num_angles[i], opt.max_num_orientations);
+      R.two_orientations += used[i] >= 2;
+      for (int a = 0; a < used[i]; ++a) {
+        const double angle = angles[kMaxAngles * i + (size_t)a];
+        float row[4];
+        FeatureRow(keys[i], angle, row);
+        R.keypoints.insert(R.keypoints.end(), row, row + 4);
+        R.octave_level.push_back(oc.o); R.octave_level.push_back(keys[i].is);
+        R.angles.push_back(angle);
+        feats.push_back(SiftFeature{(int32_t)i, 0, angle, std::sin(angle), std::cos(angle)});
+      }
+    }
+    AppendLevels(oc.o, is_of_key.data(), used.data(), (int64_t)K, &R.levels);
+    const size_t F = feats.size();
+    if (!descriptors || F == 0) {
+      R.raw.resize(R.raw.size() + kDescBins * F, 0.f);
+      R.descriptors.resize(R.descriptors.size() + kDescBins * F, 0);
+      continue;
+    }
+    {
+      const bool regrow = !h->feats || h->cap_feats < F;
+      const size_t want = std::max<size_t>(F, 2 * h->cap_feats);
+      if (regrow) { if (h->feats) h->blocks.Free(&h->feats); h->cap_feats = 0; PP_TRY(h->blocks.Alloc(&h->feats, want)); h->cap_feats = want; }
+      PP_TRY(GrowBeside(h->blocks, &h->raw, regrow, kDescBins * h->cap_feats));
+      PP_TRY(GrowBeside(h->blocks, &h->bytes, regrow, kDescBins * h->cap_feats));
+      PP_TRY(GrowBeside(h->blocks, &h->window, regrow, h->cap_feats));
+    }
+    PP_TRY(Upload(h->feats, feats.data(), F, s));
+    hipLaunchKernelGGL(k_sift_describe, grid((int64_t)F, kSiftLaneBlock), dim3(kSiftLaneBlock), 0, s, (int32_t)F, (const SiftFeature*)h->feats, (const Keypoint*)h->keys,
+                       (const float*)grad, w, hgt, g.s_min, g.s_max, xper, (const double*)h->expn, (int)opt.normalization, h->raw, h->bytes, h->window);
+    const size_t at = R.raw.size();
+    R.raw.resize(at + kDescBins * F);
+    R.descriptors.resize(at + kDescBins * F);
+    window.resize(F);
+    PP_TRY(Download(R.raw.data() + at, (const float*)h->raw, kDescBins * F, s));
+    PP_TRY(Download(R.descriptors.data() + at, (const uint8_t*)h->bytes, kDescBins * F, s));
+    PP_TRY(Download(window.data(), (const DescriptorWindow*)h->window, F, s));
+    PP_TRY(close_span(kDescribe));
+    for (const DescriptorWindow& win : window) { R.windows_cut += win.cut; R.descriptors_skipped += !win.computed; }
+  }
+  PP_HIP_TRY(hipGetLastError());
+  PP_TRY(timer.End());
+  PP_HIP_TRY(hipStreamSynchronize(s));
+  PP_TRY(timer.Add());
+
+  // ---- the host rule
+  R.cut = SelectLevels(R.levels, opt.max_num_features);
+  report->num_octaves = g.O;
+  report->num_levels = (int32_t)R.levels.size();
+  report->first_level_to_keep = R.cut.first_level_to_keep;
+  report->num_features_found = (int64_t)R.angles.size();
+  report->num_features = R.cut.num_features;
+  report->num_two_orientations = R.two_orientations;
+  report->num_windows_cut = R.windows_cut;
+  report->num_descriptors_skipped = R.descriptors_skipped;
+  for (size_t q = 0; q < R.octaves.size(); ++q) {
+    const OctaveCounts& c = R.octaves[q];
+    report->octave_width[q] = c.width; report->octave_height[q] = c.height;
+    report->octave_candidates[q] = c.num_candidates; report->octave_keypoints[q] = c.num_keypoints;
+    report->num_keypoints += c.num_keypoints; report->num_moved += c.moved;
+    report->num_rejected_peak += c.reject_peak; report->num_rejected_edge += c.reject_edge;
+    report->num_rejected_offset += c.reject_offset; report->num_rejected_bounds += c.reject_bounds;
+  }
+  for (int p = 0; p < 5; ++p) report->phase_ms[p] = options->phase_timings ? phase_ms[p] : 0.0;
+  report->device_ms = timer.ms;
+  h->geom = g;
+  h->octaves = std::move(octaves);
+  h->last_raw = std::move(R.raw);
+  h->last_octave_level = std::move(R.octave_level);
+  h->last_angles = std::move(R.angles);
+  h->extracted = true;
+  *num = R.cut.num_features;
+  report->total_ms = MsSince(t_begin);
+  PP_REQUIRE(capacity >= R.cut.num_features, "%s: capacity %lld for %lld features", where, (long long)capacity, (long long)R.cut.num_features);
+  const size_t first = (size_t)R.cut.first_feature, count = (size_t)R.cut.num_features;
+  if (count) std::memcpy(keypoints, R.keypoints.data() + 4 * first, 4 * count * sizeof(float));
+  if (count && descriptors) std::memcpy(descriptors, R.descriptors.data() + kDescBins * first, kDescBins * count);
+  report->total_ms = MsSince(t_begin);
+  return PP_OK;
+} PP_API_CATCH("pp_sift_extract")
+
+int pp_sift_extract_stage(pp_sift_extractor_handle h, int32_t kind, int32_t octave, int32_t level, float* out, int64_t capacity, int32_t* width,
+                          int32_t* height) try {
+  const char* where = "pp_sift_extract_stage";
+  PP_REQUIRE(h && out && width && height, "%s: null argument", where);
+  PP_REQUIRE(h->extracted, "%s: no extraction on this handle", where);
+  const Geometry& g = h->geom;
+  PP_REQUIRE(octave >= g.o_min && octave < g.o_min + g.O, "%s: octave %d", where, octave);
+  const SiftOctave& oc = h->octaves[(size_t)(octave - g.o_min)];
+  const size_t lev = (size_t)oc.w * oc.h;
+  size_t offset = 0, count = lev;
+  if (kind == 0) {
+    PP_REQUIRE(level >= g.s_min && level <= g.s_max, "%s: Gaussian level %d", where, level);
+    offset = oc.gauss + (size_t)(level - g.s_min) * lev;
+  } else if (kind == 1) {
+    PP_REQUIRE(level >= g.s_min && level <= g.s_max - 1, "%s: DoG level %d", where, level);
+    offset = oc.dog + (size_t)(level - g.s_min) * lev;
+  } else {
+    PP_REQUIRE(kind == 2, "%s: kind %d", where, kind);
+    PP_REQUIRE(oc.has_grad && level >= g.s_min + 1 && level <= g.s_max - 2, "%s: gradient level %d", where, level);
+    offset = oc.grad + 2 * (size_t)(level - g.s_min - 1) * lev;
+    count = 2 * lev;
+  }
+  *width = oc.w; *height = oc.h;
+  PP_REQUIRE(capacity >= (int64_t)count, "%s: capacity %lld for %lld floats", where, (long long)capacity, (long long)count);
+  PP_HIP_TRY(hipSetDevice(h->device));
+  PP_TRY(Download(out, (const float*)(h->pyramid + offset), count, h->stream));
+  PP_HIP_TRY(hipStreamSynchronize(h->stream));
+  return PP_OK;
+} PP_API_CATCH("pp_sift_extract_stage")
+
+int pp_sift_extract_candidates(pp_sift_extractor_handle h, int32_t octave, int32_t* xys, int64_t capacity, int64_t* num) try {
+  const char* where = "pp_sift_extract_candidates";
+  PP_REQUIRE(h && num, "%s: null argument", where);
+  PP_REQUIRE(h->extracted, "%s: no extraction on this handle", where);
+  PP_REQUIRE(octave >= h->geom.o_min && octave < h->geom.o_min + h->geom.O, "%s: octave %d", where, octave);
+  const std::vector<int32_t>& c = h->octaves[(size_t)(octave - h->geom.o_min)].cand;
+  *num = (int64_t)(c.size() / 3);
+  PP_REQUIRE(xys || c.empty(), "%s: null argument", where);
+  PP_REQUIRE(capacity >= *num, "%s: capacity %lld for %lld candidates", where, (long long)capacity, (long long)*num);
+  if (!c.empty()) std::memcpy(xys, c.data(), c.size() * sizeof(int32_t));
+  return PP_OK;
+} PP_API_CATCH("pp_sift_extract_candidates")
+
+int pp_sift_extract_features(pp_sift_extractor_handle h, float* raw, int32_t* octave_level, double* angles, int64_t capacity, int64_t* num) try {
+  const char* where = "pp_sift_extract_features";
+  PP_REQUIRE(h && num, "%s: null argument", where);
+  PP_REQUIRE(h->extracted, "%s: no extraction on this handle", where);
+  const size_t n = h->last_angles.size();
+  *num = (int64_t)n;
+  PP_REQUIRE(capacity >= *num, "%s: capacity %lld for %lld features", where, (long long)capacity, (long long)*num);
+  if (n && raw) std::memcpy(raw, h->last_raw.data(), kDescBins * n * sizeof(float));
+  if (n && octave_level) std::memcpy(octave_level, h->last_octave_level.data(), 2 * n * sizeof(int32_t));
+  if (n && angles) std::memcpy(angles, h->last_angles.data(), n * sizeof(double));
+  return PP_OK;
+} PP_API_CATCH("pp_sift_extract_features")
+
+}  // extern "C"

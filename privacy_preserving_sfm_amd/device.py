@@ -1007,6 +1007,75 @@ class PairSelector(_Handle):
         return rep, self.get(want_sqdist=False)[0]
 
 
+def sift_extract_options(**kw):
+    return _capi.options(_capi.SiftExtractOptions, "pp_sift_extract_options_default", **kw)
+
+
+class SiftExtractor(_Handle):
+    """pp_sift_extractor_handle (K21): extract() is ExtractSiftFeaturesCPU for one grey image; the handle's workspace grows to the largest image seen
+    and keeps the pyramid of the last extraction for stage(), candidates() and features()."""
+    _destroy = "pp_sift_extractor_destroy"
+
+    def __init__(self, device=0):
+        super().__init__()
+        check(_capi.lib().pp_sift_extractor_create(int(device), C.byref(self._h)))
+        self.last_report = None
+
+    def extract(self, image, options=None, want_descriptors=True, capacity=None):
+        """image [H, W] uint8 -> (keypoints [N, 4] float32 (x, y, scale, orientation), descriptors [N, 128] uint8 in UBC order or None, report).
+        capacity None: the call is repeated with the reported need when the first guess was too small."""
+        im = np.asarray(image)
+        if im.dtype != np.uint8 or im.ndim != 2:
+            raise ValueError("the image is an [H, W] uint8 array")
+        im = np.ascontiguousarray(im)
+        o = options or sift_extract_options()
+        guess = min(2 * int(o.max_num_features), 1 << 16) if capacity is None else int(capacity)
+        for cap in (guess, None):
+            num, rep = C.c_int64(), _capi.SiftExtractReport()
+            if cap is None:
+                cap = int(self.last_report.num_features)
+            kp = np.zeros((max(cap, 1), 4), dtype=np.float32)
+            desc = np.zeros((max(cap, 1), 128), dtype=np.uint8) if want_descriptors else None
+            rc = _capi.lib().pp_sift_extract(self._h, C.byref(o), int(im.shape[1]), int(im.shape[0]), ptr(im, _capi.c_u8p), C.byref(rep), cap,
+                                             ptr(kp, C.POINTER(C.c_float)), ptr(desc, _capi.c_u8p), C.byref(num))
+            self.last_report = rep
+            if rc == 0 or capacity is not None or num.value <= cap:
+                break
+        check(rc)
+        n = num.value
+        return kp[:n].copy(), None if desc is None else desc[:n].copy(), rep
+
+    def stage(self, kind, octave, level):
+        """one level of the last extraction's pyramid: kind _capi.SIFT_STAGE_* -> [h, w] float32 ([h, w, 2] modulus / angle for the gradient)"""
+        w, h = C.c_int32(), C.c_int32()
+        per = 2 if kind == _capi.SIFT_STAGE_GRADIENT else 1
+        out = np.zeros(1, dtype=np.float32)
+        rc = _capi.lib().pp_sift_extract_stage(self._h, int(kind), int(octave), int(level), ptr(out, C.POINTER(C.c_float)), 0, C.byref(w), C.byref(h))
+        if w.value <= 0 or h.value <= 0:
+            check(rc)
+        out = np.zeros(per * w.value * h.value, dtype=np.float32)
+        check(_capi.lib().pp_sift_extract_stage(self._h, int(kind), int(octave), int(level), ptr(out, C.POINTER(C.c_float)), out.size, C.byref(w), C.byref(h)))
+        return out.reshape(h.value, w.value, 2) if per == 2 else out.reshape(h.value, w.value)
+
+    def candidates(self, octave):
+        """the unrefined extrema of one octave in scan order -> [M, 3] int32 (x, y, level)"""
+        num = C.c_int64()
+        _capi.lib().pp_sift_extract_candidates(self._h, int(octave), None, 0, C.byref(num))
+        out = np.zeros((max(num.value, 1), 3), dtype=np.int32)
+        check(_capi.lib().pp_sift_extract_candidates(self._h, int(octave), ptr(out, _capi.c_ip), num.value, C.byref(num)))
+        return out[:num.value]
+
+    def features(self):
+        """every feature of the last extraction before the max_num_features cut -> (raw [F, 128] float32 in VLFeat's order before the last
+        normalisation, octave_level [F, 2] int32, angles [F] float64); the kept features are the last `report.num_features` rows"""
+        num = C.c_int64()
+        _capi.lib().pp_sift_extract_features(self._h, None, None, None, 0, C.byref(num))
+        n = num.value
+        raw, ol, ang = np.zeros((max(n, 1), 128), dtype=np.float32), np.zeros((max(n, 1), 2), dtype=np.int32), np.zeros(max(n, 1))
+        check(_capi.lib().pp_sift_extract_features(self._h, ptr(raw, C.POINTER(C.c_float)), ptr(ol, _capi.c_ip), dp(ang), n, C.byref(num)))
+        return raw[:n], ol[:n], ang[:n]
+
+
 def line_features_options(**kw):
     return _capi.options(_capi.LineFeaturesOptions, "pp_line_features_options_default", **kw)
 

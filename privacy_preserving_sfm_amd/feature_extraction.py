@@ -3,7 +3,9 @@
 `FeatureKeypoint` (feature/types.cc:38-105), `ScaleKeypoints` / `MaskKeypoints` (feature/extraction.cc:49-85), `LoadSiftFeaturesFromTextFile`
 (feature/sift.cc:902-955) and the line generation of LineFeatureWriterThread::Run (feature/extraction.cc:437-505): every keypoint is undistorted with its
 image's camera and gets a line through it - gravity-aligned for a share `aligned_line_ratio` of the features of an image that has a gravity direction,
-of random direction otherwise - divided by the norm of its first two components.  The SIFT detector and descriptor stay outside the package.
+of random direction otherwise - divided by the norm of its first two components.  The keypoints and descriptors themselves come from
+`ExtractSiftFeatures` (ExtractSiftFeaturesCPU, feature/sift.cc:399-573, on the device: K21, csrc/sift_extract.hip), and `extract_features_to_lines`
+runs both steps over a list of images.
 
 `generate_line_features` is the numpy host mirror (ImageToWorld with the reference's Newton iteration restated literally, the counter-based generator
 of csrc/line_features_replay.hpp restated in uint64 arithmetic), `generate_line_features_on_device` the same through pp_line_features_from_keypoints
@@ -404,3 +406,82 @@ def generate_line_features_on_device(images, cameras, keypoints, aligned_line_ra
             im.lines = [FeatureLine(line[i], bool(aligned[i]), kInvalidPoint3DId) for i in range(b - a)]
         rep["lines"][im.image_id], rep["aligned"][im.image_id], rep["dirs"][im.image_id] = line, aligned, out["dirs"][a:b]
     return rep
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+
+class SiftExtractionOptions:
+    """feature/sift.h:46-113 with its defaults.  num_threads, use_gpu, gpu_index and max_image_size are carried and not used (one image, one device, the
+    caller supplies the array at the size it wants); darkness_adaptivity is ignored as the reference's CPU path ignores it; estimate_affine_shape and
+    domain_size_pooling are refused."""
+    L1_ROOT, L2 = "L1_ROOT", "L2"
+    _FIELDS = dict(num_threads=-1, use_gpu=True, gpu_index="-1", max_image_size=3200, max_num_features=8192, first_octave=-1, num_octaves=4,
+                   octave_resolution=3, peak_threshold=None, edge_threshold=10.0, estimate_affine_shape=False, max_num_orientations=2, upright=False,
+                   darkness_adaptivity=False, domain_size_pooling=False, dsp_min_scale=1.0 / 6.0, dsp_max_scale=3.0, dsp_num_scales=10,
+                   normalization="L1_ROOT")
+
+    def __init__(self, **kw):
+        for k in kw:
+            if k not in self._FIELDS:
+                raise AttributeError(k)
+        for k, v in self._FIELDS.items():
+            setattr(self, k, kw.get(k, v))
+        if self.peak_threshold is None:
+            self.peak_threshold = 0.02 / self.octave_resolution if self.octave_resolution > 0 else 0.02 / 3      # (Check() refuses the resolution)
+
+    def Check(self):
+        """SiftExtractionOptions::Check (sift.cc:371-387)"""
+        ok = self.max_image_size > 0 and self.max_num_features > 0 and self.octave_resolution > 0 and self.peak_threshold > 0.0
+        ok = ok and self.edge_threshold > 0.0 and self.max_num_orientations > 0
+        if self.domain_size_pooling:
+            ok = ok and self.dsp_min_scale > 0 and self.dsp_max_scale >= self.dsp_min_scale and self.dsp_num_scales > 0
+        return bool(ok)
+
+    def device_options(self, phase_timings=False):
+        """-> pp_sift_extract_options"""
+        from .device import sift_extract_options
+        if self.estimate_affine_shape or self.domain_size_pooling:
+            raise ValueError("estimate_affine_shape and domain_size_pooling belong to the covariant extractor, which is absent")
+        if self.normalization not in (self.L1_ROOT, self.L2):
+            raise ValueError("normalization is L1_ROOT or L2")
+        return sift_extract_options(max_num_features=int(self.max_num_features), first_octave=int(self.first_octave), num_octaves=int(self.num_octaves),
+                                    octave_resolution=int(self.octave_resolution), peak_threshold=float(self.peak_threshold),
+                                    edge_threshold=float(self.edge_threshold), max_num_orientations=int(self.max_num_orientations),
+                                    upright=int(bool(self.upright)), normalization=_capi.SIFT_L2 if self.normalization == self.L2 else _capi.SIFT_L1_ROOT,
+                                    phase_timings=int(bool(phase_timings)))
+
+
+def ExtractSiftFeatures(image_uint8, options=None, device=0, extractor=None, as_arrays=False):
+    """ExtractSiftFeaturesCPU for one grey image on the device -> (FeatureKeypoints: a list of FeatureKeypoint, descriptors [N, 128] uint8 in UBC order).
+    as_arrays: the keypoints as the [N, 4] float32 array (x, y, scale, orientation) the device returns.  extractor: a device.SiftExtractor to reuse."""
+    from .device import SiftExtractor
+    options = options or SiftExtractionOptions()
+    if not options.Check():
+        raise ValueError("SiftExtractionOptions.Check() failed")
+    o = options.device_options()
+    ex = extractor or SiftExtractor(device=device)
+    try:
+        kp, desc, _ = ex.extract(image_uint8, o)
+    finally:
+        if extractor is None:
+            ex.close()
+    if as_arrays:
+        return kp, desc
+    return [FeatureKeypoint(r[0], r[1], r[2], r[3]) for r in kp], desc
+
+
+def extract_features_to_lines(images, cameras, bitmaps, options=None, aligned_line_ratio=DEFAULT_ALIGNED_LINE_RATIO, seed=0, device=0):
+    """Image arrays to what the matcher and the graph builder take.  images: bundle_adjustment.Image objects; cameras as for generate_line_features;
+    bitmaps: {image_id: [H, W] uint8}.  Per image ExtractSiftFeatures, then generate_line_features_on_device over all of them (it fills image.lines).
+    -> dict(keypoints {image_id: [N, 4] float32}, descriptors {image_id: [N, 128] uint8}, num_lines {image_id: N}, lines: the line report).
+    Line index = keypoint index = descriptor row."""
+    from .device import SiftExtractor
+    ex = SiftExtractor(device=device)
+    keypoints, descriptors = {}, {}
+    try:
+        for im in images:
+            keypoints[im.image_id], descriptors[im.image_id] = ExtractSiftFeatures(bitmaps[im.image_id], options, extractor=ex, as_arrays=True)
+    finally:
+        ex.close()
+    rep = generate_line_features_on_device(images, cameras, keypoints, aligned_line_ratio=aligned_line_ratio, seed=seed, device=device)
+    return dict(keypoints=keypoints, descriptors=descriptors, num_lines={k: len(v) for k, v in keypoints.items()}, lines=rep)
