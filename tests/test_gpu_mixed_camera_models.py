@@ -409,7 +409,8 @@ def test_filters_with_mixed_models_match_oracle(oracle, seed, max_err, min_ang, 
 def test_triangulate_tracks_with_mixed_models_matches_oracle(oracle, residual_type, max_error, min_angle):
     """14 views on 7 cameras of 7 models (view v -> camera v % 7), 400 tracks: agreement shares and point tolerances of
     test_gpu_triangulation.test_triangulate_tracks_matches_oracle; its counts (800 decided, 300 clean of 1500 tracks) scaled by 400 / 1500 - the oracle alone
-    decides 339 / 335 and finds 289 / 292 clean ones here"""
+    decides 339 / 335 and finds 289 / 292 clean ones here.  A statistical comparison; every model alone and all eleven in one call are held exactly to a
+    50-digit reference in tests/test_gpu_triangulation_exact.py (the `models` set)"""
     from privacy_preserving_sfm_amd.device import triangulate_tracks, triangulation_options
     sc = mm.mix_track_scene(synthetic.make_track_scene(14, 400, seed=3 + residual_type), TRACK_MODELS)
     opt = triangulation_options(min_tri_angle=min_angle, residual_type=residual_type, max_error=max_error, confidence=0.9999, min_inlier_ratio=0.02)
