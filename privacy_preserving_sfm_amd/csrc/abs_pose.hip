@@ -1,7 +1,8 @@
 // K4 / K5 — absolute pose from six line/point pairs: batched minimal solver, batched scoring, and
-// the RANSAC driver that keeps the reference's sequential semantics.
+// the device backend of the RANSAC replay that keeps the reference's sequential semantics.
 //
-//   RANSAC<P6LEstimator>::Estimate              reference src/optim/ransac.h:178-278
+//   RANSAC<P6LEstimator>::Estimate              reference src/optim/ransac.h:178-278: every rule of it is PoseRansacReplay (ransac_host.hpp, host only);
+//                                               pp_pose_ransac below solves and scores the chunks it draws
 //   P6LEstimator::Residuals -> ComputeSquaredLineReprojectionError   src/estimators/utils.cc:40-89
 //   InlierSupportMeasurer::{Evaluate, Compare}  src/optim/support_measurement.cc:36-60
 //   EstimateAbsolutePoseFromLines               src/estimators/pose.cc:52-94 (host mirror: ppsfm/pose.hpp)
@@ -16,7 +17,6 @@
 // FMA contraction disabled, so `r <= max_residual` decides bit-identically to the CPU reference.
 #include <algorithm>
 #include <cstdlib>
-#include <chrono>
 #include <cfloat>
 #include <cstring>
 #include <vector>
@@ -52,7 +52,7 @@ struct pp_pose_impl : ppsfm::DeviceHandle {
   int64_t cap_pin = 0;
   uint32_t *pin_samples = nullptr, *pin_inl = nullptr;
   int32_t* pin_nm = nullptr;
-  double *pin_sm = nullptr, *pin_mdl = nullptr;
+  double* pin_mdl = nullptr;
   int64_t last_hyp = 0;     // hypotheses of the last pp_pose_hypotheses call (their scores are still on the device)
 };
 
@@ -445,12 +445,11 @@ static int EnsureCapacity(pp_pose_impl* h, int64_t hyp) {
 static int EnsurePinned(pp_pose_impl* h, int64_t hyp) {
   if (hyp <= h->cap_pin) return PP_OK;
   DeviceBlocks& B = h->blocks;
-  B.Free(&h->pin_samples); B.Free(&h->pin_inl); B.Free(&h->pin_nm); B.Free(&h->pin_sm); B.Free(&h->pin_mdl);
+  B.Free(&h->pin_samples); B.Free(&h->pin_inl); B.Free(&h->pin_nm); B.Free(&h->pin_mdl);
   h->cap_pin = 0;
   PP_TRY(B.AllocPinned(reinterpret_cast<void**>(&h->pin_samples), sizeof(uint32_t) * 6 * (size_t)hyp));
   PP_TRY(B.AllocPinned(reinterpret_cast<void**>(&h->pin_inl), sizeof(uint32_t) * 8 * (size_t)hyp));
   PP_TRY(B.AllocPinned(reinterpret_cast<void**>(&h->pin_nm), sizeof(int32_t) * (size_t)hyp));
-  PP_TRY(B.AllocPinned(reinterpret_cast<void**>(&h->pin_sm), sizeof(double) * 8 * (size_t)hyp));
   PP_TRY(B.AllocPinned(reinterpret_cast<void**>(&h->pin_mdl), sizeof(double) * 96 * (size_t)hyp));
   h->cap_pin = hyp;
   return PP_OK;
@@ -540,11 +539,11 @@ int pp_pose_residuals(pp_pose_handle h, int32_t num_models, const double* models
     PP_TRY(h->blocks.Alloc(&h->residuals, (size_t)need));
     h->cap_res = need;
   }
-  int rc = EnsureCapacity(h, CeilDiv(num_models, 8) + 1); if (rc) return rc;
-  rc = Upload(h->models, models, (size_t)num_models * 12, h->stream); if (rc) return rc;
+  PP_TRY(EnsureCapacity(h, CeilDiv(num_models, 8) + 1));
+  PP_TRY(Upload(h->models, models, (size_t)num_models * 12, h->stream));
   hipLaunchKernelGGL(k_residuals, dim3(CeilDiv(h->n, 256), num_models), dim3(256), 0, h->stream, Corr(h), num_models, h->models, h->residuals);
   PP_HIP_TRY(hipGetLastError());
-  rc = Download(residuals_out, h->residuals, (size_t)need, h->stream); if (rc) return rc;
+  PP_TRY(Download(residuals_out, h->residuals, (size_t)need, h->stream));
   PP_HIP_TRY(hipStreamSynchronize(h->stream));
   return PP_OK;
 } PP_API_CATCH("pp_pose_residuals")
@@ -554,8 +553,8 @@ static int ScoreImpl(pp_pose_handle h, int32_t num_models, const double* models,
   PP_REQUIRE(h && num_models >= 0 && (num_models == 0 || (models && num_inliers && residual_sum)), "pp_pose_score: bad argument");
   if (num_models == 0) return PP_OK;
   PP_HIP_TRY(hipSetDevice(h->device));
-  int rc = EnsureCapacity(h, CeilDiv(num_models, 8) + 1); if (rc) return rc;
-  rc = Upload(h->models, models, (size_t)num_models * 12, h->stream); if (rc) return rc;
+  PP_TRY(EnsureCapacity(h, CeilDiv(num_models, 8) + 1));
+  PP_TRY(Upload(h->models, models, (size_t)num_models * 12, h->stream));
   if (sequential)
     hipLaunchKernelGGL(k_support_sequential, dim3(CeilDiv(num_models, 4)), dim3(256), 0, h->stream, Corr(h), num_models, h->models, max_residual, h->inliers, h->sums);
   else {   // the RANSAC scoring kernel itself, on the identity list
@@ -563,8 +562,8 @@ static int ScoreImpl(pp_pose_handle h, int32_t num_models, const double* models,
     LaunchScoreFlat(h, num_models, max_residual);
   }
   PP_HIP_TRY(hipGetLastError());
-  rc = Download(num_inliers, h->inliers, (size_t)num_models, h->stream); if (rc) return rc;
-  rc = Download(residual_sum, h->sums, (size_t)num_models, h->stream); if (rc) return rc;
+  PP_TRY(Download(num_inliers, h->inliers, (size_t)num_models, h->stream));
+  PP_TRY(Download(residual_sum, h->sums, (size_t)num_models, h->stream));
   PP_HIP_TRY(hipStreamSynchronize(h->stream));
   return PP_OK;
 }
@@ -583,13 +582,13 @@ int pp_pose_p6l_batch(pp_pose_handle h, int64_t num_hyp, const uint32_t* samples
   if (num_hyp == 0) return PP_OK;
   for (int64_t i = 0; i < 6 * num_hyp; ++i) PP_REQUIRE(samples[i] < (uint32_t)h->n, "pp_pose_p6l_batch: sample index out of range");
   PP_HIP_TRY(hipSetDevice(h->device));
-  int rc = EnsureCapacity(h, num_hyp); if (rc) return rc;
-  rc = Upload(h->samples, samples, (size_t)num_hyp * 6, h->stream); if (rc) return rc;
+  PP_TRY(EnsureCapacity(h, num_hyp));
+  PP_TRY(Upload(h->samples, samples, (size_t)num_hyp * 6, h->stream));
   PP_HIP_TRY(hipMemsetAsync(h->models, 0, sizeof(double) * 96 * (size_t)num_hyp, h->stream));
   hipLaunchKernelGGL(k_p6l, dim3(CeilDiv(num_hyp, 64)), dim3(64), 0, h->stream, Corr(h), h->aligned, num_hyp, h->samples, h->models, h->num_models);
   PP_HIP_TRY(hipGetLastError());
-  rc = Download(models_out, h->models, (size_t)num_hyp * 96, h->stream); if (rc) return rc;
-  rc = Download(num_models_out, h->num_models, (size_t)num_hyp, h->stream); if (rc) return rc;
+  PP_TRY(Download(models_out, h->models, (size_t)num_hyp * 96, h->stream));
+  PP_TRY(Download(num_models_out, h->num_models, (size_t)num_hyp, h->stream));
   PP_HIP_TRY(hipStreamSynchronize(h->stream));
   return PP_OK;
 } PP_API_CATCH("pp_pose_p6l_batch")
@@ -617,31 +616,33 @@ int pp_pose_hypotheses(pp_pose_handle h, int64_t num_hyp, const uint32_t* sample
   PP_REQUIRE(h && rep && num_hyp > 0, "pp_pose_hypotheses: bad argument");
   PP_REQUIRE(h->n >= 6, "pp_pose_hypotheses: fewer than 6 correspondences");
   PP_HIP_TRY(hipSetDevice(h->device));
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = Clock::now();
+  StreamTimer timer(*h);
   std::memset(rep, 0, sizeof(*rep));
-  int rc = EnsureCapacity(h, num_hyp); if (rc) return rc;
+  PP_TRY(EnsureCapacity(h, num_hyp));
   if (samples) {
-    rc = Upload(h->samples, samples, (size_t)num_hyp * 6, h->stream); if (rc) return rc;
+    PP_TRY(Upload(h->samples, samples, (size_t)num_hyp * 6, h->stream));
   } else {
     if ((int64_t)h->h_samples.size() != num_hyp * 6 || h->h_samples_seed != seed) {
       h->h_samples.resize((size_t)num_hyp * 6);
       h->h_samples_seed = seed;
       RandomSampler sampler(6, seed); sampler.Initialize((uint32_t)h->n);
-      for (int64_t i = 0; i < num_hyp; ++i) sampler.Sample(h->h_samples.data() + 6 * i);
+      sampler.Fill((uint64_t)num_hyp, h->h_samples.data());
     }
-    rc = Upload(h->samples, h->h_samples.data(), (size_t)num_hyp * 6, h->stream); if (rc) return rc;
+    PP_TRY(Upload(h->samples, h->h_samples.data(), (size_t)num_hyp * 6, h->stream));
   }
-  PP_HIP_TRY(hipEventRecord(h->ev0, h->stream));
-  rc = SolveAndScore(h, num_hyp, max_residual); if (rc) return rc;
+  PP_TRY(timer.Begin());
+  PP_TRY(SolveAndScore(h, num_hyp, max_residual));
   const int nblk = 1024;
   hipLaunchKernelGGL(k_best_candidates, dim3(nblk), dim3(256), 0, h->stream, num_hyp, h->num_models, h->inliers, h->sums, h->best_key);
   PP_HIP_TRY(hipGetLastError());
-  PP_HIP_TRY(hipEventRecord(h->ev1, h->stream));
+  PP_TRY(timer.End());
   std::vector<unsigned long long> cand(3 * nblk);
-  rc = Download(cand.data(), h->best_key, cand.size(), h->stream); if (rc) return rc;
+  PP_TRY(Download(cand.data(), h->best_key, cand.size(), h->stream));
   std::vector<int32_t> nm((size_t)num_hyp);
-  rc = Download(nm.data(), h->num_models, (size_t)num_hyp, h->stream); if (rc) return rc;
+  PP_TRY(Download(nm.data(), h->num_models, (size_t)num_hyp, h->stream));
   PP_HIP_TRY(hipStreamSynchronize(h->stream));
+  PP_TRY(timer.Add());
   uint32_t bi = 0; double bs = DBL_MAX; unsigned long long bidx = ~0ull;
   for (int b = 0; b < nblk; ++b) {
     const uint32_t c = (uint32_t)cand[3 * b]; double s; std::memcpy(&s, &cand[3 * b + 1], 8); const unsigned long long idx = cand[3 * b + 2];
@@ -657,9 +658,8 @@ int pp_pose_hypotheses(pp_pose_handle h, int64_t num_hyp, const uint32_t* sample
     rep->best_trial = (int64_t)(bidx / 8); rep->best_model_index = (int32_t)(bidx % 8);
     PP_HIP_TRY(hipMemcpy(rep->model, h->models + bidx * 12, sizeof(double) * 12, hipMemcpyDeviceToHost));
   }
-  float ms = 0; PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  rep->device_time_s = ms * 1e-3;
-  rep->total_time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  rep->device_time_s = timer.ms * 1e-3;
+  rep->total_time_s = MsSince(t0) * 1e-3;
   return PP_OK;
 } PP_API_CATCH("pp_pose_hypotheses")
 
@@ -668,172 +668,66 @@ int pp_pose_last_scores(pp_pose_handle h, int64_t num_hyp, int32_t* num_models, 
   PP_REQUIRE(num_hyp <= h->last_hyp, "pp_pose_last_scores: the last pp_pose_hypotheses call scored %lld hypotheses, %lld asked for",
              (long long)h->last_hyp, (long long)num_hyp);
   PP_HIP_TRY(hipSetDevice(h->device));
-  int rc;
-  if (num_models && (rc = Download(num_models, h->num_models, (size_t)num_hyp, h->stream))) return rc;
-  if (num_inliers && (rc = Download(num_inliers, h->inliers, (size_t)num_hyp * 8, h->stream))) return rc;
-  if (residual_sum && (rc = Download(residual_sum, h->sums, (size_t)num_hyp * 8, h->stream))) return rc;
+  if (num_models) PP_TRY(Download(num_models, h->num_models, (size_t)num_hyp, h->stream));
+  if (num_inliers) PP_TRY(Download(num_inliers, h->inliers, (size_t)num_hyp * 8, h->stream));
+  if (residual_sum) PP_TRY(Download(residual_sum, h->sums, (size_t)num_hyp * 8, h->stream));
   PP_HIP_TRY(hipStreamSynchronize(h->stream));
   return PP_OK;
 } PP_API_CATCH("pp_pose_last_scores")
 
+// The device backend of PoseRansacReplay (ransac_host.hpp), which owns every rule of optim/ransac.h:143-278: per chunk K5 + K4 over the drawn samples,
+// then the sequential-order sums of the models the replay names, in one launch and one read-back (instead of a round trip per tie).
 int pp_pose_ransac(pp_pose_handle h, const pp_ransac_options* o, pp_ransac_report* rep, uint8_t* inlier_mask) try {
   PP_REQUIRE(h && o && rep, "pp_pose_ransac: null argument");
   // RANSACOptions::Check (optim/ransac.h:68-75)
   PP_REQUIRE(o->max_error > 0 && o->min_inlier_ratio >= 0 && o->min_inlier_ratio <= 1 && o->confidence >= 0 && o->confidence <= 1 &&
              o->min_num_trials <= o->max_num_trials, "pp_pose_ransac: RANSACOptions::Check failed");
   PP_HIP_TRY(hipSetDevice(h->device));
-  const auto t0 = std::chrono::steady_clock::now();
-  std::memset(rep, 0, sizeof(*rep));
-  rep->best_trial = -1; rep->best_model_index = -1;
-  rep->residual_sum = DBL_MAX;  // InlierSupportMeasurer::Support default (support_measurement.h:44-50)
+  const auto t0 = Clock::now();
+  StreamTimer timer(*h);
   const int n = h->n;
+  PoseRansacReplay replay(*o, n);
+  *rep = replay.Finish();      // the preset: what an error return leaves behind
   if (inlier_mask && n > 0) std::memset(inlier_mask, 0, (size_t)n);
-  const int kMin = 6;
-  // ctor: a-priori cap of max_num_trials (optim/ransac.h:149-155)
-  uint64_t max_num_trials = o->max_num_trials;
-  {
-    const uint64_t kNumSamples = 100000;
-    const uint64_t dyn = ComputeNumTrials((uint64_t)(o->min_inlier_ratio * kNumSamples), kNumSamples, o->confidence,
-                                          o->dyn_num_trials_multiplier, kMin);
-    max_num_trials = std::min(max_num_trials, dyn);
-  }
-  if (n < kMin) { rep->total_time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); return PP_OK; }
-
   const double max_residual = o->max_error * o->max_error;
-  RandomSampler sampler(kMin, o->seed);
-  sampler.Initialize((uint32_t)n);
-  uint64_t dyn_max_num_trials = max_num_trials;
-  // best support so far; the exact (sequential-order) residual sum is computed lazily, only when a
-  // comparison actually needs it (a tie in num_inliers, or the final report)
-  uint64_t best_inl = 0; double best_sum = DBL_MAX; bool best_sum_exact = true; bool have_best = false;
-  double best_model[12] = {0};
-  bool abort = false;
-  uint64_t trial = 0;
-  uint32_t chunk = o->chunk_trials ? o->chunk_trials : 1024;
-  uint32_t* hs = nullptr; int32_t* nm = nullptr; uint32_t* inl = nullptr; double* sm = nullptr; double* mdl = nullptr;   // pinned mirrors of a chunk
-  std::vector<size_t> cand; std::vector<double> cand_models, cand_sums, exact_of;
-  double dev_s = 0;
-
-  auto exact_support = [&](const double* model, uint32_t* c, double* s) -> int {
-    int rc = Upload(h->models, model, 12, h->stream); if (rc) return rc;
-    hipLaunchKernelGGL(k_support_sequential, dim3(1), dim3(256), 0, h->stream, Corr(h), 1, h->models, max_residual, h->inliers, h->sums);
-    PP_HIP_TRY(hipGetLastError());
-    rc = Download(c, h->inliers, 1, h->stream); if (rc) return rc;
-    rc = Download(s, h->sums, 1, h->stream); if (rc) return rc;
+  std::vector<size_t> slots;
+  std::vector<double> slot_models, slot_sums;
+  while (!replay.Done()) {
+    PP_TRY(EnsurePinned(h, (int64_t)replay.MaxWidth()));
+    const uint64_t want = replay.Draw(h->pin_samples);
+    PP_TRY(EnsureCapacity(h, (int64_t)std::max<uint64_t>(want, 64)));
+    PP_TRY(Upload(h->samples, h->pin_samples, want * 6, h->stream));
+    PP_TRY(timer.Begin());
+    PP_TRY(SolveAndScore(h, (int64_t)want, max_residual));
+    PP_TRY(timer.End());
+    PP_TRY(Download(h->pin_nm, h->num_models, want, h->stream));
+    PP_TRY(Download(h->pin_inl, h->inliers, want * 8, h->stream));
+    PP_TRY(Download(h->pin_mdl, h->models, want * 96, h->stream));
     PP_HIP_TRY(hipStreamSynchronize(h->stream));
-    return PP_OK;
-  };
-
-  while (trial < max_num_trials && !abort) {
-    // speculate: never beyond the static cap; shrink towards the dynamic bound once it is known
-    uint64_t want = std::min<uint64_t>(chunk, max_num_trials - trial);
-    if (dyn_max_num_trials < max_num_trials) {
-      const uint64_t floor_trials = std::max<uint64_t>(dyn_max_num_trials, o->min_num_trials);
-      if (floor_trials > trial) want = std::min<uint64_t>(want, floor_trials - trial + 1);
-      else want = std::min<uint64_t>(want, 64);
+    PP_TRY(timer.Add());
+    const PoseChunk chunk{h->pin_nm, h->pin_inl, h->pin_mdl};
+    replay.Candidates(want, chunk, &slots);
+    const size_t K = slots.size();
+    slot_models.resize(K * 12); slot_sums.resize(K);
+    for (size_t k = 0; k < K; ++k) std::memcpy(&slot_models[k * 12], h->pin_mdl + slots[k] * 12, sizeof(double) * 12);
+    if (K > 0) {
+      PP_TRY(Upload(h->models, slot_models.data(), K * 12, h->stream));
+      hipLaunchKernelGGL(k_support_sequential, dim3(CeilDiv((int64_t)K, 4)), dim3(256), 0, h->stream, Corr(h), (int)K, h->models, max_residual, h->inliers, h->sums);
+      PP_HIP_TRY(hipGetLastError());
+      PP_TRY(Download(slot_sums.data(), h->sums, K, h->stream));
+      PP_HIP_TRY(hipStreamSynchronize(h->stream));
     }
-    want = std::max<uint64_t>(want, 1);
-    int rc = EnsureCapacity(h, (int64_t)std::max<uint64_t>(want, 64)); if (rc) return rc;
-    rc = EnsurePinned(h, (int64_t)std::max<uint64_t>(want, chunk)); if (rc) return rc;
-    hs = h->pin_samples; nm = h->pin_nm; inl = h->pin_inl; sm = h->pin_sm; mdl = h->pin_mdl;
-    for (uint64_t i = 0; i < want; ++i) sampler.Sample(hs + 6 * i);
-    rc = Upload(h->samples, hs, want * 6, h->stream); if (rc) return rc;
-    PP_HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    rc = SolveAndScore(h, (int64_t)want, max_residual); if (rc) return rc;
-    PP_HIP_TRY(hipEventRecord(h->ev1, h->stream));
-    rc = Download(nm, h->num_models, want, h->stream); if (rc) return rc;
-    rc = Download(inl, h->inliers, want * 8, h->stream); if (rc) return rc;
-    rc = Download(sm, h->sums, want * 8, h->stream); if (rc) return rc;
-    rc = Download(mdl, h->models, want * 96, h->stream); if (rc) return rc;
-    PP_HIP_TRY(hipStreamSynchronize(h->stream));
-    float ms = 0; PP_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1)); dev_s += ms * 1e-3;
-    rep->hypotheses_evaluated += want;
-
-    // The exact (sequential-order) residual sums the replay can ask for, in ONE batch: a model can only become the best or
-    // tie with it if its inlier count reaches the running maximum of the counts before it, and that maximum follows from
-    // the counts alone.  (One launch + one read-back per chunk instead of a round trip per tie.)
-    exact_of.assign(want * 8, 0.0);
-    {
-      cand.clear(); cand_models.clear();
-      const bool carry = have_best && !best_sum_exact;
-      if (carry) cand_models.insert(cand_models.end(), best_model, best_model + 12);
-      uint64_t run = have_best ? best_inl : 0; bool hb = have_best;
-      for (uint64_t i = 0; i < want; ++i)
-        for (int m = 0; m < nm[i]; ++m) {
-          const uint64_t c = inl[i * 8 + m];
-          if (!hb || c >= run) {
-            cand.push_back(i * 8 + m);
-            cand_models.insert(cand_models.end(), mdl + (i * 8 + m) * 12, mdl + (i * 8 + m) * 12 + 12);
-            if (!hb || c > run) run = c;
-            hb = true;
-          }
-        }
-      const size_t K = cand_models.size() / 12;
-      if (K > 0) {
-        rc = Upload(h->models, cand_models.data(), cand_models.size(), h->stream); if (rc) return rc;
-        hipLaunchKernelGGL(k_support_sequential, dim3(CeilDiv((int64_t)K, 4)), dim3(256), 0, h->stream, Corr(h), (int)K, h->models, max_residual, h->inliers, h->sums);
-        PP_HIP_TRY(hipGetLastError());
-        cand_sums.resize(K);
-        rc = Download(cand_sums.data(), h->sums, K, h->stream); if (rc) return rc;
-        PP_HIP_TRY(hipStreamSynchronize(h->stream));
-        size_t k0 = 0;
-        if (carry) { best_sum = cand_sums[0]; best_sum_exact = true; k0 = 1; }
-        for (size_t k = 0; k < cand.size(); ++k) exact_of[cand[k]] = cand_sums[k0 + k];
-      }
-    }
-    // replay of optim/ransac.h:213-249 in trial order
-    for (uint64_t i = 0; i < want; ++i, ++trial) {
-      if (trial >= max_num_trials) break;
-      if (abort) break;
-      const int nmod = nm[i];
-      for (int m = 0; m < nmod; ++m) {
-        rep->models_scored += 1;
-        const uint64_t c = inl[i * 8 + m];
-        bool better = false;
-        if (!have_best) {
-          // Compare(support, default Support{0, DBL_MAX}): more inliers, or 0 inliers with sum 0 < DBL_MAX
-          better = true;
-        } else if (c > best_inl) {
-          better = true;
-        } else if (c == best_inl) {
-          // tie on the count: the reference compares the SEQUENTIAL residual sums
-          uint32_t ce;
-          if (!best_sum_exact) { rc = exact_support(best_model, &ce, &best_sum); if (rc) return rc; best_sum_exact = true; }   // (not reached: batch above)
-          const double se = exact_of[i * 8 + m];
-          if (se < best_sum) better = true;
-        }
-        if (better) {
-          have_best = true; best_inl = c;
-          best_sum = exact_of[i * 8 + m]; best_sum_exact = true;
-          std::memcpy(best_model, mdl + (i * 8 + m) * 12, sizeof(best_model));
-          rep->best_trial = (int64_t)trial; rep->best_model_index = m;
-          dyn_max_num_trials = ComputeNumTrials(best_inl, (uint64_t)n, o->confidence, o->dyn_num_trials_multiplier, kMin);
-        }
-        if (trial >= dyn_max_num_trials && trial >= o->min_num_trials) { abort = true; break; }
-      }
-    }
+    replay.Consume(want, chunk, slots, slot_sums.data());
   }
-  // num_trials bookkeeping of the reference loop (optim/ransac.h:213-218): an abort raised in trial t
-  // ends the run with num_trials = t + 2 (for-increment, then the `if (abort) num_trials += 1`), or
-  // t + 1 when t + 1 already equals max_num_trials
-  // (after an abort in trial t the replay loop above leaves `trial` == t + 1)
-  rep->num_trials = trial;
-  if (abort && trial < max_num_trials) rep->num_trials = trial + 1;
-
-  if (have_best && !best_sum_exact) { uint32_t ce; int rc = exact_support(best_model, &ce, &best_sum); if (rc) return rc; best_inl = ce; }
-  rep->num_inliers = best_inl; rep->residual_sum = have_best ? best_sum : DBL_MAX;
-  std::memcpy(rep->model, best_model, sizeof(best_model));
-  rep->device_time_s = dev_s;
-  if (best_inl >= (uint64_t)kMin) {
-    rep->success = 1;
-    if (inlier_mask) {
-      // final mask: residuals of the winner, `<=` threshold (optim/ransac.h:265-275)
-      std::vector<double> res((size_t)n);
-      int rc = pp_pose_residuals(h, 1, best_model, res.data()); if (rc) return rc;
-      for (int i = 0; i < n; ++i) inlier_mask[i] = res[i] <= max_residual ? 1 : 0;
-    }
+  *rep = replay.Finish();
+  rep->device_time_s = timer.ms * 1e-3;
+  if (rep->success && inlier_mask) {
+    // final mask: residuals of the winner, `<=` threshold (optim/ransac.h:265-275)
+    std::vector<double> res((size_t)n);
+    PP_TRY(pp_pose_residuals(h, 1, rep->model, res.data()));
+    for (int i = 0; i < n; ++i) inlier_mask[i] = res[i] <= max_residual ? 1 : 0;
   }
-  rep->total_time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  rep->total_time_s = MsSince(t0) * 1e-3;
   return PP_OK;
 } PP_API_CATCH("pp_pose_ransac")
 

@@ -217,6 +217,31 @@ def test_ransac_matches_sequential_oracle(oracle, seed, n, out):
     pp.close()
 
 
+def test_ransac_does_not_depend_on_the_chunk_width(oracle):
+    """chunk_trials only sets how far the device runs ahead of the replay (csrc/ransac_host.hpp): one trial per launch, a width that divides nothing,
+    64 and the default give the same report, model and mask bit for bit - and the oracle's, as test_ransac_matches_sequential_oracle asserts it"""
+    from privacy_preserving_sfm_amd.device import PoseProblem, ransac_options
+    seed, n, out = 1, 150, 0.2
+    sc = synthetic.make_ransac_scene(n, outlier_ratio=out, noise_px=0.3, seed=50 + seed, aligned_ratio=0.2)
+    pp = PoseProblem(sc["lines"], sc["points"], sc["aligned"])
+    kw = dict(min_inlier_ratio=0.25, confidence=0.99999, min_num_trials=100, max_num_trials=10000)      # the mapper's options
+    ref, ref_mask = oracle.p6l_ransac(sc["lines"], sc["points"], sc["aligned"], sc["max_error"], seed=seed, mult=3.0, **kw)
+    runs = []
+    for chunk in (1, 7, 64, 0):
+        rep, mask = pp.ransac(ransac_options(max_error=sc["max_error"], seed=seed, dyn_num_trials_multiplier=3.0, chunk_trials=chunk, **kw))
+        assert rep.success == ref.success == 1
+        assert rep.num_trials == ref.num_trials
+        assert rep.best_trial == ref.best_trial and rep.best_model_index == ref.best_model_idx
+        assert rep.num_inliers == ref.num_inliers
+        assert np.array_equal(mask, ref_mask)
+        assert np.allclose(np.array(rep.model), np.array(ref.model), rtol=1e-7, atol=1e-8)
+        assert abs(rep.residual_sum - ref.residual_sum) <= 1e-6 * ref.residual_sum
+        assert rep.hypotheses_evaluated >= rep.num_trials - 1
+        runs.append((rep.num_trials, rep.best_trial, rep.best_model_index, rep.num_inliers, rep.residual_sum, tuple(rep.model), mask.tobytes()))
+    assert all(r == runs[0] for r in runs[1:])
+    pp.close()
+
+
 def test_ransac_edge_cases():
     from privacy_preserving_sfm_amd.device import PoseProblem, ransac_options
     from privacy_preserving_sfm_amd._capi import PPError
@@ -231,6 +256,9 @@ def test_ransac_edge_cases():
     sc = synthetic.make_ransac_scene(50, seed=3, aligned_ratio=1.1)
     pp = PoseProblem(sc["lines"], sc["points"], sc["aligned"])
     rep, mask = pp.ransac(ransac_options(max_error=sc["max_error"], max_num_trials=200))
+    assert rep.success == 0 and rep.num_trials == 200 and rep.num_inliers == 0
+    # chunks that do not divide the cap stop exactly at it
+    rep, mask = pp.ransac(ransac_options(max_error=sc["max_error"], max_num_trials=200, chunk_trials=7))
     assert rep.success == 0 and rep.num_trials == 200 and rep.num_inliers == 0
     pp.close()
 
