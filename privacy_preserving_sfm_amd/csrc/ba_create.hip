@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "ba_impl.hpp"
+#include "image_ordering.hpp"
 #include "device_handle.hpp"
 #include "camera_models.hpp"
 using namespace ppsfm;
@@ -134,6 +135,7 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   // Variable intrinsics ride along: their columns follow the pose columns in the conjugate-gradient vectors, their part of the operator is applied
   // from the per-observation intrinsics Jacobians, their diagonal blocks (the preconditioner's) are assembled from the (k, k) pair lists alone.
   const bool iterative = h->iterative = st.iterative = ppsfm::WillIterate(d, sw.ba_linear_solver);
+  const int nv_private = iterative ? 0 : ppsfm::PrivateIntrinsicsColumns(d, st.cam_np.data(), sw.ba_intr_layout);
   st.sw = sw;
   PP_TRY(PoolStreamAcquire(&h->stream));
   PP_TRY(PoolEventAcquire(&h->ev0, true));
@@ -151,10 +153,10 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   if (lists_on_device) {
     PP_TRY(B.Alloc(&h->obs_pose, M)); PP_TRY(B.Put(&h->obs_point, d->obs_point, M, s)); PP_TRY(B.Alloc(&h->pose_const, C)); PP_TRY(B.Put(&h->point_const, st.point_const.data(), P, s));
     PP_TRY(B.Put(&h->pt_start, st.pt_start.data(), P + 1, s)); PP_TRY(B.Put(&h->pt_obs, st.pt_obs.data(), M, s));
-    if (ppsfm::OrderingReadsObservations(d, NI, sw)) {
+    if (ppsfm::OrderingReadsObservations(d, NI, st.cam_np.data(), sw)) {
       const auto tg = std::chrono::steady_clock::now();
       std::vector<uint8_t> fixed(C, 0);
-      if (d->pose_const && (iterative || ppsfm::PrivateIntrinsicsColumns(d, sw.ba_intr_layout) == 0)) std::memcpy(fixed.data(), d->pose_const, C);      // (as ChooseImageOrdering's fixed_image)
+      for (int c = 0; c < C; ++c) fixed[c] = ppsfm::ImageIsFixed(nv_private, d->pose_const, c) ? 1 : 0;
       PP_TRY(Upload(h->obs_pose, d->obs_pose, M, s)); PP_TRY(Upload(h->pose_const, fixed.data(), C, s));
       PP_TRY(CoVisibilityOnDevice(C, M, h->pt_start, h->pt_obs, h->obs_pose, h->obs_point, h->pose_const, h->point_const, s, &graph_bits));
       graph_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tg).count();
@@ -163,13 +165,13 @@ int pp_ba_create(const pp_ba_problem_desc* d, int device, pp_ba_handle* out) try
   }
 
   // the image order (ba_structure.hpp ApplyImageOrder says what it is) and the problem in it
-  ppsfm::ImageOrdering ord = ppsfm::ChooseImageOrdering(d, NI, sw, graph_bits.empty() ? nullptr : graph_bits.data());
+  ppsfm::ImageOrdering ord = ppsfm::ChooseImageOrdering(d, NI, st.cam_np.data(), sw, graph_bits.empty() ? nullptr : graph_bits.data());
   const double ordering_ms = graph_ms + ord.plan_ms;
   st.old_of_new.swap(ord.old_of_new); st.new_of_old.swap(ord.new_of_old);
   lap("image order");
   h->pose_old_of_new = st.old_of_new; h->pose_new_of_old = st.new_of_old;
   h->nnz_tiles_natural = ord.nnz_natural; h->nnz_tiles_ordered = ord.nnz_ordered;
-  ApplyImageOrder(&st, iterative ? 0 : ppsfm::PrivateIntrinsicsColumns(d, sw.ba_intr_layout));
+  ApplyImageOrder(&st, nv_private);
   h->spos_identity = st.nv_private == 0;
   h->intr_private_nv = st.nv_private;
   h->intr_wide_nv = st.intr_wide_nv;
@@ -258,30 +260,21 @@ int pp_ba_covisibility(const pp_ba_problem_desc* d, uint8_t* out) try {
   const int C = d->num_poses, P = d->num_points;
   const int64_t M = d->num_obs;
   PP_REQUIRE(C > 0 && P > 0 && M >= 0, "pp_ba_covisibility: empty problem");
+  std::vector<int32_t> cam_np;
   if (d->camera_const_mask) {      // (PrivateIntrinsicsColumns walks the cameras of the images: the same checks as pp_ba_create / pp_ba_plan_ordering)
     PP_REQUIRE(d->pose_camera && d->camera_model && d->num_cameras > 0, "pp_ba_covisibility: camera_const_mask without pose_camera / camera_model");
-    for (int k = 0; k < d->num_cameras; ++k) PP_REQUIRE(CameraNumParams(d->camera_model[k]) > 0, "pp_ba_covisibility: unknown camera model %d", d->camera_model[k]);
+    for (int k = 0; k < d->num_cameras; ++k) { cam_np.push_back(CameraNumParams(d->camera_model[k])); PP_REQUIRE(cam_np[k] > 0, "pp_ba_covisibility: unknown camera model %d", d->camera_model[k]); }
     for (int c = 0; c < C; ++c) PP_REQUIRE(d->pose_camera[c] >= 0 && d->pose_camera[c] < d->num_cameras, "pp_ba_covisibility: pose_camera[%d] out of range", c);
   }
   for (int64_t o = 0; o < M; ++o)
     PP_REQUIRE(d->obs_pose[o] >= 0 && d->obs_pose[o] < C && d->obs_point[o] >= 0 && d->obs_point[o] < P, "pp_ba_covisibility: observation %lld indexes out of range", (long long)o);
   std::memset(out, 0, (size_t)C * C);
-  std::vector<int32_t> ps, po;      // by point: the IMAGE of every observation
-  GroupByKey(M, P, [d](int64_t o) { return d->obs_point[o]; }, &ps, &po);
-  for (int32_t& o : po) o = d->obs_pose[o];
-  const uint8_t* fixed = (d->camera_const_mask && ppsfm::PrivateIntrinsicsColumns(d, ppsfm::ReadSwitches().ba_intr_layout) > 0) ? nullptr : d->pose_const;      // (intrinsics of its own beside the pose: every image has columns)
-  for (int p = 0; p < P; ++p) {
-    if (d->point_const && d->point_const[p]) continue;
-    for (int a = ps[p]; a < ps[p + 1]; ++a) {
-      const int ca = po[a];
-      if (fixed && fixed[ca]) continue;
-      for (int b = ps[p]; b < a; ++b) {
-        const int cb = po[b];
-        if (cb == ca || (fixed && fixed[cb])) continue;
-        out[(size_t)ca * C + cb] = 1; out[(size_t)cb * C + ca] = 1;
-      }
-    }
-  }
+  // (intrinsics of its own beside the pose: every image has columns)
+  const int nv_private = d->camera_const_mask ? ppsfm::PrivateIntrinsicsColumns(d, cam_np.data(), ppsfm::ReadSwitches().ba_intr_layout) : 0;
+  std::vector<uint64_t> bits((size_t)C * ppsfm::BitWords(C), 0);
+  ppsfm::FillFromObservations(d, nv_private, 0, bits.data());
+  const ppsfm::Adjacency adj = ppsfm::AdjacencyOf(C, bits.data());
+  for (int i = 0; i < C; ++i) for (int j : adj[i]) out[(size_t)i * C + j] = 1;
   return PP_OK;
 } PP_API_CATCH("pp_ba_covisibility")
 

@@ -71,18 +71,10 @@ __device__ __forceinline__ void BlockPartialSum(double v0, double* partials0, do
 // chain steps of the one-launch factorisation of a T x T tile map (closed under fill-in): the block columns on the longest dependency path when its
 // elimination tree has independent sub-trees (several chains, chol_plan.hpp "ChainRanges"), T otherwise; *chains (may be null): the number of chains
 int CholeskyChainSteps(int T, const uint8_t* nz, const Switches& sw, int* chains = nullptr);
-// the same from the chain plan alone (no task list is built or replayed): what a candidate image order costs (image_ordering.hip)
-int CholeskyPlanSteps(int T, const uint8_t* nz, const Switches& sw, int* chains = nullptr);
-// The image order pp_ba_create gives the reduced camera system (image_ordering.hip; host only): old_of_new empty = the caller's order.
-// nnz_*: non-zero tiles of the factor in the caller's order / in the order taken (-1: not computed); dense_exit: the co-visibility turned out too dense
-// for any order to pay and was not completed; chains / chain_steps: of the order taken (0: not planned); plan_ms: host time spent.
-struct ImageOrdering { std::vector<int32_t> old_of_new, new_of_old; int nnz_natural = -1, nnz_ordered = -1, chains = 0, chain_steps = 0; bool dense_exit = false; double plan_ms = 0; };
-ImageOrdering ChooseImageOrdering(const pp_ba_problem_desc* d, int NI, const Switches& sw, const uint64_t* graph_bits = nullptr);
-bool OrderingReadsObservations(const pp_ba_problem_desc* d, int NI, const Switches& sw);      // ChooseImageOrdering would walk the observations for the co-visibility graph
-// the reduced camera system is solved by conjugate gradients (ba_pcg.hip): the descriptor's linear solver unless PPSFM_BA_LINEAR_SOLVER overrides it -
-// ITERATIVE_SCHUR above PP_MAX_NUM_IMAGES_DIRECT_SOLVER images for AUTO (bundle_adjustment.cc:273-286)
-bool WillIterate(const pp_ba_problem_desc* d, LinearSolverSwitch sw);
-int CountVariableIntrinsics(const pp_ba_problem_desc* d);
+// The image order pp_ba_create gives the reduced camera system: image_ordering.hpp's ChooseImageOrdering with the winner verified through CholeskyChainSteps
+// (image_ordering.hip; host only).  cam_np: CameraNumParams of every camera's model.
+struct ImageOrdering;
+ImageOrdering ChooseImageOrdering(const pp_ba_problem_desc* d, int NI, const int32_t* cam_np, const Switches& sw, const uint64_t* graph_bits = nullptr);
 // the Schur pair lists on the device (pair_lists.hip)
 bool PairListsOnDeviceEligible(int C, int64_t M, PairListsSwitch sw);
 int BuildPairListsOnDevice(int C, int64_t M, const int32_t* d_pt_start, const int32_t* d_pt_obs, const int32_t* d_obs_pose, const int32_t* d_obs_point,
@@ -94,7 +86,6 @@ void BuildPairListsOnHost(int C, int P, int64_t M, const int32_t* pt_start, cons
 // the co-visibility graph of the variable images from the same arrays (any image numbering): bits[i * ceil(C / 64) + (j >> 6)] bit (j & 63), j < i
 int CoVisibilityOnDevice(int C, int64_t M, const int32_t* d_pt_start, const int32_t* d_pt_obs, const int32_t* d_obs_pose, const int32_t* d_obs_point,
                          const uint8_t* d_pose_const, const uint8_t* d_point_const, hipStream_t s, std::vector<uint64_t>* bits);
-int PrivateIntrinsicsColumns(const pp_ba_problem_desc* d, IntrLayout layout);      // n_v > 0: every image carries its own n_v variable intrinsics beside its pose columns (image_ordering.hip)
 }  // namespace ppsfm
 
 namespace ppsfm {

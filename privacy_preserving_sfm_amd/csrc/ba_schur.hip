@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void k_prepare(int point_blocks, int P, const 
 // (both walk the same observation list and the same records; they used to be two wavefront-per-image kernels of ~25 us each), and by image 0 the
 // augmented corner and the identity padding.  (What was tried here after k_reduce: the remark at PoseReduceBody, ba_step.hip.)
 // NV = 0: the 6 x 6 pose block; an iterative handle (a.Sd) gets the blocks in Sd [C][36] and the rhs in rhs_out [6C] instead.
-// NV > 0: every image with NV variable intrinsics of its own beside its pose columns (pp_ba_impl::intr_wide_nv; image_ordering.hip PrivateIntrinsicsColumns).
+// NV > 0: every image with NV variable intrinsics of its own beside its pose columns (pp_ba_impl::intr_wide_nv; image_ordering.hpp PrivateIntrinsicsColumns).
 // The image's W = 6 + NV columns are ONE block of the reduced system, J_w,o = [J_pose,o diag(s_c) | J_intr,o diag(s_k)] (2 x W: the record's pose rows and
 // the compact scaled rows of JkS), and the blocks are those of the pose gather with wider rows:
 //   diagonal   S_cc = U_c + D^2 (pose part) + sum_{o of c} J_w^T J_w (every entry with an intrinsics column) - sum_o J_w^T G_oo J_w

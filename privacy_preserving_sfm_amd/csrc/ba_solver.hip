@@ -450,7 +450,7 @@ int pp_ba_get_structure(pp_ba_handle h, int32_t* info) try {
   info[5] = h->iterative ? 1 : 0;
   // the chains of the one-launch factorisation (several: a nested-dissection order whose sub-trees are factorised side by side) and its chain steps
   info[6] = 1; info[7] = T;
-  if (BaSparseActive(h) && T >= 4 && T <= 128 && !h->tile_nz.empty()) {
+  if (BaSparseActive(h) && UseTasks(T) && !h->tile_nz.empty()) {
     if (h->structure_steps < 0) h->structure_steps = CholeskyChainSteps(T, h->tile_nz.data(), h->sw, &h->structure_chains);      // (planned once per handle; the plan itself is cached per tile map)
     info[6] = h->structure_chains; info[7] = h->structure_steps;
   }

@@ -127,7 +127,7 @@ inline void ApplyImageOrder(BaStructure* st, int nv_private) {
   }
   const int32_t *in_obs_pose = st->obs_pose(), *in_pose_camera = st->pose_camera();
   // columns of the reduced system: the vectors' order (pose c at 6c, intrinsics block k at 6C + intr_off[k]) unless every image carries its own variable
-  // intrinsics, which then sit beside its pose columns (image_ordering.hip PrivateIntrinsicsColumns; internal image order)
+  // intrinsics, which then sit beside its pose columns (image_ordering.hpp PrivateIntrinsicsColumns; internal image order)
   const int W6 = st->W6 = 6 + (st->nv_private = nv_private);
   // (PPSFM_BA_INTR_WIDE=0: the general block-pair lists (ba_intr.hip) also for per-image intrinsics - tests / comparisons)
   st->intr_wide_nv = (nv_private >= 2 && nv_private <= 8 && st->sw.ba_intr_wide) ? nv_private : 0;
@@ -154,6 +154,32 @@ inline void ApplyImageOrder(BaStructure* st, int nv_private) {
   for (int p = 0; p < st->P; ++p) if (!st->point_const[(size_t)p]) neff += 3;
 }
 
+// ---- the columns of the reduced camera system and its 64x64 tiles: the one place that knows ------------------------------------------------------
+// W6 columns per image - its pose and, when every image carries nv_private variable intrinsics of its own (image_ordering.hpp PrivateIntrinsicsColumns),
+// those beside it, coupled with the same images as the pose -, image at position p at W6 p; behind the images (tail0) the NI_tail columns of the shared
+// intrinsics blocks, which couple with every image; then the right-hand side's row n_red.  Tt: tiles per side.
+struct ReducedColumns {
+  int nv_private, W6, tail0, NI_tail, n_red, Tt;
+  ReducedColumns(int C, int NI, int nv) : nv_private(nv), W6(6 + nv), tail0(W6 * C), NI_tail(NI - nv * C), n_red(6 * C + NI), Tt((n_red + 1 + 63) / 64) {}
+};
+// an image whose pose is constant has no part in the reduced system - no node of the co-visibility graph, no pair lists - unless every image carries variable
+// intrinsics of its own beside its pose columns (its block pairs with the images it shares points with exist whatever its pose is)
+inline bool ImageIsFixed(int nv_private, const uint8_t* pose_const, int c) { return nv_private == 0 && pose_const && pose_const[c]; }
+// the tiles (lower triangle of the Tt x Tt map nz) of the block pair of the images at positions pi and pj (pi == pj: the diagonal block); returns how many were new
+inline int MarkImagePair(const ReducedColumns& rc, int pi, int pj, uint8_t* nz) {
+  const int r0 = rc.W6 * std::max(pi, pj), c0 = rc.W6 * std::min(pi, pj);
+  int marked = 0;
+  for (int ti = r0 / 64; ti <= (r0 + rc.W6 - 1) / 64; ++ti)
+    for (int tj = c0 / 64; tj <= (c0 + rc.W6 - 1) / 64; ++tj) if (tj <= ti && !nz[(size_t)ti * rc.Tt + tj]) { nz[(size_t)ti * rc.Tt + tj] = 1; ++marked; }
+  return marked;
+}
+// the rows of the shared intrinsics (they couple with every image) and the right-hand side's row (without a tail: the row of n_red alone)
+inline void MarkTailAndRhs(const ReducedColumns& rc, uint8_t* nz) {
+  for (int ti = rc.tail0 / 64; ti <= rc.n_red / 64; ++ti) for (int tj = 0; tj <= ti; ++tj) nz[(size_t)ti * rc.Tt + tj] = 1;
+}
+// the block-sparse path takes a closed tile map when at most 0.7 of the lower triangle is in it (variable intrinsics: dense rows, the pose part keeps its structure - an arrow)
+inline bool BlockSparsePays(int Tt, int nnz) { return (int64_t)nnz * 10 <= (int64_t)Tt * (Tt + 1) / 2 * 7; }
+
 // Tile structure of the reduced camera system (64x64 tiles of its lower triangle): which tiles the co-visibility puts an
 // entry in, closed under the fill-in of the factorisation.  When a good part of them stays empty (a sequence: images only
 // share points with their neighbours) the assembly, the factorisation and the back substitution skip them - what the
@@ -161,20 +187,15 @@ inline void ApplyImageOrder(BaStructure* st, int nv_private) {
 // Reads the pair lists as the builder left them; returns the refusal (pp_last_error's text) of a co-visibility matrix that is not the group's union, or "".
 inline std::string BuildTileMap(BaStructure* st) {
   const pp_ba_problem_desc* d = st->d;
-  const int C = st->C, W6 = st->W6, nv_private = st->nv_private, n_red = st->n_red, reordered = st->reordered();
+  const int C = st->C, nv_private = st->nv_private, reordered = st->reordered();
   const std::vector<int32_t>&pair_ij = st->pair_ij, &old_of_new = st->old_of_new, &new_of_old = st->new_of_old;
-  const int Nn = ((n_red + 1 + 63) / 64) * 64, Tt = Nn / 64;
-  std::vector<uint8_t> nz((size_t)Tt * Tt, 0);
+  const ReducedColumns rc(C, st->intr.NI, nv_private);
+  std::vector<uint8_t> nz((size_t)rc.Tt * rc.Tt, 0);
   int64_t marked = 0;
-  const int64_t image_rows = (W6 * C - 1) / 64 + 1, all_tiles = image_rows * (image_rows + 1) / 2;      // the tiles the images' columns can reach
-  auto mark = [&](int r0, int r1, int c0, int c1) {
-    for (int ti = r0 / 64; ti <= r1 / 64; ++ti)
-      for (int tj = c0 / 64; tj <= c1 / 64; ++tj) if (tj <= ti && !nz[(size_t)ti * Tt + tj]) { nz[(size_t)ti * Tt + tj] = 1; ++marked; }
-  };
-  // (W6 columns per image: its pose and, when every image carries its own variable intrinsics, those beside it - coupled with the same images as the pose)
-  for (int c = 0; c < C; ++c) mark(W6 * c, W6 * c + W6 - 1, W6 * c, W6 * c + W6 - 1);
+  const int64_t image_rows = (rc.W6 * C - 1) / 64 + 1, all_tiles = image_rows * (image_rows + 1) / 2;      // the tiles the images' columns can reach
+  for (int c = 0; c < C; ++c) marked += MarkImagePair(rc, c, c, nz.data());
   // (a dense co-visibility has every tile after a fraction of its 125 000 pairs: the walk stops there)
-  for (size_t i = 0; i + 1 < pair_ij.size() && marked < all_tiles; i += 2) mark(W6 * pair_ij[i], W6 * pair_ij[i] + W6 - 1, W6 * pair_ij[i + 1], W6 * pair_ij[i + 1] + W6 - 1);
+  for (size_t i = 0; i + 1 < pair_ij.size() && marked < all_tiles; i += 2) marked += MarkImagePair(rc, pair_ij[i], pair_ij[i + 1], nz.data());
   if (d->covisibility) {
     // a pair of THIS shard that the given matrix lacks: the matrix is not the group's union (stale, partial, another scene's) and the other ranks - who
     // only have the matrix - would lay out another tile map than this one: refuse here instead of exchanging differently sized systems later
@@ -189,19 +210,16 @@ inline std::string BuildTileMap(BaStructure* st) {
     }
     // (the union over a group's shards: tiles other ranks' points fill, in the internal order)
     for (int i = 1; i < C; ++i) {
-      if (nv_private == 0 && d->pose_const && d->pose_const[i]) continue;
+      if (ImageIsFixed(nv_private, d->pose_const, i)) continue;
       const int ni = reordered ? new_of_old[(size_t)i] : i;
       for (int j = 0; j < i; ++j)
-        if ((d->covisibility[(size_t)i * C + j] || d->covisibility[(size_t)j * C + i]) && !(nv_private == 0 && d->pose_const && d->pose_const[j])) {
-          const int nj = reordered ? new_of_old[(size_t)j] : j, hi = std::max(ni, nj), lo = std::min(ni, nj);
-          mark(W6 * hi, W6 * hi + W6 - 1, W6 * lo, W6 * lo + W6 - 1);
-        }
+        if ((d->covisibility[(size_t)i * C + j] || d->covisibility[(size_t)j * C + i]) && !ImageIsFixed(nv_private, d->pose_const, j))
+          MarkImagePair(rc, ni, reordered ? new_of_old[(size_t)j] : j, nz.data());
     }
   }
-  if (st->intr.NI > nv_private * C) mark(W6 * C, n_red - 1, 0, n_red - 1);      // the shared intrinsics rows couple with every image
-  mark(n_red, n_red, 0, n_red);                        // the right-hand side's row
-  const int nnz = CloseTileMap(Tt, nz.data());
-  st->sparse_tiles = !st->iterative && st->sw.ba_sparse && Tt >= 8 && (int64_t)nnz * 10 <= (int64_t)Tt * (Tt + 1) / 2 * 7;      // (variable intrinsics: their rows are dense, the pose part keeps its structure - an arrow)
+  MarkTailAndRhs(rc, nz.data());
+  const int nnz = CloseTileMap(rc.Tt, nz.data());
+  st->sparse_tiles = !st->iterative && st->sw.ba_sparse && rc.Tt >= 8 && BlockSparsePays(rc.Tt, nnz);
   st->tile_nz.swap(nz); st->num_nz_tiles = nnz;
   return std::string();
 }

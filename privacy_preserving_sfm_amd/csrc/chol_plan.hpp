@@ -47,6 +47,10 @@ constexpr int BacksubNumPairs(int T) { return T >= 7 ? (T - 3) / 2 : 0; }      /
 
 constexpr int kMaxSteps = 128;       // block columns the counter arrays hold (N <= 8192)
 constexpr int kMaxSuper = kMaxSteps / 2 + 1;
+// The sizes of the one-launch path, dense or block-sparse: up to kMaxSteps block columns, the whole range of its counter arrays (round 2 stopped at 88 - equal
+// at n = 6000, slower at 8000; with the two-panel updates of round 3: n = 3000 0.68 against 0.83 ms, 4000 1.08 / 1.36, 6000 2.57 / 3.00, 8000 5.53 / 5.96 -
+// tools/chol_time.py)
+constexpr bool UseTasks(int T) { return T >= 4 && T <= kMaxSteps; }
 constexpr int kScratchCounters = 2048;      // counters of the per-chain accumulation sequences (several chains, see ChainRanges), handed out by the host
 enum { cSol0 = 8, cVer0 = cSol0 + kMaxChains * kMaxSteps, cSub0 = cVer0 + kMaxSuper * kMaxSuper, cScratch0 = cSub0 + kMaxSuper * kMaxSuper,
        kNumCounters = cScratch0 + kScratchCounters };      // sol: one set of row counters per chain (cSol0 + chain x kMaxSteps + row)

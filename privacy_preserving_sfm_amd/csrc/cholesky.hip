@@ -14,7 +14,7 @@
 //   task mode     (k_cholesky_tasks, 4 to 128 block columns, dense or block-sparse) the whole factorisation in ONE launch: a persistent chain
 //                 workgroup + one workgroup per item of a priority-sorted task list, per-tile dependency counters, mailbox
 //                 hand-offs - see "task mode" in chol_tasks.hpp; a block-sparse system whose elimination tree has independent sub-trees (a nested-dissection
-//                 order of the cameras, image_ordering.hip DissectBand) gets a chain workgroup per sub-tree - see "ChainRanges" in chol_plan.hpp;
+//                 order of the cameras, image_ordering.hpp BandDissector) gets a chain workgroup per sub-tree - see "ChainRanges" in chol_plan.hpp;
 //   column mode   (k_column_step: 3 or more than 128 block columns, PPSFM_CHOL_MODE=columns, a task list that failed its host replay, and
 //                 after a fallback) one launch per block column, over every tile or, for a block-sparse system, over its non-zero tiles only
 //                 (the per-launch lists of EnsureSparseLists); captured into a graph once per bind and replayed.
@@ -114,19 +114,6 @@ static int EnsureSparseLists(CholeskyState* st, int T, hipStream_t strm) {
   PP_HIP_TRY(hipStreamSynchronize(strm));     // (the caller's stream, not the legacy one: another host thread may be capturing its own factorisation)
   st->sparse_T = T;
   return PP_OK;
-}
-
-// The sizes of the one-launch path, dense or block-sparse: up to kMaxSteps block columns, the whole range of its counter arrays (round 2 stopped at 88 - equal
-// at n = 6000, slower at 8000; with the two-panel updates of round 3: n = 3000 0.68 against 0.83 ms, 4000 1.08 / 1.36, 6000 2.57 / 3.00, 8000 5.53 / 5.96 -
-// tools/chol_time.py)
-static bool UseTasks(int T) { return T >= 4 && T <= kMaxSteps; }
-
-int CholeskyPlanSteps(int T, const uint8_t* nz, const Switches& sw, int* chains) {
-  if (chains) *chains = 1;
-  if (!nz || !UseTasks(T)) return T;
-  const ChainPlan plan = PlanChains(T, nz, sw.plan);
-  if (chains) *chains = plan.cr.n;
-  return plan.Steps();
 }
 
 static std::recursive_mutex g_setup_mutex;

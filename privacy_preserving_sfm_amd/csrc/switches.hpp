@@ -25,7 +25,7 @@
 //   PPSFM_BA_SPARSE             atoi, 0 = off                on               BuildTileMap, SetupOf (block-sparse system)   A/B
 //   PPSFM_BA_ORDERING           letter n natural, r rcm,     by chain steps   SetupOf, ChooseImageOrdering                 A/B
 //                               b band (any case)
-//   PPSFM_BA_GRAPH_ND           atoi, 0 never / else always  by band cuts     ChooseImageOrdering (graph dissections)      A/B
+//   PPSFM_BA_GRAPH_ND           atoi, 0 never / else always  by band cuts     DissectionCandidates (image_ordering.hpp)    A/B
 //   PPSFM_BA_INTR_LAYOUT        letter t|T tail              beside the pose  PrivateIntrinsicsColumns                     A/B
 //   PPSFM_BA_INTR_WIDE          atoi, 0 = off                on               ApplyImageOrder (k_schur_wide_* blocks)       A/B
 //   PPSFM_BA_PAIR_LISTS         letter h|H host, d|D device  by size          PairListsOnDeviceEligible                    A/B

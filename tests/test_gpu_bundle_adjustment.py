@@ -925,6 +925,33 @@ def test_sequence_scene_is_dissected_and_factorised_by_several_chains(oracle, mo
     assert np.abs(points - rpoints).max() <= 1e-5 * np.abs(rpoints).max() and np.abs(poses - rposes).max() <= 1e-5 * np.abs(rposes).max()
 
 
+@pytest.mark.parametrize("lists", ["device", "host"])
+@pytest.mark.parametrize("per_image_intrinsics", [False, True])
+def test_handle_structure_is_what_plan_ordering_plans(monkeypatch, per_image_intrinsics, lists):
+    """pp_ba_create feeds the image ordering from the co-visibility bits it builds on the device (PPSFM_BA_PAIR_LISTS=device) or lets it walk the
+    observations (host), and applies the fixed-image rule itself before either: a constant pose is no node of the graph unless every image carries variable
+    intrinsics of its own (0b0110: 8 columns per image).  The handle's structure is the one pp_ba_plan_ordering plans on the host alone: 300 images,
+    window 20, about a tenth of the poses constant."""
+    from privacy_preserving_sfm_amd.device import BAProblem, plan_ordering
+    sc = synthetic.make_ba_scene(300, 6000, 6, seed=0xC0FFEE + 300, model=2, window=20, num_intrinsics=300 if per_image_intrinsics else 1)
+    pc = np.array(sc["pose_const"], dtype=np.uint8)
+    pc[3::10] = 1
+    sc = dict(sc, pose_const=pc)
+    if per_image_intrinsics:
+        sc["camera_const_mask"] = np.full(300, 0b0110, dtype=np.uint16)
+    monkeypatch.setenv("PPSFM_BA_PAIR_LISTS", lists)
+    _, plan = plan_ordering(sc)
+    pb = BAProblem(sc)
+    st = pb.structure()
+    pb.close()
+    T = plan["block_columns"]
+    assert T == ((8 if per_image_intrinsics else 6) * 300 + 1 + 63) // 64 and st["private_intrinsics"] == (2 if per_image_intrinsics else 0)
+    assert plan["reordered"] and plan["chains"] >= 2, plan
+    want = dict(reordered=plan["reordered"], tiles=T * (T + 1) // 2, nnz_used=plan["nnz_used"], chains=plan["chains"], chain_steps=plan["chain_steps"],
+                block_sparse=plan["block_sparse"])
+    assert {k: st[k] for k in want} == want, (st, plan)
+
+
 def test_several_chains_timeout_falls_back_to_column_launches(monkeypatch):
     """the bounded waits of the one-launch factorisation with SEVERAL chain workgroups: half of the task list missing -> every chain and task leaves,
     the host repeats the step with one launch per block column over the same (dissected) tile map and stays with that mode; same end point."""

@@ -1,5 +1,5 @@
 """The image order pp_ba_create gives the reduced camera system - reverse Cuthill-McKee, then a nested dissection of the band whose parts the one-launch
-factorisation runs side by side (csrc/image_ordering.hip: ReverseCuthillMcKee, DissectBand; csrc/cholesky.hip: PlanChains) - computed on the host alone through
+factorisation runs side by side (csrc/image_ordering.hpp: ReverseCuthillMcKee, BandDissector; csrc/chol_plan.hpp: PlanChains) - computed on the host alone through
 pp_ba_plan_ordering.  What Ceres' SPARSE_SCHUR ordering does for the reference between 50 and 1000 images (src/optim/bundle_adjustment.cc:279-282); the
 numerics of the orders are covered on the GPU (tests/test_gpu_bundle_adjustment.py::test_sequence_scene_*)."""
 import numpy as np
@@ -94,7 +94,7 @@ def test_clustered_collection_is_dissected_by_separators_of_the_graph_itself(top
     """Photo collections: dense groups of images joined by a few bridge images (a hub with satellites / a chain of groups), ids shuffled.  The plain
     Cuthill-McKee band of such a graph is ONE chain over all block columns; a vertex separator - the bridge images - leaves the groups as independent parts,
     each a chain of the one-launch factorisation.  Two sources of candidates find such separators: the cuts of the band whose parts are re-ordered by their own
-    Cuthill-McKee (round 4; on these scenes it finds the same cuts) and the level-structure separators of the graph itself (round 5: DissectGraph, the
+    Cuthill-McKee (round 4; on these scenes it finds the same cuts) and the level-structure separators of the graph itself (round 5: GraphDissector, the
     components a separator leaves as parts of their own); the fewest chain steps win.  What Ceres' SPARSE_SCHUR ordering handles for the reference on any graph
     (src/optim/bundle_adjustment.cc:279-282)."""
     sc = synthetic.make_ba_scene(500, 10000, 6, seed=0xC0FFEE + 11 * clusters, model=2, clusters=clusters, bridge=4, topology=topology)
