@@ -176,13 +176,16 @@ __global__ __launch_bounds__(256) void k_planar_evaluate(int n, const double* __
 }
 
 // PlanarOffsetEstimator::MinimalSolver up to the offsets (initializer.cc:236-262), one lane per sample.
-// sample_size == 3: direct 3x3 solve; larger samples (the LO non-minimal solver): least squares by normal equations.
+// sample_size == 3: direct 3x3 solve; larger samples (the LO non-minimal solver): least squares by a QR of the equations themselves, as the reference's
+// colPivHouseholderQr - the triangular factor R and Q^T b are updated row by row with Givens rotations (nine + three registers, no row is kept).  The
+// normal equations that stood here squared the condition of the system: on ten-track samples the offsets were up to ten times further from the exact
+// least-squares solution than the oracle's (tests/test_gpu_init_solvers_exact.py).
 __global__ __launch_bounds__(64) void k_planar_solve(int n, const double* __restrict__ lines, const double* __restrict__ poses,
                                                      const double* __restrict__ Rg, int64_t num, int sample_size, const int32_t* __restrict__ samples,
                                                      double* __restrict__ offsets) {
   const int64_t h = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (h >= num) return;
-  double AtA[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Atb[3] = {0, 0, 0}, Ad[9], bd[3];
+  double Rt[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Qtb[3] = {0, 0, 0}, Ad[9], bd[3];      // Rt: upper triangular, row-major
   bool ok = true;
   for (int s = 0; s < sample_size; ++s) {
     const int idx = samples[h * sample_size + s];
@@ -219,17 +222,35 @@ __global__ __launch_bounds__(64) void k_planar_solve(int n, const double* __rest
       for (int c = 0; c < 3; ++c) Ad[3 * s + c] = row[c];
       bd[s] = bi;
     }
+    // rotate the new equation (row | bi) into the triangle: column k of the row against R[k][k]
+    double w = bi;
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      Atb[r] += row[r] * bi;
+    for (int k = 0; k < 3; ++k) {
+      if (row[k] != 0.0) {
+        const double rkk = Rt[3 * k + k];
+        const double len = sqrt(rkk * rkk + row[k] * row[k]);
+        const double cs = rkk / len, sn = row[k] / len;
+        Rt[3 * k + k] = len;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) AtA[3 * r + c] += row[r] * row[c];
+        for (int c = k + 1; c < 3; ++c) {
+          const double rkc = Rt[3 * k + c];
+          Rt[3 * k + c] = cs * rkc + sn * row[c];
+          row[c] = cs * row[c] - sn * rkc;
+        }
+        const double qk = Qtb[k];
+        Qtb[k] = cs * qk + sn * w;
+        w = cs * w - sn * qk;
+      }
     }
   }
   double out[3] = {NAN, NAN, NAN};
   if (ok) {
     if (sample_size == 3) { if (Solve3<1>(Ad, bd)) { out[0] = bd[0]; out[1] = bd[1]; out[2] = bd[2]; } }
-    else { if (Solve3<1>(AtA, Atb)) { out[0] = Atb[0]; out[1] = Atb[1]; out[2] = Atb[2]; } }
+    else if (Rt[0] != 0.0 && Rt[4] != 0.0 && Rt[8] != 0.0) {      // (rank deficient: no model, as a zero pivot of the direct solve)
+      out[2] = Qtb[2] / Rt[8];
+      out[1] = (Qtb[1] - Rt[5] * out[2]) / Rt[4];
+      out[0] = (Qtb[0] - Rt[1] * out[1] - Rt[2] * out[2]) / Rt[0];
+    }
   }
   offsets[3 * h] = out[0]; offsets[3 * h + 1] = out[1]; offsets[3 * h + 2] = out[2];
 }

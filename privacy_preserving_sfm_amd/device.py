@@ -491,6 +491,14 @@ class FourView2dProblem(_Handle):
         check(_capi.lib().pp_fourview2d_evaluate(self._h, dp(cams), dp(err), dp(X)))
         return err, X
 
+    def evaluate_points(self, cams, X):
+        """EvaluateModelOnPoint against the model's own points X [n,2] (a model refined by LeastSquares) -> errors [n]."""
+        cams = f64(cams).reshape(24); X = f64(X)
+        assert X.shape == (self.n, 2)
+        err = np.zeros(self.n)
+        check(_capi.lib().pp_fourview2d_evaluate_points(self._h, dp(cams), dp(X), dp(err)))
+        return err
+
     def minimal_batch(self, samples, frames=None):
         """FourView2dEstimator::MinimalSolver per sample -> (cams [num,16,4,2,3], counts [num])."""
         samples = np.ascontiguousarray(samples, dtype=np.int32)
