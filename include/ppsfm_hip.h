@@ -1325,6 +1325,51 @@ int pp_sift_extract_candidates(pp_sift_extractor_handle h, int32_t octave, int32
  * level); angles capacity doubles.  Any of the three may be NULL; *num either way. */
 int pp_sift_extract_features(pp_sift_extractor_handle h, float* raw, int32_t* octave_level, double* angles, int64_t capacity, int64_t* num);
 
+/* ---- a batch of images in one call (K23) ------------------------------------------------------------------------------------------------------ */
+typedef struct pp_sift_batch_image {
+  int32_t width, height;
+  const uint8_t* grey;             /* width x height uint8, row-major                                                                           */
+} pp_sift_batch_image;
+
+typedef struct pp_sift_batch_report {
+  int32_t num_images;
+  int32_t num_sub_batches;         /* the images ran in this many groups (see MEMORY below)                                                      */
+  int64_t num_features;            /* features kept, all images = offsets[num_images]                                                           */
+  int64_t workspace_bytes;         /* pyramids, images and row counts of the largest sub-batch                                                  */
+  double phase_ms[5];              /* as in pp_sift_extract_report, for the batch as a whole, with phase_timings                                */
+  double device_ms;
+  double total_ms;
+} pp_sift_batch_report;
+
+/* ExtractSiftFeaturesCPU for num_images grey images of possibly different sizes under ONE option set.  Image i's kept features are the rows
+ * offsets[i] .. offsets[i + 1] of keypoints (capacity x 4) and descriptors (NULL or capacity x 128): in the order, and with exactly the bytes,
+ * pp_sift_extract gives for that image alone; max_num_features cuts per image.  reports: num_images of them, the counts of each image, the timing
+ * fields zero.  offsets: num_images + 1.
+ * WHAT THE BATCH SHARES: the images go through the octaves in lock-step.  For one octave index the pyramid, the gradient, the candidate counts and
+ * their scan of every image are launched (the kernels of pp_sift_extract, per image, on slices of one workspace) and all totals come back in one
+ * download and one wait; likewise the refined candidates, the orientations and the descriptors: four waits per octave for the whole batch where a
+ * loop over the images pays four per octave per image.  The descriptors of all images of an octave are ONE launch of a kernel that gives a
+ * wavefront to every feature.  ITS ORDER RULE: the 64 lanes stage 64 window pixels at a time in scan order; each lane owns two of the 128 bins and
+ * adds, pixel by pixel in that order, what the pixels contribute to them - so every bin receives its additions in the reference's order, and the
+ * float descriptor, the bytes and the window flags equal the single call's bit for bit.  The norms are summed over the entries 0 .. 127 in order.
+ * MEMORY: a group of images keeps the whole pyramid of each of them (a 3200 x 2400 image needs about 3 GB).  workspace_bytes is the target for the
+ * sum, 0 means 8 GiB; groups are consecutive images in input order taken greedily under the target, an image that exceeds it on its own runs alone.
+ * The result does not depend on the split.
+ * AFTER THE CALL the handle holds no single extraction: pp_sift_extract_stage, _candidates and _features are PP_ERR_INVALID until the next
+ * pp_sift_extract; pp_sift_extract_batch_features reads the batch.
+ * CAPACITY: with capacity < offsets[num_images] PP_ERR_INVALID; batch_report, reports and offsets are filled, keypoints and descriptors untouched.
+ * ERRORS: PP_ERR_INVALID before the handle is read, the outputs untouched, for: a null argument (descriptors may be NULL) or a null image,
+ * num_images < 1, a negative capacity or workspace_bytes, every option and every size pp_sift_extract refuses - pp_last_error() names the index of
+ * the offending image.
+ * ABSENT: batch forms of the stage and candidate readers; orientation assignment by wavefront (it is the single call's kernel, per image). */
+int pp_sift_extract_batch(pp_sift_extractor_handle h, const pp_sift_extract_options* options, int32_t num_images, const pp_sift_batch_image* images,
+                          int64_t workspace_bytes, pp_sift_batch_report* batch_report, pp_sift_extract_report* reports, int64_t capacity, float* keypoints,
+                          uint8_t* descriptors, int64_t* offsets);
+/* pp_sift_extract_features for image `image` of the LAST batch: every feature of it before the cut.  PP_ERR_INVALID without a batch on the handle
+ * (a pp_sift_extract since then discards it) or for an image outside it. */
+int pp_sift_extract_batch_features(pp_sift_extractor_handle h, int32_t image, float* raw, int32_t* octave_level, double* angles, int64_t capacity,
+                                   int64_t* num);
+
 #ifdef __cplusplus
 }
 #endif

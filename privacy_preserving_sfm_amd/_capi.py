@@ -254,6 +254,15 @@ class SiftExtractReport(C.Structure):
                 ("phase_ms", C.c_double * 5), ("device_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class SiftBatchImage(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("grey", C.POINTER(C.c_uint8))]
+
+
+class SiftBatchReport(C.Structure):
+    _fields_ = [("num_images", C.c_int32), ("num_sub_batches", C.c_int32), ("num_features", C.c_int64), ("workspace_bytes", C.c_int64),
+                ("phase_ms", C.c_double * 5), ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class LoMsacOptions(C.Structure):
     _fields_ = [("min_num_iterations", C.c_uint32), ("max_num_iterations", C.c_uint32), ("success_probability", C.c_double),
                 ("squared_inlier_threshold", C.c_double), ("random_seed", C.c_uint32), ("num_lo_steps", C.c_int32),
@@ -294,7 +303,7 @@ _EXPORTS = [
     "pp_line_features_options_default", "pp_line_features_from_keypoints",
     "pp_pairs_create", "pp_pairs_destroy", "pp_pairs_spatial", "pp_pairs_transitive", "pp_pairs_num", "pp_pairs_get",
     "pp_sift_extract_options_default", "pp_sift_extractor_create", "pp_sift_extractor_destroy", "pp_sift_extract", "pp_sift_extract_stage",
-    "pp_sift_extract_candidates", "pp_sift_extract_features",
+    "pp_sift_extract_candidates", "pp_sift_extract_features", "pp_sift_extract_batch", "pp_sift_extract_batch_features",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -449,6 +458,9 @@ def lib():
     L.pp_sift_extract_stage.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int64, c_ip, c_ip]
     L.pp_sift_extract_candidates.argtypes = [C.c_void_p, C.c_int32, c_ip, C.c_int64, C.POINTER(C.c_int64)]
     L.pp_sift_extract_features.argtypes = [C.c_void_p, C.POINTER(C.c_float), c_ip, c_dp, C.c_int64, C.POINTER(C.c_int64)]
+    L.pp_sift_extract_batch.argtypes = [C.c_void_p, C.POINTER(SiftExtractOptions), C.c_int32, C.POINTER(SiftBatchImage), C.c_int64, C.POINTER(SiftBatchReport),
+                                        C.POINTER(SiftExtractReport), C.c_int64, C.POINTER(C.c_float), c_u8p, C.POINTER(C.c_int64)]
+    L.pp_sift_extract_batch_features.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float), c_ip, c_dp, C.c_int64, C.POINTER(C.c_int64)]
     _lib = L
     return L
 

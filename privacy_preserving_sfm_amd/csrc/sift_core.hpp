@@ -379,5 +379,122 @@ PP_SIFT_HD void FinishDescriptor(const float* __restrict__ raw, int normalizatio
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The descriptor by parts, for a wavefront per feature (k_sift_describe_wave, and ExtractOnHost's wave route through the same functions).
+// Descriptor() + FinishDescriptor() above are the definition; these restate their pieces so that 64 lanes can share one feature and still give every
+// bit of it.  THE ORDER RULE: a bin receives its additions in the window's scan order (dyi outer, dxi inner) from 0.f.  The eight contributions of one
+// pixel go to eight different bins, so the order of the pixels is the whole order: a bin's owner that walks the pixels in scan order and adds what
+// they give to ITS bin performs the additions of Descriptor() on that bin, one for one.  The weight is (((win * mod) * ax) * ay) * at in float32, as
+// the reference's product associates; the three norms run over the entries 0 .. 127 in index order.
+
+// what Descriptor() settles before its loops: the keypoint in the octave's pixels, the bin size, the window dyi = y0 .. y1, dxi = x0 .. x1 (empty,
+// y1 < y0, for a keypoint that fails the bounds check - and possibly for one that passes it)
+struct DescriptorFrame {
+  double x, y, SBP;
+  int32_t xi, yi, y0, y1, x0, x1;
+  DescriptorWindow win;
+};
+
+PP_SIFT_HD DescriptorFrame MakeDescriptorFrame(int w, int h, int s_min, int s_max, const Keypoint& k, double xper) {
+  PP_SIFT_EXACT
+  DescriptorFrame f;
+  f.x = (double)k.x / xper; f.y = (double)k.y / xper;
+  const double sigma = (double)k.sigma / xper;
+  f.xi = (int)(f.x + 0.5); f.yi = (int)(f.y + 0.5);
+  const int xi = f.xi, yi = f.yi, si = k.is;
+  f.SBP = kMagnif * sigma + kEpsD;
+  const int W = (int)FloorD(1.4142135623730951 * f.SBP * 5 / 2.0 + 0.5);
+  f.y0 = 0; f.y1 = -1; f.x0 = 0; f.x1 = -1;
+  f.win.computed = 0; f.win.cut = 0;
+  if (xi < 0 || xi >= w || yi < 0 || yi >= h - 1 || si < s_min + 1 || si > s_max - 2) return f;
+  f.win.computed = 1;
+  f.y0 = -W > 1 - yi ? -W : 1 - yi; f.y1 = W < h - yi - 2 ? W : h - yi - 2;
+  f.x0 = -W > 1 - xi ? -W : 1 - xi; f.x1 = W < w - xi - 2 ? W : w - xi - 2;
+  f.win.cut = f.y0 != -W || f.y1 != W || f.x0 != -W || f.x1 != W;
+  return f;
+}
+
+// the pixels of the window; pixel p of the scan is (dxi, dyi) = (x0 + p % nx, y0 + p / nx), nx = x1 - x0 + 1
+PP_SIFT_HD int32_t DescriptorWindowPixels(const DescriptorFrame& f) {
+  const int nx = f.x1 - f.x0 + 1, ny = f.y1 - f.y0 + 1;
+  return nx > 0 && ny > 0 ? nx * ny : 0;
+}
+
+// one window pixel before it is spread over its eight bins: 32 bytes, read by every bin owner
+struct alignas(16) DescriptorTap {
+  float wm;                        // win * mod
+  float rbinx, rbiny, rbint;
+  int32_t binx, biny, bint, pad_;
+};
+
+// the body of Descriptor()'s pixel loop down to the bins, for the pixel (dxi, dyi) of the window with gradient (mod, angle)
+PP_SIFT_HD DescriptorTap DescriptorSample(const DescriptorFrame& f, double angle0, double st0, double ct0, const double* __restrict__ expn, int dxi, int dyi,
+                                          float mod, float angle) {
+  PP_SIFT_EXACT
+  const float wsigma = (float)kWindowSize;
+  const float theta = Mod2PiF((float)((double)angle - angle0));
+  const float dx = (float)((double)(f.xi + dxi) - f.x), dy = (float)((double)(f.yi + dyi) - f.y);
+  const float nx = (float)((ct0 * (double)dx + st0 * (double)dy) / f.SBP);
+  const float ny = (float)((-st0 * (double)dx + ct0 * (double)dy) / f.SBP);
+  const float nt = (float)((double)(8 * theta) / (2 * kPi));
+  const float win = (float)FastExpn(expn, (double)(nx * nx + ny * ny) / (2.0 * (double)wsigma * (double)wsigma));
+  DescriptorTap t;
+  t.binx = (int)FloorF((float)((double)nx - 0.5)); t.biny = (int)FloorF((float)((double)ny - 0.5)); t.bint = (int)FloorF(nt);
+  t.rbinx = (float)((double)nx - (t.binx + 0.5)); t.rbiny = (float)((double)ny - (t.biny + 0.5)); t.rbint = nt - (float)t.bint;
+  t.wm = win * mod;
+  t.pad_ = 0;
+  return t;
+}
+
+// What the owner of the bins (orientation t0, t0 + 1; t0 even) of the spatial cell (cx, cy), -2 <= cx, cy < 2, adds for one pixel: *acc0 is bin
+// t0 + (cy + 2) * 32 + (cx + 2) * 8 of the descriptor, *acc1 the next one.  The pixel reaches the cell with dbinx = cx - binx and dbiny = cy - biny
+// where both are 0 or 1 (Descriptor()'s in-range test stands as written); of its two orientations (bint + dbint) % 8 at most one is t0 and at most
+// one t0 + 1.
+PP_SIFT_HD void DescriptorFold(const DescriptorTap& t, int cx, int cy, int t0, float* acc0, float* acc1) {
+  PP_SIFT_EXACT
+  const int dbinx = cx - t.binx, dbiny = cy - t.biny;
+  if (dbinx < 0 || dbinx > 1 || dbiny < 0 || dbiny > 1) return;
+  if (!(t.binx + dbinx >= -2 && t.binx + dbinx < 2 && t.biny + dbiny >= -2 && t.biny + dbiny < 2)) return;
+  const float wxy = t.wm * AbsF((float)(1 - dbinx) - t.rbinx) * AbsF((float)(1 - dbiny) - t.rbiny);
+  for (int dbint = 0; dbint < 2; ++dbint) {
+    const int o = (t.bint + dbint) % 8;
+    if (o != t0 && o != t0 + 1) continue;
+    const float weight = wxy * AbsF((float)(1 - dbint) - t.rbint);
+    if (o == t0) *acc0 += weight; else *acc1 += weight;
+  }
+}
+
+// NormalizeHistogram()'s norm: the sequential sum of squares over the 128 entries, the fast root, the epsilon
+PP_SIFT_HD float HistogramNorm(const float* d) {
+  PP_SIFT_EXACT
+  float norm = 0.0f;
+  for (int i = 0; i < kDescBins; ++i) norm += d[i] * d[i];
+  return FastSqrtF(norm) + kEpsF;
+}
+PP_SIFT_HD float ClampBin(float v) { return (double)v > 0.2 ? (float)0.2 : v; }
+
+// FinishDescriptor() in two parts: its norm over the 128 entries in order, and one entry of its output (raw[i] goes to byte UbcIndex(i))
+PP_SIFT_HD float FinishNorm(const float* raw, int normalization) {
+  PP_SIFT_EXACT
+  float norm = 0.f;
+  if (normalization == 0) {
+    for (int i = 0; i < kDescBins; ++i) norm += AbsF(raw[i]);
+    return norm;
+  }
+  for (int i = 0; i < kDescBins; ++i) norm += raw[i] * raw[i];
+  return __builtin_sqrtf(norm);
+}
+PP_SIFT_HD uint8_t FinishByte(float raw, float norm, int normalization) {
+  PP_SIFT_EXACT
+  float v = 0.f;
+  if (norm > 0.f) {
+    v = raw / norm;
+    if (normalization == 0) v = __builtin_sqrtf(v);
+  }
+  const float scaled = RoundF(512.0f * v);
+  return (uint8_t)(scaled > 255.f ? 255.f : scaled);
+}
+PP_SIFT_HD int UbcIndex(int i) { return (i & ~7) + ((8 - (i & 7)) & 7); }
+
 }  // namespace sift
 }  // namespace ppsfm

@@ -14,8 +14,10 @@
 // K21e k_sift_refine     one lane per candidate; the host keeps the survivors in order and evaluates pow for their sigma
 // K21f k_sift_orient     one lane per keypoint walking its window in the reference's order (the histogram is a sequential double sum)
 // K21g k_sift_describe   one lane per feature: the 4 x 4 x 8 float accumulation in the reference's order straight into the feature's row of the raw
-//                        descriptors, then the last normalisation to bytes.  The long pole at thousands of features; a wavefront per keypoint with a
-//                        fixed-order fold is the follow-up.
+//                        descriptors, then the last normalisation to bytes.  The single call's kernel, and the on-device reference of K23.
+// K23  pp_sift_extract_batch: the images of a batch through the octaves in lock-step, the kernels above per image on slices of one workspace, four
+//                        waits per octave for all of them; k_sift_describe_wave describes the features of every image of an octave in one launch, a
+//                        wavefront per feature with a fixed-order fold (see the kernel).
 #include <cstring>
 
 #include "device_handle.hpp"
@@ -157,7 +159,7 @@ __global__ __launch_bounds__(kSiftLaneBlock) void k_sift_orient(int32_t n, const
 }
 
 struct SiftFeature {
-  int32_t key, reserved_;
+  int32_t key, image;                      // image: its slot in the batch's image table (k_sift_describe_wave); 0 for the single call
   double angle, sin_angle, cos_angle;      // the host's libm
 };
 
@@ -183,6 +185,170 @@ struct SiftOctave {
   std::vector<int32_t> cand;                // the unrefined candidates of the last extraction
 };
 
+// K23 k_sift_describe_wave - one wavefront (a workgroup of 64) per feature, the features of any number of images in one launch: feats[f].image is the
+// slot of the feature's image in `images`, feats[f].key its keypoint in `keys` (all images' keypoints, end to end).  Lane l takes pixel 64 c + l of
+// the window's scan for chunk c (the lanes of a window row read adjacent (modulus, angle) pairs) and stages DescriptorSample() of it in LDS; then
+// every lane walks the staged pixels in order - all lanes read the same address, a broadcast - and folds them into the two bins it owns, 2 l and
+// 2 l + 1: the spatial cell l / 4, the orientations 2 (l % 4) and the next.  So each bin receives its additions in scan order, as in Descriptor().
+// The norms: every lane sums the 128 entries from LDS in index order; the divisions, the clamp and the bytes are spread two entries per lane.
+struct SiftWaveImage {
+  const float* grad;      // the gradient levels s_min + 1 .. of the image's current octave
+  int32_t w, h;
+  double xper;
+};
+
+__global__ __launch_bounds__(kWave) void k_sift_describe_wave(const SiftFeature* __restrict__ feats, const Keypoint* __restrict__ keys,
+                                                             const SiftWaveImage* __restrict__ images, int s_min, int s_max,
+                                                             const double* __restrict__ expn, int normalization, float* __restrict__ raw,
+                                                             uint8_t* __restrict__ bytes, DescriptorWindow* __restrict__ window) {
+  __shared__ DescriptorTap staged[kWave];
+  __shared__ float hist[kDescBins];
+  const int64_t f = blockIdx.x;
+  const int lane = threadIdx.x;
+  const SiftFeature q = feats[f];
+  const Keypoint k = keys[q.key];
+  const SiftWaveImage im = images[q.image];
+  const DescriptorFrame fr = MakeDescriptorFrame(im.w, im.h, s_min, s_max, k, im.xper);
+  const int cx = ((lane >> 2) & 3) - 2, cy = (lane >> 4) - 2, t0 = 2 * (lane & 3);
+  float acc0 = 0.f, acc1 = 0.f;
+  const int n = DescriptorWindowPixels(fr);      // (0 unless the bounds check passed: nothing is read for a level that does not exist)
+  if (n > 0) {
+    const int nx = fr.x1 - fr.x0 + 1;
+    const float* pt = im.grad + (int64_t)(k.is - s_min - 1) * 2 * ((int64_t)im.w * im.h) + 2 * fr.xi + (int64_t)(2 * im.w) * fr.yi;
+    for (int base = 0; base < n; base += kWave) {
+      const int p = base + lane;
+      if (p < n) {
+        const int dxi = fr.x0 + p % nx, dyi = fr.y0 + p / nx;
+        const float* gp = pt + 2 * dxi + (int64_t)(2 * im.w) * dyi;
+        staged[lane] = DescriptorSample(fr, q.angle, q.sin_angle, q.cos_angle, expn, dxi, dyi, gp[0], gp[1]);
+      }
+      __syncthreads();
+      const int m = n - base < kWave ? n - base : kWave;
+      for (int j = 0; j < m; ++j) DescriptorFold(staged[j], cx, cy, t0, &acc0, &acc1);
+      __syncthreads();
+    }
+  }
+  hist[2 * lane] = acc0; hist[2 * lane + 1] = acc1;
+  __syncthreads();
+  float norm = HistogramNorm(hist);
+  acc0 = ClampBin(acc0 / norm); acc1 = ClampBin(acc1 / norm);
+  __syncthreads();
+  hist[2 * lane] = acc0; hist[2 * lane + 1] = acc1;
+  __syncthreads();
+  norm = HistogramNorm(hist);
+  acc0 = acc0 / norm; acc1 = acc1 / norm;
+  __syncthreads();
+  hist[2 * lane] = acc0; hist[2 * lane + 1] = acc1;
+  __syncthreads();
+  norm = FinishNorm(hist, normalization);
+  raw[kDescBins * f + 2 * lane] = acc0; raw[kDescBins * f + 2 * lane + 1] = acc1;
+  bytes[kDescBins * f + UbcIndex(2 * lane)] = FinishByte(acc0, norm, normalization);
+  bytes[kDescBins * f + UbcIndex(2 * lane + 1)] = FinishByte(acc1, norm, normalization);
+  if (lane == 0) window[f] = fr.win;
+}
+
+// The filters of one option set, one after the other: [0] the first octave's first level (or none), [1] a later octave's (none with the reference's
+// geometry), then the levels s_min + 1 .. s_max
+struct SiftFilter { size_t offset; int W; };
+struct SiftFilters {
+  std::vector<float> taps;
+  std::vector<SiftFilter> filters;
+};
+
+inline int MakeSiftFilters(const char* where, const Geometry& g, SiftFilters* out) {
+  auto add_filter = [&](double sigma) {
+    if (!(sigma > 0.0)) { out->filters.push_back(SiftFilter{0, 0}); return; }
+    const std::vector<float> t = GaussTaps(sigma);
+    out->filters.push_back(SiftFilter{out->taps.size(), (int)t.size() / 2});
+    out->taps.insert(out->taps.end(), t.begin(), t.end());
+  };
+  add_filter(FirstLevelSigma(g, true));
+  add_filter(FirstLevelSigma(g, false));
+  for (int s = g.s_min + 1; s <= g.s_max; ++s) add_filter(LevelSigma(g, s));
+  for (const SiftFilter& f : out->filters) PP_REQUIRE(f.W <= kMaxFilterHalfWidth, "%s: a filter of half width %d", where, f.W);
+  return PP_OK;
+}
+
+// The octaves of one image and their places in its pyramid (offsets in floats from the pyramid's start), the transposed temporary behind them
+struct SiftLayout {
+  std::vector<SiftOctave> octaves;
+  size_t total = 0, temp_offset = 0;      // floats of the pyramid with the temporary; where the temporary starts
+  int max_rows = 1;                       // the detection rows (level, y) of the tallest octave
+  size_t rows_need = 0;                   // int32s: row counts, row starts, the total (2), the scan's scratch
+};
+
+inline SiftLayout LayoutOctaves(const Geometry& g, int width, int height) {
+  SiftLayout lay;
+  const int L = g.levels(), num_grad = g.S;
+  lay.octaves.resize((size_t)g.O);
+  for (int q = 0; q < g.O; ++q) {
+    SiftOctave& oc = lay.octaves[(size_t)q];
+    oc.o = g.o_min + q;
+    oc.w = ShiftLeft(width, -oc.o); oc.h = ShiftLeft(height, -oc.o);
+    oc.has_grad = oc.w >= 2 && oc.h >= 2;
+    const size_t lev = (size_t)oc.w * oc.h;
+    oc.gauss = lay.total; lay.total += lev * (size_t)L;
+    oc.dog = lay.total; lay.total += lev * (size_t)(L - 1);
+    oc.grad = lay.total; lay.total += 2 * lev * (size_t)num_grad;
+  }
+  lay.temp_offset = lay.total;
+  lay.total += (size_t)lay.octaves[0].w * lay.octaves[0].h;
+  for (const SiftOctave& oc : lay.octaves) lay.max_rows = std::max(lay.max_rows, g.S * oc.h);
+  lay.rows_need = 2 * (size_t)lay.max_rows + 2 + ScanScratchCount(lay.max_rows);
+  return lay;
+}
+
+inline dim3 SiftGrid(int64_t n, int block) { return dim3((unsigned)std::max<int64_t>(CeilDiv(n, block), 1)); }
+
+// The Gaussian and DoG levels of octave q of one image: its first level from `image` (width x height floats) or from the octave before, the
+// smoothing level by level, the differences.  pyramid: where the image's pyramid starts; d_taps: the filters' taps on the device.
+inline void LaunchOctavePyramid(hipStream_t s, const Geometry& g, const SiftFilters& filters, const float* d_taps, const SiftLayout& lay, int q, float* pyramid,
+                                const float* image, int width, int height) {
+  const SiftOctave& oc = lay.octaves[(size_t)q];
+  const int w = oc.w, hgt = oc.h, L = g.levels();
+  const int64_t lev = (int64_t)w * hgt;
+  float* gauss = pyramid + oc.gauss;
+  float* dog = pyramid + oc.dog;
+  float* temp = pyramid + lay.temp_offset;
+  auto smooth = [&](float* out, const float* in, const SiftFilter& f) {
+    const size_t lds = ((size_t)(kSiftTile + 2 * f.W) * kSiftPitch + 2 * (size_t)f.W + 1) * sizeof(float);
+    hipLaunchKernelGGL(k_sift_convolve, dim3((unsigned)CeilDiv(w, kSiftTile), (unsigned)CeilDiv(hgt, kSiftTile)), dim3(kSiftBlock), lds, s, temp, in, w, hgt,
+                       d_taps + f.offset, f.W);
+    hipLaunchKernelGGL(k_sift_convolve, dim3((unsigned)CeilDiv(hgt, kSiftTile), (unsigned)CeilDiv(w, kSiftTile)), dim3(kSiftBlock), lds, s, out, (const float*)temp, hgt, w,
+                       d_taps + f.offset, f.W);
+  };
+  // ---- the octave's first level
+  if (q == 0) {
+    if (g.o_min < 0) {
+      hipLaunchKernelGGL(k_sift_upsample, SiftGrid(2 * (int64_t)width * height, kSiftBlock), dim3(kSiftBlock), 0, s, temp, image, width, height);
+      hipLaunchKernelGGL(k_sift_upsample, SiftGrid(4 * (int64_t)width * height, kSiftBlock), dim3(kSiftBlock), 0, s, gauss, (const float*)temp, height, 2 * width);
+      for (int d = -1; d > g.o_min; --d) {      // (the reference's arguments, as they stand)
+        const int dw = width << -d, dh = height << -d;
+        hipLaunchKernelGGL(k_sift_upsample, SiftGrid(2 * (int64_t)dw * dh, kSiftBlock), dim3(kSiftBlock), 0, s, temp, (const float*)gauss, dw, dh);
+        hipLaunchKernelGGL(k_sift_upsample, SiftGrid(4 * (int64_t)dw * dh, kSiftBlock), dim3(kSiftBlock), 0, s, gauss, (const float*)temp, dw, 2 * dh);
+      }
+    } else {
+      hipLaunchKernelGGL(k_sift_downsample, SiftGrid(lev, kSiftBlock), dim3(kSiftBlock), 0, s, gauss, image, width, w, hgt, 1 << g.o_min);
+    }
+  } else {
+    const SiftOctave& prev = lay.octaves[(size_t)q - 1];
+    const int s_best = std::min(g.s_min + g.S, g.s_max);
+    const float* from = pyramid + prev.gauss + (size_t)(s_best - g.s_min) * ((size_t)prev.w * prev.h);
+    hipLaunchKernelGGL(k_sift_downsample, SiftGrid(lev, kSiftBlock), dim3(kSiftBlock), 0, s, gauss, from, prev.w, w, hgt, 2);
+  }
+  const SiftFilter& f0 = filters.filters[q == 0 ? 0 : 1];
+  if (f0.W > 0) smooth(gauss, gauss, f0);
+  for (int lvl = 1; lvl < L; ++lvl) smooth(gauss + (size_t)lvl * lev, gauss + (size_t)(lvl - 1) * lev, filters.filters[(size_t)lvl + 1]);
+  hipLaunchKernelGGL(k_sift_dog, SiftGrid(lev * (L - 1), kSiftBlock), dim3(kSiftBlock), 0, s, dog, (const float*)gauss, lev, lev * (L - 1));
+}
+
+// every feature of one image of the last batch, before the cut: what pp_sift_extract_batch_features hands out
+struct SiftBatchFeatures {
+  std::vector<float> raw;
+  std::vector<int32_t> octave_level;
+  std::vector<double> angles;
+};
+
 }  // namespace ppsfm
 
 struct pp_sift_extractor_impl : ppsfm::DeviceHandle {
@@ -195,6 +361,7 @@ struct pp_sift_extractor_impl : ppsfm::DeviceHandle {
   ppsfm::SiftFeature* feats = nullptr;      float* raw = nullptr;      uint8_t* bytes = nullptr;      ppsfm::sift::DescriptorWindow* window = nullptr;      size_t cap_feats = 0;
   double* expn = nullptr;
   float* taps = nullptr;          size_t cap_taps = 0;
+  ppsfm::SiftWaveImage* wave_images = nullptr;      size_t cap_wave_images = 0;      // the image table of k_sift_describe_wave
   // the last extraction
   bool extracted = false;
   ppsfm::sift::Geometry geom{};
@@ -202,6 +369,8 @@ struct pp_sift_extractor_impl : ppsfm::DeviceHandle {
   std::vector<float> last_raw;
   std::vector<int32_t> last_octave_level;
   std::vector<double> last_angles;
+  // or the last batch: one entry per image (then `extracted` is false)
+  std::vector<ppsfm::SiftBatchFeatures> batch;
 };
 
 using namespace ppsfm;
@@ -224,6 +393,26 @@ int GrowBeside(DeviceBlocks& b, T** p, bool regrow, size_t count) {      // a bu
   if (*p && !regrow) return PP_OK;
   if (*p) b.Free(p);
   return b.Alloc(p, count);
+}
+
+// the counts of one image's extraction (R.cut set); the timing fields are the caller's
+void FillReport(const HostResult& R, const Geometry& g, pp_sift_extract_report* report) {
+  report->num_octaves = g.O;
+  report->num_levels = (int32_t)R.levels.size();
+  report->first_level_to_keep = R.cut.first_level_to_keep;
+  report->num_features_found = (int64_t)R.angles.size();
+  report->num_features = R.cut.num_features;
+  report->num_two_orientations = R.two_orientations;
+  report->num_windows_cut = R.windows_cut;
+  report->num_descriptors_skipped = R.descriptors_skipped;
+  for (size_t q = 0; q < R.octaves.size(); ++q) {
+    const OctaveCounts& c = R.octaves[q];
+    report->octave_width[q] = c.width; report->octave_height[q] = c.height;
+    report->octave_candidates[q] = c.num_candidates; report->octave_keypoints[q] = c.num_keypoints;
+    report->num_keypoints += c.num_keypoints; report->num_moved += c.moved;
+    report->num_rejected_peak += c.reject_peak; report->num_rejected_edge += c.reject_edge;
+    report->num_rejected_offset += c.reject_offset; report->num_rejected_bounds += c.reject_bounds;
+  }
 }
 
 Options FromC(const pp_sift_extract_options& c) {
@@ -276,47 +465,20 @@ int pp_sift_extract(pp_sift_extractor_handle h, const pp_sift_extract_options* o
   PP_REQUIRE(wrong.empty(), "%s: %s", where, wrong.c_str());
   PP_REQUIRE(h, "%s: null handle", where);
   const Geometry g = MakeGeometry(opt);
-  const int L = g.levels(), num_grad = g.S;      // Gaussian levels; gradient levels s_min + 1 .. s_max - 2
+  const int num_grad = g.S;      // gradient levels s_min + 1 .. s_max - 2
 
-  // the filters, one after the other: [0] the first octave's first level (or none), [1] a later octave's (none with the reference's geometry), then
-  // the levels s_min + 1 .. s_max
-  struct Filter { size_t offset; int W; };
-  std::vector<float> taps;
-  std::vector<Filter> filters;
-  auto add_filter = [&](double sigma) {
-    if (!(sigma > 0.0)) { filters.push_back(Filter{0, 0}); return; }
-    const std::vector<float> t = GaussTaps(sigma);
-    filters.push_back(Filter{taps.size(), (int)t.size() / 2});
-    taps.insert(taps.end(), t.begin(), t.end());
-  };
-  add_filter(FirstLevelSigma(g, true));
-  add_filter(FirstLevelSigma(g, false));
-  for (int s = g.s_min + 1; s <= g.s_max; ++s) add_filter(LevelSigma(g, s));
-  for (const Filter& f : filters) PP_REQUIRE(f.W <= kMaxFilterHalfWidth, "%s: a filter of half width %d", where, f.W);
-
-  // the octaves and their places in the pyramid
-  std::vector<SiftOctave> octaves((size_t)g.O);
-  size_t total = 0;
-  for (int q = 0; q < g.O; ++q) {
-    SiftOctave& oc = octaves[(size_t)q];
-    oc.o = g.o_min + q;
-    oc.w = ShiftLeft(width, -oc.o); oc.h = ShiftLeft(height, -oc.o);
-    oc.has_grad = oc.w >= 2 && oc.h >= 2;
-    const size_t lev = (size_t)oc.w * oc.h;
-    oc.gauss = total; total += lev * (size_t)L;
-    oc.dog = total; total += lev * (size_t)(L - 1);
-    oc.grad = total; total += 2 * lev * (size_t)num_grad;
-  }
-  const size_t nel0 = (size_t)octaves[0].w * octaves[0].h;
-  const size_t temp_offset = total;
-  total += nel0;
-  int max_rows = 1;
-  for (const SiftOctave& oc : octaves) max_rows = std::max(max_rows, g.S * oc.h);
-  const size_t rows_need = 2 * (size_t)max_rows + 2 + ScanScratchCount(max_rows);
+  SiftFilters filters;
+  PP_TRY(MakeSiftFilters(where, g, &filters));
+  const SiftLayout lay = LayoutOctaves(g, width, height);
+  std::vector<SiftOctave> octaves = lay.octaves;
+  const size_t total = lay.total, rows_need = lay.rows_need;
+  const int max_rows = lay.max_rows;
+  const std::vector<float>& taps = filters.taps;
 
   PP_HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   h->extracted = false;
+  h->batch.clear();
   PP_TRY(Grow(h->blocks, &h->pyramid, &h->cap_pyramid, total));
   {
     const bool regrow = !h->image || h->cap_image < (size_t)width * height;
@@ -342,16 +504,7 @@ int pp_sift_extract(pp_sift_extractor_handle h, const pp_sift_extract_options* o
     return timer.Begin();
   };
   auto phase_boundary = [&](int phase) -> int { return options->phase_timings ? close_span(phase) : PP_OK; };
-  auto grid = [](int64_t n, int block) { return dim3((unsigned)std::max<int64_t>(CeilDiv(n, block), 1)); };
-  auto smooth = [&](float* out, const float* in, int w, int hgt, const Filter& f) {
-    float* temp = h->pyramid + temp_offset;
-    const size_t lds = ((size_t)(kSiftTile + 2 * f.W) * kSiftPitch + 2 * (size_t)f.W + 1) * sizeof(float);
-    hipLaunchKernelGGL(k_sift_convolve, dim3((unsigned)CeilDiv(w, kSiftTile), (unsigned)CeilDiv(hgt, kSiftTile)), dim3(kSiftBlock), lds, s, temp, in, w, hgt,
-                       (const float*)(h->taps + f.offset), f.W);
-    hipLaunchKernelGGL(k_sift_convolve, dim3((unsigned)CeilDiv(hgt, kSiftTile), (unsigned)CeilDiv(w, kSiftTile)), dim3(kSiftBlock), lds, s, out, (const float*)temp, hgt, w,
-                       (const float*)(h->taps + f.offset), f.W);
-  };
-
+  auto grid = SiftGrid;
   HostResult R;      // the containers of the reference, filled octave by octave
   std::vector<Refined> refined;
   std::vector<Keypoint> keys;
@@ -370,30 +523,7 @@ int pp_sift_extract(pp_sift_extractor_handle h, const pp_sift_extract_options* o
     float* gauss = h->pyramid + oc.gauss;
     float* dog = h->pyramid + oc.dog;
     float* grad = h->pyramid + oc.grad;
-    float* temp = h->pyramid + temp_offset;
-    // ---- the octave's first level
-    if (q == 0) {
-      if (g.o_min < 0) {
-        hipLaunchKernelGGL(k_sift_upsample, grid(2 * (int64_t)width * height, kSiftBlock), dim3(kSiftBlock), 0, s, temp, (const float*)h->image, width, height);
-        hipLaunchKernelGGL(k_sift_upsample, grid(4 * (int64_t)width * height, kSiftBlock), dim3(kSiftBlock), 0, s, gauss, (const float*)temp, height, 2 * width);
-        for (int d = -1; d > g.o_min; --d) {      // (the reference's arguments, as they stand)
-          const int dw = width << -d, dh = height << -d;
-          hipLaunchKernelGGL(k_sift_upsample, grid(2 * (int64_t)dw * dh, kSiftBlock), dim3(kSiftBlock), 0, s, temp, (const float*)gauss, dw, dh);
-          hipLaunchKernelGGL(k_sift_upsample, grid(4 * (int64_t)dw * dh, kSiftBlock), dim3(kSiftBlock), 0, s, gauss, (const float*)temp, dw, 2 * dh);
-        }
-      } else {
-        hipLaunchKernelGGL(k_sift_downsample, grid(lev, kSiftBlock), dim3(kSiftBlock), 0, s, gauss, (const float*)h->image, width, w, hgt, 1 << g.o_min);
-      }
-    } else {
-      const SiftOctave& prev = octaves[(size_t)q - 1];
-      const int s_best = std::min(g.s_min + g.S, g.s_max);
-      const float* from = h->pyramid + prev.gauss + (size_t)(s_best - g.s_min) * ((size_t)prev.w * prev.h);
-      hipLaunchKernelGGL(k_sift_downsample, grid(lev, kSiftBlock), dim3(kSiftBlock), 0, s, gauss, from, prev.w, w, hgt, 2);
-    }
-    const Filter& f0 = filters[q == 0 ? 0 : 1];
-    if (f0.W > 0) smooth(gauss, gauss, w, hgt, f0);
-    for (int lvl = 1; lvl < L; ++lvl) smooth(gauss + (size_t)lvl * lev, gauss + (size_t)(lvl - 1) * lev, w, hgt, filters[(size_t)lvl + 1]);
-    hipLaunchKernelGGL(k_sift_dog, grid(lev * (L - 1), kSiftBlock), dim3(kSiftBlock), 0, s, dog, (const float*)gauss, lev, lev * (L - 1));
+    LaunchOctavePyramid(s, g, filters, (const float*)h->taps, lay, q, h->pyramid, (const float*)h->image, width, height);
     PP_TRY(phase_boundary(kPyramid));
     if (oc.has_grad)
       hipLaunchKernelGGL(k_sift_gradient, grid(lev * num_grad, kSiftBlock), dim3(kSiftBlock), 0, s, grad, (const float*)(gauss + lev), w, hgt, lev * num_grad);
@@ -512,22 +642,7 @@ int pp_sift_extract(pp_sift_extractor_handle h, const pp_sift_extract_options* o
 
   // ---- the host rule
   R.cut = SelectLevels(R.levels, opt.max_num_features);
-  report->num_octaves = g.O;
-  report->num_levels = (int32_t)R.levels.size();
-  report->first_level_to_keep = R.cut.first_level_to_keep;
-  report->num_features_found = (int64_t)R.angles.size();
-  report->num_features = R.cut.num_features;
-  report->num_two_orientations = R.two_orientations;
-  report->num_windows_cut = R.windows_cut;
-  report->num_descriptors_skipped = R.descriptors_skipped;
-  for (size_t q = 0; q < R.octaves.size(); ++q) {
-    const OctaveCounts& c = R.octaves[q];
-    report->octave_width[q] = c.width; report->octave_height[q] = c.height;
-    report->octave_candidates[q] = c.num_candidates; report->octave_keypoints[q] = c.num_keypoints;
-    report->num_keypoints += c.num_keypoints; report->num_moved += c.moved;
-    report->num_rejected_peak += c.reject_peak; report->num_rejected_edge += c.reject_edge;
-    report->num_rejected_offset += c.reject_offset; report->num_rejected_bounds += c.reject_bounds;
-  }
+  FillReport(R, g, report);
   for (int p = 0; p < 5; ++p) report->phase_ms[p] = options->phase_timings ? phase_ms[p] : 0.0;
   report->device_ms = timer.ms;
   h->geom = g;
@@ -601,5 +716,333 @@ int pp_sift_extract_features(pp_sift_extractor_handle h, float* raw, int32_t* oc
   if (n && angles) std::memcpy(angles, h->last_angles.data(), n * sizeof(double));
   return PP_OK;
 } PP_API_CATCH("pp_sift_extract_features")
+
+// K23: the images of a sub-batch go through the octaves in lock-step.  Every image has its own slice of the pyramid, of the grey and float images and
+// of the row counts, and the kernels of the single call run on those slices; what the host must know before it can go on - the candidate totals, the
+// refined candidates, the orientations, the descriptors - comes back for ALL images of the sub-batch in one download and one wait each.
+int pp_sift_extract_batch(pp_sift_extractor_handle h, const pp_sift_extract_options* options, int32_t num_images, const pp_sift_batch_image* images,
+                          int64_t workspace_bytes, pp_sift_batch_report* batch_report, pp_sift_extract_report* reports, int64_t capacity, float* keypoints,
+                          uint8_t* descriptors, int64_t* offsets) try {
+  const char* where = "pp_sift_extract_batch";
+  PP_REQUIRE(options && images && batch_report && reports && keypoints && offsets, "%s: null argument", where);
+  PP_REQUIRE(num_images >= 1, "%s: num_images %d", where, num_images);
+  PP_REQUIRE(capacity >= 0, "%s: negative capacity", where);
+  PP_REQUIRE(workspace_bytes >= 0, "%s: negative workspace_bytes", where);
+  const auto t_begin = Clock::now();
+  const Options opt = FromC(*options);
+  for (int32_t i = 0; i < num_images; ++i) {
+    PP_REQUIRE(images[i].grey, "%s: image %d: null argument", where, i);
+    const std::string wrong = CheckOptions(opt, images[i].width, images[i].height);
+    PP_REQUIRE(wrong.empty(), "%s: image %d: %s", where, i, wrong.c_str());
+  }
+  PP_REQUIRE(h, "%s: null handle", where);
+  const Geometry g = MakeGeometry(opt);
+  const int num_grad = g.S;
+  SiftFilters filters;
+  PP_TRY(MakeSiftFilters(where, g, &filters));
+  const size_t N = (size_t)num_images;
+  std::vector<SiftLayout> layouts(N);
+  std::vector<int64_t> bytes_per_image(N);
+  for (size_t i = 0; i < N; ++i) {
+    layouts[i] = LayoutOctaves(g, images[i].width, images[i].height);
+    const int64_t pixels = (int64_t)images[i].width * images[i].height;
+    bytes_per_image[i] = (int64_t)((layouts[i].total + layouts[i].rows_need) * sizeof(float)) + pixels * (int64_t)(sizeof(float) + 1);
+  }
+  const std::vector<int32_t> plan = PlanSiftBatches(bytes_per_image, workspace_bytes > 0 ? workspace_bytes : (int64_t)8 << 30);
+  const int num_sub_batches = (int)plan.size() - 1;
+
+  PP_HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  h->extracted = false;
+  h->batch.clear();
+  PP_TRY(Grow(h->blocks, &h->taps, &h->cap_taps, filters.taps.size()));
+  PP_TRY(Upload(h->taps, filters.taps.data(), filters.taps.size(), s));
+
+  StreamTimer timer(*h);
+  double phase_ms[5] = {0, 0, 0, 0, 0};
+  enum { kPyramid = 0, kDetect = 1, kGradient = 2, kOrient = 3, kDescribe = 4 };
+  auto close_span = [&](int phase) -> int {      // (as in pp_sift_extract: the wait)
+    PP_HIP_TRY(hipGetLastError());
+    PP_TRY(timer.End());
+    PP_HIP_TRY(hipStreamSynchronize(s));
+    const float before = timer.ms;
+    PP_TRY(timer.Add());
+    phase_ms[phase] += (double)(timer.ms - before);
+    return timer.Begin();
+  };
+  auto phase_boundary = [&](int phase) -> int { return options->phase_timings ? close_span(phase) : PP_OK; };
+
+  std::vector<HostResult> results(N);      // the containers of the reference, per image, filled octave by octave
+  int64_t workspace_used = 0;
+  const double threshold = 0.8 * opt.peak_threshold;
+  for (int b = 0; b < num_sub_batches; ++b) {
+    const size_t first = (size_t)plan[(size_t)b], n = (size_t)plan[(size_t)b + 1] - first;
+    // ---- the slices: pyramid (floats), image (pixels), rows (int32s; the n totals stand in front of the images' slices)
+    std::vector<size_t> pyr_off(n), img_off(n), rows_off(n);
+    size_t pyr_total = 0, img_total = 0, rows_total = n;
+    int64_t sub_bytes = 0;
+    for (size_t i = 0; i < n; ++i) {
+      pyr_off[i] = pyr_total; pyr_total += layouts[first + i].total;
+      img_off[i] = img_total; img_total += (size_t)images[first + i].width * images[first + i].height;
+      rows_off[i] = rows_total; rows_total += layouts[first + i].rows_need;
+      sub_bytes += bytes_per_image[first + i];
+    }
+    workspace_used = std::max(workspace_used, sub_bytes);
+    PP_TRY(Grow(h->blocks, &h->pyramid, &h->cap_pyramid, pyr_total));      // (the stream has drained: the call before, or the sub-batch before)
+    {
+      const bool regrow = !h->image || h->cap_image < img_total;
+      PP_TRY(Grow(h->blocks, &h->image, &h->cap_image, img_total));
+      PP_TRY(GrowBeside(h->blocks, &h->grey, regrow, h->cap_image));
+    }
+    PP_TRY(Grow(h->blocks, &h->rows, &h->cap_rows, rows_total));
+    PP_TRY(Grow(h->blocks, &h->wave_images, &h->cap_wave_images, n));
+    for (size_t i = 0; i < n; ++i) PP_TRY(Upload(h->grey + img_off[i], images[first + i].grey, (size_t)images[first + i].width * images[first + i].height, s));
+
+    std::vector<int32_t> totals(n), cand_off(n), key_off(n), num_keys(n), feat_off(n), num_feats(n);
+    std::vector<Refined> refined;
+    std::vector<Keypoint> keys;
+    std::vector<int32_t> num_angles, is_of_key, used;
+    std::vector<double> angles;
+    std::vector<SiftFeature> feats;
+    std::vector<SiftWaveImage> table(n);
+    std::vector<DescriptorWindow> window;
+
+    PP_TRY(timer.Begin());
+    for (size_t i = 0; i < n; ++i) {
+      const int64_t pixels = (int64_t)images[first + i].width * images[first + i].height;
+      hipLaunchKernelGGL(k_sift_load, SiftGrid(pixels, kSiftBlock), dim3(kSiftBlock), 0, s, pixels, (const uint8_t*)(h->grey + img_off[i]), h->image + img_off[i]);
+    }
+    for (int q = 0; q < g.O; ++q) {
+      const int o = g.o_min + q;
+      // ---- pyramid, gradient, candidate counts and their scan, image by image; then the n totals in one download
+      for (size_t i = 0; i < n; ++i)
+        LaunchOctavePyramid(s, g, filters, (const float*)h->taps, layouts[first + i], q, h->pyramid + pyr_off[i], (const float*)(h->image + img_off[i]),
+                            images[first + i].width, images[first + i].height);
+      PP_TRY(phase_boundary(kPyramid));
+      for (size_t i = 0; i < n; ++i) {
+        const SiftOctave& oc = layouts[first + i].octaves[(size_t)q];
+        const int64_t lev = (int64_t)oc.w * oc.h;
+        float* pyr = h->pyramid + pyr_off[i];
+        if (oc.has_grad)
+          hipLaunchKernelGGL(k_sift_gradient, SiftGrid(lev * num_grad, kSiftBlock), dim3(kSiftBlock), 0, s, pyr + oc.grad, (const float*)(pyr + oc.gauss + lev), oc.w, oc.h,
+                             lev * num_grad);
+      }
+      PP_TRY(phase_boundary(kGradient));
+      bool any_detect = false;
+      for (size_t i = 0; i < n; ++i) {
+        const SiftLayout& lay = layouts[first + i];
+        const SiftOctave& oc = lay.octaves[(size_t)q];
+        if (!(oc.w >= 3 && oc.h >= 3)) continue;
+        any_detect = true;
+        const int64_t lev = (int64_t)oc.w * oc.h;
+        const int rows = g.S * oc.h;
+        int32_t* row_count = h->rows + rows_off[i];
+        int32_t* row_start = row_count + lay.max_rows;
+        int32_t* scan_scratch = row_count + 2 * (size_t)lay.max_rows + 2;
+        hipLaunchKernelGGL(k_sift_detect_count, dim3((unsigned)rows), dim3(kSiftBlock), 0, s, (const float*)(h->pyramid + pyr_off[i] + oc.dog + lev), oc.w, oc.h, threshold,
+                           row_count);
+        const ScanJob<int32_t> job{row_count, row_start, h->rows + i};
+        LaunchExclusiveScan<int32_t>(s, rows, &job, 1, scan_scratch);
+      }
+      std::fill(totals.begin(), totals.end(), 0);
+      if (any_detect) {
+        PP_TRY(Download(totals.data(), (const int32_t*)h->rows, n, s));
+        PP_TRY(close_span(kDetect));
+      }
+      size_t num_cand = 0;
+      for (size_t i = 0; i < n; ++i) {
+        const SiftOctave& oc = layouts[first + i].octaves[(size_t)q];
+        if (!(oc.w >= 3 && oc.h >= 3)) totals[i] = 0;      // (its total was not written)
+        cand_off[i] = (int32_t)num_cand;
+        num_cand += (size_t)totals[i];
+      }
+      PP_REQUIRE(num_cand < ((size_t)1 << 31) / 3, "%s: %lld candidates in one octave of a sub-batch", where, (long long)num_cand);
+      // ---- scatter and refinement of every image into one candidate array
+      refined.assign(num_cand, Refined{});
+      if (num_cand > 0) {
+        {      // (the stream has drained)
+          const bool regrow = !h->cand || h->cap_cand < num_cand;
+          const size_t want = std::max<size_t>(num_cand, 2 * h->cap_cand);
+          if (regrow) { if (h->cand) h->blocks.Free(&h->cand); h->cap_cand = 0; PP_TRY(h->blocks.Alloc(&h->cand, 3 * want)); h->cap_cand = want; }
+          PP_TRY(GrowBeside(h->blocks, &h->refined, regrow, h->cap_cand));
+        }
+        for (size_t i = 0; i < n; ++i) {
+          if (totals[i] == 0) continue;
+          const SiftLayout& lay = layouts[first + i];
+          const SiftOctave& oc = lay.octaves[(size_t)q];
+          const int64_t lev = (int64_t)oc.w * oc.h;
+          const float* dog = h->pyramid + pyr_off[i] + oc.dog;
+          const int32_t* row_count = h->rows + rows_off[i];
+          int32_t* cand = h->cand + 3 * (size_t)cand_off[i];
+          hipLaunchKernelGGL(k_sift_detect_scatter, dim3((unsigned)(g.S * oc.h)), dim3(kSiftBlock), 0, s, dog + lev, oc.w, oc.h, g.s_min + 1, threshold, row_count,
+                             row_count + lay.max_rows, cand);
+          hipLaunchKernelGGL(k_sift_refine, SiftGrid(totals[i], kSiftLaneBlock), dim3(kSiftLaneBlock), 0, s, totals[i], (const int32_t*)cand, dog, oc.w, oc.h, g.s_min,
+                             g.s_max, opt.peak_threshold, opt.edge_threshold, h->refined + cand_off[i]);
+        }
+        PP_TRY(Download(refined.data(), (const Refined*)h->refined, num_cand, s));
+        PP_TRY(close_span(kDetect));
+      }
+      keys.clear();
+      for (size_t i = 0; i < n; ++i) {
+        const SiftOctave& oc = layouts[first + i].octaves[(size_t)q];
+        OctaveCounts counts{oc.w, oc.h, totals[i], 0, 0, 0, 0, 0, 0};
+        key_off[i] = (int32_t)keys.size();
+        for (int32_t c = 0; c < totals[i]; ++c) {
+          const Refined& r = refined[(size_t)cand_off[i] + (size_t)c];
+          counts.moved += r.moves > 0;
+          counts.reject_peak += r.reject == 1; counts.reject_edge += r.reject == 2; counts.reject_offset += r.reject == 3; counts.reject_bounds += r.reject == 4;
+          if (r.good) keys.push_back(MakeKeypoint(r, o, g));
+        }
+        num_keys[i] = (int32_t)keys.size() - key_off[i];
+        counts.num_keypoints = num_keys[i];
+        results[first + i].octaves.push_back(counts);
+      }
+      const size_t K = keys.size();
+      if (K == 0) continue;
+      // ---- orientations: the keys of every image uploaded together
+      const double xper = std::ldexp(1.0, o);
+      {
+        const bool regrow = !h->keys || h->cap_keys < K;
+        const size_t want = std::max<size_t>(K, 2 * h->cap_keys);
+        if (regrow) { if (h->keys) h->blocks.Free(&h->keys); h->cap_keys = 0; PP_TRY(h->blocks.Alloc(&h->keys, want)); h->cap_keys = want; }
+        PP_TRY(GrowBeside(h->blocks, &h->num_angles, regrow, h->cap_keys));
+        PP_TRY(GrowBeside(h->blocks, &h->angles, regrow, kMaxAngles * h->cap_keys));
+      }
+      if (!opt.upright || descriptors) PP_TRY(Upload(h->keys, keys.data(), K, s));
+      num_angles.assign(K, 1);
+      angles.assign(kMaxAngles * K, 0.0);
+      if (!opt.upright) {
+        for (size_t i = 0; i < n; ++i) {
+          if (num_keys[i] == 0) continue;
+          const SiftOctave& oc = layouts[first + i].octaves[(size_t)q];
+          hipLaunchKernelGGL(k_sift_orient, SiftGrid(num_keys[i], kSiftLaneBlock), dim3(kSiftLaneBlock), 0, s, num_keys[i], (const Keypoint*)(h->keys + key_off[i]),
+                             (const float*)(h->pyramid + pyr_off[i] + oc.grad), oc.w, oc.h, g.s_min, g.s_max, xper, (const double*)h->expn, h->num_angles + key_off[i],
+                             h->angles + kMaxAngles * (size_t)key_off[i]);
+        }
+        PP_TRY(Download(num_angles.data(), (const int32_t*)h->num_angles, K, s));
+        PP_TRY(Download(angles.data(), (const double*)h->angles, kMaxAngles * K, s));
+        PP_TRY(close_span(kOrient));
+      }
+      // ---- the features of the octave: per image into its containers, all of them into one descriptor launch
+      feats.clear();
+      for (size_t i = 0; i < n; ++i) {
+        HostResult& R = results[first + i];
+        const size_t K_i = (size_t)num_keys[i], k0 = (size_t)key_off[i];
+        feat_off[i] = (int32_t)feats.size();
+        is_of_key.resize(K_i); used.resize(K_i);
+        for (size_t j = 0; j < K_i; ++j) {
+          const Keypoint& key = keys[k0 + j];
+          is_of_key[j] = key.is;
+          used[j] = std::min(num_angles[k0 + j], opt.max_num_orientations);
+          R.two_orientations += used[j] >= 2;
+          for (int a = 0; a < used[j]; ++a) {
+            const double angle = angles[kMaxAngles * (k0 + j) + (size_t)a];
+            float row[4];
+            FeatureRow(key, angle, row);
+            R.keypoints.insert(R.keypoints.end(), row, row + 4);
+            R.octave_level.push_back(o); R.octave_level.push_back(key.is);
+            R.angles.push_back(angle);
+            feats.push_back(SiftFeature{(int32_t)(k0 + j), (int32_t)i, angle, std::sin(angle), std::cos(angle)});
+          }
+        }
+        num_feats[i] = (int32_t)feats.size() - feat_off[i];
+        AppendLevels(o, is_of_key.data(), used.data(), (int64_t)K_i, &R.levels);
+      }
+      const size_t F = feats.size();
+      if (!descriptors || F == 0) {
+        for (size_t i = 0; i < n; ++i) {
+          HostResult& R = results[first + i];
+          R.raw.resize(R.raw.size() + kDescBins * (size_t)num_feats[i], 0.f);
+          R.descriptors.resize(R.descriptors.size() + kDescBins * (size_t)num_feats[i], 0);
+        }
+        continue;
+      }
+      {
+        const bool regrow = !h->feats || h->cap_feats < F;
+        const size_t want = std::max<size_t>(F, 2 * h->cap_feats);
+        if (regrow) { if (h->feats) h->blocks.Free(&h->feats); h->cap_feats = 0; PP_TRY(h->blocks.Alloc(&h->feats, want)); h->cap_feats = want; }
+        PP_TRY(GrowBeside(h->blocks, &h->raw, regrow, kDescBins * h->cap_feats));
+        PP_TRY(GrowBeside(h->blocks, &h->bytes, regrow, kDescBins * h->cap_feats));
+        PP_TRY(GrowBeside(h->blocks, &h->window, regrow, h->cap_feats));
+      }
+      for (size_t i = 0; i < n; ++i) {
+        const SiftOctave& oc = layouts[first + i].octaves[(size_t)q];
+        table[i] = SiftWaveImage{h->pyramid + pyr_off[i] + oc.grad, oc.w, oc.h, xper};
+      }
+      PP_TRY(Upload(h->wave_images, table.data(), n, s));
+      PP_TRY(Upload(h->feats, feats.data(), F, s));
+      hipLaunchKernelGGL(k_sift_describe_wave, dim3((unsigned)F), dim3(kWave), 0, s, (const SiftFeature*)h->feats, (const Keypoint*)h->keys,
+                         (const SiftWaveImage*)h->wave_images, g.s_min, g.s_max, (const double*)h->expn, (int)opt.normalization, h->raw, h->bytes, h->window);
+      window.resize(F);
+      for (size_t i = 0; i < n; ++i) {      // each image's rows straight into its containers (no second copy on the host), then the one wait
+        HostResult& R = results[first + i];
+        const size_t f0 = (size_t)feat_off[i], F_i = (size_t)num_feats[i], at = R.raw.size();
+        R.raw.resize(at + kDescBins * F_i);
+        R.descriptors.resize(at + kDescBins * F_i);
+        PP_TRY(Download(R.raw.data() + at, (const float*)(h->raw + kDescBins * f0), kDescBins * F_i, s));
+        PP_TRY(Download(R.descriptors.data() + at, (const uint8_t*)(h->bytes + kDescBins * f0), kDescBins * F_i, s));
+      }
+      PP_TRY(Download(window.data(), (const DescriptorWindow*)h->window, F, s));
+      PP_TRY(close_span(kDescribe));
+      for (size_t i = 0; i < n; ++i) {
+        HostResult& R = results[first + i];
+        for (size_t f = (size_t)feat_off[i]; f < (size_t)feat_off[i] + (size_t)num_feats[i]; ++f) { R.windows_cut += window[f].cut; R.descriptors_skipped += !window[f].computed; }
+      }
+    }
+    PP_HIP_TRY(hipGetLastError());
+    PP_TRY(timer.End());
+    PP_HIP_TRY(hipStreamSynchronize(s));
+    PP_TRY(timer.Add());
+  }
+
+  // ---- the host rule, per image
+  std::memset(batch_report, 0, sizeof(*batch_report));
+  offsets[0] = 0;
+  for (size_t i = 0; i < N; ++i) {
+    HostResult& R = results[i];
+    R.cut = SelectLevels(R.levels, opt.max_num_features);
+    std::memset(&reports[i], 0, sizeof(reports[i]));
+    FillReport(R, g, &reports[i]);
+    offsets[i + 1] = offsets[i] + R.cut.num_features;
+  }
+  batch_report->num_images = num_images;
+  batch_report->num_sub_batches = num_sub_batches;
+  batch_report->num_features = offsets[N];
+  batch_report->workspace_bytes = workspace_used;
+  for (int p = 0; p < 5; ++p) batch_report->phase_ms[p] = options->phase_timings ? phase_ms[p] : 0.0;
+  batch_report->device_ms = timer.ms;
+  h->batch.resize(N);
+  for (size_t i = 0; i < N; ++i) {
+    h->batch[i].raw = std::move(results[i].raw);
+    h->batch[i].octave_level = std::move(results[i].octave_level);
+    h->batch[i].angles = std::move(results[i].angles);
+  }
+  batch_report->total_ms = MsSince(t_begin);
+  PP_REQUIRE(capacity >= offsets[N], "%s: capacity %lld for %lld features", where, (long long)capacity, (long long)offsets[N]);
+  for (size_t i = 0; i < N; ++i) {
+    const HostResult& R = results[i];
+    const size_t from = (size_t)R.cut.first_feature, count = (size_t)R.cut.num_features, at = (size_t)offsets[i];
+    if (count) std::memcpy(keypoints + 4 * at, R.keypoints.data() + 4 * from, 4 * count * sizeof(float));
+    if (count && descriptors) std::memcpy(descriptors + kDescBins * at, R.descriptors.data() + kDescBins * from, kDescBins * count);
+  }
+  batch_report->total_ms = MsSince(t_begin);
+  return PP_OK;
+} PP_API_CATCH("pp_sift_extract_batch")
+
+int pp_sift_extract_batch_features(pp_sift_extractor_handle h, int32_t image, float* raw, int32_t* octave_level, double* angles, int64_t capacity,
+                                   int64_t* num) try {
+  const char* where = "pp_sift_extract_batch_features";
+  PP_REQUIRE(h && num, "%s: null argument", where);
+  PP_REQUIRE(!h->batch.empty(), "%s: no batch on this handle", where);
+  PP_REQUIRE(image >= 0 && (size_t)image < h->batch.size(), "%s: image %d of %lld", where, image, (long long)h->batch.size());
+  const SiftBatchFeatures& b = h->batch[(size_t)image];
+  const size_t n = b.angles.size();
+  *num = (int64_t)n;
+  PP_REQUIRE(capacity >= *num, "%s: capacity %lld for %lld features", where, (long long)capacity, (long long)*num);
+  if (n && raw) std::memcpy(raw, b.raw.data(), kDescBins * n * sizeof(float));
+  if (n && octave_level) std::memcpy(octave_level, b.octave_level.data(), 2 * n * sizeof(int32_t));
+  if (n && angles) std::memcpy(angles, b.angles.data(), n * sizeof(double));
+  return PP_OK;
+} PP_API_CATCH("pp_sift_extract_batch_features")
 
 }  // extern "C"

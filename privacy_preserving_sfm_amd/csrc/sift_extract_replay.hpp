@@ -5,7 +5,10 @@
 //     descriptor's rotation (sin, cos).  The device never evaluates one of these, so the host's libm is the only one in the result;
 //   - the per-level containers, level_num_features (a keypoint without an orientation counts) and the max_num_features cut from the coarsest level
 //     down (sift.cc:534-570);
-//   - ExtractOnHost: the whole extraction run serially through the functions of sift_core.hpp - the CPU mirror of sift_extract.hip.
+//   - ExtractOnHost: the whole extraction run serially through the functions of sift_core.hpp - the CPU mirror of sift_extract.hip, with the
+//     descriptor by either route: Descriptor() as the lane-per-feature kernel calls it, or the wavefront scheme of k_sift_describe_wave replayed
+//     with 64 "lanes" in a loop;
+//   - PlanSiftBatches: how pp_sift_extract_batch splits its images into sub-batches under a workspace target.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -170,7 +173,55 @@ struct HostResult {
   std::vector<OctaveCounts> octaves;
   Cut cut{0, 0, 0};
   int64_t two_orientations = 0, windows_cut = 0, descriptors_skipped = 0;
+  std::vector<DescriptorWindow> windows;      // N (with descriptors)
+  std::vector<int32_t> window_pixels;         // N: the pixels of each descriptor's window
 };
+
+// Consecutive images in input order, taken greedily while the sum of their bytes stays within the target; an image that exceeds the target on its
+// own runs alone.  -> the first image of every sub-batch, then the number of images: sub-batch b is [out[b], out[b + 1]).
+inline std::vector<int32_t> PlanSiftBatches(const std::vector<int64_t>& bytes_per_image, int64_t target) {
+  std::vector<int32_t> first;
+  int64_t sum = 0;
+  for (size_t i = 0; i < bytes_per_image.size(); ++i) {
+    const int64_t b = bytes_per_image[i];
+    if (first.empty() || b > target - sum) { first.push_back((int32_t)i); sum = 0; }      // (sum <= target, or the sub-batch is one oversized image)
+    sum = b > target ? target : sum + b;
+  }
+  first.push_back((int32_t)bytes_per_image.size());
+  return first;
+}
+
+constexpr int kWaveLanes = 64;
+
+// Descriptor() + FinishDescriptor() by the scheme of k_sift_describe_wave, serially: chunks of 64 window pixels in scan order are staged (the array
+// in place of LDS), then each of the 64 "lanes" folds the staged pixels, in order, into the two bins it owns; the norms run over the 128 entries.
+inline DescriptorWindow DescriptorByWave(const float* grad, int w, int h, int s_min, int s_max, const Keypoint& k, double xper, double angle0, double st0,
+                                         double ct0, const double* expn, int normalization, float* descr, uint8_t* bytes) {
+  const DescriptorFrame f = MakeDescriptorFrame(w, h, s_min, s_max, k, xper);
+  float hist[kDescBins];
+  for (int i = 0; i < kDescBins; ++i) hist[i] = 0.f;
+  const int n = DescriptorWindowPixels(f), nx = f.x1 - f.x0 + 1;
+  DescriptorTap staged[kWaveLanes];
+  for (int base = 0; base < n; base += kWaveLanes) {
+    const int m = std::min(kWaveLanes, n - base);
+    for (int lane = 0; lane < m; ++lane) {
+      const int p = base + lane, dxi = f.x0 + p % nx, dyi = f.y0 + p / nx;
+      const float* g = grad + 2 * (f.xi + dxi) + (int64_t)(2 * w) * (f.yi + dyi);
+      staged[lane] = DescriptorSample(f, angle0, st0, ct0, expn, dxi, dyi, g[0], g[1]);
+    }
+    for (int lane = 0; lane < kWaveLanes; ++lane)
+      for (int j = 0; j < m; ++j) DescriptorFold(staged[j], ((lane >> 2) & 3) - 2, (lane >> 4) - 2, 2 * (lane & 3), &hist[2 * lane], &hist[2 * lane + 1]);
+  }
+  float norm = HistogramNorm(hist);
+  for (int i = 0; i < kDescBins; ++i) hist[i] = ClampBin(hist[i] / norm);
+  norm = HistogramNorm(hist);
+  for (int i = 0; i < kDescBins; ++i) descr[i] = hist[i] / norm;
+  norm = FinishNorm(descr, normalization);
+  for (int i = 0; i < kDescBins; ++i) bytes[UbcIndex(i)] = FinishByte(descr[i], norm, normalization);
+  return f.win;
+}
+
+enum class DescriptorRoute { kLane, kWave };      // Descriptor() as it stands / the wavefront scheme
 
 // name, element size, count, data
 using StageSink = std::function<void(const std::string&, size_t, size_t, const void*)>;
@@ -195,7 +246,8 @@ inline void UpsampleRowsTransposed(float* dst, const float* src, int w, int h) {
     for (int X = 0; X < 2 * w; ++X) dst[(int64_t)X * h + y] = UpsampleRowValue(src + (int64_t)y * w, w, X);
 }
 
-inline HostResult ExtractOnHost(const Options& opt, int width, int height, const uint8_t* grey, bool want_descriptors, const StageSink& sink) {
+inline HostResult ExtractOnHost(const Options& opt, int width, int height, const uint8_t* grey, bool want_descriptors, const StageSink& sink,
+                                DescriptorRoute route = DescriptorRoute::kLane) {
   HostResult R;
   const Geometry g = MakeGeometry(opt);
   const std::vector<double> expn = ExpnTable();
@@ -292,10 +344,17 @@ inline HostResult ExtractOnHost(const Options& opt, int width, int height, const
         R.angles.push_back(angles[a]);
         if (!want_descriptors) continue;
         float d[kDescBins];
-        const DescriptorWindow win = Descriptor(level, w, h, g.s_min, g.s_max, k, xper, angles[a], std::sin(angles[a]), std::cos(angles[a]), expn.data(), d);
-        R.windows_cut += win.cut; R.descriptors_skipped += !win.computed;
         uint8_t u[kDescBins];
-        FinishDescriptor(d, opt.normalization, u);
+        DescriptorWindow win;
+        if (route == DescriptorRoute::kWave) {
+          win = DescriptorByWave(level, w, h, g.s_min, g.s_max, k, xper, angles[a], std::sin(angles[a]), std::cos(angles[a]), expn.data(), opt.normalization, d, u);
+        } else {
+          win = Descriptor(level, w, h, g.s_min, g.s_max, k, xper, angles[a], std::sin(angles[a]), std::cos(angles[a]), expn.data(), d);
+          FinishDescriptor(d, opt.normalization, u);
+        }
+        R.windows_cut += win.cut; R.descriptors_skipped += !win.computed;
+        R.windows.push_back(win);
+        R.window_pixels.push_back(DescriptorWindowPixels(MakeDescriptorFrame(w, h, g.s_min, g.s_max, k, xper)));
         R.raw.insert(R.raw.end(), d, d + kDescBins);
         R.descriptors.insert(R.descriptors.end(), u, u + kDescBins);
       }

@@ -1021,13 +1021,15 @@ def sift_extract_options(**kw):
 
 class SiftExtractor(_Handle):
     """pp_sift_extractor_handle (K21): extract() is ExtractSiftFeaturesCPU for one grey image; the handle's workspace grows to the largest image seen
-    and keeps the pyramid of the last extraction for stage(), candidates() and features()."""
+    and keeps the pyramid of the last extraction for stage(), candidates() and features().  extract_batch() is the same for a sequence of images in
+    one call (K23); batch_features(i) reads its results."""
     _destroy = "pp_sift_extractor_destroy"
 
     def __init__(self, device=0):
         super().__init__()
         check(_capi.lib().pp_sift_extractor_create(int(device), C.byref(self._h)))
         self.last_report = None
+        self.last_batch_report = None
 
     def extract(self, image, options=None, want_descriptors=True, capacity=None):
         """image [H, W] uint8 -> (keypoints [N, 4] float32 (x, y, scale, orientation), descriptors [N, 128] uint8 in UBC order or None, report).
@@ -1081,6 +1083,52 @@ class SiftExtractor(_Handle):
         n = num.value
         raw, ol, ang = np.zeros((max(n, 1), 128), dtype=np.float32), np.zeros((max(n, 1), 2), dtype=np.int32), np.zeros(max(n, 1))
         check(_capi.lib().pp_sift_extract_features(self._h, ptr(raw, C.POINTER(C.c_float)), ptr(ol, _capi.c_ip), dp(ang), n, C.byref(num)))
+        return raw[:n], ol[:n], ang[:n]
+
+    def extract_batch(self, images, options=None, want_descriptors=True, workspace_bytes=0, capacity=None):
+        """pp_sift_extract_batch: images, a sequence of [H, W] uint8 arrays of any sizes -> [(keypoints, descriptors or None, report)] per image, each
+        what extract() gives for that image alone; last_batch_report is the batch's.  The images go through the octaves together and their descriptors
+        through one launch per octave.  workspace_bytes: the target for the pyramids held at once (0: 8 GiB); more images than fit run in consecutive
+        groups, with the same result.  capacity None: the call is repeated with the reported need when the first guess was too small.  Afterwards
+        stage(), candidates() and features() raise until the next extract(); batch_features(i) reads the batch."""
+        ims = []
+        for image in images:
+            im = np.asarray(image)
+            if im.dtype != np.uint8 or im.ndim != 2:
+                raise ValueError("every image is an [H, W] uint8 array")
+            ims.append(np.ascontiguousarray(im))
+        n = len(ims)
+        table = (_capi.SiftBatchImage * max(n, 1))()
+        for i, im in enumerate(ims):
+            table[i].width, table[i].height, table[i].grey = int(im.shape[1]), int(im.shape[0]), ptr(im, _capi.c_u8p)
+        o = options or sift_extract_options()
+        guess = min(n * min(2 * int(o.max_num_features), 1 << 16), 1 << 22) if capacity is None else int(capacity)
+        for cap in (guess, None):
+            brep, reps, offsets = _capi.SiftBatchReport(), (_capi.SiftExtractReport * max(n, 1))(), np.full(n + 1, -1, dtype=np.int64)
+            if cap is None:
+                cap = int(self.last_batch_report.num_features)
+            kp = np.zeros((max(cap, 1), 4), dtype=np.float32)
+            desc = np.zeros((max(cap, 1), 128), dtype=np.uint8) if want_descriptors else None
+            rc = _capi.lib().pp_sift_extract_batch(self._h, C.byref(o), n, table, int(workspace_bytes), C.byref(brep), reps, cap,
+                                                   ptr(kp, C.POINTER(C.c_float)), ptr(desc, _capi.c_u8p), ptr(offsets, C.POINTER(C.c_int64)))
+            if rc == 0 or capacity is not None or offsets[n] <= cap:      # (offsets[n] stays -1 where the arguments were refused)
+                break
+            self.last_batch_report = brep
+        check(rc)
+        self.last_batch_report = brep
+        out = []
+        for i in range(n):
+            a, b = int(offsets[i]), int(offsets[i + 1])
+            out.append((kp[a:b].copy(), None if desc is None else desc[a:b].copy(), reps[i]))
+        return out
+
+    def batch_features(self, image):
+        """features() for image `image` of the last extract_batch"""
+        num = C.c_int64()
+        _capi.lib().pp_sift_extract_batch_features(self._h, int(image), None, None, None, 0, C.byref(num))
+        n = num.value
+        raw, ol, ang = np.zeros((max(n, 1), 128), dtype=np.float32), np.zeros((max(n, 1), 2), dtype=np.int32), np.zeros(max(n, 1))
+        check(_capi.lib().pp_sift_extract_batch_features(self._h, int(image), ptr(raw, C.POINTER(C.c_float)), ptr(ol, _capi.c_ip), dp(ang), n, C.byref(num)))
         return raw[:n], ol[:n], ang[:n]
 
 

@@ -470,17 +470,42 @@ def ExtractSiftFeatures(image_uint8, options=None, device=0, extractor=None, as_
     return [FeatureKeypoint(r[0], r[1], r[2], r[3]) for r in kp], desc
 
 
-def extract_features_to_lines(images, cameras, bitmaps, options=None, aligned_line_ratio=DEFAULT_ALIGNED_LINE_RATIO, seed=0, device=0):
+def ExtractSiftFeaturesBatch(images_uint8, options=None, device=0, extractor=None, as_arrays=False):
+    """ExtractSiftFeatures for a sequence of grey images of any sizes in one device call (SiftExtractor.extract_batch) -> a list of what
+    ExtractSiftFeatures returns, image by image, with the same values."""
+    from .device import SiftExtractor
+    options = options or SiftExtractionOptions()
+    if not options.Check():
+        raise ValueError("SiftExtractionOptions.Check() failed")
+    o = options.device_options()
+    ex = extractor or SiftExtractor(device=device)
+    try:
+        results = ex.extract_batch(images_uint8, o)
+    finally:
+        if extractor is None:
+            ex.close()
+    if as_arrays:
+        return [(kp, desc) for kp, desc, _ in results]
+    return [([FeatureKeypoint(r[0], r[1], r[2], r[3]) for r in kp], desc) for kp, desc, _ in results]
+
+
+def extract_features_to_lines(images, cameras, bitmaps, options=None, aligned_line_ratio=DEFAULT_ALIGNED_LINE_RATIO, seed=0, device=0, batched=True):
     """Image arrays to what the matcher and the graph builder take.  images: bundle_adjustment.Image objects; cameras as for generate_line_features;
-    bitmaps: {image_id: [H, W] uint8}.  Per image ExtractSiftFeatures, then generate_line_features_on_device over all of them (it fills image.lines).
+    bitmaps: {image_id: [H, W] uint8}.  ExtractSiftFeaturesBatch over the images (batched=False: ExtractSiftFeatures image by image - the same arrays),
+    then generate_line_features_on_device over all of them (it fills image.lines).
     -> dict(keypoints {image_id: [N, 4] float32}, descriptors {image_id: [N, 128] uint8}, num_lines {image_id: N}, lines: the line report).
     Line index = keypoint index = descriptor row."""
     from .device import SiftExtractor
     ex = SiftExtractor(device=device)
     keypoints, descriptors = {}, {}
     try:
-        for im in images:
-            keypoints[im.image_id], descriptors[im.image_id] = ExtractSiftFeatures(bitmaps[im.image_id], options, extractor=ex, as_arrays=True)
+        if batched and len(images) > 0:
+            found = ExtractSiftFeaturesBatch([bitmaps[im.image_id] for im in images], options, extractor=ex, as_arrays=True)
+            for im, (kp, desc) in zip(images, found):
+                keypoints[im.image_id], descriptors[im.image_id] = kp, desc
+        else:
+            for im in images:
+                keypoints[im.image_id], descriptors[im.image_id] = ExtractSiftFeatures(bitmaps[im.image_id], options, extractor=ex, as_arrays=True)
     finally:
         ex.close()
     rep = generate_line_features_on_device(images, cameras, keypoints, aligned_line_ratio=aligned_line_ratio, seed=seed, device=device)
