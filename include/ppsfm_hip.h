@@ -1111,6 +1111,10 @@ int pp_sift_match_pairs(pp_sift_handle h, const pp_sift_match_options* options, 
 /* The one-way scan of image1's features against image2's (K17a alone), N1 entries each: best = the largest dist, best_j = the lowest index that attains
  * it (-1: no positive dist), second = the second largest with multiplicity.  For tests and for a caller with another rule on top. */
 int pp_sift_top2(pp_sift_handle h, int32_t image1, int32_t image2, int32_t* best_j, int32_t* best, int32_t* second);
+/* The uint8 rows of one image of a handle, downloaded: descriptors is capacity x 128.  For a handle from pp_sift_create these are the bytes it was
+ * given, for one from pp_sift_extract_to_matcher the bytes pp_sift_extract_batch returns for that image.  *num = the image's rows either way;
+ * PP_ERR_INVALID for a null handle or num, an image outside the handle (then *num is untouched) or capacity < *num. */
+int pp_sift_get_descriptors(pp_sift_handle h, int32_t image, uint8_t* descriptors, int64_t capacity, int64_t* num);
 /* The integers the device compares (host only, needs no device): the distance rule passes iff best >= d_min (and best >= 1), the ratio rule iff
  * min(second, 262144) <= table[min(best, 262144) - d_min] (-1: never).  *count = 262144 - d_min + 1 entries; table may be NULL to ask for the count,
  * else capacity >= *count.  PP_ERR_INTERNAL when this host's acosf is not monotonic (csrc/sift_match_replay.hpp). */
@@ -1369,6 +1373,26 @@ int pp_sift_extract_batch(pp_sift_extractor_handle h, const pp_sift_extract_opti
  * (a pp_sift_extract since then discards it) or for an image outside it. */
 int pp_sift_extract_batch_features(pp_sift_extractor_handle h, int32_t image, float* raw, int32_t* octave_level, double* angles, int64_t capacity,
                                    int64_t* num);
+
+/* ---- a batch of images straight into a matcher (K24) -------------------------------------------------------------------------------------------- */
+/* pp_sift_extract_batch for the case in which the features go to pp_sift_match_pairs: keypoints, offsets, reports, the argument checks, the groups
+ * under workspace_bytes and the capacity rule are that call's.  There is no descriptor output on the host: *matcher becomes a NEW pp_sift_handle on
+ * the extractor's device whose image i holds exactly the rows offsets[i] .. offsets[i + 1], in the state pp_sift_create would leave it in had it been
+ * given the descriptors pp_sift_extract_batch returns - byte for byte (pp_sift_get_descriptors reads them).  Every pp_sift_* call works on it; the
+ * caller destroys it with pp_sift_destroy, before or after the extractor.
+ * WHAT IS NOT COMPUTED: max_num_features selects levels by their KEYPOINT counts, which are known after refinement.  A group therefore goes through
+ * its octaves up to the keypoints first (two waits per octave), the cut is made on the host, and only the kept keypoints get orientations (one wait
+ * per group) and descriptors: ONE launch per group over all octaves, a wavefront per feature with the order rule of pp_sift_extract_batch, which
+ * writes each row where the matcher reads it.  2 x octaves + 2 waits per group; no float descriptor and no dropped feature leaves the device.
+ * REPORTS: as pp_sift_extract_batch fills them, except that num_features_found, num_two_orientations, num_windows_cut and num_descriptors_skipped
+ * count the KEPT containers only (num_features_found == num_features): the others were never computed.  The two are equal where nothing is cut.
+ * AFTER THE CALL the extractor holds neither a single extraction nor a batch: the stage, candidate and feature readers and
+ * pp_sift_extract_batch_features are PP_ERR_INVALID until the next pp_sift_extract or pp_sift_extract_batch.
+ * ERRORS: those of pp_sift_extract_batch (descriptors aside), and a null matcher.  On any error *matcher is NULL and nothing stays allocated; with a
+ * capacity too small batch_report, reports and offsets are filled as there. */
+int pp_sift_extract_to_matcher(pp_sift_extractor_handle h, const pp_sift_extract_options* options, int32_t num_images,
+                               const pp_sift_batch_image* images, int64_t workspace_bytes, pp_sift_batch_report* batch_report,
+                               pp_sift_extract_report* reports, int64_t capacity, float* keypoints, int64_t* offsets, pp_sift_handle* matcher);
 
 #ifdef __cplusplus
 }

@@ -299,11 +299,13 @@ _EXPORTS = [
     "pp_tracks_filter_points", "pp_tracks_filter_negative_depth", "pp_tracks_filter_images",
     "pp_init_sets_options_default", "pp_tracks_find_initial_sets", "pp_tracks_bundle_setup",
     "pp_sift_match_options_default", "pp_sift_create", "pp_sift_destroy", "pp_sift_match_pairs", "pp_sift_top2", "pp_sift_match_thresholds",
+    "pp_sift_get_descriptors",
     "pp_corr_graph_create", "pp_corr_graph_destroy", "pp_corr_graph_build", "pp_corr_graph_num_entries", "pp_corr_graph_get", "pp_corr_graph_pair_counts",
     "pp_line_features_options_default", "pp_line_features_from_keypoints",
     "pp_pairs_create", "pp_pairs_destroy", "pp_pairs_spatial", "pp_pairs_transitive", "pp_pairs_num", "pp_pairs_get",
     "pp_sift_extract_options_default", "pp_sift_extractor_create", "pp_sift_extractor_destroy", "pp_sift_extract", "pp_sift_extract_stage",
     "pp_sift_extract_candidates", "pp_sift_extract_features", "pp_sift_extract_batch", "pp_sift_extract_batch_features",
+    "pp_sift_extract_to_matcher",
     "pp_fourview2d_evaluate", "pp_fourview2d_evaluate_points", "pp_fourview2d_default_frames", "pp_fourview2d_minimal_batch", "pp_fourview2d_nonminimal_batch", "pp_fourview2d_least_squares", "pp_fourview2d_lomsac",
 ]
 
@@ -430,6 +432,7 @@ def lib():
     L.pp_sift_match_pairs.argtypes = [C.c_void_p, C.POINTER(SiftMatchOptions), C.c_int64, c_ip, C.POINTER(SiftMatchReport), C.POINTER(C.c_int64), c_ip, C.c_int64]
     L.pp_sift_top2.argtypes = [C.c_void_p, C.c_int32, C.c_int32, c_ip, c_ip, c_ip]
     L.pp_sift_match_thresholds.argtypes = [C.POINTER(SiftMatchOptions), c_ip, c_ip, C.c_int64, C.POINTER(C.c_int64)]
+    L.pp_sift_get_descriptors.argtypes = [C.c_void_p, C.c_int32, c_u8p, C.c_int64, C.POINTER(C.c_int64)]
     L.pp_corr_graph_create.argtypes = [C.c_int32, c_ip, C.c_int, C.POINTER(C.c_void_p)]
     L.pp_corr_graph_destroy.argtypes = [C.c_void_p]
     L.pp_corr_graph_build.argtypes = [C.c_void_p, C.c_int32, C.c_int64, c_ip, C.POINTER(C.c_int64), c_ip, C.POINTER(CorrGraphReport)]
@@ -461,6 +464,8 @@ def lib():
     L.pp_sift_extract_batch.argtypes = [C.c_void_p, C.POINTER(SiftExtractOptions), C.c_int32, C.POINTER(SiftBatchImage), C.c_int64, C.POINTER(SiftBatchReport),
                                         C.POINTER(SiftExtractReport), C.c_int64, C.POINTER(C.c_float), c_u8p, C.POINTER(C.c_int64)]
     L.pp_sift_extract_batch_features.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float), c_ip, c_dp, C.c_int64, C.POINTER(C.c_int64)]
+    L.pp_sift_extract_to_matcher.argtypes = [C.c_void_p, C.POINTER(SiftExtractOptions), C.c_int32, C.POINTER(SiftBatchImage), C.c_int64, C.POINTER(SiftBatchReport),
+                                             C.POINTER(SiftExtractReport), C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]
     _lib = L
     return L
 

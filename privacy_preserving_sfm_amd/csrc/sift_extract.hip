@@ -18,11 +18,15 @@
 // K23  pp_sift_extract_batch: the images of a batch through the octaves in lock-step, the kernels above per image on slices of one workspace, four
 //                        waits per octave for all of them; k_sift_describe_wave describes the features of every image of an octave in one launch, a
 //                        wavefront per feature with a fixed-order fold (see the kernel).
+// K24  pp_sift_extract_to_matcher: the batch with a pp_sift_handle as its way out.  The max_num_features cut is made from the keypoint counts, before
+//                        any orientation or descriptor; k_sift_describe_kept describes the kept features of all octaves of a group in one launch
+//                        and writes each row, and its offset, where k_sift_top2 (sift_match.hip) reads it.
 #include <cstring>
 
 #include "device_handle.hpp"
 #include "scan.hpp"
 #include "sift_extract_replay.hpp"
+#include "sift_match_handle.hpp"
 
 namespace ppsfm {
 
@@ -197,17 +201,12 @@ struct SiftWaveImage {
   double xper;
 };
 
-__global__ __launch_bounds__(kWave) void k_sift_describe_wave(const SiftFeature* __restrict__ feats, const Keypoint* __restrict__ keys,
-                                                             const SiftWaveImage* __restrict__ images, int s_min, int s_max,
-                                                             const double* __restrict__ expn, int normalization, float* __restrict__ raw,
-                                                             uint8_t* __restrict__ bytes, DescriptorWindow* __restrict__ window) {
-  __shared__ DescriptorTap staged[kWave];
-  __shared__ float hist[kDescBins];
-  const int64_t f = blockIdx.x;
+// The wavefront's work on one feature up to the last norm: *acc0, *acc1 = the lane's two entries 2 l, 2 l + 1 of the float descriptor before the last
+// normalisation, *last_norm = FinishNorm() over all 128 (the same on every lane); -> the window.  staged: kWave taps of LDS, hist: kDescBins floats.
+__device__ __forceinline__ DescriptorWindow DescribeByWave(const SiftFeature& q, const Keypoint& k, const SiftWaveImage& im, int s_min, int s_max,
+                                                          const double* __restrict__ expn, int normalization, DescriptorTap* staged, float* hist,
+                                                          float* out0, float* out1, float* last_norm) {
   const int lane = threadIdx.x;
-  const SiftFeature q = feats[f];
-  const Keypoint k = keys[q.key];
-  const SiftWaveImage im = images[q.image];
   const DescriptorFrame fr = MakeDescriptorFrame(im.w, im.h, s_min, s_max, k, im.xper);
   const int cx = ((lane >> 2) & 3) - 2, cy = (lane >> 4) - 2, t0 = 2 * (lane & 3);
   float acc0 = 0.f, acc1 = 0.f;
@@ -240,11 +239,52 @@ __global__ __launch_bounds__(kWave) void k_sift_describe_wave(const SiftFeature*
   __syncthreads();
   hist[2 * lane] = acc0; hist[2 * lane + 1] = acc1;
   __syncthreads();
-  norm = FinishNorm(hist, normalization);
+  *last_norm = FinishNorm(hist, normalization);
+  *out0 = acc0; *out1 = acc1;
+  return fr.win;
+}
+
+__global__ __launch_bounds__(kWave) void k_sift_describe_wave(const SiftFeature* __restrict__ feats, const Keypoint* __restrict__ keys,
+                                                             const SiftWaveImage* __restrict__ images, int s_min, int s_max,
+                                                             const double* __restrict__ expn, int normalization, float* __restrict__ raw,
+                                                             uint8_t* __restrict__ bytes, DescriptorWindow* __restrict__ window) {
+  __shared__ DescriptorTap staged[kWave];
+  __shared__ float hist[kDescBins];
+  const int64_t f = blockIdx.x;
+  const int lane = threadIdx.x;
+  const SiftFeature q = feats[f];
+  float acc0, acc1, norm;
+  const DescriptorWindow win = DescribeByWave(q, keys[q.key], images[q.image], s_min, s_max, expn, normalization, staged, hist, &acc0, &acc1, &norm);
   raw[kDescBins * f + 2 * lane] = acc0; raw[kDescBins * f + 2 * lane + 1] = acc1;
   bytes[kDescBins * f + UbcIndex(2 * lane)] = FinishByte(acc0, norm, normalization);
   bytes[kDescBins * f + UbcIndex(2 * lane + 1)] = FinishByte(acc1, norm, normalization);
-  if (lane == 0) window[f] = fr.win;
+  if (lane == 0) window[f] = win;
+}
+
+// K24 k_sift_describe_kept - k_sift_describe_wave for the features pp_sift_extract_to_matcher keeps, written as the matcher reads them.  One launch
+// covers every octave of a group: `images` has a slot per (octave, image) and feats[f].image names the feature's.  The accumulation and the norms
+// are DescribeByWave(), so the bytes are those of the batch call; the tail differs.  No float descriptor leaves the kernel.  The 128 bytes are put
+// together in UBC order in LDS with their top bit flipped (d - 128, what k_sift_top2 multiplies) and go to row dst_row[f] of the store as eight
+// 16-byte pieces; the row's offset 128 * sum(d) - 2^20 is the integer sum over the wavefront of the two bytes each lane made.
+__global__ __launch_bounds__(kWave) void k_sift_describe_kept(const SiftFeature* __restrict__ feats, const Keypoint* __restrict__ keys,
+                                                             const SiftWaveImage* __restrict__ images, const int32_t* __restrict__ dst_row, int s_min,
+                                                             int s_max, const double* __restrict__ expn, int normalization, int8_t* __restrict__ d_desc,
+                                                             int32_t* __restrict__ d_off, DescriptorWindow* __restrict__ window) {
+  __shared__ DescriptorTap staged[kWave];
+  __shared__ float hist[kDescBins];
+  __shared__ __attribute__((aligned(16))) uint8_t row[kDescBins];
+  const int64_t f = blockIdx.x;
+  const int lane = threadIdx.x;
+  const SiftFeature q = feats[f];
+  float acc0, acc1, norm;
+  const DescriptorWindow win = DescribeByWave(q, keys[q.key], images[q.image], s_min, s_max, expn, normalization, staged, hist, &acc0, &acc1, &norm);
+  const uint8_t b0 = FinishByte(acc0, norm, normalization), b1 = FinishByte(acc1, norm, normalization);
+  row[UbcIndex(2 * lane)] = b0 ^ 0x80; row[UbcIndex(2 * lane + 1)] = b1 ^ 0x80;
+  const int sum = WaveSumInt((int)b0 + (int)b1);
+  __syncthreads();
+  const int64_t r = dst_row[f];
+  if (lane < kDescBins / 16) reinterpret_cast<uint4*>(d_desc + kDescBins * r)[lane] = reinterpret_cast<const uint4*>(row)[lane];
+  if (lane == 0) { d_off[r] = 128 * sum - (1 << 20); window[f] = win; }
 }
 
 // The filters of one option set, one after the other: [0] the first octave's first level (or none), [1] a later octave's (none with the reference's
@@ -361,7 +401,8 @@ struct pp_sift_extractor_impl : ppsfm::DeviceHandle {
   ppsfm::SiftFeature* feats = nullptr;      float* raw = nullptr;      uint8_t* bytes = nullptr;      ppsfm::sift::DescriptorWindow* window = nullptr;      size_t cap_feats = 0;
   double* expn = nullptr;
   float* taps = nullptr;          size_t cap_taps = 0;
-  ppsfm::SiftWaveImage* wave_images = nullptr;      size_t cap_wave_images = 0;      // the image table of k_sift_describe_wave
+  ppsfm::SiftWaveImage* wave_images = nullptr;      size_t cap_wave_images = 0;      // the image table of k_sift_describe_wave / _kept
+  ppsfm::SiftFeature* kept_feats = nullptr;      int32_t* kept_rows = nullptr;      ppsfm::sift::DescriptorWindow* kept_window = nullptr;      size_t cap_kept = 0;      // k_sift_describe_kept
   // the last extraction
   bool extracted = false;
   ppsfm::sift::Geometry geom{};
@@ -422,6 +463,218 @@ Options FromC(const pp_sift_extract_options& c) {
   o.normalization = c.normalization;
   return o;
 }
+
+// ---- what pp_sift_extract_batch and pp_sift_extract_to_matcher share: the plan, the event time by phases, a group's way through an octave
+
+enum { kPyramid = 0, kDetect = 1, kGradient = 2, kOrient = 3, kDescribe = 4 };
+
+// the device time of a call: the spans between Begin() and a wait, each counted to the phase that ended in the wait
+struct SiftPhases {
+  StreamTimer timer;
+  hipStream_t s;
+  bool split;      // phase_timings: the phases that do not end in a wait get one
+  double ms[5] = {0, 0, 0, 0, 0};
+  SiftPhases(const DeviceHandle& h, bool phase_timings) : timer(h), s(h.stream), split(phase_timings) {}
+  // the span since the last Begin() belongs to `phase`: close it (the wait) and open the next one
+  int Close(int phase) {
+    PP_HIP_TRY(hipGetLastError());
+    PP_TRY(timer.End());
+    PP_HIP_TRY(hipStreamSynchronize(s));
+    const float before = timer.ms;
+    PP_TRY(timer.Add());
+    ms[phase] += (double)(timer.ms - before);
+    return timer.Begin();
+  }
+  int Boundary(int phase) { return split ? Close(phase) : PP_OK; }
+  int End() {      // the last span, to no phase
+    PP_HIP_TRY(hipGetLastError());
+    PP_TRY(timer.End());
+    PP_HIP_TRY(hipStreamSynchronize(s));
+    return timer.Add();
+  }
+};
+
+// everything the two calls settle before any device work: the options, the filters, every image's layout and the groups
+struct SiftBatchPlan {
+  Options opt;
+  Geometry g;
+  SiftFilters filters;
+  std::vector<SiftLayout> layouts;
+  std::vector<int64_t> bytes_per_image;
+  std::vector<int32_t> first;      // PlanSiftBatches: group b is the images first[b] .. first[b + 1] - 1
+  int num_groups() const { return (int)first.size() - 1; }
+};
+
+// the argument checks of a batch behind the null pointers (in the order pp_sift_extract_batch has always made them), then the plan
+int PlanSiftBatch(const char* where, const pp_sift_extract_options* options, int32_t num_images, const pp_sift_batch_image* images, int64_t workspace_bytes,
+                  int64_t capacity, SiftBatchPlan* plan) {
+  PP_REQUIRE(num_images >= 1, "%s: num_images %d", where, num_images);
+  PP_REQUIRE(capacity >= 0, "%s: negative capacity", where);
+  PP_REQUIRE(workspace_bytes >= 0, "%s: negative workspace_bytes", where);
+  plan->opt = FromC(*options);
+  for (int32_t i = 0; i < num_images; ++i) {
+    PP_REQUIRE(images[i].grey, "%s: image %d: null argument", where, i);
+    const std::string wrong = CheckOptions(plan->opt, images[i].width, images[i].height);
+    PP_REQUIRE(wrong.empty(), "%s: image %d: %s", where, i, wrong.c_str());
+  }
+  plan->g = MakeGeometry(plan->opt);
+  PP_TRY(MakeSiftFilters(where, plan->g, &plan->filters));
+  const size_t N = (size_t)num_images;
+  plan->layouts.resize(N);
+  plan->bytes_per_image.resize(N);
+  for (size_t i = 0; i < N; ++i) {
+    plan->layouts[i] = LayoutOctaves(plan->g, images[i].width, images[i].height);
+    const int64_t pixels = (int64_t)images[i].width * images[i].height;
+    plan->bytes_per_image[i] = (int64_t)((plan->layouts[i].total + plan->layouts[i].rows_need) * sizeof(float)) + pixels * (int64_t)(sizeof(float) + 1);
+  }
+  plan->first = PlanSiftBatches(plan->bytes_per_image, workspace_bytes > 0 ? workspace_bytes : (int64_t)8 << 30);
+  return PP_OK;
+}
+
+// the keypoint buffers regrown to K keypoints (the stream has drained)
+int GrowKeys(pp_sift_extractor_impl* h, size_t K) {
+  const bool regrow = !h->keys || h->cap_keys < K;
+  const size_t want = std::max<size_t>(K, 2 * h->cap_keys);
+  if (regrow) { if (h->keys) h->blocks.Free(&h->keys); h->cap_keys = 0; PP_TRY(h->blocks.Alloc(&h->keys, want)); h->cap_keys = want; }
+  PP_TRY(GrowBeside(h->blocks, &h->num_angles, regrow, h->cap_keys));
+  return GrowBeside(h->blocks, &h->angles, regrow, kMaxAngles * h->cap_keys);
+}
+
+// One group of images in the handle's workspace.  Every image has its own slice of the pyramid, of the grey and float images and of the row counts
+// (the n candidate totals stand in front of the images' slices).
+struct SiftGroup {
+  pp_sift_extractor_impl* h;
+  const SiftBatchPlan& plan;
+  const pp_sift_batch_image* images;
+  size_t first, n;
+  std::vector<size_t> pyr_off, img_off, rows_off;
+  int64_t bytes = 0;
+  std::vector<int32_t> totals, cand_off;
+  std::vector<Refined> refined;
+
+  SiftGroup(pp_sift_extractor_impl* handle, const SiftBatchPlan& p, const pp_sift_batch_image* ims, int b)
+      : h(handle), plan(p), images(ims), first((size_t)p.first[(size_t)b]), n((size_t)p.first[(size_t)b + 1] - first), pyr_off(n), img_off(n), rows_off(n), totals(n),
+        cand_off(n) {}
+  const SiftOctave& Octave(size_t i, int q) const { return plan.layouts[first + i].octaves[(size_t)q]; }
+  float* Pyramid(size_t i) const { return h->pyramid + pyr_off[i]; }
+
+  // the slices, the workspace grown to them (the stream has drained: the call before, or the group before), the images uploaded and converted;
+  // table_slots: the image table of the descriptor kernel
+  int Begin(SiftPhases* phases, size_t table_slots) {
+    hipStream_t s = h->stream;
+    size_t pyr_total = 0, img_total = 0, rows_total = n;
+    for (size_t i = 0; i < n; ++i) {
+      pyr_off[i] = pyr_total; pyr_total += plan.layouts[first + i].total;
+      img_off[i] = img_total; img_total += (size_t)images[first + i].width * images[first + i].height;
+      rows_off[i] = rows_total; rows_total += plan.layouts[first + i].rows_need;
+      bytes += plan.bytes_per_image[first + i];
+    }
+    PP_TRY(Grow(h->blocks, &h->pyramid, &h->cap_pyramid, pyr_total));
+    {
+      const bool regrow = !h->image || h->cap_image < img_total;
+      PP_TRY(Grow(h->blocks, &h->image, &h->cap_image, img_total));
+      PP_TRY(GrowBeside(h->blocks, &h->grey, regrow, h->cap_image));
+    }
+    PP_TRY(Grow(h->blocks, &h->rows, &h->cap_rows, rows_total));
+    PP_TRY(Grow(h->blocks, &h->wave_images, &h->cap_wave_images, table_slots));
+    for (size_t i = 0; i < n; ++i) PP_TRY(Upload(h->grey + img_off[i], images[first + i].grey, (size_t)images[first + i].width * images[first + i].height, s));
+    PP_TRY(phases->timer.Begin());
+    for (size_t i = 0; i < n; ++i) {
+      const int64_t pixels = (int64_t)images[first + i].width * images[first + i].height;
+      hipLaunchKernelGGL(k_sift_load, SiftGrid(pixels, kSiftBlock), dim3(kSiftBlock), 0, s, pixels, (const uint8_t*)(h->grey + img_off[i]), h->image + img_off[i]);
+    }
+    return PP_OK;
+  }
+
+  // Octave q of every image up to its keypoints, in two waits: pyramid, gradient, candidate counts and their scan image by image, the n totals in one
+  // download; then scatter and refinement of every image into one candidate array, the refined candidates in one download.  The keypoints are
+  // APPENDED to keys - image i's are the num_keys[i] from key_off[i] on - and the octave's counts to results[first + i].octaves.
+  int Keypoints(const char* where, int q, SiftPhases* phases, std::vector<HostResult>* results, std::vector<Keypoint>* keys, int32_t* key_off, int32_t* num_keys) {
+    hipStream_t s = h->stream;
+    const Geometry& g = plan.g;
+    const int o = g.o_min + q, num_grad = g.S;
+    const double threshold = 0.8 * plan.opt.peak_threshold;
+    for (size_t i = 0; i < n; ++i)
+      LaunchOctavePyramid(s, g, plan.filters, (const float*)h->taps, plan.layouts[first + i], q, Pyramid(i), (const float*)(h->image + img_off[i]), images[first + i].width,
+                          images[first + i].height);
+    PP_TRY(phases->Boundary(kPyramid));
+    for (size_t i = 0; i < n; ++i) {
+      const SiftOctave& oc = Octave(i, q);
+      const int64_t lev = (int64_t)oc.w * oc.h;
+      if (oc.has_grad)
+        hipLaunchKernelGGL(k_sift_gradient, SiftGrid(lev * num_grad, kSiftBlock), dim3(kSiftBlock), 0, s, Pyramid(i) + oc.grad, (const float*)(Pyramid(i) + oc.gauss + lev), oc.w,
+                           oc.h, lev * num_grad);
+    }
+    PP_TRY(phases->Boundary(kGradient));
+    bool any_detect = false;
+    for (size_t i = 0; i < n; ++i) {
+      const SiftLayout& lay = plan.layouts[first + i];
+      const SiftOctave& oc = lay.octaves[(size_t)q];
+      if (!(oc.w >= 3 && oc.h >= 3)) continue;
+      any_detect = true;
+      const int64_t lev = (int64_t)oc.w * oc.h;
+      const int rows = g.S * oc.h;
+      int32_t* row_count = h->rows + rows_off[i];
+      int32_t* row_start = row_count + lay.max_rows;
+      int32_t* scan_scratch = row_count + 2 * (size_t)lay.max_rows + 2;
+      hipLaunchKernelGGL(k_sift_detect_count, dim3((unsigned)rows), dim3(kSiftBlock), 0, s, (const float*)(Pyramid(i) + oc.dog + lev), oc.w, oc.h, threshold, row_count);
+      const ScanJob<int32_t> job{row_count, row_start, h->rows + i};
+      LaunchExclusiveScan<int32_t>(s, rows, &job, 1, scan_scratch);
+    }
+    std::fill(totals.begin(), totals.end(), 0);
+    if (any_detect) {
+      PP_TRY(Download(totals.data(), (const int32_t*)h->rows, n, s));
+      PP_TRY(phases->Close(kDetect));
+    }
+    size_t num_cand = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const SiftOctave& oc = Octave(i, q);
+      if (!(oc.w >= 3 && oc.h >= 3)) totals[i] = 0;      // (its total was not written)
+      cand_off[i] = (int32_t)num_cand;
+      num_cand += (size_t)totals[i];
+    }
+    PP_REQUIRE(num_cand < ((size_t)1 << 31) / 3, "%s: %lld candidates in one octave of a sub-batch", where, (long long)num_cand);
+    refined.assign(num_cand, Refined{});
+    if (num_cand > 0) {
+      {      // (the stream has drained)
+        const bool regrow = !h->cand || h->cap_cand < num_cand;
+        const size_t want = std::max<size_t>(num_cand, 2 * h->cap_cand);
+        if (regrow) { if (h->cand) h->blocks.Free(&h->cand); h->cap_cand = 0; PP_TRY(h->blocks.Alloc(&h->cand, 3 * want)); h->cap_cand = want; }
+        PP_TRY(GrowBeside(h->blocks, &h->refined, regrow, h->cap_cand));
+      }
+      for (size_t i = 0; i < n; ++i) {
+        if (totals[i] == 0) continue;
+        const SiftLayout& lay = plan.layouts[first + i];
+        const SiftOctave& oc = lay.octaves[(size_t)q];
+        const int64_t lev = (int64_t)oc.w * oc.h;
+        const float* dog = Pyramid(i) + oc.dog;
+        const int32_t* row_count = h->rows + rows_off[i];
+        int32_t* cand = h->cand + 3 * (size_t)cand_off[i];
+        hipLaunchKernelGGL(k_sift_detect_scatter, dim3((unsigned)(g.S * oc.h)), dim3(kSiftBlock), 0, s, dog + lev, oc.w, oc.h, g.s_min + 1, threshold, row_count,
+                           row_count + lay.max_rows, cand);
+        hipLaunchKernelGGL(k_sift_refine, SiftGrid(totals[i], kSiftLaneBlock), dim3(kSiftLaneBlock), 0, s, totals[i], (const int32_t*)cand, dog, oc.w, oc.h, g.s_min,
+                           g.s_max, plan.opt.peak_threshold, plan.opt.edge_threshold, h->refined + cand_off[i]);
+      }
+      PP_TRY(Download(refined.data(), (const Refined*)h->refined, num_cand, s));
+      PP_TRY(phases->Close(kDetect));
+    }
+    for (size_t i = 0; i < n; ++i) {
+      const SiftOctave& oc = Octave(i, q);
+      OctaveCounts counts{oc.w, oc.h, totals[i], 0, 0, 0, 0, 0, 0};
+      key_off[i] = (int32_t)keys->size();
+      for (int32_t c = 0; c < totals[i]; ++c) {
+        const Refined& r = refined[(size_t)cand_off[i] + (size_t)c];
+        counts.moved += r.moves > 0;
+        counts.reject_peak += r.reject == 1; counts.reject_edge += r.reject == 2; counts.reject_offset += r.reject == 3; counts.reject_bounds += r.reject == 4;
+        if (r.good) keys->push_back(MakeKeypoint(r, o, g));
+      }
+      num_keys[i] = (int32_t)keys->size() - key_off[i];
+      counts.num_keypoints = num_keys[i];
+      (*results)[first + i].octaves.push_back(counts);
+    }
+    return PP_OK;
+  }
+};
 
 }  // namespace
 
@@ -725,81 +978,33 @@ int pp_sift_extract_batch(pp_sift_extractor_handle h, const pp_sift_extract_opti
                           uint8_t* descriptors, int64_t* offsets) try {
   const char* where = "pp_sift_extract_batch";
   PP_REQUIRE(options && images && batch_report && reports && keypoints && offsets, "%s: null argument", where);
-  PP_REQUIRE(num_images >= 1, "%s: num_images %d", where, num_images);
-  PP_REQUIRE(capacity >= 0, "%s: negative capacity", where);
-  PP_REQUIRE(workspace_bytes >= 0, "%s: negative workspace_bytes", where);
   const auto t_begin = Clock::now();
-  const Options opt = FromC(*options);
-  for (int32_t i = 0; i < num_images; ++i) {
-    PP_REQUIRE(images[i].grey, "%s: image %d: null argument", where, i);
-    const std::string wrong = CheckOptions(opt, images[i].width, images[i].height);
-    PP_REQUIRE(wrong.empty(), "%s: image %d: %s", where, i, wrong.c_str());
-  }
+  SiftBatchPlan plan;
+  PP_TRY(PlanSiftBatch(where, options, num_images, images, workspace_bytes, capacity, &plan));
   PP_REQUIRE(h, "%s: null handle", where);
-  const Geometry g = MakeGeometry(opt);
-  const int num_grad = g.S;
-  SiftFilters filters;
-  PP_TRY(MakeSiftFilters(where, g, &filters));
+  const Options& opt = plan.opt;
+  const Geometry& g = plan.g;
+  const std::vector<SiftLayout>& layouts = plan.layouts;
   const size_t N = (size_t)num_images;
-  std::vector<SiftLayout> layouts(N);
-  std::vector<int64_t> bytes_per_image(N);
-  for (size_t i = 0; i < N; ++i) {
-    layouts[i] = LayoutOctaves(g, images[i].width, images[i].height);
-    const int64_t pixels = (int64_t)images[i].width * images[i].height;
-    bytes_per_image[i] = (int64_t)((layouts[i].total + layouts[i].rows_need) * sizeof(float)) + pixels * (int64_t)(sizeof(float) + 1);
-  }
-  const std::vector<int32_t> plan = PlanSiftBatches(bytes_per_image, workspace_bytes > 0 ? workspace_bytes : (int64_t)8 << 30);
-  const int num_sub_batches = (int)plan.size() - 1;
+  const int num_sub_batches = plan.num_groups();
 
   PP_HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   h->extracted = false;
   h->batch.clear();
-  PP_TRY(Grow(h->blocks, &h->taps, &h->cap_taps, filters.taps.size()));
-  PP_TRY(Upload(h->taps, filters.taps.data(), filters.taps.size(), s));
+  PP_TRY(Grow(h->blocks, &h->taps, &h->cap_taps, plan.filters.taps.size()));
+  PP_TRY(Upload(h->taps, plan.filters.taps.data(), plan.filters.taps.size(), s));
 
-  StreamTimer timer(*h);
-  double phase_ms[5] = {0, 0, 0, 0, 0};
-  enum { kPyramid = 0, kDetect = 1, kGradient = 2, kOrient = 3, kDescribe = 4 };
-  auto close_span = [&](int phase) -> int {      // (as in pp_sift_extract: the wait)
-    PP_HIP_TRY(hipGetLastError());
-    PP_TRY(timer.End());
-    PP_HIP_TRY(hipStreamSynchronize(s));
-    const float before = timer.ms;
-    PP_TRY(timer.Add());
-    phase_ms[phase] += (double)(timer.ms - before);
-    return timer.Begin();
-  };
-  auto phase_boundary = [&](int phase) -> int { return options->phase_timings ? close_span(phase) : PP_OK; };
-
+  SiftPhases phases(*h, options->phase_timings != 0);
   std::vector<HostResult> results(N);      // the containers of the reference, per image, filled octave by octave
   int64_t workspace_used = 0;
-  const double threshold = 0.8 * opt.peak_threshold;
   for (int b = 0; b < num_sub_batches; ++b) {
-    const size_t first = (size_t)plan[(size_t)b], n = (size_t)plan[(size_t)b + 1] - first;
-    // ---- the slices: pyramid (floats), image (pixels), rows (int32s; the n totals stand in front of the images' slices)
-    std::vector<size_t> pyr_off(n), img_off(n), rows_off(n);
-    size_t pyr_total = 0, img_total = 0, rows_total = n;
-    int64_t sub_bytes = 0;
-    for (size_t i = 0; i < n; ++i) {
-      pyr_off[i] = pyr_total; pyr_total += layouts[first + i].total;
-      img_off[i] = img_total; img_total += (size_t)images[first + i].width * images[first + i].height;
-      rows_off[i] = rows_total; rows_total += layouts[first + i].rows_need;
-      sub_bytes += bytes_per_image[first + i];
-    }
-    workspace_used = std::max(workspace_used, sub_bytes);
-    PP_TRY(Grow(h->blocks, &h->pyramid, &h->cap_pyramid, pyr_total));      // (the stream has drained: the call before, or the sub-batch before)
-    {
-      const bool regrow = !h->image || h->cap_image < img_total;
-      PP_TRY(Grow(h->blocks, &h->image, &h->cap_image, img_total));
-      PP_TRY(GrowBeside(h->blocks, &h->grey, regrow, h->cap_image));
-    }
-    PP_TRY(Grow(h->blocks, &h->rows, &h->cap_rows, rows_total));
-    PP_TRY(Grow(h->blocks, &h->wave_images, &h->cap_wave_images, n));
-    for (size_t i = 0; i < n; ++i) PP_TRY(Upload(h->grey + img_off[i], images[first + i].grey, (size_t)images[first + i].width * images[first + i].height, s));
+    SiftGroup group(h, plan, images, b);
+    const size_t first = group.first, n = group.n;
+    PP_TRY(group.Begin(&phases, n));
+    workspace_used = std::max(workspace_used, group.bytes);
 
-    std::vector<int32_t> totals(n), cand_off(n), key_off(n), num_keys(n), feat_off(n), num_feats(n);
-    std::vector<Refined> refined;
+    std::vector<int32_t> key_off(n), num_keys(n), feat_off(n), num_feats(n);
     std::vector<Keypoint> keys;
     std::vector<int32_t> num_angles, is_of_key, used;
     std::vector<double> angles;
@@ -807,107 +1012,15 @@ int pp_sift_extract_batch(pp_sift_extractor_handle h, const pp_sift_extract_opti
     std::vector<SiftWaveImage> table(n);
     std::vector<DescriptorWindow> window;
 
-    PP_TRY(timer.Begin());
-    for (size_t i = 0; i < n; ++i) {
-      const int64_t pixels = (int64_t)images[first + i].width * images[first + i].height;
-      hipLaunchKernelGGL(k_sift_load, SiftGrid(pixels, kSiftBlock), dim3(kSiftBlock), 0, s, pixels, (const uint8_t*)(h->grey + img_off[i]), h->image + img_off[i]);
-    }
     for (int q = 0; q < g.O; ++q) {
       const int o = g.o_min + q;
-      // ---- pyramid, gradient, candidate counts and their scan, image by image; then the n totals in one download
-      for (size_t i = 0; i < n; ++i)
-        LaunchOctavePyramid(s, g, filters, (const float*)h->taps, layouts[first + i], q, h->pyramid + pyr_off[i], (const float*)(h->image + img_off[i]),
-                            images[first + i].width, images[first + i].height);
-      PP_TRY(phase_boundary(kPyramid));
-      for (size_t i = 0; i < n; ++i) {
-        const SiftOctave& oc = layouts[first + i].octaves[(size_t)q];
-        const int64_t lev = (int64_t)oc.w * oc.h;
-        float* pyr = h->pyramid + pyr_off[i];
-        if (oc.has_grad)
-          hipLaunchKernelGGL(k_sift_gradient, SiftGrid(lev * num_grad, kSiftBlock), dim3(kSiftBlock), 0, s, pyr + oc.grad, (const float*)(pyr + oc.gauss + lev), oc.w, oc.h,
-                             lev * num_grad);
-      }
-      PP_TRY(phase_boundary(kGradient));
-      bool any_detect = false;
-      for (size_t i = 0; i < n; ++i) {
-        const SiftLayout& lay = layouts[first + i];
-        const SiftOctave& oc = lay.octaves[(size_t)q];
-        if (!(oc.w >= 3 && oc.h >= 3)) continue;
-        any_detect = true;
-        const int64_t lev = (int64_t)oc.w * oc.h;
-        const int rows = g.S * oc.h;
-        int32_t* row_count = h->rows + rows_off[i];
-        int32_t* row_start = row_count + lay.max_rows;
-        int32_t* scan_scratch = row_count + 2 * (size_t)lay.max_rows + 2;
-        hipLaunchKernelGGL(k_sift_detect_count, dim3((unsigned)rows), dim3(kSiftBlock), 0, s, (const float*)(h->pyramid + pyr_off[i] + oc.dog + lev), oc.w, oc.h, threshold,
-                           row_count);
-        const ScanJob<int32_t> job{row_count, row_start, h->rows + i};
-        LaunchExclusiveScan<int32_t>(s, rows, &job, 1, scan_scratch);
-      }
-      std::fill(totals.begin(), totals.end(), 0);
-      if (any_detect) {
-        PP_TRY(Download(totals.data(), (const int32_t*)h->rows, n, s));
-        PP_TRY(close_span(kDetect));
-      }
-      size_t num_cand = 0;
-      for (size_t i = 0; i < n; ++i) {
-        const SiftOctave& oc = layouts[first + i].octaves[(size_t)q];
-        if (!(oc.w >= 3 && oc.h >= 3)) totals[i] = 0;      // (its total was not written)
-        cand_off[i] = (int32_t)num_cand;
-        num_cand += (size_t)totals[i];
-      }
-      PP_REQUIRE(num_cand < ((size_t)1 << 31) / 3, "%s: %lld candidates in one octave of a sub-batch", where, (long long)num_cand);
-      // ---- scatter and refinement of every image into one candidate array
-      refined.assign(num_cand, Refined{});
-      if (num_cand > 0) {
-        {      // (the stream has drained)
-          const bool regrow = !h->cand || h->cap_cand < num_cand;
-          const size_t want = std::max<size_t>(num_cand, 2 * h->cap_cand);
-          if (regrow) { if (h->cand) h->blocks.Free(&h->cand); h->cap_cand = 0; PP_TRY(h->blocks.Alloc(&h->cand, 3 * want)); h->cap_cand = want; }
-          PP_TRY(GrowBeside(h->blocks, &h->refined, regrow, h->cap_cand));
-        }
-        for (size_t i = 0; i < n; ++i) {
-          if (totals[i] == 0) continue;
-          const SiftLayout& lay = layouts[first + i];
-          const SiftOctave& oc = lay.octaves[(size_t)q];
-          const int64_t lev = (int64_t)oc.w * oc.h;
-          const float* dog = h->pyramid + pyr_off[i] + oc.dog;
-          const int32_t* row_count = h->rows + rows_off[i];
-          int32_t* cand = h->cand + 3 * (size_t)cand_off[i];
-          hipLaunchKernelGGL(k_sift_detect_scatter, dim3((unsigned)(g.S * oc.h)), dim3(kSiftBlock), 0, s, dog + lev, oc.w, oc.h, g.s_min + 1, threshold, row_count,
-                             row_count + lay.max_rows, cand);
-          hipLaunchKernelGGL(k_sift_refine, SiftGrid(totals[i], kSiftLaneBlock), dim3(kSiftLaneBlock), 0, s, totals[i], (const int32_t*)cand, dog, oc.w, oc.h, g.s_min,
-                             g.s_max, opt.peak_threshold, opt.edge_threshold, h->refined + cand_off[i]);
-        }
-        PP_TRY(Download(refined.data(), (const Refined*)h->refined, num_cand, s));
-        PP_TRY(close_span(kDetect));
-      }
       keys.clear();
-      for (size_t i = 0; i < n; ++i) {
-        const SiftOctave& oc = layouts[first + i].octaves[(size_t)q];
-        OctaveCounts counts{oc.w, oc.h, totals[i], 0, 0, 0, 0, 0, 0};
-        key_off[i] = (int32_t)keys.size();
-        for (int32_t c = 0; c < totals[i]; ++c) {
-          const Refined& r = refined[(size_t)cand_off[i] + (size_t)c];
-          counts.moved += r.moves > 0;
-          counts.reject_peak += r.reject == 1; counts.reject_edge += r.reject == 2; counts.reject_offset += r.reject == 3; counts.reject_bounds += r.reject == 4;
-          if (r.good) keys.push_back(MakeKeypoint(r, o, g));
-        }
-        num_keys[i] = (int32_t)keys.size() - key_off[i];
-        counts.num_keypoints = num_keys[i];
-        results[first + i].octaves.push_back(counts);
-      }
+      PP_TRY(group.Keypoints(where, q, &phases, &results, &keys, key_off.data(), num_keys.data()));
       const size_t K = keys.size();
       if (K == 0) continue;
       // ---- orientations: the keys of every image uploaded together
       const double xper = std::ldexp(1.0, o);
-      {
-        const bool regrow = !h->keys || h->cap_keys < K;
-        const size_t want = std::max<size_t>(K, 2 * h->cap_keys);
-        if (regrow) { if (h->keys) h->blocks.Free(&h->keys); h->cap_keys = 0; PP_TRY(h->blocks.Alloc(&h->keys, want)); h->cap_keys = want; }
-        PP_TRY(GrowBeside(h->blocks, &h->num_angles, regrow, h->cap_keys));
-        PP_TRY(GrowBeside(h->blocks, &h->angles, regrow, kMaxAngles * h->cap_keys));
-      }
+      PP_TRY(GrowKeys(h, K));
       if (!opt.upright || descriptors) PP_TRY(Upload(h->keys, keys.data(), K, s));
       num_angles.assign(K, 1);
       angles.assign(kMaxAngles * K, 0.0);
@@ -916,12 +1029,12 @@ int pp_sift_extract_batch(pp_sift_extractor_handle h, const pp_sift_extract_opti
           if (num_keys[i] == 0) continue;
           const SiftOctave& oc = layouts[first + i].octaves[(size_t)q];
           hipLaunchKernelGGL(k_sift_orient, SiftGrid(num_keys[i], kSiftLaneBlock), dim3(kSiftLaneBlock), 0, s, num_keys[i], (const Keypoint*)(h->keys + key_off[i]),
-                             (const float*)(h->pyramid + pyr_off[i] + oc.grad), oc.w, oc.h, g.s_min, g.s_max, xper, (const double*)h->expn, h->num_angles + key_off[i],
+                             (const float*)(group.Pyramid(i) + oc.grad), oc.w, oc.h, g.s_min, g.s_max, xper, (const double*)h->expn, h->num_angles + key_off[i],
                              h->angles + kMaxAngles * (size_t)key_off[i]);
         }
         PP_TRY(Download(num_angles.data(), (const int32_t*)h->num_angles, K, s));
         PP_TRY(Download(angles.data(), (const double*)h->angles, kMaxAngles * K, s));
-        PP_TRY(close_span(kOrient));
+        PP_TRY(phases.Close(kOrient));
       }
       // ---- the features of the octave: per image into its containers, all of them into one descriptor launch
       feats.clear();
@@ -967,7 +1080,7 @@ int pp_sift_extract_batch(pp_sift_extractor_handle h, const pp_sift_extract_opti
       }
       for (size_t i = 0; i < n; ++i) {
         const SiftOctave& oc = layouts[first + i].octaves[(size_t)q];
-        table[i] = SiftWaveImage{h->pyramid + pyr_off[i] + oc.grad, oc.w, oc.h, xper};
+        table[i] = SiftWaveImage{group.Pyramid(i) + oc.grad, oc.w, oc.h, xper};
       }
       PP_TRY(Upload(h->wave_images, table.data(), n, s));
       PP_TRY(Upload(h->feats, feats.data(), F, s));
@@ -983,16 +1096,13 @@ int pp_sift_extract_batch(pp_sift_extractor_handle h, const pp_sift_extract_opti
         PP_TRY(Download(R.descriptors.data() + at, (const uint8_t*)(h->bytes + kDescBins * f0), kDescBins * F_i, s));
       }
       PP_TRY(Download(window.data(), (const DescriptorWindow*)h->window, F, s));
-      PP_TRY(close_span(kDescribe));
+      PP_TRY(phases.Close(kDescribe));
       for (size_t i = 0; i < n; ++i) {
         HostResult& R = results[first + i];
         for (size_t f = (size_t)feat_off[i]; f < (size_t)feat_off[i] + (size_t)num_feats[i]; ++f) { R.windows_cut += window[f].cut; R.descriptors_skipped += !window[f].computed; }
       }
     }
-    PP_HIP_TRY(hipGetLastError());
-    PP_TRY(timer.End());
-    PP_HIP_TRY(hipStreamSynchronize(s));
-    PP_TRY(timer.Add());
+    PP_TRY(phases.End());
   }
 
   // ---- the host rule, per image
@@ -1009,8 +1119,8 @@ int pp_sift_extract_batch(pp_sift_extractor_handle h, const pp_sift_extract_opti
   batch_report->num_sub_batches = num_sub_batches;
   batch_report->num_features = offsets[N];
   batch_report->workspace_bytes = workspace_used;
-  for (int p = 0; p < 5; ++p) batch_report->phase_ms[p] = options->phase_timings ? phase_ms[p] : 0.0;
-  batch_report->device_ms = timer.ms;
+  for (int p = 0; p < 5; ++p) batch_report->phase_ms[p] = options->phase_timings ? phases.ms[p] : 0.0;
+  batch_report->device_ms = phases.timer.ms;
   h->batch.resize(N);
   for (size_t i = 0; i < N; ++i) {
     h->batch[i].raw = std::move(results[i].raw);
@@ -1028,6 +1138,196 @@ int pp_sift_extract_batch(pp_sift_extractor_handle h, const pp_sift_extract_opti
   batch_report->total_ms = MsSince(t_begin);
   return PP_OK;
 } PP_API_CATCH("pp_sift_extract_batch")
+
+// K24: pp_sift_extract_batch with the cut BEFORE the orientations and the descriptors, and the matcher as the way out.  Pass 1 takes a group through
+// the octaves up to its keypoints (SiftGroup::Keypoints, two waits per octave); the keypoints stay on the host, every octave's gradient levels in the
+// workspace.  The cut reads the keypoint counts alone (SelectKeptKeypoints).  Pass 2 runs on what is kept: the kept keypoints of all octaves in one
+// upload, k_sift_orient per (octave, image) and one wait, then ONE launch of k_sift_describe_kept over all octaves that writes the matcher's store,
+// and one wait: 2 x octaves + 2 waits for a group.  The store belongs to the new pp_sift_handle and is written on the extractor's stream, which has
+// drained before the handle is handed out or, on an error, destroyed.
+int pp_sift_extract_to_matcher(pp_sift_extractor_handle h, const pp_sift_extract_options* options, int32_t num_images, const pp_sift_batch_image* images,
+                               int64_t workspace_bytes, pp_sift_batch_report* batch_report, pp_sift_extract_report* reports, int64_t capacity, float* keypoints,
+                               int64_t* offsets, pp_sift_handle* matcher) try {
+  const char* where = "pp_sift_extract_to_matcher";
+  PP_REQUIRE(matcher, "%s: null argument", where);
+  *matcher = nullptr;
+  PP_REQUIRE(options && images && batch_report && reports && keypoints && offsets, "%s: null argument", where);
+  const auto t_begin = Clock::now();
+  SiftBatchPlan plan;
+  PP_TRY(PlanSiftBatch(where, options, num_images, images, workspace_bytes, capacity, &plan));
+  PP_REQUIRE(h, "%s: null handle", where);
+  const Options& opt = plan.opt;
+  const Geometry& g = plan.g;
+  const size_t N = (size_t)num_images, O = (size_t)g.O;
+
+  PP_HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  h->extracted = false;
+  h->batch.clear();
+  UnderConstruction<pp_sift_impl, pp_sift_destroy> m{new pp_sift_impl()};
+  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};      // (destroyed before m: nothing writes the store when it goes back)
+  PP_TRY(m->Open(h->device));
+  m->num_images = num_images;
+  size_t store_rows = 0;      // what the matcher's store holds; the rows of the groups so far are filled
+  // the store regrown to `rows`, the `filled` first ones carried over by a copy on the extractor's stream; the old blocks go back behind a wait
+  auto grow_store = [&](size_t rows, size_t filled) -> int {
+    int8_t* desc = nullptr;
+    int32_t* off = nullptr;
+    PP_TRY(AllocSiftStore(m->blocks, (int64_t)rows, &desc, &off));
+    if (m->d_desc) {
+      if (filled) {
+        PP_HIP_TRY(hipMemcpyAsync(desc, m->d_desc, filled * kDescBins, hipMemcpyDeviceToDevice, s));
+        PP_HIP_TRY(hipMemcpyAsync(off, m->d_off, filled * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+      }
+      PP_HIP_TRY(hipStreamSynchronize(s));
+      m->blocks.Free(&m->d_desc); m->blocks.Free(&m->d_off);
+    }
+    m->d_desc = desc; m->d_off = off; store_rows = rows;
+    return PP_OK;
+  };
+  PP_TRY(Grow(h->blocks, &h->taps, &h->cap_taps, plan.filters.taps.size()));
+  PP_TRY(Upload(h->taps, plan.filters.taps.data(), plan.filters.taps.size(), s));
+
+  SiftPhases phases(*h, options->phase_timings != 0);
+  std::vector<HostResult> results(N);      // levels (keypoint counts), octaves, cut and the kept-only counts; keypoints: the kept rows
+  std::vector<int64_t> row0(N + 1, 0);     // image i's first row in the store: the offsets
+  int64_t workspace_used = 0;
+  for (int b = 0; b < plan.num_groups(); ++b) {
+    SiftGroup group(h, plan, images, b);
+    const size_t first = group.first, n = group.n;
+    PP_TRY(group.Begin(&phases, O * n));
+    workspace_used = std::max(workspace_used, group.bytes);
+    // ---- pass 1: the keypoints of every octave, block q * n + i = (octave q, image i)
+    std::vector<Keypoint> keys, kept;
+    std::vector<int32_t> key_off(O * n), num_keys(O * n), kept_off(O * n), kept_num(O * n), is_of_key, none;
+    for (size_t q = 0; q < O; ++q) {
+      PP_TRY(group.Keypoints(where, (int)q, &phases, &results, &keys, key_off.data() + q * n, num_keys.data() + q * n));
+      for (size_t i = 0; i < n; ++i) {
+        const size_t K_i = (size_t)num_keys[q * n + i], k0 = (size_t)key_off[q * n + i];
+        is_of_key.resize(K_i); none.assign(K_i, 0);
+        for (size_t j = 0; j < K_i; ++j) is_of_key[j] = keys[k0 + j].is;
+        AppendLevels(g.o_min + (int)q, is_of_key.data(), none.data(), (int64_t)K_i, &results[first + i].levels);
+      }
+    }
+    // ---- the cut
+    std::vector<KeptCut> cuts(n);
+    for (size_t i = 0; i < n; ++i) cuts[i] = SelectKeptKeypoints(results[first + i].levels, opt.max_num_features, g.o_min, g.O);
+    for (size_t q = 0; q < O; ++q)
+      for (size_t i = 0; i < n; ++i) {
+        const KeptRange& r = cuts[i].octaves[q];
+        kept_off[q * n + i] = (int32_t)kept.size(); kept_num[q * n + i] = (int32_t)r.count;
+        const auto from = keys.begin() + key_off[q * n + i] + r.first;
+        kept.insert(kept.end(), from, from + r.count);
+      }
+    // ---- pass 2: orientations of the kept keypoints
+    const size_t K = kept.size();
+    std::vector<int32_t> num_angles(K, 1);
+    std::vector<double> angles(kMaxAngles * K, 0.0);
+    if (K > 0) {
+      PP_TRY(GrowKeys(h, K));      // (nothing outstanding on the stream reads these)
+      PP_TRY(Upload(h->keys, kept.data(), K, s));
+    }
+    if (K > 0 && !opt.upright) {
+      for (size_t q = 0; q < O; ++q)
+        for (size_t i = 0; i < n; ++i) {
+          const int32_t K_b = kept_num[q * n + i], k0 = kept_off[q * n + i];
+          if (K_b == 0) continue;
+          const SiftOctave& oc = group.Octave(i, (int)q);
+          hipLaunchKernelGGL(k_sift_orient, SiftGrid(K_b, kSiftLaneBlock), dim3(kSiftLaneBlock), 0, s, K_b, (const Keypoint*)(h->keys + k0), (const float*)(group.Pyramid(i) + oc.grad),
+                             oc.w, oc.h, g.s_min, g.s_max, std::ldexp(1.0, oc.o), (const double*)h->expn, h->num_angles + k0, h->angles + kMaxAngles * (size_t)k0);
+        }
+      PP_TRY(Download(num_angles.data(), (const int32_t*)h->num_angles, K, s));
+      PP_TRY(Download(angles.data(), (const double*)h->angles, kMaxAngles * K, s));
+      PP_TRY(phases.Close(kOrient));
+    }
+    // ---- the features in the reference's order per image, and their rows in the store
+    std::vector<SiftFeature> feats;
+    std::vector<int64_t> counts(O * n, 0);
+    for (size_t q = 0; q < O; ++q)
+      for (size_t i = 0; i < n; ++i) {
+        HostResult& R = results[first + i];
+        for (int32_t j = kept_off[q * n + i]; j < kept_off[q * n + i] + kept_num[q * n + i]; ++j) {
+          const Keypoint& key = kept[(size_t)j];
+          const int used = std::min(num_angles[(size_t)j], opt.max_num_orientations);
+          R.two_orientations += used >= 2;
+          for (int a = 0; a < used; ++a) {
+            const double angle = angles[kMaxAngles * (size_t)j + (size_t)a];
+            float row[4];
+            FeatureRow(key, angle, row);
+            R.keypoints.insert(R.keypoints.end(), row, row + 4);
+            feats.push_back(SiftFeature{j, (int32_t)(q * n + i), angle, std::sin(angle), std::cos(angle)});
+          }
+          counts[q * n + i] += used;
+        }
+      }
+    for (size_t i = 0; i < n; ++i) row0[first + i + 1] = row0[first + i] + (int64_t)(results[first + i].keypoints.size() / 4);
+    PP_REQUIRE(SiftRowsFit(row0[first + n]), "%s: too many descriptors", where);
+    const std::vector<int64_t> block_row = KeptBlockRows(counts, O, n, row0.data() + first);
+    const size_t F = feats.size();
+    std::vector<int32_t> rows;
+    rows.reserve(F);
+    for (size_t blk = 0; blk < O * n; ++blk)
+      for (int64_t c = 0; c < counts[blk]; ++c) rows.push_back((int32_t)(block_row[blk] + c));
+    // ---- the descriptors of the group: one launch into the store
+    if (F > 0) {
+      const size_t filled = (size_t)row0[first], need = (size_t)row0[first + n];
+      if (need > store_rows) PP_TRY(grow_store(b + 1 == plan.num_groups() ? need : std::max(need, 2 * store_rows), filled));
+      {
+        const bool regrow = !h->kept_feats || h->cap_kept < F;
+        const size_t want = std::max<size_t>(F, 2 * h->cap_kept);
+        if (regrow) { if (h->kept_feats) h->blocks.Free(&h->kept_feats); h->cap_kept = 0; PP_TRY(h->blocks.Alloc(&h->kept_feats, want)); h->cap_kept = want; }
+        PP_TRY(GrowBeside(h->blocks, &h->kept_rows, regrow, h->cap_kept));
+        PP_TRY(GrowBeside(h->blocks, &h->kept_window, regrow, h->cap_kept));
+      }
+      std::vector<SiftWaveImage> table(O * n);
+      for (size_t q = 0; q < O; ++q)
+        for (size_t i = 0; i < n; ++i) {
+          const SiftOctave& oc = group.Octave(i, (int)q);
+          table[q * n + i] = SiftWaveImage{group.Pyramid(i) + oc.grad, oc.w, oc.h, std::ldexp(1.0, oc.o)};
+        }
+      PP_TRY(Upload(h->wave_images, table.data(), table.size(), s));
+      PP_TRY(Upload(h->kept_feats, feats.data(), F, s));
+      PP_TRY(Upload(h->kept_rows, rows.data(), F, s));
+      hipLaunchKernelGGL(k_sift_describe_kept, dim3((unsigned)F), dim3(kWave), 0, s, (const SiftFeature*)h->kept_feats, (const Keypoint*)h->keys,
+                         (const SiftWaveImage*)h->wave_images, (const int32_t*)h->kept_rows, g.s_min, g.s_max, (const double*)h->expn, (int)opt.normalization, m->d_desc,
+                         m->d_off, h->kept_window);
+      std::vector<DescriptorWindow> window(F);
+      PP_TRY(Download(window.data(), (const DescriptorWindow*)h->kept_window, F, s));
+      PP_TRY(phases.Close(kDescribe));
+      for (size_t f = 0; f < F; ++f) {
+        HostResult& R = results[first + (size_t)feats[f].image % n];
+        R.windows_cut += window[f].cut; R.descriptors_skipped += !window[f].computed;
+      }
+    }
+    for (size_t i = 0; i < n; ++i) results[first + i].cut = Cut{cuts[i].first_level_to_keep, 0, row0[first + i + 1] - row0[first + i]};
+    PP_TRY(phases.End());
+  }
+  if (!m->d_desc) PP_TRY(grow_store(0, 0));      // no feature in any image: the blocks of an empty handle
+  m->desc_start = row0;
+
+  // ---- the reports: FillReport's counts; the four that follow the features cover the kept ones, nothing else was computed
+  std::memset(batch_report, 0, sizeof(*batch_report));
+  for (size_t i = 0; i < N; ++i) {
+    std::memset(&reports[i], 0, sizeof(reports[i]));
+    FillReport(results[i], g, &reports[i]);
+    reports[i].num_features_found = reports[i].num_features;
+    offsets[i] = row0[i];
+  }
+  offsets[N] = row0[N];
+  batch_report->num_images = num_images;
+  batch_report->num_sub_batches = plan.num_groups();
+  batch_report->num_features = offsets[N];
+  batch_report->workspace_bytes = workspace_used;
+  for (int p = 0; p < 5; ++p) batch_report->phase_ms[p] = options->phase_timings ? phases.ms[p] : 0.0;
+  batch_report->device_ms = phases.timer.ms;
+  batch_report->total_ms = MsSince(t_begin);
+  PP_REQUIRE(capacity >= offsets[N], "%s: capacity %lld for %lld features", where, (long long)capacity, (long long)offsets[N]);
+  for (size_t i = 0; i < N; ++i)
+    if (!results[i].keypoints.empty()) std::memcpy(keypoints + 4 * (size_t)offsets[i], results[i].keypoints.data(), results[i].keypoints.size() * sizeof(float));
+  *matcher = m.release();
+  batch_report->total_ms = MsSince(t_begin);
+  return PP_OK;
+} PP_API_CATCH("pp_sift_extract_to_matcher")
 
 int pp_sift_extract_batch_features(pp_sift_extractor_handle h, int32_t image, float* raw, int32_t* octave_level, double* angles, int64_t capacity,
                                    int64_t* num) try {

@@ -8,7 +8,9 @@
 //   - ExtractOnHost: the whole extraction run serially through the functions of sift_core.hpp - the CPU mirror of sift_extract.hip, with the
 //     descriptor by either route: Descriptor() as the lane-per-feature kernel calls it, or the wavefront scheme of k_sift_describe_wave replayed
 //     with 64 "lanes" in a loop;
-//   - PlanSiftBatches: how pp_sift_extract_batch splits its images into sub-batches under a workspace target.
+//   - PlanSiftBatches: how pp_sift_extract_batch splits its images into sub-batches under a workspace target;
+//   - SelectKeptKeypoints, KeptBlockRows: the cut from the keypoint counts alone and the rows of the kept features in the matcher's store
+//     (pp_sift_extract_to_matcher).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -156,6 +158,44 @@ inline Cut SelectLevels(const std::vector<Level>& levels, int64_t max_num_featur
   }
   for (int i = 0; i < c.first_level_to_keep; ++i) c.first_feature += levels[(size_t)i].size;
   return c;
+}
+
+// K24 - the same cut from the keypoint counts alone.  SelectLevels reads `size` only to count what it keeps; the level it selects depends on
+// num_features, and those are known after refinement - before any orientation or descriptor.  The kept keypoints of an octave are a suffix of its
+// list (the levels of an octave stand in the order of its keypoints), all of them in the octaves above the cut, none in those below.
+struct KeptRange { int64_t first, count; };      // the keypoints [first, first + count) of one octave's list
+struct KeptCut {
+  int32_t first_level_to_keep;
+  int64_t num_keypoints;               // kept, all octaves
+  std::vector<KeptRange> octaves;      // by octave index q = octave - o_min
+};
+
+inline KeptCut SelectKeptKeypoints(const std::vector<Level>& levels, int64_t max_num_features, int o_min, int num_octaves) {
+  KeptCut c{0, 0, std::vector<KeptRange>((size_t)num_octaves, KeptRange{0, 0})};
+  int64_t num_features = 0;
+  for (int i = (int)levels.size() - 1; i >= 0; --i) {
+    num_features += levels[(size_t)i].num_features;
+    if (num_features > max_num_features) { c.first_level_to_keep = i; break; }
+  }
+  for (size_t i = 0; i < levels.size(); ++i) {
+    KeptRange& r = c.octaves[(size_t)(levels[i].octave - o_min)];
+    if ((int)i < c.first_level_to_keep) { r.first += levels[i].num_features; continue; }
+    r.count += levels[i].num_features;
+    c.num_keypoints += levels[i].num_features;
+  }
+  return c;
+}
+
+// Where the kept features of a group of n images go in the matcher's store.  The descriptor launch lists them in blocks, octave by octave and image
+// by image inside an octave: block q * n + i holds counts[q * n + i] features of image i in the reference's order.  Image i owns the rows from
+// row0[i] on and takes its blocks in octave order, so its rows are in the reference's order.  -> the first row of every block.
+inline std::vector<int64_t> KeptBlockRows(const std::vector<int64_t>& counts, size_t num_octaves, size_t n, const int64_t* row0) {
+  std::vector<int64_t> rows(counts.size());
+  for (size_t i = 0; i < n; ++i) {
+    int64_t at = row0[i];
+    for (size_t q = 0; q < num_octaves; ++q) { rows[q * n + i] = at; at += counts[q * n + i]; }
+  }
+  return rows;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 // K17 - SIFT descriptor matching: MatchSiftFeaturesCPUBruteForce (reference src/feature/sift.cc:54-143, 170-203, 957-970) for a list of image pairs, exact.
-// The rule and its integer thresholds are in sift_match_replay.hpp; this file is the device half and the C ABI.
+// The rule and its integer thresholds are in sift_match_replay.hpp, the handle in sift_match_handle.hpp (sift_extract.hip fills one too); this file is
+// the device half and the C ABI.
 //   dist(i, j) = d1[i] . d2[j] over 128 uint8.  The gfx950 i8 MFMA is signed, so a handle keeps d' = d - 128 (the same byte with its top bit flipped) and, per
 //   row, off = 128 * sum(d') + 2^20 = 128 * sum(d) - 2^20:   dist = d1' . d2' + off1 + off2   (128^3 = 2^21 split over the two sides), exact in int32 - the
 //   signed product stays below 2^21.
@@ -21,13 +22,11 @@
 // No atomics, no kernel waits for another workgroup: the output does not depend on the schedule.
 #include <cstring>
 
-#include "device_handle.hpp"
 #include "scan.hpp"
-#include "sift_match_replay.hpp"
+#include "sift_match_handle.hpp"
 
 namespace ppsfm {
 
-constexpr int kSiftRowTile = 128;       // query rows per workgroup: 4 wavefronts x the MFMA's 32
 constexpr int kSiftColTile = 64;        // scanned rows per LDS tile: two MFMA blocks of 32
 constexpr int kSiftLdsStride = 144;     // bytes per staged row: 128 + 16, so that the 32 rows of a fragment read spread over the banks
 constexpr int32_t kSiftPadOff = -(1 << 30);
@@ -218,19 +217,6 @@ __global__ __launch_bounds__(256) void k_sift_offsets(int32_t n, int32_t* __rest
 
 }  // namespace ppsfm
 
-struct pp_sift_impl : ppsfm::DeviceHandle {      // blocks: the descriptors, their offsets and the threshold table
-  int32_t num_images = 0;
-  std::vector<int64_t> desc_start;      // num_images + 1
-  int8_t* d_desc = nullptr;             // total x 128, d - 128
-  int32_t* d_off = nullptr;             // total
-  // the thresholds of the last options used, on the host and on the device
-  bool have_thresholds = false;
-  float key_ratio = 0.f, key_distance = 0.f;
-  ppsfm::SiftThresholds thresholds;
-  int32_t* d_table = nullptr;
-  int32_t Rows(int32_t image) const { return (int32_t)(desc_start[(size_t)image + 1] - desc_start[(size_t)image]); }
-};
-
 using namespace ppsfm;
 
 namespace {
@@ -309,7 +295,7 @@ int pp_sift_create(int32_t num_images, const int64_t* desc_start, const uint8_t*
   PP_REQUIRE(desc_start[0] == 0, "%s: desc_start[0] != 0", where);
   for (int32_t k = 0; k < num_images; ++k) PP_REQUIRE(desc_start[k] <= desc_start[k + 1], "%s: desc_start decreases at image %d", where, k);
   const int64_t total = desc_start[num_images];
-  PP_REQUIRE(total < 0x7FFFFFFFll - kSiftRowTile, "%s: too many descriptors", where);
+  PP_REQUIRE(SiftRowsFit(total), "%s: too many descriptors", where);
   PP_REQUIRE(total == 0 || descriptors, "%s: null descriptors", where);
   PP_TRY(UseDevice(where, device));
   UnderConstruction<pp_sift_impl, pp_sift_destroy> h{new pp_sift_impl()};
@@ -317,12 +303,11 @@ int pp_sift_create(int32_t num_images, const int64_t* desc_start, const uint8_t*
   h->desc_start.assign(desc_start, desc_start + num_images + 1);
   PP_TRY(h->Open(device));
   hipStream_t s = h->stream;
-  uint8_t* d_raw = nullptr;
-  PP_TRY(h->blocks.Put(&d_raw, descriptors, (size_t)total * kSiftDim, s, 16));
-  PP_TRY(h->blocks.Put(&h->d_off, (const int32_t*)nullptr, (size_t)total, s, 1));
+  PP_TRY(AllocSiftStore(h->blocks, total, &h->d_desc, &h->d_off));
+  uint8_t* d_raw = reinterpret_cast<uint8_t*>(h->d_desc);      // (k_sift_prepare turns the bytes into d - 128 in place)
+  PP_TRY(Upload(d_raw, descriptors, (size_t)total * kSiftDim, s));
   if (total > 0) hipLaunchKernelGGL(k_sift_prepare, dim3(CeilDiv(total, 256)), dim3(256), 0, s, total, d_raw, h->d_off);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { SetLastError("%s: upload failed", where); return PP_ERR_HIP; }
-  h->d_desc = reinterpret_cast<int8_t*>(d_raw);
   *out = h.release();
   return PP_OK;
 } PP_API_CATCH("pp_sift_create")
@@ -349,6 +334,22 @@ int pp_sift_top2(pp_sift_handle h, int32_t image1, int32_t image2, int32_t* best
   PP_HIP_TRY(hipStreamSynchronize(s));
   return PP_OK;
 } PP_API_CATCH("pp_sift_top2")
+
+int pp_sift_get_descriptors(pp_sift_handle h, int32_t image, uint8_t* descriptors, int64_t capacity, int64_t* num) try {
+  const char* where = "pp_sift_get_descriptors";
+  PP_REQUIRE(h && num, "%s: null argument", where);
+  PP_REQUIRE(image >= 0 && image < h->num_images, "%s: image %d of %d", where, image, h->num_images);
+  const int64_t rows = h->Rows(image);
+  *num = rows;
+  PP_REQUIRE(capacity >= rows && (descriptors || rows == 0), "%s: capacity %lld for %lld descriptors", where, (long long)capacity, (long long)rows);
+  if (rows == 0) return PP_OK;
+  PP_HIP_TRY(hipSetDevice(h->device));
+  const size_t count = (size_t)rows * kSiftDim;
+  PP_TRY(Download(descriptors, reinterpret_cast<const uint8_t*>(h->d_desc) + (size_t)h->desc_start[(size_t)image] * kSiftDim, count, h->stream));
+  PP_HIP_TRY(hipStreamSynchronize(h->stream));
+  for (size_t i = 0; i < count; ++i) descriptors[i] ^= 0x80;      // the store holds d - 128
+  return PP_OK;
+} PP_API_CATCH("pp_sift_get_descriptors")
 
 int pp_sift_match_pairs(pp_sift_handle h, const pp_sift_match_options* options, int64_t num_pairs, const int32_t* pairs, pp_sift_match_report* report,
                         int64_t* match_start, int32_t* matches, int64_t capacity) try {

@@ -873,7 +873,7 @@ def sift_match_thresholds(options=None):
 
 class SiftMatcher(_Handle):
     """pp_sift_handle: the descriptors ([N_k, 128] uint8 each) of a list of images on the device; match_pairs() is MatchSiftFeaturesCPUBruteForce for a
-    list of pairs of positions in that list, top2() the one-way scan underneath it."""
+    list of pairs of positions in that list, top2() the one-way scan underneath it.  from_handle() wraps a handle that was filled on the device."""
     _destroy = "pp_sift_destroy"
 
     def __init__(self, descriptors_by_image, device=0):
@@ -892,6 +892,24 @@ class SiftMatcher(_Handle):
         flat = np.ascontiguousarray(flat, dtype=np.uint8)
         check(_capi.lib().pp_sift_create(self.num_images, ptr(start, C.POINTER(C.c_int64)), ptr(flat, _capi.c_u8p) if flat.size else None, int(device),
                                          C.byref(self._h)))
+
+    @classmethod
+    def from_handle(cls, handle, offsets):
+        """a pp_sift_handle this class did not create (SiftExtractor.extract_to_matcher), owned from here on; offsets [num_images + 1]: image k holds
+        the rows offsets[k] .. offsets[k + 1]"""
+        self = cls.__new__(cls)
+        _Handle.__init__(self)
+        self._h = handle
+        self.num_features = [int(b - a) for a, b in zip(offsets[:-1], offsets[1:])]
+        self.num_images = len(self.num_features)
+        return self
+
+    def descriptors(self, image):
+        """-> [N, 128] uint8: the descriptor rows of one image as they were given, or as extract_to_matcher made them (pp_sift_get_descriptors)"""
+        n = self.num_features[image]
+        out, num = np.zeros((max(n, 1), 128), dtype=np.uint8), C.c_int64()
+        check(_capi.lib().pp_sift_get_descriptors(self._h, int(image), ptr(out, _capi.c_u8p), n, C.byref(num)))
+        return out[:num.value]
 
     def capacity(self, pairs, cross_check=True):
         """the number of matches that always suffices for these pairs"""
@@ -1022,7 +1040,8 @@ def sift_extract_options(**kw):
 class SiftExtractor(_Handle):
     """pp_sift_extractor_handle (K21): extract() is ExtractSiftFeaturesCPU for one grey image; the handle's workspace grows to the largest image seen
     and keeps the pyramid of the last extraction for stage(), candidates() and features().  extract_batch() is the same for a sequence of images in
-    one call (K23); batch_features(i) reads its results."""
+    one call (K23); batch_features(i) reads its results.  extract_to_matcher() is extract_batch() with a SiftMatcher as the way out (K24): the
+    descriptors of the kept features are written on the device where the matcher reads them."""
     _destroy = "pp_sift_extractor_destroy"
 
     def __init__(self, device=0):
@@ -1085,24 +1104,35 @@ class SiftExtractor(_Handle):
         check(_capi.lib().pp_sift_extract_features(self._h, ptr(raw, C.POINTER(C.c_float)), ptr(ol, _capi.c_ip), dp(ang), n, C.byref(num)))
         return raw[:n], ol[:n], ang[:n]
 
-    def extract_batch(self, images, options=None, want_descriptors=True, workspace_bytes=0, capacity=None):
-        """pp_sift_extract_batch: images, a sequence of [H, W] uint8 arrays of any sizes -> [(keypoints, descriptors or None, report)] per image, each
-        what extract() gives for that image alone; last_batch_report is the batch's.  The images go through the octaves together and their descriptors
-        through one launch per octave.  workspace_bytes: the target for the pyramids held at once (0: 8 GiB); more images than fit run in consecutive
-        groups, with the same result.  capacity None: the call is repeated with the reported need when the first guess was too small.  Afterwards
-        stage(), candidates() and features() raise until the next extract(); batch_features(i) reads the batch."""
+    @staticmethod
+    def _batch_table(images):
+        """the images of a batch call as contiguous arrays (kept alive by the caller) and the pp_sift_batch_image table over them"""
         ims = []
         for image in images:
             im = np.asarray(image)
             if im.dtype != np.uint8 or im.ndim != 2:
                 raise ValueError("every image is an [H, W] uint8 array")
             ims.append(np.ascontiguousarray(im))
-        n = len(ims)
-        table = (_capi.SiftBatchImage * max(n, 1))()
+        table = (_capi.SiftBatchImage * max(len(ims), 1))()
         for i, im in enumerate(ims):
             table[i].width, table[i].height, table[i].grey = int(im.shape[1]), int(im.shape[0]), ptr(im, _capi.c_u8p)
+        return ims, table
+
+    @staticmethod
+    def _batch_guess(n, o):
+        """the first capacity of a batch call that was given none"""
+        return min(n * min(2 * int(o.max_num_features), 1 << 16), 1 << 22)
+
+    def extract_batch(self, images, options=None, want_descriptors=True, workspace_bytes=0, capacity=None):
+        """pp_sift_extract_batch: images, a sequence of [H, W] uint8 arrays of any sizes -> [(keypoints, descriptors or None, report)] per image, each
+        what extract() gives for that image alone; last_batch_report is the batch's.  The images go through the octaves together and their descriptors
+        through one launch per octave.  workspace_bytes: the target for the pyramids held at once (0: 8 GiB); more images than fit run in consecutive
+        groups, with the same result.  capacity None: the call is repeated with the reported need when the first guess was too small.  Afterwards
+        stage(), candidates() and features() raise until the next extract(); batch_features(i) reads the batch."""
+        ims, table = self._batch_table(images)
+        n = len(ims)
         o = options or sift_extract_options()
-        guess = min(n * min(2 * int(o.max_num_features), 1 << 16), 1 << 22) if capacity is None else int(capacity)
+        guess = self._batch_guess(n, o) if capacity is None else int(capacity)
         for cap in (guess, None):
             brep, reps, offsets = _capi.SiftBatchReport(), (_capi.SiftExtractReport * max(n, 1))(), np.full(n + 1, -1, dtype=np.int64)
             if cap is None:
@@ -1121,6 +1151,31 @@ class SiftExtractor(_Handle):
             a, b = int(offsets[i]), int(offsets[i + 1])
             out.append((kp[a:b].copy(), None if desc is None else desc[a:b].copy(), reps[i]))
         return out
+
+    def extract_to_matcher(self, images, options=None, workspace_bytes=0, capacity=None):
+        """pp_sift_extract_to_matcher: extract_batch for features that go to the matcher -> (keypoints per image ([N_i, 4] float32 each), reports per
+        image, the batch report, a SiftMatcher on this extractor's device whose image i holds the N_i descriptors of images[i]).  Keypoints and
+        descriptors (SiftMatcher.descriptors(i)) are extract_batch's; only the kept features get an orientation and a descriptor, and no descriptor
+        comes to the host.  The four report counts that follow the features cover the kept ones only.  The caller closes the matcher.  Afterwards
+        stage(), candidates(), features() and batch_features() raise until the next extract() or extract_batch()."""
+        ims, table = self._batch_table(images)
+        n = len(ims)
+        o = options or sift_extract_options()
+        guess = self._batch_guess(n, o) if capacity is None else int(capacity)
+        for cap in (guess, None):
+            brep, reps, offsets = _capi.SiftBatchReport(), (_capi.SiftExtractReport * max(n, 1))(), np.full(n + 1, -1, dtype=np.int64)
+            if cap is None:
+                cap = int(self.last_batch_report.num_features)
+            kp, handle = np.zeros((max(cap, 1), 4), dtype=np.float32), C.c_void_p()
+            rc = _capi.lib().pp_sift_extract_to_matcher(self._h, C.byref(o), n, table, int(workspace_bytes), C.byref(brep), reps, cap,
+                                                        ptr(kp, C.POINTER(C.c_float)), ptr(offsets, C.POINTER(C.c_int64)), C.byref(handle))
+            if rc == 0 or capacity is not None or offsets[n] <= cap:      # (offsets[n] stays -1 where the arguments were refused)
+                break
+            self.last_batch_report = brep
+        check(rc)
+        self.last_batch_report = brep
+        matcher = SiftMatcher.from_handle(handle, offsets)
+        return [kp[int(offsets[i]):int(offsets[i + 1])].copy() for i in range(n)], [reps[i] for i in range(n)], brep, matcher
 
     def batch_features(self, image):
         """features() for image `image` of the last extract_batch"""

@@ -489,17 +489,27 @@ def ExtractSiftFeaturesBatch(images_uint8, options=None, device=0, extractor=Non
     return [([FeatureKeypoint(r[0], r[1], r[2], r[3]) for r in kp], desc) for kp, desc, _ in results]
 
 
-def extract_features_to_lines(images, cameras, bitmaps, options=None, aligned_line_ratio=DEFAULT_ALIGNED_LINE_RATIO, seed=0, device=0, batched=True):
+def extract_features_to_lines(images, cameras, bitmaps, options=None, aligned_line_ratio=DEFAULT_ALIGNED_LINE_RATIO, seed=0, device=0, batched=True,
+                              to_matcher=False):
     """Image arrays to what the matcher and the graph builder take.  images: bundle_adjustment.Image objects; cameras as for generate_line_features;
     bitmaps: {image_id: [H, W] uint8}.  ExtractSiftFeaturesBatch over the images (batched=False: ExtractSiftFeatures image by image - the same arrays),
     then generate_line_features_on_device over all of them (it fills image.lines).
     -> dict(keypoints {image_id: [N, 4] float32}, descriptors {image_id: [N, 128] uint8}, num_lines {image_id: N}, lines: the line report).
-    Line index = keypoint index = descriptor row."""
+    Line index = keypoint index = descriptor row.
+    to_matcher: the descriptors stay on the device (SiftExtractor.extract_to_matcher) and the dict holds matcher=, a feature_matching.FeatureMatcher
+    over the images' ids under the default SiftMatchingOptions (the caller closes it), in place of descriptors=."""
     from .device import SiftExtractor
     ex = SiftExtractor(device=device)
-    keypoints, descriptors = {}, {}
+    keypoints, descriptors, sift_matcher = {}, {}, None
     try:
-        if batched and len(images) > 0:
+        if to_matcher:
+            options = options or SiftExtractionOptions()
+            if not options.Check():
+                raise ValueError("SiftExtractionOptions.Check() failed")
+            found, _, _, sift_matcher = ex.extract_to_matcher([bitmaps[im.image_id] for im in images], options.device_options())
+            for im, kp in zip(images, found):
+                keypoints[im.image_id] = kp
+        elif batched and len(images) > 0:
             found = ExtractSiftFeaturesBatch([bitmaps[im.image_id] for im in images], options, extractor=ex, as_arrays=True)
             for im, (kp, desc) in zip(images, found):
                 keypoints[im.image_id], descriptors[im.image_id] = kp, desc
@@ -508,5 +518,14 @@ def extract_features_to_lines(images, cameras, bitmaps, options=None, aligned_li
                 keypoints[im.image_id], descriptors[im.image_id] = ExtractSiftFeatures(bitmaps[im.image_id], options, extractor=ex, as_arrays=True)
     finally:
         ex.close()
-    rep = generate_line_features_on_device(images, cameras, keypoints, aligned_line_ratio=aligned_line_ratio, seed=seed, device=device)
-    return dict(keypoints=keypoints, descriptors=descriptors, num_lines={k: len(v) for k, v in keypoints.items()}, lines=rep)
+    if not to_matcher:
+        rep = generate_line_features_on_device(images, cameras, keypoints, aligned_line_ratio=aligned_line_ratio, seed=seed, device=device)
+        return dict(keypoints=keypoints, descriptors=descriptors, num_lines={k: len(v) for k, v in keypoints.items()}, lines=rep)
+    from .feature_matching import FeatureMatcher, SiftMatchingOptions
+    try:
+        rep = generate_line_features_on_device(images, cameras, keypoints, aligned_line_ratio=aligned_line_ratio, seed=seed, device=device)
+        matcher = FeatureMatcher.from_matcher(SiftMatchingOptions(), [im.image_id for im in images], sift_matcher, device=device)
+    except Exception:
+        sift_matcher.close()
+        raise
+    return dict(keypoints=keypoints, matcher=matcher, num_lines={k: len(v) for k, v in keypoints.items()}, lines=rep)

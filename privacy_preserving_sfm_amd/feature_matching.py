@@ -329,6 +329,25 @@ class FeatureMatcher:
         self._matcher = SiftMatcher([descriptors_by_image_id[i] for i in self.image_ids_], device=device)
         self.last_report = None
 
+    @classmethod
+    def from_matcher(cls, options, image_ids, sift_matcher, device=0, workspace_bytes=0):
+        """A FeatureMatcher over a device.SiftMatcher that exists already (SiftExtractor.extract_to_matcher): image_ids[k] is the id of the matcher's
+        image k.  The matcher is owned from here on: close() closes it.  device: the matcher's, for the pair selections that run there."""
+        if not options.Check():
+            raise ValueError("SiftMatchingOptions.Check() failed")
+        image_ids = list(image_ids)
+        if len(image_ids) != sift_matcher.num_images or len(set(image_ids)) != len(image_ids):
+            raise ValueError("one distinct image id per image of the matcher")
+        self = cls.__new__(cls)
+        self.options_ = options
+        self.image_ids_ = sorted(image_ids)
+        self._index = {i: k for k, i in enumerate(image_ids)}
+        self._workspace_bytes = workspace_bytes
+        self._device = device
+        self._matcher = sift_matcher
+        self.last_report = None
+        return self
+
     def close(self):
         self._matcher.close()
 
